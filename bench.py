@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: random-restart IK solves/sec (Panda 7-DoF, tol_f = 1e-6).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A *step* is one pass of the hot path over one batch: R = 65 536 restarts (BASELINE.json config 2: Panda
 7-DoF, SolutionMode::Speed) of one synthetic reachable target, every restart run to termination (no early
@@ -10,8 +10,14 @@ the timed region.  The K timed steps of a run are the K targets of ONE launch of
 its own target, seed and output columns; at this size the lane-per-restart form, ik_lane64.hpp): the
 persistent waves pull (step, restart) work items from one queue, so a run pays one fill and one drain of the
 chip -- `config.workload` says so, and `config.other_configs.config2_single_launch` is the ISOLATED launch of
-one step's 65 536 restarts.  The timed run is repeated until ~2 s of GPU work are inside the timed regions
-(--reps overrides); `value` / `ms_per_step` are the MEDIAN repetition's.
+one step's 65 536 restarts.  A plain run times its K steps once: `value` is their restarts/s, `ms_per_step` the
+milliseconds one of them took.  With --full the timed run is repeated until ~2 s of GPU work are inside the timed
+regions, and --reps sets any count; `value` / `ms_per_step` are then the MEDIAN repetition's.
+
+A plain run does only what the headline figure needs: set-up, the W warm-up steps, the K timed steps, the outputs
+(--dump-outputs DIR: the last timed step's winner x / f / index and every restart's x, f, status and evals, as
+DIR/<name>.npy in float64; the inputs are seeded, so two builds can be compared output for output) and the line.
+--full adds the legs below marked so: the CPU baseline, config.other_configs and the collective latencies.
 
 Multi-GPU.  `python bench.py --gpus N` with no launcher around it starts the N ranks itself: it
 re-executes under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
@@ -20,7 +26,7 @@ re-executes under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
 line's "n_gpus" is the number of ranks that actually joined the process group, and config carries
 the world size, the backend string, RCCL's version, every rank's device (index, name, UUID: two ranks on
 one physical GPU are refused unless OPTIK_BENCH_ONE_DEVICE=1) and the measured latency of each collective;
-a --gpus that disagrees with WORLD_SIZE is refused.  With N > 1 the same invocation also times BASELINE
+a --gpus that disagrees with WORLD_SIZE is refused.  With N > 1 and --full the same invocation also times BASELINE
 config 4 (4 M restarts, Quality, strong scaling) and config 5 (4096 targets x 256, cut per rank) in short
 runs: `config.other_configs`, so that one scaling sweep yields all three curves.  `--inprocess` drives the
 other multi-GPU form instead: ONE process, N devices behind the C ABI (optik_robot_set_devices: a host thread
@@ -46,12 +52,13 @@ The JSON line carries:
                 (HBM is not what binds this path): `frac_algorithmic` prices the oracle-counted f64
                 operations of a restart (oracle/optik_oracle_flops.cpp) at this line's rate against the
                 no-FMA ceiling, the PMC instruction counts sit beside it
-  cpu_baseline  the CPU oracle (a port of the reference algorithm, NOT the reference binary) timed on this
-                host's cores (1 thread = BASELINE config 1, half, all) on a bounded sample; `single_ik_ms` (one ik()
+  cpu_baseline  (--full; null otherwise) the CPU oracle (a port of the reference algorithm, NOT the reference binary)
+                timed on this host's cores (1 thread = BASELINE config 1, half, all) on a bounded sample; `single_ik_ms` (one ik()
                 call: 1 thread, and all cores under the reference's find_any rule) and `config5_ik_calls_per_s` on the
                 targets of the GPU legs of the same names.  Runs BETWEEN the GPU legs (headline first, other configs last)
-  config.other_configs   (N = 1, the default command) BASELINE configs 3, 4's one-GPU shard and 5, the isolated
+  config.other_configs   (--full, N = 1; null otherwise) BASELINE configs 3, 4's one-GPU shard and 5, the isolated
                 config-2 launch and a single ik() through the C ABI, each in a short run of its own
+  config.collective_us   (--full, a process group; null otherwise) microseconds per collective of a step's exchange
 """
 import argparse
 import json
@@ -290,6 +297,7 @@ def inprocess_main(args):
     cfg = SolverConfig(solution_mode="quality", max_time=0.0, max_restarts=R * G, tol_f=1e-6)
 
     parts_used = []  # devices every timed call was actually cut over (optik_robot_last_parts)
+    last = {}  # what the latest call returned
 
     def run_steps(first, count):
         out = []
@@ -297,6 +305,7 @@ def inprocess_main(args):
             r = robot.ik(cfg, targets[k], x0[k], return_index=True)
             out.append(-1 if r is None else int(r[2]))
             parts_used.append(robot.last_parts())
+            last["r"] = r
         return out
 
     if W:
@@ -304,7 +313,7 @@ def inprocess_main(args):
     for d in set(devices):
         torch.cuda.synchronize(d)
     rep_elapsed, winners = [], None
-    for _rep in range(max(1, args.reps or 5)):
+    for _rep in range(max(1, default_reps(args) or 5)):
         t0 = time.perf_counter()
         w_rep = run_steps(W, K)  # Robot.ik blocks until the G parts are done and reduced
         rep_elapsed.append(time.perf_counter() - t0)
@@ -312,6 +321,10 @@ def inprocess_main(args):
             raise SystemExit("winners differ between repetitions of the same steps")
         winners = w_rep
     elapsed = sorted(rep_elapsed)[len(rep_elapsed) // 2]
+    if args.dump_outputs:
+        r = last["r"]  # Robot.ik's (x, f, index) of the last timed step, None: no solution
+        dump_outputs(args.dump_outputs, {"win_x": [r[0] if r else [0.0] * n], "win_f": [r[1] if r else 0.0],
+                                         "win_idx": [r[2] if r else -1]})
     total = float(R) * G * K
     out_bytes = 8 * n + 8 + 8 + 4 + 4
     parts = sorted(set(parts_used[-K:]))
@@ -413,6 +426,7 @@ def run_workload(ctx, robot_name, mode, scaling, T, R, K, W, reps, find_any=Fals
     # (one set of output buffers per run length: the timed run of K steps and the warm-up run of W)
     kbufs = {c: hc.alloc_ik_buffers(c, cols) for c in {K, W} if c} if pooled else {}
     win_xf = {}  # the global winners' x and f of the last run (every rank holds them, as Robot::ik returns them)
+    last_step = {}  # the solver outputs of the latest step of a --targets run (references only: no work is added)
 
     def exchange(rec):
         """The cross-rank half of a step (lib.rs:397-413 over the ranks): two 8-byte min-all-reduces pick the
@@ -434,6 +448,7 @@ def run_workload(ctx, robot_name, mode, scaling, T, R, K, W, reps, find_any=Fals
         win = torch.full((tg.shape[0],), I64_MAX, dtype=torch.int64, device=dev)
         live = torch.arange(tg.shape[0], device=dev)
         b, rnd = begin, 128
+        rounds = []
         while b < end and live.numel():
             e = min(end, b + rnd)
             out = hc.ik_batch(cfg, tg[live].contiguous(), xs[live].contiguous(), b, e,
@@ -441,8 +456,10 @@ def run_workload(ctx, robot_name, mode, scaling, T, R, K, W, reps, find_any=Fals
                               | (nat.IK_FIND_ANY if find_any else 0), per_restart=False)
             solved = out["win_idx"] >= 0
             win[live[solved]] = out["win_idx"][solved]
+            rounds.append((live, solved, out))
             live = live[~solved]
             b, rnd = e, rnd * 4
+        last_step["rounds"] = rounds
         return win
 
     def run_steps(first, count):
@@ -459,6 +476,7 @@ def run_workload(ctx, robot_name, mode, scaling, T, R, K, W, reps, find_any=Fals
                 winners.append(batch_rounds(targets[i:i + T_loc], x0[i:i + T_loc]))
                 continue
             out = hc.ik_batch(cfg, targets[i:i + T_loc], x0[i:i + T_loc], begin, end, per_restart=False)
+            last_step["rounds"] = [(None, None, out)]
             winners.append(select_winner(out, mode, False).clone())
         return torch.stack(winners)
 
@@ -499,7 +517,61 @@ def run_workload(ctx, robot_name, mode, scaling, T, R, K, W, reps, find_any=Fals
         res["mean_evals"] = float(last["evals"].double().mean().item())
     else:
         res["n_success"], res["mean_evals"] = None, None
+    # what the last timed step handed its caller (--dump-outputs): the winner of each of the step's targets -- x and f,
+    # zero where none was found, index -1 -- and with one launch per run every restart's x, f, status and evals
+    win_idx = winners[-1]
+    found = (win_idx >= 0) & (win_idx < I64_MAX)
+    if pooled:
+        kb, sl = kbufs[K], slice((K - 1) * cols, K * cols)
+        wx, wf = (win_xf["x"], win_xf["f"]) if win_xf else (kb["win_x"], kb["win_f"])
+        outs = {"x": kb["x"][:, sl].T, "f": kb["f"][sl], "status": kb["status"][sl], "evals": kb["evals"][sl],
+                "restart_index": torch.arange(begin, end, device=dev), "win_x": wx[K - 1:K], "win_f": wf[K - 1:K]}
+    else:
+        wx = torch.zeros((T_loc, n), dtype=torch.float64, device=dev)
+        wf = torch.zeros(T_loc, dtype=torch.float64, device=dev)
+        for live, solved, out in last_step["rounds"]:
+            if live is None:  # (Quality: one launch over the step's targets)
+                wx, wf = out["win_x"], out["win_f"]
+            else:
+                wx[live[solved]] = out["win_x"][solved]
+                wf[live[solved]] = out["win_f"][solved]
+        outs = {"win_x": wx, "win_f": wf}
+    outs["win_x"] = torch.where(found[:, None], outs["win_x"], torch.zeros_like(outs["win_x"]))
+    outs["win_f"] = torch.where(found, outs["win_f"], torch.zeros_like(outs["win_f"]))
+    outs["win_idx"] = torch.where(found, win_idx, torch.full_like(win_idx, -1))
+    res["last_outputs"] = outs
     return res
+
+
+DUMP_BUDGET_BYTES = 63_000_000  # (64 MB in all, the .npy headers included)
+PER_RESTART = ("x", "f", "status", "evals", "restart_index")  # arrays with one row per restart of the step
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as <out_dir>/<name>.npy in float64 (int32 / int64 values below 2^53 are exact).
+    Per-restart arrays that would take the dump past its budget are cut to the same seeded sample of restarts
+    (restart_index.npy says which)."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: np.ascontiguousarray(v.cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float64)
+            for k, v in arrays.items()}
+    rowwise = [k for k in PER_RESTART if k in host]
+    if rowwise:
+        rows = host["restart_index"].shape[0]
+        row_bytes = sum(host[k].nbytes for k in rowwise) // max(rows, 1)
+        keep = (DUMP_BUDGET_BYTES - sum(v.nbytes for k, v in host.items() if k not in rowwise)) // max(row_bytes, 1)
+        if rows > keep:
+            pick = np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
+            for k in rowwise:
+                host[k] = np.ascontiguousarray(host[k][pick])
+    for k, v in host.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), v)
+
+
+def default_reps(args):
+    """A plain run times its K steps once; --full repeats them until ~2 s are inside the timed regions (None)."""
+    if args.reps is not None:
+        return args.reps
+    return None if args.full else 1
 
 
 def user_inputs(ctx):
@@ -663,7 +735,14 @@ def main():
                          "Quality, restart budget R x N) instead of one process per GPU")
     ap.add_argument("--reps", type=int, default=None,
                     help="repetitions of the K-step timed run: value / ms_per_step are the MEDIAN repetition's, "
-                         "config.value_reps lists all of them; default: as many as put ~2 s inside the timed regions (>= 5)")
+                         "config.value_reps lists all of them; default: 1 (the K timed steps, once), with --full as many "
+                         "as put ~2 s inside the timed regions (>= 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the CPU baseline, config.other_configs, the latency of "
+                         "each collective, the ~2 s repetition of the timed run (a plain run only times its K steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float64; rank 0's restarts; at most 64 MB, a fixed seeded sample of the restarts beyond that)")
     ap.add_argument("--steps", type=int, default=48,
                     help="timed steps of a run: the targets of ONE launch of the solve kernel")
     ap.add_argument("--warmup", type=int, default=3)
@@ -766,15 +845,18 @@ def main():
 
     ctx = Ctx(dev, rank, world, distributed, dist, backend_name)
     R, K, W, T, mode = args.restarts, args.steps, args.warmup, args.targets, args.mode
-    primary = run_workload(ctx, args.robot, mode, args.scaling, T, R, K, W, args.reps, args.find_any, min_timed_s=2.0)
-    # the other workloads of the same invocation (every rank takes part in the multi-rank ones)
+    primary = run_workload(ctx, args.robot, mode, args.scaling, T, R, K, W, default_reps(args), args.find_any,
+                           min_timed_s=2.0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, primary["last_outputs"])
+    # the other workloads of the same invocation (--full; every rank takes part in the multi-rank ones)
     headline = args.robot == "panda" and not T and mode == "speed" and args.scaling == "weak" and R == 65536
-    want_others = not args.no_other_configs and headline
+    want_others = args.full and not args.no_other_configs and headline
     # Order of the legs at N = 1: GPU (the headline above), CPU (the oracle baseline), GPU (the other configurations) -- the
     # driver's 5-s GPU-busy sampler then meets GPU work at both ends of the run instead of ~11 s of CPU work at its end.
     user = None
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not T:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not T:
         if want_others and not args.force_distributed:
             try:
                 user = user_inputs(ctx)
@@ -797,7 +879,7 @@ def main():
                 others = other_configs_one_gpu(ctx, args, primary, user or user_inputs(ctx))
         except Exception as e:  # noqa: BLE001
             others = {"error": f"{type(e).__name__}: {e}"[:300]}
-    coll_us = collective_latency(ctx)
+    coll_us = collective_latency(ctx) if args.full else None
 
     if rank == 0:
         n, hc, robot = primary["n"], primary["hc"], primary["robot"]

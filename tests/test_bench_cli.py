@@ -69,3 +69,42 @@ def test_ranks_sharing_a_gpu_are_refused():
     with pytest.raises(SystemExit, match="share a physical GPU"):
         bench.check_distinct_devices(shared, False)
     assert bench.check_distinct_devices(shared, True) is None  # OPTIK_BENCH_ONE_DEVICE=1: the one-GPU test box
+
+
+def test_a_plain_run_times_its_steps_once():
+    """`--steps K` is the number of timed steps of a plain run; --full keeps the ~2 s repetition, --reps sets any count."""
+    import argparse
+    import bench
+    assert bench.default_reps(argparse.Namespace(reps=None, full=False)) == 1
+    assert bench.default_reps(argparse.Namespace(reps=None, full=True)) is None
+    assert bench.default_reps(argparse.Namespace(reps=7, full=False)) == 7
+
+
+def test_dump_outputs_stays_within_its_budget(tmp_path):
+    """--dump-outputs: float64 .npy files, at most 64 MB in all; per-restart arrays beyond the budget are cut to the same
+    seeded sample of rows on every run, restart_index.npy naming them."""
+    import numpy as np
+    import bench
+    rows, n = 1 << 20, 7
+    rng = np.random.default_rng(1)
+    arrays = {"x": rng.standard_normal((rows, n)), "f": rng.standard_normal(rows),
+              "status": rng.integers(-5, 5, rows).astype(np.int32), "evals": rng.integers(0, 99, rows).astype(np.int32),
+              "restart_index": np.arange(1000, 1000 + rows, dtype=np.int64),
+              "win_x": np.ones((1, n)), "win_f": np.zeros(1), "win_idx": np.array([1234], dtype=np.int64)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    total = 0
+    for name in arrays:
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, b), name
+        total += os.path.getsize(tmp_path / "a" / f"{name}.npy")
+    assert total <= 64_000_000
+    idx = np.load(tmp_path / "a" / "restart_index.npy").astype(np.int64)
+    assert 0 < len(idx) < rows and np.all(np.diff(idx) > 0)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "x.npy"), arrays["x"][idx - 1000])
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "status.npy"), arrays["status"][idx - 1000])
+    assert np.load(tmp_path / "a" / "win_idx.npy").tolist() == [1234.0]
+    # a dump that fits is written whole
+    small = {k: (v[:4096] if k in bench.PER_RESTART else v) for k, v in arrays.items()}
+    bench.dump_outputs(str(tmp_path / "c"), small)
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / "x.npy"), arrays["x"][:4096])

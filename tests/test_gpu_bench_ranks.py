@@ -92,7 +92,7 @@ def test_config5_targets_sharded_two_ranks():
 def test_plain_gpus_flag_spawns_the_ranks_itself():
     """`python bench.py --gpus 2` with no launcher around it must run TWO ranks (it re-executes under
     torch.distributed.run) and say so: n_gpus == 2, both ranks listed, the 1-rank winners."""
-    common = ["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--reps", "2"]
+    common = ["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--reps", "2", "--full"]
     one = subprocess.run([sys.executable, "bench.py", "--restarts", "4096", *common], cwd=ROOT,
                          capture_output=True, text=True, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
@@ -117,12 +117,12 @@ def test_plain_gpus_flag_spawns_the_ranks_itself():
 
 @pytest.mark.gpu
 def test_headline_command_on_two_ranks_also_times_configs_4_and_5():
-    """The driver's scaling sweep runs ONE command per N: with N > 1 the headline line carries config 4 (Quality, strong)
-    and config 5 (targets cut per rank) as well -- here two ranks sharing the box's GPU over gloo."""
+    """The driver's scaling sweep runs ONE command per N: with N > 1 and --full the headline line carries config 4 (Quality,
+    strong) and config 5 (targets cut per rank) as well -- here two ranks sharing the box's GPU over gloo."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     env.update(OPTIK_BENCH_BACKEND="gloo", OPTIK_BENCH_ONE_DEVICE="1")
     two = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--reps", "2",
-                          "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                          "--no-cpu-baseline", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert two.returncode == 0, two.stderr[-3000:]
     b = _line(two.stdout)
     oc = b["config"]["other_configs"]
@@ -134,14 +134,14 @@ def test_headline_command_on_two_ranks_also_times_configs_4_and_5():
 
 @pytest.mark.gpu
 def test_headline_command_on_eight_ranks_gives_a_well_formed_line():
-    """The width the driver's scaling sweep ends at: `bench.py --gpus 8` (two steps), eight ranks sharing the test box's
-    GPU over gloo.  The line must be well formed: world 8, eight distinct processes, the eight restart ranges of the
+    """The width the driver's scaling sweep ends at: `bench.py --gpus 8 --full` (two steps), eight ranks sharing the test
+    box's GPU over gloo.  The line must be well formed: world 8, eight distinct processes, the eight restart ranges of the
     weak-scaling headline, config 4 cut into 524 288 restarts per rank and config 5 into 512 targets per rank
     (VERDICT r5 item 6)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     env.update(OPTIK_BENCH_BACKEND="gloo", OPTIK_BENCH_ONE_DEVICE="1")
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "8", "--steps", "2", "--warmup", "1", "--reps", "1",
-                        "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
+                        "--no-cpu-baseline", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     b = _line(r.stdout)
     assert b["n_gpus"] == 8 and b["config"]["world"] == 8 and b["scaling"] == "weak" and b["steps"] == 2
