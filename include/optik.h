@@ -116,6 +116,15 @@ int32_t optik_robot_last_parts(const optik_robot *robot);
 int optik_robot_diff_ik_ex(const optik_robot *robot, const double *x0, const double *V_WE6,
                            const double *v_max, const double *ee_offset16, double *alpha_out,
                            double *v_out);
+/* Many diff_ik calls at once (extension): row b returns what optik_robot_diff_ik_ex(robot, x0[b], V[b], v_max[b],
+ * ee_offset16) returns, bit for bit.  Host buffers, row-major: x0 [B][n], V [B][6], v_max [B][n] ->
+ * alpha_out [B], v_out [B][n], status_out [B] (0 solved, 1 no solution: alpha and v zero); any output may be
+ * NULL.  One kernel launch per 262 144 rows on the robot's first device (staged through pinned memory kept
+ * with the robot).  rc 0, or -1 with the single call's message: null argument, more than 8 joint positions,
+ * prismatic joints. */
+int optik_robot_diff_ik_batch(const optik_robot *robot, int64_t B, const double *x0, const double *V_WE6,
+                              const double *v_max, const double *ee_offset16, double *alpha_out,
+                              double *v_out, int32_t *status_out);
 int optik_robot_fk_ex(const optik_robot *robot, const double *x, const double *ee_offset16,
                       double *pose16_out);
 int optik_robot_joint_jacobian_ex(const optik_robot *robot, const double *x,

@@ -117,6 +117,18 @@ int optik_hip_eval_batch(const optik_hip_chain *chain, const optik_solver_config
 int optik_hip_fk_batch(const optik_hip_chain *chain, const double *ee_offset7, const double *d_q,
                        int64_t B, double *d_pose, double *d_jac, void *stream);
 
+/* Robot::diff_ik (lib.rs:123-239) for B configurations, each row exactly as optik_robot_diff_ik_ex solves it
+ * (the same FK / Jacobian device code and the same LP source, csrc/diff_ik_lp.hpp: the same bits).
+ * d_q [n][B]; d_V [6][ld_V] with ld_V >= B, or ld_V = 0 for one twist d_V[6] shared by every row;
+ * d_vmax [n][ld_vmax] likewise (0: one limit vector d_vmax[n]) -> d_alpha [B], d_v [n][B], d_status [B]
+ * (0 solved; 1 no solution -- some v_max_i < 0 or NaN -- with alpha and v zero).  ee_offset7 may be NULL.
+ * One thread per row, no workspace, no allocation.  Refused with OPTIK_HIP_EUNSUPPORTED, also when B = 0 (a
+ * call with B = 0 and NULL buffers is how to ask): chains of more than 8 joint positions and chains with
+ * prismatic joints, as the single call refuses them.  Otherwise B = 0 is a no-op. */
+int optik_hip_diff_ik_batch(const optik_hip_chain *chain, const double *ee_offset7, const double *d_q,
+                            const double *d_V, int64_t ld_V, const double *d_vmax, int64_t ld_vmax,
+                            int64_t B, double *d_alpha, double *d_v, int32_t *d_status, void *stream);
+
 /* Restart seeds: ChaCha8Rng::seed_from_u64(42), set_stream(i), one uniform draw
  * per joint (lib.rs:358-370, 86-91) for i = first .. first+count-1 -> d_q [n][count]. */
 int optik_hip_seed_batch(const optik_hip_chain *chain, uint64_t first, int64_t count, double *d_q,

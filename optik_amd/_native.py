@@ -86,6 +86,7 @@ def lib():
     L.optik_hip_eval_batch.argtypes = [vp, C.POINTER(SolverConfigC), dp, dp, vp, C.c_int64, vp, vp, vp]
     L.optik_hip_fk_batch.argtypes = [vp, dp, vp, C.c_int64, vp, vp, vp]
     L.optik_hip_seed_batch.argtypes = [vp, C.c_uint64, C.c_int64, vp, vp]
+    L.optik_hip_diff_ik_batch.argtypes = [vp, dp, vp, vp, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, vp, vp]
     L.optik_hip_ik_batch.argtypes = [vp, C.POINTER(SolverConfigC), vp, vp, C.c_int32, dp,
                                      C.c_uint64, C.c_uint64, C.c_uint32, C.c_double,
                                      C.POINTER(IkOutputs), vp]

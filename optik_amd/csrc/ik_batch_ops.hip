@@ -2,10 +2,12 @@
 //
 //   eval_batch_kernel     objective + gradient (objective.rs:40-110) for a batch of configurations
 //   fk_batch_kernel       end-effector pose (+ body Jacobian, kinematics.rs:123-196) for a batch
+//   diff_ik_batch_kernel  Robot::diff_ik (lib.rs:123-239) for a batch: FK + Jacobian, then the LP of diff_ik_lp.hpp
 //   fk_general_kernel     forward kinematics of a chain with prismatic joints (kinematics.rs:243-255)
 //   seed_batch_kernel     ChaCha8 restart seeds (lib.rs:358-370, 86-91)
 //   probe_kernel, probe_math_kernel    elementary functions / the math.rs functions one at a time (test hooks)
 // One configuration per lane, chain table staged in LDS, coalesced struct-of-arrays in and out.  All f64.
+#include "diff_ik_lp.hpp"
 #include "ik_host.hpp"
 
 using namespace optik;
@@ -52,6 +54,20 @@ struct FkLaunch {
     double *jac;   // [6n][B] or null
 };
 
+// joint_jacobian, kinematics.rs:166-196: column k of the body Jacobian (linear, angular; end-effector frame).
+// fk_batch_kernel and diff_ik_batch_kernel share it: the same operations on the same operands, the same bits.
+template <int N, bool TIP>
+__device__ __forceinline__ void jacobian_column(const ChainDev &sch, const Kin<N, TIP> &kin, const Q4 eeqc, int k,
+                                                double (&c6)[6]) {
+    const V3 ax{sch.axis[k][0], sch.axis[k][1], sch.axis[k][2]};
+    const V3 angular = qrot(kin.tf[k].q, ax);
+    const V3 d{kin.ee.t.x - kin.tf[k].t.x, kin.ee.t.y - kin.tf[k].t.y, kin.ee.t.z - kin.tf[k].t.z};
+    const V3 linear = cross(angular, d);
+    const V3 al = qrot(eeqc, angular);
+    const V3 ll = qrot(eeqc, linear);
+    c6[0] = ll.x; c6[1] = ll.y; c6[2] = ll.z; c6[3] = al.x; c6[4] = al.y; c6[5] = al.z;
+}
+
 template <int N, bool TIP>
 __global__ __launch_bounds__(256) void fk_batch_kernel(const FkLaunch a) {
     __shared__ ChainDev sch;
@@ -71,17 +87,74 @@ __global__ __launch_bounds__(256) void fk_batch_kernel(const FkLaunch a) {
             const Q4 eeqc = qconj(kin.ee.q);
 #pragma unroll
             for (int k = 0; k < N; ++k) {
-                const V3 ax{sch.axis[k][0], sch.axis[k][1], sch.axis[k][2]};
-                const V3 angular = qrot(kin.tf[k].q, ax);
-                const V3 d{kin.ee.t.x - kin.tf[k].t.x, kin.ee.t.y - kin.tf[k].t.y, kin.ee.t.z - kin.tf[k].t.z};
-                const V3 linear = cross(angular, d);
-                const V3 al = qrot(eeqc, angular);
-                const V3 ll = qrot(eeqc, linear);
-                const double c6[6] = {ll.x, ll.y, ll.z, al.x, al.y, al.z};
+                double c6[6];
+                jacobian_column<N, TIP>(sch, kin, eeqc, k, c6);
 #pragma unroll
                 for (int r = 0; r < 6; ++r) a.jac[(size_t)(k * 6 + r) * a.B + b] = c6[r];
             }
         }
+    }
+}
+
+struct DiffIkLaunch {
+    const ChainDev *chain;
+    EvalParams ep;      // only the ee_offset part is used
+    const double *q;    // [n][B]
+    const double *V;    // [6][ld_V], ld_V = 0: one twist for every row
+    const double *vmax; // [n][ld_vmax], ld_vmax = 0: one limit vector for every row
+    long long ld_V, ld_vmax;
+    long long B;
+    double *alpha;      // [B]
+    double *v;          // [n][B]
+    int32_t *status;    // [B]
+};
+
+// One configuration per thread, every step of optik_robot_diff_ik_ex in that thread: FK and the body Jacobian with
+// fk_batch_kernel's code, then the LP of diff_ik_lp.hpp -- no [7 + 6n][B] workspace between them.  The LP's work
+// depends on the row (C(2(n+1), d) vertex solves, d = n + 1 - rank: 14 for a non-singular 6-joint arm, 120 for 7
+// joints, 816 for 8, more at a singularity), so the threads of a wave diverge where their configurations differ in
+// d; and the runtime-indexed pivots keep the LP's small matrices in scratch.  Both are accepted in this first
+// version (the measured rate and what bounds it).
+template <int N, bool TIP>
+__global__ __launch_bounds__(256) void diff_ik_batch_kernel(const DiffIkLaunch a) {
+    __shared__ ChainDev sch;
+    stage_chain(sch, a.chain);
+    for (long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x; b < a.B;
+         b += (long long)gridDim.x * blockDim.x) {
+        double q[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) q[i] = a.q[(size_t)i * a.B + b];
+        Kin<N, TIP> kin;
+        forward_kinematics<N, TIP>(sch, a.ep, q, kin);
+        double jac[6 * N];
+        const Q4 eeqc = qconj(kin.ee.q);
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            double c6[6];
+            jacobian_column<N, TIP>(sch, kin, eeqc, k, c6);
+#pragma unroll
+            for (int r = 0; r < 6; ++r) jac[k * 6 + r] = c6[r];
+        }
+        // (ld = 0: component k of the one shared vector is element k)
+        const long long bV = a.ld_V ? b : 0, bM = a.ld_vmax ? b : 0;
+        const long long sV = a.ld_V ? a.ld_V : 1, sM = a.ld_vmax ? a.ld_vmax : 1;
+        double V[6], vmax[N];
+#pragma unroll
+        for (int r = 0; r < 6; ++r) V[r] = a.V[(size_t)r * sV + bV];
+#pragma unroll
+        for (int i = 0; i < N; ++i) vmax[i] = a.vmax[(size_t)i * sM + bM];
+        const double quat[4] = {kin.ee.q.i, kin.ee.q.j, kin.ee.q.k, kin.ee.q.w};
+        double alpha = 0.0, v[N];
+        const int st = lp::diff_ik_lp<N>(N, quat, jac, V, vmax, &alpha, v);
+        if (st) {
+            alpha = 0.0;
+#pragma unroll
+            for (int i = 0; i < N; ++i) v[i] = 0.0;
+        }
+        a.alpha[b] = alpha;
+#pragma unroll
+        for (int i = 0; i < N; ++i) a.v[(size_t)i * a.B + b] = v[i];
+        a.status[b] = st;
     }
 }
 
@@ -197,6 +270,10 @@ __global__ void probe_math_kernel(int op, const double *poses, long long count, 
     }
 }
 
+// (the Jacobian's refusal: fk_batch with d_jac, diff_ik_batch -- and through them the host layer's single calls)
+const char *const kPrismaticJacobianMsg =
+    "joint_jacobian: prismatic joints are not implemented (the reference panics: kinematics.rs:185 todo!())";
+
 }  // namespace
 
 extern "C" {
@@ -239,9 +316,7 @@ int optik_hip_fk_batch(const optik_hip_chain *ch, const double *ee_offset7, cons
     if (B == 0) return 0;
     BIND_DEVICE(ch);
     if (ch->prismatic) {
-        if (d_jac)
-            return fail(OPTIK_HIP_EUNSUPPORTED,
-                        "joint_jacobian: prismatic joints are not implemented (the reference panics: kinematics.rs:185 todo!())");
+        if (d_jac) return fail(OPTIK_HIP_EUNSUPPORTED, kPrismaticJacobianMsg);
         FkGeneralLaunch g;
         std::memset(&g, 0, sizeof g);
         g.n_joints = ch->n_joints;
@@ -273,6 +348,33 @@ int optik_hip_fk_batch(const optik_hip_chain *ch, const double *ee_offset7, cons
     a.q = d_q; a.B = B; a.pose = d_pose; a.jac = d_jac;
     const int grid = grid_for(ch, B, 256, 8);
 #define CALL(NN, TT) hipLaunchKernelGGL((fk_batch_kernel<NN, TT>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a)
+    OPTIK_DISPATCH(ch, CALL);
+#undef CALL
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int optik_hip_diff_ik_batch(const optik_hip_chain *ch, const double *ee_offset7, const double *d_q, const double *d_V,
+                            int64_t ld_V, const double *d_vmax, int64_t ld_vmax, int64_t B, double *d_alpha,
+                            double *d_v, int32_t *d_status, void *stream) {
+    // (the chain's refusals come first: a call with B = 0 asks whether the chain is supported)
+    if (!ch || B < 0) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    if (ch->wide || ch->n > 8)
+        return fail(OPTIK_HIP_EUNSUPPORTED, "diff_ik: chains of more than 8 joint positions are not supported");
+    if (ch->prismatic) return fail(OPTIK_HIP_EUNSUPPORTED, kPrismaticJacobianMsg);
+    if (B == 0) return 0;
+    if (!d_q || !d_V || !d_vmax || !d_alpha || !d_v || !d_status) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    if ((ld_V != 0 && ld_V < B) || (ld_vmax != 0 && ld_vmax < B))
+        return fail(OPTIK_HIP_EINVAL, "ld_V / ld_vmax: 0 (one vector for every row) or at least B");
+    BIND_DEVICE(ch);
+    DiffIkLaunch a;
+    a.chain = ch->dev;
+    const double one[3] = {1, 1, 1};
+    make_eval_params(one, one, ee_offset7, a.ep);
+    a.q = d_q; a.V = d_V; a.vmax = d_vmax; a.ld_V = ld_V; a.ld_vmax = ld_vmax;
+    a.B = B; a.alpha = d_alpha; a.v = d_v; a.status = d_status;
+    const int grid = grid_for(ch, B, 256, 8);
+#define CALL(NN, TT) hipLaunchKernelGGL((diff_ik_batch_kernel<NN, TT>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a)
     OPTIK_DISPATCH(ch, CALL);
 #undef CALL
     HIP_TRY(hipGetLastError());

@@ -27,6 +27,7 @@
 
 #include "../../include/optik.h"
 #include "device_scope.hpp"
+#include "diff_ik_lp.hpp"
 #include "urdf_chain.hpp"
 
 using optik_host::Chain;
@@ -86,6 +87,11 @@ int set_err(int code, const std::string &msg) {
     g_robot_err = msg;
     return code;
 }
+
+// diff_ik and diff_ik_batch refuse the same chains with the same words
+const char *const kDiffIkMaxNMsg =
+    "diff_ik: chains of more than 8 joint positions are not supported (the reference's own "
+    "diff_ik only runs for n = 6: lib.rs:196-197 builds a 6-row block for n columns)";
 
 std::vector<int> devices_from_env();
 
@@ -887,167 +893,93 @@ const double *optik_robot_ik(const optik_robot *r, const CSolverConfig *config, 
 }
 
 // Robot::diff_ik, lib.rs:123-239: the largest 0 <= alpha <= 1 for which joint velocities v with
-// |v_i| <= v_max_i realise the end-effector twist alpha * V_WE (world frame):
-//     max alpha   s.t.   J_W(q) v = alpha V,   -v_max <= v <= v_max,   0 <= alpha <= 1.
-// The reference hands this LP to Clarabel (an interior-point solver; un-vendored).  It has at
-// most 8 unknowns, so it is solved exactly here: the equality constraints are eliminated
-// (null space of [J_W | -V] by Gauss-Jordan with full pivoting) and the vertices of the
-// remaining polytope (any dimension: d = n + 1 - rank) are enumerated.  The optimal alpha is
-// unique.  Where the reference's own code can run the optimal v is unique too: lib.rs:196-197
-// sizes the equality block as `b.extend(vec![0.0; n]); K.push(ZeroConeT(n))` for a 6-row
-// matrix, so DefaultSolver::new only accepts n = 6 (for any other n the dimensions disagree
-// and the `expect("solver initialization failed")` panics), and a non-singular 6 x 6 Jacobian
-// leaves a single ray v = alpha J^-1 V (tests: closed form on UR3e).  For n != 6 -- an
-// extension -- and at singularities the optimal face may have positive dimension: for d = 2
-// the minimum-norm point of the optimal edge is returned, for d > 2 an optimal vertex of
-// minimum norm among the vertices (an interior-point solver would return a point inside the
-// face).  FK and the Jacobian come from the HIP kernels.
+// |v_i| <= v_max_i realise the end-effector twist alpha * V_WE (world frame).  The reference hands this LP to
+// Clarabel (an interior-point solver; un-vendored); here it is solved exactly by diff_ik_lp.hpp -- the same
+// function diff_ik_batch_kernel runs on the device, so a row of optik_robot_diff_ik_batch returns these bits.
+// FK and the Jacobian come from the HIP kernels.
 int optik_robot_diff_ik_ex(const optik_robot *r, const double *x0, const double *V_WE, const double *v_max,
                            const double *ee16, double *alpha_out, double *v_out) {
     if (!r || !x0 || !V_WE || !v_max) return set_err(-1, "null argument");
-    const int n = r->n, nz = n + 1;
-    if (n > 8)
-        return set_err(-1, "diff_ik: chains of more than 8 joint positions are not supported (the reference's own "
-                           "diff_ik only runs for n = 6: lib.rs:196-197 builds a 6-row block for n columns)");
-    double p7[7];
-    std::vector<double> jac(6 * (size_t)n);
-    if (fk_on_device(r, x0, ee16, p7, jac.data())) return -1;
-    for (int i = 0; i < n; ++i)
-        if (!(v_max[i] >= 0.0)) return 1;  // infeasible box
-    // body-frame Jacobian -> world frame: both 3-row blocks rotated by R_WE (lib.rs:190-197)
-    const double qi = p7[3], qj = p7[4], qk = p7[5], qw = p7[6];
-    const double R[3][3] = {{qw * qw + qi * qi - qj * qj - qk * qk, 2 * (qi * qj - qw * qk), 2 * (qw * qj + qi * qk)},
-                            {2 * (qw * qk + qi * qj), qw * qw - qi * qi + qj * qj - qk * qk, 2 * (qj * qk - qw * qi)},
-                            {2 * (qi * qk - qw * qj), 2 * (qw * qi + qj * qk), qw * qw - qi * qi - qj * qj + qk * qk}};
-    double M[6][9];  // [J_W | -V], 6 x (n + 1)
-    for (int c = 0; c < n; ++c)
-        for (int blk = 0; blk < 2; ++blk)
-            for (int a = 0; a < 3; ++a) {
-                double acc = 0.0;
-                for (int b = 0; b < 3; ++b) acc += R[a][b] * jac[(size_t)c * 6 + blk * 3 + b];
-                M[blk * 3 + a][c] = acc;
-            }
-    double scale = 0.0;
-    for (int a = 0; a < 6; ++a) {
-        M[a][n] = -V_WE[a];
-        for (int c = 0; c < nz; ++c) scale = std::max(scale, std::fabs(M[a][c]));
+    const int n = r->n;
+    if (n > 8) return set_err(-1, kDiffIkMaxNMsg);
+    double p7[7], jac[6 * 8];
+    if (fk_on_device(r, x0, ee16, p7, jac)) return -1;
+    double alpha = 0.0, v[8];
+    if (optik::lp::diff_ik_lp<8>(n, p7 + 3, jac, V_WE, v_max, &alpha, v)) return 1;
+    if (alpha_out) *alpha_out = alpha;
+    if (v_out) std::memcpy(v_out, v, sizeof(double) * (size_t)n);
+    return 0;
+}
+
+// B diff_ik calls in one launch per chunk of rows (optik_hip_diff_ik_batch: the same FK, Jacobian and LP code as
+// the call above, on the device).  Rows are staged to struct-of-arrays through the robot's pinned batch block.
+int optik_robot_diff_ik_batch(const optik_robot *r, int64_t B, const double *x0, const double *V_WE,
+                              const double *v_max, const double *ee16, double *alpha_out, double *v_out,
+                              int32_t *status_out) {
+    if (!r || !x0 || !V_WE || !v_max) return set_err(-1, "null argument");
+    if (B < 0) return set_err(-1, "bad argument");
+    const int n = r->n;
+    if (n > 8) return set_err(-1, kDiffIkMaxNMsg);
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    // (B = 0: the kernel layer's refusals of the chain alone -- prismatic joints -- before anything is staged)
+    if (optik_hip_diff_ik_batch(c->chain, nullptr, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr,
+                                nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (B == 0) return 0;
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    std::lock_guard<std::mutex> lock(c->batch_mu);
+    optik::DeviceScope dev_scope(c->device);
+    if (!dev_scope.ok()) return set_err(-1, "hipSetDevice failed");
+    // rows per launch: bounds the block (~66 MB for 8 joints) whatever B is
+    const int64_t chunk = B < ((int64_t)1 << 18) ? B : ((int64_t)1 << 18);
+    // per row: q n | V 6 | v_max n | alpha 1 | v n doubles, then the int32 status words (half a double each)
+    const size_t need = (size_t)(3 * n + 7) * (size_t)chunk + ((size_t)chunk + 1) / 2;
+    if (need > c->batch_cap) {
+        if (c->d_batch) (void)hipFree(c->d_batch);
+        if (c->h_batch) (void)hipHostFree(c->h_batch);
+        c->d_batch = nullptr; c->h_batch = nullptr; c->batch_cap = 0;
+        if (hipMalloc(&c->d_batch, sizeof(double) * need) != hipSuccess
+            || hipHostMalloc(&c->h_batch, sizeof(double) * need) != hipSuccess)
+            return set_err(-1, "batch workspace allocation failed");
+        c->batch_cap = need;
     }
-    // Gauss-Jordan with full pivoting: pivot columns pc[0..rank), the others are free
-    int pc[6], rank = 0;
-    bool is_pivot[9] = {false};
-    for (int step = 0; step < 6; ++step) {
-        int br = -1, bc = -1;
-        double best = 1e-12 * (scale > 0.0 ? scale : 1.0);
-        for (int a = step; a < 6; ++a)
-            for (int c = 0; c < nz; ++c)
-                if (!is_pivot[c] && std::fabs(M[a][c]) > best) { best = std::fabs(M[a][c]); br = a; bc = c; }
-        if (br < 0) break;
-        for (int c = 0; c < nz; ++c) std::swap(M[step][c], M[br][c]);
-        const double piv = M[step][bc];
-        for (int c = 0; c < nz; ++c) M[step][c] /= piv;
-        for (int a = 0; a < 6; ++a)
-            if (a != step) {
-                const double f = M[a][bc];
-                if (f != 0.0) for (int c = 0; c < nz; ++c) M[a][c] -= f * M[step][c];
+    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+        const size_t L = (size_t)(B - b0 < chunk ? B - b0 : chunk);
+        double *h_q = c->h_batch, *h_V = h_q + (size_t)n * L, *h_vm = h_V + 6 * L, *h_a = h_vm + (size_t)n * L,
+               *h_v = h_a + L;
+        const int32_t *h_st = reinterpret_cast<const int32_t *>(h_v + (size_t)n * L);
+        double *d_q = c->d_batch, *d_V = d_q + (size_t)n * L, *d_vm = d_V + 6 * L, *d_a = d_vm + (size_t)n * L,
+               *d_v = d_a + L;
+        int32_t *d_st = reinterpret_cast<int32_t *>(d_v + (size_t)n * L);
+        parallel_ranges(L, [&](size_t k0, size_t k1) {
+            for (size_t k = k0; k < k1; ++k) {
+                const size_t row = (size_t)b0 + k;
+                for (int i = 0; i < n; ++i) h_q[(size_t)i * L + k] = x0[row * n + i];
+                for (int i = 0; i < 6; ++i) h_V[(size_t)i * L + k] = V_WE[row * 6 + i];
+                for (int i = 0; i < n; ++i) h_vm[(size_t)i * L + k] = v_max[row * n + i];
             }
-        is_pivot[bc] = true;
-        pc[rank++] = bc;
+        });
+        if (hipMemcpyAsync(d_q, h_q, sizeof(double) * (size_t)(2 * n + 6) * L, hipMemcpyHostToDevice, nullptr)
+            != hipSuccess)
+            return set_err(-1, "upload failed");
+        if (optik_hip_diff_ik_batch(c->chain, ee16 ? ee7 : nullptr, d_q, d_V, (int64_t)L, d_vm, (int64_t)L,
+                                    (int64_t)L, d_a, d_v, d_st, nullptr))
+            return set_err(-1, optik_hip_last_error());
+        if (hipMemcpyAsync(h_a, d_a, sizeof(double) * (size_t)(n + 1) * L + sizeof(int32_t) * L,
+                           hipMemcpyDeviceToHost, nullptr) != hipSuccess
+            || hipStreamSynchronize(nullptr) != hipSuccess)
+            return set_err(-1, "download failed");
+        parallel_ranges(L, [&](size_t k0, size_t k1) {
+            for (size_t k = k0; k < k1; ++k) {
+                const size_t row = (size_t)b0 + k;
+                if (alpha_out) alpha_out[row] = h_a[k];
+                if (v_out) for (int i = 0; i < n; ++i) v_out[row * n + i] = h_v[(size_t)i * L + k];
+                if (status_out) status_out[row] = h_st[k];
+            }
+        });
     }
-    const int d = nz - rank;  // dimension of {z = (v, alpha) : [J_W | -V] z = 0}
-    std::vector<double> best_z((size_t)nz, 0.0);  // z = 0 (alpha = 0, v = 0) is always feasible
-    double best_alpha = 0.0, best_norm = 0.0;
-    if (d >= 1) {
-        // basis B (nz x d): free variable k = 1, pivot variables from the reduced rows
-        int freec[9], nf = 0;
-        for (int c = 0; c < nz; ++c) if (!is_pivot[c]) freec[nf++] = c;
-        double B[9][9];
-        for (int k = 0; k < d; ++k) {
-            for (int c = 0; c < nz; ++c) B[c][k] = 0.0;
-            B[freec[k]][k] = 1.0;
-            for (int rr = 0; rr < rank; ++rr) B[pc[rr]][k] = -M[rr][freec[k]];
-        }
-        // half-spaces lo_c <= (B t)_c <= hi_c; vertices = d of them tight
-        const int nh = 2 * nz;
-        auto bound = [&](int h, double &sgn) -> double {  // constraint h: sgn * (B t)_c <= value
-            const int c = h / 2;
-            const bool upper = (h % 2) == 0;
-            sgn = upper ? 1.0 : -1.0;
-            if (c == n) return upper ? 1.0 : 0.0;
-            return v_max[c];
-        };
-        const double tol = 1e-9;
-        auto consider = [&](const double *t) {
-            double z[9];
-            for (int c = 0; c < nz; ++c) { z[c] = 0.0; for (int k = 0; k < d; ++k) z[c] += B[c][k] * t[k]; }
-            for (int h = 0; h < nh; ++h) {
-                double sgn; const double val = bound(h, sgn);
-                if (sgn * z[h / 2] > val + tol * (1.0 + val)) return;
-            }
-            double nrm = 0.0;
-            for (int c = 0; c < n; ++c) nrm += z[c] * z[c];
-            if (z[n] > best_alpha + 1e-12 || (std::fabs(z[n] - best_alpha) <= 1e-12 && nrm < best_norm)) {
-                best_alpha = z[n]; best_norm = nrm;
-                for (int c = 0; c < nz; ++c) best_z[(size_t)c] = z[c];
-            }
-        };
-        auto vertex = [&](const int *idx) {  // the point where the d constraints idx[] are tight
-            double A[9][10];
-            for (int q = 0; q < d; ++q) {
-                double sgn; const double val = bound(idx[q], sgn);
-                for (int k = 0; k < d; ++k) A[q][k] = sgn * B[idx[q] / 2][k];
-                A[q][d] = val;
-            }
-            for (int q = 0; q < d; ++q) {  // Gauss-Jordan, partial pivoting
-                int pr = q;
-                for (int a = q + 1; a < d; ++a) if (std::fabs(A[a][q]) > std::fabs(A[pr][q])) pr = a;
-                if (std::fabs(A[pr][q]) < 1e-13) return;  // the constraints are parallel: no vertex
-                for (int k = 0; k <= d; ++k) std::swap(A[q][k], A[pr][k]);
-                for (int a = 0; a < d; ++a)
-                    if (a != q) {
-                        const double f = A[a][q] / A[q][q];
-                        for (int k = q; k <= d; ++k) A[a][k] -= f * A[q][k];
-                    }
-            }
-            double t[9];
-            for (int q = 0; q < d; ++q) t[q] = A[q][d] / A[q][q];
-            consider(t);
-        };
-        // every choice of d of the nh half-spaces (d <= 9, nh <= 18: at most 48 620 small solves,
-        // and d > 2 only at a kinematic singularity)
-        int idx[9];
-        for (int q = 0; q < d; ++q) idx[q] = q;
-        for (bool more = d <= nh; more;) {
-            vertex(idx);
-            int q = d - 1;
-            while (q >= 0 && idx[q] == nh - d + q) --q;
-            if (q < 0) { more = false; break; }
-            ++idx[q];
-            for (int k = q + 1; k < d; ++k) idx[k] = idx[k - 1] + 1;
-        }
-        // a redundant arm at the optimum: slide along the optimal face to the minimum-norm v
-        if (d == 2) {
-            // direction inside the face: alpha fixed -> B[n] . dt = 0
-            const double dt[2] = {-B[n][1], B[n][0]};
-            double dz[9], dd = 0.0, zd = 0.0;
-            for (int c = 0; c < nz; ++c) dz[c] = B[c][0] * dt[0] + B[c][1] * dt[1];
-            for (int c = 0; c < n; ++c) { dd += dz[c] * dz[c]; zd += best_z[(size_t)c] * dz[c]; }
-            if (dd > 0.0) {
-                double lo = -1e300, hi = 1e300;  // feasible range of the step along dz
-                for (int c = 0; c < n; ++c) {
-                    if (std::fabs(dz[c]) < 1e-14) continue;
-                    double a1 = (-v_max[c] - best_z[(size_t)c]) / dz[c], a2 = (v_max[c] - best_z[(size_t)c]) / dz[c];
-                    if (a1 > a2) std::swap(a1, a2);
-                    lo = std::max(lo, a1); hi = std::min(hi, a2);
-                }
-                double step = -zd / dd;
-                step = std::min(std::max(step, lo), hi);
-                if (lo <= hi && std::isfinite(step))
-                    for (int c = 0; c < n; ++c) best_z[(size_t)c] += step * dz[c];
-            }
-        }
-    }
-    if (alpha_out) *alpha_out = std::min(std::max(best_z[(size_t)n], 0.0), 1.0);
-    if (v_out) for (int c = 0; c < n; ++c) v_out[c] = best_z[(size_t)c];
     return 0;
 }
 

@@ -87,6 +87,24 @@ class HipChain:
                                                B, _ptr(pose), _ptr(jac), _stream_ptr()))
         return (pose, jac) if jacobian else pose
 
+    def diff_ik_batch(self, q, V, v_max, ee_offset7=None):
+        """Robot.diff_ik for every column of q [n, B] (float64 cuda tensors): V [6, B] or one twist [6], v_max
+        [n, B] or one limit vector [n].  Stream-ordered on the current stream; returns (alpha [B], v [n, B],
+        status [B] int32: 0 solved, 1 no solution with alpha and v zero)."""
+        assert q.is_cuda and q.dtype == torch.float64 and q.dim() == 2 and q.shape[0] == self.n and q.is_contiguous()
+        B = q.shape[1]
+        for t, rows in ((V, 6), (v_max, self.n)):
+            assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.device == q.device
+            assert tuple(t.shape) in ((rows,), (rows, B)), f"expected [{rows}] or [{rows}, {B}], got {tuple(t.shape)}"
+        alpha = torch.empty(B, dtype=torch.float64, device=q.device)
+        v = torch.empty((self.n, B), dtype=torch.float64, device=q.device)
+        status = torch.empty(B, dtype=torch.int32, device=q.device)
+        ee = np.ascontiguousarray(ee_offset7, dtype=np.float64) if ee_offset7 is not None else None
+        nat.check(nat.lib().optik_hip_diff_ik_batch(
+            self._h, _dp(ee) if ee is not None else None, _ptr(q), _ptr(V), B if V.dim() == 2 else 0,
+            _ptr(v_max), B if v_max.dim() == 2 else 0, B, _ptr(alpha), _ptr(v), _ptr(status), _stream_ptr()))
+        return alpha, v, status
+
     def seed_batch(self, first, count):
         q = torch.empty((self.n, count), dtype=torch.float64, device=self.device)
         nat.check(nat.lib().optik_hip_seed_batch(self._h, int(first), int(count), _ptr(q), _stream_ptr()))

@@ -35,6 +35,7 @@ def _bind(L):
                                              dp, dp, C.POINTER(C.c_int32)]
     L.optik_robot_fk_ex.argtypes = [vp, dp, dp, dp]
     L.optik_robot_diff_ik_ex.argtypes = [vp, dp, dp, dp, dp, C.POINTER(C.c_double), dp]
+    L.optik_robot_diff_ik_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_int32)]
     L.optik_robot_joint_jacobian_ex.argtypes = [vp, dp, dp, dp]
     L.optik_robot_set_devices.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32]
     L.optik_robot_num_devices.argtypes = [vp]
@@ -280,6 +281,36 @@ class Robot:
         if rc == 1:
             return None
         return alpha.value, v.tolist()
+
+    def diff_ik_batch_arrays(self, x0s, V_WE, v_max, ee_offset=None):
+        """Many diff_ik() calls at once (extension), array form: `x0s` [B, n], `V_WE` [B, 6] or one twist [6],
+        `v_max` [B, n] or one limit vector [n] -> (alpha [B], v [B, n], found [B] bool).  Row b is what
+        diff_ik(x0s[b], V_WE[b], v_max[b], ee_offset) returns, bit for bit; rows with found False are zero.
+        One kernel launch per 262 144 rows (include/optik.h: optik_robot_diff_ik_batch)."""
+        n = self.num_positions()
+        x0s = np.asarray(x0s, dtype=np.float64)
+        if x0s.ndim != 2 or x0s.shape[1] != n:
+            raise ValueError("x0s must be [B, n]")
+        B = x0s.shape[0]
+        x0s = np.ascontiguousarray(x0s)
+        # (a shared twist / limit vector is repeated here: the host layer takes one row per configuration)
+        V = np.ascontiguousarray(np.broadcast_to(np.asarray(V_WE, dtype=np.float64), (B, 6)))
+        vm = np.ascontiguousarray(np.broadcast_to(np.asarray(v_max, dtype=np.float64), (B, n)))
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        alpha, v = np.zeros(B), np.zeros((B, n))
+        status = np.zeros(B, dtype=np.int32)
+        rc = self._L.optik_robot_diff_ik_batch(self._h, B, _dp(x0s), _dp(V), _dp(vm),
+                                               _dp(ee) if ee is not None else None, _dp(alpha), _dp(v),
+                                               status.ctypes.data_as(C.POINTER(C.c_int32)))
+        if rc < 0:
+            raise RuntimeError(_err(self._L))
+        return alpha, v, status == 0
+
+    def diff_ik_batch(self, x0s, V_WE, v_max, ee_offset=None):
+        """diff_ik_batch_arrays as a list: (alpha, v) or None per row, like B calls of diff_ik()."""
+        alpha, v, found = self.diff_ik_batch_arrays(x0s, V_WE, v_max, ee_offset)
+        al, vs = alpha.tolist(), v.tolist()
+        return [(al[b], vs[b]) if ok else None for b, ok in enumerate(found.tolist())]
 
     # -- extensions ---------------------------------------------------------------
     def chain_tables(self):
