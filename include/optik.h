@@ -98,6 +98,24 @@ int optik_robot_ik_batch_poses(const optik_robot *robot, const CSolverConfig *co
                                const double *targets16, uint32_t flags, const double *x0,
                                const double *ee_offset16, double *x_out, double *f_out,
                                int32_t *found_out);
+/* Up to K distinct solutions per target (extension; optik_hip_ik_solutions): every restart index in
+ * [0, config->max_restarts) of every target runs to its end, Speed as well as Quality, and the successes are taken
+ * in (key, index) order -- Quality: distance to the seed, Speed: the index -- keeping one only if its largest joint
+ * difference to every solution kept before it is > min_dist.  On a redundant arm the successes form a continuum and
+ * min_dist sets the spacing of the returned samples.  With K = 1 the solution is what ik() returns for the target
+ * (Quality with max_time = 0; Speed after set_parallelism(1)).  targets16 [T][16], flags and x0 [T][n] as in
+ * optik_robot_ik_batch_poses (rc -3: invalid transform, -2: seed outside the limits) -> count_out [T] (0..K),
+ * x_out [T][K][n], f_out [T][K], idx_out [T][K] in acceptance order; slots past the count: NaN, idx UINT64_MAX.  Any
+ * output may be NULL.  max_restarts = 0 (unlimited) and max_restarts > OPTIK_ROBOT_MAX_SOLUTION_RESTARTS are refused
+ * (-1) before any GPU work, as are K outside 1..256 and a NaN or negative min_dist.  The targets are cut into one
+ * contiguous part per device and each part into launches of about 4 M (target, restart) items; a target never spans
+ * two launches, so the result does not depend on either.  max_time: the time left is each launch's deadline; a launch
+ * that would start after it is not run and its targets keep count 0. */
+#define OPTIK_ROBOT_MAX_SOLUTION_RESTARTS (1ull << 22)
+int optik_robot_ik_solutions(const optik_robot *robot, const CSolverConfig *config, int32_t T,
+                             const double *targets16, uint32_t flags, const double *x0, const double *ee16,
+                             int32_t K, double min_dist, int32_t *count_out, double *x_out /* [T][K][n] */,
+                             double *f_out /* [T][K] */, uint64_t *idx_out /* [T][K] */);
 /* GPUs of this node the robot spreads its work over (restarts shard trivially: lib.rs:297-300
  * hands the same index range to rayon workers).  optik_robot_ik / _ik_ex: after the
  * latency-sized first launch every round's restart range is cut into one contiguous part per

@@ -176,6 +176,31 @@ int optik_hip_ik_batch(optik_hip_chain *chain, const optik_solver_config *cfg,
                        uint32_t flags, double deadline_s, const optik_hip_ik_outputs *out,
                        void *stream);
 
+/* Up to K distinct solutions per target, from one launch of restarts restart_begin..restart_end-1 run to their end
+ * (no early exit, Speed as well as Quality; deadline_s as in optik_hip_ik_batch).  The candidates of a target are
+ * its successful restarts (lib.rs:376-379), in the order of (key, restart index) -- key = ||x - x0||_2 summed left
+ * to right for Quality, (double)index for Speed, as in optik_hip_ik_batch.  They are taken greedily: a candidate is
+ * accepted if max_i |x_i - a_i| > min_dist for every solution a accepted before it (no angle wrapping; min_dist = 0
+ * merges exact duplicates only), until K are accepted.  On a redundant arm the successes form a continuum and
+ * min_dist sets the spacing of the returned samples.  With K = 1 the one solution is optik_hip_ik_batch's winner
+ * without early exit.  The set does not depend on the solver that ran or on the launch size.
+ * Outputs, slot order = acceptance order; any pointer may be NULL.  Slots past count: x and f NaN, idx UINT64_MAX,
+ * key +inf.  Refused as optik_hip_ik_batch refuses (prismatic chains, infinite limits with random restarts, a bad
+ * solution_mode, too many selection tiles), and for K outside 1..OPTIK_HIP_MAX_SOLUTIONS or a NaN or negative
+ * min_dist.  Stream-ordered; uses the chain's launch workspace like optik_hip_ik_batch. */
+#define OPTIK_HIP_MAX_SOLUTIONS 256
+typedef struct optik_hip_ik_solutions_outputs {
+    int32_t *d_count; /* [T]                                        */
+    double *d_x;      /* [T][K][n]  NaN past count                  */
+    double *d_f;      /* [T][K]     the restart's returned objective */
+    uint64_t *d_idx;  /* [T][K]     UINT64_MAX past count           */
+    double *d_key;    /* [T][K]     +inf past count                 */
+} optik_hip_ik_solutions_outputs;
+int optik_hip_ik_solutions(optik_hip_chain *chain, const optik_solver_config *cfg,
+                           const double *d_targets, const double *d_x0, int32_t T, const double *ee_offset7,
+                           uint64_t restart_begin, uint64_t restart_end, double deadline_s,
+                           int32_t K, double min_dist, const optik_hip_ik_solutions_outputs *out, void *stream);
+
 /* Tuning options of the kernel layer (diagnostics: tests and tools; the defaults are what the product runs with).
  * Each option's default comes from the environment variable named with it, read ONCE when the library first needs
  * an option; afterwards only this call changes it.  Not synchronised with calls in flight.

@@ -54,6 +54,26 @@ class IkOutputs(C.Structure):
     ]
 
 
+class IkSolutionsOutputs(C.Structure):
+    """optik_hip_ik_solutions_outputs (include/optik_hip.h)."""
+    _fields_ = [("d_count", C.c_void_p), ("d_x", C.c_void_p), ("d_f", C.c_void_p), ("d_idx", C.c_void_p),
+                ("d_key", C.c_void_p)]
+
+
+MAX_SOLUTIONS = 256  # OPTIK_HIP_MAX_SOLUTIONS
+MAX_SOLUTION_RESTARTS = 1 << 22  # OPTIK_ROBOT_MAX_SOLUTION_RESTARTS
+
+
+def check_solutions_args(k, min_dist):
+    """The argument rules of optik_hip_ik_solutions, checked on the host: (k, min_dist) as int, float."""
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= MAX_SOLUTIONS:
+        raise ValueError(f"k must be an integer in 1..{MAX_SOLUTIONS}, got {k!r}")
+    min_dist = float(min_dist)
+    if not (min_dist >= 0.0 and min_dist != float("inf")):
+        raise ValueError(f"min_dist must be finite and >= 0, got {min_dist!r}")
+    return int(k), min_dist
+
+
 class LaunchInfo(C.Structure):
     _fields_ = [("grid", C.c_int32), ("block", C.c_int32), ("lds_bytes", C.c_int32),
                 ("tiles", C.c_int32), ("kernel_ms", C.c_float)]
@@ -90,6 +110,9 @@ def lib():
     L.optik_hip_ik_batch.argtypes = [vp, C.POINTER(SolverConfigC), vp, vp, C.c_int32, dp,
                                      C.c_uint64, C.c_uint64, C.c_uint32, C.c_double,
                                      C.POINTER(IkOutputs), vp]
+    L.optik_hip_ik_solutions.argtypes = [vp, C.POINTER(SolverConfigC), vp, vp, C.c_int32, dp, C.c_uint64,
+                                         C.c_uint64, C.c_double, C.c_int32, C.c_double,
+                                         C.POINTER(IkSolutionsOutputs), vp]
     L.optik_hip_ik_host.argtypes = [vp, C.POINTER(SolverConfigC), dp, dp, C.c_int32, dp,
                                     C.c_uint64, C.c_uint64, C.c_uint32, C.c_double, dp, dp,
                                     C.POINTER(C.c_uint64), dp]

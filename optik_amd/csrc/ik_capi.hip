@@ -1,10 +1,10 @@
 // ik_capi.hip -- the C ABI of include/optik_hip.h: chains, tuning options, the restart launch (optik_hip_ik_batch),
-// its host-buffer form (optik_hip_ik_host), timing.
+// its host-buffer form (optik_hip_ik_host), the solution sets (optik_hip_ik_solutions), timing.
 //
 // The solvers are launched from here and defined in their own translation units: the lane-per-restart form
 // (ik_lane_kernel.hip), the quad solver (ik_quad_kernel.hip), the general run-time-n solver (ik_wide_kernel.hip);
-// optik_hip_ik_batch picks one by launch size and joint count.  The selection kernels: ik_select.hip; the batch
-// operators: ik_batch_ops.hip.  No CPU fallback exists: every entry point fails loudly without a device.
+// optik_hip_ik_batch picks one by launch size and joint count.  The selection kernels: ik_select.hip and
+// ik_solutions.hip; the batch operators: ik_batch_ops.hip.  No CPU fallback exists: every entry point fails loudly without a device.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -166,6 +166,7 @@ void optik_hip_chain_destroy(optik_hip_chain *ch) {
     if (ch->wide_ws) hipFree(ch->wide_ws);
     if (ch->tile_recs) hipFree(ch->tile_recs);
     if (ch->first_success) hipFree(ch->first_success);
+    if (ch->sol_pick) hipFree(ch->sol_pick);
     if (ch->tmp_x) hipFree(ch->tmp_x);
     if (ch->tmp_f) hipFree(ch->tmp_f);
     if (ch->tmp_key) hipFree(ch->tmp_key);
@@ -199,6 +200,27 @@ int32_t optik_hip_chain_range_rule(const optik_hip_chain *ch) { return ch ? ch->
 
 }  // extern "C"
 
+// What the solver half of a launch (solve_locked) leaves for the selection stage behind it.
+struct SolvedLaunch {
+    double *px, *pf, *pk;     // per-restart x [n][cols], f [cols], key [cols] (the caller's buffers or chain scratch)
+    uint64_t R;
+    uint64_t tiles_per_target;  // selection tiles of SEL_TILE restarts
+    size_t cols;              // T * R
+    size_t fs_clean_after;    // ch->fs_clean once the launch's last kernel has put the first-success words back
+    bool early;               // the launch used the first-success words
+};
+
+// The solver half of optik_hip_ik_batch and optik_hip_ik_solutions, with the chain's launch mutex held: argument
+// checks, workspace, the solver choice and its launch.  want_sel: a selection stage follows (the per-restart keys go
+// to scratch; need_x / need_f: it reads x / f, scratch for what the caller does not provide).  The selection stage
+// has to put the work-item counter (and, with sl->early, the first-success words) back and then set queue_clean /
+// fs_clean / clean_stream.
+static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, const double *d_targets,
+                        const double *d_x0, int32_t T, const double *ee_offset7, uint64_t restart_begin,
+                        uint64_t restart_end, uint32_t flags, double deadline_s, const optik_hip_ik_outputs *out,
+                        bool want_sel, bool need_x, bool need_f, hipStream_t stream, bool claim_request,
+                        bool *claim_armed, SolvedLaunch *sl);
+
 // optik_hip_ik_batch with the chain's launch mutex already held.
 static int ik_batch_locked(optik_hip_chain *ch, const optik_solver_config *cfg, const double *d_targets,
                            const double *d_x0, int32_t T, const double *ee_offset7, uint64_t restart_begin,
@@ -224,6 +246,43 @@ static int ik_batch_locked(optik_hip_chain *ch, const optik_solver_config *cfg, 
                            uint64_t restart_end, uint32_t flags, double deadline_s, const optik_hip_ik_outputs *out,
                            void *stream_v, bool claim_request, bool *claim_armed) {
     if (claim_armed) *claim_armed = false;
+    if (!out) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    hipStream_t stream = (hipStream_t)stream_v;
+    const bool want_win = out->d_win_x || out->d_win_f || out->d_win_idx || out->d_win_key;
+    SolvedLaunch sl;
+    if (int rc = solve_locked(ch, cfg, d_targets, d_x0, T, ee_offset7, restart_begin, restart_end, flags, deadline_s,
+                              out, want_win, out->d_win_x != nullptr, out->d_win_f != nullptr, stream, claim_request,
+                              claim_armed, &sl))
+        return rc;
+    BIND_DEVICE(ch);
+    if (want_win) {
+        SelectLaunch s;
+        std::memset(&s, 0, sizeof s);
+        s.out_key = sl.pk; s.out_x = sl.px; s.out_f = sl.pf;
+        s.tile_recs = ch->tile_recs;
+        s.tiles_per_target = (int)sl.tiles_per_target;
+        s.tile = SEL_TILE;
+        s.n = ch->n;
+        s.restart_begin = restart_begin;
+        s.n_restarts = sl.R;
+        s.ld = sl.cols;
+        s.win_x = out->d_win_x; s.win_f = out->d_win_f;
+        s.win_idx = (unsigned long long *)out->d_win_idx; s.win_key = out->d_win_key;
+        s.reset_queue = ch->queue;
+        s.reset_fs = sl.early ? ch->first_success : nullptr;
+        HIP_TRY(select_launch(s, T, stream));
+        ch->queue_clean = true;
+        ch->fs_clean = sl.fs_clean_after;
+        ch->clean_stream = stream;
+    }
+    return 0;
+}
+
+static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, const double *d_targets,
+                        const double *d_x0, int32_t T, const double *ee_offset7, uint64_t restart_begin,
+                        uint64_t restart_end, uint32_t flags, double deadline_s, const optik_hip_ik_outputs *out,
+                        bool want_sel, bool need_x, bool need_f, hipStream_t stream, bool claim_request,
+                        bool *claim_armed, SolvedLaunch *sl) {
     if (!ch || !cfg || !d_targets || !d_x0 || !out || T < 1) return fail(OPTIK_HIP_EINVAL, "bad argument");
     if (restart_end <= restart_begin) return fail(OPTIK_HIP_EINVAL, "empty restart range");
     if (cfg->solution_mode != 1 && cfg->solution_mode != 2)
@@ -233,7 +292,6 @@ static int ik_batch_locked(optik_hip_chain *ch, const optik_solver_config *cfg, 
         for (int k = 0; k < ch->n; ++k)
             if (std::isnan(ch->scale[k]))
                 return fail(OPTIK_HIP_EINVAL, "random restarts need finite joint limits (reference: random_range panics)");
-    hipStream_t stream = (hipStream_t)stream_v;
     if (ch->prismatic)
         return fail(OPTIK_HIP_EUNSUPPORTED,
                     "prismatic joints: only forward kinematics is available (the reference's Jacobian panics, kinematics.rs:185)");
@@ -279,10 +337,9 @@ static int ik_batch_locked(optik_hip_chain *ch, const optik_solver_config *cfg, 
         ch->fs_clean = 0;
     }
     // the selection needs the per-restart x / f / key: scratch if the caller skips them
-    const bool want_win = out->d_win_x || out->d_win_f || out->d_win_idx || out->d_win_key;
     double *px = out->d_x, *pf = out->d_f, *pk = nullptr;
-    if (want_win) {
-        const bool need_xf = (!px || !pf) && (out->d_win_x || out->d_win_f);
+    if (want_sel) {
+        const bool need_xf = (!px || !pf) && (need_x || need_f);
         if (cols > ch->tmp_cols) {
             if (ch->tmp_x) HIP_TRY(hipFree(ch->tmp_x));
             if (ch->tmp_f) HIP_TRY(hipFree(ch->tmp_f));
@@ -296,8 +353,8 @@ static int ik_batch_locked(optik_hip_chain *ch, const optik_solver_config *cfg, 
             HIP_TRY(hipMalloc(&ch->tmp_f, sizeof(double) * ch->tmp_cols));
         }
         pk = ch->tmp_key;
-        if (!px && out->d_win_x) px = ch->tmp_x;
-        if (!pf && out->d_win_f) pf = ch->tmp_f;
+        if (!px && need_x) px = ch->tmp_x;
+        if (!pf && need_f) pf = ch->tmp_f;
     }
 
     SolveLaunch a;
@@ -458,30 +515,63 @@ static int ik_batch_locked(optik_hip_chain *ch, const optik_solver_config *cfg, 
     if (ch->timing) { HIP_TRY(hipEventRecord(ch->ev1[ev_slot], stream)); ch->ev_count += 1; }
     ch->last.grid = grid; ch->last.block = WAVE; ch->last.lds_bytes = lds; ch->last.tiles = n_tiles;
 
-    if (want_win) {
-        SelectLaunch s;
-        std::memset(&s, 0, sizeof s);
-        s.out_key = pk; s.out_x = px; s.out_f = pf;
-        s.tile_recs = ch->tile_recs;
-        s.tiles_per_target = (int)tiles_per_target;
-        s.tile = SEL_TILE;
-        s.n = ch->n;
-        s.restart_begin = restart_begin;
-        s.n_restarts = R;
-        s.ld = cols;
-        s.win_x = out->d_win_x; s.win_f = out->d_win_f;
-        s.win_idx = (unsigned long long *)out->d_win_idx; s.win_key = out->d_win_key;
-        s.reset_queue = ch->queue;
-        s.reset_fs = early ? ch->first_success : nullptr;
-        HIP_TRY(select_launch(s, T, stream));
-        ch->queue_clean = true;
-        ch->fs_clean = fs_clean_after;
-        ch->clean_stream = stream;
-    }
+    sl->px = px; sl->pf = pf; sl->pk = pk;
+    sl->R = R;
+    sl->tiles_per_target = tiles_per_target;
+    sl->cols = cols;
+    sl->fs_clean_after = fs_clean_after;
+    sl->early = early;
     return 0;
 }
 
 extern "C" {
+
+int optik_hip_ik_solutions(optik_hip_chain *ch, const optik_solver_config *cfg, const double *d_targets,
+                           const double *d_x0, int32_t T, const double *ee_offset7, uint64_t restart_begin,
+                           uint64_t restart_end, double deadline_s, int32_t K, double min_dist,
+                           const optik_hip_ik_solutions_outputs *out, void *stream_v) {
+    if (!ch || !out) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    if (K < 1 || K > OPTIK_HIP_MAX_SOLUTIONS) return fail(OPTIK_HIP_EINVAL, "K must be in 1..256");
+    if (!(min_dist >= 0.0) || !std::isfinite(min_dist))
+        return fail(OPTIK_HIP_EINVAL, "min_dist must be finite and >= 0");
+    std::lock_guard<std::mutex> lock(ch->mu);
+    hipStream_t stream = (hipStream_t)stream_v;
+    // every restart runs to its end: no flags (no early exit, so the first-success words stay as they are)
+    optik_hip_ik_outputs none;
+    std::memset(&none, 0, sizeof none);
+    SolvedLaunch sl;
+    if (int rc = solve_locked(ch, cfg, d_targets, d_x0, T, ee_offset7, restart_begin, restart_end, 0u, deadline_s,
+                              &none, true, true, out->d_f != nullptr, stream, false, nullptr, &sl))
+        return rc;
+    BIND_DEVICE(ch);
+    if (sl.tiles_per_target > 1 && (size_t)T > ch->sol_pick_cap) {  // (the multi-tile form's round-to-round acceptances)
+        if (ch->sol_pick) HIP_TRY(hipFree(ch->sol_pick));
+        ch->sol_pick = nullptr; ch->sol_pick_cap = 0;
+        HIP_TRY(hipMalloc(&ch->sol_pick, sizeof(unsigned long long) * (size_t)T));
+        ch->sol_pick_cap = (size_t)T;
+    }
+    SolutionsLaunch s;
+    std::memset(&s, 0, sizeof s);
+    s.out_key = sl.pk; s.out_x = sl.px; s.out_f = sl.pf;
+    s.tile_recs = ch->tile_recs;
+    s.pick = ch->sol_pick;
+    s.tiles_per_target = (int)sl.tiles_per_target;
+    s.tile = SEL_TILE;
+    s.n = ch->n;
+    s.K = K;
+    s.min_dist = min_dist;
+    s.restart_begin = restart_begin;
+    s.n_restarts = sl.R;
+    s.ld = sl.cols;
+    s.count = out->d_count; s.x = out->d_x; s.f = out->d_f;
+    s.idx = (unsigned long long *)out->d_idx; s.key = out->d_key;
+    s.reset_queue = ch->queue;
+    HIP_TRY(solutions_launch(s, T, stream));
+    ch->queue_clean = true;
+    ch->fs_clean = sl.fs_clean_after;
+    ch->clean_stream = stream;
+    return 0;
+}
 
 /* Tuning options (tests, tools): see `struct Options` (ik_host.hpp).  Names: solve_kernel (0 auto, 1 quad, 2 lane64,
  * 3 general), wide_form (0 lds, 1 hbm), range_rule (of chains created afterwards), stop_x_legacy.  Not synchronised

@@ -3,6 +3,7 @@
 //
 //   ik_capi.hip        chains, options, optik_hip_ik_batch / optik_hip_ik_host, timing (the C ABI of optik_hip.h)
 //   ik_select.hip      the selection of lib.rs:397-413 over the per-restart keys
+//   ik_solutions.hip   up to K distinct solutions per target over the same keys (optik_hip_ik_solutions)
 //   ik_batch_ops.hip   objective / gradient, FK / Jacobian and seed batches, the test probes
 //   ik_lane_kernel.hip, ik_quad_kernel.hip, ik_wide_kernel.hip    the restart solvers (one restart loop each)
 #pragma once
@@ -56,6 +57,32 @@ struct SelectLaunch {
 constexpr int SEL_TILE = 4096;  // restarts per 256-thread selection block
 // per-tile argmin + per-target reduction (one kernel when a target has a single tile); T blocks publish the winners
 hipError_t select_launch(const SelectLaunch &s, int T, hipStream_t stream);
+
+// ---- the solution sets of optik_hip_ik_solutions (ik_solutions.hip) --------------------------------------------
+struct SolutionsLaunch {
+    double *out_key;         // [T*R] the launch's keys (chain scratch): a candidate that is eliminated goes to +inf
+    const double *out_x;     // [n][ld]
+    const double *out_f;     // [ld] (null when no f is wanted)
+    TileRec *tile_recs;      // [T][tiles_per_target]
+    unsigned long long *pick;  // [T] column of the solution the last round accepted, ~0 if none (multi-tile form)
+    int tiles_per_target;
+    int tile;                // restarts per tile (SEL_TILE)
+    int n;
+    int K;
+    double min_dist;
+    unsigned long long restart_begin;
+    unsigned long long n_restarts;
+    size_t ld;               // T * R
+    int32_t *count;          // [T]
+    double *x;               // [T][K][n]
+    double *f;               // [T][K]
+    unsigned long long *idx;  // [T][K]
+    double *key;             // [T][K]
+    unsigned long long *reset_queue;  // the launch's work-item counter, put back to 0 by the last kernel
+};
+// K rounds of (argmin of the surviving candidates, elimination of those within min_dist of it): one kernel when a
+// target has a single tile, otherwise a tile kernel and a per-target kernel per round
+hipError_t solutions_launch(const SolutionsLaunch &s, int T, hipStream_t stream);
 
 // ---- options ---------------------------------------------------------------------------------------------
 // Every tuning option of the kernel layer, in one place.  The defaults come from the environment ONCE, at the
@@ -152,6 +179,8 @@ struct optik_hip_chain {
     size_t tile_cap = 0;
     unsigned long long *first_success = nullptr;
     size_t fs_cap = 0;
+    unsigned long long *sol_pick = nullptr;  // optik_hip_ik_solutions: per target, the last accepted column
+    size_t sol_pick_cap = 0;
     // (what the last launch's selection kernel left behind: the work-item counter at 0, this many leading
     // first-success words at ~0 -- a launch that finds them so skips its fill commands)
     // (host-side knowledge that holds for launches ORDERED behind that selection kernel: the stream it ran on is kept

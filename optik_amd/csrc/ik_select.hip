@@ -8,22 +8,12 @@
 //                            launches, a Speed batch's rounds)
 // The last kernel of a launch also puts the launch's work-item counter and first-success words back to their
 // initial values, so that the next launch needs no fill commands in front of it.
+#include "ik_argmin.hpp"
 #include "ik_host.hpp"
 
 namespace optik {
 namespace host {
 namespace {
-
-// (key, idx) argmin across the wave: smaller key wins, ties -> smaller idx; idx ~0 = none.
-__device__ __forceinline__ void wave_argmin(double &key, unsigned long long &idx) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double okey = __shfl_xor(key, off, WAVE);
-        const unsigned long long oidx = __shfl_xor(idx, off, WAVE);
-        const bool take = (oidx != ~0ull) && (idx == ~0ull || okey < key || (okey == key && oidx < idx));
-        if (take) { key = okey; idx = oidx; }
-    }
-}
 
 // Stage 1 of the selection (lib.rs:397-413): per-block argmin of the keys of one
 // tile of one target -- wavefront shuffles, then one 16-byte record per block.

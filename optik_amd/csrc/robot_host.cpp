@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <random>
@@ -651,6 +652,25 @@ int optik_robot_ik_pose(const optik_robot *r, const CSolverConfig *config, const
 
 namespace {
 
+// targets16 [T][16] (row-major or column-major 4x4) -> [T][7] poses, the iterative or the closed-form conversion
+extern "C++" std::vector<double> targets_pose7(int32_t T, const double *targets16, bool row_major, bool iterative) {
+    std::vector<double> tgt7((size_t)T * 7);
+    parallel_ranges((size_t)T, [&](size_t t0, size_t t1) {
+        for (size_t t = t0; t < t1; ++t) {
+            const double *m = targets16 + t * 16;
+            double cm[16];
+            if (row_major) {
+                for (int a = 0; a < 4; ++a)
+                    for (int b = 0; b < 4; ++b) cm[b * 4 + a] = m[a * 4 + b];
+                m = cm;
+            }
+            if (iterative) pose7_from_mat16_iterative(m, &tgt7[t * 7]);
+            else pose7_from_mat16(m, &tgt7[t * 7]);
+        }
+    });
+    return tgt7;
+}
+
 // optik_robot_ik_batch_ex for the targets of one GPU: rounds of `round` restart indices per
 // target (sizes: see the loop), each round ONE launch of optik_hip_ik_batch (which picks the solver by
 // launch size); targets already solved (Speed) drop out of later rounds; max_time is enforced inside a
@@ -671,21 +691,8 @@ int ik_batch_on_device(const optik_robot *r, DeviceCtx *c, const CSolverConfig *
     optik::DeviceScope dev_scope(c->device);
     if (!dev_scope.ok()) { err = "hipSetDevice failed"; return -1; }
 
-    std::vector<double> tgt7((size_t)T * 7), best_key((size_t)T, 0.0);
+    std::vector<double> tgt7 = targets_pose7(T, targets16, row_major, iterative), best_key((size_t)T, 0.0);
     std::vector<uint64_t> best_idx((size_t)T, UINT64_MAX);
-    parallel_ranges((size_t)T, [&](size_t t0, size_t t1) {
-        for (size_t t = t0; t < t1; ++t) {
-            const double *m = targets16 + t * 16;
-            double cm[16];
-            if (row_major) {
-                for (int a = 0; a < 4; ++a)
-                    for (int b = 0; b < 4; ++b) cm[b * 4 + a] = m[a * 4 + b];
-                m = cm;
-            }
-            if (iterative) pose7_from_mat16_iterative(m, &tgt7[t * 7]);
-            else pose7_from_mat16(m, &tgt7[t * 7]);
-        }
-    });
     std::vector<int> live((size_t)T);
     for (int t = 0; t < T; ++t) live[t] = t;
     for (int t = 0; t < T; ++t) if (found_out) found_out[t] = 0;
@@ -811,10 +818,11 @@ int optik_robot_ik_batch_ex(const optik_robot *r, const CSolverConfig *config, i
     return optik_robot_ik_batch_poses(r, config, T, targets16, OPTIK_POSE_FROM_MATRIX, x0, ee16, x_out, f_out, found_out);
 }
 
-int optik_robot_ik_batch_poses(const optik_robot *r, const CSolverConfig *config, int32_t T,
-                               const double *targets16, uint32_t flags, const double *x0, const double *ee16,
-                               double *x_out, double *f_out, int32_t *found_out) {
-    if (!r || !config || !targets16 || !x0 || T < 1) return set_err(-1, "bad argument");
+namespace {
+
+// The host-side checks of a batch of targets (optik_robot_ik_batch_poses, optik_robot_ik_solutions): with
+// OPTIK_BATCH_VALIDATE_POSES every target's isometry test (-3), then every seed against the joint limits (-2).
+extern "C++" int check_batch_inputs(const optik_robot *r, int32_t T, const double *targets16, uint32_t flags, const double *x0) {
     const int n = r->n;
     const bool row_major = (flags & OPTIK_BATCH_ROW_MAJOR) != 0;
     if (flags & OPTIK_BATCH_VALIDATE_POSES) {
@@ -848,9 +856,13 @@ int optik_robot_ik_batch_poses(const optik_robot *r, const CSolverConfig *config
         for (int i = 0; i < n; ++i)
             if (x0[(size_t)t * n + i] < r->lb[i] || x0[(size_t)t * n + i] > r->ub[i])
                 return set_err(-2, "seed joint position outside of joint limits");
-    double ee7[7];
-    if (ee16) pose7_from_mat16(ee16, ee7);
-    const auto start = std::chrono::steady_clock::now();
+    return 0;
+}
+
+// fn(ctx, t0, t1, err) -> rc for one contiguous part [t0, t1) of the T targets per device of the robot, each part
+// on its own host thread; last_parts is set.  0, or -1 with the first failing part's message.
+extern "C++" template <class Fn>
+int run_device_parts(const optik_robot *r, int32_t T, Fn fn) {
     size_t G = device_count(r);
     if (G > (size_t)T) G = (size_t)T;
     struct Part { DeviceCtx *ctx; int32_t t0, t1; int rc; std::string err; };
@@ -862,13 +874,7 @@ int optik_robot_ik_batch_poses(const optik_robot *r, const CSolverConfig *config
         parts.push_back(p);
     }
     r->last_parts.store((int32_t)parts.size());
-    auto run_part = [&](Part &p) {
-        p.rc = ik_batch_on_device(r, p.ctx, config, p.t1 - p.t0, targets16 + (size_t)p.t0 * 16, row_major,
-                                  (flags & OPTIK_POSE_FROM_MATRIX) != 0,
-                                  x0 + (size_t)p.t0 * n, ee16 ? ee7 : nullptr, start,
-                                  x_out ? x_out + (size_t)p.t0 * n : nullptr, f_out ? f_out + p.t0 : nullptr,
-                                  found_out ? found_out + p.t0 : nullptr, p.err);
-    };
+    auto run_part = [&](Part &p) { p.rc = fn(p.ctx, p.t0, p.t1, p.err); };
     if (parts.size() == 1) {
         run_part(parts[0]);
     } else {
@@ -880,6 +886,134 @@ int optik_robot_ik_batch_poses(const optik_robot *r, const CSolverConfig *config
     for (const Part &p : parts)
         if (p.rc) return set_err(-1, p.err);
     return 0;
+}
+
+}  // namespace
+
+int optik_robot_ik_batch_poses(const optik_robot *r, const CSolverConfig *config, int32_t T,
+                               const double *targets16, uint32_t flags, const double *x0, const double *ee16,
+                               double *x_out, double *f_out, int32_t *found_out) {
+    if (!r || !config || !targets16 || !x0 || T < 1) return set_err(-1, "bad argument");
+    const int n = r->n;
+    const bool row_major = (flags & OPTIK_BATCH_ROW_MAJOR) != 0;
+    if (int rc = check_batch_inputs(r, T, targets16, flags, x0)) return rc;
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    const auto start = std::chrono::steady_clock::now();
+    return run_device_parts(r, T, [&](DeviceCtx *ctx, int32_t t0, int32_t t1, std::string &err) {
+        return ik_batch_on_device(r, ctx, config, t1 - t0, targets16 + (size_t)t0 * 16, row_major,
+                                  (flags & OPTIK_POSE_FROM_MATRIX) != 0,
+                                  x0 + (size_t)t0 * n, ee16 ? ee7 : nullptr, start,
+                                  x_out ? x_out + (size_t)t0 * n : nullptr, f_out ? f_out + t0 : nullptr,
+                                  found_out ? found_out + t0 : nullptr, err);
+    });
+}
+
+namespace {
+
+// optik_robot_ik_solutions for the targets of one GPU: chunks of whole targets, each ONE launch of
+// optik_hip_ik_solutions over every restart index [0, R) (about 4 M work items a launch at most, as the rounds of
+// ik_batch_on_device).  A chunk that starts after the max_time budget is spent is not run: its targets keep count 0.
+extern "C++" int ik_solutions_on_device(const optik_robot *r, DeviceCtx *c, const CSolverConfig *config, int32_t T,
+                           const double *targets16, bool row_major, bool iterative, const double *x0,
+                           const double *ee7, std::chrono::steady_clock::time_point start, int32_t K, double min_dist,
+                           int32_t *count_out, double *x_out, double *f_out, uint64_t *idx_out, std::string &err) {
+    const int n = r->n;
+    const uint64_t R = config->max_restarts;
+    const uint64_t round_items = (uint64_t)4 << 20;
+    const size_t chunk = (size_t)std::min<uint64_t>((uint64_t)T, std::max<uint64_t>(1, round_items / R));
+    std::lock_guard<std::mutex> lock(c->batch_mu);
+    optik::DeviceScope dev_scope(c->device);
+    if (!dev_scope.ok()) { err = "hipSetDevice failed"; return -1; }
+    const std::vector<double> tgt7 = targets_pose7(T, targets16, row_major, iterative);
+
+    // the robot's batch block: in = targets [C][7] | x0 [C][n]; out = x [C][K][n] | f [C][K] | idx [C][K] | count [C]
+    const size_t KC = (size_t)K * chunk;
+    const size_t n_in = (size_t)(7 + n) * chunk, n_out = KC * (size_t)(n + 2) + chunk;
+    if (n_in + n_out > c->batch_cap) {
+        if (c->d_batch) (void)hipFree(c->d_batch);
+        if (c->h_batch) (void)hipHostFree(c->h_batch);
+        c->d_batch = nullptr; c->h_batch = nullptr; c->batch_cap = 0;
+        if (hipMalloc(&c->d_batch, sizeof(double) * (n_in + n_out)) != hipSuccess
+            || hipHostMalloc(&c->h_batch, sizeof(double) * (n_in + n_out)) != hipSuccess) {
+            err = "batch workspace allocation failed";
+            return -1;
+        }
+        c->batch_cap = n_in + n_out;
+    }
+    for (size_t t0 = 0; t0 < (size_t)T; t0 += chunk) {
+        const size_t L = std::min(chunk, (size_t)T - t0), KL = (size_t)K * L;
+        double deadline = 0.0;
+        if (config->max_time > 0.0) {
+            deadline = config->max_time - std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+            if (deadline <= 0.0) break;  // (the targets left keep count 0)
+        }
+        double *h_t = c->h_batch, *h_out = h_t + (size_t)(7 + n) * L;
+        double *d_t = c->d_batch, *d_x0 = d_t + 7 * L, *d_x = d_x0 + (size_t)n * L, *d_f = d_x + KL * (size_t)n;
+        uint64_t *d_idx = reinterpret_cast<uint64_t *>(d_f + KL);
+        int32_t *d_count = reinterpret_cast<int32_t *>(d_idx + KL);
+        std::memcpy(h_t, &tgt7[t0 * 7], sizeof(double) * 7 * L);
+        std::memcpy(h_t + 7 * L, x0 + t0 * (size_t)n, sizeof(double) * (size_t)n * L);
+        if (hipMemcpyAsync(d_t, h_t, sizeof(double) * (size_t)(7 + n) * L, hipMemcpyHostToDevice, nullptr) != hipSuccess) {
+            err = "upload failed";
+            return -1;
+        }
+        optik_hip_ik_solutions_outputs o;
+        o.d_count = d_count; o.d_x = d_x; o.d_f = d_f; o.d_idx = d_idx; o.d_key = nullptr;
+        if (optik_hip_ik_solutions(c->chain, config, d_t, d_x0, (int32_t)L, ee7, 0, R, deadline, K, min_dist, &o,
+                                   nullptr)) {
+            err = optik_hip_last_error();
+            return -1;
+        }
+        const size_t out_doubles = KL * (size_t)(n + 2) + L;
+        if (hipMemcpyAsync(h_out, d_x, sizeof(double) * out_doubles, hipMemcpyDeviceToHost, nullptr) != hipSuccess
+            || hipStreamSynchronize(nullptr) != hipSuccess) {
+            err = "download failed";
+            return -1;
+        }
+        const double *hx = h_out, *hf = hx + KL * (size_t)n;
+        const uint64_t *hi = reinterpret_cast<const uint64_t *>(hf + KL);
+        const int32_t *hc = reinterpret_cast<const int32_t *>(hi + KL);
+        if (x_out) std::memcpy(x_out + t0 * (size_t)K * n, hx, sizeof(double) * KL * (size_t)n);
+        if (f_out) std::memcpy(f_out + t0 * (size_t)K, hf, sizeof(double) * KL);
+        if (idx_out) std::memcpy(idx_out + t0 * (size_t)K, hi, sizeof(uint64_t) * KL);
+        if (count_out) std::memcpy(count_out + t0, hc, sizeof(int32_t) * L);
+    }
+    return 0;
+}
+
+}  // namespace
+
+int optik_robot_ik_solutions(const optik_robot *r, const CSolverConfig *config, int32_t T, const double *targets16,
+                             uint32_t flags, const double *x0, const double *ee16, int32_t K, double min_dist,
+                             int32_t *count_out, double *x_out, double *f_out, uint64_t *idx_out) {
+    if (!r || !config || !targets16 || !x0 || T < 1) return set_err(-1, "bad argument");
+    if (K < 1 || K > OPTIK_HIP_MAX_SOLUTIONS) return set_err(-1, "ik_solutions: K must be in 1..256");
+    if (!(min_dist >= 0.0) || !std::isfinite(min_dist))
+        return set_err(-1, "ik_solutions: min_dist must be finite and >= 0");
+    if (config->max_restarts == 0)
+        return set_err(-1, "ik_solutions: max_restarts must be set (every restart index in [0, max_restarts) runs)");
+    if (config->max_restarts > OPTIK_ROBOT_MAX_SOLUTION_RESTARTS)
+        return set_err(-1, "ik_solutions: max_restarts must be at most 2^22");
+    const int n = r->n;
+    if (int rc = check_batch_inputs(r, T, targets16, flags, x0)) return rc;
+    // (slots of targets whose chunk is never run stay padding)
+    const size_t TK = (size_t)T * (size_t)K;
+    if (count_out) std::fill(count_out, count_out + T, 0);
+    if (x_out) std::fill(x_out, x_out + TK * (size_t)n, std::numeric_limits<double>::quiet_NaN());
+    if (f_out) std::fill(f_out, f_out + TK, std::numeric_limits<double>::quiet_NaN());
+    if (idx_out) std::fill(idx_out, idx_out + TK, UINT64_MAX);
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    const auto start = std::chrono::steady_clock::now();
+    return run_device_parts(r, T, [&](DeviceCtx *ctx, int32_t t0, int32_t t1, std::string &err) {
+        return ik_solutions_on_device(r, ctx, config, t1 - t0, targets16 + (size_t)t0 * 16,
+                                      (flags & OPTIK_BATCH_ROW_MAJOR) != 0, (flags & OPTIK_POSE_FROM_MATRIX) != 0,
+                                      x0 + (size_t)t0 * n, ee16 ? ee7 : nullptr, start, K, min_dist,
+                                      count_out ? count_out + t0 : nullptr, x_out ? x_out + (size_t)t0 * K * n : nullptr,
+                                      f_out ? f_out + (size_t)t0 * K : nullptr,
+                                      idx_out ? idx_out + (size_t)t0 * K : nullptr, err);
+    });
 }
 
 const double *optik_robot_ik(const optik_robot *r, const CSolverConfig *config, const double *target,

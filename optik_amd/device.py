@@ -149,6 +149,38 @@ class HipChain:
             _stream_ptr()))
         return bufs
 
+    def ik_solutions(self, cfg, targets, x0, restart_begin, restart_end, k, min_dist, deadline_s=0.0,
+                     ee_offset7=None, bufs=None):
+        """Up to k distinct solutions per target (optik_hip_ik_solutions): every restart of [restart_begin,
+        restart_end) runs to its end, the successes are taken in (key, index) order and kept if their largest joint
+        difference to every solution kept before is > min_dist.  targets [T, 7], x0 [T, n] float64 cuda tensors.
+        Stream-ordered on the current stream; returns a dict of device tensors: count [T] int32, x [T, k, n],
+        f [T, k], idx [T, k] int64 (-1 past count), key [T, k] (+inf past count)."""
+        k, min_dist = nat.check_solutions_args(k, min_dist)
+        if not (targets.is_cuda and targets.dtype == torch.float64 and targets.is_contiguous()
+                and targets.dim() == 2 and targets.shape[1] == 7):
+            raise ValueError("targets must be a contiguous float64 cuda tensor [T, 7]")
+        T = targets.shape[0]
+        if not (x0.is_cuda and x0.dtype == torch.float64 and x0.is_contiguous() and tuple(x0.shape) == (T, self.n)):
+            raise ValueError(f"x0 must be a contiguous float64 cuda tensor [T, n] = [{T}, {self.n}]")
+        if int(restart_end) <= int(restart_begin) or int(restart_begin) < 0:
+            raise ValueError("empty restart range")
+        if bufs is None:
+            dev = targets.device
+            bufs = dict(count=torch.empty(T, dtype=torch.int32, device=dev),
+                        x=torch.empty((T, k, self.n), dtype=torch.float64, device=dev),
+                        f=torch.empty((T, k), dtype=torch.float64, device=dev),
+                        idx=torch.empty((T, k), dtype=torch.int64, device=dev),
+                        key=torch.empty((T, k), dtype=torch.float64, device=dev))
+        o = nat.IkSolutionsOutputs()
+        o.d_count, o.d_x, o.d_f = _ptr(bufs.get("count")), _ptr(bufs.get("x")), _ptr(bufs.get("f"))
+        o.d_idx, o.d_key = _ptr(bufs.get("idx")), _ptr(bufs.get("key"))
+        ee = np.ascontiguousarray(ee_offset7, dtype=np.float64) if ee_offset7 is not None else None
+        nat.check(nat.lib().optik_hip_ik_solutions(
+            self._h, C.byref(cfg), _ptr(targets), _ptr(x0), T, _dp(ee) if ee is not None else None,
+            int(restart_begin), int(restart_end), float(deadline_s), k, min_dist, C.byref(o), _stream_ptr()))
+        return bufs
+
     def ik_host(self, cfg, targets, x0, restart_begin, restart_end, flags=0, deadline_s=0.0, ee_offset7=None):
         """optik_hip_ik_host: host arrays in (targets [T, 7], x0 [T, n]), the winners back as numpy arrays; blocking.
         With IK_EARLY_EXIT | IK_FIND_ANY and one target the call returns when the first restart has succeeded."""

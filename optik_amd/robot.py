@@ -33,6 +33,9 @@ def _bind(L):
                                           C.POINTER(C.c_int32)]
     L.optik_robot_ik_batch_poses.argtypes = [vp, C.POINTER(nat.SolverConfigC), C.c_int32, dp, C.c_uint32, dp, dp,
                                              dp, dp, C.POINTER(C.c_int32)]
+    L.optik_robot_ik_solutions.argtypes = [vp, C.POINTER(nat.SolverConfigC), C.c_int32, dp, C.c_uint32, dp, dp,
+                                           C.c_int32, C.c_double, C.POINTER(C.c_int32), dp, dp,
+                                           C.POINTER(C.c_uint64)]
     L.optik_robot_fk_ex.argtypes = [vp, dp, dp, dp]
     L.optik_robot_diff_ik_ex.argtypes = [vp, dp, dp, dp, dp, C.POINTER(C.c_double), dp]
     L.optik_robot_diff_ik_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_int32)]
@@ -264,6 +267,58 @@ class Robot:
         finally:
             if pause:
                 gc.enable()
+
+    def ik_solutions_batch_arrays(self, config: SolverConfig, targets, x0s, k=8, min_dist=0.1, ee_offset=None):
+        """Up to k distinct solutions per target (extension; include/optik.h: optik_robot_ik_solutions), array form:
+        `targets` [T, 4, 4] row-major poses, `x0s` [T, n] seeds -> (x [T, k, n], c [T, k], idx [T, k] int64,
+        count [T]).  Every restart index in [0, config.max_restarts) runs to its end; the successes are taken best
+        first (Quality: nearest to the seed, Speed: lowest index), each kept only if its largest joint difference to
+        every solution kept before it is > min_dist.  Slots past count: x and c NaN, idx -1.  On a redundant arm the
+        successes form a continuum and min_dist sets the spacing of the returned samples."""
+        k, min_dist = nat.check_solutions_args(k, min_dist)
+        R = config.max_restarts
+        if R <= 0 or R >= U64_MAX:
+            raise ValueError("ik_solutions needs a finite max_restarts: every restart index in [0, max_restarts) runs")
+        if R > nat.MAX_SOLUTION_RESTARTS:
+            raise ValueError(f"ik_solutions: max_restarts must be at most {nat.MAX_SOLUTION_RESTARTS}")
+        tg = np.asarray(targets, dtype=np.float64)
+        if tg.ndim != 3 or tg.shape[1:] != (4, 4) or tg.shape[0] < 1:
+            raise ValueError("targets must be [T, 4, 4]")
+        T = tg.shape[0]
+        n = self.num_positions()
+        x0s = np.asarray(x0s, dtype=np.float64)
+        if x0s.shape != (T, n):
+            raise ValueError(f"x0s must be [T, n] = [{T}, {n}], got {list(x0s.shape)}")
+        x0s = np.ascontiguousarray(x0s)
+        tg16 = np.ascontiguousarray(tg).reshape(T, 16)
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        cfg = config.to_c()
+        x = np.empty((T, k, n))
+        f = np.empty((T, k))
+        idx = np.empty((T, k), dtype=np.uint64)
+        count = np.empty(T, dtype=np.int32)
+        rc = self._L.optik_robot_ik_solutions(self._h, C.byref(cfg), T, _dp(tg16), BATCH_ROW_MAJOR | BATCH_VALIDATE_POSES,
+                                              _dp(x0s), _dp(ee) if ee is not None else None, k, min_dist,
+                                              count.ctypes.data_as(C.POINTER(C.c_int32)), _dp(x), _dp(f),
+                                              idx.ctypes.data_as(C.POINTER(C.c_uint64)))
+        if rc == -3:
+            raise ValueError(_err(self._L))
+        if rc < 0:
+            raise RuntimeError(_err(self._L))
+        return x, f, idx.view(np.int64), count
+
+    def ik_solutions(self, config: SolverConfig, target, x0, k=8, min_dist=0.1, ee_offset=None, return_index=False):
+        """Up to k distinct solutions of one target, best first: a list of (x, c) (or (x, c, restart index)),
+        empty when no restart succeeded.  See ik_solutions_batch_arrays."""
+        x0 = self._check_x(x0)
+        tgt = np.asarray(target, dtype=np.float64)
+        _pose16(tgt)  # (the single call's checks and messages)
+        x, f, idx, count = self.ik_solutions_batch_arrays(config, tgt[None], x0[None], k, min_dist, ee_offset)
+        m = int(count[0])
+        xs, fs, ids = x[0, :m].tolist(), f[0, :m].tolist(), idx[0, :m].tolist()
+        if return_index:
+            return [(xs[i], fs[i], ids[i]) for i in range(m)]
+        return [(xs[i], fs[i]) for i in range(m)]
 
     def diff_ik(self, x0, V_WE, v_max, ee_offset=None):
         """Returns (alpha, v) or None (optik.pyi:43-49; lib.rs:123-239): the joint velocities
