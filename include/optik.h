@@ -116,6 +116,24 @@ int optik_robot_ik_solutions(const optik_robot *robot, const CSolverConfig *conf
                              const double *targets16, uint32_t flags, const double *x0, const double *ee16,
                              int32_t K, double min_dist, int32_t *count_out, double *x_out /* [T][K][n] */,
                              double *f_out /* [T][K] */, uint64_t *idx_out /* [T][K] */);
+/* Warm-started IK along P paths of L waypoints each (extension; optik_hip_ik_path): waypoint l of path p is solved
+ * over restarts [0, config->max_restarts) from the path's current configuration c_p (first x0[p], then the last
+ * accepted solution).  The accepted solution is the best success -- Quality: nearest to c_p, Speed: lowest index --
+ * among those with max_i |x_i - c_i| <= max_step (+inf: every success; no angle wrapping).  A waypoint without one
+ * keeps c_p and gives x and f NaN, idx UINT64_MAX, step NaN, found 0.  Speed with max_step = +inf equals a host loop
+ * of ik() seeded from the previous result (set_parallelism(1), max_time = 0).  targets16 [P][L][16], flags as in
+ * optik_robot_ik_batch_poses (rc -3: invalid transform; -2: a start configuration outside the limits), x0 [P][n] ->
+ * path-major x_out [P][L][n], f_out, idx_out, step_out (max_i |x_i - c_i| against the configuration the waypoint was
+ * solved from), found_out [P][L]; any output may be NULL.  Refused (-1) before any GPU work: max_restarts = 0
+ * (unlimited) or above OPTIK_HIP_PATH_MAX_RESTARTS (4096), a NaN or negative max_step.  max_time, if set, is each
+ * waypoint launch's deadline (not a budget for the call).  The paths are cut into one contiguous part per device
+ * and each part into chunks of whole paths (a waypoint launch of about 4 M items at most): one upload, one
+ * optik_hip_ik_path over every waypoint and one download per chunk.  The result depends on neither. */
+int optik_robot_ik_path(const optik_robot *robot, const CSolverConfig *config, int32_t P, int32_t L,
+                        const double *targets16 /* [P][L][16] */, uint32_t flags, const double *x0 /* [P][n] */,
+                        const double *ee16, double max_step, double *x_out /* [P][L][n] */,
+                        double *f_out /* [P][L] */, uint64_t *idx_out /* [P][L] */, double *step_out /* [P][L] */,
+                        int32_t *found_out /* [P][L] */);
 /* GPUs of this node the robot spreads its work over (restarts shard trivially: lib.rs:297-300
  * hands the same index range to rayon workers).  optik_robot_ik / _ik_ex: after the
  * latency-sized first launch every round's restart range is cut into one contiguous part per

@@ -201,6 +201,35 @@ int optik_hip_ik_solutions(optik_hip_chain *chain, const optik_solver_config *cf
                            uint64_t restart_begin, uint64_t restart_end, double deadline_s,
                            int32_t K, double min_dist, const optik_hip_ik_solutions_outputs *out, void *stream);
 
+/* P independent paths of L waypoints, each waypoint solved from the previous one's solution (warm start).  Path p
+ * carries a seed c_p, first d_x0[p].  Waypoint l of path p runs restarts restart_begin..restart_end-1 with seed c_p
+ * (restart 0 = c_p; Quality's key = ||x - c_p||_2).  The candidates are its successful restarts (lib.rs:376-379)
+ * whose max_i |x_i - c_i| (no angle wrapping) is <= max_step (+inf: every success); the accepted solution is their
+ * (key, restart index) minimum, as in optik_hip_ik_batch.  c_p then becomes the accepted solution; a waypoint with no
+ * candidate leaves c_p unchanged and its outputs x, f, step NaN, idx UINT64_MAX, key +inf.
+ * Schedule: Speed with max_step = +inf runs with early exit under the deterministic rule, and every waypoint equals
+ * optik_hip_ik_batch(EARLY_EXIT) with d_x0 = c, bit for bit; Speed with a finite max_step and Quality run every
+ * restart to its end.  The result does not depend on the solver, the launch size or timing (deadline_s excepted: it
+ * applies to each waypoint's launch, as in optik_hip_ik_batch).
+ * d_targets [L][P][7] (waypoint-major); d_x0 [P][n].  flags: 0 or OPTIK_HIP_IK_RESTART_MAJOR (hand-out order only).
+ * Refused: R = restart_end - restart_begin outside 1..OPTIK_HIP_PATH_MAX_RESTARTS (one selection block per path;
+ * warm-started paths need few restarts), other flags, a NaN or negative max_step, P or L < 1, and whatever
+ * optik_hip_ik_batch refuses.  Stream-ordered, with no host synchronisation between waypoints: per waypoint one
+ * solver launch and one selection kernel; holds the chain for the whole call and uses its launch workspace. */
+#define OPTIK_HIP_PATH_MAX_RESTARTS 4096
+typedef struct optik_hip_ik_path_outputs {
+    double *d_x;      /* [L][P][n]  NaN where no solution           */
+    double *d_f;      /* [L][P]     the restart's returned objective */
+    uint64_t *d_idx;  /* [L][P]     UINT64_MAX where no solution    */
+    double *d_key;    /* [L][P]     +inf where no solution          */
+    double *d_step;   /* [L][P]     max_i |x_i - c_i|; NaN where no solution */
+    double *d_last;   /* [P][n]     each path's final seed c_p       */
+} optik_hip_ik_path_outputs;
+int optik_hip_ik_path(optik_hip_chain *chain, const optik_solver_config *cfg, const double *d_targets,
+                      const double *d_x0, int32_t P, int32_t L, const double *ee_offset7, uint64_t restart_begin,
+                      uint64_t restart_end, uint32_t flags, double deadline_s, double max_step,
+                      const optik_hip_ik_path_outputs *out, void *stream);
+
 /* Tuning options of the kernel layer (diagnostics: tests and tools; the defaults are what the product runs with).
  * Each option's default comes from the environment variable named with it, read ONCE when the library first needs
  * an option; afterwards only this call changes it.  Not synchronised with calls in flight.

@@ -74,6 +74,23 @@ def check_solutions_args(k, min_dist):
     return int(k), min_dist
 
 
+class IkPathOutputs(C.Structure):
+    """optik_hip_ik_path_outputs (include/optik_hip.h)."""
+    _fields_ = [("d_x", C.c_void_p), ("d_f", C.c_void_p), ("d_idx", C.c_void_p), ("d_key", C.c_void_p),
+                ("d_step", C.c_void_p), ("d_last", C.c_void_p)]
+
+
+PATH_MAX_RESTARTS = 4096  # OPTIK_HIP_PATH_MAX_RESTARTS
+
+
+def check_max_step(max_step):
+    """The max_step rule of optik_hip_ik_path, checked on the host: >= 0, +inf for no limit; as float."""
+    max_step = float(max_step)
+    if not max_step >= 0.0:
+        raise ValueError(f"max_step must be >= 0 (+inf: no limit), got {max_step!r}")
+    return max_step
+
+
 class LaunchInfo(C.Structure):
     _fields_ = [("grid", C.c_int32), ("block", C.c_int32), ("lds_bytes", C.c_int32),
                 ("tiles", C.c_int32), ("kernel_ms", C.c_float)]
@@ -113,6 +130,8 @@ def lib():
     L.optik_hip_ik_solutions.argtypes = [vp, C.POINTER(SolverConfigC), vp, vp, C.c_int32, dp, C.c_uint64,
                                          C.c_uint64, C.c_double, C.c_int32, C.c_double,
                                          C.POINTER(IkSolutionsOutputs), vp]
+    L.optik_hip_ik_path.argtypes = [vp, C.POINTER(SolverConfigC), vp, vp, C.c_int32, C.c_int32, dp, C.c_uint64,
+                                    C.c_uint64, C.c_uint32, C.c_double, C.c_double, C.POINTER(IkPathOutputs), vp]
     L.optik_hip_ik_host.argtypes = [vp, C.POINTER(SolverConfigC), dp, dp, C.c_int32, dp,
                                     C.c_uint64, C.c_uint64, C.c_uint32, C.c_double, dp, dp,
                                     C.POINTER(C.c_uint64), dp]

@@ -1,5 +1,5 @@
-// ik_argmin.hpp -- the (key, restart index) order of the selection kernels (ik_select.hip, ik_solutions.hip):
-// the smaller key first, ties to the smaller index; index ~0 = no entry.
+// ik_argmin.hpp -- the (key, restart index) order of the selection kernels (ik_select.hip, ik_solutions.hip,
+// ik_path.hip): the smaller key first, ties to the smaller index; index ~0 = no entry.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -20,6 +20,22 @@ __device__ __forceinline__ void wave_argmin(double &key, unsigned long long &idx
         const unsigned long long oidx = __shfl_xor(idx, off, 64);
         if (argmin_takes(key, idx, okey, oidx)) { key = okey; idx = oidx; }
     }
+}
+
+// The argmin of a BLOCK-thread block (BLOCK / 64 waves); every thread ends with it.  s_key / s_idx: BLOCK / 64
+// shared entries, free again on return.
+template <int BLOCK>
+__device__ __forceinline__ void block_argmin(double &key, unsigned long long &idx, double *s_key,
+                                             unsigned long long *s_idx) {
+    wave_argmin(key, idx);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { s_key[wave] = key; s_idx[wave] = idx; }
+    __syncthreads();
+    key = s_key[0];
+    idx = s_idx[0];
+    for (int w = 1; w < BLOCK / 64; ++w)
+        if (argmin_takes(key, idx, s_key[w], s_idx[w])) { key = s_key[w]; idx = s_idx[w]; }
+    __syncthreads();
 }
 
 }  // namespace host

@@ -1,10 +1,11 @@
 // ik_capi.hip -- the C ABI of include/optik_hip.h: chains, tuning options, the restart launch (optik_hip_ik_batch),
-// its host-buffer form (optik_hip_ik_host), the solution sets (optik_hip_ik_solutions), timing.
+// its host-buffer form (optik_hip_ik_host), the solution sets (optik_hip_ik_solutions), warm-started paths
+// (optik_hip_ik_path), timing.
 //
 // The solvers are launched from here and defined in their own translation units: the lane-per-restart form
 // (ik_lane_kernel.hip), the quad solver (ik_quad_kernel.hip), the general run-time-n solver (ik_wide_kernel.hip);
-// optik_hip_ik_batch picks one by launch size and joint count.  The selection kernels: ik_select.hip and
-// ik_solutions.hip; the batch operators: ik_batch_ops.hip.  No CPU fallback exists: every entry point fails loudly without a device.
+// optik_hip_ik_batch picks one by launch size and joint count.  The selection kernels: ik_select.hip,
+// ik_solutions.hip and ik_path.hip; the batch operators: ik_batch_ops.hip.  No CPU fallback exists: every entry point fails loudly without a device.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -167,6 +168,7 @@ void optik_hip_chain_destroy(optik_hip_chain *ch) {
     if (ch->tile_recs) hipFree(ch->tile_recs);
     if (ch->first_success) hipFree(ch->first_success);
     if (ch->sol_pick) hipFree(ch->sol_pick);
+    if (ch->path_carry) hipFree(ch->path_carry);
     if (ch->tmp_x) hipFree(ch->tmp_x);
     if (ch->tmp_f) hipFree(ch->tmp_f);
     if (ch->tmp_key) hipFree(ch->tmp_key);
@@ -570,6 +572,73 @@ int optik_hip_ik_solutions(optik_hip_chain *ch, const optik_solver_config *cfg, 
     ch->queue_clean = true;
     ch->fs_clean = sl.fs_clean_after;
     ch->clean_stream = stream;
+    return 0;
+}
+
+int optik_hip_ik_path(optik_hip_chain *ch, const optik_solver_config *cfg, const double *d_targets,
+                      const double *d_x0, int32_t P, int32_t L, const double *ee_offset7, uint64_t restart_begin,
+                      uint64_t restart_end, uint32_t flags, double deadline_s, double max_step,
+                      const optik_hip_ik_path_outputs *out, void *stream_v) {
+    if (!ch || !cfg || !d_targets || !d_x0 || !out || P < 1 || L < 1) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    if (restart_end <= restart_begin) return fail(OPTIK_HIP_EINVAL, "empty restart range");
+    if (restart_end - restart_begin > (uint64_t)OPTIK_HIP_PATH_MAX_RESTARTS)
+        return fail(OPTIK_HIP_EINVAL, "ik_path: at most 4096 restarts per waypoint (one selection block per path)");
+    if (flags & ~(uint32_t)OPTIK_HIP_IK_RESTART_MAJOR)
+        return fail(OPTIK_HIP_EINVAL, "ik_path: flags may only hold OPTIK_HIP_IK_RESTART_MAJOR");
+    if (!(max_step >= 0.0)) return fail(OPTIK_HIP_EINVAL, "ik_path: max_step must be >= 0 (+inf: no limit)");
+    std::lock_guard<std::mutex> lock(ch->mu);
+    hipStream_t stream = (hipStream_t)stream_v;
+    const int n = ch->n;
+    const bool filter = max_step < __builtin_huge_val();
+    // Speed without a step limit: the deterministic early exit, whose winner is the lowest successful index -- the
+    // filter cannot reject it.  With a limit (and in Quality) every restart runs to its end: early exit could abandon
+    // the one restart that passes the filter.
+    const uint32_t solve_flags = flags | ((cfg->solution_mode == 2 && !filter) ? OPTIK_HIP_IK_EARLY_EXIT : 0u);
+    {
+        BIND_DEVICE(ch);
+        const size_t need = (size_t)P * (size_t)n;
+        if (need > ch->path_carry_cap) {
+            if (ch->path_carry) HIP_TRY(hipFree(ch->path_carry));
+            ch->path_carry = nullptr; ch->path_carry_cap = 0;
+            HIP_TRY(hipMalloc(&ch->path_carry, sizeof(double) * need));
+            ch->path_carry_cap = need;
+        }
+    }
+    optik_hip_ik_outputs none;
+    std::memset(&none, 0, sizeof none);
+    for (int32_t l = 0; l < L; ++l) {
+        const double *seed = l == 0 ? d_x0 : ch->path_carry;
+        SolvedLaunch sl;
+        if (int rc = solve_locked(ch, cfg, d_targets + (size_t)l * (size_t)P * 7, seed, P, ee_offset7, restart_begin,
+                                  restart_end, solve_flags, deadline_s, &none, true, true, out->d_f != nullptr, stream,
+                                  false, nullptr, &sl))
+            return rc;
+        BIND_DEVICE(ch);
+        const size_t w = (size_t)l * (size_t)P;
+        PathSelectLaunch s;
+        std::memset(&s, 0, sizeof s);
+        s.out_key = sl.pk; s.out_x = sl.px; s.out_f = sl.pf;
+        s.seed = seed;
+        s.carry = ch->path_carry;
+        s.last = l + 1 == L ? out->d_last : nullptr;
+        s.n = n;
+        s.filter = filter ? 1 : 0;
+        s.max_step = max_step;
+        s.restart_begin = restart_begin;
+        s.n_restarts = sl.R;
+        s.ld = sl.cols;
+        s.x = out->d_x ? out->d_x + w * (size_t)n : nullptr;
+        s.f = out->d_f ? out->d_f + w : nullptr;
+        s.idx = out->d_idx ? (unsigned long long *)out->d_idx + w : nullptr;
+        s.key = out->d_key ? out->d_key + w : nullptr;
+        s.step = out->d_step ? out->d_step + w : nullptr;
+        s.reset_queue = ch->queue;
+        s.reset_fs = sl.early ? ch->first_success : nullptr;
+        HIP_TRY(path_select_launch(s, P, stream));
+        ch->queue_clean = true;
+        ch->fs_clean = sl.fs_clean_after;
+        ch->clean_stream = stream;
+    }
     return 0;
 }
 

@@ -4,6 +4,7 @@
 //   ik_capi.hip        chains, options, optik_hip_ik_batch / optik_hip_ik_host, timing (the C ABI of optik_hip.h)
 //   ik_select.hip      the selection of lib.rs:397-413 over the per-restart keys
 //   ik_solutions.hip   up to K distinct solutions per target over the same keys (optik_hip_ik_solutions)
+//   ik_path.hip        the per-waypoint selection of warm-started paths (optik_hip_ik_path)
 //   ik_batch_ops.hip   objective / gradient, FK / Jacobian and seed batches, the test probes
 //   ik_lane_kernel.hip, ik_quad_kernel.hip, ik_wide_kernel.hip    the restart solvers (one restart loop each)
 #pragma once
@@ -55,6 +56,7 @@ struct SelectLaunch {
     unsigned long long *reset_fs;  // [T]
 };
 constexpr int SEL_TILE = 4096;  // restarts per 256-thread selection block
+static_assert(OPTIK_HIP_PATH_MAX_RESTARTS <= SEL_TILE, "ik_path selects each path's restarts in one block");
 // per-tile argmin + per-target reduction (one kernel when a target has a single tile); T blocks publish the winners
 hipError_t select_launch(const SelectLaunch &s, int T, hipStream_t stream);
 
@@ -83,6 +85,31 @@ struct SolutionsLaunch {
 // K rounds of (argmin of the surviving candidates, elimination of those within min_dist of it): one kernel when a
 // target has a single tile, otherwise a tile kernel and a per-target kernel per round
 hipError_t solutions_launch(const SolutionsLaunch &s, int T, hipStream_t stream);
+
+// ---- one waypoint of the paths of optik_hip_ik_path (ik_path.hip) ----------------------------------------------
+struct PathSelectLaunch {
+    const double *out_key;   // [P*R] the waypoint launch's keys, +inf unless the restart succeeded
+    const double *out_x;     // [n][ld]
+    const double *out_f;     // [ld] (null when no f is wanted)
+    const double *seed;      // [P][n] the seeds the waypoint was solved from
+    double *carry;           // [P][n] the next waypoint's seeds (may be `seed` itself)
+    double *last;            // [P][n] a copy of `carry` (the last waypoint only; may be null)
+    int n;
+    int filter;              // max_step < +inf: candidates must lie within max_step of the seed
+    double max_step;
+    unsigned long long restart_begin;
+    unsigned long long n_restarts;  // <= SEL_TILE
+    size_t ld;               // P * R
+    double *x;               // [P][n] this waypoint's outputs; any may be null
+    double *f;               // [P]
+    unsigned long long *idx;  // [P]
+    double *key;             // [P]
+    double *step;            // [P]
+    unsigned long long *reset_queue;  // the launch's work-item counter, put back to 0
+    unsigned long long *reset_fs;     // [P] the first-success words, put back to ~0 (null: launch without early exit)
+};
+// one 256-thread block per path: the filtered (key, index) argmin, the waypoint's outputs and the next seed
+hipError_t path_select_launch(const PathSelectLaunch &s, int P, hipStream_t stream);
 
 // ---- options ---------------------------------------------------------------------------------------------
 // Every tuning option of the kernel layer, in one place.  The defaults come from the environment ONCE, at the
@@ -181,6 +208,8 @@ struct optik_hip_chain {
     size_t fs_cap = 0;
     unsigned long long *sol_pick = nullptr;  // optik_hip_ik_solutions: per target, the last accepted column
     size_t sol_pick_cap = 0;
+    double *path_carry = nullptr;  // optik_hip_ik_path: [P][n] the seeds of the next waypoint
+    size_t path_carry_cap = 0;     // doubles
     // (what the last launch's selection kernel left behind: the work-item counter at 0, this many leading
     // first-success words at ~0 -- a launch that finds them so skips its fill commands)
     // (host-side knowledge that holds for launches ORDERED behind that selection kernel: the stream it ran on is kept

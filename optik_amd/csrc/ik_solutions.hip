@@ -36,20 +36,6 @@ __device__ __forceinline__ double linf_dist(const SolutionsLaunch &a, size_t col
     return d;
 }
 
-// The argmin of a 256-thread block; every thread ends with it.  (The shared arrays are free again on return.)
-__device__ __forceinline__ void block_argmin(double &key, unsigned long long &idx, double *s_key,
-                                             unsigned long long *s_idx) {
-    wave_argmin(key, idx);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { s_key[wave] = key; s_idx[wave] = idx; }
-    __syncthreads();
-    key = s_key[0];
-    idx = s_idx[0];
-    for (int w = 1; w < SOL_BLOCK / WAVE; ++w)
-        if (argmin_takes(key, idx, s_key[w], s_idx[w])) { key = s_key[w]; idx = s_idx[w]; }
-    __syncthreads();
-}
-
 // Slot k of target t gets the solution in column col (lanes < n write x, lane 0 the rest).
 __device__ __forceinline__ void put_solution(const SolutionsLaunch &a, int t, int k, size_t col, double key,
                                              unsigned long long idx) {
@@ -96,7 +82,7 @@ __global__ __launch_bounds__(SOL_BLOCK) void ik_solutions_small_kernel(const Sol
             const unsigned long long i = a.restart_begin + threadIdx.x + (unsigned long long)j * SOL_BLOCK;
             if (kk[j] < __builtin_huge_val() && argmin_takes(key, idx, kk[j], i)) { key = kk[j]; idx = i; }
         }
-        block_argmin(key, idx, s_key, s_idx);
+        block_argmin<SOL_BLOCK>(key, idx, s_key, s_idx);
         if (idx == ~0ull) break;  // (the same for the whole block)
         const size_t col = base + (size_t)(idx - a.restart_begin);
         if ((int)threadIdx.x < a.n) s_a[threadIdx.x] = a.out_x[(size_t)threadIdx.x * a.ld + col];
@@ -155,7 +141,7 @@ __global__ __launch_bounds__(SOL_BLOCK) void ik_solutions_tile_kernel(const Solu
         const unsigned long long i = a.restart_begin + r;
         if (argmin_takes(key, idx, kr, i)) { key = kr; idx = i; }
     }
-    block_argmin(key, idx, s_key, s_idx);
+    block_argmin<SOL_BLOCK>(key, idx, s_key, s_idx);
     if (threadIdx.x == 0) { TileRec r; r.idx = idx; r.key = key; *rec = r; }
 }
 

@@ -820,9 +820,11 @@ int optik_robot_ik_batch_ex(const optik_robot *r, const CSolverConfig *config, i
 
 namespace {
 
-// The host-side checks of a batch of targets (optik_robot_ik_batch_poses, optik_robot_ik_solutions): with
-// OPTIK_BATCH_VALIDATE_POSES every target's isometry test (-3), then every seed against the joint limits (-2).
-extern "C++" int check_batch_inputs(const optik_robot *r, int32_t T, const double *targets16, uint32_t flags, const double *x0) {
+// The host-side checks of a batch of targets (optik_robot_ik_batch_poses, optik_robot_ik_solutions,
+// optik_robot_ik_path): with OPTIK_BATCH_VALIDATE_POSES every target's isometry test (-3), then every seed against the
+// joint limits (-2).  S: the number of seeds, T by default.
+extern "C++" int check_batch_inputs(const optik_robot *r, int32_t T, const double *targets16, uint32_t flags, const double *x0,
+                                    int32_t S = -1) {
     const int n = r->n;
     const bool row_major = (flags & OPTIK_BATCH_ROW_MAJOR) != 0;
     if (flags & OPTIK_BATCH_VALIDATE_POSES) {
@@ -852,7 +854,8 @@ extern "C++" int check_batch_inputs(const optik_robot *r, int32_t T, const doubl
         });
         if (!all_ok) return set_err(-3, "invalid target transform specified");
     }
-    for (int t = 0; t < T; ++t)
+    if (S < 0) S = T;
+    for (int t = 0; t < S; ++t)
         for (int i = 0; i < n; ++i)
             if (x0[(size_t)t * n + i] < r->lb[i] || x0[(size_t)t * n + i] > r->ub[i])
                 return set_err(-2, "seed joint position outside of joint limits");
@@ -1013,6 +1016,118 @@ int optik_robot_ik_solutions(const optik_robot *r, const CSolverConfig *config, 
                                       count_out ? count_out + t0 : nullptr, x_out ? x_out + (size_t)t0 * K * n : nullptr,
                                       f_out ? f_out + (size_t)t0 * K : nullptr,
                                       idx_out ? idx_out + (size_t)t0 * K : nullptr, err);
+    });
+}
+
+namespace {
+
+// optik_robot_ik_path for the paths of one GPU: chunks of whole paths, each ONE upload, ONE optik_hip_ik_path (every
+// waypoint of the chunk, stream-ordered) and ONE download.  A chunk's waypoint launch holds about 4 M (path, restart)
+// items at most, and its share of the robot's batch block about 2^24 doubles (one path at least).
+extern "C++" int ik_path_on_device(const optik_robot *r, DeviceCtx *c, const CSolverConfig *config, int32_t P,
+                                   int32_t L, const double *tgt7, const double *x0, const double *ee7, double max_step,
+                                   double *x_out, double *f_out, uint64_t *idx_out, double *step_out,
+                                   int32_t *found_out, std::string &err) {
+    const int n = r->n;
+    const uint64_t R = config->max_restarts;
+    const size_t per_path = (size_t)L * (size_t)(7 + n + 3) + (size_t)n;  // doubles of the block per path
+    const uint64_t round_items = (uint64_t)4 << 20;
+    size_t chunk = (size_t)std::min<uint64_t>((uint64_t)P, std::max<uint64_t>(1, round_items / R));
+    chunk = std::min(chunk, std::max<size_t>(1, ((size_t)1 << 24) / per_path));
+    // Speed without a step limit: restart-major hand-out, so that every path's restart 0 (its warm start) runs first
+    const uint32_t flags = (config->solution_mode == 2 && !(max_step < __builtin_huge_val())) ? OPTIK_HIP_IK_RESTART_MAJOR : 0u;
+    const double deadline = config->max_time > 0.0 ? config->max_time : 0.0;
+    std::lock_guard<std::mutex> lock(c->batch_mu);
+    optik::DeviceScope dev_scope(c->device);
+    if (!dev_scope.ok()) { err = "hipSetDevice failed"; return -1; }
+
+    // the robot's batch block: in = targets [L][C][7] | x0 [C][n]; out = x [L][C][n] | f [L][C] | idx [L][C] |
+    // step [L][C]
+    const size_t need = per_path * chunk;
+    if (need > c->batch_cap) {
+        if (c->d_batch) (void)hipFree(c->d_batch);
+        if (c->h_batch) (void)hipHostFree(c->h_batch);
+        c->d_batch = nullptr; c->h_batch = nullptr; c->batch_cap = 0;
+        if (hipMalloc(&c->d_batch, sizeof(double) * need) != hipSuccess
+            || hipHostMalloc(&c->h_batch, sizeof(double) * need) != hipSuccess) {
+            err = "batch workspace allocation failed";
+            return -1;
+        }
+        c->batch_cap = need;
+    }
+    for (size_t p0 = 0; p0 < (size_t)P; p0 += chunk) {
+        const size_t C = std::min(chunk, (size_t)P - p0), LC = (size_t)L * C;
+        double *h_t = c->h_batch, *h_out = h_t + 7 * LC + (size_t)n * C;
+        double *d_t = c->d_batch, *d_x0 = d_t + 7 * LC, *d_x = d_x0 + (size_t)n * C, *d_f = d_x + LC * (size_t)n;
+        uint64_t *d_idx = reinterpret_cast<uint64_t *>(d_f + LC);
+        double *d_step = reinterpret_cast<double *>(d_idx + LC);
+        // (paths p0.. of tgt7 [P][L][7] -> [L][C][7], waypoint-major)
+        for (size_t p = 0; p < C; ++p)
+            for (int32_t l = 0; l < L; ++l)
+                std::memcpy(h_t + ((size_t)l * C + p) * 7, tgt7 + ((p0 + p) * (size_t)L + (size_t)l) * 7,
+                            sizeof(double) * 7);
+        std::memcpy(h_t + 7 * LC, x0 + p0 * (size_t)n, sizeof(double) * (size_t)n * C);
+        if (hipMemcpyAsync(d_t, h_t, sizeof(double) * (7 * LC + (size_t)n * C), hipMemcpyHostToDevice, nullptr)
+            != hipSuccess) {
+            err = "upload failed";
+            return -1;
+        }
+        optik_hip_ik_path_outputs o;
+        std::memset(&o, 0, sizeof o);
+        o.d_x = d_x; o.d_f = d_f; o.d_idx = d_idx; o.d_step = d_step;
+        if (optik_hip_ik_path(c->chain, config, d_t, d_x0, (int32_t)C, L, ee7, 0, R, flags, deadline, max_step, &o,
+                              nullptr)) {
+            err = optik_hip_last_error();
+            return -1;
+        }
+        const size_t out_doubles = LC * (size_t)(n + 3);
+        if (hipMemcpyAsync(h_out, d_x, sizeof(double) * out_doubles, hipMemcpyDeviceToHost, nullptr) != hipSuccess
+            || hipStreamSynchronize(nullptr) != hipSuccess) {
+            err = "download failed";
+            return -1;
+        }
+        const double *hx = h_out, *hf = hx + LC * (size_t)n;
+        const uint64_t *hi = reinterpret_cast<const uint64_t *>(hf + LC);
+        const double *hs = reinterpret_cast<const double *>(hi + LC);
+        // ([L][C] -> path-major [P][L])
+        for (size_t p = 0; p < C; ++p)
+            for (int32_t l = 0; l < L; ++l) {
+                const size_t dv = (size_t)l * C + p, hv = (p0 + p) * (size_t)L + (size_t)l;
+                if (x_out) std::memcpy(x_out + hv * n, hx + dv * n, sizeof(double) * (size_t)n);
+                if (f_out) f_out[hv] = hf[dv];
+                if (idx_out) idx_out[hv] = hi[dv];
+                if (step_out) step_out[hv] = hs[dv];
+                if (found_out) found_out[hv] = hi[dv] != UINT64_MAX ? 1 : 0;
+            }
+    }
+    return 0;
+}
+
+}  // namespace
+
+int optik_robot_ik_path(const optik_robot *r, const CSolverConfig *config, int32_t P, int32_t L,
+                        const double *targets16, uint32_t flags, const double *x0, const double *ee16,
+                        double max_step, double *x_out, double *f_out, uint64_t *idx_out, double *step_out,
+                        int32_t *found_out) {
+    if (!r || !config || !targets16 || !x0 || P < 1 || L < 1) return set_err(-1, "bad argument");
+    if ((int64_t)P * (int64_t)L > INT32_MAX) return set_err(-1, "ik_path: too many waypoints (P * L >= 2^31)");
+    if (config->max_restarts == 0)
+        return set_err(-1, "ik_path: max_restarts must be set (every waypoint runs restarts [0, max_restarts))");
+    if (config->max_restarts > OPTIK_HIP_PATH_MAX_RESTARTS)
+        return set_err(-1, "ik_path: max_restarts must be at most 4096");
+    if (!(max_step >= 0.0)) return set_err(-1, "ik_path: max_step must be >= 0 (+inf: no limit)");
+    const int n = r->n;
+    if (int rc = check_batch_inputs(r, P * L, targets16, flags, x0, P)) return rc;
+    const std::vector<double> tgt7 = targets_pose7(P * L, targets16, (flags & OPTIK_BATCH_ROW_MAJOR) != 0,
+                                                   (flags & OPTIK_POSE_FROM_MATRIX) != 0);
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    return run_device_parts(r, P, [&](DeviceCtx *ctx, int32_t p0, int32_t p1, std::string &err) {
+        const size_t w = (size_t)p0 * (size_t)L;
+        return ik_path_on_device(r, ctx, config, p1 - p0, L, tgt7.data() + w * 7, x0 + (size_t)p0 * n,
+                                 ee16 ? ee7 : nullptr, max_step, x_out ? x_out + w * n : nullptr,
+                                 f_out ? f_out + w : nullptr, idx_out ? idx_out + w : nullptr,
+                                 step_out ? step_out + w : nullptr, found_out ? found_out + w : nullptr, err);
     });
 }
 

@@ -181,6 +181,45 @@ class HipChain:
             int(restart_begin), int(restart_end), float(deadline_s), k, min_dist, C.byref(o), _stream_ptr()))
         return bufs
 
+    def ik_path(self, cfg, targets, x0, restart_begin, restart_end, max_step=float("inf"), flags=0, deadline_s=0.0,
+                ee_offset7=None, bufs=None):
+        """Warm-started IK along P paths of L waypoints (optik_hip_ik_path): waypoint l of path p is solved from the
+        path's current seed (x0[p], then the last accepted solution), its accepted solution being the (key, index)
+        minimum of the successes within max_step (L-infinity) of that seed.  targets [L, P, 7] (waypoint-major),
+        x0 [P, n] float64 cuda tensors; restart_end - restart_begin <= 4096.  Stream-ordered on the current stream;
+        returns a dict of device tensors: x [L, P, n], f [L, P], idx [L, P] int64 (-1 = none), key [L, P] (+inf =
+        none), step [L, P] (NaN = none), last [P, n] (each path's final seed)."""
+        max_step = nat.check_max_step(max_step)
+        if not (targets.is_cuda and targets.dtype == torch.float64 and targets.is_contiguous()
+                and targets.dim() == 3 and targets.shape[2] == 7 and targets.shape[0] >= 1 and targets.shape[1] >= 1):
+            raise ValueError("targets must be a contiguous float64 cuda tensor [L, P, 7]")
+        L, P = int(targets.shape[0]), int(targets.shape[1])
+        if not (x0.is_cuda and x0.dtype == torch.float64 and x0.is_contiguous() and tuple(x0.shape) == (P, self.n)):
+            raise ValueError(f"x0 must be a contiguous float64 cuda tensor [P, n] = [{P}, {self.n}]")
+        b, e = int(restart_begin), int(restart_end)
+        if b < 0 or e <= b:
+            raise ValueError("empty restart range")
+        if e - b > nat.PATH_MAX_RESTARTS:
+            raise ValueError(f"ik_path runs at most {nat.PATH_MAX_RESTARTS} restarts per waypoint, got {e - b}")
+        if int(flags) & ~nat.IK_RESTART_MAJOR:
+            raise ValueError("ik_path: flags may only hold IK_RESTART_MAJOR")
+        if bufs is None:
+            dev = targets.device
+            bufs = dict(x=torch.empty((L, P, self.n), dtype=torch.float64, device=dev),
+                        f=torch.empty((L, P), dtype=torch.float64, device=dev),
+                        idx=torch.empty((L, P), dtype=torch.int64, device=dev),
+                        key=torch.empty((L, P), dtype=torch.float64, device=dev),
+                        step=torch.empty((L, P), dtype=torch.float64, device=dev),
+                        last=torch.empty((P, self.n), dtype=torch.float64, device=dev))
+        o = nat.IkPathOutputs()
+        o.d_x, o.d_f, o.d_idx = _ptr(bufs.get("x")), _ptr(bufs.get("f")), _ptr(bufs.get("idx"))
+        o.d_key, o.d_step, o.d_last = _ptr(bufs.get("key")), _ptr(bufs.get("step")), _ptr(bufs.get("last"))
+        ee = np.ascontiguousarray(ee_offset7, dtype=np.float64) if ee_offset7 is not None else None
+        nat.check(nat.lib().optik_hip_ik_path(
+            self._h, C.byref(cfg), _ptr(targets), _ptr(x0), P, L, _dp(ee) if ee is not None else None, b, e,
+            int(flags), float(deadline_s), max_step, C.byref(o), _stream_ptr()))
+        return bufs
+
     def ik_host(self, cfg, targets, x0, restart_begin, restart_end, flags=0, deadline_s=0.0, ee_offset7=None):
         """optik_hip_ik_host: host arrays in (targets [T, 7], x0 [T, n]), the winners back as numpy arrays; blocking.
         With IK_EARLY_EXIT | IK_FIND_ANY and one target the call returns when the first restart has succeeded."""

@@ -36,6 +36,8 @@ def _bind(L):
     L.optik_robot_ik_solutions.argtypes = [vp, C.POINTER(nat.SolverConfigC), C.c_int32, dp, C.c_uint32, dp, dp,
                                            C.c_int32, C.c_double, C.POINTER(C.c_int32), dp, dp,
                                            C.POINTER(C.c_uint64)]
+    L.optik_robot_ik_path.argtypes = [vp, C.POINTER(nat.SolverConfigC), C.c_int32, C.c_int32, dp, C.c_uint32, dp, dp,
+                                      C.c_double, dp, dp, C.POINTER(C.c_uint64), dp, C.POINTER(C.c_int32)]
     L.optik_robot_fk_ex.argtypes = [vp, dp, dp, dp]
     L.optik_robot_diff_ik_ex.argtypes = [vp, dp, dp, dp, dp, C.POINTER(C.c_double), dp]
     L.optik_robot_diff_ik_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_int32)]
@@ -319,6 +321,60 @@ class Robot:
         if return_index:
             return [(xs[i], fs[i], ids[i]) for i in range(m)]
         return [(xs[i], fs[i]) for i in range(m)]
+
+    def ik_paths_arrays(self, config: SolverConfig, targets, x0s, max_step=float("inf"), ee_offset=None):
+        """Warm-started IK along P paths of L waypoints (extension; include/optik.h: optik_robot_ik_path), array
+        form: `targets` [P, L, 4, 4] row-major poses, `x0s` [P, n] start configurations -> (x [P, L, n], c [P, L],
+        idx [P, L] int64 (-1 = none), step [P, L], found [P, L] bool).  Each waypoint is solved over restarts
+        [0, config.max_restarts) (at most 4096) from the path's current configuration: the start, then the last
+        accepted solution.  Accepted is the best success (Quality: nearest, Speed: lowest restart index) whose largest
+        joint change from that configuration is <= max_step; a waypoint without one leaves the path where it was
+        (x, c and step NaN).  step: the largest joint change of the accepted solution.  max_time, if set, is each
+        waypoint's deadline."""
+        max_step = nat.check_max_step(max_step)
+        R = config.max_restarts
+        if R <= 0 or R >= U64_MAX:
+            raise ValueError("ik_path needs a finite max_restarts: every waypoint runs restarts [0, max_restarts)")
+        if R > nat.PATH_MAX_RESTARTS:
+            raise ValueError(f"ik_path: max_restarts must be at most {nat.PATH_MAX_RESTARTS}")
+        tg = np.asarray(targets, dtype=np.float64)
+        if tg.ndim != 4 or tg.shape[2:] != (4, 4) or tg.shape[0] < 1 or tg.shape[1] < 1:
+            raise ValueError("targets must be [P, L, 4, 4]")
+        P, L = tg.shape[:2]
+        n = self.num_positions()
+        x0s = np.asarray(x0s, dtype=np.float64)
+        if x0s.shape != (P, n):
+            raise ValueError(f"x0s must be [P, n] = [{P}, {n}], got {list(x0s.shape)}")
+        x0s = np.ascontiguousarray(x0s)
+        tg16 = np.ascontiguousarray(tg).reshape(P * L, 16)
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        cfg = config.to_c()
+        x = np.empty((P, L, n))
+        f = np.empty((P, L))
+        idx = np.empty((P, L), dtype=np.uint64)
+        step = np.empty((P, L))
+        found = np.empty((P, L), dtype=np.int32)
+        rc = self._L.optik_robot_ik_path(self._h, C.byref(cfg), P, L, _dp(tg16), BATCH_ROW_MAJOR | BATCH_VALIDATE_POSES,
+                                         _dp(x0s), _dp(ee) if ee is not None else None, max_step, _dp(x), _dp(f),
+                                         idx.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(step),
+                                         found.ctypes.data_as(C.POINTER(C.c_int32)))
+        if rc in (-2, -3):  # a start configuration outside the limits, an invalid transform
+            raise ValueError(_err(self._L))
+        if rc < 0:
+            raise RuntimeError(_err(self._L))
+        return x, f, idx.view(np.int64), step, found.astype(bool)
+
+    def ik_path(self, config: SolverConfig, targets, x0, max_step=float("inf"), ee_offset=None):
+        """One path of L waypoints (`targets` [L, 4, 4]) from x0: a list of L entries, (x, c) or None where the
+        waypoint had no accepted solution (the path then carries on from its last configuration).  See
+        ik_paths_arrays."""
+        x0 = self._check_x(x0)
+        tg = np.asarray(targets, dtype=np.float64)
+        if tg.ndim != 3 or tg.shape[1:] != (4, 4):
+            raise ValueError("targets must be [L, 4, 4]")
+        x, f, _, _, found = self.ik_paths_arrays(config, tg[None], x0[None], max_step, ee_offset)
+        xs, fs = x[0].tolist(), f[0].tolist()
+        return [(xs[w], fs[w]) if ok else None for w, ok in enumerate(found[0].tolist())]
 
     def diff_ik(self, x0, V_WE, v_max, ee_offset=None):
         """Returns (alpha, v) or None (optik.pyi:43-49; lib.rs:123-239): the joint velocities
