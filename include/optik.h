@@ -161,6 +161,13 @@ int optik_robot_diff_ik_ex(const optik_robot *robot, const double *x0, const dou
 int optik_robot_diff_ik_batch(const optik_robot *robot, int64_t B, const double *x0, const double *V_WE6,
                               const double *v_max, const double *ee_offset16, double *alpha_out,
                               double *v_out, int32_t *status_out);
+/* The measures of solution modes 3 and 4 (extension; include/optik_hip.h: OPTIK_MODE_*, optik_hip_manip_batch) for
+ * B configurations: x [B][n] row-major -> w_out [B] manipulability, c_out [B] condition; either may be NULL.
+ * ee_offset16 may be NULL.  One kernel launch per 262 144 rows on the robot's first device, as
+ * optik_robot_diff_ik_batch.  rc 0, or -1: null argument, prismatic joints.  The modes themselves are valid for
+ * optik_robot_ik*, optik_robot_ik_solutions and optik_robot_ik_path, and are scheduled there as Quality. */
+int optik_robot_manipulability_batch(const optik_robot *robot, int64_t B, const double *x, const double *ee_offset16,
+                                     double *w_out, double *c_out);
 int optik_robot_fk_ex(const optik_robot *robot, const double *x, const double *ee_offset16,
                       double *pose16_out);
 int optik_robot_joint_jacobian_ex(const optik_robot *robot, const double *x,

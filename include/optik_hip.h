@@ -54,10 +54,21 @@ enum {
     OPTIK_RES_XTOL_REACHED = 4
 };
 
+/* optik_solver_config.solution_mode.  Quality and Speed are the reference's (config.rs:3-8).  The two extensions
+ * rank the successful restarts by the body Jacobian J of their solution (the TRAC-IK solve types Manip1 / Manip2,
+ * without TRAC-IK's joint-limit penalty factor; J unscaled, metres and radians as KDL's): Manipulability keeps the
+ * largest w = sqrt(det G) = the product of J's min(n, 6) largest singular values, Condition the largest
+ * c = sigma_min / sigma_max (G = J^T J for n <= 6, J J^T for n > 6; the operation order: csrc/manip_measure.hpp).
+ * Both are scheduled as Quality: every restart of the range runs to its end (no early exit, no FIND_ANY). */
+#define OPTIK_MODE_QUALITY 1
+#define OPTIK_MODE_SPEED 2
+#define OPTIK_MODE_MANIPULABILITY 3
+#define OPTIK_MODE_CONDITION 4
+
 /* SolverConfig with the layout of CSolverConfig
  * (crates/optik-cpp/src/lib.rs:10-20; config.rs:22-50): 96 bytes on LP64. */
 typedef struct optik_solver_config {
-    int32_t solution_mode; /* 1 = Quality, 2 = Speed (config.rs:3-8) */
+    int32_t solution_mode; /* OPTIK_MODE_*: 1 = Quality, 2 = Speed (config.rs:3-8); 3, 4: extensions */
     int32_t _pad;
     double max_time;       /* seconds, 0 = unlimited */
     uint64_t max_restarts; /* 0 = unlimited */
@@ -129,6 +140,14 @@ int optik_hip_diff_ik_batch(const optik_hip_chain *chain, const double *ee_offse
                             const double *d_V, int64_t ld_V, const double *d_vmax, int64_t ld_vmax,
                             int64_t B, double *d_alpha, double *d_v, int32_t *d_status, void *stream);
 
+/* The measures of solution modes 3 and 4 for B configurations d_q [n][B] (any chain of 1 .. 16 revolute joint
+ * positions): d_w [B] manipulability w = sqrt(det G), d_c [B] condition c = sigma_min / sigma_max, both of the body
+ * Jacobian fk_batch returns (ee_offset7 may be NULL).  Either output may be NULL.  A G that is not numerically
+ * positive definite (an LDL^T pivot <= 0) gives w = c = 0 exactly.  One thread per configuration, no workspace.
+ * Refused with OPTIK_HIP_EUNSUPPORTED: chains with prismatic joints. */
+int optik_hip_manip_batch(const optik_hip_chain *chain, const double *ee_offset7, const double *d_q, int64_t B,
+                          double *d_w, double *d_c, void *stream);
+
 /* Restart seeds: ChaCha8Rng::seed_from_u64(42), set_stream(i), one uniform draw
  * per joint (lib.rs:358-370, 86-91) for i = first .. first+count-1 -> d_q [n][count]. */
 int optik_hip_seed_batch(const optik_hip_chain *chain, uint64_t first, int64_t count, double *d_q,
@@ -161,7 +180,7 @@ typedef struct optik_hip_ik_outputs {
     double *d_win_x;      /* [T][n]                                           */
     double *d_win_f;      /* [T]                                              */
     uint64_t *d_win_idx;  /* [T] winning restart index, UINT64_MAX if none    */
-    double *d_win_key;    /* [T] Quality: ||x - x0||_2 ; Speed: (double)index */
+    double *d_win_key;    /* [T] Quality: ||x - x0||_2 ; Speed: (double)index ; Manipulability: -w ; Condition: -c */
 } optik_hip_ik_outputs;
 
 /* The hot path: for each of T targets run restarts restart_begin..restart_end-1
@@ -169,7 +188,13 @@ typedef struct optik_hip_ik_outputs {
  * (lib.rs:376-379) and select (Speed: lowest successful index = the reference's
  * 1-thread order; Quality: min ||x - x0||_2, ties to the lower index).
  * d_targets [T][7], d_x0 [T][n].  deadline_s > 0 abandons restarts still running
- * that many seconds after the kernel starts (max_time, lib.rs:260-264, 308). */
+ * that many seconds after the kernel starts (max_time, lib.rs:260-264, 308).
+ * OPTIK_MODE_MANIPULABILITY / _CONDITION: scheduled as Quality (EARLY_EXIT and FIND_ANY have no effect); after the
+ * solver, on the same stream, a key kernel replaces the key of every successful restart by -w / -c of its x (with
+ * ee_offset7, as optik_hip_manip_batch computes them); failed restarts keep +inf.  The selection is unchanged --
+ * minimum (key, index), ties to the lower index -- so the winner is the most manipulable / best conditioned success.
+ * The per-restart x is kept in the chain's workspace when d_x is NULL.  The same holds for optik_hip_ik_solutions
+ * (best first) and optik_hip_ik_path (the best within max_step).  Chains with prismatic joints are refused. */
 int optik_hip_ik_batch(optik_hip_chain *chain, const optik_solver_config *cfg,
                        const double *d_targets, const double *d_x0, int32_t T,
                        const double *ee_offset7, uint64_t restart_begin, uint64_t restart_end,

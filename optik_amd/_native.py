@@ -123,6 +123,7 @@ def lib():
     L.optik_hip_eval_batch.argtypes = [vp, C.POINTER(SolverConfigC), dp, dp, vp, C.c_int64, vp, vp, vp]
     L.optik_hip_fk_batch.argtypes = [vp, dp, vp, C.c_int64, vp, vp, vp]
     L.optik_hip_seed_batch.argtypes = [vp, C.c_uint64, C.c_int64, vp, vp]
+    L.optik_hip_manip_batch.argtypes = [vp, dp, vp, C.c_int64, vp, vp, vp]
     L.optik_hip_diff_ik_batch.argtypes = [vp, dp, vp, vp, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, vp, vp]
     L.optik_hip_ik_batch.argtypes = [vp, C.POINTER(SolverConfigC), vp, vp, C.c_int32, dp,
                                      C.c_uint64, C.c_uint64, C.c_uint32, C.c_double,
@@ -150,10 +151,24 @@ def check(rc: int):
         raise OptikHipError(f"optik_hip error {rc}: {msg.decode() if msg else '?'}")
 
 
+# optik_solver_config.solution_mode (include/optik_hip.h: OPTIK_MODE_*).  quality and speed are the reference's;
+# manipulability and condition rank the successes by -w / -c of their body Jacobian (csrc/manip_measure.hpp)
+SOLUTION_MODES = {"quality": 1, "speed": 2, "manipulability": 3, "condition": 4}
+MEASURE_MODES = ("manipulability", "condition")
+
+
+def solution_mode_code(solution_mode):
+    """The OPTIK_MODE_* value of a mode name; ValueError for anything else."""
+    if not isinstance(solution_mode, str) or solution_mode not in SOLUTION_MODES:
+        raise ValueError("solution_mode must be one of " + ", ".join(repr(m) for m in SOLUTION_MODES)
+                         + f", got {solution_mode!r}")
+    return SOLUTION_MODES[solution_mode]
+
+
 def make_config(solution_mode="speed", max_time=0.0, max_restarts=0, tol_f=1e-6, tol_df=-1.0,
                 tol_dx=-1.0, linear_weight=(1.0, 1.0, 1.0), angular_weight=(1.0, 1.0, 1.0)):
     cfg = SolverConfigC()
-    cfg.solution_mode = {"quality": 1, "speed": 2}[solution_mode]
+    cfg.solution_mode = solution_mode_code(solution_mode)
     cfg.max_time = float(max_time)
     cfg.max_restarts = int(max_restarts)
     cfg.tol_f, cfg.tol_df, cfg.tol_dx = float(tol_f), float(tol_df), float(tol_dx)

@@ -1,7 +1,7 @@
 // ik_batch_ops.hip -- the batched stand-alone operators of the kernel layer and the test probes.
 //
 //   eval_batch_kernel     objective + gradient (objective.rs:40-110) for a batch of configurations
-//   fk_batch_kernel       end-effector pose (+ body Jacobian, kinematics.rs:123-196) for a batch
+//   fk_batch_kernel       end-effector pose (+ body Jacobian, kinematics.rs:123-196; jacobian_column: ik_jacobian.hpp)
 //   diff_ik_batch_kernel  Robot::diff_ik (lib.rs:123-239) for a batch: FK + Jacobian, then the LP of diff_ik_lp.hpp
 //   fk_general_kernel     forward kinematics of a chain with prismatic joints (kinematics.rs:243-255)
 //   seed_batch_kernel     ChaCha8 restart seeds (lib.rs:358-370, 86-91)
@@ -9,6 +9,7 @@
 // One configuration per lane, chain table staged in LDS, coalesced struct-of-arrays in and out.  All f64.
 #include "diff_ik_lp.hpp"
 #include "ik_host.hpp"
+#include "ik_jacobian.hpp"
 
 using namespace optik;
 using namespace optik::host;
@@ -53,20 +54,6 @@ struct FkLaunch {
     double *pose;  // [7][B]
     double *jac;   // [6n][B] or null
 };
-
-// joint_jacobian, kinematics.rs:166-196: column k of the body Jacobian (linear, angular; end-effector frame).
-// fk_batch_kernel and diff_ik_batch_kernel share it: the same operations on the same operands, the same bits.
-template <int N, bool TIP>
-__device__ __forceinline__ void jacobian_column(const ChainDev &sch, const Kin<N, TIP> &kin, const Q4 eeqc, int k,
-                                                double (&c6)[6]) {
-    const V3 ax{sch.axis[k][0], sch.axis[k][1], sch.axis[k][2]};
-    const V3 angular = qrot(kin.tf[k].q, ax);
-    const V3 d{kin.ee.t.x - kin.tf[k].t.x, kin.ee.t.y - kin.tf[k].t.y, kin.ee.t.z - kin.tf[k].t.z};
-    const V3 linear = cross(angular, d);
-    const V3 al = qrot(eeqc, angular);
-    const V3 ll = qrot(eeqc, linear);
-    c6[0] = ll.x; c6[1] = ll.y; c6[2] = ll.z; c6[3] = al.x; c6[4] = al.y; c6[5] = al.z;
-}
 
 template <int N, bool TIP>
 __global__ __launch_bounds__(256) void fk_batch_kernel(const FkLaunch a) {

@@ -4,7 +4,8 @@
 //
 // The solvers are launched from here and defined in their own translation units: the lane-per-restart form
 // (ik_lane_kernel.hip), the quad solver (ik_quad_kernel.hip), the general run-time-n solver (ik_wide_kernel.hip);
-// optik_hip_ik_batch picks one by launch size and joint count.  The selection kernels: ik_select.hip,
+// optik_hip_ik_batch picks one by launch size and joint count.  The key pass of solution modes 3 and 4: ik_manip.hip.
+// The selection kernels: ik_select.hip,
 // ik_solutions.hip and ik_path.hip; the batch operators: ik_batch_ops.hip.  No CPU fallback exists: every entry point fails loudly without a device.
 #include <algorithm>
 #include <cstdio>
@@ -287,8 +288,12 @@ static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, con
                         bool *claim_armed, SolvedLaunch *sl) {
     if (!ch || !cfg || !d_targets || !d_x0 || !out || T < 1) return fail(OPTIK_HIP_EINVAL, "bad argument");
     if (restart_end <= restart_begin) return fail(OPTIK_HIP_EINVAL, "empty restart range");
-    if (cfg->solution_mode != 1 && cfg->solution_mode != 2)
-        return fail(OPTIK_HIP_EINVAL, "solution_mode must be 1 (Quality) or 2 (Speed)");
+    const int mode = cfg->solution_mode;
+    if (mode < OPTIK_MODE_QUALITY || mode > OPTIK_MODE_CONDITION)
+        return fail(OPTIK_HIP_EINVAL,
+                    "solution_mode must be 1 (Quality), 2 (Speed), 3 (Manipulability) or 4 (Condition)");
+    // Manipulability and Condition: scheduled as Quality, then a key pass over the successes (ik_manip.hip)
+    const bool manip = mode == OPTIK_MODE_MANIPULABILITY || mode == OPTIK_MODE_CONDITION;
     const uint64_t R = restart_end - restart_begin;
     if (restart_end > 1 || restart_begin > 0)
         for (int k = 0; k < ch->n; ++k)
@@ -323,7 +328,7 @@ static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, con
     if (stream != ch->clean_stream) { ch->queue_clean = false; ch->fs_clean = 0; }
     if (!ch->queue_clean) HIP_TRY(hipMemsetAsync(ch->queue, 0, sizeof(unsigned long long), stream));
     ch->queue_clean = false;  // (until this launch's selection kernel has put it back)
-    const bool early = (flags & OPTIK_HIP_IK_EARLY_EXIT) && cfg->solution_mode == 2;
+    const bool early = (flags & OPTIK_HIP_IK_EARLY_EXIT) && mode == OPTIK_MODE_SPEED;
     size_t fs_clean_after = ch->fs_clean;  // (a launch without early exit leaves the words alone)
     if (early) {
         if ((size_t)T > ch->fs_cap) {
@@ -338,8 +343,10 @@ static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, con
         fs_clean_after = std::max(ch->fs_clean, (size_t)T);  // once the selection kernel has put words [0, T) back
         ch->fs_clean = 0;
     }
-    // the selection needs the per-restart x / f / key: scratch if the caller skips them
+    // the selection needs the per-restart x / f / key: scratch if the caller skips them (the key pass of modes 3 and
+    // 4 reads x: grown here, before the launch -- nothing is allocated between the solve and the selection)
     double *px = out->d_x, *pf = out->d_f, *pk = nullptr;
+    need_x = need_x || (want_sel && manip);
     if (want_sel) {
         const bool need_xf = (!px || !pf) && (need_x || need_f);
         if (cols > ch->tmp_cols) {
@@ -379,7 +386,7 @@ static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, con
     a.wq.restart_major = (flags & OPTIK_HIP_IK_RESTART_MAJOR) ? 1 : 0;
     a.wq.n_targets = (unsigned long long)T;
     a.wq.deadline = 0;
-    a.wq.quality = (cfg->solution_mode == 1);
+    a.wq.quality = (mode != OPTIK_MODE_SPEED);  // (modes 3 and 4: Quality's keys, replaced by the key pass below)
     a.wq.out_x = px;
     a.wq.out_f = pf;
     a.wq.out_key = pk;
@@ -515,6 +522,9 @@ static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, con
     else return fail(OPTIK_HIP_EUNSUPPORTED, "no solver for this chain in this build");
     HIP_TRY(hipGetLastError());
     if (ch->timing) { HIP_TRY(hipEventRecord(ch->ev1[ev_slot], stream)); ch->ev_count += 1; }
+    // modes 3 and 4: the successes' keys become -w / -c, on the same stream, before any selection kernel
+    if (manip && pk)
+        if (int rc = manip_key_launch(ch, mode, ee_offset7, px, pk, cols, stream)) return rc;
     ch->last.grid = grid; ch->last.block = WAVE; ch->last.lds_bytes = lds; ch->last.tiles = n_tiles;
 
     sl->px = px; sl->pf = pf; sl->pk = pk;
@@ -593,7 +603,7 @@ int optik_hip_ik_path(optik_hip_chain *ch, const optik_solver_config *cfg, const
     // Speed without a step limit: the deterministic early exit, whose winner is the lowest successful index -- the
     // filter cannot reject it.  With a limit (and in Quality) every restart runs to its end: early exit could abandon
     // the one restart that passes the filter.
-    const uint32_t solve_flags = flags | ((cfg->solution_mode == 2 && !filter) ? OPTIK_HIP_IK_EARLY_EXIT : 0u);
+    const uint32_t solve_flags = flags | ((cfg->solution_mode == OPTIK_MODE_SPEED && !filter) ? OPTIK_HIP_IK_EARLY_EXIT : 0u);
     {
         BIND_DEVICE(ch);
         const size_t need = (size_t)P * (size_t)n;
@@ -723,7 +733,7 @@ int optik_hip_ik_host(optik_hip_chain *ch, const optik_solver_config *cfg, const
     // other restarts notice the flag at their next evaluation and the launch ends behind the caller's back (the
     // next launch of the chain queues behind it).  Without a success the call ends with the launch, as before.
     const bool claim = T == 1 && (flags & OPTIK_HIP_IK_FIND_ANY) && (flags & OPTIK_HIP_IK_EARLY_EXIT)
-                       && cfg->solution_mode == 2;
+                       && cfg->solution_mode == OPTIK_MODE_SPEED;
     if (claim && !ch->hw_claim) {
         HIP_TRY(hipHostMalloc(&ch->hw_claim, sizeof(unsigned long long) * (3 + MAX_DOF), hipHostMallocCoherent));
         std::memset(ch->hw_claim, 0, sizeof(unsigned long long) * (3 + MAX_DOF));

@@ -5,6 +5,7 @@
 //   ik_select.hip      the selection of lib.rs:397-413 over the per-restart keys
 //   ik_solutions.hip   up to K distinct solutions per target over the same keys (optik_hip_ik_solutions)
 //   ik_path.hip        the per-waypoint selection of warm-started paths (optik_hip_ik_path)
+//   ik_manip.hip       the manipulability / condition keys of solution modes 3 and 4, optik_hip_manip_batch
 //   ik_batch_ops.hip   objective / gradient, FK / Jacobian and seed batches, the test probes
 //   ik_lane_kernel.hip, ik_quad_kernel.hip, ik_wide_kernel.hip    the restart solvers (one restart loop each)
 #pragma once
@@ -110,6 +111,12 @@ struct PathSelectLaunch {
 };
 // one 256-thread block per path: the filtered (key, index) argmin, the waypoint's outputs and the next seed
 hipError_t path_select_launch(const PathSelectLaunch &s, int P, hipStream_t stream);
+
+// ---- the keys of solution modes 3 and 4 (ik_manip.hip) -------------------------------------------------------
+// Overwrites every key < +inf of a solver launch (x [n][cols], key [cols]) with -w (OPTIK_MODE_MANIPULABILITY) or -c
+// (OPTIK_MODE_CONDITION) of that restart's x; one kernel on `stream`.  0 or a fail() code.
+int manip_key_launch(const optik_hip_chain *ch, int mode, const double *ee_offset7, const double *x, double *key,
+                     size_t cols, hipStream_t stream);
 
 // ---- options ---------------------------------------------------------------------------------------------
 // Every tuning option of the kernel layer, in one place.  The defaults come from the environment ONCE, at the

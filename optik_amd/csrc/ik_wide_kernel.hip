@@ -5,20 +5,12 @@
 
 #include <cstdlib>
 
+#include "ik_jacobian.hpp"
 #include "ik_wide.hpp"
 
 namespace optik {
 
 namespace {
-
-__device__ __forceinline__ void stage_wide_chain(WideChainDev &dst, const WideChainDev *src) {
-    constexpr int ND = (int)(sizeof(WideChainDev) / sizeof(double));
-    static_assert(sizeof(WideChainDev) % sizeof(double) == 0, "WideChainDev is a whole number of doubles");
-    const double *s = reinterpret_cast<const double *>(src);
-    double *d = reinterpret_cast<double *>(&dst);
-    for (int i = threadIdx.x; i < ND; i += blockDim.x) d[i] = s[i];
-    __syncthreads();
-}
 
 __global__ __launch_bounds__(64, 2) void wide_solve_kernel(const WideSolveLaunch a) {
     __shared__ WideChainDev sch;
@@ -82,15 +74,8 @@ __global__ __launch_bounds__(256) void wide_fk_batch_kernel(const WideBatchLaunc
             // joint_jacobian, kinematics.rs:166-196
             const Q4 eeqc = qconj(ee.q);
             for (int k = 0; k < n; ++k) {
-                const V3 tk{tf[7 * k + 0], tf[7 * k + 1], tf[7 * k + 2]};
-                const Q4 tq{tf[7 * k + 3], tf[7 * k + 4], tf[7 * k + 5], tf[7 * k + 6]};
-                const V3 ax{sch.axis[k][0], sch.axis[k][1], sch.axis[k][2]};
-                const V3 angular = qrot(tq, ax);
-                const V3 d{ee.t.x - tk.x, ee.t.y - tk.y, ee.t.z - tk.z};
-                const V3 linear = cross(angular, d);
-                const V3 al = qrot(eeqc, angular);
-                const V3 ll = qrot(eeqc, linear);
-                const double c6[6] = {ll.x, ll.y, ll.z, al.x, al.y, al.z};
+                double c6[6];
+                wide_jacobian_column(sch, tf, ee, eeqc, k, c6);
 #pragma unroll
                 for (int r = 0; r < 6; ++r) a.jac[(size_t)(k * 6 + r) * a.B + b] = c6[r];
             }

@@ -524,7 +524,8 @@ int optik_robot_ik_pose(const optik_robot *r, const CSolverConfig *config, const
         return std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
     };
     const uint64_t max_restarts = config->max_restarts > 0 ? config->max_restarts : UINT64_MAX;  // lib.rs:273-277
-    const bool quality = config->solution_mode == 1;
+    // (Manipulability and Condition are scheduled as Quality: every restart runs, the best key wins)
+    const bool quality = config->solution_mode != OPTIK_MODE_SPEED;
     // The first launch covers as many restart indices as the chip holds resident waves (one
     // restart per wave: no wave pays for the phases of 63 other restarts, and a third to a
     // half of the restarts succeed, so it almost always contains the answer); later launches
@@ -684,7 +685,7 @@ int ik_batch_on_device(const optik_robot *r, DeviceCtx *c, const CSolverConfig *
         return std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
     };
     const uint64_t max_restarts = config->max_restarts > 0 ? config->max_restarts : UINT64_MAX;
-    const bool quality = config->solution_mode == 1;
+    const bool quality = config->solution_mode != OPTIK_MODE_SPEED;  // (Manipulability, Condition: as Quality)
     // work items (target x restart index) per round: ~4 M -- 288 MB of per-restart keys, points and residuals
     const uint64_t round_items = (uint64_t)4 << 20;
     std::lock_guard<std::mutex> lock(c->batch_mu);
@@ -1035,7 +1036,7 @@ extern "C++" int ik_path_on_device(const optik_robot *r, DeviceCtx *c, const CSo
     size_t chunk = (size_t)std::min<uint64_t>((uint64_t)P, std::max<uint64_t>(1, round_items / R));
     chunk = std::min(chunk, std::max<size_t>(1, ((size_t)1 << 24) / per_path));
     // Speed without a step limit: restart-major hand-out, so that every path's restart 0 (its warm start) runs first
-    const uint32_t flags = (config->solution_mode == 2 && !(max_step < __builtin_huge_val())) ? OPTIK_HIP_IK_RESTART_MAJOR : 0u;
+    const uint32_t flags = (config->solution_mode == OPTIK_MODE_SPEED && !(max_step < __builtin_huge_val())) ? OPTIK_HIP_IK_RESTART_MAJOR : 0u;
     const double deadline = config->max_time > 0.0 ? config->max_time : 0.0;
     std::lock_guard<std::mutex> lock(c->batch_mu);
     optik::DeviceScope dev_scope(c->device);
@@ -1228,6 +1229,60 @@ int optik_robot_diff_ik_batch(const optik_robot *r, int64_t B, const double *x0,
                 if (status_out) status_out[row] = h_st[k];
             }
         });
+    }
+    return 0;
+}
+
+// The measures of solution modes 3 and 4 for B configurations (optik_hip_manip_batch), staged as
+// optik_robot_diff_ik_batch stages its rows.
+int optik_robot_manipulability_batch(const optik_robot *r, int64_t B, const double *x, const double *ee16,
+                                     double *w_out, double *c_out) {
+    if (!r || !x) return set_err(-1, "null argument");
+    if (B < 0) return set_err(-1, "bad argument");
+    const int n = r->n;
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    // (B = 0: the kernel layer's refusals of the chain alone -- prismatic joints -- before anything is staged)
+    if (optik_hip_manip_batch(c->chain, nullptr, nullptr, 0, nullptr, nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (B == 0 || (!w_out && !c_out)) return 0;
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    std::lock_guard<std::mutex> lock(c->batch_mu);
+    optik::DeviceScope dev_scope(c->device);
+    if (!dev_scope.ok()) return set_err(-1, "hipSetDevice failed");
+    const int64_t chunk = B < ((int64_t)1 << 18) ? B : ((int64_t)1 << 18);
+    // per row: q n | w 1 | c 1 doubles
+    const size_t need = (size_t)(n + 2) * (size_t)chunk;
+    if (need > c->batch_cap) {
+        if (c->d_batch) (void)hipFree(c->d_batch);
+        if (c->h_batch) (void)hipHostFree(c->h_batch);
+        c->d_batch = nullptr; c->h_batch = nullptr; c->batch_cap = 0;
+        if (hipMalloc(&c->d_batch, sizeof(double) * need) != hipSuccess
+            || hipHostMalloc(&c->h_batch, sizeof(double) * need) != hipSuccess)
+            return set_err(-1, "batch workspace allocation failed");
+        c->batch_cap = need;
+    }
+    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+        const size_t L = (size_t)(B - b0 < chunk ? B - b0 : chunk);
+        double *h_q = c->h_batch, *h_w = h_q + (size_t)n * L, *h_c = h_w + L;
+        double *d_q = c->d_batch, *d_w = d_q + (size_t)n * L, *d_c = d_w + L;
+        parallel_ranges(L, [&](size_t k0, size_t k1) {
+            for (size_t k = k0; k < k1; ++k) {
+                const size_t row = (size_t)b0 + k;
+                for (int i = 0; i < n; ++i) h_q[(size_t)i * L + k] = x[row * n + i];
+            }
+        });
+        if (hipMemcpyAsync(d_q, h_q, sizeof(double) * (size_t)n * L, hipMemcpyHostToDevice, nullptr) != hipSuccess)
+            return set_err(-1, "upload failed");
+        if (optik_hip_manip_batch(c->chain, ee16 ? ee7 : nullptr, d_q, (int64_t)L, w_out ? d_w : nullptr,
+                                  c_out ? d_c : nullptr, nullptr))
+            return set_err(-1, optik_hip_last_error());
+        if (hipMemcpyAsync(h_w, d_w, sizeof(double) * 2 * L, hipMemcpyDeviceToHost, nullptr) != hipSuccess
+            || hipStreamSynchronize(nullptr) != hipSuccess)
+            return set_err(-1, "download failed");
+        if (w_out) std::memcpy(w_out + b0, h_w, sizeof(double) * L);
+        if (c_out) std::memcpy(c_out + b0, h_c, sizeof(double) * L);
     }
     return 0;
 }

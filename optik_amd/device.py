@@ -105,6 +105,24 @@ class HipChain:
             _ptr(v_max), B if v_max.dim() == 2 else 0, B, _ptr(alpha), _ptr(v), _ptr(status), _stream_ptr()))
         return alpha, v, status
 
+    def manip_batch(self, q, ee_offset7=None):
+        """The measures of solution modes "manipulability" / "condition" for every column of q [n, B] (float64 cuda
+        tensor): (w [B], c [B]) -- w = product of the min(n, 6) largest singular values of the body Jacobian, c =
+        sigma_min / sigma_max (csrc/manip_measure.hpp; include/optik_hip.h: optik_hip_manip_batch).  Stream-ordered.
+        The keys ik_batch / ik_solutions / ik_path report in these modes are -w / -c."""
+        if not (isinstance(q, torch.Tensor) and q.is_cuda and q.dtype == torch.float64 and q.dim() == 2
+                and q.shape[0] == self.n and q.is_contiguous()):
+            raise ValueError(f"q must be a contiguous float64 cuda tensor [n, B] with n = {self.n}")
+        B = q.shape[1]
+        w = torch.empty(B, dtype=torch.float64, device=q.device)
+        c = torch.empty(B, dtype=torch.float64, device=q.device)
+        ee = np.ascontiguousarray(ee_offset7, dtype=np.float64) if ee_offset7 is not None else None
+        if ee is not None and ee.shape != (7,):
+            raise ValueError("ee_offset7 must be 7 numbers: t, then the quaternion i, j, k, w")
+        nat.check(nat.lib().optik_hip_manip_batch(self._h, _dp(ee) if ee is not None else None, _ptr(q), B,
+                                                  _ptr(w), _ptr(c), _stream_ptr()))
+        return w, c
+
     def seed_batch(self, first, count):
         q = torch.empty((self.n, count), dtype=torch.float64, device=self.device)
         nat.check(nat.lib().optik_hip_seed_batch(self._h, int(first), int(count), _ptr(q), _stream_ptr()))

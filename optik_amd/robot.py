@@ -38,6 +38,7 @@ def _bind(L):
                                            C.POINTER(C.c_uint64)]
     L.optik_robot_ik_path.argtypes = [vp, C.POINTER(nat.SolverConfigC), C.c_int32, C.c_int32, dp, C.c_uint32, dp, dp,
                                       C.c_double, dp, dp, C.POINTER(C.c_uint64), dp, C.POINTER(C.c_int32)]
+    L.optik_robot_manipulability_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp]
     L.optik_robot_fk_ex.argtypes = [vp, dp, dp, dp]
     L.optik_robot_diff_ik_ex.argtypes = [vp, dp, dp, dp, dp, C.POINTER(C.c_double), dp]
     L.optik_robot_diff_ik_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_int32)]
@@ -94,8 +95,11 @@ class SolverConfig:
     def __init__(self, solution_mode="speed", max_time=0.1, max_restarts=U64_MAX, tol_f=1e-6,
                  tol_df=-1.0, tol_dx=-1.0, linear_weight=(1.0, 1.0, 1.0),
                  angular_weight=(1.0, 1.0, 1.0)):
-        if solution_mode not in ("speed", "quality"):
-            raise ValueError("solution_mode must be 'speed' or 'quality'")  # config.rs:10-20
+        # config.rs:10-20; "manipulability" and "condition" are extensions (include/optik_hip.h: OPTIK_MODE_*):
+        # every restart runs, as under "quality", and the success with the largest measure of Robot.manipulability
+        # wins (w, resp. c)
+        if solution_mode not in nat.SOLUTION_MODES:
+            raise ValueError("solution_mode must be 'speed', 'quality', 'manipulability' or 'condition'")
         if max_time == 0.0 and max_restarts == 0:
             # optik-py/src/lib.rs:45-47
             raise ValueError("no time or restart limit applied (solver would run forever)")
@@ -422,6 +426,33 @@ class Robot:
         alpha, v, found = self.diff_ik_batch_arrays(x0s, V_WE, v_max, ee_offset)
         al, vs = alpha.tolist(), v.tolist()
         return [(al[b], vs[b]) if ok else None for b, ok in enumerate(found.tolist())]
+
+    def manipulability_batch_arrays(self, xs, ee_offset=None):
+        """The measures of solution modes "manipulability" and "condition" (extension) for B configurations:
+        `xs` [B, n] -> (w [B], c [B]).  w = sqrt(det G) is the product of the min(n, 6) largest singular values of
+        the body Jacobian, c = sigma_min / sigma_max in [0, 1] (G = J^T J for n <= 6, J J^T otherwise); both 0
+        where G is not numerically positive definite.  The Jacobian is joint_jacobian's, unscaled (metres and
+        radians); TRAC-IK's joint-limit penalty is not applied.  The IK modes rank successes by exactly these
+        numbers (include/optik.h: optik_robot_manipulability_batch)."""
+        n = self.num_positions()
+        xs = np.asarray(xs, dtype=np.float64)
+        if xs.ndim != 2 or xs.shape[1] != n:
+            raise ValueError(f"xs must be [B, n] with n = {n}, got {list(xs.shape)}")
+        B = xs.shape[0]
+        xs = np.ascontiguousarray(xs)
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        w, c = np.zeros(B), np.zeros(B)
+        rc = self._L.optik_robot_manipulability_batch(self._h, B, _dp(xs), _dp(ee) if ee is not None else None,
+                                                      _dp(w), _dp(c))
+        if rc < 0:
+            raise RuntimeError(_err(self._L))
+        return w, c
+
+    def manipulability(self, x, ee_offset=None):
+        """(w, c) of one configuration: see manipulability_batch_arrays."""
+        x = self._check_x(x)
+        w, c = self.manipulability_batch_arrays(x[None], ee_offset)
+        return float(w[0]), float(c[0])
 
     # -- extensions ---------------------------------------------------------------
     def chain_tables(self):
