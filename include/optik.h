@@ -168,6 +168,23 @@ int optik_robot_diff_ik_batch(const optik_robot *robot, int64_t B, const double 
  * optik_robot_ik*, optik_robot_ik_solutions and optik_robot_ik_path, and are scheduled there as Quality. */
 int optik_robot_manipulability_batch(const optik_robot *robot, int64_t B, const double *x, const double *ee_offset16,
                                      double *w_out, double *c_out);
+/* The collision filter (extension; include/optik_hip.h: optik_hip_chain_set_collision_model and what follows it).
+ * Host arrays, checked before any device work (rc -1 and the reason in optik_robot_last_error: the refusals of
+ * optik_hip_chain_set_collision_model / _set_world, and a model on a chain with prismatic joints), kept with the
+ * robot and applied to every device chain it has or creates later (optik_robot_set_devices included).  While a model
+ * with S >= 1 is set, every IK entry point returns free successes only: Speed runs every restart of a launch and
+ * returns the lowest-index free success (set_parallelism has no effect on it), Quality and modes 3 and 4 the best
+ * free success, ik_solutions free successes only, ik_path free waypoints only.  S = 0 clears the model. */
+int optik_robot_set_collision_model(optik_robot *robot, const int32_t *frames, const double *centers3,
+                                    const double *radii, int32_t S, const int32_t *pairs2, int32_t P, double margin);
+int optik_robot_set_world(optik_robot *robot, const double *spheres4, int32_t Ms, const double *boxes10, int32_t Mb);
+/* x [B][n] -> frames16_out [B][n + 2][16]: every frame as a column-major 4x4 (as optik_robot_fk_ex writes it; frame
+ * n + 1 is fk's pose).  ee_offset16 may be NULL.  On the robot's first device; rc 0 or -1. */
+int optik_robot_link_frames_batch(const optik_robot *robot, int64_t B, const double *x, const double *ee_offset16,
+                                  double *frames16_out);
+/* x [B][n] -> clearance_out [B], free_out [B] (1 iff clearance >= margin); either may be NULL.  rc 0 or -1. */
+int optik_robot_collision_batch(const optik_robot *robot, int64_t B, const double *x, const double *ee_offset16,
+                                double *clearance_out, uint8_t *free_out);
 int optik_robot_fk_ex(const optik_robot *robot, const double *x, const double *ee_offset16,
                       double *pose16_out);
 int optik_robot_joint_jacobian_ex(const optik_robot *robot, const double *x,

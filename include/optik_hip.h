@@ -148,6 +148,48 @@ int optik_hip_diff_ik_batch(const optik_hip_chain *chain, const double *ee_offse
 int optik_hip_manip_batch(const optik_hip_chain *chain, const double *ee_offset7, const double *d_q, int64_t B,
                           double *d_w, double *d_c, void *stream);
 
+/* The collision filter (extension; the arithmetic: csrc/collision_measure.hpp).
+ * A chain with n joint positions has n + 2 frames: 0 the base (identity), k = 1 .. n the pose after joint k's motion,
+ * n + 1 the end effector (the pose fk_batch returns, with the call's ee_offset7).  The model: S robot spheres, each
+ * (frame index, centre in that frame, radius >= 0), S <= OPTIK_HIP_MAX_COLLISION_SPHERES; P self pairs (a, b), a != b,
+ * P <= OPTIK_HIP_MAX_COLLISION_PAIRS; a margin >= 0.  The world, in the base frame: spheres4 [Ms][4] (centre,
+ * radius) and boxes10 [Mb][10] (t, unit quaternion i, j, k, w, half extents), up to OPTIK_HIP_MAX_WORLD_OBSTACLES
+ * of each.  The clearance of a configuration is the minimum of every (robot sphere, obstacle) signed distance and
+ * every self-pair distance: +inf with nothing to check, NaN for a NaN configuration.  It is free iff
+ * clearance >= margin.
+ *
+ * The filter is active exactly while the chain has a model with S >= 1 (S = 0 clears it).  Then every solver launch
+ * (optik_hip_ik_batch, optik_hip_ik_host, optik_hip_ik_solutions, optik_hip_ik_path) runs a key kernel after the
+ * solver (and after the key pass of modes 3 and 4), on the same stream, before any selection: each success that
+ * is not free gets the key +inf and is never chosen.  Speed is scheduled as Quality (EARLY_EXIT, FIND_ANY and the
+ * single-call claim have no effect; every restart runs to its end) with Speed's keys: its winner is the lowest-index
+ * free success.  d_status and d_x are left as the solver wrote them, so a rejected restart still shows a success
+ * status; optik_hip_collision_batch on d_x gives the reason.  Without a model nothing of this runs.
+ *
+ * set_collision_model / set_world take host arrays, wait for the chain's device to finish the work in flight and
+ * replace the whole model / world (Ms = Mb = 0: an empty world).  Refused with OPTIK_HIP_EINVAL, before any device
+ * work: a frame index outside 0 .. n + 1, a non-finite centre, a NaN or negative radius or half extent, a pair index
+ * out of range or a == b, a NaN, infinite or negative margin, a box quaternion with |q|^2 more than 1e-9 from 1,
+ * counts over the limits; with OPTIK_HIP_EUNSUPPORTED: a model (S >= 1) on a chain with prismatic joints. */
+#define OPTIK_HIP_MAX_COLLISION_SPHERES 256
+#define OPTIK_HIP_MAX_COLLISION_PAIRS 4096
+#define OPTIK_HIP_MAX_WORLD_OBSTACLES 65536
+int optik_hip_chain_set_collision_model(optik_hip_chain *chain, const int32_t *frames, const double *centers3,
+                                        const double *radii, int32_t S, const int32_t *pairs2, int32_t P,
+                                        double margin);
+int optik_hip_chain_set_world(optik_hip_chain *chain, const double *spheres4, int32_t Ms, const double *boxes10,
+                              int32_t Mb);
+/* All n + 2 frames of B configurations d_q [n][B] -> d_frames [B][n + 2][7] (pose7: t, quaternion i, j, k, w);
+ * frame n + 1 equals fk_batch's pose bit for bit.  Revolute chains of 1 .. 16 joint positions (prismatic:
+ * OPTIK_HIP_EUNSUPPORTED).  Stream-ordered. */
+int optik_hip_link_frames_batch(const optik_hip_chain *chain, const double *ee_offset7, const double *d_q, int64_t B,
+                                double *d_frames, void *stream);
+/* The clearance d_clearance [B] of B configurations d_q [n][B] against the chain's model and world, and the free flag
+ * d_free [B] (1 iff clearance >= margin); either may be NULL.  Without a model: clearance +inf (NaN for a NaN
+ * configuration), free 1 unless NaN.  Stream-ordered; refused as optik_hip_link_frames_batch. */
+int optik_hip_collision_batch(const optik_hip_chain *chain, const double *ee_offset7, const double *d_q, int64_t B,
+                              double *d_clearance, uint8_t *d_free, void *stream);
+
 /* Restart seeds: ChaCha8Rng::seed_from_u64(42), set_stream(i), one uniform draw
  * per joint (lib.rs:358-370, 86-91) for i = first .. first+count-1 -> d_q [n][count]. */
 int optik_hip_seed_batch(const optik_hip_chain *chain, uint64_t first, int64_t count, double *d_q,

@@ -124,6 +124,11 @@ def lib():
     L.optik_hip_fk_batch.argtypes = [vp, dp, vp, C.c_int64, vp, vp, vp]
     L.optik_hip_seed_batch.argtypes = [vp, C.c_uint64, C.c_int64, vp, vp]
     L.optik_hip_manip_batch.argtypes = [vp, dp, vp, C.c_int64, vp, vp, vp]
+    ip = C.POINTER(C.c_int32)
+    L.optik_hip_chain_set_collision_model.argtypes = [vp, ip, dp, dp, C.c_int32, ip, C.c_int32, C.c_double]
+    L.optik_hip_chain_set_world.argtypes = [vp, dp, C.c_int32, dp, C.c_int32]
+    L.optik_hip_link_frames_batch.argtypes = [vp, dp, vp, C.c_int64, vp, vp]
+    L.optik_hip_collision_batch.argtypes = [vp, dp, vp, C.c_int64, vp, vp, vp]
     L.optik_hip_diff_ik_batch.argtypes = [vp, dp, vp, vp, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, vp, vp]
     L.optik_hip_ik_batch.argtypes = [vp, C.POINTER(SolverConfigC), vp, vp, C.c_int32, dp,
                                      C.c_uint64, C.c_uint64, C.c_uint32, C.c_double,

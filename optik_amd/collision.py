@@ -1,0 +1,96 @@
+"""The collision filter's model and world on the host (extension; include/optik_hip.h: the collision filter,
+DESIGN.md section 5.12).
+
+A chain of n joint positions has n + 2 frames: 0 the base, k = 1 .. n the pose after joint k's motion, n + 1 the end
+effector.  A robot model is a list of spheres, each fixed in one of those frames, a list of self pairs and a margin;
+the world is spheres [M, 4] (centre, radius) and oriented boxes [M, 10] (t, unit quaternion i, j, k, w, half
+extents) in the base frame.  Everything here only shapes arrays: the distances are computed by the kernels
+(csrc/ik_collision.hip), and the arguments are checked again, with the same words, by the C layer.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+MAX_SPHERES = 256      # OPTIK_HIP_MAX_COLLISION_SPHERES
+MAX_PAIRS = 4096       # OPTIK_HIP_MAX_COLLISION_PAIRS
+MAX_OBSTACLES = 65536  # OPTIK_HIP_MAX_WORLD_OBSTACLES, of each kind
+
+
+def auto_pairs(frames):
+    """Every sphere pair (a, b), a < b, whose frames differ by 2 or more: spheres on the same or on neighbouring
+    frames overlap at the joint between them in every configuration, so they are not checked against each other."""
+    f = np.asarray(frames, dtype=np.int64).ravel()
+    a, b = np.triu_indices(len(f), k=1)
+    keep = np.abs(f[a] - f[b]) >= 2
+    return np.stack([a[keep], b[keep]], axis=1).astype(np.int32).reshape(-1, 2)
+
+
+def model_arrays(frames, centers, radii, self_pairs="auto", margin=0.0):
+    """(frames int32 [S], centers [S, 3], radii [S], pairs int32 [P, 2], margin) in the layout of the C ABI.
+    self_pairs: "auto" (auto_pairs), None (no pairs) or [P, 2] sphere indices.  Shapes are checked here; values
+    (frame range, radii, pair indices, margin) by the C layer."""
+    frames = np.ascontiguousarray(np.asarray(frames).ravel(), dtype=np.int32)
+    S = len(frames)
+    centers = np.ascontiguousarray(np.asarray(centers, dtype=np.float64).reshape(S, 3) if S else np.zeros((0, 3)))
+    radii = np.ascontiguousarray(np.broadcast_to(np.asarray(radii, dtype=np.float64), (S,)), dtype=np.float64)
+    if isinstance(self_pairs, str):
+        if self_pairs != "auto":
+            raise ValueError("self_pairs must be 'auto', None or a [P, 2] array of sphere indices")
+        pairs = auto_pairs(frames)
+    elif self_pairs is None:
+        pairs = np.zeros((0, 2), dtype=np.int32)
+    else:
+        pairs = np.asarray(self_pairs)
+        if pairs.size and (pairs.ndim != 2 or pairs.shape[1] != 2):
+            raise ValueError("self_pairs must be [P, 2] sphere indices")
+        pairs = pairs.reshape(-1, 2)
+        if pairs.size and not np.issubdtype(pairs.dtype, np.integer):
+            raise ValueError("self_pairs must hold integer sphere indices")
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+    return frames, centers, radii, pairs, float(margin)
+
+
+def world_arrays(spheres=None, boxes=None):
+    """(spheres [Ms, 4], boxes [Mb, 10]) in the layout of the C ABI; None means none of that kind."""
+    sph = np.zeros((0, 4)) if spheres is None else np.asarray(spheres, dtype=np.float64)
+    box = np.zeros((0, 10)) if boxes is None else np.asarray(boxes, dtype=np.float64)
+    if sph.size == 0:
+        sph = np.zeros((0, 4))
+    if box.size == 0:
+        box = np.zeros((0, 10))
+    if sph.ndim != 2 or sph.shape[1] != 4:
+        raise ValueError("spheres must be [M, 4]: centre x, y, z, radius")
+    if box.ndim != 2 or box.shape[1] != 10:
+        raise ValueError("boxes must be [M, 10]: t (3), unit quaternion i, j, k, w (4), half extents (3)")
+    return np.ascontiguousarray(sph), np.ascontiguousarray(box)
+
+
+def spheres_along_chain(robot, radius, per_link):
+    """A sphere model for a chain without collision geometry: spheres of `radius` along every segment between
+    consecutive frame origins.  Segment k runs from frame k's origin to frame k + 1's -- the joint origin's offset
+    (frame n to n + 1: the tip joint's, without any ee_offset), which does not depend on the configuration -- and
+    its spheres sit in frame k.  `per_link` spheres are spread evenly over the part of the segment that keeps 1.5
+    radii from both joints; segments shorter than 3 radii get none.  The gap keeps the spheres of two segments joined
+    by a zero-length one ("auto" pairs: frames 2 apart) from overlapping in every configuration; the price is that
+    the joints themselves and short links (a wrist, a flange) are not covered.  Returns (frames, centers, radii) for
+    Robot.set_collision_model."""
+    radius = float(radius)
+    per_link = int(per_link)
+    if not (radius > 0.0) or per_link < 1:
+        raise ValueError("radius must be > 0 and per_link >= 1")
+    tables = robot.chain_tables()
+    origins = np.asarray(tables["origins"])
+    gap = 1.5 * radius
+    frames, centers = [], []
+    for k in range(len(origins)):
+        off = origins[k, :3]
+        length = float(np.linalg.norm(off))
+        if length < 2.0 * gap:
+            continue
+        fr = [0.5] if per_link == 1 else list(np.linspace(gap / length, 1.0 - gap / length, per_link))
+        for s in fr:
+            frames.append(k)
+            centers.append(s * off)
+    frames = np.array(frames, dtype=np.int32)
+    centers = np.array(centers, dtype=np.float64).reshape(-1, 3)
+    return frames, centers, np.full(len(frames), radius)

@@ -1,0 +1,120 @@
+// collision_measure.hpp -- the signed distances of the collision filter, one source for the host and the device
+// (optik_hip_collision_batch and the key pass of a chain with a collision model, optik_hip.h).
+//
+// The robot is a set of spheres, each fixed in one frame of the chain; the world is a set of spheres and oriented boxes
+// in the base frame.  A pose is 7 doubles: t (3), then the unit quaternion i, j, k, w.  A chain of n joint positions
+// has n + 2 frames: 0 the base (identity), k = 1 .. n the pose after joint k's motion, n + 1 the end effector (with the
+// tip joint and the call's ee_offset: the pose fk_batch returns).
+//
+// The exact operation order (the tests depend on it; both sides are compiled with -ffp-contract=off and use only
+// the correctly rounded + - * / sqrt, fabs and fmin / fmax, so one source gives one set of bits wherever it runs):
+//
+//  1. A robot sphere's centre in the base frame: p = t_f + qrot(q_f, c), component by component t_f.x + r.x, where
+//     qrot is ik_math.hpp's (nalgebra's) order: u = 2 * (v x c) (the cross product first, then each component times
+//     2.0), w = v x u, r = (u * q.w + w) + c, with v = (q.i, q.j, q.k).
+//  2. Sphere to sphere, a = the robot sphere (or the first sphere of a self pair), b = the other:
+//         dx = a.x - b.x (dy, dz alike);  d = ((sqrt((dx * dx + dy * dy) + dz * dz) - r_a) - r_b)
+//  3. Sphere (centre p, radius r) to box (t_b, unit q_b, half extents h):
+//         l = qrot(conj(q_b), p - t_b)  (p - t_b component by component; conj = (-i, -j, -k, w))
+//         e_i = fabs(l_i) - h_i
+//         outside = sqrt((fmax(e0, 0)^2 + fmax(e1, 0)^2) + fmax(e2, 0)^2)   (x^2 = x * x)
+//         inside  = fmin(fmax(fmax(e0, e1), e2), 0)
+//         d = (outside + inside) - r
+//  4. The clearance of a configuration is the minimum of every (robot sphere, world sphere), every (robot sphere,
+//     world box) and every self-pair distance; +inf when there is nothing to check; NaN when any frame holds a NaN
+//     (every frame after a NaN joint position does).  The configuration is free iff clearance >= margin.
+//
+// The minimum is exact in any order: every term is computed on its own from the frames, so a pass that visits the
+// terms in another order -- the device groups the spheres by frame and the pairs by frame pair -- gets the same
+// value, and a pass that only classifies (the key pass) may stop at the first term below the margin: it decides
+// "not free" exactly as the full clearance does.  Terms are never NaN once the frames are not (the inputs are
+// refused unless centres are finite and radii / half extents are >= 0; +inf radii give -inf).
+//
+// Plain host C++ compiles this header too (no HIP runtime): tests/test_collision_host.py drives it with g++.
+#pragma once
+
+#include <cmath>
+#include <cstdint>
+
+#if defined(__HIP__) || defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define OPTIK_CM_HD __host__ __device__
+#else
+#define OPTIK_CM_HD
+#endif
+
+namespace optik {
+namespace coll {
+
+// qrot of ik_math.hpp, restated for plain C++: r' = (u * w + (v x u)) + r with u = 2 (v x r).
+OPTIK_CM_HD inline void qrot3(const double *q, const double *r, double *o) {
+    const double vx = q[0], vy = q[1], vz = q[2], w = q[3];
+    double ux = vy * r[2] - vz * r[1], uy = vz * r[0] - vx * r[2], uz = vx * r[1] - vy * r[0];
+    ux *= 2.0; uy *= 2.0; uz *= 2.0;
+    const double cx = vy * uz - vz * uy, cy = vz * ux - vx * uz, cz = vx * uy - vy * ux;
+    o[0] = ux * w + cx + r[0];
+    o[1] = uy * w + cy + r[1];
+    o[2] = uz * w + cz + r[2];
+}
+
+// Step 1: the centre c (in the frame of pose7) in the base frame.
+OPTIK_CM_HD inline void sphere_centre(const double *pose7, const double *c, double *p) {
+    double r[3];
+    qrot3(pose7 + 3, c, r);
+    p[0] = pose7[0] + r[0];
+    p[1] = pose7[1] + r[1];
+    p[2] = pose7[2] + r[2];
+}
+
+// Step 2.
+OPTIK_CM_HD inline double sphere_sphere(const double *a, double ra, const double *b, double rb) {
+    const double dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
+    return sqrt((dx * dx + dy * dy) + dz * dz) - ra - rb;
+}
+
+// Step 3.  box10 = t (3), q (4: i, j, k, w), half extents (3).
+OPTIK_CM_HD inline double sphere_box(const double *p, double r, const double *box10) {
+    const double d[3] = {p[0] - box10[0], p[1] - box10[1], p[2] - box10[2]};
+    const double qc[4] = {-box10[3], -box10[4], -box10[5], box10[6]};
+    double l[3];
+    qrot3(qc, d, l);
+    const double e0 = fabs(l[0]) - box10[7], e1 = fabs(l[1]) - box10[8], e2 = fabs(l[2]) - box10[9];
+    const double o0 = fmax(e0, 0.0), o1 = fmax(e1, 0.0), o2 = fmax(e2, 0.0);
+    const double outside = sqrt((o0 * o0 + o1 * o1) + o2 * o2);
+    const double inside = fmin(fmax(fmax(e0, e1), e2), 0.0);
+    return (outside + inside) - r;
+}
+
+OPTIK_CM_HD inline bool pose_has_nan(const double *pose7) {
+    bool nan = false;
+    for (int i = 0; i < 7; ++i) nan = nan || (pose7[i] != pose7[i]);
+    return nan;
+}
+
+// Step 4, the reference form (the tests' g++ driver): frames [nf][7]; robot spheres: frame index, centre [S][3],
+// radius [S]; self pairs [P][2]; world spheres [Ms][4] (centre, radius), boxes [Mb][10].  Terms in the order
+// (sphere s, world spheres, world boxes) for s ascending, then the pairs.
+inline double clearance(int nf, const double *frames, int S, const int32_t *frame, const double *centers,
+                        const double *radii, int P, const int32_t *pairs, int Ms, const double *wspheres, int Mb,
+                        const double *wboxes) {
+    for (int f = 0; f < nf; ++f)
+        if (pose_has_nan(frames + 7 * f)) return NAN;
+    double c = INFINITY;
+    for (int s = 0; s < S; ++s) {
+        double p[3];
+        sphere_centre(frames + 7 * frame[s], centers + 3 * s, p);
+        for (int m = 0; m < Ms; ++m) c = fmin(c, sphere_sphere(p, radii[s], wspheres + 4 * m, wspheres[4 * m + 3]));
+        for (int m = 0; m < Mb; ++m) c = fmin(c, sphere_box(p, radii[s], wboxes + 10 * m));
+    }
+    for (int k = 0; k < P; ++k) {
+        const int a = pairs[2 * k], b = pairs[2 * k + 1];
+        double pa[3], pb[3];
+        sphere_centre(frames + 7 * frame[a], centers + 3 * a, pa);
+        sphere_centre(frames + 7 * frame[b], centers + 3 * b, pb);
+        c = fmin(c, sphere_sphere(pa, radii[a], pb, radii[b]));
+    }
+    return c;
+}
+
+}  // namespace coll
+}  // namespace optik

@@ -1,0 +1,153 @@
+// collision_model.hpp -- the collision model and world of a chain on the host: the argument checks shared by the
+// kernel layer (optik_hip_chain_set_collision_model / _set_world, ik_collision.hip) and the robot layer
+// (optik_robot_set_collision_model / _set_world, robot_host.cpp), and the device layout of the model.
+//
+// The device model keeps the robot spheres grouped by frame and the self pairs grouped by (frame of a, frame of b):
+// the kernels look a frame up once per group, not once per sphere (collision_measure.hpp: the minimum is exact in
+// any order, and every pair keeps the (a, b) orientation it was given, so its distance has the same bits).
+#pragma once
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/optik_hip.h"
+
+namespace optik {
+namespace coll {
+
+constexpr int MAX_SPHERES = OPTIK_HIP_MAX_COLLISION_SPHERES;  // 256: a sphere index fits a byte
+constexpr int MAX_PAIRS = OPTIK_HIP_MAX_COLLISION_PAIRS;      // 4096
+constexpr int MAX_OBSTACLES = OPTIK_HIP_MAX_WORLD_OBSTACLES;  // 65 536 of each kind
+constexpr int MAX_FRAMES = 16 + 2;                            // n + 2 frames, n <= 16
+constexpr int MAX_GROUPS = MAX_FRAMES * MAX_FRAMES;
+static_assert(MAX_SPHERES <= 256, "pairs hold sphere indices in a byte each");
+
+// What the kernels stage in LDS (only the first S spheres, P pairs and n_groups groups are read).
+struct ModelDev {
+    double sph[MAX_SPHERES][4];            // centre in its frame, radius; grouped by frame
+    uint16_t pair[MAX_PAIRS];              // a | b << 8 (indices into sph); grouped by (frame a, frame b)
+    uint16_t frame_begin[MAX_FRAMES + 2];  // spheres of frame f: [frame_begin[f], frame_begin[f + 1])
+    uint16_t group_begin[MAX_GROUPS + 4];  // pairs of group g: [group_begin[g], group_begin[g + 1])
+    uint8_t group_fa[MAX_GROUPS], group_fb[MAX_GROUPS];
+};
+static_assert(sizeof(ModelDev) % 8 == 0, "staged as doubles");
+
+inline bool finite3(const double *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
+inline bool nonneg(double v) { return v >= 0.0; }  // (false for NaN)
+
+// 0, or OPTIK_HIP_EINVAL with the reason in err.  n: the chain's joint positions (frames 0 .. n + 1).
+inline int check_model(int n, const int32_t *frames, const double *centers3, const double *radii, int32_t S,
+                       const int32_t *pairs2, int32_t P, double margin, std::string &err) {
+    if (S < 0 || S > MAX_SPHERES) { err = "collision model: sphere count must be in 0..256"; return OPTIK_HIP_EINVAL; }
+    if (P < 0 || P > MAX_PAIRS) { err = "collision model: self pair count must be in 0..4096"; return OPTIK_HIP_EINVAL; }
+    if (S > 0 && (!frames || !centers3 || !radii)) { err = "collision model: null sphere array"; return OPTIK_HIP_EINVAL; }
+    if (P > 0 && !pairs2) { err = "collision model: null pair array"; return OPTIK_HIP_EINVAL; }
+    if (!(margin >= 0.0) || !std::isfinite(margin)) {
+        err = "collision model: margin must be finite and >= 0";
+        return OPTIK_HIP_EINVAL;
+    }
+    for (int s = 0; s < S; ++s) {
+        if (frames[s] < 0 || frames[s] > n + 1) {
+            err = "collision model: sphere " + std::to_string(s) + " has frame " + std::to_string(frames[s])
+                  + " outside 0.." + std::to_string(n + 1);
+            return OPTIK_HIP_EINVAL;
+        }
+        if (!finite3(centers3 + 3 * s)) {
+            err = "collision model: sphere " + std::to_string(s) + " has a non-finite centre";
+            return OPTIK_HIP_EINVAL;
+        }
+        if (!nonneg(radii[s])) {
+            err = "collision model: sphere " + std::to_string(s) + " has a NaN or negative radius";
+            return OPTIK_HIP_EINVAL;
+        }
+    }
+    for (int k = 0; k < P; ++k) {
+        const int32_t a = pairs2[2 * k], b = pairs2[2 * k + 1];
+        if (a < 0 || a >= S || b < 0 || b >= S) {
+            err = "collision model: self pair " + std::to_string(k) + " has a sphere index out of range";
+            return OPTIK_HIP_EINVAL;
+        }
+        if (a == b) {
+            err = "collision model: self pair " + std::to_string(k) + " pairs a sphere with itself";
+            return OPTIK_HIP_EINVAL;
+        }
+    }
+    return 0;
+}
+
+inline int check_world(const double *spheres4, int32_t Ms, const double *boxes10, int32_t Mb, std::string &err) {
+    if (Ms < 0 || Ms > MAX_OBSTACLES || Mb < 0 || Mb > MAX_OBSTACLES) {
+        err = "world: at most 65536 spheres and 65536 boxes";
+        return OPTIK_HIP_EINVAL;
+    }
+    if ((Ms > 0 && !spheres4) || (Mb > 0 && !boxes10)) { err = "world: null obstacle array"; return OPTIK_HIP_EINVAL; }
+    for (int m = 0; m < Ms; ++m) {
+        const double *s = spheres4 + 4 * m;
+        if (!finite3(s)) { err = "world: sphere " + std::to_string(m) + " has a non-finite centre"; return OPTIK_HIP_EINVAL; }
+        if (!nonneg(s[3])) {
+            err = "world: sphere " + std::to_string(m) + " has a NaN or negative radius";
+            return OPTIK_HIP_EINVAL;
+        }
+    }
+    for (int m = 0; m < Mb; ++m) {
+        const double *b = boxes10 + 10 * m;
+        if (!finite3(b)) { err = "world: box " + std::to_string(m) + " has a non-finite centre"; return OPTIK_HIP_EINVAL; }
+        const double q2 = b[3] * b[3] + b[4] * b[4] + b[5] * b[5] + b[6] * b[6];
+        if (!(std::fabs(q2 - 1.0) <= 1e-9)) {
+            err = "world: box " + std::to_string(m) + " needs a unit quaternion (|q|^2 within 1e-9 of 1)";
+            return OPTIK_HIP_EINVAL;
+        }
+        if (!nonneg(b[7]) || !nonneg(b[8]) || !nonneg(b[9])) {
+            err = "world: box " + std::to_string(m) + " has a NaN or negative half extent";
+            return OPTIK_HIP_EINVAL;
+        }
+    }
+    return 0;
+}
+
+// The device layout of a checked model; returns the number of pair groups.
+inline int pack_model(int n, const int32_t *frames, const double *centers3, const double *radii, int32_t S,
+                      const int32_t *pairs2, int32_t P, ModelDev &m) {
+    std::memset(&m, 0, sizeof m);
+    const int nf = n + 2;
+    std::vector<int> order((size_t)S), slot((size_t)S);
+    for (int s = 0; s < S; ++s) order[(size_t)s] = s;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return frames[x] < frames[y]; });
+    for (int i = 0; i < S; ++i) {
+        const int s = order[(size_t)i];
+        slot[(size_t)s] = i;
+        for (int k = 0; k < 3; ++k) m.sph[i][k] = centers3[3 * s + k];
+        m.sph[i][3] = radii[s];
+    }
+    for (int f = 0, i = 0; f <= nf; ++f) {
+        while (i < S && frames[order[(size_t)i]] < f) ++i;
+        m.frame_begin[f] = (uint16_t)i;
+    }
+    std::vector<int> porder((size_t)P);
+    for (int k = 0; k < P; ++k) porder[(size_t)k] = k;
+    auto gkey = [&](int k) { return frames[pairs2[2 * k]] * nf + frames[pairs2[2 * k + 1]]; };
+    std::stable_sort(porder.begin(), porder.end(), [&](int x, int y) { return gkey(x) < gkey(y); });
+    int g = -1, last = -1;
+    for (int i = 0; i < P; ++i) {
+        const int k = porder[(size_t)i];
+        const int a = pairs2[2 * k], b = pairs2[2 * k + 1];
+        m.pair[i] = (uint16_t)(slot[(size_t)a] | (slot[(size_t)b] << 8));
+        if (gkey(k) != last) {
+            ++g;
+            last = gkey(k);
+            m.group_begin[g] = (uint16_t)i;
+            m.group_fa[g] = (uint8_t)frames[a];
+            m.group_fb[g] = (uint8_t)frames[b];
+        }
+    }
+    const int groups = g + 1;
+    m.group_begin[groups] = (uint16_t)P;
+    return groups;
+}
+
+}  // namespace coll
+}  // namespace optik

@@ -4,7 +4,8 @@
 //
 // The solvers are launched from here and defined in their own translation units: the lane-per-restart form
 // (ik_lane_kernel.hip), the quad solver (ik_quad_kernel.hip), the general run-time-n solver (ik_wide_kernel.hip);
-// optik_hip_ik_batch picks one by launch size and joint count.  The key pass of solution modes 3 and 4: ik_manip.hip.
+// optik_hip_ik_batch picks one by launch size and joint count.  The key pass of solution modes 3 and 4: ik_manip.hip;
+// that of the collision filter: ik_collision.hip.
 // The selection kernels: ik_select.hip,
 // ik_solutions.hip and ik_path.hip; the batch operators: ik_batch_ops.hip.  No CPU fallback exists: every entry point fails loudly without a device.
 #include <algorithm>
@@ -170,6 +171,8 @@ void optik_hip_chain_destroy(optik_hip_chain *ch) {
     if (ch->first_success) hipFree(ch->first_success);
     if (ch->sol_pick) hipFree(ch->sol_pick);
     if (ch->path_carry) hipFree(ch->path_carry);
+    if (ch->coll_dev) hipFree(ch->coll_dev);
+    if (ch->world_dev) hipFree(ch->world_dev);
     if (ch->tmp_x) hipFree(ch->tmp_x);
     if (ch->tmp_f) hipFree(ch->tmp_f);
     if (ch->tmp_key) hipFree(ch->tmp_key);
@@ -294,6 +297,9 @@ static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, con
                     "solution_mode must be 1 (Quality), 2 (Speed), 3 (Manipulability) or 4 (Condition)");
     // Manipulability and Condition: scheduled as Quality, then a key pass over the successes (ik_manip.hip)
     const bool manip = mode == OPTIK_MODE_MANIPULABILITY || mode == OPTIK_MODE_CONDITION;
+    // the collision filter: Speed is scheduled as Quality (no early exit, no claim; Speed's keys), and a key pass
+    // after the solver rejects the successes that are not free (ik_collision.hip)
+    const bool coll = ch && ch->coll_S > 0;
     const uint64_t R = restart_end - restart_begin;
     if (restart_end > 1 || restart_begin > 0)
         for (int k = 0; k < ch->n; ++k)
@@ -328,7 +334,7 @@ static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, con
     if (stream != ch->clean_stream) { ch->queue_clean = false; ch->fs_clean = 0; }
     if (!ch->queue_clean) HIP_TRY(hipMemsetAsync(ch->queue, 0, sizeof(unsigned long long), stream));
     ch->queue_clean = false;  // (until this launch's selection kernel has put it back)
-    const bool early = (flags & OPTIK_HIP_IK_EARLY_EXIT) && mode == OPTIK_MODE_SPEED;
+    const bool early = (flags & OPTIK_HIP_IK_EARLY_EXIT) && mode == OPTIK_MODE_SPEED && !coll;
     size_t fs_clean_after = ch->fs_clean;  // (a launch without early exit leaves the words alone)
     if (early) {
         if ((size_t)T > ch->fs_cap) {
@@ -343,10 +349,11 @@ static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, con
         fs_clean_after = std::max(ch->fs_clean, (size_t)T);  // once the selection kernel has put words [0, T) back
         ch->fs_clean = 0;
     }
-    // the selection needs the per-restart x / f / key: scratch if the caller skips them (the key pass of modes 3 and
-    // 4 reads x: grown here, before the launch -- nothing is allocated between the solve and the selection)
+    // the selection needs the per-restart x / f / key: scratch if the caller skips them (the key passes of modes 3
+    // and 4 and of the collision filter read x: grown here, before the launch -- nothing is allocated between the
+    // solve and the selection)
     double *px = out->d_x, *pf = out->d_f, *pk = nullptr;
-    need_x = need_x || (want_sel && manip);
+    need_x = need_x || (want_sel && (manip || coll));
     if (want_sel) {
         const bool need_xf = (!px || !pf) && (need_x || need_f);
         if (cols > ch->tmp_cols) {
@@ -525,6 +532,9 @@ static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, con
     // modes 3 and 4: the successes' keys become -w / -c, on the same stream, before any selection kernel
     if (manip && pk)
         if (int rc = manip_key_launch(ch, mode, ee_offset7, px, pk, cols, stream)) return rc;
+    // the collision filter: the successes that are not free get key +inf, behind the key pass above
+    if (coll && pk)
+        if (int rc = collision_key_launch(ch, ee_offset7, px, pk, cols, stream)) return rc;
     ch->last.grid = grid; ch->last.block = WAVE; ch->last.lds_bytes = lds; ch->last.tiles = n_tiles;
 
     sl->px = px; sl->pf = pf; sl->pk = pk;
@@ -732,8 +742,9 @@ int optik_hip_ik_host(optik_hip_chain *ch, const optik_solver_config *cfg, const
     // succeed writes its answer to a host-coherent block and the call returns as soon as it is there; the launch's
     // other restarts notice the flag at their next evaluation and the launch ends behind the caller's back (the
     // next launch of the chain queues behind it).  Without a success the call ends with the launch, as before.
+    // (not under the collision filter: the first success may not be free)
     const bool claim = T == 1 && (flags & OPTIK_HIP_IK_FIND_ANY) && (flags & OPTIK_HIP_IK_EARLY_EXIT)
-                       && cfg->solution_mode == OPTIK_MODE_SPEED;
+                       && cfg->solution_mode == OPTIK_MODE_SPEED && ch->coll_S == 0;
     if (claim && !ch->hw_claim) {
         HIP_TRY(hipHostMalloc(&ch->hw_claim, sizeof(unsigned long long) * (3 + MAX_DOF), hipHostMallocCoherent));
         std::memset(ch->hw_claim, 0, sizeof(unsigned long long) * (3 + MAX_DOF));

@@ -6,6 +6,7 @@
 //   ik_solutions.hip   up to K distinct solutions per target over the same keys (optik_hip_ik_solutions)
 //   ik_path.hip        the per-waypoint selection of warm-started paths (optik_hip_ik_path)
 //   ik_manip.hip       the manipulability / condition keys of solution modes 3 and 4, optik_hip_manip_batch
+//   ik_collision.hip   the collision filter: model and world, its key pass, link frames and clearance batches
 //   ik_batch_ops.hip   objective / gradient, FK / Jacobian and seed batches, the test probes
 //   ik_lane_kernel.hip, ik_quad_kernel.hip, ik_wide_kernel.hip    the restart solvers (one restart loop each)
 #pragma once
@@ -24,6 +25,9 @@
 #include "ik_wide_launch.hpp"
 
 namespace optik {
+namespace coll {
+struct ModelDev;  // collision_model.hpp
+}  // namespace coll
 namespace host {
 
 constexpr int WAVE = 64;
@@ -117,6 +121,12 @@ hipError_t path_select_launch(const PathSelectLaunch &s, int P, hipStream_t stre
 // (OPTIK_MODE_CONDITION) of that restart's x; one kernel on `stream`.  0 or a fail() code.
 int manip_key_launch(const optik_hip_chain *ch, int mode, const double *ee_offset7, const double *x, double *key,
                      size_t cols, hipStream_t stream);
+
+// ---- the collision filter (ik_collision.hip) ---------------------------------------------------------------
+// Sets to +inf every key < +inf of a solver launch (x [n][cols], key [cols]) whose x is not free against the chain's
+// model and world; one kernel on `stream`, after the key pass of modes 3 and 4.  Only while ch->coll_S > 0.
+int collision_key_launch(const optik_hip_chain *ch, const double *ee_offset7, const double *x, double *key,
+                         size_t cols, hipStream_t stream);
 
 // ---- options ---------------------------------------------------------------------------------------------
 // Every tuning option of the kernel layer, in one place.  The defaults come from the environment ONCE, at the
@@ -217,6 +227,14 @@ struct optik_hip_chain {
     size_t sol_pick_cap = 0;
     double *path_carry = nullptr;  // optik_hip_ik_path: [P][n] the seeds of the next waypoint
     size_t path_carry_cap = 0;     // doubles
+    // the collision filter (ik_collision.hip): active while coll_S > 0; the model as the kernels stage it, the world
+    // as spheres [world_Ms][4] then boxes [world_Mb][10]
+    int coll_S = 0, coll_P = 0, coll_groups = 0;
+    double coll_margin = 0.0;
+    optik::coll::ModelDev *coll_dev = nullptr;
+    double *world_dev = nullptr;
+    size_t world_cap = 0;  // doubles
+    int world_Ms = 0, world_Mb = 0;
     // (what the last launch's selection kernel left behind: the work-item counter at 0, this many leading
     // first-success words at ~0 -- a launch that finds them so skips its fill commands)
     // (host-side knowledge that holds for launches ORDERED behind that selection kernel: the stream it ran on is kept

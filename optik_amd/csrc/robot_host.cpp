@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/optik.h"
+#include "collision_model.hpp"
 #include "device_scope.hpp"
 #include "diff_ik_lp.hpp"
 #include "urdf_chain.hpp"
@@ -71,6 +72,16 @@ struct optik_robot {
     mutable std::vector<std::unique_ptr<DeviceCtx>> devs;
     // over how many of them the widest round of the last ik / ik_batch call was actually cut (optik_robot_last_parts)
     mutable std::atomic<int32_t> last_parts{0};
+    // the collision model and world (optik_robot_set_collision_model / _set_world), kept on the host and applied to
+    // every device chain, also to those created later; the filter is active while coll_frames is not empty
+    std::vector<int32_t> coll_frames, coll_pairs;
+    std::vector<double> coll_centers, coll_radii;
+    double coll_margin = 0.0;
+    std::vector<double> world_spheres, world_boxes;
+    bool collision_active() const {
+        std::lock_guard<std::mutex> lock(mu);
+        return !coll_frames.empty();
+    }
 };
 
 namespace {
@@ -175,6 +186,20 @@ DeviceCtx *device_ctx(const optik_robot *r, size_t k = 0) {
         if (c->d_scratch) { (void)hipFree(c->d_scratch); c->d_scratch = nullptr; }
         optik_hip_chain_destroy(h);
         g_robot_err = "GPU scratch allocation failed";
+        return nullptr;
+    }
+    // (a model or world set before this chain existed)
+    if ((!r->coll_frames.empty()
+         && optik_hip_chain_set_collision_model(h, r->coll_frames.data(), r->coll_centers.data(), r->coll_radii.data(),
+                                                (int32_t)r->coll_frames.size(), r->coll_pairs.data(),
+                                                (int32_t)(r->coll_pairs.size() / 2), r->coll_margin))
+        || ((!r->world_spheres.empty() || !r->world_boxes.empty())
+            && optik_hip_chain_set_world(h, r->world_spheres.data(), (int32_t)(r->world_spheres.size() / 4),
+                                         r->world_boxes.data(), (int32_t)(r->world_boxes.size() / 10)))) {
+        g_robot_err = std::string("collision model upload failed: ") + optik_hip_last_error();
+        (void)hipFree(c->d_scratch); c->d_scratch = nullptr;
+        (void)hipHostFree(c->h_scratch); c->h_scratch = nullptr;
+        optik_hip_chain_destroy(h);
         return nullptr;
     }
     (void)hipDeviceGetAttribute(&c->num_cus, hipDeviceAttributeMultiprocessorCount, devid);
@@ -564,7 +589,10 @@ int optik_robot_ik_pose(const optik_robot *r, const CSolverConfig *config, const
     const uint64_t big_batch = (uint64_t)1 << ((quality && !(config->max_time > 0.0)) ? OPTIK_QUALITY_BATCH_LOG2 : 20);
     const uint64_t big_from = 262144;              // (from this many restarts left on: rounds of big_batch)
     const size_t G = device_count(r);
-    const uint32_t speed_flags = OPTIK_HIP_IK_EARLY_EXIT | (r->parallelism != 1 ? OPTIK_HIP_IK_FIND_ANY : 0u);
+    // (the collision filter: Speed takes Quality's route -- no early exit, no first-success claim -- and keeps its keys,
+    // so the first round with a free success holds the lowest-index one and still ends the call)
+    const uint32_t speed_flags = r->collision_active() ? 0u
+                                 : OPTIK_HIP_IK_EARLY_EXIT | (r->parallelism != 1 ? OPTIK_HIP_IK_FIND_ANY : 0u);
     struct Part {
         DeviceCtx *ctx = nullptr;
         uint64_t begin = 0, end = 0, widx = UINT64_MAX;
@@ -686,6 +714,10 @@ int ik_batch_on_device(const optik_robot *r, DeviceCtx *c, const CSolverConfig *
     };
     const uint64_t max_restarts = config->max_restarts > 0 ? config->max_restarts : UINT64_MAX;
     const bool quality = config->solution_mode != OPTIK_MODE_SPEED;  // (Manipulability, Condition: as Quality)
+    // (the collision filter: Speed takes Quality's route in each round; a target's first round with a free success
+    // holds its lowest-index one, so the target still leaves the batch then.  Read before batch_mu: the setters take
+    // the robot's lock first)
+    const bool filtered = r->collision_active();
     // work items (target x restart index) per round: ~4 M -- 288 MB of per-restart keys, points and residuals
     const uint64_t round_items = (uint64_t)4 << 20;
     std::lock_guard<std::mutex> lock(c->batch_mu);
@@ -767,9 +799,9 @@ int ik_batch_on_device(const optik_robot *r, DeviceCtx *c, const CSolverConfig *
         // targets or more, on a streaming engine: retired in round 5, the single launch is 15 - 28 % faster at every
         // size where the engine was used -- profiles/r5a_engine_retire_probe.txt.)
         const uint32_t mode_flags =
-            quality ? 0u : (OPTIK_HIP_IK_EARLY_EXIT | (r->parallelism != 1 ? OPTIK_HIP_IK_FIND_ANY : 0u));
+            (quality || filtered) ? 0u : (OPTIK_HIP_IK_EARLY_EXIT | (r->parallelism != 1 ? OPTIK_HIP_IK_FIND_ANY : 0u));
         const int rck = optik_hip_ik_batch(c->chain, config, d_t, d_x0, (int32_t)L, ee7, begin, end,
-                                           mode_flags | ((!quality && begin < 256) ? OPTIK_HIP_IK_RESTART_MAJOR : 0u),
+                                           mode_flags | ((!quality && !filtered && begin < 256) ? OPTIK_HIP_IK_RESTART_MAJOR : 0u),
                                            deadline, &o, nullptr);
         if (rck) { err = optik_hip_last_error(); return -1; }
         if (hipMemcpyAsync(h_out, d_wx, sizeof(double) * (size_t)(n + 3) * L, hipMemcpyDeviceToHost, nullptr) != hipSuccess
@@ -1036,7 +1068,9 @@ extern "C++" int ik_path_on_device(const optik_robot *r, DeviceCtx *c, const CSo
     size_t chunk = (size_t)std::min<uint64_t>((uint64_t)P, std::max<uint64_t>(1, round_items / R));
     chunk = std::min(chunk, std::max<size_t>(1, ((size_t)1 << 24) / per_path));
     // Speed without a step limit: restart-major hand-out, so that every path's restart 0 (its warm start) runs first
-    const uint32_t flags = (config->solution_mode == OPTIK_MODE_SPEED && !(max_step < __builtin_huge_val())) ? OPTIK_HIP_IK_RESTART_MAJOR : 0u;
+    // (not under the collision filter: every restart runs to its end there, as in Quality)
+    const uint32_t flags = (config->solution_mode == OPTIK_MODE_SPEED && !(max_step < __builtin_huge_val())
+                            && !r->collision_active()) ? OPTIK_HIP_IK_RESTART_MAJOR : 0u;
     const double deadline = config->max_time > 0.0 ? config->max_time : 0.0;
     std::lock_guard<std::mutex> lock(c->batch_mu);
     optik::DeviceScope dev_scope(c->device);
@@ -1285,6 +1319,148 @@ int optik_robot_manipulability_batch(const optik_robot *r, int64_t B, const doub
         if (c_out) std::memcpy(c_out + b0, h_c, sizeof(double) * L);
     }
     return 0;
+}
+
+// The collision model and world (include/optik.h): checked on the host before any device work, kept with the robot
+// and applied to every device chain it has (device_ctx applies them to the chains it creates later).
+int optik_robot_set_collision_model(optik_robot *r, const int32_t *frames, const double *centers3, const double *radii,
+                                    int32_t S, const int32_t *pairs2, int32_t P, double margin) {
+    if (!r) return set_err(-1, "null argument");
+    std::string err;
+    if (optik::coll::check_model(r->n, frames, centers3, radii, S, pairs2, P, margin, err)) return set_err(-1, err);
+    if (S > 0)
+        for (int32_t t : r->types)
+            if (t == optik_host::PRISMATIC)
+                return set_err(-1, "collision: prismatic joints are not supported (IK refuses such chains)");
+    std::lock_guard<std::mutex> lock(r->mu);
+    if (S > 0) {
+        r->coll_frames.assign(frames, frames + S);
+        r->coll_centers.assign(centers3, centers3 + 3 * (size_t)S);
+        r->coll_radii.assign(radii, radii + S);
+        if (P > 0) r->coll_pairs.assign(pairs2, pairs2 + 2 * (size_t)P);
+        else r->coll_pairs.clear();
+        r->coll_margin = margin;
+    } else {
+        r->coll_frames.clear(); r->coll_centers.clear(); r->coll_radii.clear(); r->coll_pairs.clear();
+        r->coll_margin = 0.0;
+    }
+    for (auto &c : r->devs) {
+        if (!c->chain) continue;
+        std::lock_guard<std::mutex> batch_lock(c->batch_mu);
+        if (optik_hip_chain_set_collision_model(c->chain, frames, centers3, radii, S, pairs2, P, margin))
+            return set_err(-1, optik_hip_last_error());
+    }
+    return 0;
+}
+
+int optik_robot_set_world(optik_robot *r, const double *spheres4, int32_t Ms, const double *boxes10, int32_t Mb) {
+    if (!r) return set_err(-1, "null argument");
+    std::string err;
+    if (optik::coll::check_world(spheres4, Ms, boxes10, Mb, err)) return set_err(-1, err);
+    std::lock_guard<std::mutex> lock(r->mu);
+    if (Ms > 0) r->world_spheres.assign(spheres4, spheres4 + 4 * (size_t)Ms);
+    else r->world_spheres.clear();
+    if (Mb > 0) r->world_boxes.assign(boxes10, boxes10 + 10 * (size_t)Mb);
+    else r->world_boxes.clear();
+    for (auto &c : r->devs) {
+        if (!c->chain) continue;
+        std::lock_guard<std::mutex> batch_lock(c->batch_mu);
+        if (optik_hip_chain_set_world(c->chain, spheres4, Ms, boxes10, Mb)) return set_err(-1, optik_hip_last_error());
+    }
+    return 0;
+}
+
+namespace {
+
+// B rows of x [B][n] through one of the per-configuration kernels of ik_collision.hip on the robot's first device, in
+// chunks of 2^18 rows: per row `out_doubles` doubles come back (what `run` has the kernel write into d_out [L][..]).
+extern "C++" template <class Run, class Take>
+int collision_rows(const optik_robot *r, int64_t B, const double *x, size_t out_doubles, Run run, Take take) {
+    const int n = r->n;
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    std::lock_guard<std::mutex> lock(c->batch_mu);
+    optik::DeviceScope dev_scope(c->device);
+    if (!dev_scope.ok()) return set_err(-1, "hipSetDevice failed");
+    const int64_t chunk = B < ((int64_t)1 << 18) ? B : ((int64_t)1 << 18);
+    const size_t need = ((size_t)n + out_doubles) * (size_t)chunk;
+    if (need > c->batch_cap) {
+        if (c->d_batch) (void)hipFree(c->d_batch);
+        if (c->h_batch) (void)hipHostFree(c->h_batch);
+        c->d_batch = nullptr; c->h_batch = nullptr; c->batch_cap = 0;
+        if (hipMalloc(&c->d_batch, sizeof(double) * need) != hipSuccess
+            || hipHostMalloc(&c->h_batch, sizeof(double) * need) != hipSuccess)
+            return set_err(-1, "batch workspace allocation failed");
+        c->batch_cap = need;
+    }
+    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+        const size_t L = (size_t)(B - b0 < chunk ? B - b0 : chunk);
+        double *h_q = c->h_batch, *h_out = h_q + (size_t)n * L;
+        double *d_q = c->d_batch, *d_out = d_q + (size_t)n * L;
+        parallel_ranges(L, [&](size_t k0, size_t k1) {
+            for (size_t k = k0; k < k1; ++k)
+                for (int i = 0; i < n; ++i) h_q[(size_t)i * L + k] = x[((size_t)b0 + k) * n + i];
+        });
+        if (hipMemcpyAsync(d_q, h_q, sizeof(double) * (size_t)n * L, hipMemcpyHostToDevice, nullptr) != hipSuccess)
+            return set_err(-1, "upload failed");
+        if (run(c->chain, d_q, (int64_t)L, d_out)) return set_err(-1, optik_hip_last_error());
+        if (hipMemcpyAsync(h_out, d_out, sizeof(double) * out_doubles * L, hipMemcpyDeviceToHost, nullptr) != hipSuccess
+            || hipStreamSynchronize(nullptr) != hipSuccess)
+            return set_err(-1, "download failed");
+        take((size_t)b0, L, h_out);
+    }
+    return 0;
+}
+
+}  // namespace
+
+int optik_robot_link_frames_batch(const optik_robot *r, int64_t B, const double *x, const double *ee16,
+                                  double *frames16_out) {
+    if (!r || !x || !frames16_out) return set_err(-1, "null argument");
+    if (B < 0) return set_err(-1, "bad argument");
+    DeviceCtx *c0 = device_ctx(r);
+    if (!c0) return -1;
+    // (B = 0: the kernel layer's refusals of the chain alone -- prismatic joints -- before anything is staged)
+    if (optik_hip_link_frames_batch(c0->chain, nullptr, nullptr, 0, nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (B == 0) return 0;
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    const size_t nf = (size_t)r->n + 2;
+    return collision_rows(
+        r, B, x, 7 * nf,
+        [&](optik_hip_chain *ch, const double *d_q, int64_t L, double *d_out) {
+            return optik_hip_link_frames_batch(ch, ee16 ? ee7 : nullptr, d_q, L, d_out, nullptr);
+        },
+        [&](size_t b0, size_t L, const double *h_out) {
+            parallel_ranges(L * nf, [&](size_t k0, size_t k1) {
+                for (size_t k = k0; k < k1; ++k) mat16_from_pose7(h_out + 7 * k, frames16_out + 16 * (b0 * nf + k));
+            });
+        });
+}
+
+int optik_robot_collision_batch(const optik_robot *r, int64_t B, const double *x, const double *ee16,
+                                double *clearance_out, uint8_t *free_out) {
+    if (!r || !x) return set_err(-1, "null argument");
+    if (B < 0) return set_err(-1, "bad argument");
+    DeviceCtx *c0 = device_ctx(r);
+    if (!c0) return -1;
+    if (optik_hip_collision_batch(c0->chain, nullptr, nullptr, 0, nullptr, nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (B == 0 || (!clearance_out && !free_out)) return 0;
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    // per row: the clearance, then the free flag in the bytes of a second double
+    return collision_rows(
+        r, B, x, 2,
+        [&](optik_hip_chain *ch, const double *d_q, int64_t L, double *d_out) {
+            return optik_hip_collision_batch(ch, ee16 ? ee7 : nullptr, d_q, L, d_out,
+                                             reinterpret_cast<uint8_t *>(d_out + L), nullptr);
+        },
+        [&](size_t b0, size_t L, const double *h_out) {
+            if (clearance_out) std::memcpy(clearance_out + b0, h_out, sizeof(double) * L);
+            if (free_out) std::memcpy(free_out + b0, reinterpret_cast<const uint8_t *>(h_out + L), L);
+        });
 }
 
 // lib.rs:165-183 of optik-cpp: the joint velocities only, malloc'ed; NULL = no solution.

@@ -123,6 +123,63 @@ class HipChain:
                                                   _ptr(w), _ptr(c), _stream_ptr()))
         return w, c
 
+    # -- the collision filter (include/optik_hip.h) --------------------------------------
+    def set_collision_model(self, frames, centers, radii, self_pairs="auto", margin=0.0):
+        """The chain's robot spheres (frame index in 0 .. n + 1, centre in that frame, radius), self pairs ("auto":
+        every pair whose frames differ by >= 2; None: none; or [P, 2] indices) and margin.  While a model with at
+        least one sphere is set, ik_batch / ik_host / ik_solutions / ik_path return free successes only (Speed: the
+        lowest-index one; every restart runs to its end).  Waits for the device; host arrays."""
+        from .collision import model_arrays
+        f, c, r, p, m = model_arrays(frames, centers, radii, self_pairs, margin)
+        nat.check(nat.lib().optik_hip_chain_set_collision_model(
+            self._h, f.ctypes.data_as(C.POINTER(C.c_int32)), _dp(c), _dp(r), len(f),
+            p.ctypes.data_as(C.POINTER(C.c_int32)), len(p), m))
+
+    def clear_collision_model(self):
+        """No model: every path runs exactly as without the filter."""
+        nat.check(nat.lib().optik_hip_chain_set_collision_model(self._h, None, None, None, 0, None, 0, 0.0))
+
+    def set_world(self, spheres=None, boxes=None):
+        """Replaces the world: spheres [M, 4] (centre, radius), boxes [M, 10] (t, unit quaternion i, j, k, w, half
+        extents), in the base frame."""
+        from .collision import world_arrays
+        sph, box = world_arrays(spheres, boxes)
+        nat.check(nat.lib().optik_hip_chain_set_world(self._h, _dp(sph), len(sph), _dp(box), len(box)))
+
+    def _check_q(self, q):
+        if not (isinstance(q, torch.Tensor) and q.is_cuda and q.dtype == torch.float64 and q.dim() == 2
+                and q.shape[0] == self.n and q.is_contiguous()):
+            raise ValueError(f"q must be a contiguous float64 cuda tensor [n, B] with n = {self.n}")
+        return q.shape[1]
+
+    @staticmethod
+    def _ee7(ee_offset7):
+        ee = np.ascontiguousarray(ee_offset7, dtype=np.float64) if ee_offset7 is not None else None
+        if ee is not None and ee.shape != (7,):
+            raise ValueError("ee_offset7 must be 7 numbers: t, then the quaternion i, j, k, w")
+        return ee
+
+    def link_frames_batch(self, q, ee_offset7=None):
+        """All n + 2 frames of every column of q [n, B]: [B, n + 2, 7] (t, quaternion i, j, k, w); frame n + 1 is
+        fk_batch's pose.  Stream-ordered."""
+        B = self._check_q(q)
+        ee = self._ee7(ee_offset7)
+        frames = torch.empty((B, self.n + 2, 7), dtype=torch.float64, device=q.device)
+        nat.check(nat.lib().optik_hip_link_frames_batch(self._h, _dp(ee) if ee is not None else None, _ptr(q), B,
+                                                        _ptr(frames), _stream_ptr()))
+        return frames
+
+    def collision_batch(self, q, ee_offset7=None):
+        """(clearance [B], free [B] bool) of every column of q [n, B] against the chain's model and world
+        (csrc/collision_measure.hpp).  Stream-ordered."""
+        B = self._check_q(q)
+        ee = self._ee7(ee_offset7)
+        clearance = torch.empty(B, dtype=torch.float64, device=q.device)
+        free = torch.empty(B, dtype=torch.uint8, device=q.device)
+        nat.check(nat.lib().optik_hip_collision_batch(self._h, _dp(ee) if ee is not None else None, _ptr(q), B,
+                                                      _ptr(clearance), _ptr(free), _stream_ptr()))
+        return clearance, free.bool()
+
     def seed_batch(self, first, count):
         q = torch.empty((self.n, count), dtype=torch.float64, device=self.device)
         nat.check(nat.lib().optik_hip_seed_batch(self._h, int(first), int(count), _ptr(q), _stream_ptr()))

@@ -40,6 +40,11 @@ def _bind(L):
                                       C.c_double, dp, dp, C.POINTER(C.c_uint64), dp, C.POINTER(C.c_int32)]
     L.optik_robot_manipulability_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp]
     L.optik_robot_fk_ex.argtypes = [vp, dp, dp, dp]
+    ip = C.POINTER(C.c_int32)
+    L.optik_robot_set_collision_model.argtypes = [vp, ip, dp, dp, C.c_int32, ip, C.c_int32, C.c_double]
+    L.optik_robot_set_world.argtypes = [vp, dp, C.c_int32, dp, C.c_int32]
+    L.optik_robot_link_frames_batch.argtypes = [vp, C.c_int64, dp, dp, dp]
+    L.optik_robot_collision_batch.argtypes = [vp, C.c_int64, dp, dp, dp, C.POINTER(C.c_uint8)]
     L.optik_robot_diff_ik_ex.argtypes = [vp, dp, dp, dp, dp, C.POINTER(C.c_double), dp]
     L.optik_robot_diff_ik_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_int32)]
     L.optik_robot_joint_jacobian_ex.argtypes = [vp, dp, dp, dp]
@@ -453,6 +458,69 @@ class Robot:
         x = self._check_x(x)
         w, c = self.manipulability_batch_arrays(x[None], ee_offset)
         return float(w[0]), float(c[0])
+
+    # -- the collision filter (extension; include/optik.h) --------------------------------
+    def set_collision_model(self, frames, centers, radii, self_pairs="auto", margin=0.0):
+        """Robot spheres for the collision filter: frames [S] (0 the base, k = 1 .. n after joint k, n + 1 the end
+        effector), centers [S, 3] in those frames, radii [S] (or one radius); self_pairs "auto" (every pair whose
+        frames differ by >= 2), None, or [P, 2] sphere indices; margin >= 0.  While a model is set, ik, ik_batch*,
+        ik_solutions* and ik_path* return only solutions whose clearance (collision_clearance) is >= margin; Speed
+        then returns the lowest-index free success (every restart of a launch runs).  Applied to every GPU of the
+        robot.  ValueError for a refused model (before any device work)."""
+        from .collision import model_arrays
+        f, c, r, p, m = model_arrays(frames, centers, radii, self_pairs, margin)
+        if self._L.optik_robot_set_collision_model(self._h, f.ctypes.data_as(C.POINTER(C.c_int32)), _dp(c), _dp(r),
+                                                   len(f), p.ctypes.data_as(C.POINTER(C.c_int32)), len(p), m):
+            raise ValueError(_err(self._L))
+
+    def clear_collision_model(self):
+        """No model: every IK path runs exactly as without the filter."""
+        if self._L.optik_robot_set_collision_model(self._h, None, None, None, 0, None, 0, 0.0):
+            raise RuntimeError(_err(self._L))
+
+    def set_world(self, spheres=None, boxes=None):
+        """Replaces the obstacles, in the base frame: spheres [M, 4] (centre, radius), boxes [M, 10] (t, unit
+        quaternion i, j, k, w, half extents).  ValueError for a refused world."""
+        from .collision import world_arrays
+        sph, box = world_arrays(spheres, boxes)
+        if self._L.optik_robot_set_world(self._h, _dp(sph), len(sph), _dp(box), len(box)):
+            raise ValueError(_err(self._L))
+
+    def _check_xs(self, xs):
+        n = self.num_positions()
+        xs = np.asarray(xs, dtype=np.float64)
+        if xs.ndim != 2 or xs.shape[1] != n:
+            raise ValueError(f"xs must be [B, n] with n = {n}, got {list(xs.shape)}")
+        return np.ascontiguousarray(xs)
+
+    def link_frames_batch_arrays(self, xs, ee_offset=None):
+        """All n + 2 frames of B configurations xs [B, n] -> [B, n + 2, 4, 4] row-major poses (frame n + 1 is
+        fk's pose)."""
+        xs = self._check_xs(xs)
+        B, n = xs.shape
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        out = np.zeros((B, n + 2, 16))
+        if self._L.optik_robot_link_frames_batch(self._h, B, _dp(xs), _dp(ee) if ee is not None else None, _dp(out)):
+            raise RuntimeError(_err(self._L))
+        return out.reshape(B, n + 2, 4, 4).transpose(0, 1, 3, 2).copy()
+
+    def collision_clearance_batch_arrays(self, xs, ee_offset=None):
+        """(clearance [B], free [B] bool) of B configurations xs [B, n] against the model and world (+inf clearance
+        without a model)."""
+        xs = self._check_xs(xs)
+        B = xs.shape[0]
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        clr, free = np.zeros(B), np.zeros(B, dtype=np.uint8)
+        if self._L.optik_robot_collision_batch(self._h, B, _dp(xs), _dp(ee) if ee is not None else None, _dp(clr),
+                                               free.ctypes.data_as(C.POINTER(C.c_uint8))):
+            raise RuntimeError(_err(self._L))
+        return clr, free.astype(bool)
+
+    def collision_clearance(self, x, ee_offset=None):
+        """The clearance of one configuration (see collision_clearance_batch_arrays)."""
+        x = self._check_x(x)
+        clr, _ = self.collision_clearance_batch_arrays(x[None], ee_offset)
+        return float(clr[0])
 
     # -- extensions ---------------------------------------------------------------
     def chain_tables(self):
