@@ -185,6 +185,18 @@ int optik_robot_link_frames_batch(const optik_robot *robot, int64_t B, const dou
 /* x [B][n] -> clearance_out [B], free_out [B] (1 iff clearance >= margin); either may be NULL.  rc 0 or -1. */
 int optik_robot_collision_batch(const optik_robot *robot, int64_t B, const double *x, const double *ee_offset16,
                                 double *clearance_out, uint8_t *free_out);
+/* The motion check (extension; include/optik_hip.h: optik_hip_collision_motion_batch and what precedes it).  B segments
+ * xa, xb [B][n] row-major at `resolution` (finite, > 0) -> clearance_out [B], free_out [B], first_out [B], steps_out
+ * [B]; any may be NULL (clearance_out NULL: the call only classifies).  On the robot's first device, 65 536 segments
+ * per launch.  rc 0, or -1: null argument, B < 0, a bad resolution, prismatic joints. */
+int optik_robot_collision_motion_batch(const optik_robot *robot, int64_t B, const double *xa, const double *xb,
+                                       double resolution, const double *ee_offset16, double *clearance_out,
+                                       uint8_t *free_out, int32_t *first_out, int32_t *steps_out);
+/* The resolution h of the motion check of optik_robot_ik_path between a path's seed and each candidate (include/
+ * optik_hip.h: optik_hip_chain_set_motion_resolution): 0 (the default) is off; it acts while a collision model is
+ * set.  Kept with the robot and applied to every device chain it has or creates later (optik_robot_set_devices
+ * included).  The other IK entry points ignore it.  rc 0, or -1 for a NaN, negative or infinite h. */
+int optik_robot_set_motion_resolution(optik_robot *robot, double h);
 int optik_robot_fk_ex(const optik_robot *robot, const double *x, const double *ee_offset16,
                       double *pose16_out);
 int optik_robot_joint_jacobian_ex(const optik_robot *robot, const double *x,

@@ -190,6 +190,41 @@ int optik_hip_link_frames_batch(const optik_hip_chain *chain, const double *ee_o
 int optik_hip_collision_batch(const optik_hip_chain *chain, const double *ee_offset7, const double *d_q, int64_t B,
                               double *d_clearance, uint8_t *d_free, void *stream);
 
+/* The motion check (extension; the arithmetic: csrc/motion_measure.hpp): is the straight
+ * joint-space segment qa -> qb free at a resolution h > 0 (L-infinity, radians)?  With d = max_i |qb_i - qa_i| the
+ * segment has K = max(1, (int)ceil(d / h)) steps and K + 1 samples: sample 0 is qa and sample K is qb, copied, and
+ * sample k between them is qa_i + ((double)k / (double)K) * (qb_i - qa_i).  The motion clearance is the minimum of
+ * the samples' clearances (optik_hip_collision_batch's, with the same model, world and ee_offset7), NaN if any is NaN;
+ * the motion is free iff every sample is free; first is the lowest k whose sample is not free, -1 for a free motion;
+ * steps is K.  A segment with d NaN or infinite or with K > OPTIK_HIP_MAX_MOTION_STEPS is not sampled: clearance
+ * NaN, free 0, first -1, steps -1.  Without a model: clearance +inf and free 1 (NaN and 0 if a sample is NaN).  The
+ * results do not depend on the launch shape or on the order the samples are visited in.
+ *
+ * optik_hip_collision_motion_batch: B segments d_qa, d_qb [n][B] -> d_clearance [B], d_free [B], d_first [B],
+ * d_steps [B]; any output may be NULL.  With d_clearance NULL the call only classifies and skips the samples above a
+ * non-free one it has found; free, first and steps are the same.  Stream-ordered, no host synchronisation; its
+ * workspace (24 bytes per segment) belongs to the chain and grows on demand, so one call per chain handle at a time,
+ * as for the solver launches.  Revolute chains of 1 .. 16 joint positions.  Refused with OPTIK_HIP_EINVAL before any
+ * device work: a NaN, infinite, zero or negative resolution, B < 0 (B = 0 is a no-op), more than 2^30 segments; with
+ * OPTIK_HIP_EUNSUPPORTED: chains with prismatic joints.
+ *
+ * optik_hip_chain_set_motion_resolution: the resolution h of optik_hip_ik_path's motion key pass; 0 (the default)
+ * switches it off; NaN, negative or infinite: OPTIK_HIP_EINVAL.  Waits for the chain's device as set_world does.
+ * The pass is active exactly while h > 0 and the chain has a collision model with S >= 1.  Then every waypoint
+ * launch of optik_hip_ik_path runs it after the solver, the key pass of modes 3 and 4 and the collision key pass, on
+ * the same stream, before the selection: for each restart with a finite key whose L-infinity distance to the path's
+ * carried seed is <= max_step, the motion seed -> x is checked at resolution h (the seed is read on the device: no
+ * host synchronisation between waypoints), and the key becomes +inf if that motion is not free (a motion that is
+ * not sampled is not free).  Successes beyond max_step are left alone: the selection rejects them.  A path whose
+ * seed is itself in collision (a start configuration, say) has no free motion from it: every waypoint of it reports
+ * no solution until the caller gives it a free start.  optik_hip_ik_batch, optik_hip_ik_host and
+ * optik_hip_ik_solutions ignore the setting; with h = 0 or without a model nothing extra is launched. */
+#define OPTIK_HIP_MAX_MOTION_STEPS 4096
+int optik_hip_collision_motion_batch(optik_hip_chain *chain, const double *ee_offset7, const double *d_qa,
+                                     const double *d_qb, int64_t B, double resolution, double *d_clearance,
+                                     uint8_t *d_free, int32_t *d_first, int32_t *d_steps, void *stream);
+int optik_hip_chain_set_motion_resolution(optik_hip_chain *chain, double h);
+
 /* Restart seeds: ChaCha8Rng::seed_from_u64(42), set_stream(i), one uniform draw
  * per joint (lib.rs:358-370, 86-91) for i = first .. first+count-1 -> d_q [n][count]. */
 int optik_hip_seed_batch(const optik_hip_chain *chain, uint64_t first, int64_t count, double *d_q,

@@ -7,6 +7,7 @@ usable, the calls raise.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -129,6 +130,8 @@ def lib():
     L.optik_hip_chain_set_world.argtypes = [vp, dp, C.c_int32, dp, C.c_int32]
     L.optik_hip_link_frames_batch.argtypes = [vp, dp, vp, C.c_int64, vp, vp]
     L.optik_hip_collision_batch.argtypes = [vp, dp, vp, C.c_int64, vp, vp, vp]
+    L.optik_hip_collision_motion_batch.argtypes = [vp, dp, vp, vp, C.c_int64, C.c_double, vp, vp, vp, vp, vp]
+    L.optik_hip_chain_set_motion_resolution.argtypes = [vp, C.c_double]
     L.optik_hip_diff_ik_batch.argtypes = [vp, dp, vp, vp, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, vp, vp]
     L.optik_hip_ik_batch.argtypes = [vp, C.POINTER(SolverConfigC), vp, vp, C.c_int32, dp,
                                      C.c_uint64, C.c_uint64, C.c_uint32, C.c_double,
@@ -148,6 +151,17 @@ def lib():
     L.optik_hip_timing_mean.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     _lib = L
     return L
+
+
+MAX_MOTION_STEPS = 4096  # include/optik_hip.h: OPTIK_HIP_MAX_MOTION_STEPS
+
+
+def check_resolution(h, allow_zero=False):
+    """The resolution of a motion check as a float: finite and > 0 (allow_zero: 0 switches the ik_path pass off)."""
+    h = float(h)
+    if not (math.isfinite(h) and (h > 0.0 or (allow_zero and h == 0.0))):
+        raise ValueError("motion resolution must be finite and " + (">= 0" if allow_zero else "> 0") + f", got {h}")
+    return h
 
 
 def check(rc: int):

@@ -173,6 +173,7 @@ void optik_hip_chain_destroy(optik_hip_chain *ch) {
     if (ch->path_carry) hipFree(ch->path_carry);
     if (ch->coll_dev) hipFree(ch->coll_dev);
     if (ch->world_dev) hipFree(ch->world_dev);
+    if (ch->motion_ws) hipFree(ch->motion_ws);
     if (ch->tmp_x) hipFree(ch->tmp_x);
     if (ch->tmp_f) hipFree(ch->tmp_f);
     if (ch->tmp_key) hipFree(ch->tmp_key);
@@ -624,6 +625,12 @@ int optik_hip_ik_path(optik_hip_chain *ch, const optik_solver_config *cfg, const
             ch->path_carry_cap = need;
         }
     }
+    // the motion check between waypoints (ik_motion.hip): one more key pass per waypoint, in front of the selection
+    const bool motion = ch->motion_h > 0.0 && ch->coll_S > 0;
+    if (motion) {
+        BIND_DEVICE(ch);
+        if (int rc = motion_reserve(ch, (long long)P * (long long)(restart_end - restart_begin))) return rc;
+    }
     optik_hip_ik_outputs none;
     std::memset(&none, 0, sizeof none);
     for (int32_t l = 0; l < L; ++l) {
@@ -634,6 +641,10 @@ int optik_hip_ik_path(optik_hip_chain *ch, const optik_solver_config *cfg, const
                                   false, nullptr, &sl))
             return rc;
         BIND_DEVICE(ch);
+        if (motion)
+            if (int rc = motion_key_launch(ch, ee_offset7, seed, sl.px, sl.pk, P, (size_t)sl.R, filter ? 1 : 0, max_step,
+                                           stream))
+                return rc;
         const size_t w = (size_t)l * (size_t)P;
         PathSelectLaunch s;
         std::memset(&s, 0, sizeof s);

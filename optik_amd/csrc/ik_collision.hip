@@ -15,118 +15,14 @@
 // frame and pairs by frame pair (collision_model.hpp), so a frame is selected once per group.  The key form reads
 // only the restarts that succeeded and leaves a wave's loop as soon as none of its lanes is still free: stopping at
 // the first term below the margin decides exactly what the full minimum decides.
-#include "collision_measure.hpp"
-#include "collision_model.hpp"
-#include "ik_host.hpp"
-#include "ik_jacobian.hpp"
-#include "ik_wide.hpp"
+#include "collision_device.hpp"
 
 using namespace optik;
 using namespace optik::host;
 using namespace optik::hostparams;
-using optik::coll::ModelDev;
+using namespace optik::colldev;
 
 namespace {
-
-enum : int { FORM_FRAMES = 0, FORM_BATCH = 1, FORM_KEY = 2 };
-
-struct CollLaunch {
-    const ChainDev *chain;       // n <= 8
-    const WideChainDev *wchain;  // 9 .. 16 joint positions
-    EvalParams ep;               // only the ee_offset part is used
-    const ModelDev *model;       // null: no model (S = 0)
-    int S, P, groups, nf;        // spheres, pairs, pair groups, frames (n + 2)
-    double margin;
-    const double *wsph;          // [Ms][4]
-    const double *wbox;          // [Mb][10]
-    int Ms, Mb;
-    const double *q;             // [n][B]: the configurations (key form: the launch's per-restart x)
-    long long B;
-    double *key;                 // key form: [B], read, and set to +inf where the success is not free
-    double *clearance;           // batch form: [B] or null
-    uint8_t *free_flag;          // batch form: [B] or null
-    double *frames;              // frames form: [B][nf][7]
-};
-
-// The model's S spheres, P pairs and group tables into LDS (whole words; the struct is 8-byte aligned).
-__device__ __forceinline__ void stage_model(ModelDev &dst, const CollLaunch &a) {
-    {
-        const double *s = &a.model->sph[0][0];
-        double *d = &dst.sph[0][0];
-        for (int i = threadIdx.x; i < 4 * a.S; i += blockDim.x) d[i] = s[i];
-    }
-    {
-        const uint32_t *s = reinterpret_cast<const uint32_t *>(a.model->pair);
-        uint32_t *d = reinterpret_cast<uint32_t *>(dst.pair);
-        for (int i = threadIdx.x; i < (a.P + 1) / 2; i += blockDim.x) d[i] = s[i];
-    }
-    {
-        constexpr int off = (int)(offsetof(ModelDev, frame_begin) / sizeof(double));
-        constexpr int nd = (int)(sizeof(ModelDev) / sizeof(double)) - off;
-        static_assert(offsetof(ModelDev, frame_begin) % sizeof(double) == 0, "tables start on a double");
-        const double *s = reinterpret_cast<const double *>(a.model) + off;
-        double *d = reinterpret_cast<double *>(&dst) + off;
-        for (int i = threadIdx.x; i < nd; i += blockDim.x) d[i] = s[i];
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ bool wave_any_lane(bool p) { return __ballot(p) != 0ull; }
-
-// The clearance of one configuration (FORM_BATCH) or whether it is free (FORM_KEY: the return value is 0.0 for free,
-// anything else for not free; a wave stops once none of its lanes is free).  frame_of(f, pose7) gives frame f.
-template <int FORM, class FrameFn>
-__device__ __forceinline__ double clearance_of(const ModelDev &m, const CollLaunch &a, bool nan, FrameFn &&frame_of,
-                                               bool &free_out) {
-    double c = __builtin_huge_val();
-    bool ok = !nan;
-    const double margin = a.margin;
-    if (a.Ms + a.Mb > 0) {
-        for (int f = 0; f < a.nf; ++f) {
-            const int s0 = m.frame_begin[f], s1 = m.frame_begin[f + 1];
-            if (s0 == s1) continue;
-            double fp[7];
-            frame_of(f, fp);
-            for (int s = s0; s < s1; ++s) {
-                double p[3];
-                coll::sphere_centre(fp, m.sph[s], p);
-                const double r = m.sph[s][3];
-                for (int k = 0; k < a.Ms; ++k) {
-                    const double *w = a.wsph + 4 * k;
-                    const double d = coll::sphere_sphere(p, r, w, w[3]);
-                    if (FORM == FORM_KEY) ok = ok && d >= margin;
-                    else c = fmin(c, d);
-                }
-                for (int k = 0; k < a.Mb; ++k) {
-                    const double d = coll::sphere_box(p, r, a.wbox + 10 * k);
-                    if (FORM == FORM_KEY) ok = ok && d >= margin;
-                    else c = fmin(c, d);
-                }
-                if (FORM == FORM_KEY && !wave_any_lane(ok)) { free_out = false; return 0.0; }
-            }
-        }
-    }
-    for (int g = 0; g < a.groups; ++g) {
-        double pa7[7], pb7[7];
-        frame_of(m.group_fa[g], pa7);
-        frame_of(m.group_fb[g], pb7);
-        const int k1 = m.group_begin[g + 1];
-        for (int k = m.group_begin[g]; k < k1; ++k) {
-            const int ia = m.pair[k] & 0xff, ib = m.pair[k] >> 8;
-            double pa[3], pb[3];
-            coll::sphere_centre(pa7, m.sph[ia], pa);
-            coll::sphere_centre(pb7, m.sph[ib], pb);
-            const double d = coll::sphere_sphere(pa, m.sph[ia][3], pb, m.sph[ib][3]);
-            if (FORM == FORM_KEY) ok = ok && d >= margin;
-            else c = fmin(c, d);
-        }
-        if (FORM == FORM_KEY && !wave_any_lane(ok)) { free_out = false; return 0.0; }
-    }
-    if (FORM == FORM_KEY) { free_out = ok; return 0.0; }
-    if (nan) c = __builtin_nan("");
-    free_out = c >= margin;
-    return c;
-}
 
 // What one configuration's result becomes.
 template <int FORM>
@@ -137,19 +33,6 @@ __device__ __forceinline__ void coll_store(const CollLaunch &a, long long b, dou
         if (a.clearance) a.clearance[b] = c;
         if (a.free_flag) a.free_flag[b] = free_ ? 1 : 0;
     }
-}
-
-__device__ __forceinline__ void store_pose7(double *dst, const Pose &p) {
-    dst[0] = p.t.x; dst[1] = p.t.y; dst[2] = p.t.z;
-    dst[3] = p.q.i; dst[4] = p.q.j; dst[5] = p.q.k; dst[6] = p.q.w;
-}
-
-__device__ __forceinline__ void pose7_of(const Pose &p, double (&o)[7]) {
-    o[0] = p.t.x; o[1] = p.t.y; o[2] = p.t.z; o[3] = p.q.i; o[4] = p.q.j; o[5] = p.q.k; o[6] = p.q.w;
-}
-
-__device__ __forceinline__ void identity7(double (&o)[7]) {
-    o[0] = 0.0; o[1] = 0.0; o[2] = 0.0; o[3] = 0.0; o[4] = 0.0; o[5] = 0.0; o[6] = 1.0;
 }
 
 template <int N, bool TIP, int FORM>
@@ -164,9 +47,9 @@ __device__ __forceinline__ void coll_body(const CollLaunch &a) {
         double q[N];
 #pragma unroll
         for (int i = 0; i < N; ++i) q[i] = a.q[(size_t)i * a.B + b];
-        Kin<N, TIP> kin;
-        forward_kinematics<N, TIP>(sch, a.ep, q, kin);
         if (FORM == FORM_FRAMES) {
+            Kin<N, TIP> kin;
+            forward_kinematics<N, TIP>(sch, a.ep, q, kin);
             double *dst = a.frames + (size_t)b * (size_t)(N + 2) * 7;
             const Pose id{V3{0.0, 0.0, 0.0}, Q4{0.0, 0.0, 0.0, 1.0}};
             store_pose7(dst, id);
@@ -175,29 +58,8 @@ __device__ __forceinline__ void coll_body(const CollLaunch &a) {
             store_pose7(dst + 7 * (N + 1), kin.ee);
             continue;
         }
-        bool nan = false;
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            nan = nan || kin.tf[k].t.x != kin.tf[k].t.x || kin.tf[k].t.y != kin.tf[k].t.y
-                  || kin.tf[k].t.z != kin.tf[k].t.z || kin.tf[k].q.i != kin.tf[k].q.i || kin.tf[k].q.j != kin.tf[k].q.j
-                  || kin.tf[k].q.k != kin.tf[k].q.k || kin.tf[k].q.w != kin.tf[k].q.w;
-        }
-        nan = nan || kin.ee.t.x != kin.ee.t.x || kin.ee.t.y != kin.ee.t.y || kin.ee.t.z != kin.ee.t.z
-              || kin.ee.q.i != kin.ee.q.i || kin.ee.q.j != kin.ee.q.j || kin.ee.q.k != kin.ee.q.k
-              || kin.ee.q.w != kin.ee.q.w;
-        // frame f of the configuration: a wave-uniform index, so the selection is a scalar-predicated one
-        auto frame_of = [&](int f, double (&o)[7]) {
-            f = __builtin_amdgcn_readfirstlane(f);
-            identity7(o);
-#pragma unroll
-            for (int k = 0; k < N; ++k)
-                if (f == k + 1) pose7_of(kin.tf[k], o);
-            if (f == N + 1) pose7_of(kin.ee, o);
-        };
         bool free_ = true;
-        double c = __builtin_huge_val();
-        if (a.model) c = clearance_of<FORM>(sm, a, nan, frame_of, free_);
-        else if (nan) { c = __builtin_nan(""); free_ = false; }
+        const double c = config_clearance<N, TIP, FORM == FORM_KEY ? FORM_KEY : FORM_BATCH>(sch, sm, a, q, free_);
         coll_store<FORM>(a, b, c, free_);
     }
 }
@@ -209,7 +71,7 @@ __global__ __launch_bounds__(256) void collision_batch_kernel(const CollLaunch a
 template <int N, bool TIP>
 __global__ __launch_bounds__(256) void collision_key_kernel(const CollLaunch a) { coll_body<N, TIP, FORM_KEY>(a); }
 
-// 9 .. 16 joint positions: the joint frames wide_forward writes (7 per joint) in a per-lane array.
+// 9 .. 16 joint positions (run-time n).
 template <int FORM>
 __device__ __forceinline__ void wide_coll_body(const CollLaunch &a) {
     __shared__ WideChainDev sch;
@@ -220,10 +82,11 @@ __device__ __forceinline__ void wide_coll_body(const CollLaunch &a) {
     for (long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x; b < a.B;
          b += (long long)gridDim.x * blockDim.x) {
         if (FORM == FORM_KEY && !(a.key[b] < __builtin_huge_val())) continue;
-        double q[WIDE_MAX_DOF], tf[7 * WIDE_MAX_DOF];
+        double q[WIDE_MAX_DOF];
         for (int i = 0; i < n; ++i) q[i] = a.q[(size_t)i * a.B + b];
-        const Pose ee = wide_forward(sch, a.ep, n, q, tf);
         if (FORM == FORM_FRAMES) {
+            double tf[7 * WIDE_MAX_DOF];
+            const Pose ee = wide_forward(sch, a.ep, n, q, tf);
             double *dst = a.frames + (size_t)b * (size_t)(n + 2) * 7;
             const Pose id{V3{0.0, 0.0, 0.0}, Q4{0.0, 0.0, 0.0, 1.0}};
             store_pose7(dst, id);
@@ -231,21 +94,8 @@ __device__ __forceinline__ void wide_coll_body(const CollLaunch &a) {
             store_pose7(dst + 7 * (n + 1), ee);
             continue;
         }
-        bool nan = false;
-        for (int k = 0; k < 7 * n; ++k) nan = nan || tf[k] != tf[k];
-        nan = nan || ee.t.x != ee.t.x || ee.t.y != ee.t.y || ee.t.z != ee.t.z || ee.q.i != ee.q.i
-              || ee.q.j != ee.q.j || ee.q.k != ee.q.k || ee.q.w != ee.q.w;
-        auto frame_of = [&](int f, double (&o)[7]) {
-            f = __builtin_amdgcn_readfirstlane(f);
-            if (f == 0) identity7(o);
-            else if (f == n + 1) pose7_of(ee, o);
-            else
-                for (int i = 0; i < 7; ++i) o[i] = tf[7 * (f - 1) + i];
-        };
         bool free_ = true;
-        double c = __builtin_huge_val();
-        if (a.model) c = clearance_of<FORM>(sm, a, nan, frame_of, free_);
-        else if (nan) { c = __builtin_nan(""); free_ = false; }
+        const double c = wide_config_clearance<FORM == FORM_KEY ? FORM_KEY : FORM_BATCH>(sch, sm, a, n, q, free_);
         coll_store<FORM>(a, b, c, free_);
     }
 }
@@ -254,31 +104,7 @@ __global__ __launch_bounds__(256) void wide_link_frames_batch_kernel(const CollL
 __global__ __launch_bounds__(256) void wide_collision_batch_kernel(const CollLaunch a) { wide_coll_body<FORM_BATCH>(a); }
 __global__ __launch_bounds__(256) void wide_collision_key_kernel(const CollLaunch a) { wide_coll_body<FORM_KEY>(a); }
 
-const char *const kCollPrismaticMsg =
-    "collision: prismatic joints are not supported (IK refuses such chains; the reference's Jacobian panics: "
-    "kinematics.rs:185 todo!())";
-
-void fill_launch(const optik_hip_chain *ch, const double *ee_offset7, const double *q, long long B, CollLaunch &a) {
-    std::memset(&a, 0, sizeof a);
-    a.chain = ch->dev;
-    a.wchain = ch->wdev;
-    const double one[3] = {1, 1, 1};
-    make_eval_params(one, one, ee_offset7, a.ep);
-    a.q = q;
-    a.B = B;
-    a.nf = ch->n + 2;
-    if (ch->coll_S > 0) {
-        a.model = ch->coll_dev;
-        a.S = ch->coll_S;
-        a.P = ch->coll_P;
-        a.groups = ch->coll_groups;
-        a.margin = ch->coll_margin;
-        a.Ms = ch->world_Ms;
-        a.Mb = ch->world_Mb;
-        a.wsph = ch->world_dev;
-        a.wbox = ch->world_dev ? ch->world_dev + 4 * (size_t)ch->world_Ms : nullptr;
-    }
-}
+const char *const kCollPrismaticMsg = prismatic_msg();
 
 int coll_launch(const optik_hip_chain *ch, const CollLaunch &a, int form, hipStream_t stream) {
     const int grid = grid_for(ch, a.B, 256, 8);

@@ -7,6 +7,7 @@
 //   ik_path.hip        the per-waypoint selection of warm-started paths (optik_hip_ik_path)
 //   ik_manip.hip       the manipulability / condition keys of solution modes 3 and 4, optik_hip_manip_batch
 //   ik_collision.hip   the collision filter: model and world, its key pass, link frames and clearance batches
+//   ik_motion.hip      the motion check: segments between configurations, the motion key pass of optik_hip_ik_path
 //   ik_batch_ops.hip   objective / gradient, FK / Jacobian and seed batches, the test probes
 //   ik_lane_kernel.hip, ik_quad_kernel.hip, ik_wide_kernel.hip    the restart solvers (one restart loop each)
 #pragma once
@@ -128,6 +129,15 @@ int manip_key_launch(const optik_hip_chain *ch, int mode, const double *ee_offse
 int collision_key_launch(const optik_hip_chain *ch, const double *ee_offset7, const double *x, double *key,
                          size_t cols, hipStream_t stream);
 
+// ---- the motion check (ik_motion.hip) ------------------------------------------------------------------------
+// The workspace of a motion launch over `segments` segments, grown on demand (under ch->mu, before the solver launch).
+int motion_reserve(optik_hip_chain *ch, long long segments);
+// One waypoint of optik_hip_ik_path, behind the collision key pass and before the selection: every success (key < +inf)
+// of path p's R restarts (x [n][P * R]) within max_step of the path's seed (seed [P][n], read on the device) whose
+// motion seed -> x is not free at the chain's resolution gets key +inf.  Only while ch->motion_h > 0 and ch->coll_S > 0.
+int motion_key_launch(const optik_hip_chain *ch, const double *ee_offset7, const double *seed, const double *x,
+                      double *key, int P, size_t R, int filter, double max_step, hipStream_t stream);
+
 // ---- options ---------------------------------------------------------------------------------------------
 // Every tuning option of the kernel layer, in one place.  The defaults come from the environment ONCE, at the
 // first use (the OPTIK_* names below); tests and tools change them through optik_hip_set_option (optik_hip.h).
@@ -235,6 +245,11 @@ struct optik_hip_chain {
     double *world_dev = nullptr;
     size_t world_cap = 0;  // doubles
     int world_Ms = 0, world_Mb = 0;
+    // the motion check (ik_motion.hip): the resolution of ik_path's motion key pass (0: off) and the workspace of a
+    // motion launch (prefix of the sample counts, the segments' reduction words)
+    double motion_h = 0.0;
+    void *motion_ws = nullptr;
+    size_t motion_ws_cap = 0;  // bytes
     // (what the last launch's selection kernel left behind: the work-item counter at 0, this many leading
     // first-success words at ~0 -- a launch that finds them so skips its fill commands)
     // (host-side knowledge that holds for launches ORDERED behind that selection kernel: the stream it ran on is kept

@@ -78,6 +78,7 @@ struct optik_robot {
     std::vector<double> coll_centers, coll_radii;
     double coll_margin = 0.0;
     std::vector<double> world_spheres, world_boxes;
+    double motion_h = 0.0;  // optik_robot_set_motion_resolution (0: off)
     bool collision_active() const {
         std::lock_guard<std::mutex> lock(mu);
         return !coll_frames.empty();
@@ -195,8 +196,9 @@ DeviceCtx *device_ctx(const optik_robot *r, size_t k = 0) {
                                                 (int32_t)(r->coll_pairs.size() / 2), r->coll_margin))
         || ((!r->world_spheres.empty() || !r->world_boxes.empty())
             && optik_hip_chain_set_world(h, r->world_spheres.data(), (int32_t)(r->world_spheres.size() / 4),
-                                         r->world_boxes.data(), (int32_t)(r->world_boxes.size() / 10)))) {
-        g_robot_err = std::string("collision model upload failed: ") + optik_hip_last_error();
+                                         r->world_boxes.data(), (int32_t)(r->world_boxes.size() / 10)))
+        || (r->motion_h > 0.0 && optik_hip_chain_set_motion_resolution(h, r->motion_h))) {
+        g_robot_err = std::string("collision model, world or motion resolution upload failed: ") + optik_hip_last_error();
         (void)hipFree(c->d_scratch); c->d_scratch = nullptr;
         (void)hipHostFree(c->h_scratch); c->h_scratch = nullptr;
         optik_hip_chain_destroy(h);
@@ -1461,6 +1463,87 @@ int optik_robot_collision_batch(const optik_robot *r, int64_t B, const double *x
             if (clearance_out) std::memcpy(clearance_out + b0, h_out, sizeof(double) * L);
             if (free_out) std::memcpy(free_out + b0, reinterpret_cast<const uint8_t *>(h_out + L), L);
         });
+}
+
+int optik_robot_set_motion_resolution(optik_robot *r, double h) {
+    if (!r) return set_err(-1, "null argument");
+    if (!(h >= 0.0) || !std::isfinite(h))
+        return set_err(-1, "motion resolution must be finite and >= 0 (0: no motion check)");
+    std::lock_guard<std::mutex> lock(r->mu);
+    r->motion_h = h;
+    for (auto &c : r->devs) {
+        if (!c->chain) continue;
+        std::lock_guard<std::mutex> batch_lock(c->batch_mu);
+        if (optik_hip_chain_set_motion_resolution(c->chain, h)) return set_err(-1, optik_hip_last_error());
+    }
+    return 0;
+}
+
+int optik_robot_collision_motion_batch(const optik_robot *r, int64_t B, const double *xa, const double *xb,
+                                       double resolution, const double *ee16, double *clearance_out,
+                                       uint8_t *free_out, int32_t *first_out, int32_t *steps_out) {
+    if (!r || !xa || !xb) return set_err(-1, "null argument");
+    if (B < 0) return set_err(-1, "bad argument");
+    // (refused on the host, before a device context exists)
+    if (!(resolution > 0.0) || !std::isfinite(resolution))
+        return set_err(-1, "motion resolution must be finite and > 0");
+    for (int32_t t : r->types)
+        if (t == optik_host::PRISMATIC)
+            return set_err(-1, "collision: prismatic joints are not supported (IK refuses such chains)");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    // (B = 0: the kernel layer's own refusals of the chain, before anything is staged)
+    if (optik_hip_collision_motion_batch(c->chain, nullptr, nullptr, nullptr, 0, resolution, nullptr, nullptr, nullptr,
+                                         nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (B == 0 || (!clearance_out && !free_out && !first_out && !steps_out)) return 0;
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    const int n = r->n;
+    std::lock_guard<std::mutex> lock(c->batch_mu);
+    optik::DeviceScope dev_scope(c->device);
+    if (!dev_scope.ok()) return set_err(-1, "hipSetDevice failed");
+    // per segment: qa and qb (2 n doubles) in, the clearance, then first and steps in a second double and the free
+    // flag in the bytes of a third
+    const int64_t chunk = B < ((int64_t)1 << 16) ? B : ((int64_t)1 << 16);
+    const size_t need = (2 * (size_t)n + 3) * (size_t)chunk;
+    if (need > c->batch_cap) {
+        if (c->d_batch) (void)hipFree(c->d_batch);
+        if (c->h_batch) (void)hipHostFree(c->h_batch);
+        c->d_batch = nullptr; c->h_batch = nullptr; c->batch_cap = 0;
+        if (hipMalloc(&c->d_batch, sizeof(double) * need) != hipSuccess
+            || hipHostMalloc(&c->h_batch, sizeof(double) * need) != hipSuccess)
+            return set_err(-1, "batch workspace allocation failed");
+        c->batch_cap = need;
+    }
+    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+        const size_t L = (size_t)(B - b0 < chunk ? B - b0 : chunk);
+        double *h_q = c->h_batch, *h_out = h_q + 2 * (size_t)n * L;
+        double *d_q = c->d_batch, *d_out = d_q + 2 * (size_t)n * L;
+        parallel_ranges(L, [&](size_t k0, size_t k1) {
+            for (size_t k = k0; k < k1; ++k)
+                for (int i = 0; i < n; ++i) {
+                    h_q[(size_t)i * L + k] = xa[((size_t)b0 + k) * n + i];
+                    h_q[((size_t)n + i) * L + k] = xb[((size_t)b0 + k) * n + i];
+                }
+        });
+        if (hipMemcpyAsync(d_q, h_q, sizeof(double) * 2 * (size_t)n * L, hipMemcpyHostToDevice, nullptr) != hipSuccess)
+            return set_err(-1, "upload failed");
+        int32_t *d_first = reinterpret_cast<int32_t *>(d_out + L);
+        if (optik_hip_collision_motion_batch(c->chain, ee16 ? ee7 : nullptr, d_q, d_q + (size_t)n * L, (int64_t)L,
+                                             resolution, clearance_out ? d_out : nullptr,
+                                             reinterpret_cast<uint8_t *>(d_out + 2 * L), d_first, d_first + L, nullptr))
+            return set_err(-1, optik_hip_last_error());
+        if (hipMemcpyAsync(h_out, d_out, sizeof(double) * 3 * L, hipMemcpyDeviceToHost, nullptr) != hipSuccess
+            || hipStreamSynchronize(nullptr) != hipSuccess)
+            return set_err(-1, "download failed");
+        const int32_t *h_first = reinterpret_cast<const int32_t *>(h_out + L);
+        if (clearance_out) std::memcpy(clearance_out + b0, h_out, sizeof(double) * L);
+        if (first_out) std::memcpy(first_out + b0, h_first, sizeof(int32_t) * L);
+        if (steps_out) std::memcpy(steps_out + b0, h_first + L, sizeof(int32_t) * L);
+        if (free_out) std::memcpy(free_out + b0, reinterpret_cast<const uint8_t *>(h_out + 2 * L), L);
+    }
+    return 0;
 }
 
 // lib.rs:165-183 of optik-cpp: the joint velocities only, malloc'ed; NULL = no solution.

@@ -180,6 +180,33 @@ class HipChain:
                                                       _ptr(clearance), _ptr(free), _stream_ptr()))
         return clearance, free.bool()
 
+    # -- the motion check (include/optik_hip.h) ------------------------------------------
+    def collision_motion_batch(self, qa, qb, resolution, ee_offset=None, clearance=True):
+        """The straight joint-space motions qa[:, b] -> qb[:, b] (float64 cuda tensors [n, B]) sampled at
+        `resolution` (L-infinity, radians; csrc/motion_measure.hpp) against the chain's model and world: (clearance
+        [B], free [B] bool, first [B] int32, steps [B] int32) -- the minimum of the samples' clearances, whether every
+        sample is free, the lowest sample index that is not (-1: none) and the number of steps K (-1: not sampled,
+        then clearance NaN and free False).  clearance=False only classifies (faster for blocked motions) and returns
+        None in its place.  ee_offset: 7 numbers, as collision_batch.  Stream-ordered."""
+        B = self._check_q(qa)
+        if self._check_q(qb) != B or qb.device != qa.device:
+            raise ValueError(f"qa and qb must have the same shape and device, got {tuple(qa.shape)} and {tuple(qb.shape)}")
+        h = nat.check_resolution(resolution)
+        ee = self._ee7(ee_offset)
+        clr = torch.empty(B, dtype=torch.float64, device=qa.device) if clearance else None
+        free = torch.empty(B, dtype=torch.uint8, device=qa.device)
+        first = torch.empty(B, dtype=torch.int32, device=qa.device)
+        steps = torch.empty(B, dtype=torch.int32, device=qa.device)
+        nat.check(nat.lib().optik_hip_collision_motion_batch(
+            self._h, _dp(ee) if ee is not None else None, _ptr(qa), _ptr(qb), B, h, _ptr(clr), _ptr(free),
+            _ptr(first), _ptr(steps), _stream_ptr()))
+        return clr, free.bool(), first, steps
+
+    def set_motion_resolution(self, h):
+        """The resolution of ik_path's motion check between a path's seed and every candidate within max_step (0:
+        off, the default); it acts while a collision model is set.  Waits for the device."""
+        nat.check(nat.lib().optik_hip_chain_set_motion_resolution(self._h, nat.check_resolution(h, allow_zero=True)))
+
     def seed_batch(self, first, count):
         q = torch.empty((self.n, count), dtype=torch.float64, device=self.device)
         nat.check(nat.lib().optik_hip_seed_batch(self._h, int(first), int(count), _ptr(q), _stream_ptr()))

@@ -45,6 +45,9 @@ def _bind(L):
     L.optik_robot_set_world.argtypes = [vp, dp, C.c_int32, dp, C.c_int32]
     L.optik_robot_link_frames_batch.argtypes = [vp, C.c_int64, dp, dp, dp]
     L.optik_robot_collision_batch.argtypes = [vp, C.c_int64, dp, dp, dp, C.POINTER(C.c_uint8)]
+    L.optik_robot_collision_motion_batch.argtypes = [vp, C.c_int64, dp, dp, C.c_double, dp, dp, C.POINTER(C.c_uint8),
+                                                     ip, ip]
+    L.optik_robot_set_motion_resolution.argtypes = [vp, C.c_double]
     L.optik_robot_diff_ik_ex.argtypes = [vp, dp, dp, dp, dp, C.POINTER(C.c_double), dp]
     L.optik_robot_diff_ik_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_int32)]
     L.optik_robot_joint_jacobian_ex.argtypes = [vp, dp, dp, dp]
@@ -521,6 +524,44 @@ class Robot:
         x = self._check_x(x)
         clr, _ = self.collision_clearance_batch_arrays(x[None], ee_offset)
         return float(clr[0])
+
+    # -- the motion check (extension; include/optik.h) ------------------------------------
+    def collision_motion_batch_arrays(self, xa, xb, resolution, ee_offset=None):
+        """The straight joint-space motions xa[b] -> xb[b] ([B, n] each) sampled at `resolution` (L-infinity,
+        radians) against the model and world: (clearance [B], free [B] bool, first [B] int32, steps [B] int32) --
+        the minimum clearance over the samples, whether all of them are free, the lowest sample index that is not
+        (-1: none), and the number of steps (-1: more than 4096 steps or a non-finite distance: not sampled,
+        clearance NaN, free False)."""
+        xa, xb = self._check_xs(xa), self._check_xs(xb)
+        if xa.shape != xb.shape:
+            raise ValueError(f"xa and xb must have the same shape, got {list(xa.shape)} and {list(xb.shape)}")
+        h = nat.check_resolution(resolution)
+        B = xa.shape[0]
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        clr, free = np.zeros(B), np.zeros(B, dtype=np.uint8)
+        first, steps = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        if self._L.optik_robot_collision_motion_batch(self._h, B, _dp(xa), _dp(xb), h,
+                                                      _dp(ee) if ee is not None else None, _dp(clr),
+                                                      free.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                      first.ctypes.data_as(ip), steps.ctypes.data_as(ip)):
+            raise RuntimeError(_err(self._L))
+        return clr, free.astype(bool), first, steps
+
+    def collision_motion(self, xa, xb, resolution, ee_offset=None):
+        """One motion: (clearance, free, first, steps) as Python scalars (see collision_motion_batch_arrays)."""
+        xa, xb = self._check_x(xa), self._check_x(xb)
+        clr, free, first, steps = self.collision_motion_batch_arrays(xa[None], xb[None], resolution, ee_offset)
+        return float(clr[0]), bool(free[0]), int(first[0]), int(steps[0])
+
+    def set_motion_resolution(self, h):
+        """The resolution of ik_path*'s motion check (0, the default: off).  While it is > 0 and a collision model is
+        set, a waypoint's candidates are only the successes whose straight joint-space motion from the path's seed is
+        free at this resolution, so consecutive accepted waypoints are joined by checked motions.  A start
+        configuration in collision blocks every motion from it.  Applied to every GPU of the robot; ik, ik_batch* and
+        ik_solutions* ignore it.  ValueError for a NaN, negative or infinite h."""
+        if self._L.optik_robot_set_motion_resolution(self._h, nat.check_resolution(h, allow_zero=True)):
+            raise ValueError(_err(self._L))
 
     # -- extensions ---------------------------------------------------------------
     def chain_tables(self):
