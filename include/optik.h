@@ -178,6 +178,15 @@ int optik_robot_manipulability_batch(const optik_robot *robot, int64_t B, const 
 int optik_robot_set_collision_model(optik_robot *robot, const int32_t *frames, const double *centers3,
                                     const double *radii, int32_t S, const int32_t *pairs2, int32_t P, double margin);
 int optik_robot_set_world(optik_robot *robot, const double *spheres4, int32_t Ms, const double *boxes10, int32_t Mb);
+/* The distance-field world (extension; include/optik_hip.h: optik_hip_chain_set_world_grid and what precedes it).
+ * Host arrays; the grid is kept with the robot and applied to every device chain it has or creates later
+ * (optik_robot_set_devices included), as the model and the world are.  values == NULL with zero dims clears it.
+ * optik_robot_world_grid_bake bakes the robot's current spheres and boxes on its first device into values_out
+ * (host, nx * ny * nz floats) and installs nothing.  rc 0, or -1 with the refusal of the kernel layer. */
+int optik_robot_set_world_grid(optik_robot *robot, const double *origin3, double voxel, int32_t nx, int32_t ny,
+                               int32_t nz, const float *values);
+int optik_robot_world_grid_bake(const optik_robot *robot, const double *origin3, double voxel, int32_t nx, int32_t ny,
+                                int32_t nz, float *values_out);
 /* x [B][n] -> frames16_out [B][n + 2][16]: every frame as a column-major 4x4 (as optik_robot_fk_ex writes it; frame
  * n + 1 is fk's pose).  ee_offset16 may be NULL.  On the robot's first device; rc 0 or -1. */
 int optik_robot_link_frames_batch(const optik_robot *robot, int64_t B, const double *x, const double *ee_offset16,

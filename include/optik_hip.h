@@ -190,6 +190,32 @@ int optik_hip_link_frames_batch(const optik_hip_chain *chain, const double *ee_o
 int optik_hip_collision_batch(const optik_hip_chain *chain, const double *ee_offset7, const double *d_q, int64_t B,
                               double *d_clearance, uint8_t *d_free, void *stream);
 
+/* The distance-field world (extension; the arithmetic: csrc/collision_measure.hpp, steps
+ * 5 - 7): a third obstacle kind next to the spheres and boxes, a sampled signed distance field (an ESDF / TSDF voxel
+ * grid) that is axis-aligned in the base frame.  Node (i, j, k) sits at origin3 + voxel * (i, j, k); values is float32
+ * [nx][ny][nz] in C order (z fastest).  Each robot sphere inside the grid contributes the trilinearly interpolated
+ * value at its centre minus its radius to the clearance minimum; a sphere whose centre lies outside [origin, origin +
+ * voxel * (n - 1)] on any axis contributes nothing.  Every consumer of the world reads the grid: collision_batch, the
+ * collision key pass of the solver launches, collision_motion_batch and ik_path's motion key pass.  The interpolated
+ * field approximates the true distance to within sqrt(3) * voxel (for a 1-Lipschitz field) plus f32 rounding: a
+ * caller who needs a conservative answer adds that to the margin.
+ *
+ * optik_hip_chain_set_world_grid takes host arrays, waits for the chain's device as set_world does and replaces the
+ * whole grid; values == NULL with nx = ny = nz = 0 clears it.  set_world leaves the grid alone and this call leaves
+ * the spheres and boxes alone.  Refused with OPTIK_HIP_EINVAL before any device work: a dimension outside 2 ..
+ * OPTIK_HIP_MAX_GRID_DIM, more than OPTIK_HIP_MAX_GRID_NODES nodes, a voxel that is zero, negative, NaN or infinite,
+ * a non-finite origin, a NaN or infinite value.
+ *
+ * optik_hip_world_grid_bake writes (float)(the signed distance of the chain's current spheres and boxes at the
+ * node) for every node of the given grid to d_values_out (device memory, nx * ny * nz floats).  Stream-ordered; it
+ * installs nothing.  Refused as above, and for a world without spheres and boxes. */
+#define OPTIK_HIP_MAX_GRID_DIM 1024
+#define OPTIK_HIP_MAX_GRID_NODES (1 << 24)
+int optik_hip_chain_set_world_grid(optik_hip_chain *chain, const double *origin3, double voxel, int32_t nx, int32_t ny,
+                                   int32_t nz, const float *values);
+int optik_hip_world_grid_bake(const optik_hip_chain *chain, const double *origin3, double voxel, int32_t nx,
+                              int32_t ny, int32_t nz, float *d_values_out, void *stream);
+
 /* The motion check (extension; the arithmetic: csrc/motion_measure.hpp): is the straight
  * joint-space segment qa -> qb free at a resolution h > 0 (L-infinity, radians)?  With d = max_i |qb_i - qa_i| the
  * segment has K = max(1, (int)ceil(d / h)) steps and K + 1 samples: sample 0 is qa and sample K is qb, copied, and

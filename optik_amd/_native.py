@@ -128,6 +128,8 @@ def lib():
     ip = C.POINTER(C.c_int32)
     L.optik_hip_chain_set_collision_model.argtypes = [vp, ip, dp, dp, C.c_int32, ip, C.c_int32, C.c_double]
     L.optik_hip_chain_set_world.argtypes = [vp, dp, C.c_int32, dp, C.c_int32]
+    L.optik_hip_chain_set_world_grid.argtypes = [vp, dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp]
+    L.optik_hip_world_grid_bake.argtypes = [vp, dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp, vp]
     L.optik_hip_link_frames_batch.argtypes = [vp, dp, vp, C.c_int64, vp, vp]
     L.optik_hip_collision_batch.argtypes = [vp, dp, vp, C.c_int64, vp, vp, vp]
     L.optik_hip_collision_motion_batch.argtypes = [vp, dp, vp, vp, C.c_int64, C.c_double, vp, vp, vp, vp, vp]

@@ -14,6 +14,8 @@ import numpy as np
 MAX_SPHERES = 256      # OPTIK_HIP_MAX_COLLISION_SPHERES
 MAX_PAIRS = 4096       # OPTIK_HIP_MAX_COLLISION_PAIRS
 MAX_OBSTACLES = 65536  # OPTIK_HIP_MAX_WORLD_OBSTACLES, of each kind
+MAX_GRID_DIM = 1024    # OPTIK_HIP_MAX_GRID_DIM, per axis (at least 2)
+MAX_GRID_NODES = 1 << 24  # OPTIK_HIP_MAX_GRID_NODES
 
 
 def auto_pairs(frames):
@@ -63,6 +65,31 @@ def world_arrays(spheres=None, boxes=None):
     if box.ndim != 2 or box.shape[1] != 10:
         raise ValueError("boxes must be [M, 10]: t (3), unit quaternion i, j, k, w (4), half extents (3)")
     return np.ascontiguousarray(sph), np.ascontiguousarray(box)
+
+
+def grid_arrays(origin, voxel, values=None, shape=None):
+    """(origin float64 [3], voxel, values float32 [nx, ny, nz] C-contiguous or None, (nx, ny, nz)) in the layout of the
+    C ABI, for the distance-field world: node (i, j, k) sits at origin + voxel * (i, j, k) in
+    the base frame.  Give `values` (anything convertible to float32 [nx, ny, nz]) to install a grid, or `shape` alone
+    to bake one.  Shapes are checked here; the dimensions' range, the node count, voxel, origin and the values'
+    finiteness by the C layer."""
+    origin = np.ascontiguousarray(np.asarray(origin, dtype=np.float64).ravel())
+    if origin.shape != (3,):
+        raise ValueError("origin must be 3 numbers: the position of node (0, 0, 0) in the base frame")
+    if values is not None:
+        with np.errstate(over="ignore"):  # (a value beyond float32 becomes infinite and is refused by the C layer)
+            values = np.ascontiguousarray(np.asarray(values, dtype=np.float32))
+        if values.ndim != 3:
+            raise ValueError(f"values must be [nx, ny, nz], got {list(values.shape)}")
+        if shape is not None and tuple(int(v) for v in shape) != values.shape:
+            raise ValueError("shape does not match values")
+        shape = values.shape
+    elif shape is None:
+        raise ValueError("values or shape is needed")
+    shape = tuple(int(v) for v in shape)
+    if len(shape) != 3:
+        raise ValueError("shape must be (nx, ny, nz)")
+    return origin, float(voxel), values, shape
 
 
 def spheres_along_chain(robot, radius, per_link):

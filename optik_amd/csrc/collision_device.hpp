@@ -33,6 +33,7 @@ struct CollLaunch {
     const double *wsph;          // [Ms][4]
     const double *wbox;          // [Mb][10]
     int Ms, Mb;
+    coll::Grid grid;             // the distance-field world (values null: none)
     const double *q;             // [n][B]: the configurations (key form: the launch's per-restart x)
     long long B;
     double *key;                 // key form: [B], read, and set to +inf where the success is not free
@@ -74,7 +75,8 @@ __device__ __forceinline__ double clearance_of(const ModelDev &m, const CollLaun
     double c = __builtin_huge_val();
     bool ok = !nan;
     const double margin = a.margin;
-    if (a.Ms + a.Mb > 0) {
+    const bool has_grid = a.grid.values != nullptr;  // (a launch argument: wave-uniform)
+    if (a.Ms + a.Mb > 0 || has_grid) {
         for (int f = 0; f < a.nf; ++f) {
             const int s0 = m.frame_begin[f], s1 = m.frame_begin[f + 1];
             if (s0 == s1) continue;
@@ -92,6 +94,11 @@ __device__ __forceinline__ double clearance_of(const ModelDev &m, const CollLaun
                 }
                 for (int k = 0; k < a.Mb; ++k) {
                     const double d = coll::sphere_box(p, r, a.wbox + 10 * k);
+                    if (FORM == FORM_KEY) ok = ok && d >= margin;
+                    else c = fmin(c, d);
+                }
+                if (has_grid) {
+                    const double d = coll::grid_distance(p, r, a.grid);
                     if (FORM == FORM_KEY) ok = ok && d >= margin;
                     else c = fmin(c, d);
                 }
@@ -218,6 +225,14 @@ inline void fill_launch(const optik_hip_chain *ch, const double *ee_offset7, con
         a.Mb = ch->world_Mb;
         a.wsph = ch->world_dev;
         a.wbox = ch->world_dev ? ch->world_dev + 4 * (size_t)ch->world_Ms : nullptr;
+        if (ch->grid_n[0] > 0) {
+            a.grid.values = ch->grid_dev;
+            a.grid.inv = ch->grid_inv;
+            for (int k = 0; k < 3; ++k) {
+                a.grid.origin[k] = ch->grid_origin[k];
+                a.grid.n[k] = ch->grid_n[k];
+            }
+        }
     }
 }
 

@@ -30,7 +30,35 @@
 // "not free" exactly as the full clearance does.  Terms are never NaN once the frames are not (the inputs are
 // refused unless centres are finite and radii / half extents are >= 0; +inf radii give -inf).
 //
-// Plain host C++ compiles this header too (no HIP runtime): tests/test_collision_host.py drives it with g++.
+//
+// The distance-field world: a third obstacle kind, a sampled signed distance field on an
+// axis-aligned grid in the base frame.  Node (i, j, k) sits at origin_a + voxel * (double)i_a per axis; values are
+// float32 [nx][ny][nz] in C order (z fastest), every one finite; each of nx, ny, nz is in 2 .. 1024 and nx * ny * nz
+// <= 2^24; voxel > 0 and finite.  The host stores inv = 1.0 / voxel once and both sides multiply by it.  All
+// arithmetic is f64 (f32 -> f64 is exact).
+//
+//  5. The grid term of a robot sphere (centre p, radius r), per axis a with n_a nodes:
+//         u_a = (p_a - origin_a) * inv
+//     unless 0.0 <= u_a <= (double)(n_a - 1) on all three axes the grid says nothing about the sphere: +inf (a NaN
+//     u_a fails the test, so a NaN centre reads nothing).  Otherwise
+//         i_a = min((int)floor(u_a), n_a - 2);  f_a = u_a - (double)i_a      (u_a = n_a - 1: cell n_a - 2, f_a = 1)
+//         v_xyz = (double)values[i_x + x][i_y + y][i_z + z],  x, y, z in {0, 1}
+//         along z:  c_xy = v_xy0 + f_z * (v_xy1 - v_xy0)
+//         along y:  c_x  = c_x0 + f_y * (c_x1 - c_x0)
+//         along x:  c    = c_0 + f_x * (c_1 - c_0)
+//         d = c - r
+//  6. With a grid the clearance of step 4 is the minimum of its terms and the S grid terms; NaN frames still give
+//     NaN, free is still clearance >= margin.  clearance() below keeps its signature (steps 1 - 4);
+//     clearance_grid() is the minimum of the grid terms alone, and the two are combined with fmin.
+//  7. The bake: the world's signed distance at a point p, primitive_field, is the minimum over the world of
+//     sphere_sphere(p, 0, c, r) and sphere_box(p, 0, box) (spheres first, then boxes); the baked value of a node is
+//     (float)primitive_field(node) (round to nearest even), the node at origin_a + voxel * (double)i_a.
+//
+// The interpolated field approximates: for a 1-Lipschitz field it is a convex combination of corners within one cell
+// diagonal of p, so within sqrt(3) * voxel of the true distance, plus the f32 rounding of the values.
+//
+// Plain host C++ compiles this header too (no HIP runtime): tests/test_collision_host.py and
+// tests/test_world_grid_host.py drive it with g++.
 #pragma once
 
 #include <cmath>
@@ -85,6 +113,58 @@ OPTIK_CM_HD inline double sphere_box(const double *p, double r, const double *bo
     return (outside + inside) - r;
 }
 
+// The distance-field world as both sides see it (values: host memory for the host, device memory for the device).
+struct Grid {
+    const float *values;  // [n[0]][n[1]][n[2]], z fastest; null: no grid
+    double origin[3];
+    double inv;           // 1.0 / voxel
+    int32_t n[3];
+};
+
+// Step 5.
+OPTIK_CM_HD inline double grid_distance(const double *p, double r, const Grid &g) {
+    const double ux = (p[0] - g.origin[0]) * g.inv;
+    const double uy = (p[1] - g.origin[1]) * g.inv;
+    const double uz = (p[2] - g.origin[2]) * g.inv;
+    const bool inside = ux >= 0.0 && ux <= (double)(g.n[0] - 1) && uy >= 0.0 && uy <= (double)(g.n[1] - 1)
+                        && uz >= 0.0 && uz <= (double)(g.n[2] - 1);
+    if (!inside) return INFINITY;
+    int ix = (int)floor(ux), iy = (int)floor(uy), iz = (int)floor(uz);
+    if (ix > g.n[0] - 2) ix = g.n[0] - 2;
+    if (iy > g.n[1] - 2) iy = g.n[1] - 2;
+    if (iz > g.n[2] - 2) iz = g.n[2] - 2;
+    const double fx = ux - (double)ix, fy = uy - (double)iy, fz = uz - (double)iz;
+    const int sy = g.n[2], sx = g.n[1] * g.n[2];
+    const float *v = g.values + ((ix * g.n[1] + iy) * g.n[2] + iz);
+    const double v000 = (double)v[0], v001 = (double)v[1];
+    const double v010 = (double)v[sy], v011 = (double)v[sy + 1];
+    const double v100 = (double)v[sx], v101 = (double)v[sx + 1];
+    const double v110 = (double)v[sx + sy], v111 = (double)v[sx + sy + 1];
+    const double c00 = v000 + fz * (v001 - v000);
+    const double c01 = v010 + fz * (v011 - v010);
+    const double c10 = v100 + fz * (v101 - v100);
+    const double c11 = v110 + fz * (v111 - v110);
+    const double c0 = c00 + fy * (c01 - c00);
+    const double c1 = c10 + fy * (c11 - c10);
+    const double c = c0 + fx * (c1 - c0);
+    return c - r;
+}
+
+// Step 7: the world's signed distance at p, and the position of node (i, j, k).
+OPTIK_CM_HD inline double primitive_field(const double *p, const double *spheres, int Ms, const double *boxes,
+                                          int Mb) {
+    double c = INFINITY;
+    for (int m = 0; m < Ms; ++m) c = fmin(c, sphere_sphere(p, 0.0, spheres + 4 * m, spheres[4 * m + 3]));
+    for (int m = 0; m < Mb; ++m) c = fmin(c, sphere_box(p, 0.0, boxes + 10 * m));
+    return c;
+}
+
+OPTIK_CM_HD inline void grid_node(const double *origin, double voxel, int i, int j, int k, double *p) {
+    p[0] = origin[0] + voxel * (double)i;
+    p[1] = origin[1] + voxel * (double)j;
+    p[2] = origin[2] + voxel * (double)k;
+}
+
 OPTIK_CM_HD inline bool pose_has_nan(const double *pose7) {
     bool nan = false;
     for (int i = 0; i < 7; ++i) nan = nan || (pose7[i] != pose7[i]);
@@ -112,6 +192,21 @@ inline double clearance(int nf, const double *frames, int S, const int32_t *fram
         sphere_centre(frames + 7 * frame[a], centers + 3 * a, pa);
         sphere_centre(frames + 7 * frame[b], centers + 3 * b, pb);
         c = fmin(c, sphere_sphere(pa, radii[a], pb, radii[b]));
+    }
+    return c;
+}
+
+// Step 6, the reference form: the minimum of the S grid terms (+inf without a grid or without spheres).
+inline double clearance_grid(int nf, const double *frames, int S, const int32_t *frame, const double *centers,
+                             const double *radii, const Grid &grid) {
+    for (int f = 0; f < nf; ++f)
+        if (pose_has_nan(frames + 7 * f)) return NAN;
+    double c = INFINITY;
+    if (!grid.values) return c;
+    for (int s = 0; s < S; ++s) {
+        double p[3];
+        sphere_centre(frames + 7 * frame[s], centers + 3 * s, p);
+        c = fmin(c, grid_distance(p, radii[s], grid));
     }
     return c;
 }

@@ -109,6 +109,40 @@ inline int check_world(const double *spheres4, int32_t Ms, const double *boxes10
     return 0;
 }
 
+// The distance-field world (collision_measure.hpp, steps 5 - 7): the geometry of a grid, and its values unless
+// `values` is null (the bake checks the geometry alone).
+inline int check_grid(const double *origin3, double voxel, int32_t nx, int32_t ny, int32_t nz, const float *values,
+                      bool with_values, std::string &err) {
+    if (!origin3 || (with_values && !values)) { err = "world grid: null origin or value array"; return OPTIK_HIP_EINVAL; }
+    const int32_t dims[3] = {nx, ny, nz};
+    for (int a = 0; a < 3; ++a)
+        if (dims[a] < 2 || dims[a] > OPTIK_HIP_MAX_GRID_DIM) {
+            err = "world grid: each of nx, ny, nz must be in 2..1024, got " + std::to_string(nx) + " x "
+                  + std::to_string(ny) + " x " + std::to_string(nz);
+            return OPTIK_HIP_EINVAL;
+        }
+    const int64_t nodes = (int64_t)nx * ny * nz;
+    if (nodes > (int64_t)OPTIK_HIP_MAX_GRID_NODES) {
+        err = "world grid: " + std::to_string(nodes) + " nodes, more than 2^24";
+        return OPTIK_HIP_EINVAL;
+    }
+    if (!(voxel > 0.0) || !std::isfinite(voxel) || !std::isfinite(1.0 / voxel)) {
+        err = "world grid: voxel must be finite and > 0 (and so must 1 / voxel)";
+        return OPTIK_HIP_EINVAL;
+    }
+    if (!finite3(origin3)) { err = "world grid: non-finite origin"; return OPTIK_HIP_EINVAL; }
+    if (with_values)
+        for (int64_t i = 0; i < nodes; ++i)
+            if (!std::isfinite(values[i])) {
+                err = "world grid: the value of node (" + std::to_string(i / ((int64_t)ny * nz)) + ", "
+                      + std::to_string(i / nz % ny) + ", " + std::to_string(i % nz) + ") is NaN or infinite";
+                return OPTIK_HIP_EINVAL;
+            }
+    return 0;
+}
+
+inline const char *bake_empty_msg() { return "world grid bake: the world has no spheres and no boxes"; }
+
 // The device layout of a checked model; returns the number of pair groups.
 inline int pack_model(int n, const int32_t *frames, const double *centers3, const double *radii, int32_t S,
                       const int32_t *pairs2, int32_t P, ModelDev &m) {

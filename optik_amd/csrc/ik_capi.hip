@@ -173,6 +173,7 @@ void optik_hip_chain_destroy(optik_hip_chain *ch) {
     if (ch->path_carry) hipFree(ch->path_carry);
     if (ch->coll_dev) hipFree(ch->coll_dev);
     if (ch->world_dev) hipFree(ch->world_dev);
+    if (ch->grid_dev) hipFree(ch->grid_dev);
     if (ch->motion_ws) hipFree(ch->motion_ws);
     if (ch->tmp_x) hipFree(ch->tmp_x);
     if (ch->tmp_f) hipFree(ch->tmp_f);

@@ -104,6 +104,27 @@ __global__ __launch_bounds__(256) void wide_link_frames_batch_kernel(const CollL
 __global__ __launch_bounds__(256) void wide_collision_batch_kernel(const CollLaunch a) { wide_coll_body<FORM_BATCH>(a); }
 __global__ __launch_bounds__(256) void wide_collision_key_kernel(const CollLaunch a) { wide_coll_body<FORM_KEY>(a); }
 
+// The bake (collision_measure.hpp, step 7): one lane per node, grid-stride; the primitives are read at wave-uniform
+// addresses, as the key pass reads them.
+struct BakeLaunch {
+    const double *wsph, *wbox;
+    int Ms, Mb;
+    double origin[3], voxel;
+    int n[3];
+    float *out;
+};
+
+__global__ __launch_bounds__(256) void grid_bake_kernel(const BakeLaunch a) {
+    const long long nodes = (long long)a.n[0] * a.n[1] * a.n[2];
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nodes;
+         i += (long long)gridDim.x * blockDim.x) {
+        const int iz = (int)(i % a.n[2]), iy = (int)(i / a.n[2] % a.n[1]), ix = (int)(i / ((long long)a.n[1] * a.n[2]));
+        double p[3];
+        coll::grid_node(a.origin, a.voxel, ix, iy, iz, p);
+        a.out[i] = (float)coll::primitive_field(p, a.wsph, a.Ms, a.wbox, a.Mb);
+    }
+}
+
 const char *const kCollPrismaticMsg = prismatic_msg();
 
 int coll_launch(const optik_hip_chain *ch, const CollLaunch &a, int form, hipStream_t stream) {
@@ -201,6 +222,55 @@ int optik_hip_chain_set_world(optik_hip_chain *ch, const double *spheres4, int32
         HIP_TRY(hipMemcpy(ch->world_dev + 4 * (size_t)Ms, boxes10, sizeof(double) * 10 * (size_t)Mb,
                           hipMemcpyHostToDevice));
     ch->world_Ms = Ms; ch->world_Mb = Mb;
+    return 0;
+}
+
+int optik_hip_chain_set_world_grid(optik_hip_chain *ch, const double *origin3, double voxel, int32_t nx, int32_t ny,
+                                   int32_t nz, const float *values) {
+    if (!ch) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    const bool clear = !values && nx == 0 && ny == 0 && nz == 0;
+    std::string err;
+    if (!clear)
+        if (int rc = coll::check_grid(origin3, voxel, nx, ny, nz, values, true, err)) return fail(rc, err);
+    std::lock_guard<std::mutex> lock(ch->mu);
+    BIND_DEVICE(ch);
+    if (int rc = drain_chain(ch)) return rc;
+    ch->grid_n[0] = ch->grid_n[1] = ch->grid_n[2] = 0;
+    if (clear) return 0;
+    const size_t need = (size_t)nx * (size_t)ny * (size_t)nz;
+    if (need > ch->grid_cap) {
+        if (ch->grid_dev) HIP_TRY(hipFree(ch->grid_dev));
+        ch->grid_dev = nullptr; ch->grid_cap = 0;
+        HIP_TRY(hipMalloc(&ch->grid_dev, sizeof(float) * need));
+        ch->grid_cap = need;
+    }
+    HIP_TRY(hipMemcpy(ch->grid_dev, values, sizeof(float) * need, hipMemcpyHostToDevice));
+    for (int k = 0; k < 3; ++k) ch->grid_origin[k] = origin3[k];
+    ch->grid_inv = 1.0 / voxel;
+    ch->grid_n[0] = nx; ch->grid_n[1] = ny; ch->grid_n[2] = nz;
+    return 0;
+}
+
+int optik_hip_world_grid_bake(const optik_hip_chain *ch, const double *origin3, double voxel, int32_t nx, int32_t ny,
+                              int32_t nz, float *d_values_out, void *stream) {
+    if (!ch) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    std::string err;
+    if (int rc = coll::check_grid(origin3, voxel, nx, ny, nz, nullptr, false, err)) return fail(rc, err);
+    if (ch->world_Ms + ch->world_Mb == 0) return fail(OPTIK_HIP_EINVAL, coll::bake_empty_msg());
+    if (!d_values_out) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    BIND_DEVICE(ch);
+    BakeLaunch a;
+    std::memset(&a, 0, sizeof a);
+    a.wsph = ch->world_dev;
+    a.wbox = ch->world_dev + 4 * (size_t)ch->world_Ms;
+    a.Ms = ch->world_Ms; a.Mb = ch->world_Mb;
+    for (int k = 0; k < 3; ++k) a.origin[k] = origin3[k];
+    a.voxel = voxel;
+    a.n[0] = nx; a.n[1] = ny; a.n[2] = nz;
+    a.out = d_values_out;
+    const int grid = grid_for(ch, (long long)nx * ny * nz, 256, 8);
+    hipLaunchKernelGGL(grid_bake_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 

@@ -245,6 +245,12 @@ struct optik_hip_chain {
     double *world_dev = nullptr;
     size_t world_cap = 0;  // doubles
     int world_Ms = 0, world_Mb = 0;
+    // the distance-field world (optik_hip_chain_set_world_grid): float32 [nx][ny][nz]; null: no grid
+    float *grid_dev = nullptr;
+    size_t grid_cap = 0;  // floats
+    int grid_n[3] = {0, 0, 0};
+    double grid_origin[3] = {0.0, 0.0, 0.0};
+    double grid_inv = 0.0;
     // the motion check (ik_motion.hip): the resolution of ik_path's motion key pass (0: off) and the workspace of a
     // motion launch (prefix of the sample counts, the segments' reduction words)
     double motion_h = 0.0;

@@ -78,6 +78,10 @@ struct optik_robot {
     std::vector<double> coll_centers, coll_radii;
     double coll_margin = 0.0;
     std::vector<double> world_spheres, world_boxes;
+    // the distance-field world (optik_robot_set_world_grid); no grid while grid_values is empty
+    std::vector<float> grid_values;
+    double grid_origin[3] = {0.0, 0.0, 0.0}, grid_voxel = 0.0;
+    int32_t grid_n[3] = {0, 0, 0};
     double motion_h = 0.0;  // optik_robot_set_motion_resolution (0: off)
     bool collision_active() const {
         std::lock_guard<std::mutex> lock(mu);
@@ -197,6 +201,9 @@ DeviceCtx *device_ctx(const optik_robot *r, size_t k = 0) {
         || ((!r->world_spheres.empty() || !r->world_boxes.empty())
             && optik_hip_chain_set_world(h, r->world_spheres.data(), (int32_t)(r->world_spheres.size() / 4),
                                          r->world_boxes.data(), (int32_t)(r->world_boxes.size() / 10)))
+        || (!r->grid_values.empty()
+            && optik_hip_chain_set_world_grid(h, r->grid_origin, r->grid_voxel, r->grid_n[0], r->grid_n[1],
+                                              r->grid_n[2], r->grid_values.data()))
         || (r->motion_h > 0.0 && optik_hip_chain_set_motion_resolution(h, r->motion_h))) {
         g_robot_err = std::string("collision model, world or motion resolution upload failed: ") + optik_hip_last_error();
         (void)hipFree(c->d_scratch); c->d_scratch = nullptr;
@@ -1370,6 +1377,57 @@ int optik_robot_set_world(optik_robot *r, const double *spheres4, int32_t Ms, co
         if (optik_hip_chain_set_world(c->chain, spheres4, Ms, boxes10, Mb)) return set_err(-1, optik_hip_last_error());
     }
     return 0;
+}
+
+int optik_robot_set_world_grid(optik_robot *r, const double *origin3, double voxel, int32_t nx, int32_t ny, int32_t nz,
+                               const float *values) {
+    if (!r) return set_err(-1, "null argument");
+    const bool clear = !values && nx == 0 && ny == 0 && nz == 0;
+    std::string err;
+    if (!clear && optik::coll::check_grid(origin3, voxel, nx, ny, nz, values, true, err)) return set_err(-1, err);
+    std::lock_guard<std::mutex> lock(r->mu);
+    if (clear) {
+        r->grid_values.clear();
+        r->grid_n[0] = r->grid_n[1] = r->grid_n[2] = 0;
+    } else {
+        r->grid_values.assign(values, values + (size_t)nx * (size_t)ny * (size_t)nz);
+        for (int k = 0; k < 3; ++k) r->grid_origin[k] = origin3[k];
+        r->grid_voxel = voxel;
+        r->grid_n[0] = nx; r->grid_n[1] = ny; r->grid_n[2] = nz;
+    }
+    for (auto &c : r->devs) {
+        if (!c->chain) continue;
+        std::lock_guard<std::mutex> batch_lock(c->batch_mu);
+        if (optik_hip_chain_set_world_grid(c->chain, origin3, voxel, nx, ny, nz, values))
+            return set_err(-1, optik_hip_last_error());
+    }
+    return 0;
+}
+
+int optik_robot_world_grid_bake(const optik_robot *r, const double *origin3, double voxel, int32_t nx, int32_t ny,
+                                int32_t nz, float *values_out) {
+    if (!r || !values_out) return set_err(-1, "null argument");
+    std::string err;
+    if (optik::coll::check_grid(origin3, voxel, nx, ny, nz, nullptr, false, err)) return set_err(-1, err);
+    {
+        std::lock_guard<std::mutex> lock(r->mu);
+        if (r->world_spheres.empty() && r->world_boxes.empty()) return set_err(-1, optik::coll::bake_empty_msg());
+    }
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    std::lock_guard<std::mutex> lock(c->batch_mu);
+    optik::DeviceScope dev_scope(c->device);
+    if (!dev_scope.ok()) return set_err(-1, "hipSetDevice failed");
+    const size_t nodes = (size_t)nx * (size_t)ny * (size_t)nz;
+    float *d_out = nullptr;
+    if (hipMalloc(&d_out, sizeof(float) * nodes) != hipSuccess) return set_err(-1, "bake buffer allocation failed");
+    int rc = 0;
+    if (optik_hip_world_grid_bake(c->chain, origin3, voxel, nx, ny, nz, d_out, nullptr))
+        rc = set_err(-1, optik_hip_last_error());
+    else if (hipMemcpy(values_out, d_out, sizeof(float) * nodes, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = set_err(-1, "download failed");
+    (void)hipFree(d_out);
+    return rc;
 }
 
 namespace {

@@ -146,6 +146,33 @@ class HipChain:
         sph, box = world_arrays(spheres, boxes)
         nat.check(nat.lib().optik_hip_chain_set_world(self._h, _dp(sph), len(sph), _dp(box), len(box)))
 
+    # -- the distance-field world (include/optik_hip.h) ------------------------------------
+    def set_world_grid(self, origin, voxel, values):
+        """A sampled signed distance field next to the spheres and boxes: values [nx, ny, nz] (a host array or a
+        tensor, converted to float32), node (i, j, k) at origin + voxel * (i, j, k) in the base frame.  Replaces the
+        whole grid and leaves the spheres and boxes alone.  Waits for the device; the values are checked on the host
+        (a tensor is copied there first)."""
+        from .collision import grid_arrays
+        if isinstance(values, torch.Tensor):
+            values = values.detach().to(torch.float32).cpu().numpy()
+        o, v, vals, (nx, ny, nz) = grid_arrays(origin, voxel, values)
+        nat.check(nat.lib().optik_hip_chain_set_world_grid(self._h, _dp(o), v, nx, ny, nz,
+                                                           C.c_void_p(vals.ctypes.data)))
+
+    def clear_world_grid(self):
+        """No grid: every call returns what it returns with the spheres and boxes alone."""
+        nat.check(nat.lib().optik_hip_chain_set_world_grid(self._h, None, 0.0, 0, 0, 0, None))
+
+    def bake_world_grid(self, origin, voxel, shape):
+        """The signed distance of the chain's current spheres and boxes at every node: a float32 cuda tensor
+        [nx, ny, nz].  Stream-ordered; installs nothing."""
+        from .collision import grid_arrays
+        o, v, _, (nx, ny, nz) = grid_arrays(origin, voxel, shape=shape)
+        nodes = nx * ny * nz
+        out = torch.empty(nodes if 0 < nodes <= (1 << 24) else 1, dtype=torch.float32, device=self.device)
+        nat.check(nat.lib().optik_hip_world_grid_bake(self._h, _dp(o), v, nx, ny, nz, _ptr(out), _stream_ptr()))
+        return out.view(nx, ny, nz)
+
     def _check_q(self, q):
         if not (isinstance(q, torch.Tensor) and q.is_cuda and q.dtype == torch.float64 and q.dim() == 2
                 and q.shape[0] == self.n and q.is_contiguous()):

@@ -43,6 +43,8 @@ def _bind(L):
     ip = C.POINTER(C.c_int32)
     L.optik_robot_set_collision_model.argtypes = [vp, ip, dp, dp, C.c_int32, ip, C.c_int32, C.c_double]
     L.optik_robot_set_world.argtypes = [vp, dp, C.c_int32, dp, C.c_int32]
+    L.optik_robot_set_world_grid.argtypes = [vp, dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp]
+    L.optik_robot_world_grid_bake.argtypes = [vp, dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp]
     L.optik_robot_link_frames_batch.argtypes = [vp, C.c_int64, dp, dp, dp]
     L.optik_robot_collision_batch.argtypes = [vp, C.c_int64, dp, dp, dp, C.POINTER(C.c_uint8)]
     L.optik_robot_collision_motion_batch.argtypes = [vp, C.c_int64, dp, dp, C.c_double, dp, dp, C.POINTER(C.c_uint8),
@@ -488,6 +490,36 @@ class Robot:
         sph, box = world_arrays(spheres, boxes)
         if self._L.optik_robot_set_world(self._h, _dp(sph), len(sph), _dp(box), len(box)):
             raise ValueError(_err(self._L))
+
+    # -- the distance-field world (extension; include/optik.h) ----------------------------
+    def set_world_grid(self, origin, voxel, values):
+        """A sampled signed distance field as a third obstacle kind: values [nx, ny, nz] (anything convertible to
+        float32; z fastest), node (i, j, k) at origin + voxel * (i, j, k) in the base frame.  Every robot sphere whose
+        centre lies inside the grid adds (trilinear value - radius) to the clearance minimum; spheres outside it add
+        nothing.  The interpolated field is within sqrt(3) * voxel of a true distance field: add that to the margin
+        for a conservative answer.  set_world leaves the grid alone and this leaves the spheres and boxes alone.
+        Applied to every GPU of the robot.  ValueError for a refused grid."""
+        from .collision import grid_arrays
+        o, v, vals, (nx, ny, nz) = grid_arrays(origin, voxel, values)
+        if self._L.optik_robot_set_world_grid(self._h, _dp(o), v, nx, ny, nz, C.c_void_p(vals.ctypes.data)):
+            raise ValueError(_err(self._L))
+
+    def clear_world_grid(self):
+        """No grid: every call returns what it returns with the spheres and boxes alone."""
+        if self._L.optik_robot_set_world_grid(self._h, None, 0.0, 0, 0, 0, None):
+            raise RuntimeError(_err(self._L))
+
+    def bake_world_grid(self, origin, voxel, shape):
+        """The signed distance of the robot's current spheres and boxes at every node of the grid (origin, voxel,
+        shape = (nx, ny, nz)), computed on the GPU: np.float32 [nx, ny, nz].  Installs nothing (hand the result to
+        set_world_grid).  ValueError for a refused grid or an empty world."""
+        from .collision import grid_arrays
+        o, v, _, (nx, ny, nz) = grid_arrays(origin, voxel, shape=shape)
+        nodes = nx * ny * nz
+        out = np.zeros(nodes if 0 < nodes <= (1 << 24) else 1, dtype=np.float32)
+        if self._L.optik_robot_world_grid_bake(self._h, _dp(o), v, nx, ny, nz, C.c_void_p(out.ctypes.data)):
+            raise ValueError(_err(self._L))
+        return out.reshape(nx, ny, nz)
 
     def _check_xs(self, xs):
         n = self.num_positions()
