@@ -187,6 +187,17 @@ int optik_robot_set_world_grid(optik_robot *robot, const double *origin3, double
                                int32_t nz, const float *values);
 int optik_robot_world_grid_bake(const optik_robot *robot, const double *origin3, double voxel, int32_t nx, int32_t ny,
                                 int32_t nz, float *values_out);
+/* From sensor data to that grid (extension; include/optik_hip.h: optik_hip_world_grid_from_occupancy and
+ * optik_hip_occupancy_from_points).  Host arrays, on the robot's first device; both install nothing.
+ * optik_robot_world_grid_from_occupancy: occupied (nx * ny * nz bytes, non-zero = occupied) -> values_out (floats), the
+ * signed field of an exact Euclidean distance transform, clamped to +-max_distance.
+ * optik_robot_occupancy_from_points: marks in `occupied` (read, then written back: clouds accumulate) the nodes of the
+ * N points3 that none of the E exclude4 spheres (centre, radius; all finite here) holds.  rc 0, or -1. */
+int optik_robot_world_grid_from_occupancy(const optik_robot *robot, double voxel, int32_t nx, int32_t ny, int32_t nz,
+                                          const uint8_t *occupied, double max_distance, float *values_out);
+int optik_robot_occupancy_from_points(const optik_robot *robot, const double *origin3, double voxel, int32_t nx,
+                                      int32_t ny, int32_t nz, const double *points3, int64_t N,
+                                      const double *exclude4, int32_t E, uint8_t *occupied);
 /* x [B][n] -> frames16_out [B][n + 2][16]: every frame as a column-major 4x4 (as optik_robot_fk_ex writes it; frame
  * n + 1 is fk's pose).  ee_offset16 may be NULL.  On the robot's first device; rc 0 or -1. */
 int optik_robot_link_frames_batch(const optik_robot *robot, int64_t B, const double *x, const double *ee_offset16,

@@ -216,6 +216,37 @@ int optik_hip_chain_set_world_grid(optik_hip_chain *chain, const double *origin3
 int optik_hip_world_grid_bake(const optik_hip_chain *chain, const double *origin3, double voxel, int32_t nx,
                               int32_t ny, int32_t nz, float *d_values_out, void *stream);
 
+/* From sensor data to a distance-field world (extension; the arithmetic:
+ * csrc/collision_measure.hpp, steps 8 and 9).  Both calls take device buffers, are stream-ordered and install nothing:
+ * hand the values to optik_hip_chain_set_world_grid.  An occupancy grid is uint8 [nx][ny][nz] on the nodes of a grid
+ * as above (z fastest), non-zero = occupied.
+ *
+ * optik_hip_world_grid_from_occupancy writes the signed field of d_occupied to d_values_out (nx * ny * nz floats) by
+ * an exact Euclidean distance transform: voxel * (distance in voxels to the nearest occupied node - 0.5) at a free
+ * node, minus voxel * (distance to the nearest free node - 0.5) at an occupied one, clamped to +-max_distance; a grid
+ * without occupied (free) nodes is +max_distance (-max_distance) everywhere.  The zero level lies midway between a
+ * free node and an occupied neighbour.  The field takes an occupied voxel for its node: it exceeds the distance to
+ * the voxel cubes by up to (sqrt(3) - 1) / 2 * voxel, on top of the interpolation bound above; a conservative caller
+ * adds both to the margin.  The chain owns the workspace (16 bytes per node, 256 MiB at the 2^24 nodes a grid may
+ * have); it grows on demand, which waits for the device, and is freed with the chain.  One call per chain at a time.
+ *
+ * optik_hip_occupancy_from_points sets d_occupied[node] = 1 at the nearest node (halves up) of each of the N points of
+ * d_points3 ([N][3] doubles, base frame) that lies within half a voxel of the grid and in none of the E exclusion
+ * spheres of d_exclude4 ([E][4]: centre, radius; the self-filter: the robot's own spheres, optik_amd.collision.
+ * spheres_at).  NaN and infinite points are skipped and a NaN sphere excludes nothing.  It only marks and never
+ * clears: clouds accumulate, and the caller zeroes the buffer.  N = 0 does nothing.
+ *
+ * Refused with OPTIK_HIP_EINVAL before any device work: a grid that set_world_grid would refuse for its geometry, a
+ * max_distance that is zero, negative, NaN or infinite, N < 0, E outside 0 .. OPTIK_HIP_MAX_EXCLUDE_SPHERES, a null
+ * buffer that is needed. */
+#define OPTIK_HIP_MAX_EXCLUDE_SPHERES 1024
+int optik_hip_world_grid_from_occupancy(optik_hip_chain *chain, double voxel, int32_t nx, int32_t ny, int32_t nz,
+                                        const uint8_t *d_occupied, double max_distance, float *d_values_out,
+                                        void *stream);
+int optik_hip_occupancy_from_points(const optik_hip_chain *chain, const double *origin3, double voxel, int32_t nx,
+                                    int32_t ny, int32_t nz, const double *d_points3, int64_t N,
+                                    const double *d_exclude4, int32_t E, uint8_t *d_occupied, void *stream);
+
 /* The motion check (extension; the arithmetic: csrc/motion_measure.hpp): is the straight
  * joint-space segment qa -> qb free at a resolution h > 0 (L-infinity, radians)?  With d = max_i |qb_i - qa_i| the
  * segment has K = max(1, (int)ceil(d / h)) steps and K + 1 samples: sample 0 is qa and sample K is qb, copied, and

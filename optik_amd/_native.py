@@ -130,6 +130,10 @@ def lib():
     L.optik_hip_chain_set_world.argtypes = [vp, dp, C.c_int32, dp, C.c_int32]
     L.optik_hip_chain_set_world_grid.argtypes = [vp, dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp]
     L.optik_hip_world_grid_bake.argtypes = [vp, dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp, vp]
+    L.optik_hip_world_grid_from_occupancy.argtypes = [vp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp, C.c_double,
+                                                      vp, vp]
+    L.optik_hip_occupancy_from_points.argtypes = [vp, dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64,
+                                                  vp, C.c_int32, vp, vp]
     L.optik_hip_link_frames_batch.argtypes = [vp, dp, vp, C.c_int64, vp, vp]
     L.optik_hip_collision_batch.argtypes = [vp, dp, vp, C.c_int64, vp, vp, vp]
     L.optik_hip_collision_motion_batch.argtypes = [vp, dp, vp, vp, C.c_int64, C.c_double, vp, vp, vp, vp, vp]

@@ -9,6 +9,8 @@ extents) in the base frame.  Everything here only shapes arrays: the distances a
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
 MAX_SPHERES = 256      # OPTIK_HIP_MAX_COLLISION_SPHERES
@@ -16,6 +18,7 @@ MAX_PAIRS = 4096       # OPTIK_HIP_MAX_COLLISION_PAIRS
 MAX_OBSTACLES = 65536  # OPTIK_HIP_MAX_WORLD_OBSTACLES, of each kind
 MAX_GRID_DIM = 1024    # OPTIK_HIP_MAX_GRID_DIM, per axis (at least 2)
 MAX_GRID_NODES = 1 << 24  # OPTIK_HIP_MAX_GRID_NODES
+MAX_EXCLUDE_SPHERES = 1024  # OPTIK_HIP_MAX_EXCLUDE_SPHERES
 
 
 def auto_pairs(frames):
@@ -90,6 +93,53 @@ def grid_arrays(origin, voxel, values=None, shape=None):
     if len(shape) != 3:
         raise ValueError("shape must be (nx, ny, nz)")
     return origin, float(voxel), values, shape
+
+
+def default_max_distance(voxel, shape):
+    """The grid diagonal voxel * sqrt(nx^2 + ny^2 + nz^2): the clamp of a distance transform that never clamps while
+    the grid holds both occupied and free nodes (the largest distance in it is voxel * sqrt(sum (n - 1)^2))."""
+    return float(voxel) * math.sqrt(float(sum(int(v) * int(v) for v in shape)))
+
+
+def occupancy_array(occupied):
+    """uint8 [nx, ny, nz], C-contiguous, 1 where `occupied` is non-zero (a bool array, counts, anything numeric)."""
+    occupied = np.asarray(occupied)
+    if occupied.ndim != 3:
+        raise ValueError(f"occupied must be [nx, ny, nz], got {list(occupied.shape)}")
+    return np.ascontiguousarray(occupied != 0).view(np.uint8)
+
+
+def cloud_arrays(points, exclude=None):
+    """(points float64 [N, 3], exclude float64 [E, 4]) in the layout of the C ABI; E = 0 without `exclude`."""
+    points = np.asarray(points, dtype=np.float64)
+    if points.ndim != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must be [N, 3], got {list(points.shape)}")
+    exclude = np.zeros((0, 4)) if exclude is None else np.asarray(exclude, dtype=np.float64)
+    if exclude.size == 0:
+        exclude = np.zeros((0, 4))
+    if exclude.ndim != 2 or exclude.shape[1] != 4:
+        raise ValueError(f"exclude must be [E, 4] (centre, radius), got {list(exclude.shape)}")
+    return np.ascontiguousarray(points), np.ascontiguousarray(exclude)
+
+
+def spheres_at(robot, x, frames, centers, radii, pad=0.0, ee_offset=None):
+    """The spheres of a model (frames, centers, radii as set_collision_model takes them) in the base frame at the
+    configuration x: [S, 4] rows of centre and radius, each radius grown by `pad`.  This is the self-filter's input:
+    hand it as `exclude` to occupancy_from_points / set_world_points and the points the camera sees of the robot itself
+    are dropped (pad: the sensor's noise plus whatever the sphere model leaves uncovered).  The frames come from
+    link_frames_batch_arrays (the GPU); the rotation is done here in numpy."""
+    frames = np.asarray(frames, dtype=np.int64).ravel()
+    centers = np.asarray(centers, dtype=np.float64).reshape(-1, 3)
+    radii = np.broadcast_to(np.asarray(radii, dtype=np.float64), (len(frames),))
+    if len(centers) != len(frames):
+        raise ValueError("frames, centers and radii must describe the same number of spheres")
+    T = robot.link_frames_batch_arrays(np.asarray(x, dtype=np.float64).reshape(1, -1), ee_offset)[0]  # [n + 2, 4, 4]
+    if len(frames) and (frames.min() < 0 or frames.max() >= len(T)):
+        raise ValueError(f"frames must be in 0..{len(T) - 1}")
+    out = np.zeros((len(frames), 4))
+    out[:, :3] = np.einsum("sij,sj->si", T[frames, :3, :3], centers) + T[frames, :3, 3]
+    out[:, 3] = radii + float(pad)
+    return out
 
 
 def spheres_along_chain(robot, radius, per_link):

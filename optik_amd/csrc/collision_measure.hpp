@@ -57,8 +57,43 @@
 // The interpolated field approximates: for a 1-Lipschitz field it is a convex combination of corners within one cell
 // diagonal of p, so within sqrt(3) * voxel of the true distance, plus the f32 rounding of the values.
 //
-// Plain host C++ compiles this header too (no HIP runtime): tests/test_collision_host.py and
-// tests/test_world_grid_host.py drive it with g++.
+//
+// From sensor data to that grid: an occupancy grid is turned into a signed field by an
+// exact Euclidean distance transform, and a point cloud is turned into an occupancy grid.  `occupied` is uint8
+// [nx][ny][nz] on the nodes of a grid as above (z fastest), non-zero = occupied.
+//
+//  8. The signed field of an occupancy grid.  For a node p, D2_occ(p) is the minimum over the occupied nodes q of the
+//     squared distance in voxel units, (i_p - i_q)^2 + (j_p - j_q)^2 + (k_p - k_q)^2, an exact integer of at most
+//     3 * 1023^2; D2_free(p) is the same over the free nodes.  max_distance is finite and > 0.
+//         free node:      s = voxel * (sqrt((double)D2_occ) - 0.5)
+//         occupied node:  s = -(voxel * (sqrt((double)D2_free) - 0.5))
+//         a free node of a grid without occupied nodes:  s = +max_distance  (assigned, no arithmetic on a sentinel)
+//         an occupied node of a grid without free nodes: s = -max_distance  (likewise)
+//         value = (float)fmax(fmin(s, max_distance), -max_distance)
+//     The zero level lies midway between a free node and an occupied neighbour (+voxel/2 and -voxel/2), and every
+//     value is finite.  D2 is computed separably and exactly in int32 (edt_scan below): three passes, along z, y and
+//     x, each out[i] = min_j in[j] + (j - i)^2 along its lines, both fields at once.  The first pass reads
+//     in = 0 at the nodes of the field's own set and EDT_NONE = 2^30 elsewhere.  The candidate j = i is always
+//     taken, so no pass ever stores more than EDT_NONE, and the largest sum formed is 2^30 + 1023^2 < 2^31.  A node
+//     still at EDT_NONE after the third pass has no node of that set anywhere in the grid.  D2 is neither capped
+//     nor is the search bounded by a window of max_distance: every D2 is the exact one.
+//  9. Voxelization of a point cloud.  A point p (base frame) has, per axis a,
+//         u_a = (p_a - origin_a) * inv;  w_a = u_a + 0.5
+//     and lies inside iff w_a >= 0.0 && w_a < (double)n_a on all three axes (a NaN fails and the point is skipped;
+//     so is an infinite one).  Its node is i_a = (int)floor(w_a): the nearest node, halves up.  With E exclusion
+//     spheres (c, r) in the base frame the point is dropped iff, for any of them, with dx = p_x - c_x (dy, dz alike),
+//         ((dx * dx + dy * dy) + dz * dz) <= r * r          (a NaN sphere excludes nothing)
+//     A kept point sets occupied[i_x][i_y][i_z] = 1.  Nothing is ever cleared: clouds accumulate in one buffer.
+//
+// What the field of step 8 is not: it takes an occupied voxel for its node, a point.  The true distance from p to the
+// occupied voxel CUBES (side voxel, centred on their nodes) lies between dist_node - (sqrt(3)/2) * voxel and dist_node
+// - voxel/2, where dist_node = voxel * sqrt(D2_occ); the field's voxel * (sqrt(D2_occ) - 0.5) is the upper end of that
+// range, so it is optimistic by up to ((sqrt(3) - 1) / 2) * voxel = 0.366 * voxel.  The trilinear bound above comes on
+// top: a caller who needs a conservative answer adds (sqrt(3) + (sqrt(3) - 1) / 2) * voxel = 2.098 * voxel to the
+// margin (and whatever the sensor's own error is).  The arithmetic does not hide any of this.
+//
+// Plain host C++ compiles this header too (no HIP runtime): tests/test_collision_host.py,
+// tests/test_world_grid_host.py and tests/test_world_occupancy_host.py drive it with g++.
 #pragma once
 
 #include <cmath>
@@ -165,6 +200,76 @@ OPTIK_CM_HD inline void grid_node(const double *origin, double voxel, int i, int
     p[2] = origin[2] + voxel * (double)k;
 }
 
+// Step 8.  The squared distances of one node to both node sets, in voxel units.
+struct alignas(8) EdtPair {
+    int32_t occ;    // to the nearest occupied node
+    int32_t free_;  // to the nearest free node
+};
+constexpr int32_t EDT_NONE = 1 << 30;  // no node of the set seen so far
+
+// What the first pass reads at a node.
+OPTIK_CM_HD inline EdtPair edt_source(uint8_t occupied) {
+    return occupied ? EdtPair{0, EDT_NONE} : EdtPair{EDT_NONE, 0};
+}
+
+// One node of one pass: min_j in(j) + (j - i)^2 over the line's nodes j = 0 .. n - 1, for both fields.  in(j) >= 0,
+// so a candidate at distance t is at least t^2: the scan walks outward from i and stops once t^2 reaches the larger
+// of the two minima (or both ends of the line).  Exact; t <= 1023, in(j) <= 2^30.
+template <class In>
+OPTIK_CM_HD inline EdtPair edt_scan(const In &in, int i, int n) {
+    EdtPair best = in(i);
+    for (int t = 1; t < n; ++t) {
+        const int32_t tt = t * t;
+        if (tt >= (best.occ > best.free_ ? best.occ : best.free_)) break;
+        const bool lo = i - t >= 0, hi = i + t < n;
+        if (!lo && !hi) break;
+        if (lo) {
+            const EdtPair v = in(i - t);
+            if (v.occ + tt < best.occ) best.occ = v.occ + tt;
+            if (v.free_ + tt < best.free_) best.free_ = v.free_ + tt;
+        }
+        if (hi) {
+            const EdtPair v = in(i + t);
+            if (v.occ + tt < best.occ) best.occ = v.occ + tt;
+            if (v.free_ + tt < best.free_) best.free_ = v.free_ + tt;
+        }
+    }
+    return best;
+}
+
+// The value of a node from its two squared distances after the third pass.
+OPTIK_CM_HD inline float occupancy_value(uint8_t occupied, EdtPair d2, double voxel, double max_distance) {
+    double s;
+    if (occupied) {
+        if (d2.free_ >= EDT_NONE) s = -max_distance;
+        else s = -(voxel * (sqrt((double)d2.free_) - 0.5));
+    } else {
+        if (d2.occ >= EDT_NONE) s = max_distance;
+        else s = voxel * (sqrt((double)d2.occ) - 0.5);
+    }
+    return (float)fmax(fmin(s, max_distance), -max_distance);
+}
+
+// Step 9: the node of a point, or false (outside, NaN, infinite).
+OPTIK_CM_HD inline bool point_node(const double *p, const double *origin, double inv, const int32_t *n, int *ijk) {
+    const double wx = (p[0] - origin[0]) * inv + 0.5;
+    const double wy = (p[1] - origin[1]) * inv + 0.5;
+    const double wz = (p[2] - origin[2]) * inv + 0.5;
+    const bool inside = wx >= 0.0 && wx < (double)n[0] && wy >= 0.0 && wy < (double)n[1]
+                        && wz >= 0.0 && wz < (double)n[2];
+    if (!inside) return false;
+    ijk[0] = (int)floor(wx);
+    ijk[1] = (int)floor(wy);
+    ijk[2] = (int)floor(wz);
+    return true;
+}
+
+// Step 9: does the exclusion sphere (c, r) = sphere4 drop the point?
+OPTIK_CM_HD inline bool point_excluded(const double *p, const double *sphere4) {
+    const double dx = p[0] - sphere4[0], dy = p[1] - sphere4[1], dz = p[2] - sphere4[2];
+    return ((dx * dx + dy * dy) + dz * dz) <= sphere4[3] * sphere4[3];
+}
+
 OPTIK_CM_HD inline bool pose_has_nan(const double *pose7) {
     bool nan = false;
     for (int i = 0; i < 7; ++i) nan = nan || (pose7[i] != pose7[i]);
@@ -209,6 +314,42 @@ inline double clearance_grid(int nf, const double *frames, int S, const int32_t 
         c = fmin(c, grid_distance(p, radii[s], grid));
     }
     return c;
+}
+
+// Step 8, the reference form: the three passes on the host.  a, b: workspace, nx * ny * nz pairs each.
+inline void occupancy_field(const uint8_t *occupied, int nx, int ny, int nz, double voxel, double max_distance,
+                            EdtPair *a, EdtPair *b, float *out) {
+    const long long nodes = (long long)nx * ny * nz;
+    const long long sy = nz, sx = (long long)ny * nz;
+    for (long long p = 0; p < nodes; ++p) {
+        const long long base = p - p % nz;
+        a[p] = edt_scan([&](int j) { return edt_source(occupied[base + j]); }, (int)(p % nz), nz);
+    }
+    for (long long p = 0; p < nodes; ++p) {
+        const int i = (int)(p / sy % ny);
+        const long long base = p - i * sy;
+        b[p] = edt_scan([&](int j) { return a[base + j * sy]; }, i, ny);
+    }
+    for (long long p = 0; p < nodes; ++p) {
+        const int i = (int)(p / sx);
+        const long long base = p - i * sx;
+        a[p] = edt_scan([&](int j) { return b[base + j * sx]; }, i, nx);
+    }
+    for (long long p = 0; p < nodes; ++p) out[p] = occupancy_value(occupied[p], a[p], voxel, max_distance);
+}
+
+// Step 9, the reference form: marks and never clears.
+inline void voxelize(const double *origin, double voxel, const int32_t *n, const double *points3, long long N,
+                     const double *exclude4, int E, uint8_t *occupied) {
+    const double inv = 1.0 / voxel;
+    for (long long i = 0; i < N; ++i) {
+        const double *p = points3 + 3 * i;
+        int ijk[3];
+        if (!point_node(p, origin, inv, n, ijk)) continue;
+        bool drop = false;
+        for (int e = 0; e < E && !drop; ++e) drop = point_excluded(p, exclude4 + 4 * e);
+        if (!drop) occupied[((long long)ijk[0] * n[1] + ijk[1]) * n[2] + ijk[2]] = 1;
+    }
 }
 
 }  // namespace coll

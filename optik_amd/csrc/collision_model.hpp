@@ -141,6 +141,25 @@ inline int check_grid(const double *origin3, double voxel, int32_t nx, int32_t n
     return 0;
 }
 
+// The arguments of the distance transform and of the voxelization beyond the grid's geometry (collision_measure.hpp,
+// steps 8 and 9).
+inline int check_max_distance(double max_distance, std::string &err) {
+    if (!(max_distance > 0.0) || !std::isfinite(max_distance)) {
+        err = "world grid from occupancy: max_distance must be finite and > 0";
+        return OPTIK_HIP_EINVAL;
+    }
+    return 0;
+}
+
+inline int check_cloud(int64_t N, int32_t E, std::string &err) {
+    if (N < 0) { err = "occupancy from points: the point count is negative"; return OPTIK_HIP_EINVAL; }
+    if (E < 0 || E > OPTIK_HIP_MAX_EXCLUDE_SPHERES) {
+        err = "occupancy from points: the exclusion sphere count must be in 0..1024";
+        return OPTIK_HIP_EINVAL;
+    }
+    return 0;
+}
+
 inline const char *bake_empty_msg() { return "world grid bake: the world has no spheres and no boxes"; }
 
 // The device layout of a checked model; returns the number of pair groups.

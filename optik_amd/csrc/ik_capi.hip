@@ -175,6 +175,7 @@ void optik_hip_chain_destroy(optik_hip_chain *ch) {
     if (ch->world_dev) hipFree(ch->world_dev);
     if (ch->grid_dev) hipFree(ch->grid_dev);
     if (ch->motion_ws) hipFree(ch->motion_ws);
+    if (ch->edt_ws) hipFree(ch->edt_ws);
     if (ch->tmp_x) hipFree(ch->tmp_x);
     if (ch->tmp_f) hipFree(ch->tmp_f);
     if (ch->tmp_key) hipFree(ch->tmp_key);

@@ -8,6 +8,7 @@
 //   ik_manip.hip       the manipulability / condition keys of solution modes 3 and 4, optik_hip_manip_batch
 //   ik_collision.hip   the collision filter: model and world, its key pass, link frames and clearance batches
 //   ik_motion.hip      the motion check: segments between configurations, the motion key pass of optik_hip_ik_path
+//   ik_occupancy.hip   occupancy grids and point clouds into distance-field worlds (distance transform, voxelize)
 //   ik_batch_ops.hip   objective / gradient, FK / Jacobian and seed batches, the test probes
 //   ik_lane_kernel.hip, ik_quad_kernel.hip, ik_wide_kernel.hip    the restart solvers (one restart loop each)
 #pragma once
@@ -287,6 +288,10 @@ struct optik_hip_chain {
     optik_hip_launch_info last{};
     int num_cus = 0;
     int wall_clock_khz = 0;
+    // the distance transform (ik_occupancy.hip): the two ping-pong buffers of optik_hip_world_grid_from_occupancy, 16
+    // bytes per node (256 MiB at 2^24 nodes); grown on demand
+    void *edt_ws = nullptr;
+    size_t edt_ws_cap = 0;  // bytes
 };
 
 namespace optik {

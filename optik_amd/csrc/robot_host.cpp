@@ -1430,6 +1430,73 @@ int optik_robot_world_grid_bake(const optik_robot *r, const double *origin3, dou
     return rc;
 }
 
+int optik_robot_world_grid_from_occupancy(const optik_robot *r, double voxel, int32_t nx, int32_t ny, int32_t nz,
+                                          const uint8_t *occupied, double max_distance, float *values_out) {
+    if (!r || !occupied || !values_out) return set_err(-1, "null argument");
+    std::string err;
+    const double zero3[3] = {0.0, 0.0, 0.0};
+    if (optik::coll::check_grid(zero3, voxel, nx, ny, nz, nullptr, false, err)
+        || optik::coll::check_max_distance(max_distance, err))
+        return set_err(-1, err);
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    std::lock_guard<std::mutex> lock(c->batch_mu);
+    optik::DeviceScope dev_scope(c->device);
+    if (!dev_scope.ok()) return set_err(-1, "hipSetDevice failed");
+    const size_t nodes = (size_t)nx * (size_t)ny * (size_t)nz;
+    // one block: the values, then the occupancy bytes
+    float *d_out = nullptr;
+    if (hipMalloc(&d_out, 5 * nodes) != hipSuccess) return set_err(-1, "occupancy buffer allocation failed");
+    uint8_t *d_occ = reinterpret_cast<uint8_t *>(d_out + nodes);
+    int rc = 0;
+    if (hipMemcpy(d_occ, occupied, nodes, hipMemcpyHostToDevice) != hipSuccess)
+        rc = set_err(-1, "upload failed");
+    else if (optik_hip_world_grid_from_occupancy(c->chain, voxel, nx, ny, nz, d_occ, max_distance, d_out, nullptr))
+        rc = set_err(-1, optik_hip_last_error());
+    else if (hipMemcpy(values_out, d_out, sizeof(float) * nodes, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = set_err(-1, "download failed");
+    (void)hipFree(d_out);
+    return rc;
+}
+
+int optik_robot_occupancy_from_points(const optik_robot *r, const double *origin3, double voxel, int32_t nx, int32_t ny,
+                                      int32_t nz, const double *points3, int64_t N, const double *exclude4, int32_t E,
+                                      uint8_t *occupied) {
+    if (!r) return set_err(-1, "null argument");
+    std::string err;
+    if (optik::coll::check_grid(origin3, voxel, nx, ny, nz, nullptr, false, err) || optik::coll::check_cloud(N, E, err))
+        return set_err(-1, err);
+    if (N == 0) return 0;
+    if (!points3 || !occupied || (E > 0 && !exclude4)) return set_err(-1, "null argument");
+    for (int64_t k = 0; k < 4 * (int64_t)E; ++k)
+        if (!std::isfinite(exclude4[k])) return set_err(-1, "occupancy from points: non-finite exclusion sphere");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    std::lock_guard<std::mutex> lock(c->batch_mu);
+    optik::DeviceScope dev_scope(c->device);
+    if (!dev_scope.ok()) return set_err(-1, "hipSetDevice failed");
+    const size_t nodes = (size_t)nx * (size_t)ny * (size_t)nz;
+    // one block: the points, the exclusion spheres, then the occupancy bytes
+    const size_t doubles = 3 * (size_t)N + 4 * (size_t)E;
+    double *d_pts = nullptr;
+    if (hipMalloc(&d_pts, sizeof(double) * doubles + nodes) != hipSuccess)
+        return set_err(-1, "point buffer allocation failed");
+    double *d_exc = d_pts + 3 * (size_t)N;
+    uint8_t *d_occ = reinterpret_cast<uint8_t *>(d_pts + doubles);
+    int rc = 0;
+    if (hipMemcpy(d_pts, points3, sizeof(double) * 3 * (size_t)N, hipMemcpyHostToDevice) != hipSuccess
+        || (E > 0 && hipMemcpy(d_exc, exclude4, sizeof(double) * 4 * (size_t)E, hipMemcpyHostToDevice) != hipSuccess)
+        || hipMemcpy(d_occ, occupied, nodes, hipMemcpyHostToDevice) != hipSuccess)
+        rc = set_err(-1, "upload failed");
+    else if (optik_hip_occupancy_from_points(c->chain, origin3, voxel, nx, ny, nz, d_pts, N, E > 0 ? d_exc : nullptr, E,
+                                             d_occ, nullptr))
+        rc = set_err(-1, optik_hip_last_error());
+    else if (hipMemcpy(occupied, d_occ, nodes, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = set_err(-1, "download failed");
+    (void)hipFree(d_pts);
+    return rc;
+}
+
 namespace {
 
 // B rows of x [B][n] through one of the per-configuration kernels of ik_collision.hip on the robot's first device, in

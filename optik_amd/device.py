@@ -173,6 +173,49 @@ class HipChain:
         nat.check(nat.lib().optik_hip_world_grid_bake(self._h, _dp(o), v, nx, ny, nz, _ptr(out), _stream_ptr()))
         return out.view(nx, ny, nz)
 
+    # -- from sensor data to that grid (include/optik_hip.h) --------------------------------
+    def world_grid_from_occupancy(self, voxel, occupied, max_distance=None):
+        """The signed field of an occupancy grid (a uint8 or bool cuda tensor [nx, ny, nz], non-zero = occupied) by an
+        exact Euclidean distance transform: a float32 cuda tensor [nx, ny, nz], clamped to +-max_distance (default:
+        the grid diagonal).  Stream-ordered; installs nothing.  The chain's workspace grows on demand."""
+        from .collision import default_max_distance
+        if not (isinstance(occupied, torch.Tensor) and occupied.is_cuda and occupied.dim() == 3
+                and occupied.dtype in (torch.uint8, torch.bool) and occupied.is_contiguous()):
+            raise ValueError("occupied must be a contiguous uint8 or bool cuda tensor [nx, ny, nz]")
+        nx, ny, nz = (int(v) for v in occupied.shape)
+        md = default_max_distance(voxel, (nx, ny, nz)) if max_distance is None else float(max_distance)
+        out = torch.empty((nx, ny, nz) if nx * ny * nz <= (1 << 24) else (1, 1, 1), dtype=torch.float32,
+                          device=self.device)
+        nat.check(nat.lib().optik_hip_world_grid_from_occupancy(self._h, float(voxel), nx, ny, nz, _ptr(occupied), md,
+                                                                _ptr(out), _stream_ptr()))
+        return out
+
+    def occupancy_from_points(self, origin, voxel, shape, points, exclude=None, into=None):
+        """Marks the nodes of a point cloud (a float64 cuda tensor [N, 3], base frame) that none of the spheres of
+        `exclude` (float64 cuda tensor [E, 4], E <= 1024) holds: a uint8 cuda tensor [nx, ny, nz].  `into`: a tensor of
+        that kind to accumulate into, in place (it is also what is returned).  Stream-ordered."""
+        from .collision import grid_arrays
+        o, v, _, (nx, ny, nz) = grid_arrays(origin, voxel, shape=shape)
+
+        def f64(t, cols, name):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.dim() == 2
+                    and t.shape[1] == cols and t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous float64 cuda tensor [*, {cols}]")
+            return t
+        points = f64(points, 3, "points")
+        E = 0 if exclude is None else int(f64(exclude, 4, "exclude").shape[0])
+        nodes = nx * ny * nz
+        if into is None:
+            into = torch.zeros((nx, ny, nz) if 0 < nodes <= (1 << 24) else (1, 1, 1), dtype=torch.uint8,
+                               device=self.device)
+        elif not (isinstance(into, torch.Tensor) and into.is_cuda and into.dtype == torch.uint8
+                  and tuple(into.shape) == (nx, ny, nz) and into.is_contiguous()):
+            raise ValueError("into must be a contiguous uint8 cuda tensor of the grid's shape")
+        nat.check(nat.lib().optik_hip_occupancy_from_points(self._h, _dp(o), v, nx, ny, nz, _ptr(points),
+                                                            int(points.shape[0]), _ptr(exclude) if E else None, E,
+                                                            _ptr(into), _stream_ptr()))
+        return into
+
     def _check_q(self, q):
         if not (isinstance(q, torch.Tensor) and q.is_cuda and q.dtype == torch.float64 and q.dim() == 2
                 and q.shape[0] == self.n and q.is_contiguous()):

@@ -45,6 +45,10 @@ def _bind(L):
     L.optik_robot_set_world.argtypes = [vp, dp, C.c_int32, dp, C.c_int32]
     L.optik_robot_set_world_grid.argtypes = [vp, dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp]
     L.optik_robot_world_grid_bake.argtypes = [vp, dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp]
+    L.optik_robot_world_grid_from_occupancy.argtypes = [vp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp, C.c_double,
+                                                        vp]
+    L.optik_robot_occupancy_from_points.argtypes = [vp, dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64,
+                                                    vp, C.c_int32, vp]
     L.optik_robot_link_frames_batch.argtypes = [vp, C.c_int64, dp, dp, dp]
     L.optik_robot_collision_batch.argtypes = [vp, C.c_int64, dp, dp, dp, C.POINTER(C.c_uint8)]
     L.optik_robot_collision_motion_batch.argtypes = [vp, C.c_int64, dp, dp, C.c_double, dp, dp, C.POINTER(C.c_uint8),
@@ -520,6 +524,55 @@ class Robot:
         if self._L.optik_robot_world_grid_bake(self._h, _dp(o), v, nx, ny, nz, C.c_void_p(out.ctypes.data)):
             raise ValueError(_err(self._L))
         return out.reshape(nx, ny, nz)
+
+    # -- from sensor data to that grid (extension; include/optik.h) --------------------------
+    def world_grid_from_occupancy(self, voxel, occupied, max_distance=None):
+        """The signed field of an occupancy grid `occupied` [nx, ny, nz] (non-zero = occupied), by an exact Euclidean
+        distance transform on the GPU: np.float32 [nx, ny, nz], voxel * (distance in voxels to the nearest occupied
+        node - 0.5) at a free node and minus voxel * (distance to the nearest free node - 0.5) at an occupied one,
+        clamped to +-max_distance (default: the grid diagonal, which never clamps while both kinds of node exist).
+        The field takes a voxel for its node: it is optimistic by up to (sqrt(3) - 1) / 2 * voxel on top of
+        set_world_grid's sqrt(3) * voxel.  Installs nothing.  ValueError for a refused grid or max_distance."""
+        from .collision import default_max_distance, occupancy_array
+        occ = occupancy_array(occupied)
+        nx, ny, nz = occ.shape
+        md = default_max_distance(voxel, occ.shape) if max_distance is None else float(max_distance)
+        nodes = nx * ny * nz
+        out = np.zeros(nodes if 0 < nodes <= (1 << 24) else 1, dtype=np.float32)
+        if self._L.optik_robot_world_grid_from_occupancy(self._h, float(voxel), nx, ny, nz, C.c_void_p(occ.ctypes.data),
+                                                         md, C.c_void_p(out.ctypes.data)):
+            raise ValueError(_err(self._L))
+        return out.reshape(nx, ny, nz)
+
+    def occupancy_from_points(self, origin, voxel, shape, points, exclude=None, into=None):
+        """The occupancy grid of a point cloud, on the GPU: a bool array [nx, ny, nz] that is True at the nearest node
+        of every point of `points` [N, 3] (base frame) that lies within half a voxel of the grid and inside none of
+        the spheres of `exclude` [E, 4] (centre, radius: the self-filter, optik_amd.collision.spheres_at).  NaN and
+        infinite points are skipped.  `into`: an earlier result to accumulate into (it is not modified).
+        ValueError for a refused grid, more than 1024 exclusion spheres or a non-finite one."""
+        from .collision import cloud_arrays, grid_arrays, occupancy_array
+        o, v, _, (nx, ny, nz) = grid_arrays(origin, voxel, shape=shape)
+        pts, exc = cloud_arrays(points, exclude)
+        nodes = nx * ny * nz
+        if into is not None:
+            occ = occupancy_array(into).copy()
+            if occ.shape != (nx, ny, nz):
+                raise ValueError("into does not have the grid's shape")
+        else:
+            occ = np.zeros((nx, ny, nz) if 0 < nodes <= (1 << 24) else (1, 1, 1), dtype=np.uint8)
+        if self._L.optik_robot_occupancy_from_points(self._h, _dp(o), v, nx, ny, nz, C.c_void_p(pts.ctypes.data),
+                                                     len(pts), C.c_void_p(exc.ctypes.data) if len(exc) else None,
+                                                     len(exc), C.c_void_p(occ.ctypes.data)):
+            raise ValueError(_err(self._L))
+        return occ.view(bool)
+
+    def set_world_points(self, origin, voxel, shape, points, exclude=None, max_distance=None):
+        """From a point cloud to the installed distance-field world: occupancy_from_points, then
+        world_grid_from_occupancy, then set_world_grid.  Returns the values it installed."""
+        occ = self.occupancy_from_points(origin, voxel, shape, points, exclude)
+        values = self.world_grid_from_occupancy(voxel, occ, max_distance)
+        self.set_world_grid(origin, voxel, values)
+        return values
 
     def _check_xs(self, xs):
         n = self.num_positions()
