@@ -19,7 +19,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "liboptik_amd.so")
 SOURCES = ["ik_capi.hip", "ik_select.hip", "ik_solutions.hip", "ik_path.hip", "ik_manip.hip", "ik_collision.hip", "ik_motion.hip", "ik_occupancy.hip", "ik_batch_ops.hip", "ik_quad_kernel.hip", "ik_lane_kernel.hip", "ik_wide_kernel.hip",
-           "robot_host.cpp"]
+           "robot_host.cpp", "robot_rows.cpp"]
 # translation units: (source, object, extra flags).  ik_quad_kernel.hip is compiled twice -- its
 # throughput form (two waves per SIMD) without the machine-LICM pass, which otherwise hoists constants and
 # LDS addresses out of the solver loop only for the register allocator to spill them to scratch
@@ -53,7 +53,8 @@ UNITS = [("ik_capi.hip", "ik_capi.o", []),          # chains, options, the resta
                                                      "-mllvm", "-greedy-reverse-local-assignment=1"]),
          # chains with 9 .. 16 joint positions: one run-time-n body per kernel (ik_wide.hpp)
          ("ik_wide_kernel.hip", "ik_wide_kernel.o", []),
-         ("robot_host.cpp", "robot_host.o", [])]
+         ("robot_host.cpp", "robot_host.o", []),    # the robot object, devices, FK / Jacobian, ik and its batches
+         ("robot_rows.cpp", "robot_rows.o", [])]    # row batches, collision model / world setters, world builders
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
          "-Wno-unused-value", "-pthread"]
 # What a translation unit depends on is what the compiler says it read: every object is compiled with

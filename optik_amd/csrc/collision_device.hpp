@@ -223,10 +223,10 @@ inline void fill_launch(const optik_hip_chain *ch, const double *ee_offset7, con
         a.margin = ch->coll_margin;
         a.Ms = ch->world_Ms;
         a.Mb = ch->world_Mb;
-        a.wsph = ch->world_dev;
-        a.wbox = ch->world_dev ? ch->world_dev + 4 * (size_t)ch->world_Ms : nullptr;
+        a.wsph = ch->world_dev.get();
+        a.wbox = a.wsph ? a.wsph + 4 * (size_t)ch->world_Ms : nullptr;
         if (ch->grid_n[0] > 0) {
-            a.grid.values = ch->grid_dev;
+            a.grid.values = ch->grid_dev.get();
             a.grid.inv = ch->grid_inv;
             for (int k = 0; k < 3; ++k) {
                 a.grid.origin[k] = ch->grid_origin[k];

@@ -1,6 +1,6 @@
 // collision_model.hpp -- the collision model and world of a chain on the host: the argument checks shared by the
 // kernel layer (optik_hip_chain_set_collision_model / _set_world, ik_collision.hip) and the robot layer
-// (optik_robot_set_collision_model / _set_world, robot_host.cpp), and the device layout of the model.
+// (optik_robot_set_collision_model / _set_world, robot_rows.cpp), and the device layout of the model.
 //
 // The device model keeps the robot spheres grouped by frame and the self pairs grouped by (frame of a, frame of b):
 // the kernels look a frame up once per group, not once per sphere (collision_measure.hpp: the minimum is exact in

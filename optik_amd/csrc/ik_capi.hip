@@ -166,29 +166,15 @@ void optik_hip_chain_destroy(optik_hip_chain *ch) {
     if (ch->claim_pending) (void)hipStreamSynchronize(nullptr);
     if (ch->dev) hipFree(ch->dev);
     if (ch->wdev) hipFree(ch->wdev);
-    if (ch->wide_ws) hipFree(ch->wide_ws);
-    if (ch->tile_recs) hipFree(ch->tile_recs);
-    if (ch->first_success) hipFree(ch->first_success);
-    if (ch->sol_pick) hipFree(ch->sol_pick);
-    if (ch->path_carry) hipFree(ch->path_carry);
     if (ch->coll_dev) hipFree(ch->coll_dev);
-    if (ch->world_dev) hipFree(ch->world_dev);
-    if (ch->grid_dev) hipFree(ch->grid_dev);
-    if (ch->motion_ws) hipFree(ch->motion_ws);
-    if (ch->edt_ws) hipFree(ch->edt_ws);
-    if (ch->tmp_x) hipFree(ch->tmp_x);
-    if (ch->tmp_f) hipFree(ch->tmp_f);
-    if (ch->tmp_key) hipFree(ch->tmp_key);
     if (ch->queue) hipFree(ch->queue);
-    if (ch->hw_dev) hipFree(ch->hw_dev);
-    if (ch->hw_pin) hipHostFree(ch->hw_pin);
     if (ch->hw_claim) hipHostFree(ch->hw_claim);
     if (ch->claim_done) hipEventDestroy(ch->claim_done);
     for (int i = 0; i < optik_hip_chain::EV_POOL; ++i) {
         if (ch->ev0[i]) hipEventDestroy(ch->ev0[i]);
         if (ch->ev1[i]) hipEventDestroy(ch->ev1[i]);
     }
-    delete ch;
+    delete ch;  // (the grow-only buffers free themselves, under dev_scope)
 }
 
 int32_t optik_hip_chain_num_positions(const optik_hip_chain *ch) { return ch ? ch->n : 0; }
@@ -268,7 +254,7 @@ static int ik_batch_locked(optik_hip_chain *ch, const optik_solver_config *cfg, 
         SelectLaunch s;
         std::memset(&s, 0, sizeof s);
         s.out_key = sl.pk; s.out_x = sl.px; s.out_f = sl.pf;
-        s.tile_recs = ch->tile_recs;
+        s.tile_recs = ch->tile_recs.get();
         s.tiles_per_target = (int)sl.tiles_per_target;
         s.tile = SEL_TILE;
         s.n = ch->n;
@@ -278,7 +264,7 @@ static int ik_batch_locked(optik_hip_chain *ch, const optik_solver_config *cfg, 
         s.win_x = out->d_win_x; s.win_f = out->d_win_f;
         s.win_idx = (unsigned long long *)out->d_win_idx; s.win_key = out->d_win_key;
         s.reset_queue = ch->queue;
-        s.reset_fs = sl.early ? ch->first_success : nullptr;
+        s.reset_fs = sl.early ? ch->first_success.get() : nullptr;
         HIP_TRY(select_launch(s, T, stream));
         ch->queue_clean = true;
         ch->fs_clean = sl.fs_clean_after;
@@ -326,12 +312,7 @@ static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, con
     const int n_tiles = (int)n_tiles64;
     const size_t cols = (size_t)T * (size_t)R;
 
-    if ((size_t)n_tiles > ch->tile_cap) {
-        if (ch->tile_recs) HIP_TRY(hipFree(ch->tile_recs));
-        ch->tile_recs = nullptr;
-        HIP_TRY(hipMalloc(&ch->tile_recs, sizeof(TileRec) * (size_t)n_tiles));
-        ch->tile_cap = (size_t)n_tiles;
-    }
+    HIP_TRY(ch->tile_recs.reserve((size_t)n_tiles));
     if (!ch->queue) { HIP_TRY(hipMalloc(&ch->queue, sizeof(unsigned long long))); ch->queue_clean = false; }
     // (the words are only known to be clean to a launch queued behind the selection kernel that cleaned them)
     if (stream != ch->clean_stream) { ch->queue_clean = false; ch->fs_clean = 0; }
@@ -340,15 +321,10 @@ static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, con
     const bool early = (flags & OPTIK_HIP_IK_EARLY_EXIT) && mode == OPTIK_MODE_SPEED && !coll;
     size_t fs_clean_after = ch->fs_clean;  // (a launch without early exit leaves the words alone)
     if (early) {
-        if ((size_t)T > ch->fs_cap) {
-            if (ch->first_success) HIP_TRY(hipFree(ch->first_success));
-            ch->first_success = nullptr;
-            ch->fs_clean = 0;
-            HIP_TRY(hipMalloc(&ch->first_success, sizeof(unsigned long long) * (size_t)T));
-            ch->fs_cap = (size_t)T;
-        }
+        if ((size_t)T > ch->first_success.capacity()) ch->fs_clean = 0;  // (a new block: no word of it is clean)
+        HIP_TRY(ch->first_success.reserve((size_t)T));
         if (ch->fs_clean < (size_t)T)
-            HIP_TRY(hipMemsetAsync(ch->first_success, 0xff, sizeof(unsigned long long) * (size_t)T, stream));
+            HIP_TRY(hipMemsetAsync(ch->first_success.get(), 0xff, sizeof(unsigned long long) * (size_t)T, stream));
         fs_clean_after = std::max(ch->fs_clean, (size_t)T);  // once the selection kernel has put words [0, T) back
         ch->fs_clean = 0;
     }
@@ -359,21 +335,18 @@ static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, con
     need_x = need_x || (want_sel && (manip || coll));
     if (want_sel) {
         const bool need_xf = (!px || !pf) && (need_x || need_f);
-        if (cols > ch->tmp_cols) {
-            if (ch->tmp_x) HIP_TRY(hipFree(ch->tmp_x));
-            if (ch->tmp_f) HIP_TRY(hipFree(ch->tmp_f));
-            if (ch->tmp_key) HIP_TRY(hipFree(ch->tmp_key));
-            ch->tmp_x = ch->tmp_f = ch->tmp_key = nullptr;
-            HIP_TRY(hipMalloc(&ch->tmp_key, sizeof(double) * cols));
-            ch->tmp_cols = cols;
+        if (cols > ch->tmp_key.capacity()) {  // (x and f go with the old key block; they come back below if wanted)
+            HIP_TRY(ch->tmp_x.reset());
+            HIP_TRY(ch->tmp_f.reset());
+            HIP_TRY(ch->tmp_key.reserve(cols));
         }
-        if (need_xf && !ch->tmp_x) {
-            HIP_TRY(hipMalloc(&ch->tmp_x, sizeof(double) * ch->tmp_cols * (size_t)ch->n));
-            HIP_TRY(hipMalloc(&ch->tmp_f, sizeof(double) * ch->tmp_cols));
+        if (need_xf) {
+            HIP_TRY(ch->tmp_x.reserve(ch->tmp_key.capacity() * (size_t)ch->n));
+            HIP_TRY(ch->tmp_f.reserve(ch->tmp_key.capacity()));
         }
-        pk = ch->tmp_key;
-        if (!px && need_x) px = ch->tmp_x;
-        if (!pf && need_f) pf = ch->tmp_f;
+        pk = ch->tmp_key.get();
+        if (!px && need_x) px = ch->tmp_x.get();
+        if (!pf && need_f) pf = ch->tmp_f.get();
     }
 
     SolveLaunch a;
@@ -389,7 +362,7 @@ static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, con
     a.wq.restart_begin = restart_begin;
     a.wq.targets = d_targets;
     a.wq.x0 = d_x0;
-    a.wq.first_success = early ? ch->first_success : nullptr;
+    a.wq.first_success = early ? ch->first_success.get() : nullptr;
     a.wq.find_any = (early && (flags & OPTIK_HIP_IK_FIND_ANY)) ? 1 : 0;
     a.wq.claim = nullptr;
     a.wq.claim_seq = 0;
@@ -509,19 +482,14 @@ static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, con
         // resident wave with its own block of the restart workspace (ik_wide.hpp)
         // (one restart per wave -- a single ik() call's rounds --: the restart's arrays in the wave's LDS)
         const bool lds_form = wide_lds;
-        if (!lds_form && (size_t)grid > ch->wide_ws_waves) {
-            if (ch->wide_ws) HIP_TRY(hipFree(ch->wide_ws));
-            ch->wide_ws = nullptr; ch->wide_ws_waves = 0;
-            HIP_TRY(hipMalloc(&ch->wide_ws, sizeof(double) * wide_ws_doubles_per_wave() * (size_t)grid));
-            ch->wide_ws_waves = (size_t)grid;
-        }
+        if (!lds_form) HIP_TRY(ch->wide_ws.reserve(wide_ws_doubles_per_wave() * (size_t)grid));
         WideSolveLaunch w;
         std::memset(&w, 0, sizeof w);
         w.chain = ch->wdev;
         w.ep = a.ep; w.sp = a.sp; w.wq = a.wq;
         std::memcpy(w.key, ch->key, sizeof w.key);
         w.deadline_ticks = a.deadline_ticks;
-        w.ws = ch->wide_ws;
+        w.ws = ch->wide_ws.get();
         lds = lds_form ? wide_lds_bytes() : (int)sizeof(WideChainDev);
         HIP_TRY(wide_solve_launch(grid, stream, w, lds_form, opt().wide_form != 2));
     } else if (lanek) {
@@ -569,17 +537,12 @@ int optik_hip_ik_solutions(optik_hip_chain *ch, const optik_solver_config *cfg, 
                               &none, true, true, out->d_f != nullptr, stream, false, nullptr, &sl))
         return rc;
     BIND_DEVICE(ch);
-    if (sl.tiles_per_target > 1 && (size_t)T > ch->sol_pick_cap) {  // (the multi-tile form's round-to-round acceptances)
-        if (ch->sol_pick) HIP_TRY(hipFree(ch->sol_pick));
-        ch->sol_pick = nullptr; ch->sol_pick_cap = 0;
-        HIP_TRY(hipMalloc(&ch->sol_pick, sizeof(unsigned long long) * (size_t)T));
-        ch->sol_pick_cap = (size_t)T;
-    }
+    if (sl.tiles_per_target > 1) HIP_TRY(ch->sol_pick.reserve((size_t)T));  // (the multi-tile form's round-to-round acceptances)
     SolutionsLaunch s;
     std::memset(&s, 0, sizeof s);
     s.out_key = sl.pk; s.out_x = sl.px; s.out_f = sl.pf;
-    s.tile_recs = ch->tile_recs;
-    s.pick = ch->sol_pick;
+    s.tile_recs = ch->tile_recs.get();
+    s.pick = ch->sol_pick.get();
     s.tiles_per_target = (int)sl.tiles_per_target;
     s.tile = SEL_TILE;
     s.n = ch->n;
@@ -619,13 +582,7 @@ int optik_hip_ik_path(optik_hip_chain *ch, const optik_solver_config *cfg, const
     const uint32_t solve_flags = flags | ((cfg->solution_mode == OPTIK_MODE_SPEED && !filter) ? OPTIK_HIP_IK_EARLY_EXIT : 0u);
     {
         BIND_DEVICE(ch);
-        const size_t need = (size_t)P * (size_t)n;
-        if (need > ch->path_carry_cap) {
-            if (ch->path_carry) HIP_TRY(hipFree(ch->path_carry));
-            ch->path_carry = nullptr; ch->path_carry_cap = 0;
-            HIP_TRY(hipMalloc(&ch->path_carry, sizeof(double) * need));
-            ch->path_carry_cap = need;
-        }
+        HIP_TRY(ch->path_carry.reserve((size_t)P * (size_t)n));
     }
     // the motion check between waypoints (ik_motion.hip): one more key pass per waypoint, in front of the selection
     const bool motion = ch->motion_h > 0.0 && ch->coll_S > 0;
@@ -636,7 +593,7 @@ int optik_hip_ik_path(optik_hip_chain *ch, const optik_solver_config *cfg, const
     optik_hip_ik_outputs none;
     std::memset(&none, 0, sizeof none);
     for (int32_t l = 0; l < L; ++l) {
-        const double *seed = l == 0 ? d_x0 : ch->path_carry;
+        const double *seed = l == 0 ? d_x0 : ch->path_carry.get();
         SolvedLaunch sl;
         if (int rc = solve_locked(ch, cfg, d_targets + (size_t)l * (size_t)P * 7, seed, P, ee_offset7, restart_begin,
                                   restart_end, solve_flags, deadline_s, &none, true, true, out->d_f != nullptr, stream,
@@ -652,7 +609,7 @@ int optik_hip_ik_path(optik_hip_chain *ch, const optik_solver_config *cfg, const
         std::memset(&s, 0, sizeof s);
         s.out_key = sl.pk; s.out_x = sl.px; s.out_f = sl.pf;
         s.seed = seed;
-        s.carry = ch->path_carry;
+        s.carry = ch->path_carry.get();
         s.last = l + 1 == L ? out->d_last : nullptr;
         s.n = n;
         s.filter = filter ? 1 : 0;
@@ -666,7 +623,7 @@ int optik_hip_ik_path(optik_hip_chain *ch, const optik_solver_config *cfg, const
         s.key = out->d_key ? out->d_key + w : nullptr;
         s.step = out->d_step ? out->d_step + w : nullptr;
         s.reset_queue = ch->queue;
-        s.reset_fs = sl.early ? ch->first_success : nullptr;
+        s.reset_fs = sl.early ? ch->first_success.get() : nullptr;
         HIP_TRY(path_select_launch(s, P, stream));
         ch->queue_clean = true;
         ch->fs_clean = sl.fs_clean_after;
@@ -716,22 +673,18 @@ int optik_hip_ik_host(optik_hip_chain *ch, const optik_solver_config *cfg, const
     const size_t n_in = (size_t)(7 + n) * (size_t)T, n_out = (size_t)(n + 3) * (size_t)T;
     // (`mu` from here to the launch: the claim state and the staging blocks belong to the launch workspace)
     std::unique_lock<std::mutex> launch_lock(ch->mu);
-    if (n_in + n_out > ch->hw_cap) {
+    if (n_in + n_out > ch->hw_dev.capacity() || 2 * (n_in + n_out) > ch->hw_pin.capacity()) {
         if (ch->claim_pending) { (void)hipStreamSynchronize(nullptr); ch->claim_pending = false; }  // (its launch reads the block about to go)
-        if (ch->hw_dev) (void)hipFree(ch->hw_dev);
-        if (ch->hw_pin) (void)hipHostFree(ch->hw_pin);
-        ch->hw_dev = nullptr; ch->hw_pin = nullptr; ch->hw_cap = 0;
-        HIP_TRY(hipMalloc(&ch->hw_dev, sizeof(double) * (n_in + n_out)));
-        HIP_TRY(hipHostMalloc(&ch->hw_pin, sizeof(double) * 2 * (n_in + n_out)));  // (two blocks, see below)
-        ch->hw_cap = n_in + n_out;
+        HIP_TRY(ch->hw_dev.reserve(n_in + n_out));
+        HIP_TRY(ch->hw_pin.reserve(2 * (n_in + n_out)));  // (two blocks, see below)
     }
     // A few targets (Robot::ik: one): the kernels read the inputs from and write the winners to the
     // pinned block directly -- no copy commands around the launch.  (Two such blocks, used in turn: a call
     // that returned on the first success -- below -- leaves a launch behind whose last restarts still read theirs.)
     const bool zero_copy = T <= 16;
-    double *pin = ch->hw_pin;
+    double *pin = ch->hw_pin.get();
     if (zero_copy) {
-        pin += (ch->hw_flip & 1u) * ch->hw_cap;
+        pin += (ch->hw_flip & 1u) * (ch->hw_pin.capacity() / 2);
         ch->hw_flip ^= 1u;
     } else if (ch->claim_pending) {
         // The staged path always uses block 0.  A launch that a first-success call left running may have been given
@@ -740,14 +693,14 @@ int optik_hip_ik_host(optik_hip_chain *ch, const optik_solver_config *cfg, const
         HIP_TRY(hipStreamSynchronize(nullptr));
         ch->claim_pending = false;
     }
-    double *io = zero_copy ? pin : ch->hw_dev;
+    double *io = zero_copy ? pin : ch->hw_dev.get();
     double *d_t = io, *d_x0 = d_t + (size_t)7 * T;
     double *d_wx = io + n_in, *d_wf = d_wx + (size_t)n * T, *d_wk = d_wf + T;
     uint64_t *d_wi = reinterpret_cast<uint64_t *>(d_wk + T);
     std::memcpy(pin, targets, sizeof(double) * 7 * (size_t)T);
     std::memcpy(pin + (size_t)7 * T, x0, sizeof(double) * (size_t)n * (size_t)T);
     if (!zero_copy)
-        HIP_TRY(hipMemcpyAsync(ch->hw_dev, pin, sizeof(double) * n_in, hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(hipMemcpyAsync(ch->hw_dev.get(), pin, sizeof(double) * n_in, hipMemcpyHostToDevice, nullptr));
     optik_hip_ik_outputs o;
     std::memset(&o, 0, sizeof o);
     o.d_win_x = d_wx; o.d_win_f = d_wf; o.d_win_idx = d_wi; o.d_win_key = d_wk;

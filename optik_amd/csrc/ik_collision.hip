@@ -210,16 +210,11 @@ int optik_hip_chain_set_world(optik_hip_chain *ch, const double *spheres4, int32
     BIND_DEVICE(ch);
     if (int rc = drain_chain(ch)) return rc;
     const size_t need = 4 * (size_t)Ms + 10 * (size_t)Mb;
-    if (need > ch->world_cap) {
-        if (ch->world_dev) HIP_TRY(hipFree(ch->world_dev));
-        ch->world_dev = nullptr; ch->world_cap = 0;
-        ch->world_Ms = ch->world_Mb = 0;
-        HIP_TRY(hipMalloc(&ch->world_dev, sizeof(double) * need));
-        ch->world_cap = need;
-    }
-    if (Ms > 0) HIP_TRY(hipMemcpy(ch->world_dev, spheres4, sizeof(double) * 4 * (size_t)Ms, hipMemcpyHostToDevice));
+    if (need > ch->world_dev.capacity()) ch->world_Ms = ch->world_Mb = 0;  // (no world while the block is replaced)
+    HIP_TRY(ch->world_dev.reserve(need));
+    if (Ms > 0) HIP_TRY(hipMemcpy(ch->world_dev.get(), spheres4, sizeof(double) * 4 * (size_t)Ms, hipMemcpyHostToDevice));
     if (Mb > 0)
-        HIP_TRY(hipMemcpy(ch->world_dev + 4 * (size_t)Ms, boxes10, sizeof(double) * 10 * (size_t)Mb,
+        HIP_TRY(hipMemcpy(ch->world_dev.get() + 4 * (size_t)Ms, boxes10, sizeof(double) * 10 * (size_t)Mb,
                           hipMemcpyHostToDevice));
     ch->world_Ms = Ms; ch->world_Mb = Mb;
     return 0;
@@ -238,13 +233,8 @@ int optik_hip_chain_set_world_grid(optik_hip_chain *ch, const double *origin3, d
     ch->grid_n[0] = ch->grid_n[1] = ch->grid_n[2] = 0;
     if (clear) return 0;
     const size_t need = (size_t)nx * (size_t)ny * (size_t)nz;
-    if (need > ch->grid_cap) {
-        if (ch->grid_dev) HIP_TRY(hipFree(ch->grid_dev));
-        ch->grid_dev = nullptr; ch->grid_cap = 0;
-        HIP_TRY(hipMalloc(&ch->grid_dev, sizeof(float) * need));
-        ch->grid_cap = need;
-    }
-    HIP_TRY(hipMemcpy(ch->grid_dev, values, sizeof(float) * need, hipMemcpyHostToDevice));
+    HIP_TRY(ch->grid_dev.reserve(need));
+    HIP_TRY(hipMemcpy(ch->grid_dev.get(), values, sizeof(float) * need, hipMemcpyHostToDevice));
     for (int k = 0; k < 3; ++k) ch->grid_origin[k] = origin3[k];
     ch->grid_inv = 1.0 / voxel;
     ch->grid_n[0] = nx; ch->grid_n[1] = ny; ch->grid_n[2] = nz;
@@ -261,8 +251,8 @@ int optik_hip_world_grid_bake(const optik_hip_chain *ch, const double *origin3, 
     BIND_DEVICE(ch);
     BakeLaunch a;
     std::memset(&a, 0, sizeof a);
-    a.wsph = ch->world_dev;
-    a.wbox = ch->world_dev + 4 * (size_t)ch->world_Ms;
+    a.wsph = ch->world_dev.get();
+    a.wbox = ch->world_dev.get() + 4 * (size_t)ch->world_Ms;
     a.Ms = ch->world_Ms; a.Mb = ch->world_Mb;
     for (int k = 0; k < 3; ++k) a.origin[k] = origin3[k];
     a.voxel = voxel;

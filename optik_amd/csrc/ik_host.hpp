@@ -21,6 +21,7 @@
 #include <string>
 
 #include "../../include/optik_hip.h"
+#include "device_buf.hpp"
 #include "device_scope.hpp"
 #include "ik_host_params.hpp"
 #include "ik_launch.hpp"
@@ -142,7 +143,7 @@ int motion_key_launch(const optik_hip_chain *ch, const double *ee_offset7, const
 // ---- options ---------------------------------------------------------------------------------------------
 // Every tuning option of the kernel layer, in one place.  The defaults come from the environment ONCE, at the
 // first use (the OPTIK_* names below); tests and tools change them through optik_hip_set_option (optik_hip.h).
-// Nothing else in this library reads the environment (robot_host.cpp: OPTIK_HOST_THREADS, OPTIK_DEVICES).
+// Nothing else in this library reads the environment (robot_host.hpp: OPTIK_HOST_THREADS, robot_host.cpp: OPTIK_DEVICES).
 enum : int { SK_AUTO = 0, SK_QUAD = 1, SK_LANE64 = 2, SK_GENERAL = 3 };
 struct Options {
     int solve_kernel = SK_AUTO;      // OPTIK_SOLVE_KERNEL = quad | lane64 | general: which single-launch solver (auto: by size)
@@ -219,8 +220,7 @@ struct optik_hip_chain {
     bool wide = false;
     optik::WideChainDev whost;
     optik::WideChainDev *wdev = nullptr;
-    double *wide_ws = nullptr;  // restart workspace of the resident waves
-    size_t wide_ws_waves = 0;
+    optik::DeviceBuf<double> wide_ws;  // restart workspace of the resident waves (wide_ws_doubles_per_wave() each)
     int device_id = 0;   // the HIP device the chain lives on (the current device at creation)
     // a chain with prismatic joints: FK only (as in the reference); the joint table for fk_general_kernel
     bool prismatic = false;
@@ -230,33 +230,27 @@ struct optik_hip_chain {
     // launch workspace (grown on demand; one in-flight ik call per chain handle)
     std::mutex mu;
     std::mutex host_mu;  // serialises optik_hip_ik_host calls (they share the staging blocks below)
-    optik::host::TileRec *tile_recs = nullptr;
-    size_t tile_cap = 0;
-    unsigned long long *first_success = nullptr;
-    size_t fs_cap = 0;
-    unsigned long long *sol_pick = nullptr;  // optik_hip_ik_solutions: per target, the last accepted column
-    size_t sol_pick_cap = 0;
-    double *path_carry = nullptr;  // optik_hip_ik_path: [P][n] the seeds of the next waypoint
-    size_t path_carry_cap = 0;     // doubles
+    // (the grow-only buffers below free themselves when the chain is deleted: optik_hip_chain_destroy binds the device)
+    optik::DeviceBuf<optik::host::TileRec> tile_recs;
+    optik::DeviceBuf<unsigned long long> first_success;
+    optik::DeviceBuf<unsigned long long> sol_pick;  // optik_hip_ik_solutions: per target, the last accepted column
+    optik::DeviceBuf<double> path_carry;            // optik_hip_ik_path: [P][n] the seeds of the next waypoint
     // the collision filter (ik_collision.hip): active while coll_S > 0; the model as the kernels stage it, the world
     // as spheres [world_Ms][4] then boxes [world_Mb][10]
     int coll_S = 0, coll_P = 0, coll_groups = 0;
     double coll_margin = 0.0;
     optik::coll::ModelDev *coll_dev = nullptr;
-    double *world_dev = nullptr;
-    size_t world_cap = 0;  // doubles
+    optik::DeviceBuf<double> world_dev;
     int world_Ms = 0, world_Mb = 0;
     // the distance-field world (optik_hip_chain_set_world_grid): float32 [nx][ny][nz]; null: no grid
-    float *grid_dev = nullptr;
-    size_t grid_cap = 0;  // floats
+    optik::DeviceBuf<float> grid_dev;
     int grid_n[3] = {0, 0, 0};
     double grid_origin[3] = {0.0, 0.0, 0.0};
     double grid_inv = 0.0;
     // the motion check (ik_motion.hip): the resolution of ik_path's motion key pass (0: off) and the workspace of a
     // motion launch (prefix of the sample counts, the segments' reduction words)
     double motion_h = 0.0;
-    void *motion_ws = nullptr;
-    size_t motion_ws_cap = 0;  // bytes
+    optik::DeviceBuf<unsigned char> motion_ws;  // bytes
     // (what the last launch's selection kernel left behind: the work-item counter at 0, this many leading
     // first-success words at ~0 -- a launch that finds them so skips its fill commands)
     // (host-side knowledge that holds for launches ORDERED behind that selection kernel: the stream it ran on is kept
@@ -265,12 +259,12 @@ struct optik_hip_chain {
     size_t fs_clean = 0;
     hipStream_t clean_stream = nullptr;
     // scratch per-restart buffers when the caller does not provide them
-    double *tmp_x = nullptr, *tmp_f = nullptr, *tmp_key = nullptr;
-    size_t tmp_cols = 0;
+    // (tmp_key's capacity is the columns; tmp_x and tmp_f follow it, allocated only when a launch needs them)
+    optik::DeviceBuf<double> tmp_x, tmp_f, tmp_key;
     unsigned long long *queue = nullptr;  // work-item counter of the in-flight launch
     unsigned long long *prof = nullptr;   // phase timers (OPTIK_PROFILE builds)
-    double *hw_dev = nullptr, *hw_pin = nullptr;  // optik_hip_ik_host: device block and pinned staging
-    size_t hw_cap = 0;                            // doubles
+    optik::DeviceBuf<double> hw_dev;  // optik_hip_ik_host: the device block ...
+    optik::PinnedBuf<double> hw_pin;  // ... and its pinned staging, two blocks of the device block's size
     // optik_hip_ik_host, one target under the first-success rule: the block the first successful restart writes its
     // answer to (WorkQueue::claim; pinned, host-coherent) and the sequence number of the last launch that used it
     unsigned long long *hw_claim = nullptr;
@@ -290,8 +284,7 @@ struct optik_hip_chain {
     int wall_clock_khz = 0;
     // the distance transform (ik_occupancy.hip): the two ping-pong buffers of optik_hip_world_grid_from_occupancy, 16
     // bytes per node (256 MiB at 2^24 nodes); grown on demand
-    void *edt_ws = nullptr;
-    size_t edt_ws_cap = 0;  // bytes
+    optik::DeviceBuf<unsigned char> edt_ws;  // bytes
 };
 
 namespace optik {

@@ -287,7 +287,7 @@ int motion_launch(const optik_hip_chain *ch, MotionLaunch &a, bool classify, uns
                   hipStream_t stream) {
     const long long B = a.B;
     const long long blocks = (B + MBLOCK - 1) / MBLOCK;
-    unsigned long long *w = static_cast<unsigned long long *>(ch->motion_ws);
+    unsigned long long *w = reinterpret_cast<unsigned long long *>(ch->motion_ws.get());
     a.G = w; w += B + 1;
     a.bsum = w; w += blocks + 1;
     a.mkey = w; w += B;
@@ -327,12 +327,7 @@ namespace host {
 
 int motion_reserve(optik_hip_chain *ch, long long segments) {
     if (segments > (1ll << 30)) return fail(OPTIK_HIP_EINVAL, "motion check: more than 2^30 segments in one launch");
-    const size_t need = ws_bytes(segments);
-    if (need <= ch->motion_ws_cap) return 0;
-    if (ch->motion_ws) HIP_TRY(hipFree(ch->motion_ws));
-    ch->motion_ws = nullptr; ch->motion_ws_cap = 0;
-    HIP_TRY(hipMalloc(&ch->motion_ws, need));
-    ch->motion_ws_cap = need;
+    HIP_TRY(ch->motion_ws.reserve(ws_bytes(segments)));
     return 0;
 }
 
@@ -340,7 +335,7 @@ int motion_key_launch(const optik_hip_chain *ch, const double *ee_offset7, const
                       double *key, int P, size_t R, int filter, double max_step, hipStream_t stream) {
     if (ch->prismatic) return fail(OPTIK_HIP_EUNSUPPORTED, prismatic_msg());
     const long long B = (long long)P * (long long)R;
-    if (ws_bytes(B) > ch->motion_ws_cap) return fail(OPTIK_HIP_EINVAL, "motion check: workspace not reserved");
+    if (ws_bytes(B) > ch->motion_ws.capacity()) return fail(OPTIK_HIP_EINVAL, "motion check: workspace not reserved");
     MotionLaunch a;
     std::memset(&a, 0, sizeof a);
     fill_launch(ch, ee_offset7, nullptr, B, a.c);

@@ -86,12 +86,7 @@ __global__ __launch_bounds__(256) void voxelize_kernel(const VoxLaunch a) {
 const double kZero3[3] = {0.0, 0.0, 0.0};
 
 int edt_reserve(optik_hip_chain *ch, size_t nodes) {
-    const size_t need = 2 * sizeof(coll::EdtPair) * nodes;
-    if (need <= ch->edt_ws_cap) return 0;
-    if (ch->edt_ws) HIP_TRY(hipFree(ch->edt_ws));
-    ch->edt_ws = nullptr; ch->edt_ws_cap = 0;
-    HIP_TRY(hipMalloc(&ch->edt_ws, need));
-    ch->edt_ws_cap = need;
+    HIP_TRY(ch->edt_ws.reserve(2 * sizeof(coll::EdtPair) * nodes));
     return 0;
 }
 
@@ -120,7 +115,7 @@ int optik_hip_world_grid_from_occupancy(optik_hip_chain *ch, double voxel, int32
     a.n[0] = nx; a.n[1] = ny; a.n[2] = nz;
     a.voxel = voxel;
     a.max_distance = max_distance;
-    coll::EdtPair *w0 = static_cast<coll::EdtPair *>(ch->edt_ws), *w1 = w0 + nodes;
+    coll::EdtPair *w0 = reinterpret_cast<coll::EdtPair *>(ch->edt_ws.get()), *w1 = w0 + nodes;
     const int grid = grid_for(ch, (long long)nodes, 256, 8);
     a.out = w0;
     hipLaunchKernelGGL(edt_pass_kernel<2>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);

@@ -26,108 +26,35 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/optik.h"
-#include "collision_model.hpp"
-#include "device_scope.hpp"
 #include "diff_ik_lp.hpp"
-#include "urdf_chain.hpp"
+#include "pose_convert.hpp"
+#include "robot_host.hpp"
 
-using optik_host::Chain;
-using optik_host::HPose;
+using namespace optik::robot;
+using namespace optik::pose;
 
-// What the robot keeps on one GPU: the uploaded chain and reusable staging for the host API.
-struct DeviceCtx {
-    int device = 0;
-    optik_hip_chain *chain = nullptr;
-    double *d_scratch = nullptr;  // q[n] | pose[7] | jac[6n]
-    double *h_scratch = nullptr;  // the same, pinned host memory the FK kernel reads and writes directly
-    int num_cus = 0;
-    // optik_robot_ik_batch_ex workspace, grown on demand and kept across calls:
-    // device block = targets [T][7] | x0 [T][n] | win_x [T][n] | win_f [T] | win_key [T] | win_idx [T]
-    double *d_batch = nullptr;
-    double *h_batch = nullptr;  // pinned mirror
-    size_t batch_cap = 0;       // doubles
-    std::mutex batch_mu;        // one batch at a time per device
-};
-
-struct optik_robot {
-    Chain chain;
-    int n = 0;
-    std::vector<double> lb, ub;
-    std::vector<double> origins, axes;  // n_joints x 7, n_joints x 3
-    std::vector<int32_t> types;
-    // set_parallelism (lib.rs:66-72).  The rayon pool size has no counterpart, but its one
-    // observable consequence has: with one thread SolutionMode::Speed returns the lowest
-    // successful restart (deterministic; tests/test_ik.rs:45-89 sets 1 for exactly that), with more
-    // it returns whichever success comes first (find_any, lib.rs:409-412; README.md:17, 96).
-    // 0 = never set = the reference's default pool (ThreadPoolBuilder::default(): every core,
-    // lib.rs:42-47) and n > 1 let a Speed call stop at the first success anywhere; 1 gives the
-    // deterministic 1-thread answer.
-    unsigned parallelism = 0;
-    mutable std::mutex mu;     // guards the lazily created device contexts and the FK scratch
-    // GPUs this robot spreads restart ranges / targets over (optik_robot_set_devices,
-    // OPTIK_DEVICES); empty = the HIP device current at first use.  The same id may be listed
-    // more than once (two contexts on one GPU: how the sharding is tested on a 1-GPU box).
-    std::vector<int> device_ids;
-    mutable std::vector<std::unique_ptr<DeviceCtx>> devs;
-    // over how many of them the widest round of the last ik / ik_batch call was actually cut (optik_robot_last_parts)
-    mutable std::atomic<int32_t> last_parts{0};
-    // the collision model and world (optik_robot_set_collision_model / _set_world), kept on the host and applied to
-    // every device chain, also to those created later; the filter is active while coll_frames is not empty
-    std::vector<int32_t> coll_frames, coll_pairs;
-    std::vector<double> coll_centers, coll_radii;
-    double coll_margin = 0.0;
-    std::vector<double> world_spheres, world_boxes;
-    // the distance-field world (optik_robot_set_world_grid); no grid while grid_values is empty
-    std::vector<float> grid_values;
-    double grid_origin[3] = {0.0, 0.0, 0.0}, grid_voxel = 0.0;
-    int32_t grid_n[3] = {0, 0, 0};
-    double motion_h = 0.0;  // optik_robot_set_motion_resolution (0: off)
-    bool collision_active() const {
-        std::lock_guard<std::mutex> lock(mu);
-        return !coll_frames.empty();
-    }
-};
+thread_local std::string optik::robot::g_robot_err;
 
 namespace {
 
-thread_local std::string g_robot_err;
-
-[[noreturn]] void panic(const std::string &msg) {
-    // A Rust panic crossing `extern "C"` aborts the process; keep the message.
-    std::fprintf(stderr, "optik: %s\n", msg.c_str());
-    std::fflush(stderr);
-    std::abort();
-}
-
-int set_err(int code, const std::string &msg) {
-    g_robot_err = msg;
-    return code;
-}
-
-// diff_ik and diff_ik_batch refuse the same chains with the same words
-const char *const kDiffIkMaxNMsg =
-    "diff_ik: chains of more than 8 joint positions are not supported (the reference's own "
-    "diff_ik only runs for n = 6: lib.rs:196-197 builds a 6-row block for n columns)";
-
-std::vector<int> devices_from_env();
-
-// fn(begin, end) over [0, count) on a few host threads when the range is long (the per-target
-// host work of a batch -- validation, pose conversion, staging, gathering -- is ~50 ns a target:
-// 13 of 60 ms at 262 144 targets on one thread)
-template <class Fn>
-void parallel_ranges(size_t count, Fn fn) {
-    static const unsigned max_threads = [] {
-        const char *e = std::getenv("OPTIK_HOST_THREADS");
-        unsigned h = e ? (unsigned)std::atoi(e) : std::thread::hardware_concurrency() / 2;
-        return h < 1 ? 1u : (h > 8 ? 8u : h);
-    }();
-    const size_t parts = count < 32768 ? 1 : std::min<size_t>(max_threads, count / 16384);
-    if (parts <= 1) { fn((size_t)0, count); return; }
-    std::vector<std::thread> th;
-    for (size_t p = 1; p < parts; ++p) th.emplace_back(fn, count * p / parts, count * (p + 1) / parts);
-    fn((size_t)0, count / parts);
-    for (auto &t : th) t.join();
+// OPTIK_DEVICES = "all" | "N" (the first N devices) | "0,2,3": GPUs a robot spreads work over
+std::vector<int> devices_from_env() {
+    std::vector<int> ids;
+    const char *e = std::getenv("OPTIK_DEVICES");
+    if (!e || !*e) return ids;
+    int have = 0;
+    (void)hipGetDeviceCount(&have);
+    const std::string v(e);
+    if (v == "all") { for (int i = 0; i < have; ++i) ids.push_back(i); return ids; }
+    if (v.find(',') == std::string::npos) {
+        const int cnt = std::atoi(v.c_str());
+        for (int i = 0; i < cnt && i < have; ++i) ids.push_back(i);
+        return ids;
+    }
+    std::stringstream ss(v);
+    for (std::string tok; std::getline(ss, tok, ',');)
+        if (!tok.empty()) ids.push_back(std::atoi(tok.c_str()));
+    return ids;
 }
 
 optik_robot *make_robot(const std::string &urdf, const char *base, const char *ee) {
@@ -159,233 +86,7 @@ optik_robot *make_robot(const std::string &urdf, const char *base, const char *e
     return r;
 }
 
-// Context k of the robot (its k-th listed GPU), created on first use.  Returns nullptr and sets
-// the error string on failure.
-DeviceCtx *device_ctx(const optik_robot *r, size_t k = 0) {
-    std::lock_guard<std::mutex> lock(r->mu);
-    if (r->devs.empty()) {
-        const size_t count = r->device_ids.empty() ? 1 : r->device_ids.size();
-        for (size_t i = 0; i < count; ++i) r->devs.emplace_back(new DeviceCtx());
-    }
-    if (k >= r->devs.size()) { g_robot_err = "no such device context"; return nullptr; }
-    DeviceCtx *c = r->devs[k].get();
-    if (c->chain) return c;
-    int devid = 0;
-    if (r->device_ids.empty()) (void)hipGetDevice(&devid);
-    else devid = r->device_ids[k];
-    // (the caller's device is current again when this returns, also when the set-up fails)
-    optik::DeviceScope dev_scope(devid);
-    if (!dev_scope.ok()) {
-        g_robot_err = "hipSetDevice(" + std::to_string(devid) + ") failed";
-        return nullptr;
-    }
-    optik_hip_chain *h = nullptr;
-    const int rc = optik_hip_chain_create(r->origins.data(), r->axes.data(), r->types.data(),
-                                          (int32_t)r->types.size(), r->lb.data(), r->ub.data(), r->n, &h);
-    if (rc) {
-        g_robot_err = std::string("GPU chain creation failed: ") + optik_hip_last_error();
-        return nullptr;
-    }
-    if (hipMalloc(&c->d_scratch, sizeof(double) * (size_t)(r->n + 7 + 6 * r->n)) != hipSuccess
-        || hipHostMalloc(&c->h_scratch, sizeof(double) * (size_t)(r->n + 7 + 6 * r->n)) != hipSuccess) {
-        if (c->d_scratch) { (void)hipFree(c->d_scratch); c->d_scratch = nullptr; }
-        optik_hip_chain_destroy(h);
-        g_robot_err = "GPU scratch allocation failed";
-        return nullptr;
-    }
-    // (a model or world set before this chain existed)
-    if ((!r->coll_frames.empty()
-         && optik_hip_chain_set_collision_model(h, r->coll_frames.data(), r->coll_centers.data(), r->coll_radii.data(),
-                                                (int32_t)r->coll_frames.size(), r->coll_pairs.data(),
-                                                (int32_t)(r->coll_pairs.size() / 2), r->coll_margin))
-        || ((!r->world_spheres.empty() || !r->world_boxes.empty())
-            && optik_hip_chain_set_world(h, r->world_spheres.data(), (int32_t)(r->world_spheres.size() / 4),
-                                         r->world_boxes.data(), (int32_t)(r->world_boxes.size() / 10)))
-        || (!r->grid_values.empty()
-            && optik_hip_chain_set_world_grid(h, r->grid_origin, r->grid_voxel, r->grid_n[0], r->grid_n[1],
-                                              r->grid_n[2], r->grid_values.data()))
-        || (r->motion_h > 0.0 && optik_hip_chain_set_motion_resolution(h, r->motion_h))) {
-        g_robot_err = std::string("collision model, world or motion resolution upload failed: ") + optik_hip_last_error();
-        (void)hipFree(c->d_scratch); c->d_scratch = nullptr;
-        (void)hipHostFree(c->h_scratch); c->h_scratch = nullptr;
-        optik_hip_chain_destroy(h);
-        return nullptr;
-    }
-    (void)hipDeviceGetAttribute(&c->num_cus, hipDeviceAttributeMultiprocessorCount, devid);
-    c->device = devid;
-    c->chain = h;
-    return c;
-}
-
 size_t device_count(const optik_robot *r) { return r->device_ids.empty() ? 1 : r->device_ids.size(); }
-
-// OPTIK_DEVICES = "all" | "N" (the first N devices) | "0,2,3": GPUs a robot spreads work over
-std::vector<int> devices_from_env() {
-    std::vector<int> ids;
-    const char *e = std::getenv("OPTIK_DEVICES");
-    if (!e || !*e) return ids;
-    int have = 0;
-    (void)hipGetDeviceCount(&have);
-    const std::string v(e);
-    if (v == "all") { for (int i = 0; i < have; ++i) ids.push_back(i); return ids; }
-    if (v.find(',') == std::string::npos) {
-        const int cnt = std::atoi(v.c_str());
-        for (int i = 0; i < cnt && i < have; ++i) ids.push_back(i);
-        return ids;
-    }
-    std::stringstream ss(v);
-    for (std::string tok; std::getline(ss, tok, ',');)
-        if (!tok.empty()) ids.push_back(std::atoi(tok.c_str()));
-    return ids;
-}
-
-// UnitQuaternion::from_rotation_matrix (nalgebra 0.34, not vendored): the four closed-form branches.  It ends in
-// Self::new_unchecked(res): NO normalisation -- both bindings' conversions go through it, so one function serves both
-// (round 5 normalised on the Python path only: ADVICE r5).
-void quat_from_rotation(const double R[3][3], double &w, double &i, double &j, double &k) {
-    const double tr = R[0][0] + R[1][1] + R[2][2];
-    if (tr > 0.0) {
-        const double d = std::sqrt(tr + 1.0) * 2.0;
-        w = 0.25 * d; i = (R[2][1] - R[1][2]) / d; j = (R[0][2] - R[2][0]) / d; k = (R[1][0] - R[0][1]) / d;
-    } else if (R[0][0] > R[1][1] && R[0][0] > R[2][2]) {
-        const double d = std::sqrt(1.0 + R[0][0] - R[1][1] - R[2][2]) * 2.0;
-        w = (R[2][1] - R[1][2]) / d; i = 0.25 * d; j = (R[0][1] + R[1][0]) / d; k = (R[0][2] + R[2][0]) / d;
-    } else if (R[1][1] > R[2][2]) {
-        const double d = std::sqrt(1.0 + R[1][1] - R[0][0] - R[2][2]) * 2.0;
-        w = (R[0][2] - R[2][0]) / d; i = (R[0][1] + R[1][0]) / d; j = 0.25 * d; k = (R[1][2] + R[2][1]) / d;
-    } else {
-        const double d = std::sqrt(1.0 + R[2][2] - R[0][0] - R[1][1]) * 2.0;
-        w = (R[1][0] - R[0][1]) / d; i = (R[0][2] + R[2][0]) / d; j = (R[1][2] + R[2][1]) / d; k = 0.25 * d;
-    }
-}
-
-// 4x4 column-major homogeneous matrix -> pose7 as the pyo3 path does it (optik-py/src/lib.rs:8-15:
-// try_convert::<Matrix4, Isometry3> -> Isometry3::from_superset_unchecked -> UnitQuaternion::from_rotation_matrix on the
-// upper-left block, as it stands).  The C path's iterative UnitQuaternion::from_matrix is pose7_from_mat16_iterative
-// below: the same rotation, last bits apart.
-void pose7_from_mat16(const double *m, double *p) {
-    double R[3][3];
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) R[r][c] = m[c * 4 + r];
-    p[0] = m[12]; p[1] = m[13]; p[2] = m[14];
-    quat_from_rotation(R, p[6], p[3], p[4], p[5]);
-}
-
-// Rotation3::from_axis_angle (nalgebra: Rodrigues' formula entry by entry; angle == 0 -> identity).
-void rot_from_axis_angle(const double u[3], double angle, double O[3][3]) {
-    if (angle == 0.0) {
-        for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) O[r][c] = r == c ? 1.0 : 0.0;
-        return;
-    }
-    const double ux = u[0], uy = u[1], uz = u[2];
-    const double sqx = ux * ux, sqy = uy * uy, sqz = uz * uz;
-    double sn, cs;  // (f64::sin_cos: platform libm; ONE sincos call here and in the oracle -- sin + cos can differ from it in the last bit)
-    ::sincos(angle, &sn, &cs);
-    const double omc = 1.0 - cs;
-    O[0][0] = sqx + (1.0 - sqx) * cs; O[0][1] = ux * uy * omc - uz * sn; O[0][2] = ux * uz * omc + uy * sn;
-    O[1][0] = ux * uy * omc + uz * sn; O[1][1] = sqy + (1.0 - sqy) * cs; O[1][2] = uy * uz * omc - ux * sn;
-    O[2][0] = ux * uz * omc - uy * sn; O[2][1] = uy * uz * omc + ux * sn; O[2][2] = sqz + (1.0 - sqz) * cs;
-}
-
-// 3x3 product as nalgebra forms it (gemv per column: the terms of an entry accumulated in order k = 0, 1, 2).
-void mat3_mul(const double A[3][3], const double B[3][3], double O[3][3]) {
-    double T[3][3];
-    for (int c = 0; c < 3; ++c)
-        for (int r = 0; r < 3; ++r) {
-            double acc = A[r][0] * B[0][c];
-            acc = A[r][1] * B[1][c] + acc;
-            acc = A[r][2] * B[2][c] + acc;
-            T[r][c] = acc;
-        }
-    std::memcpy(O, T, sizeof T);
-}
-
-// ||M - R||_F^2, column by column (Matrix::norm_squared).
-double diff_norm_squared(const double M[3][3], const double R[3][3]) {
-    double res = 0.0;
-    for (int c = 0; c < 3; ++c) {
-        const double d0 = M[0][c] - R[0][c], d1 = M[1][c] - R[1][c], d2 = M[2][c] - R[2][c];
-        res += d0 * d0 + d1 * d1 + d2 * d2;
-    }
-    return res;
-}
-
-// UnitQuaternion::from_matrix (optik-cpp/src/lib.rs:141-142) = Rotation3::from_matrix_eps(m, f64::EPSILON, 0 =
-// unlimited, identity) -- nalgebra 0.34 (Cargo.lock:579-581, not vendored), "A Robust Method to Extract the
-// Rotational Part of Deformations" (Mueller et al.) with nalgebra's perturbation step at a stalled iterate --
-// followed by from_rotation_matrix.  Restated from the crate's published source; the iteration cap is this
-// implementation's (nalgebra's is usize::MAX: a rotation matrix converges in a few dozen steps).
-void quat_from_matrix_iterative(const double M[3][3], double &w, double &i, double &j, double &k) {
-    const double eps = 2.220446049250313e-16;
-    const double eps_disturbance = std::fmax(std::sqrt(eps), eps * eps);
-    double axes[3] = {1.0, 0.0, 0.0};  // perturbation_axes = Vector3::x_axis()
-    double rot[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    for (int it = 0; it < 100000; ++it) {
-        // axis = sum_c rot.col(c) x m.col(c), denom = sum_c rot.col(c) . m.col(c)
-        double axis[3] = {0, 0, 0}, denom = 0.0;
-        for (int c = 0; c < 3; ++c) {
-            const double a0 = rot[0][c], a1 = rot[1][c], a2 = rot[2][c], b0 = M[0][c], b1 = M[1][c], b2 = M[2][c];
-            const double cr[3] = {a1 * b2 - a2 * b1, a2 * b0 - a0 * b2, a0 * b1 - a1 * b0};
-            const double dt = a0 * b0 + a1 * b1 + a2 * b2;
-            if (c == 0) { axis[0] = cr[0]; axis[1] = cr[1]; axis[2] = cr[2]; denom = dt; }
-            else { axis[0] += cr[0]; axis[1] += cr[1]; axis[2] += cr[2]; denom += dt; }
-        }
-        const double dv = std::fabs(denom) + eps;
-        double aa[3] = {axis[0] / dv, axis[1] / dv, axis[2] / dv};
-        // Unit::try_new_and_get(axisangle, eps)
-        const double sq = aa[0] * aa[0] + aa[1] * aa[1] + aa[2] * aa[2];
-        if (sq > eps * eps) {
-            const double nrm = std::sqrt(sq);
-            const double u[3] = {aa[0] / nrm, aa[1] / nrm, aa[2] / nrm};
-            double Rd[3][3];
-            rot_from_axis_angle(u, nrm, Rd);
-            mat3_mul(Rd, rot, rot);
-        } else {
-            // stuck at a stationary point of ||m - rot||: a maximum, unless a small rotation makes it worse
-            double pert[3][3];
-            std::memcpy(pert, rot, sizeof pert);
-            const double n0 = diff_norm_squared(M, rot);
-            double n1;
-            for (;;) {
-                double Rp[3][3];
-                rot_from_axis_angle(axes, eps_disturbance, Rp);
-                mat3_mul(pert, Rp, pert);
-                n1 = diff_norm_squared(M, pert);
-                if (!(std::fabs(n0 - n1) <= eps)) break;  // abs_diff_ne!(.., epsilon = f64::EPSILON): true for NaN too
-            }
-            if (n0 < n1) break;  // a minimum: done
-            const double t = axes[0];  // perturbation_axes.yzx()
-            axes[0] = axes[1]; axes[1] = axes[2]; axes[2] = t;
-            std::memcpy(rot, pert, sizeof pert);
-        }
-    }
-    quat_from_rotation(rot, w, i, j, k);
-}
-
-// 4x4 column-major -> pose7 as the C path of the reference does it (optik-cpp/src/lib.rs:137-144).
-void pose7_from_mat16_iterative(const double *m, double *p) {
-    double M[3][3];
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) M[r][c] = m[c * 4 + r];
-    p[0] = m[12]; p[1] = m[13]; p[2] = m[14];
-    quat_from_matrix_iterative(M, p[6], p[3], p[4], p[5]);
-}
-
-// pose7 -> 4x4 column-major (Isometry3::to_matrix, optik-cpp/src/lib.rs:115).
-void mat16_from_pose7(const double *p, double *m) {
-    const double i = p[3], j = p[4], k = p[5], w = p[6];
-    const double ww = w * w, ii = i * i, jj = j * j, kk = k * k;
-    const double ij = i * j * 2.0, wk = w * k * 2.0, wj = w * j * 2.0, ik = i * k * 2.0, jk = j * k * 2.0,
-                 wi = w * i * 2.0;
-    const double R[3][3] = {{ww + ii - jj - kk, ij - wk, wj + ik},
-                            {wk + ij, ww - ii + jj - kk, jk - wi},
-                            {ik - wj, wi + jk, ww - ii - jj + kk}};
-    for (int c = 0; c < 3; ++c) {
-        for (int r = 0; r < 3; ++r) m[c * 4 + r] = R[r][c];
-        m[c * 4 + 3] = 0.0;
-    }
-    m[12] = p[0]; m[13] = p[1]; m[14] = p[2]; m[15] = 1.0;
-}
 
 int fk_on_device(const optik_robot *r, const double *x, const double *ee16, double *pose7, double *jac) {
     DeviceCtx *c = device_ctx(r);
@@ -395,10 +96,10 @@ int fk_on_device(const optik_robot *r, const double *x, const double *ee16, doub
     if (ee16) pose7_from_mat16(ee16, ee7);
     std::lock_guard<std::mutex> lock(r->mu);
     optik::DeviceScope dev_scope(c->device);
-    if (!dev_scope.ok()) return set_err(-1, "hipSetDevice failed");
+    if (!dev_scope.ok()) return set_err(-1, kSetDeviceMsg);
     // one configuration: the kernel reads q from and writes the pose / Jacobian to pinned host
     // memory (one launch and one wait instead of three copies around them: 43 -> ~20 us per call)
-    double *p_q = c->h_scratch, *p_pose = p_q + r->n, *p_jac = p_pose + 7;
+    double *p_q = c->h_scratch.get(), *p_pose = p_q + r->n, *p_jac = p_pose + 7;
     std::memcpy(p_q, x, sizeof(double) * (size_t)r->n);
     if (optik_hip_fk_batch(h, ee16 ? ee7 : nullptr, p_q, 1, p_pose, jac ? p_jac : nullptr, nullptr))
         return set_err(-1, optik_hip_last_error());
@@ -415,7 +116,400 @@ double *malloc_copy(const double *src, size_t count) {
     return p;
 }
 
+// targets16 [T][16] (row-major or column-major 4x4) -> [T][7] poses, the iterative or the closed-form conversion
+std::vector<double> targets_pose7(int32_t T, const double *targets16, bool row_major, bool iterative) {
+    std::vector<double> tgt7((size_t)T * 7);
+    parallel_ranges((size_t)T, [&](size_t t0, size_t t1) {
+        for (size_t t = t0; t < t1; ++t) {
+            const double *m = targets16 + t * 16;
+            double cm[16];
+            if (row_major) {
+                for (int a = 0; a < 4; ++a)
+                    for (int b = 0; b < 4; ++b) cm[b * 4 + a] = m[a * 4 + b];
+                m = cm;
+            }
+            if (iterative) pose7_from_mat16_iterative(m, &tgt7[t * 7]);
+            else pose7_from_mat16(m, &tgt7[t * 7]);
+        }
+    });
+    return tgt7;
+}
+
+// The host-side checks of a batch of targets (optik_robot_ik_batch_poses, optik_robot_ik_solutions,
+// optik_robot_ik_path): with OPTIK_BATCH_VALIDATE_POSES every target's isometry test (-3), then every seed against the
+// joint limits (-2).  S: the number of seeds, T by default.
+int check_batch_inputs(const optik_robot *r, int32_t T, const double *targets16, uint32_t flags, const double *x0,
+                                    int32_t S = -1) {
+    const int n = r->n;
+    const bool row_major = (flags & OPTIK_BATCH_ROW_MAJOR) != 0;
+    if (flags & OPTIK_BATCH_VALIDATE_POSES) {
+        // nalgebra try_convert::<Matrix4, Isometry3> (optik-py/src/lib.rs:8-15): bottom row exactly
+        // (0, 0, 0, 1), R'R = I within 100 eps per entry, det R > 0.  Neither test depends on
+        // whether the 3x3 block is read by rows or by columns up to the bottom-row position.
+        const double eps = 100.0 * 2.220446049250313e-16;
+        std::atomic<bool> all_ok{true};
+        parallel_ranges((size_t)T, [&](size_t t0, size_t t1) {
+        for (size_t t = t0; t < t1; ++t) {
+            const double *m = targets16 + t * 16;
+            auto M = [&](int a, int b) { return row_major ? m[a * 4 + b] : m[b * 4 + a]; };
+            bool ok = M(3, 0) == 0.0 && M(3, 1) == 0.0 && M(3, 2) == 0.0 && M(3, 3) == 1.0;
+            for (int a = 0; a < 3 && ok; ++a)
+                for (int b = 0; b < 3 && ok; ++b) {
+                    const double d = M(0, a) * M(0, b) + M(1, a) * M(1, b) + M(2, a) * M(2, b) - (a == b ? 1.0 : 0.0);
+                    ok = std::fabs(d) <= eps;  // false for NaN
+                }
+            if (ok) {
+                const double det = M(0, 0) * (M(1, 1) * M(2, 2) - M(1, 2) * M(2, 1))
+                                   - M(0, 1) * (M(1, 0) * M(2, 2) - M(1, 2) * M(2, 0))
+                                   + M(0, 2) * (M(1, 0) * M(2, 1) - M(1, 1) * M(2, 0));
+                ok = det > 0.0;
+            }
+            if (!ok) { all_ok = false; return; }
+        }
+        });
+        if (!all_ok) return set_err(-3, "invalid target transform specified");
+    }
+    if (S < 0) S = T;
+    for (int t = 0; t < S; ++t)
+        for (int i = 0; i < n; ++i)
+            if (x0[(size_t)t * n + i] < r->lb[i] || x0[(size_t)t * n + i] > r->ub[i])
+                return set_err(-2, "seed joint position outside of joint limits");
+    return 0;
+}
+
+// fn(ctx, t0, t1, err) -> rc for one contiguous part [t0, t1) of the T targets per device of the robot, each part
+// on its own host thread; last_parts is set.  0, or -1 with the first failing part's message.
+template <class Fn>
+int run_device_parts(const optik_robot *r, int32_t T, Fn fn) {
+    size_t G = device_count(r);
+    if (G > (size_t)T) G = (size_t)T;
+    struct Part { DeviceCtx *ctx; int32_t t0, t1; int rc; std::string err; };
+    std::vector<Part> parts;
+    for (size_t g = 0; g < G; ++g) {
+        Part p{device_ctx(r, g), (int32_t)((int64_t)T * (int64_t)g / (int64_t)G),
+               (int32_t)((int64_t)T * (int64_t)(g + 1) / (int64_t)G), 0, {}};
+        if (!p.ctx) return -1;
+        parts.push_back(p);
+    }
+    r->last_parts.store((int32_t)parts.size());
+    return run_parts(parts, [&](Part &p) { p.rc = fn(p.ctx, p.t0, p.t1, p.err); });
+}
+
+// optik_robot_ik_batch_ex for the targets of one GPU: rounds of `round` restart indices per
+// target (sizes: see the loop), each round ONE launch of optik_hip_ik_batch (which picks the solver by
+// launch size); targets already solved (Speed) drop out of later rounds; max_time is enforced inside a
+// launch and between rounds.
+int ik_batch_on_device(const optik_robot *r, DeviceCtx *c, const CSolverConfig *config, int32_t T,
+                       const double *targets16, bool row_major, bool iterative, const double *x0, const double *ee7,
+                       std::chrono::steady_clock::time_point start, double *x_out, double *f_out,
+                       int32_t *found_out, std::string &err) {
+    const int n = r->n;
+    auto elapsed = [&]() {
+        return std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+    };
+    const uint64_t max_restarts = config->max_restarts > 0 ? config->max_restarts : UINT64_MAX;
+    const bool quality = config->solution_mode != OPTIK_MODE_SPEED;  // (Manipulability, Condition: as Quality)
+    // (the collision filter: Speed takes Quality's route in each round; a target's first round with a free success
+    // holds its lowest-index one, so the target still leaves the batch then.  Read before batch_mu: the setters take
+    // the robot's lock first)
+    const bool filtered = r->collision_active();
+    // work items (target x restart index) per round: ~4 M -- 288 MB of per-restart keys, points and residuals
+    const uint64_t round_items = (uint64_t)4 << 20;
+    BatchGuard guard(c);
+    if (!guard.ok()) { err = kSetDeviceMsg; return -1; }
+
+    std::vector<double> tgt7 = targets_pose7(T, targets16, row_major, iterative), best_key((size_t)T, 0.0);
+    std::vector<uint64_t> best_idx((size_t)T, UINT64_MAX);
+    std::vector<int> live((size_t)T);
+    for (int t = 0; t < T; ++t) live[t] = t;
+    for (int t = 0; t < T; ++t) if (found_out) found_out[t] = 0;
+
+    // one device block and its pinned mirror, kept with the context across calls
+    const size_t n_in = (size_t)(7 + n) * (size_t)T, n_out = (size_t)(n + 3) * (size_t)T;
+    if (!reserve_batch(c, n_in + n_out)) { err = kBatchAllocMsg; return -1; }
+    // Speed: the first round is latency-sized -- 128 indices: with a third of the restarts succeeding
+    // it leaves no reachable target unsolved, and the abandoned indices of a round still cost the
+    // solve kernel's groups a queue fetch each (measured per first-round size 16 / 32 / 64 / 128 / 256:
+    // 1 024 targets 3.7 / 2.0 / 2.1 / 2.2 / 2.2 ms, 16 384 targets 9.8 / 9.5 / 8.7 / 8.3 / 9.4 ms; 32 768
+    // targets 15.9 ms at 64, 13.5 at 128, 16.8 at 256); what is
+    // still unsolved after it is hard or unreachable and throughput-bound, so every later round covers
+    // four times as many indices (ten unreachable targets x 100 000 restarts are 8 rounds instead of 390)
+    const uint64_t first_round = 128;
+    uint64_t speed_round = first_round;
+    for (uint64_t begin = 0; begin < max_restarts && !live.empty();) {
+        double deadline = 0.0;
+        if (config->max_time > 0.0) {
+            deadline = config->max_time - elapsed();
+            if (deadline <= 0.0) break;  // lib.rs:393
+        }
+        const size_t L = live.size();
+        uint64_t round = quality ? 256 : speed_round;
+        // (a round's items are capped -- down to 64 indices per target, which still leave no reachable target
+        // unsolved; batches of more than 65 536 targets down to 8: nearly all of a round's higher indices are
+        // abandoned unissued -- a third to a half of the restarts succeed -- and skipping an item still costs the
+        // refilling wave a queue fetch; the handful of targets a short round leaves unsolved go through the next)
+        const uint64_t min_round = L <= 65536 ? (first_round < 64 ? first_round : 64u) : 8u;
+        const uint64_t cap_items = L <= 65536 ? round_items : 2 * round_items;
+        while (round > min_round && round * (uint64_t)L > cap_items) round >>= 1;
+        if (!quality && speed_round < ((uint64_t)1 << 40)) speed_round *= 4;
+        // Quality runs every restart of every target to the end: nothing to gain from short rounds -- as many
+        // indices per round as ~4 M items allow
+        if (quality)
+            while (round * 2 * (uint64_t)L <= round_items && round < max_restarts - begin) round <<= 1;
+        const uint64_t end = (max_restarts - begin > round) ? begin + round : max_restarts;
+        double *h_t = c->h_batch.get(), *h_x0 = h_t + 7 * L, *h_out = h_x0 + (size_t)n * L;
+        double *d_t = c->d_batch.get(), *d_x0 = d_t + 7 * L, *d_wx = d_x0 + (size_t)n * L, *d_wf = d_wx + (size_t)n * L,
+               *d_wk = d_wf + L;
+        uint64_t *d_wi = reinterpret_cast<uint64_t *>(d_wk + L);
+        parallel_ranges(L, [&](size_t k0, size_t k1) {
+            for (size_t k = k0; k < k1; ++k) {
+                std::memcpy(&h_t[k * 7], &tgt7[(size_t)live[k] * 7], sizeof(double) * 7);
+                std::memcpy(&h_x0[k * n], &x0[(size_t)live[k] * n], sizeof(double) * (size_t)n);
+            }
+        });
+        if (hipMemcpyAsync(d_t, h_t, sizeof(double) * (size_t)(7 + n) * L, hipMemcpyHostToDevice, nullptr) != hipSuccess) {
+            err = "upload failed";
+            return -1;
+        }
+        optik_hip_ik_outputs o;
+        std::memset(&o, 0, sizeof o);
+        o.d_win_x = d_wx; o.d_win_f = d_wf; o.d_win_idx = d_wi; o.d_win_key = d_wk;
+        // One launch per round.  The first rounds of a Speed batch are latency-bound -- early exit abandons most of
+        // their restarts, what is left is each target's few first restarts run to the end: restart-major hand-out
+        // keeps only a few restarts per target in flight (optik_hip_ik_batch then stays on the quad solver's shorter
+        // trip).  Everything else -- a Quality batch, the later rounds of a Speed batch (whatever 256 restarts did
+        // not solve runs nearly all of its restarts) -- is throughput-bound: target-major, the lane-per-restart form
+        // from one full load of the chip on.  (Rounds 1-4 ran those rounds, and the first round of batches of 40 960
+        // targets or more, on a streaming engine: retired in round 5, the single launch is 15 - 28 % faster at every
+        // size where the engine was used -- profiles/r5a_engine_retire_probe.txt.)
+        const uint32_t mode_flags =
+            (quality || filtered) ? 0u : (OPTIK_HIP_IK_EARLY_EXIT | (r->parallelism != 1 ? OPTIK_HIP_IK_FIND_ANY : 0u));
+        const int rck = optik_hip_ik_batch(c->chain, config, d_t, d_x0, (int32_t)L, ee7, begin, end,
+                                           mode_flags | ((!quality && !filtered && begin < 256) ? OPTIK_HIP_IK_RESTART_MAJOR : 0u),
+                                           deadline, &o, nullptr);
+        if (rck) { err = optik_hip_last_error(); return -1; }
+        if (hipMemcpyAsync(h_out, d_wx, sizeof(double) * (size_t)(n + 3) * L, hipMemcpyDeviceToHost, nullptr) != hipSuccess
+            || hipStreamSynchronize(nullptr) != hipSuccess) {
+            err = "download failed";
+            return -1;
+        }
+        const double *wx = h_out, *wf = wx + (size_t)n * L, *wk = wf + L;
+        const uint64_t *wi = reinterpret_cast<const uint64_t *>(wk + L);
+        // every target appears once in `live`, so ranges of k touch disjoint targets
+        std::vector<uint8_t> keep(L);
+        parallel_ranges(L, [&](size_t k0, size_t k1) {
+            for (size_t k = k0; k < k1; ++k) {
+                const int t = live[k];
+                keep[k] = 1;
+                if (wi[k] == UINT64_MAX) continue;
+                const bool better = best_idx[t] == UINT64_MAX || wk[k] < best_key[t]
+                                    || (wk[k] == best_key[t] && wi[k] < best_idx[t]);
+                if (better) {
+                    best_idx[t] = wi[k]; best_key[t] = wk[k];
+                    if (x_out) std::memcpy(&x_out[(size_t)t * n], &wx[k * n], sizeof(double) * (size_t)n);
+                    if (f_out) f_out[t] = wf[k];
+                    if (found_out) found_out[t] = 1;
+                }
+                if (!quality) keep[k] = 0;  // Speed: the first solution ends this target
+            }
+        });
+        std::vector<int> still;
+        for (size_t k = 0; k < L; ++k)
+            if (keep[k]) still.push_back(live[k]);
+        live.swap(still);
+        begin = end;
+    }
+    return 0;
+}
+
+// optik_robot_ik_solutions for the targets of one GPU: chunks of whole targets, each ONE launch of
+// optik_hip_ik_solutions over every restart index [0, R) (about 4 M work items a launch at most, as the rounds of
+// ik_batch_on_device).  A chunk that starts after the max_time budget is spent is not run: its targets keep count 0.
+int ik_solutions_on_device(const optik_robot *r, DeviceCtx *c, const CSolverConfig *config, int32_t T,
+                           const double *targets16, bool row_major, bool iterative, const double *x0,
+                           const double *ee7, std::chrono::steady_clock::time_point start, int32_t K, double min_dist,
+                           int32_t *count_out, double *x_out, double *f_out, uint64_t *idx_out, std::string &err) {
+    const int n = r->n;
+    const uint64_t R = config->max_restarts;
+    const uint64_t round_items = (uint64_t)4 << 20;
+    const size_t chunk = (size_t)std::min<uint64_t>((uint64_t)T, std::max<uint64_t>(1, round_items / R));
+    BatchGuard guard(c);
+    if (!guard.ok()) { err = kSetDeviceMsg; return -1; }
+    const std::vector<double> tgt7 = targets_pose7(T, targets16, row_major, iterative);
+
+    // the robot's batch block: in = targets [C][7] | x0 [C][n]; out = x [C][K][n] | f [C][K] | idx [C][K] | count [C]
+    const size_t KC = (size_t)K * chunk;
+    const size_t n_in = (size_t)(7 + n) * chunk, n_out = KC * (size_t)(n + 2) + chunk;
+    if (!reserve_batch(c, n_in + n_out)) { err = kBatchAllocMsg; return -1; }
+    for (size_t t0 = 0; t0 < (size_t)T; t0 += chunk) {
+        const size_t L = std::min(chunk, (size_t)T - t0), KL = (size_t)K * L;
+        double deadline = 0.0;
+        if (config->max_time > 0.0) {
+            deadline = config->max_time - std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+            if (deadline <= 0.0) break;  // (the targets left keep count 0)
+        }
+        double *h_t = c->h_batch.get(), *h_out = h_t + (size_t)(7 + n) * L;
+        double *d_t = c->d_batch.get(), *d_x0 = d_t + 7 * L, *d_x = d_x0 + (size_t)n * L, *d_f = d_x + KL * (size_t)n;
+        uint64_t *d_idx = reinterpret_cast<uint64_t *>(d_f + KL);
+        int32_t *d_count = reinterpret_cast<int32_t *>(d_idx + KL);
+        std::memcpy(h_t, &tgt7[t0 * 7], sizeof(double) * 7 * L);
+        std::memcpy(h_t + 7 * L, x0 + t0 * (size_t)n, sizeof(double) * (size_t)n * L);
+        if (hipMemcpyAsync(d_t, h_t, sizeof(double) * (size_t)(7 + n) * L, hipMemcpyHostToDevice, nullptr) != hipSuccess) {
+            err = "upload failed";
+            return -1;
+        }
+        optik_hip_ik_solutions_outputs o;
+        o.d_count = d_count; o.d_x = d_x; o.d_f = d_f; o.d_idx = d_idx; o.d_key = nullptr;
+        if (optik_hip_ik_solutions(c->chain, config, d_t, d_x0, (int32_t)L, ee7, 0, R, deadline, K, min_dist, &o,
+                                   nullptr)) {
+            err = optik_hip_last_error();
+            return -1;
+        }
+        const size_t out_doubles = KL * (size_t)(n + 2) + L;
+        if (hipMemcpyAsync(h_out, d_x, sizeof(double) * out_doubles, hipMemcpyDeviceToHost, nullptr) != hipSuccess
+            || hipStreamSynchronize(nullptr) != hipSuccess) {
+            err = "download failed";
+            return -1;
+        }
+        const double *hx = h_out, *hf = hx + KL * (size_t)n;
+        const uint64_t *hi = reinterpret_cast<const uint64_t *>(hf + KL);
+        const int32_t *hc = reinterpret_cast<const int32_t *>(hi + KL);
+        if (x_out) std::memcpy(x_out + t0 * (size_t)K * n, hx, sizeof(double) * KL * (size_t)n);
+        if (f_out) std::memcpy(f_out + t0 * (size_t)K, hf, sizeof(double) * KL);
+        if (idx_out) std::memcpy(idx_out + t0 * (size_t)K, hi, sizeof(uint64_t) * KL);
+        if (count_out) std::memcpy(count_out + t0, hc, sizeof(int32_t) * L);
+    }
+    return 0;
+}
+
+// optik_robot_ik_path for the paths of one GPU: chunks of whole paths, each ONE upload, ONE optik_hip_ik_path (every
+// waypoint of the chunk, stream-ordered) and ONE download.  A chunk's waypoint launch holds about 4 M (path, restart)
+// items at most, and its share of the robot's batch block about 2^24 doubles (one path at least).
+int ik_path_on_device(const optik_robot *r, DeviceCtx *c, const CSolverConfig *config, int32_t P,
+                                   int32_t L, const double *tgt7, const double *x0, const double *ee7, double max_step,
+                                   double *x_out, double *f_out, uint64_t *idx_out, double *step_out,
+                                   int32_t *found_out, std::string &err) {
+    const int n = r->n;
+    const uint64_t R = config->max_restarts;
+    const size_t per_path = (size_t)L * (size_t)(7 + n + 3) + (size_t)n;  // doubles of the block per path
+    const uint64_t round_items = (uint64_t)4 << 20;
+    size_t chunk = (size_t)std::min<uint64_t>((uint64_t)P, std::max<uint64_t>(1, round_items / R));
+    chunk = std::min(chunk, std::max<size_t>(1, ((size_t)1 << 24) / per_path));
+    // Speed without a step limit: restart-major hand-out, so that every path's restart 0 (its warm start) runs first
+    // (not under the collision filter: every restart runs to its end there, as in Quality)
+    const uint32_t flags = (config->solution_mode == OPTIK_MODE_SPEED && !(max_step < __builtin_huge_val())
+                            && !r->collision_active()) ? OPTIK_HIP_IK_RESTART_MAJOR : 0u;
+    const double deadline = config->max_time > 0.0 ? config->max_time : 0.0;
+    BatchGuard guard(c);
+    if (!guard.ok()) { err = kSetDeviceMsg; return -1; }
+
+    // the robot's batch block: in = targets [L][C][7] | x0 [C][n]; out = x [L][C][n] | f [L][C] | idx [L][C] |
+    // step [L][C]
+    const size_t need = per_path * chunk;
+    if (!reserve_batch(c, need)) { err = kBatchAllocMsg; return -1; }
+    for (size_t p0 = 0; p0 < (size_t)P; p0 += chunk) {
+        const size_t C = std::min(chunk, (size_t)P - p0), LC = (size_t)L * C;
+        double *h_t = c->h_batch.get(), *h_out = h_t + 7 * LC + (size_t)n * C;
+        double *d_t = c->d_batch.get(), *d_x0 = d_t + 7 * LC, *d_x = d_x0 + (size_t)n * C, *d_f = d_x + LC * (size_t)n;
+        uint64_t *d_idx = reinterpret_cast<uint64_t *>(d_f + LC);
+        double *d_step = reinterpret_cast<double *>(d_idx + LC);
+        // (paths p0.. of tgt7 [P][L][7] -> [L][C][7], waypoint-major)
+        for (size_t p = 0; p < C; ++p)
+            for (int32_t l = 0; l < L; ++l)
+                std::memcpy(h_t + ((size_t)l * C + p) * 7, tgt7 + ((p0 + p) * (size_t)L + (size_t)l) * 7,
+                            sizeof(double) * 7);
+        std::memcpy(h_t + 7 * LC, x0 + p0 * (size_t)n, sizeof(double) * (size_t)n * C);
+        if (hipMemcpyAsync(d_t, h_t, sizeof(double) * (7 * LC + (size_t)n * C), hipMemcpyHostToDevice, nullptr)
+            != hipSuccess) {
+            err = "upload failed";
+            return -1;
+        }
+        optik_hip_ik_path_outputs o;
+        std::memset(&o, 0, sizeof o);
+        o.d_x = d_x; o.d_f = d_f; o.d_idx = d_idx; o.d_step = d_step;
+        if (optik_hip_ik_path(c->chain, config, d_t, d_x0, (int32_t)C, L, ee7, 0, R, flags, deadline, max_step, &o,
+                              nullptr)) {
+            err = optik_hip_last_error();
+            return -1;
+        }
+        const size_t out_doubles = LC * (size_t)(n + 3);
+        if (hipMemcpyAsync(h_out, d_x, sizeof(double) * out_doubles, hipMemcpyDeviceToHost, nullptr) != hipSuccess
+            || hipStreamSynchronize(nullptr) != hipSuccess) {
+            err = "download failed";
+            return -1;
+        }
+        const double *hx = h_out, *hf = hx + LC * (size_t)n;
+        const uint64_t *hi = reinterpret_cast<const uint64_t *>(hf + LC);
+        const double *hs = reinterpret_cast<const double *>(hi + LC);
+        // ([L][C] -> path-major [P][L])
+        for (size_t p = 0; p < C; ++p)
+            for (int32_t l = 0; l < L; ++l) {
+                const size_t dv = (size_t)l * C + p, hv = (p0 + p) * (size_t)L + (size_t)l;
+                if (x_out) std::memcpy(x_out + hv * n, hx + dv * n, sizeof(double) * (size_t)n);
+                if (f_out) f_out[hv] = hf[dv];
+                if (idx_out) idx_out[hv] = hi[dv];
+                if (step_out) step_out[hv] = hs[dv];
+                if (found_out) found_out[hv] = hi[dv] != UINT64_MAX ? 1 : 0;
+            }
+    }
+    return 0;
+}
+
 }  // namespace
+
+namespace optik {
+namespace robot {
+
+DeviceCtx *device_ctx(const optik_robot *r, size_t k) {
+    std::lock_guard<std::mutex> lock(r->mu);
+    if (r->devs.empty()) r->devs.resize(device_count(r));
+    if (k >= r->devs.size()) { g_robot_err = "no such device context"; return nullptr; }
+    if (r->devs[k]) return r->devs[k].get();
+    int devid = 0;
+    if (r->device_ids.empty()) (void)hipGetDevice(&devid);
+    else devid = r->device_ids[k];
+    // (the caller's device is current again when this returns, also when the set-up fails)
+    optik::DeviceScope dev_scope(devid);
+    if (!dev_scope.ok()) {
+        g_robot_err = "hipSetDevice(" + std::to_string(devid) + ") failed";
+        return nullptr;
+    }
+    // (a context whose set-up fails is deleted on return, with its device still current)
+    std::unique_ptr<DeviceCtx> c(new DeviceCtx());
+    if (optik_hip_chain_create(r->origins.data(), r->axes.data(), r->types.data(), (int32_t)r->types.size(),
+                               r->lb.data(), r->ub.data(), r->n, &c->chain)) {
+        g_robot_err = std::string("GPU chain creation failed: ") + optik_hip_last_error();
+        return nullptr;
+    }
+    optik_hip_chain *h = c->chain;
+    if (c->d_scratch.reserve((size_t)(r->n + 7 + 6 * r->n)) != hipSuccess
+        || c->h_scratch.reserve((size_t)(r->n + 7 + 6 * r->n)) != hipSuccess) {
+        g_robot_err = "GPU scratch allocation failed";
+        return nullptr;
+    }
+    // (a model or world set before this chain existed)
+    if ((!r->coll_frames.empty()
+         && optik_hip_chain_set_collision_model(h, r->coll_frames.data(), r->coll_centers.data(), r->coll_radii.data(),
+                                                (int32_t)r->coll_frames.size(), r->coll_pairs.data(),
+                                                (int32_t)(r->coll_pairs.size() / 2), r->coll_margin))
+        || ((!r->world_spheres.empty() || !r->world_boxes.empty())
+            && optik_hip_chain_set_world(h, r->world_spheres.data(), (int32_t)(r->world_spheres.size() / 4),
+                                         r->world_boxes.data(), (int32_t)(r->world_boxes.size() / 10)))
+        || (!r->grid_values.empty()
+            && optik_hip_chain_set_world_grid(h, r->grid_origin, r->grid_voxel, r->grid_n[0], r->grid_n[1],
+                                              r->grid_n[2], r->grid_values.data()))
+        || (r->motion_h > 0.0 && optik_hip_chain_set_motion_resolution(h, r->motion_h))) {
+        g_robot_err = std::string("collision model, world or motion resolution upload failed: ") + optik_hip_last_error();
+        return nullptr;
+    }
+    (void)hipDeviceGetAttribute(&c->num_cus, hipDeviceAttributeMultiprocessorCount, devid);
+    c->device = devid;
+    r->devs[k] = std::move(c);
+    return r->devs[k].get();
+}
+
+}  // namespace robot
+}  // namespace optik
 
 extern "C" {
 
@@ -449,13 +543,9 @@ optik_robot *optik_robot_from_urdf_file(const char *path, const char *base_link,
 void optik_robot_free(optik_robot *r) {
     if (!r) return;
     for (auto &c : r->devs) {
-        if (!c->chain) continue;
+        if (!c) continue;
         optik::DeviceScope dev_scope(c->device);  // the caller's device is current again afterwards
-        optik_hip_chain_destroy(c->chain);
-        if (c->d_scratch) (void)hipFree(c->d_scratch);
-        if (c->h_scratch) (void)hipHostFree(c->h_scratch);
-        if (c->d_batch) (void)hipFree(c->d_batch);
-        if (c->h_batch) (void)hipHostFree(c->h_batch);
+        c.reset();                                // (the chain, then the context's blocks)
     }
     delete r;
 }
@@ -661,17 +751,9 @@ int optik_robot_ik_pose(const optik_robot *r, const CSolverConfig *config, const
         };
         if (begin_was_zero) r->last_parts.store(0);
         if ((int32_t)parts.size() > r->last_parts.load()) r->last_parts.store((int32_t)parts.size());
-        if (parts.size() == 1) {
-            run_part(parts[0]);
-        } else {
-            std::vector<std::thread> th;
-            for (size_t g = 1; g < parts.size(); ++g) th.emplace_back(run_part, std::ref(parts[g]));
-            run_part(parts[0]);
-            for (auto &t : th) t.join();
-        }
+        if (run_parts(parts, run_part)) return -1;
         bool found_round = false;
         for (const Part &p : parts) {
-            if (p.rc) return set_err(-1, p.err);
             if (p.widx == UINT64_MAX) continue;
             found_round = true;
             // lib.rs:397-413: Quality keeps the solution closest to the seed, Speed the first one
@@ -688,167 +770,6 @@ int optik_robot_ik_pose(const optik_robot *r, const CSolverConfig *config, const
     return 0;
 }
 
-namespace {
-
-// targets16 [T][16] (row-major or column-major 4x4) -> [T][7] poses, the iterative or the closed-form conversion
-extern "C++" std::vector<double> targets_pose7(int32_t T, const double *targets16, bool row_major, bool iterative) {
-    std::vector<double> tgt7((size_t)T * 7);
-    parallel_ranges((size_t)T, [&](size_t t0, size_t t1) {
-        for (size_t t = t0; t < t1; ++t) {
-            const double *m = targets16 + t * 16;
-            double cm[16];
-            if (row_major) {
-                for (int a = 0; a < 4; ++a)
-                    for (int b = 0; b < 4; ++b) cm[b * 4 + a] = m[a * 4 + b];
-                m = cm;
-            }
-            if (iterative) pose7_from_mat16_iterative(m, &tgt7[t * 7]);
-            else pose7_from_mat16(m, &tgt7[t * 7]);
-        }
-    });
-    return tgt7;
-}
-
-// optik_robot_ik_batch_ex for the targets of one GPU: rounds of `round` restart indices per
-// target (sizes: see the loop), each round ONE launch of optik_hip_ik_batch (which picks the solver by
-// launch size); targets already solved (Speed) drop out of later rounds; max_time is enforced inside a
-// launch and between rounds.
-int ik_batch_on_device(const optik_robot *r, DeviceCtx *c, const CSolverConfig *config, int32_t T,
-                       const double *targets16, bool row_major, bool iterative, const double *x0, const double *ee7,
-                       std::chrono::steady_clock::time_point start, double *x_out, double *f_out,
-                       int32_t *found_out, std::string &err) {
-    const int n = r->n;
-    auto elapsed = [&]() {
-        return std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
-    };
-    const uint64_t max_restarts = config->max_restarts > 0 ? config->max_restarts : UINT64_MAX;
-    const bool quality = config->solution_mode != OPTIK_MODE_SPEED;  // (Manipulability, Condition: as Quality)
-    // (the collision filter: Speed takes Quality's route in each round; a target's first round with a free success
-    // holds its lowest-index one, so the target still leaves the batch then.  Read before batch_mu: the setters take
-    // the robot's lock first)
-    const bool filtered = r->collision_active();
-    // work items (target x restart index) per round: ~4 M -- 288 MB of per-restart keys, points and residuals
-    const uint64_t round_items = (uint64_t)4 << 20;
-    std::lock_guard<std::mutex> lock(c->batch_mu);
-    optik::DeviceScope dev_scope(c->device);
-    if (!dev_scope.ok()) { err = "hipSetDevice failed"; return -1; }
-
-    std::vector<double> tgt7 = targets_pose7(T, targets16, row_major, iterative), best_key((size_t)T, 0.0);
-    std::vector<uint64_t> best_idx((size_t)T, UINT64_MAX);
-    std::vector<int> live((size_t)T);
-    for (int t = 0; t < T; ++t) live[t] = t;
-    for (int t = 0; t < T; ++t) if (found_out) found_out[t] = 0;
-
-    // one device block and its pinned mirror, kept with the context across calls
-    const size_t n_in = (size_t)(7 + n) * (size_t)T, n_out = (size_t)(n + 3) * (size_t)T;
-    if (n_in + n_out > c->batch_cap) {
-        if (c->d_batch) (void)hipFree(c->d_batch);
-        if (c->h_batch) (void)hipHostFree(c->h_batch);
-        c->d_batch = nullptr; c->h_batch = nullptr; c->batch_cap = 0;
-        if (hipMalloc(&c->d_batch, sizeof(double) * (n_in + n_out)) != hipSuccess
-            || hipHostMalloc(&c->h_batch, sizeof(double) * (n_in + n_out)) != hipSuccess) {
-            err = "batch workspace allocation failed";
-            return -1;
-        }
-        c->batch_cap = n_in + n_out;
-    }
-    // Speed: the first round is latency-sized -- 128 indices: with a third of the restarts succeeding
-    // it leaves no reachable target unsolved, and the abandoned indices of a round still cost the
-    // solve kernel's groups a queue fetch each (measured per first-round size 16 / 32 / 64 / 128 / 256:
-    // 1 024 targets 3.7 / 2.0 / 2.1 / 2.2 / 2.2 ms, 16 384 targets 9.8 / 9.5 / 8.7 / 8.3 / 9.4 ms; 32 768
-    // targets 15.9 ms at 64, 13.5 at 128, 16.8 at 256); what is
-    // still unsolved after it is hard or unreachable and throughput-bound, so every later round covers
-    // four times as many indices (ten unreachable targets x 100 000 restarts are 8 rounds instead of 390)
-    const uint64_t first_round = 128;
-    uint64_t speed_round = first_round;
-    for (uint64_t begin = 0; begin < max_restarts && !live.empty();) {
-        double deadline = 0.0;
-        if (config->max_time > 0.0) {
-            deadline = config->max_time - elapsed();
-            if (deadline <= 0.0) break;  // lib.rs:393
-        }
-        const size_t L = live.size();
-        uint64_t round = quality ? 256 : speed_round;
-        // (a round's items are capped -- down to 64 indices per target, which still leave no reachable target
-        // unsolved; batches of more than 65 536 targets down to 8: nearly all of a round's higher indices are
-        // abandoned unissued -- a third to a half of the restarts succeed -- and skipping an item still costs the
-        // refilling wave a queue fetch; the handful of targets a short round leaves unsolved go through the next)
-        const uint64_t min_round = L <= 65536 ? (first_round < 64 ? first_round : 64u) : 8u;
-        const uint64_t cap_items = L <= 65536 ? round_items : 2 * round_items;
-        while (round > min_round && round * (uint64_t)L > cap_items) round >>= 1;
-        if (!quality && speed_round < ((uint64_t)1 << 40)) speed_round *= 4;
-        // Quality runs every restart of every target to the end: nothing to gain from short rounds -- as many
-        // indices per round as ~4 M items allow
-        if (quality)
-            while (round * 2 * (uint64_t)L <= round_items && round < max_restarts - begin) round <<= 1;
-        const uint64_t end = (max_restarts - begin > round) ? begin + round : max_restarts;
-        double *h_t = c->h_batch, *h_x0 = h_t + 7 * L, *h_out = h_x0 + (size_t)n * L;
-        double *d_t = c->d_batch, *d_x0 = d_t + 7 * L, *d_wx = d_x0 + (size_t)n * L, *d_wf = d_wx + (size_t)n * L,
-               *d_wk = d_wf + L;
-        uint64_t *d_wi = reinterpret_cast<uint64_t *>(d_wk + L);
-        parallel_ranges(L, [&](size_t k0, size_t k1) {
-            for (size_t k = k0; k < k1; ++k) {
-                std::memcpy(&h_t[k * 7], &tgt7[(size_t)live[k] * 7], sizeof(double) * 7);
-                std::memcpy(&h_x0[k * n], &x0[(size_t)live[k] * n], sizeof(double) * (size_t)n);
-            }
-        });
-        if (hipMemcpyAsync(d_t, h_t, sizeof(double) * (size_t)(7 + n) * L, hipMemcpyHostToDevice, nullptr) != hipSuccess) {
-            err = "upload failed";
-            return -1;
-        }
-        optik_hip_ik_outputs o;
-        std::memset(&o, 0, sizeof o);
-        o.d_win_x = d_wx; o.d_win_f = d_wf; o.d_win_idx = d_wi; o.d_win_key = d_wk;
-        // One launch per round.  The first rounds of a Speed batch are latency-bound -- early exit abandons most of
-        // their restarts, what is left is each target's few first restarts run to the end: restart-major hand-out
-        // keeps only a few restarts per target in flight (optik_hip_ik_batch then stays on the quad solver's shorter
-        // trip).  Everything else -- a Quality batch, the later rounds of a Speed batch (whatever 256 restarts did
-        // not solve runs nearly all of its restarts) -- is throughput-bound: target-major, the lane-per-restart form
-        // from one full load of the chip on.  (Rounds 1-4 ran those rounds, and the first round of batches of 40 960
-        // targets or more, on a streaming engine: retired in round 5, the single launch is 15 - 28 % faster at every
-        // size where the engine was used -- profiles/r5a_engine_retire_probe.txt.)
-        const uint32_t mode_flags =
-            (quality || filtered) ? 0u : (OPTIK_HIP_IK_EARLY_EXIT | (r->parallelism != 1 ? OPTIK_HIP_IK_FIND_ANY : 0u));
-        const int rck = optik_hip_ik_batch(c->chain, config, d_t, d_x0, (int32_t)L, ee7, begin, end,
-                                           mode_flags | ((!quality && !filtered && begin < 256) ? OPTIK_HIP_IK_RESTART_MAJOR : 0u),
-                                           deadline, &o, nullptr);
-        if (rck) { err = optik_hip_last_error(); return -1; }
-        if (hipMemcpyAsync(h_out, d_wx, sizeof(double) * (size_t)(n + 3) * L, hipMemcpyDeviceToHost, nullptr) != hipSuccess
-            || hipStreamSynchronize(nullptr) != hipSuccess) {
-            err = "download failed";
-            return -1;
-        }
-        const double *wx = h_out, *wf = wx + (size_t)n * L, *wk = wf + L;
-        const uint64_t *wi = reinterpret_cast<const uint64_t *>(wk + L);
-        // every target appears once in `live`, so ranges of k touch disjoint targets
-        std::vector<uint8_t> keep(L);
-        parallel_ranges(L, [&](size_t k0, size_t k1) {
-            for (size_t k = k0; k < k1; ++k) {
-                const int t = live[k];
-                keep[k] = 1;
-                if (wi[k] == UINT64_MAX) continue;
-                const bool better = best_idx[t] == UINT64_MAX || wk[k] < best_key[t]
-                                    || (wk[k] == best_key[t] && wi[k] < best_idx[t]);
-                if (better) {
-                    best_idx[t] = wi[k]; best_key[t] = wk[k];
-                    if (x_out) std::memcpy(&x_out[(size_t)t * n], &wx[k * n], sizeof(double) * (size_t)n);
-                    if (f_out) f_out[t] = wf[k];
-                    if (found_out) found_out[t] = 1;
-                }
-                if (!quality) keep[k] = 0;  // Speed: the first solution ends this target
-            }
-        });
-        std::vector<int> still;
-        for (size_t k = 0; k < L; ++k)
-            if (keep[k]) still.push_back(live[k]);
-        live.swap(still);
-        begin = end;
-    }
-    return 0;
-}
-
-}  // namespace
-
 // Many independent ik() calls at once (the motion-planning workload of examples/example.rs:
 // a stream of targets, each with its own seed): every target gets the semantics of Robot::ik
 // with the same SolverConfig.  The targets are split into contiguous parts over the robot's
@@ -859,81 +780,6 @@ int optik_robot_ik_batch_ex(const optik_robot *r, const CSolverConfig *config, i
                             double *f_out, int32_t *found_out) {
     return optik_robot_ik_batch_poses(r, config, T, targets16, OPTIK_POSE_FROM_MATRIX, x0, ee16, x_out, f_out, found_out);
 }
-
-namespace {
-
-// The host-side checks of a batch of targets (optik_robot_ik_batch_poses, optik_robot_ik_solutions,
-// optik_robot_ik_path): with OPTIK_BATCH_VALIDATE_POSES every target's isometry test (-3), then every seed against the
-// joint limits (-2).  S: the number of seeds, T by default.
-extern "C++" int check_batch_inputs(const optik_robot *r, int32_t T, const double *targets16, uint32_t flags, const double *x0,
-                                    int32_t S = -1) {
-    const int n = r->n;
-    const bool row_major = (flags & OPTIK_BATCH_ROW_MAJOR) != 0;
-    if (flags & OPTIK_BATCH_VALIDATE_POSES) {
-        // nalgebra try_convert::<Matrix4, Isometry3> (optik-py/src/lib.rs:8-15): bottom row exactly
-        // (0, 0, 0, 1), R'R = I within 100 eps per entry, det R > 0.  Neither test depends on
-        // whether the 3x3 block is read by rows or by columns up to the bottom-row position.
-        const double eps = 100.0 * 2.220446049250313e-16;
-        std::atomic<bool> all_ok{true};
-        parallel_ranges((size_t)T, [&](size_t t0, size_t t1) {
-        for (size_t t = t0; t < t1; ++t) {
-            const double *m = targets16 + t * 16;
-            auto M = [&](int a, int b) { return row_major ? m[a * 4 + b] : m[b * 4 + a]; };
-            bool ok = M(3, 0) == 0.0 && M(3, 1) == 0.0 && M(3, 2) == 0.0 && M(3, 3) == 1.0;
-            for (int a = 0; a < 3 && ok; ++a)
-                for (int b = 0; b < 3 && ok; ++b) {
-                    const double d = M(0, a) * M(0, b) + M(1, a) * M(1, b) + M(2, a) * M(2, b) - (a == b ? 1.0 : 0.0);
-                    ok = std::fabs(d) <= eps;  // false for NaN
-                }
-            if (ok) {
-                const double det = M(0, 0) * (M(1, 1) * M(2, 2) - M(1, 2) * M(2, 1))
-                                   - M(0, 1) * (M(1, 0) * M(2, 2) - M(1, 2) * M(2, 0))
-                                   + M(0, 2) * (M(1, 0) * M(2, 1) - M(1, 1) * M(2, 0));
-                ok = det > 0.0;
-            }
-            if (!ok) { all_ok = false; return; }
-        }
-        });
-        if (!all_ok) return set_err(-3, "invalid target transform specified");
-    }
-    if (S < 0) S = T;
-    for (int t = 0; t < S; ++t)
-        for (int i = 0; i < n; ++i)
-            if (x0[(size_t)t * n + i] < r->lb[i] || x0[(size_t)t * n + i] > r->ub[i])
-                return set_err(-2, "seed joint position outside of joint limits");
-    return 0;
-}
-
-// fn(ctx, t0, t1, err) -> rc for one contiguous part [t0, t1) of the T targets per device of the robot, each part
-// on its own host thread; last_parts is set.  0, or -1 with the first failing part's message.
-extern "C++" template <class Fn>
-int run_device_parts(const optik_robot *r, int32_t T, Fn fn) {
-    size_t G = device_count(r);
-    if (G > (size_t)T) G = (size_t)T;
-    struct Part { DeviceCtx *ctx; int32_t t0, t1; int rc; std::string err; };
-    std::vector<Part> parts;
-    for (size_t g = 0; g < G; ++g) {
-        Part p{device_ctx(r, g), (int32_t)((int64_t)T * (int64_t)g / (int64_t)G),
-               (int32_t)((int64_t)T * (int64_t)(g + 1) / (int64_t)G), 0, {}};
-        if (!p.ctx) return -1;
-        parts.push_back(p);
-    }
-    r->last_parts.store((int32_t)parts.size());
-    auto run_part = [&](Part &p) { p.rc = fn(p.ctx, p.t0, p.t1, p.err); };
-    if (parts.size() == 1) {
-        run_part(parts[0]);
-    } else {
-        std::vector<std::thread> th;
-        for (size_t g = 1; g < parts.size(); ++g) th.emplace_back(run_part, std::ref(parts[g]));
-        run_part(parts[0]);
-        for (auto &t : th) t.join();
-    }
-    for (const Part &p : parts)
-        if (p.rc) return set_err(-1, p.err);
-    return 0;
-}
-
-}  // namespace
 
 int optik_robot_ik_batch_poses(const optik_robot *r, const CSolverConfig *config, int32_t T,
                                const double *targets16, uint32_t flags, const double *x0, const double *ee16,
@@ -953,81 +799,6 @@ int optik_robot_ik_batch_poses(const optik_robot *r, const CSolverConfig *config
                                   found_out ? found_out + t0 : nullptr, err);
     });
 }
-
-namespace {
-
-// optik_robot_ik_solutions for the targets of one GPU: chunks of whole targets, each ONE launch of
-// optik_hip_ik_solutions over every restart index [0, R) (about 4 M work items a launch at most, as the rounds of
-// ik_batch_on_device).  A chunk that starts after the max_time budget is spent is not run: its targets keep count 0.
-extern "C++" int ik_solutions_on_device(const optik_robot *r, DeviceCtx *c, const CSolverConfig *config, int32_t T,
-                           const double *targets16, bool row_major, bool iterative, const double *x0,
-                           const double *ee7, std::chrono::steady_clock::time_point start, int32_t K, double min_dist,
-                           int32_t *count_out, double *x_out, double *f_out, uint64_t *idx_out, std::string &err) {
-    const int n = r->n;
-    const uint64_t R = config->max_restarts;
-    const uint64_t round_items = (uint64_t)4 << 20;
-    const size_t chunk = (size_t)std::min<uint64_t>((uint64_t)T, std::max<uint64_t>(1, round_items / R));
-    std::lock_guard<std::mutex> lock(c->batch_mu);
-    optik::DeviceScope dev_scope(c->device);
-    if (!dev_scope.ok()) { err = "hipSetDevice failed"; return -1; }
-    const std::vector<double> tgt7 = targets_pose7(T, targets16, row_major, iterative);
-
-    // the robot's batch block: in = targets [C][7] | x0 [C][n]; out = x [C][K][n] | f [C][K] | idx [C][K] | count [C]
-    const size_t KC = (size_t)K * chunk;
-    const size_t n_in = (size_t)(7 + n) * chunk, n_out = KC * (size_t)(n + 2) + chunk;
-    if (n_in + n_out > c->batch_cap) {
-        if (c->d_batch) (void)hipFree(c->d_batch);
-        if (c->h_batch) (void)hipHostFree(c->h_batch);
-        c->d_batch = nullptr; c->h_batch = nullptr; c->batch_cap = 0;
-        if (hipMalloc(&c->d_batch, sizeof(double) * (n_in + n_out)) != hipSuccess
-            || hipHostMalloc(&c->h_batch, sizeof(double) * (n_in + n_out)) != hipSuccess) {
-            err = "batch workspace allocation failed";
-            return -1;
-        }
-        c->batch_cap = n_in + n_out;
-    }
-    for (size_t t0 = 0; t0 < (size_t)T; t0 += chunk) {
-        const size_t L = std::min(chunk, (size_t)T - t0), KL = (size_t)K * L;
-        double deadline = 0.0;
-        if (config->max_time > 0.0) {
-            deadline = config->max_time - std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
-            if (deadline <= 0.0) break;  // (the targets left keep count 0)
-        }
-        double *h_t = c->h_batch, *h_out = h_t + (size_t)(7 + n) * L;
-        double *d_t = c->d_batch, *d_x0 = d_t + 7 * L, *d_x = d_x0 + (size_t)n * L, *d_f = d_x + KL * (size_t)n;
-        uint64_t *d_idx = reinterpret_cast<uint64_t *>(d_f + KL);
-        int32_t *d_count = reinterpret_cast<int32_t *>(d_idx + KL);
-        std::memcpy(h_t, &tgt7[t0 * 7], sizeof(double) * 7 * L);
-        std::memcpy(h_t + 7 * L, x0 + t0 * (size_t)n, sizeof(double) * (size_t)n * L);
-        if (hipMemcpyAsync(d_t, h_t, sizeof(double) * (size_t)(7 + n) * L, hipMemcpyHostToDevice, nullptr) != hipSuccess) {
-            err = "upload failed";
-            return -1;
-        }
-        optik_hip_ik_solutions_outputs o;
-        o.d_count = d_count; o.d_x = d_x; o.d_f = d_f; o.d_idx = d_idx; o.d_key = nullptr;
-        if (optik_hip_ik_solutions(c->chain, config, d_t, d_x0, (int32_t)L, ee7, 0, R, deadline, K, min_dist, &o,
-                                   nullptr)) {
-            err = optik_hip_last_error();
-            return -1;
-        }
-        const size_t out_doubles = KL * (size_t)(n + 2) + L;
-        if (hipMemcpyAsync(h_out, d_x, sizeof(double) * out_doubles, hipMemcpyDeviceToHost, nullptr) != hipSuccess
-            || hipStreamSynchronize(nullptr) != hipSuccess) {
-            err = "download failed";
-            return -1;
-        }
-        const double *hx = h_out, *hf = hx + KL * (size_t)n;
-        const uint64_t *hi = reinterpret_cast<const uint64_t *>(hf + KL);
-        const int32_t *hc = reinterpret_cast<const int32_t *>(hi + KL);
-        if (x_out) std::memcpy(x_out + t0 * (size_t)K * n, hx, sizeof(double) * KL * (size_t)n);
-        if (f_out) std::memcpy(f_out + t0 * (size_t)K, hf, sizeof(double) * KL);
-        if (idx_out) std::memcpy(idx_out + t0 * (size_t)K, hi, sizeof(uint64_t) * KL);
-        if (count_out) std::memcpy(count_out + t0, hc, sizeof(int32_t) * L);
-    }
-    return 0;
-}
-
-}  // namespace
 
 int optik_robot_ik_solutions(const optik_robot *r, const CSolverConfig *config, int32_t T, const double *targets16,
                              uint32_t flags, const double *x0, const double *ee16, int32_t K, double min_dist,
@@ -1060,94 +831,6 @@ int optik_robot_ik_solutions(const optik_robot *r, const CSolverConfig *config, 
                                       idx_out ? idx_out + (size_t)t0 * K : nullptr, err);
     });
 }
-
-namespace {
-
-// optik_robot_ik_path for the paths of one GPU: chunks of whole paths, each ONE upload, ONE optik_hip_ik_path (every
-// waypoint of the chunk, stream-ordered) and ONE download.  A chunk's waypoint launch holds about 4 M (path, restart)
-// items at most, and its share of the robot's batch block about 2^24 doubles (one path at least).
-extern "C++" int ik_path_on_device(const optik_robot *r, DeviceCtx *c, const CSolverConfig *config, int32_t P,
-                                   int32_t L, const double *tgt7, const double *x0, const double *ee7, double max_step,
-                                   double *x_out, double *f_out, uint64_t *idx_out, double *step_out,
-                                   int32_t *found_out, std::string &err) {
-    const int n = r->n;
-    const uint64_t R = config->max_restarts;
-    const size_t per_path = (size_t)L * (size_t)(7 + n + 3) + (size_t)n;  // doubles of the block per path
-    const uint64_t round_items = (uint64_t)4 << 20;
-    size_t chunk = (size_t)std::min<uint64_t>((uint64_t)P, std::max<uint64_t>(1, round_items / R));
-    chunk = std::min(chunk, std::max<size_t>(1, ((size_t)1 << 24) / per_path));
-    // Speed without a step limit: restart-major hand-out, so that every path's restart 0 (its warm start) runs first
-    // (not under the collision filter: every restart runs to its end there, as in Quality)
-    const uint32_t flags = (config->solution_mode == OPTIK_MODE_SPEED && !(max_step < __builtin_huge_val())
-                            && !r->collision_active()) ? OPTIK_HIP_IK_RESTART_MAJOR : 0u;
-    const double deadline = config->max_time > 0.0 ? config->max_time : 0.0;
-    std::lock_guard<std::mutex> lock(c->batch_mu);
-    optik::DeviceScope dev_scope(c->device);
-    if (!dev_scope.ok()) { err = "hipSetDevice failed"; return -1; }
-
-    // the robot's batch block: in = targets [L][C][7] | x0 [C][n]; out = x [L][C][n] | f [L][C] | idx [L][C] |
-    // step [L][C]
-    const size_t need = per_path * chunk;
-    if (need > c->batch_cap) {
-        if (c->d_batch) (void)hipFree(c->d_batch);
-        if (c->h_batch) (void)hipHostFree(c->h_batch);
-        c->d_batch = nullptr; c->h_batch = nullptr; c->batch_cap = 0;
-        if (hipMalloc(&c->d_batch, sizeof(double) * need) != hipSuccess
-            || hipHostMalloc(&c->h_batch, sizeof(double) * need) != hipSuccess) {
-            err = "batch workspace allocation failed";
-            return -1;
-        }
-        c->batch_cap = need;
-    }
-    for (size_t p0 = 0; p0 < (size_t)P; p0 += chunk) {
-        const size_t C = std::min(chunk, (size_t)P - p0), LC = (size_t)L * C;
-        double *h_t = c->h_batch, *h_out = h_t + 7 * LC + (size_t)n * C;
-        double *d_t = c->d_batch, *d_x0 = d_t + 7 * LC, *d_x = d_x0 + (size_t)n * C, *d_f = d_x + LC * (size_t)n;
-        uint64_t *d_idx = reinterpret_cast<uint64_t *>(d_f + LC);
-        double *d_step = reinterpret_cast<double *>(d_idx + LC);
-        // (paths p0.. of tgt7 [P][L][7] -> [L][C][7], waypoint-major)
-        for (size_t p = 0; p < C; ++p)
-            for (int32_t l = 0; l < L; ++l)
-                std::memcpy(h_t + ((size_t)l * C + p) * 7, tgt7 + ((p0 + p) * (size_t)L + (size_t)l) * 7,
-                            sizeof(double) * 7);
-        std::memcpy(h_t + 7 * LC, x0 + p0 * (size_t)n, sizeof(double) * (size_t)n * C);
-        if (hipMemcpyAsync(d_t, h_t, sizeof(double) * (7 * LC + (size_t)n * C), hipMemcpyHostToDevice, nullptr)
-            != hipSuccess) {
-            err = "upload failed";
-            return -1;
-        }
-        optik_hip_ik_path_outputs o;
-        std::memset(&o, 0, sizeof o);
-        o.d_x = d_x; o.d_f = d_f; o.d_idx = d_idx; o.d_step = d_step;
-        if (optik_hip_ik_path(c->chain, config, d_t, d_x0, (int32_t)C, L, ee7, 0, R, flags, deadline, max_step, &o,
-                              nullptr)) {
-            err = optik_hip_last_error();
-            return -1;
-        }
-        const size_t out_doubles = LC * (size_t)(n + 3);
-        if (hipMemcpyAsync(h_out, d_x, sizeof(double) * out_doubles, hipMemcpyDeviceToHost, nullptr) != hipSuccess
-            || hipStreamSynchronize(nullptr) != hipSuccess) {
-            err = "download failed";
-            return -1;
-        }
-        const double *hx = h_out, *hf = hx + LC * (size_t)n;
-        const uint64_t *hi = reinterpret_cast<const uint64_t *>(hf + LC);
-        const double *hs = reinterpret_cast<const double *>(hi + LC);
-        // ([L][C] -> path-major [P][L])
-        for (size_t p = 0; p < C; ++p)
-            for (int32_t l = 0; l < L; ++l) {
-                const size_t dv = (size_t)l * C + p, hv = (p0 + p) * (size_t)L + (size_t)l;
-                if (x_out) std::memcpy(x_out + hv * n, hx + dv * n, sizeof(double) * (size_t)n);
-                if (f_out) f_out[hv] = hf[dv];
-                if (idx_out) idx_out[hv] = hi[dv];
-                if (step_out) step_out[hv] = hs[dv];
-                if (found_out) found_out[hv] = hi[dv] != UINT64_MAX ? 1 : 0;
-            }
-    }
-    return 0;
-}
-
-}  // namespace
 
 int optik_robot_ik_path(const optik_robot *r, const CSolverConfig *config, int32_t P, int32_t L,
                         const double *targets16, uint32_t flags, const double *x0, const double *ee16,
@@ -1201,473 +884,6 @@ int optik_robot_diff_ik_ex(const optik_robot *r, const double *x0, const double 
     if (optik::lp::diff_ik_lp<8>(n, p7 + 3, jac, V_WE, v_max, &alpha, v)) return 1;
     if (alpha_out) *alpha_out = alpha;
     if (v_out) std::memcpy(v_out, v, sizeof(double) * (size_t)n);
-    return 0;
-}
-
-// B diff_ik calls in one launch per chunk of rows (optik_hip_diff_ik_batch: the same FK, Jacobian and LP code as
-// the call above, on the device).  Rows are staged to struct-of-arrays through the robot's pinned batch block.
-int optik_robot_diff_ik_batch(const optik_robot *r, int64_t B, const double *x0, const double *V_WE,
-                              const double *v_max, const double *ee16, double *alpha_out, double *v_out,
-                              int32_t *status_out) {
-    if (!r || !x0 || !V_WE || !v_max) return set_err(-1, "null argument");
-    if (B < 0) return set_err(-1, "bad argument");
-    const int n = r->n;
-    if (n > 8) return set_err(-1, kDiffIkMaxNMsg);
-    DeviceCtx *c = device_ctx(r);
-    if (!c) return -1;
-    // (B = 0: the kernel layer's refusals of the chain alone -- prismatic joints -- before anything is staged)
-    if (optik_hip_diff_ik_batch(c->chain, nullptr, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr,
-                                nullptr))
-        return set_err(-1, optik_hip_last_error());
-    if (B == 0) return 0;
-    double ee7[7];
-    if (ee16) pose7_from_mat16(ee16, ee7);
-    std::lock_guard<std::mutex> lock(c->batch_mu);
-    optik::DeviceScope dev_scope(c->device);
-    if (!dev_scope.ok()) return set_err(-1, "hipSetDevice failed");
-    // rows per launch: bounds the block (~66 MB for 8 joints) whatever B is
-    const int64_t chunk = B < ((int64_t)1 << 18) ? B : ((int64_t)1 << 18);
-    // per row: q n | V 6 | v_max n | alpha 1 | v n doubles, then the int32 status words (half a double each)
-    const size_t need = (size_t)(3 * n + 7) * (size_t)chunk + ((size_t)chunk + 1) / 2;
-    if (need > c->batch_cap) {
-        if (c->d_batch) (void)hipFree(c->d_batch);
-        if (c->h_batch) (void)hipHostFree(c->h_batch);
-        c->d_batch = nullptr; c->h_batch = nullptr; c->batch_cap = 0;
-        if (hipMalloc(&c->d_batch, sizeof(double) * need) != hipSuccess
-            || hipHostMalloc(&c->h_batch, sizeof(double) * need) != hipSuccess)
-            return set_err(-1, "batch workspace allocation failed");
-        c->batch_cap = need;
-    }
-    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        const size_t L = (size_t)(B - b0 < chunk ? B - b0 : chunk);
-        double *h_q = c->h_batch, *h_V = h_q + (size_t)n * L, *h_vm = h_V + 6 * L, *h_a = h_vm + (size_t)n * L,
-               *h_v = h_a + L;
-        const int32_t *h_st = reinterpret_cast<const int32_t *>(h_v + (size_t)n * L);
-        double *d_q = c->d_batch, *d_V = d_q + (size_t)n * L, *d_vm = d_V + 6 * L, *d_a = d_vm + (size_t)n * L,
-               *d_v = d_a + L;
-        int32_t *d_st = reinterpret_cast<int32_t *>(d_v + (size_t)n * L);
-        parallel_ranges(L, [&](size_t k0, size_t k1) {
-            for (size_t k = k0; k < k1; ++k) {
-                const size_t row = (size_t)b0 + k;
-                for (int i = 0; i < n; ++i) h_q[(size_t)i * L + k] = x0[row * n + i];
-                for (int i = 0; i < 6; ++i) h_V[(size_t)i * L + k] = V_WE[row * 6 + i];
-                for (int i = 0; i < n; ++i) h_vm[(size_t)i * L + k] = v_max[row * n + i];
-            }
-        });
-        if (hipMemcpyAsync(d_q, h_q, sizeof(double) * (size_t)(2 * n + 6) * L, hipMemcpyHostToDevice, nullptr)
-            != hipSuccess)
-            return set_err(-1, "upload failed");
-        if (optik_hip_diff_ik_batch(c->chain, ee16 ? ee7 : nullptr, d_q, d_V, (int64_t)L, d_vm, (int64_t)L,
-                                    (int64_t)L, d_a, d_v, d_st, nullptr))
-            return set_err(-1, optik_hip_last_error());
-        if (hipMemcpyAsync(h_a, d_a, sizeof(double) * (size_t)(n + 1) * L + sizeof(int32_t) * L,
-                           hipMemcpyDeviceToHost, nullptr) != hipSuccess
-            || hipStreamSynchronize(nullptr) != hipSuccess)
-            return set_err(-1, "download failed");
-        parallel_ranges(L, [&](size_t k0, size_t k1) {
-            for (size_t k = k0; k < k1; ++k) {
-                const size_t row = (size_t)b0 + k;
-                if (alpha_out) alpha_out[row] = h_a[k];
-                if (v_out) for (int i = 0; i < n; ++i) v_out[row * n + i] = h_v[(size_t)i * L + k];
-                if (status_out) status_out[row] = h_st[k];
-            }
-        });
-    }
-    return 0;
-}
-
-// The measures of solution modes 3 and 4 for B configurations (optik_hip_manip_batch), staged as
-// optik_robot_diff_ik_batch stages its rows.
-int optik_robot_manipulability_batch(const optik_robot *r, int64_t B, const double *x, const double *ee16,
-                                     double *w_out, double *c_out) {
-    if (!r || !x) return set_err(-1, "null argument");
-    if (B < 0) return set_err(-1, "bad argument");
-    const int n = r->n;
-    DeviceCtx *c = device_ctx(r);
-    if (!c) return -1;
-    // (B = 0: the kernel layer's refusals of the chain alone -- prismatic joints -- before anything is staged)
-    if (optik_hip_manip_batch(c->chain, nullptr, nullptr, 0, nullptr, nullptr, nullptr))
-        return set_err(-1, optik_hip_last_error());
-    if (B == 0 || (!w_out && !c_out)) return 0;
-    double ee7[7];
-    if (ee16) pose7_from_mat16(ee16, ee7);
-    std::lock_guard<std::mutex> lock(c->batch_mu);
-    optik::DeviceScope dev_scope(c->device);
-    if (!dev_scope.ok()) return set_err(-1, "hipSetDevice failed");
-    const int64_t chunk = B < ((int64_t)1 << 18) ? B : ((int64_t)1 << 18);
-    // per row: q n | w 1 | c 1 doubles
-    const size_t need = (size_t)(n + 2) * (size_t)chunk;
-    if (need > c->batch_cap) {
-        if (c->d_batch) (void)hipFree(c->d_batch);
-        if (c->h_batch) (void)hipHostFree(c->h_batch);
-        c->d_batch = nullptr; c->h_batch = nullptr; c->batch_cap = 0;
-        if (hipMalloc(&c->d_batch, sizeof(double) * need) != hipSuccess
-            || hipHostMalloc(&c->h_batch, sizeof(double) * need) != hipSuccess)
-            return set_err(-1, "batch workspace allocation failed");
-        c->batch_cap = need;
-    }
-    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        const size_t L = (size_t)(B - b0 < chunk ? B - b0 : chunk);
-        double *h_q = c->h_batch, *h_w = h_q + (size_t)n * L, *h_c = h_w + L;
-        double *d_q = c->d_batch, *d_w = d_q + (size_t)n * L, *d_c = d_w + L;
-        parallel_ranges(L, [&](size_t k0, size_t k1) {
-            for (size_t k = k0; k < k1; ++k) {
-                const size_t row = (size_t)b0 + k;
-                for (int i = 0; i < n; ++i) h_q[(size_t)i * L + k] = x[row * n + i];
-            }
-        });
-        if (hipMemcpyAsync(d_q, h_q, sizeof(double) * (size_t)n * L, hipMemcpyHostToDevice, nullptr) != hipSuccess)
-            return set_err(-1, "upload failed");
-        if (optik_hip_manip_batch(c->chain, ee16 ? ee7 : nullptr, d_q, (int64_t)L, w_out ? d_w : nullptr,
-                                  c_out ? d_c : nullptr, nullptr))
-            return set_err(-1, optik_hip_last_error());
-        if (hipMemcpyAsync(h_w, d_w, sizeof(double) * 2 * L, hipMemcpyDeviceToHost, nullptr) != hipSuccess
-            || hipStreamSynchronize(nullptr) != hipSuccess)
-            return set_err(-1, "download failed");
-        if (w_out) std::memcpy(w_out + b0, h_w, sizeof(double) * L);
-        if (c_out) std::memcpy(c_out + b0, h_c, sizeof(double) * L);
-    }
-    return 0;
-}
-
-// The collision model and world (include/optik.h): checked on the host before any device work, kept with the robot
-// and applied to every device chain it has (device_ctx applies them to the chains it creates later).
-int optik_robot_set_collision_model(optik_robot *r, const int32_t *frames, const double *centers3, const double *radii,
-                                    int32_t S, const int32_t *pairs2, int32_t P, double margin) {
-    if (!r) return set_err(-1, "null argument");
-    std::string err;
-    if (optik::coll::check_model(r->n, frames, centers3, radii, S, pairs2, P, margin, err)) return set_err(-1, err);
-    if (S > 0)
-        for (int32_t t : r->types)
-            if (t == optik_host::PRISMATIC)
-                return set_err(-1, "collision: prismatic joints are not supported (IK refuses such chains)");
-    std::lock_guard<std::mutex> lock(r->mu);
-    if (S > 0) {
-        r->coll_frames.assign(frames, frames + S);
-        r->coll_centers.assign(centers3, centers3 + 3 * (size_t)S);
-        r->coll_radii.assign(radii, radii + S);
-        if (P > 0) r->coll_pairs.assign(pairs2, pairs2 + 2 * (size_t)P);
-        else r->coll_pairs.clear();
-        r->coll_margin = margin;
-    } else {
-        r->coll_frames.clear(); r->coll_centers.clear(); r->coll_radii.clear(); r->coll_pairs.clear();
-        r->coll_margin = 0.0;
-    }
-    for (auto &c : r->devs) {
-        if (!c->chain) continue;
-        std::lock_guard<std::mutex> batch_lock(c->batch_mu);
-        if (optik_hip_chain_set_collision_model(c->chain, frames, centers3, radii, S, pairs2, P, margin))
-            return set_err(-1, optik_hip_last_error());
-    }
-    return 0;
-}
-
-int optik_robot_set_world(optik_robot *r, const double *spheres4, int32_t Ms, const double *boxes10, int32_t Mb) {
-    if (!r) return set_err(-1, "null argument");
-    std::string err;
-    if (optik::coll::check_world(spheres4, Ms, boxes10, Mb, err)) return set_err(-1, err);
-    std::lock_guard<std::mutex> lock(r->mu);
-    if (Ms > 0) r->world_spheres.assign(spheres4, spheres4 + 4 * (size_t)Ms);
-    else r->world_spheres.clear();
-    if (Mb > 0) r->world_boxes.assign(boxes10, boxes10 + 10 * (size_t)Mb);
-    else r->world_boxes.clear();
-    for (auto &c : r->devs) {
-        if (!c->chain) continue;
-        std::lock_guard<std::mutex> batch_lock(c->batch_mu);
-        if (optik_hip_chain_set_world(c->chain, spheres4, Ms, boxes10, Mb)) return set_err(-1, optik_hip_last_error());
-    }
-    return 0;
-}
-
-int optik_robot_set_world_grid(optik_robot *r, const double *origin3, double voxel, int32_t nx, int32_t ny, int32_t nz,
-                               const float *values) {
-    if (!r) return set_err(-1, "null argument");
-    const bool clear = !values && nx == 0 && ny == 0 && nz == 0;
-    std::string err;
-    if (!clear && optik::coll::check_grid(origin3, voxel, nx, ny, nz, values, true, err)) return set_err(-1, err);
-    std::lock_guard<std::mutex> lock(r->mu);
-    if (clear) {
-        r->grid_values.clear();
-        r->grid_n[0] = r->grid_n[1] = r->grid_n[2] = 0;
-    } else {
-        r->grid_values.assign(values, values + (size_t)nx * (size_t)ny * (size_t)nz);
-        for (int k = 0; k < 3; ++k) r->grid_origin[k] = origin3[k];
-        r->grid_voxel = voxel;
-        r->grid_n[0] = nx; r->grid_n[1] = ny; r->grid_n[2] = nz;
-    }
-    for (auto &c : r->devs) {
-        if (!c->chain) continue;
-        std::lock_guard<std::mutex> batch_lock(c->batch_mu);
-        if (optik_hip_chain_set_world_grid(c->chain, origin3, voxel, nx, ny, nz, values))
-            return set_err(-1, optik_hip_last_error());
-    }
-    return 0;
-}
-
-int optik_robot_world_grid_bake(const optik_robot *r, const double *origin3, double voxel, int32_t nx, int32_t ny,
-                                int32_t nz, float *values_out) {
-    if (!r || !values_out) return set_err(-1, "null argument");
-    std::string err;
-    if (optik::coll::check_grid(origin3, voxel, nx, ny, nz, nullptr, false, err)) return set_err(-1, err);
-    {
-        std::lock_guard<std::mutex> lock(r->mu);
-        if (r->world_spheres.empty() && r->world_boxes.empty()) return set_err(-1, optik::coll::bake_empty_msg());
-    }
-    DeviceCtx *c = device_ctx(r);
-    if (!c) return -1;
-    std::lock_guard<std::mutex> lock(c->batch_mu);
-    optik::DeviceScope dev_scope(c->device);
-    if (!dev_scope.ok()) return set_err(-1, "hipSetDevice failed");
-    const size_t nodes = (size_t)nx * (size_t)ny * (size_t)nz;
-    float *d_out = nullptr;
-    if (hipMalloc(&d_out, sizeof(float) * nodes) != hipSuccess) return set_err(-1, "bake buffer allocation failed");
-    int rc = 0;
-    if (optik_hip_world_grid_bake(c->chain, origin3, voxel, nx, ny, nz, d_out, nullptr))
-        rc = set_err(-1, optik_hip_last_error());
-    else if (hipMemcpy(values_out, d_out, sizeof(float) * nodes, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = set_err(-1, "download failed");
-    (void)hipFree(d_out);
-    return rc;
-}
-
-int optik_robot_world_grid_from_occupancy(const optik_robot *r, double voxel, int32_t nx, int32_t ny, int32_t nz,
-                                          const uint8_t *occupied, double max_distance, float *values_out) {
-    if (!r || !occupied || !values_out) return set_err(-1, "null argument");
-    std::string err;
-    const double zero3[3] = {0.0, 0.0, 0.0};
-    if (optik::coll::check_grid(zero3, voxel, nx, ny, nz, nullptr, false, err)
-        || optik::coll::check_max_distance(max_distance, err))
-        return set_err(-1, err);
-    DeviceCtx *c = device_ctx(r);
-    if (!c) return -1;
-    std::lock_guard<std::mutex> lock(c->batch_mu);
-    optik::DeviceScope dev_scope(c->device);
-    if (!dev_scope.ok()) return set_err(-1, "hipSetDevice failed");
-    const size_t nodes = (size_t)nx * (size_t)ny * (size_t)nz;
-    // one block: the values, then the occupancy bytes
-    float *d_out = nullptr;
-    if (hipMalloc(&d_out, 5 * nodes) != hipSuccess) return set_err(-1, "occupancy buffer allocation failed");
-    uint8_t *d_occ = reinterpret_cast<uint8_t *>(d_out + nodes);
-    int rc = 0;
-    if (hipMemcpy(d_occ, occupied, nodes, hipMemcpyHostToDevice) != hipSuccess)
-        rc = set_err(-1, "upload failed");
-    else if (optik_hip_world_grid_from_occupancy(c->chain, voxel, nx, ny, nz, d_occ, max_distance, d_out, nullptr))
-        rc = set_err(-1, optik_hip_last_error());
-    else if (hipMemcpy(values_out, d_out, sizeof(float) * nodes, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = set_err(-1, "download failed");
-    (void)hipFree(d_out);
-    return rc;
-}
-
-int optik_robot_occupancy_from_points(const optik_robot *r, const double *origin3, double voxel, int32_t nx, int32_t ny,
-                                      int32_t nz, const double *points3, int64_t N, const double *exclude4, int32_t E,
-                                      uint8_t *occupied) {
-    if (!r) return set_err(-1, "null argument");
-    std::string err;
-    if (optik::coll::check_grid(origin3, voxel, nx, ny, nz, nullptr, false, err) || optik::coll::check_cloud(N, E, err))
-        return set_err(-1, err);
-    if (N == 0) return 0;
-    if (!points3 || !occupied || (E > 0 && !exclude4)) return set_err(-1, "null argument");
-    for (int64_t k = 0; k < 4 * (int64_t)E; ++k)
-        if (!std::isfinite(exclude4[k])) return set_err(-1, "occupancy from points: non-finite exclusion sphere");
-    DeviceCtx *c = device_ctx(r);
-    if (!c) return -1;
-    std::lock_guard<std::mutex> lock(c->batch_mu);
-    optik::DeviceScope dev_scope(c->device);
-    if (!dev_scope.ok()) return set_err(-1, "hipSetDevice failed");
-    const size_t nodes = (size_t)nx * (size_t)ny * (size_t)nz;
-    // one block: the points, the exclusion spheres, then the occupancy bytes
-    const size_t doubles = 3 * (size_t)N + 4 * (size_t)E;
-    double *d_pts = nullptr;
-    if (hipMalloc(&d_pts, sizeof(double) * doubles + nodes) != hipSuccess)
-        return set_err(-1, "point buffer allocation failed");
-    double *d_exc = d_pts + 3 * (size_t)N;
-    uint8_t *d_occ = reinterpret_cast<uint8_t *>(d_pts + doubles);
-    int rc = 0;
-    if (hipMemcpy(d_pts, points3, sizeof(double) * 3 * (size_t)N, hipMemcpyHostToDevice) != hipSuccess
-        || (E > 0 && hipMemcpy(d_exc, exclude4, sizeof(double) * 4 * (size_t)E, hipMemcpyHostToDevice) != hipSuccess)
-        || hipMemcpy(d_occ, occupied, nodes, hipMemcpyHostToDevice) != hipSuccess)
-        rc = set_err(-1, "upload failed");
-    else if (optik_hip_occupancy_from_points(c->chain, origin3, voxel, nx, ny, nz, d_pts, N, E > 0 ? d_exc : nullptr, E,
-                                             d_occ, nullptr))
-        rc = set_err(-1, optik_hip_last_error());
-    else if (hipMemcpy(occupied, d_occ, nodes, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = set_err(-1, "download failed");
-    (void)hipFree(d_pts);
-    return rc;
-}
-
-namespace {
-
-// B rows of x [B][n] through one of the per-configuration kernels of ik_collision.hip on the robot's first device, in
-// chunks of 2^18 rows: per row `out_doubles` doubles come back (what `run` has the kernel write into d_out [L][..]).
-extern "C++" template <class Run, class Take>
-int collision_rows(const optik_robot *r, int64_t B, const double *x, size_t out_doubles, Run run, Take take) {
-    const int n = r->n;
-    DeviceCtx *c = device_ctx(r);
-    if (!c) return -1;
-    std::lock_guard<std::mutex> lock(c->batch_mu);
-    optik::DeviceScope dev_scope(c->device);
-    if (!dev_scope.ok()) return set_err(-1, "hipSetDevice failed");
-    const int64_t chunk = B < ((int64_t)1 << 18) ? B : ((int64_t)1 << 18);
-    const size_t need = ((size_t)n + out_doubles) * (size_t)chunk;
-    if (need > c->batch_cap) {
-        if (c->d_batch) (void)hipFree(c->d_batch);
-        if (c->h_batch) (void)hipHostFree(c->h_batch);
-        c->d_batch = nullptr; c->h_batch = nullptr; c->batch_cap = 0;
-        if (hipMalloc(&c->d_batch, sizeof(double) * need) != hipSuccess
-            || hipHostMalloc(&c->h_batch, sizeof(double) * need) != hipSuccess)
-            return set_err(-1, "batch workspace allocation failed");
-        c->batch_cap = need;
-    }
-    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        const size_t L = (size_t)(B - b0 < chunk ? B - b0 : chunk);
-        double *h_q = c->h_batch, *h_out = h_q + (size_t)n * L;
-        double *d_q = c->d_batch, *d_out = d_q + (size_t)n * L;
-        parallel_ranges(L, [&](size_t k0, size_t k1) {
-            for (size_t k = k0; k < k1; ++k)
-                for (int i = 0; i < n; ++i) h_q[(size_t)i * L + k] = x[((size_t)b0 + k) * n + i];
-        });
-        if (hipMemcpyAsync(d_q, h_q, sizeof(double) * (size_t)n * L, hipMemcpyHostToDevice, nullptr) != hipSuccess)
-            return set_err(-1, "upload failed");
-        if (run(c->chain, d_q, (int64_t)L, d_out)) return set_err(-1, optik_hip_last_error());
-        if (hipMemcpyAsync(h_out, d_out, sizeof(double) * out_doubles * L, hipMemcpyDeviceToHost, nullptr) != hipSuccess
-            || hipStreamSynchronize(nullptr) != hipSuccess)
-            return set_err(-1, "download failed");
-        take((size_t)b0, L, h_out);
-    }
-    return 0;
-}
-
-}  // namespace
-
-int optik_robot_link_frames_batch(const optik_robot *r, int64_t B, const double *x, const double *ee16,
-                                  double *frames16_out) {
-    if (!r || !x || !frames16_out) return set_err(-1, "null argument");
-    if (B < 0) return set_err(-1, "bad argument");
-    DeviceCtx *c0 = device_ctx(r);
-    if (!c0) return -1;
-    // (B = 0: the kernel layer's refusals of the chain alone -- prismatic joints -- before anything is staged)
-    if (optik_hip_link_frames_batch(c0->chain, nullptr, nullptr, 0, nullptr, nullptr))
-        return set_err(-1, optik_hip_last_error());
-    if (B == 0) return 0;
-    double ee7[7];
-    if (ee16) pose7_from_mat16(ee16, ee7);
-    const size_t nf = (size_t)r->n + 2;
-    return collision_rows(
-        r, B, x, 7 * nf,
-        [&](optik_hip_chain *ch, const double *d_q, int64_t L, double *d_out) {
-            return optik_hip_link_frames_batch(ch, ee16 ? ee7 : nullptr, d_q, L, d_out, nullptr);
-        },
-        [&](size_t b0, size_t L, const double *h_out) {
-            parallel_ranges(L * nf, [&](size_t k0, size_t k1) {
-                for (size_t k = k0; k < k1; ++k) mat16_from_pose7(h_out + 7 * k, frames16_out + 16 * (b0 * nf + k));
-            });
-        });
-}
-
-int optik_robot_collision_batch(const optik_robot *r, int64_t B, const double *x, const double *ee16,
-                                double *clearance_out, uint8_t *free_out) {
-    if (!r || !x) return set_err(-1, "null argument");
-    if (B < 0) return set_err(-1, "bad argument");
-    DeviceCtx *c0 = device_ctx(r);
-    if (!c0) return -1;
-    if (optik_hip_collision_batch(c0->chain, nullptr, nullptr, 0, nullptr, nullptr, nullptr))
-        return set_err(-1, optik_hip_last_error());
-    if (B == 0 || (!clearance_out && !free_out)) return 0;
-    double ee7[7];
-    if (ee16) pose7_from_mat16(ee16, ee7);
-    // per row: the clearance, then the free flag in the bytes of a second double
-    return collision_rows(
-        r, B, x, 2,
-        [&](optik_hip_chain *ch, const double *d_q, int64_t L, double *d_out) {
-            return optik_hip_collision_batch(ch, ee16 ? ee7 : nullptr, d_q, L, d_out,
-                                             reinterpret_cast<uint8_t *>(d_out + L), nullptr);
-        },
-        [&](size_t b0, size_t L, const double *h_out) {
-            if (clearance_out) std::memcpy(clearance_out + b0, h_out, sizeof(double) * L);
-            if (free_out) std::memcpy(free_out + b0, reinterpret_cast<const uint8_t *>(h_out + L), L);
-        });
-}
-
-int optik_robot_set_motion_resolution(optik_robot *r, double h) {
-    if (!r) return set_err(-1, "null argument");
-    if (!(h >= 0.0) || !std::isfinite(h))
-        return set_err(-1, "motion resolution must be finite and >= 0 (0: no motion check)");
-    std::lock_guard<std::mutex> lock(r->mu);
-    r->motion_h = h;
-    for (auto &c : r->devs) {
-        if (!c->chain) continue;
-        std::lock_guard<std::mutex> batch_lock(c->batch_mu);
-        if (optik_hip_chain_set_motion_resolution(c->chain, h)) return set_err(-1, optik_hip_last_error());
-    }
-    return 0;
-}
-
-int optik_robot_collision_motion_batch(const optik_robot *r, int64_t B, const double *xa, const double *xb,
-                                       double resolution, const double *ee16, double *clearance_out,
-                                       uint8_t *free_out, int32_t *first_out, int32_t *steps_out) {
-    if (!r || !xa || !xb) return set_err(-1, "null argument");
-    if (B < 0) return set_err(-1, "bad argument");
-    // (refused on the host, before a device context exists)
-    if (!(resolution > 0.0) || !std::isfinite(resolution))
-        return set_err(-1, "motion resolution must be finite and > 0");
-    for (int32_t t : r->types)
-        if (t == optik_host::PRISMATIC)
-            return set_err(-1, "collision: prismatic joints are not supported (IK refuses such chains)");
-    DeviceCtx *c = device_ctx(r);
-    if (!c) return -1;
-    // (B = 0: the kernel layer's own refusals of the chain, before anything is staged)
-    if (optik_hip_collision_motion_batch(c->chain, nullptr, nullptr, nullptr, 0, resolution, nullptr, nullptr, nullptr,
-                                         nullptr, nullptr))
-        return set_err(-1, optik_hip_last_error());
-    if (B == 0 || (!clearance_out && !free_out && !first_out && !steps_out)) return 0;
-    double ee7[7];
-    if (ee16) pose7_from_mat16(ee16, ee7);
-    const int n = r->n;
-    std::lock_guard<std::mutex> lock(c->batch_mu);
-    optik::DeviceScope dev_scope(c->device);
-    if (!dev_scope.ok()) return set_err(-1, "hipSetDevice failed");
-    // per segment: qa and qb (2 n doubles) in, the clearance, then first and steps in a second double and the free
-    // flag in the bytes of a third
-    const int64_t chunk = B < ((int64_t)1 << 16) ? B : ((int64_t)1 << 16);
-    const size_t need = (2 * (size_t)n + 3) * (size_t)chunk;
-    if (need > c->batch_cap) {
-        if (c->d_batch) (void)hipFree(c->d_batch);
-        if (c->h_batch) (void)hipHostFree(c->h_batch);
-        c->d_batch = nullptr; c->h_batch = nullptr; c->batch_cap = 0;
-        if (hipMalloc(&c->d_batch, sizeof(double) * need) != hipSuccess
-            || hipHostMalloc(&c->h_batch, sizeof(double) * need) != hipSuccess)
-            return set_err(-1, "batch workspace allocation failed");
-        c->batch_cap = need;
-    }
-    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        const size_t L = (size_t)(B - b0 < chunk ? B - b0 : chunk);
-        double *h_q = c->h_batch, *h_out = h_q + 2 * (size_t)n * L;
-        double *d_q = c->d_batch, *d_out = d_q + 2 * (size_t)n * L;
-        parallel_ranges(L, [&](size_t k0, size_t k1) {
-            for (size_t k = k0; k < k1; ++k)
-                for (int i = 0; i < n; ++i) {
-                    h_q[(size_t)i * L + k] = xa[((size_t)b0 + k) * n + i];
-                    h_q[((size_t)n + i) * L + k] = xb[((size_t)b0 + k) * n + i];
-                }
-        });
-        if (hipMemcpyAsync(d_q, h_q, sizeof(double) * 2 * (size_t)n * L, hipMemcpyHostToDevice, nullptr) != hipSuccess)
-            return set_err(-1, "upload failed");
-        int32_t *d_first = reinterpret_cast<int32_t *>(d_out + L);
-        if (optik_hip_collision_motion_batch(c->chain, ee16 ? ee7 : nullptr, d_q, d_q + (size_t)n * L, (int64_t)L,
-                                             resolution, clearance_out ? d_out : nullptr,
-                                             reinterpret_cast<uint8_t *>(d_out + 2 * L), d_first, d_first + L, nullptr))
-            return set_err(-1, optik_hip_last_error());
-        if (hipMemcpyAsync(h_out, d_out, sizeof(double) * 3 * L, hipMemcpyDeviceToHost, nullptr) != hipSuccess
-            || hipStreamSynchronize(nullptr) != hipSuccess)
-            return set_err(-1, "download failed");
-        const int32_t *h_first = reinterpret_cast<const int32_t *>(h_out + L);
-        if (clearance_out) std::memcpy(clearance_out + b0, h_out, sizeof(double) * L);
-        if (first_out) std::memcpy(first_out + b0, h_first, sizeof(int32_t) * L);
-        if (steps_out) std::memcpy(steps_out + b0, h_first + L, sizeof(int32_t) * L);
-        if (free_out) std::memcpy(free_out + b0, reinterpret_cast<const uint8_t *>(h_out + 2 * L), L);
-    }
     return 0;
 }
 

@@ -1,0 +1,347 @@
+// robot_rows.cpp -- the row batches of the host API (diff_ik, manipulability, link frames, clearance, motion), each
+// one stage_rows over the robot's first device, and what they are checked against: the collision model, the worlds
+// and their builders.  (robot_host.hpp: the robot object and the shared plumbing.)
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <string>
+
+#include "collision_model.hpp"
+#include "pose_convert.hpp"
+#include "robot_host.hpp"
+
+using namespace optik::robot;
+using optik::pose::mat16_from_pose7;
+using optik::pose::pose7_from_mat16;
+
+namespace {
+
+constexpr int64_t kRowChunk = (int64_t)1 << 18;     // rows per launch
+constexpr int64_t kMotionChunk = (int64_t)1 << 16;  // segments per launch (each is many samples)
+
+}  // namespace
+
+extern "C" {
+
+// B diff_ik calls in one launch per chunk of rows (optik_hip_diff_ik_batch: the same FK, Jacobian and LP code as
+// optik_robot_diff_ik_ex, on the device).  Rows are staged to struct-of-arrays through the robot's pinned batch block.
+int optik_robot_diff_ik_batch(const optik_robot *r, int64_t B, const double *x0, const double *V_WE,
+                              const double *v_max, const double *ee16, double *alpha_out, double *v_out,
+                              int32_t *status_out) {
+    if (!r || !x0 || !V_WE || !v_max) return set_err(-1, "null argument");
+    if (B < 0) return set_err(-1, "bad argument");
+    const int n = r->n;
+    if (n > 8) return set_err(-1, kDiffIkMaxNMsg);
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    // (B = 0: the kernel layer's refusals of the chain alone -- prismatic joints -- before anything is staged)
+    if (optik_hip_diff_ik_batch(c->chain, nullptr, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr,
+                                nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (B == 0) return 0;
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    // per row: q n | V 6 | v_max n doubles in; alpha 1 | v n doubles, then the int32 status words (half a double each) out
+    const RowInput in[] = {{x0, (size_t)n}, {V_WE, 6}, {v_max, (size_t)n}};
+    // (rows per launch: 2^18 bounds the block, ~66 MB for 8 joints, whatever B is)
+    return stage_rows(
+        c, B, in, sizeof(double) * (size_t)(n + 1) + sizeof(int32_t), kRowChunk,
+        [&](optik_hip_chain *ch, const double *d_q, int64_t L, double *d_a) {
+            const double *d_V = d_q + (size_t)n * L, *d_vm = d_V + 6 * L;
+            double *d_v = d_a + L;
+            return optik_hip_diff_ik_batch(ch, ee16 ? ee7 : nullptr, d_q, d_V, L, d_vm, L, L, d_a, d_v,
+                                           reinterpret_cast<int32_t *>(d_v + (size_t)n * L), nullptr);
+        },
+        [&](size_t b0, size_t L, const double *h_a) {
+            const double *h_v = h_a + L;
+            const int32_t *h_st = reinterpret_cast<const int32_t *>(h_v + (size_t)n * L);
+            parallel_ranges(L, [&](size_t k0, size_t k1) {
+                for (size_t k = k0; k < k1; ++k) {
+                    const size_t row = b0 + k;
+                    if (alpha_out) alpha_out[row] = h_a[k];
+                    if (v_out) for (int i = 0; i < n; ++i) v_out[row * n + i] = h_v[(size_t)i * L + k];
+                    if (status_out) status_out[row] = h_st[k];
+                }
+            });
+        });
+}
+
+// The measures of solution modes 3 and 4 for B configurations (optik_hip_manip_batch), staged as
+// optik_robot_diff_ik_batch stages its rows.
+int optik_robot_manipulability_batch(const optik_robot *r, int64_t B, const double *x, const double *ee16,
+                                     double *w_out, double *c_out) {
+    if (!r || !x) return set_err(-1, "null argument");
+    if (B < 0) return set_err(-1, "bad argument");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    // (B = 0: the kernel layer's refusals of the chain alone -- prismatic joints -- before anything is staged)
+    if (optik_hip_manip_batch(c->chain, nullptr, nullptr, 0, nullptr, nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (B == 0 || (!w_out && !c_out)) return 0;
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    // per row: q n doubles in; w 1 | c 1 doubles out
+    const RowInput in[] = {{x, (size_t)r->n}};
+    return stage_rows(
+        c, B, in, 2 * sizeof(double), kRowChunk,
+        [&](optik_hip_chain *ch, const double *d_q, int64_t L, double *d_w) {
+            return optik_hip_manip_batch(ch, ee16 ? ee7 : nullptr, d_q, L, w_out ? d_w : nullptr,
+                                         c_out ? d_w + L : nullptr, nullptr);
+        },
+        [&](size_t b0, size_t L, const double *h_w) {
+            if (w_out) std::memcpy(w_out + b0, h_w, sizeof(double) * L);
+            if (c_out) std::memcpy(c_out + b0, h_w + L, sizeof(double) * L);
+        });
+}
+
+// The collision model and world (include/optik.h): checked on the host before any device work, kept with the robot
+// and applied to every device chain it has (device_ctx applies them to the chains it creates later).
+int optik_robot_set_collision_model(optik_robot *r, const int32_t *frames, const double *centers3, const double *radii,
+                                    int32_t S, const int32_t *pairs2, int32_t P, double margin) {
+    if (!r) return set_err(-1, "null argument");
+    std::string err;
+    if (optik::coll::check_model(r->n, frames, centers3, radii, S, pairs2, P, margin, err)) return set_err(-1, err);
+    if (S > 0)
+        for (int32_t t : r->types)
+            if (t == optik_host::PRISMATIC)
+                return set_err(-1, "collision: prismatic joints are not supported (IK refuses such chains)");
+    std::lock_guard<std::mutex> lock(r->mu);
+    if (S > 0) {
+        r->coll_frames.assign(frames, frames + S);
+        r->coll_centers.assign(centers3, centers3 + 3 * (size_t)S);
+        r->coll_radii.assign(radii, radii + S);
+        if (P > 0) r->coll_pairs.assign(pairs2, pairs2 + 2 * (size_t)P);
+        else r->coll_pairs.clear();
+        r->coll_margin = margin;
+    } else {
+        r->coll_frames.clear(); r->coll_centers.clear(); r->coll_radii.clear(); r->coll_pairs.clear();
+        r->coll_margin = 0.0;
+    }
+    return for_each_chain(r, [&](optik_hip_chain *ch) {
+        return optik_hip_chain_set_collision_model(ch, frames, centers3, radii, S, pairs2, P, margin);
+    });
+}
+
+int optik_robot_set_world(optik_robot *r, const double *spheres4, int32_t Ms, const double *boxes10, int32_t Mb) {
+    if (!r) return set_err(-1, "null argument");
+    std::string err;
+    if (optik::coll::check_world(spheres4, Ms, boxes10, Mb, err)) return set_err(-1, err);
+    std::lock_guard<std::mutex> lock(r->mu);
+    if (Ms > 0) r->world_spheres.assign(spheres4, spheres4 + 4 * (size_t)Ms);
+    else r->world_spheres.clear();
+    if (Mb > 0) r->world_boxes.assign(boxes10, boxes10 + 10 * (size_t)Mb);
+    else r->world_boxes.clear();
+    return for_each_chain(r, [&](optik_hip_chain *ch) {
+        return optik_hip_chain_set_world(ch, spheres4, Ms, boxes10, Mb);
+    });
+}
+
+int optik_robot_set_world_grid(optik_robot *r, const double *origin3, double voxel, int32_t nx, int32_t ny, int32_t nz,
+                               const float *values) {
+    if (!r) return set_err(-1, "null argument");
+    const bool clear = !values && nx == 0 && ny == 0 && nz == 0;
+    std::string err;
+    if (!clear && optik::coll::check_grid(origin3, voxel, nx, ny, nz, values, true, err)) return set_err(-1, err);
+    std::lock_guard<std::mutex> lock(r->mu);
+    if (clear) {
+        r->grid_values.clear();
+        r->grid_n[0] = r->grid_n[1] = r->grid_n[2] = 0;
+    } else {
+        r->grid_values.assign(values, values + (size_t)nx * (size_t)ny * (size_t)nz);
+        for (int k = 0; k < 3; ++k) r->grid_origin[k] = origin3[k];
+        r->grid_voxel = voxel;
+        r->grid_n[0] = nx; r->grid_n[1] = ny; r->grid_n[2] = nz;
+    }
+    return for_each_chain(r, [&](optik_hip_chain *ch) {
+        return optik_hip_chain_set_world_grid(ch, origin3, voxel, nx, ny, nz, values);
+    });
+}
+
+int optik_robot_world_grid_bake(const optik_robot *r, const double *origin3, double voxel, int32_t nx, int32_t ny,
+                                int32_t nz, float *values_out) {
+    if (!r || !values_out) return set_err(-1, "null argument");
+    std::string err;
+    if (optik::coll::check_grid(origin3, voxel, nx, ny, nz, nullptr, false, err)) return set_err(-1, err);
+    {
+        std::lock_guard<std::mutex> lock(r->mu);
+        if (r->world_spheres.empty() && r->world_boxes.empty()) return set_err(-1, optik::coll::bake_empty_msg());
+    }
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    BatchGuard guard(c);
+    if (!guard.ok()) return set_err(-1, kSetDeviceMsg);
+    const size_t nodes = (size_t)nx * (size_t)ny * (size_t)nz;
+    optik::DeviceBuf<float> d_out;  // (this call's own; freed on return, before the guard lets go)
+    if (d_out.reserve(nodes) != hipSuccess) return set_err(-1, "bake buffer allocation failed");
+    if (optik_hip_world_grid_bake(c->chain, origin3, voxel, nx, ny, nz, d_out.get(), nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (hipMemcpy(values_out, d_out.get(), sizeof(float) * nodes, hipMemcpyDeviceToHost) != hipSuccess)
+        return set_err(-1, "download failed");
+    return 0;
+}
+
+int optik_robot_world_grid_from_occupancy(const optik_robot *r, double voxel, int32_t nx, int32_t ny, int32_t nz,
+                                          const uint8_t *occupied, double max_distance, float *values_out) {
+    if (!r || !occupied || !values_out) return set_err(-1, "null argument");
+    std::string err;
+    const double zero3[3] = {0.0, 0.0, 0.0};
+    if (optik::coll::check_grid(zero3, voxel, nx, ny, nz, nullptr, false, err)
+        || optik::coll::check_max_distance(max_distance, err))
+        return set_err(-1, err);
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    BatchGuard guard(c);
+    if (!guard.ok()) return set_err(-1, kSetDeviceMsg);
+    const size_t nodes = (size_t)nx * (size_t)ny * (size_t)nz;
+    // one block: the values, then the occupancy bytes
+    optik::DeviceBuf<uint8_t> block;
+    if (block.reserve(5 * nodes) != hipSuccess) return set_err(-1, "occupancy buffer allocation failed");
+    float *d_out = reinterpret_cast<float *>(block.get());
+    uint8_t *d_occ = reinterpret_cast<uint8_t *>(d_out + nodes);
+    if (hipMemcpy(d_occ, occupied, nodes, hipMemcpyHostToDevice) != hipSuccess) return set_err(-1, "upload failed");
+    if (optik_hip_world_grid_from_occupancy(c->chain, voxel, nx, ny, nz, d_occ, max_distance, d_out, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (hipMemcpy(values_out, d_out, sizeof(float) * nodes, hipMemcpyDeviceToHost) != hipSuccess)
+        return set_err(-1, "download failed");
+    return 0;
+}
+
+int optik_robot_occupancy_from_points(const optik_robot *r, const double *origin3, double voxel, int32_t nx, int32_t ny,
+                                      int32_t nz, const double *points3, int64_t N, const double *exclude4, int32_t E,
+                                      uint8_t *occupied) {
+    if (!r) return set_err(-1, "null argument");
+    std::string err;
+    if (optik::coll::check_grid(origin3, voxel, nx, ny, nz, nullptr, false, err) || optik::coll::check_cloud(N, E, err))
+        return set_err(-1, err);
+    if (N == 0) return 0;
+    if (!points3 || !occupied || (E > 0 && !exclude4)) return set_err(-1, "null argument");
+    for (int64_t k = 0; k < 4 * (int64_t)E; ++k)
+        if (!std::isfinite(exclude4[k])) return set_err(-1, "occupancy from points: non-finite exclusion sphere");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    BatchGuard guard(c);
+    if (!guard.ok()) return set_err(-1, kSetDeviceMsg);
+    const size_t nodes = (size_t)nx * (size_t)ny * (size_t)nz;
+    // one block: the points, the exclusion spheres, then the occupancy bytes
+    const size_t doubles = 3 * (size_t)N + 4 * (size_t)E;
+    optik::DeviceBuf<uint8_t> block;
+    if (block.reserve(sizeof(double) * doubles + nodes) != hipSuccess)
+        return set_err(-1, "point buffer allocation failed");
+    double *d_pts = reinterpret_cast<double *>(block.get()), *d_exc = d_pts + 3 * (size_t)N;
+    uint8_t *d_occ = reinterpret_cast<uint8_t *>(d_pts + doubles);
+    if (hipMemcpy(d_pts, points3, sizeof(double) * 3 * (size_t)N, hipMemcpyHostToDevice) != hipSuccess
+        || (E > 0 && hipMemcpy(d_exc, exclude4, sizeof(double) * 4 * (size_t)E, hipMemcpyHostToDevice) != hipSuccess)
+        || hipMemcpy(d_occ, occupied, nodes, hipMemcpyHostToDevice) != hipSuccess)
+        return set_err(-1, "upload failed");
+    if (optik_hip_occupancy_from_points(c->chain, origin3, voxel, nx, ny, nz, d_pts, N, E > 0 ? d_exc : nullptr, E, d_occ,
+                                        nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (hipMemcpy(occupied, d_occ, nodes, hipMemcpyDeviceToHost) != hipSuccess) return set_err(-1, "download failed");
+    return 0;
+}
+
+int optik_robot_link_frames_batch(const optik_robot *r, int64_t B, const double *x, const double *ee16,
+                                  double *frames16_out) {
+    if (!r || !x || !frames16_out) return set_err(-1, "null argument");
+    if (B < 0) return set_err(-1, "bad argument");
+    DeviceCtx *c0 = device_ctx(r);
+    if (!c0) return -1;
+    // (B = 0: the kernel layer's refusals of the chain alone -- prismatic joints -- before anything is staged)
+    if (optik_hip_link_frames_batch(c0->chain, nullptr, nullptr, 0, nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (B == 0) return 0;
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    const size_t nf = (size_t)r->n + 2;
+    const RowInput in[] = {{x, (size_t)r->n}};
+    return stage_rows(
+        c0, B, in, sizeof(double) * 7 * nf, kRowChunk,
+        [&](optik_hip_chain *ch, const double *d_q, int64_t L, double *d_out) {
+            return optik_hip_link_frames_batch(ch, ee16 ? ee7 : nullptr, d_q, L, d_out, nullptr);
+        },
+        [&](size_t b0, size_t L, const double *h_out) {
+            parallel_ranges(L * nf, [&](size_t k0, size_t k1) {
+                for (size_t k = k0; k < k1; ++k) mat16_from_pose7(h_out + 7 * k, frames16_out + 16 * (b0 * nf + k));
+            });
+        });
+}
+
+int optik_robot_collision_batch(const optik_robot *r, int64_t B, const double *x, const double *ee16,
+                                double *clearance_out, uint8_t *free_out) {
+    if (!r || !x) return set_err(-1, "null argument");
+    if (B < 0) return set_err(-1, "bad argument");
+    DeviceCtx *c0 = device_ctx(r);
+    if (!c0) return -1;
+    if (optik_hip_collision_batch(c0->chain, nullptr, nullptr, 0, nullptr, nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (B == 0 || (!clearance_out && !free_out)) return 0;
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    // per row: the clearance, then the free flag in the bytes of a second double
+    const RowInput in[] = {{x, (size_t)r->n}};
+    return stage_rows(
+        c0, B, in, 2 * sizeof(double), kRowChunk,
+        [&](optik_hip_chain *ch, const double *d_q, int64_t L, double *d_out) {
+            return optik_hip_collision_batch(ch, ee16 ? ee7 : nullptr, d_q, L, d_out,
+                                             reinterpret_cast<uint8_t *>(d_out + L), nullptr);
+        },
+        [&](size_t b0, size_t L, const double *h_out) {
+            if (clearance_out) std::memcpy(clearance_out + b0, h_out, sizeof(double) * L);
+            if (free_out) std::memcpy(free_out + b0, reinterpret_cast<const uint8_t *>(h_out + L), L);
+        });
+}
+
+int optik_robot_set_motion_resolution(optik_robot *r, double h) {
+    if (!r) return set_err(-1, "null argument");
+    if (!(h >= 0.0) || !std::isfinite(h))
+        return set_err(-1, "motion resolution must be finite and >= 0 (0: no motion check)");
+    std::lock_guard<std::mutex> lock(r->mu);
+    r->motion_h = h;
+    return for_each_chain(r, [&](optik_hip_chain *ch) {
+        return optik_hip_chain_set_motion_resolution(ch, h);
+    });
+}
+
+int optik_robot_collision_motion_batch(const optik_robot *r, int64_t B, const double *xa, const double *xb,
+                                       double resolution, const double *ee16, double *clearance_out,
+                                       uint8_t *free_out, int32_t *first_out, int32_t *steps_out) {
+    if (!r || !xa || !xb) return set_err(-1, "null argument");
+    if (B < 0) return set_err(-1, "bad argument");
+    // (refused on the host, before a device context exists)
+    if (!(resolution > 0.0) || !std::isfinite(resolution))
+        return set_err(-1, "motion resolution must be finite and > 0");
+    for (int32_t t : r->types)
+        if (t == optik_host::PRISMATIC)
+            return set_err(-1, "collision: prismatic joints are not supported (IK refuses such chains)");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    // (B = 0: the kernel layer's own refusals of the chain, before anything is staged)
+    if (optik_hip_collision_motion_batch(c->chain, nullptr, nullptr, nullptr, 0, resolution, nullptr, nullptr, nullptr,
+                                         nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (B == 0 || (!clearance_out && !free_out && !first_out && !steps_out)) return 0;
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    // per segment: qa and qb (2 n doubles) in; the clearance, then first and steps in a second double and the free
+    // flag in the bytes of a third out
+    const RowInput in[] = {{xa, (size_t)r->n}, {xb, (size_t)r->n}};
+    return stage_rows(
+        c, B, in, 3 * sizeof(double), kMotionChunk,
+        [&](optik_hip_chain *ch, const double *d_q, int64_t L, double *d_out) {
+            int32_t *d_first = reinterpret_cast<int32_t *>(d_out + L);
+            return optik_hip_collision_motion_batch(ch, ee16 ? ee7 : nullptr, d_q, d_q + (size_t)r->n * L, L, resolution,
+                                                    clearance_out ? d_out : nullptr,
+                                                    reinterpret_cast<uint8_t *>(d_out + 2 * L), d_first, d_first + L,
+                                                    nullptr);
+        },
+        [&](size_t b0, size_t L, const double *h_out) {
+            const int32_t *h_first = reinterpret_cast<const int32_t *>(h_out + L);
+            if (clearance_out) std::memcpy(clearance_out + b0, h_out, sizeof(double) * L);
+            if (first_out) std::memcpy(first_out + b0, h_first, sizeof(int32_t) * L);
+            if (steps_out) std::memcpy(steps_out + b0, h_first + L, sizeof(int32_t) * L);
+            if (free_out) std::memcpy(free_out + b0, reinterpret_cast<const uint8_t *>(h_out + 2 * L), L);
+        });
+}
+
+}  // extern "C"

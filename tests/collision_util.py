@@ -108,3 +108,13 @@ def build_measure(workdir=None):
             return out
 
     return Measure()
+
+
+def small_scene(robot):
+    """A small scene for tests that need some model and world rather than a particular one: (model, spheres) -- the
+    keyword arguments of Robot.set_collision_model (two spheres per link of the chain, "auto" pairs, a 1 cm margin) and
+    two world spheres [2, 4] within reach, so that random configurations are a mix of free and colliding ones."""
+    from optik_amd.collision import auto_pairs, spheres_along_chain
+    frames, centers, radii = spheres_along_chain(robot, 0.05, 2)
+    model = dict(frames=frames, centers=centers, radii=radii, self_pairs=auto_pairs(frames), margin=0.01)
+    return model, np.array([[0.45, 0.10, 0.40, 0.12], [-0.20, -0.35, 0.65, 0.10]])
