@@ -4,7 +4,7 @@
 // bits: column k = (linear, angular) in the end-effector frame.
 #pragma once
 
-#include <hip/hip_runtime.h>
+#include "ik_platform.hpp"
 
 #include "ik_launch.hpp"
 #include "ik_wide_launch.hpp"

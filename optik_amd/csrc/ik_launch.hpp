@@ -2,7 +2,7 @@
 // shared by the translation units that hold those kernels.
 #pragma once
 
-#include <hip/hip_runtime.h>
+#include "ik_platform.hpp"
 
 #include "ik_solve.hpp"
 

@@ -1,10 +1,12 @@
 // ik_platform.hpp -- the ONE place where the device headers know about tests/emu.
 //
 // The library is never built with OPTIK_LANE_EMU.  tests/emu/quad_emu.cpp compiles the quad and lane-per-restart
-// solvers for the host with the wave emulated by one thread per lane (tests/emu/lane_emu.hpp): there the HIP runtime
-// header is replaced by the emulation -- which also provides the cross-lane builtins this code uses
-// (__builtin_amdgcn_update_dpp with quad_perm controls, mbcnt, ballot, shuffles, fences) under their device
-// names and with their device semantics, so ik_lane.hpp and everything above it is the same text on both sides --
+// solvers, and tests/emu/wide_emu.cpp the general solver of ik_wide.hpp, for the host with the wave emulated by one
+// thread per lane (tests/emu/lane_emu.hpp): there the HIP runtime header is replaced by the emulation -- every device
+// header reaches it through this file -- which also provides the cross-lane builtins this code uses
+// (__builtin_amdgcn_update_dpp with quad_perm controls, mbcnt, ballot, shuffles, lane reads, fences, __syncthreads)
+// under their device names and with their device semantics, so ik_lane.hpp and everything above it is the same text on
+// both sides --
 // and the three things below differ: the register class an empty asm statement can launder a value through, how a
 // pointer into LDS keeps its address space through that laundering, and the shape of the (partial) wave.
 #pragma once

@@ -3,7 +3,7 @@
 // host code of ik_capi.hip / ik_batch_ops.hip.
 #pragma once
 
-#include <hip/hip_runtime.h>
+#include "ik_platform.hpp"
 
 #include "ik_solve.hpp"
 

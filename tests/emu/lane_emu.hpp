@@ -1,16 +1,26 @@
 // lane_emu.hpp -- TEST INFRASTRUCTURE: host emulation of a (partial) 64-lane wavefront.
 //
-// Lets the group-distributed solver (optik_amd/csrc/ik_quad.hpp: one restart per quad of four
-// lanes, state spread over the lanes, cross-lane moves) run on the CPU so that its arithmetic can
-// be compared bit for bit with the C oracle without a GPU.  One std::thread per lane; every
-// cross-lane primitive (__shfl, __ballot, the quad moves, LDS hand-over points) is an exchange
-// through a shared array between two barriers, so the threads advance in the lock step the
-// hardware gives for free.  Only wave-uniform control flow around those primitives is supported
-// -- which is also the rule the device code must obey.
+// Lets the device solvers run on the CPU so that their arithmetic can be compared bit for bit with
+// the C oracle without a GPU: the group-distributed solver (optik_amd/csrc/ik_quad.hpp: one restart
+// per quad of four lanes, state spread over the lanes, cross-lane moves), the lane-per-restart solver
+// (ik_lane64.hpp) and the general solver of the 9 .. 16 joint chains (ik_wide.hpp, all three of its
+// forms).  One std::thread per lane; every cross-lane primitive (__shfl, __ballot, lane reads, the
+// quad moves, LDS hand-over points, the workgroup barrier) is an exchange through a shared array
+// between barriers, so the threads advance in the lock step the hardware gives for free.  Only
+// wave-uniform control flow around those primitives is supported -- which is also the rule the
+// device code must obey.
+//
+// What the lock step of the hardware gives and free-running threads do not is memory that every lane
+// of a wave updates redundantly (ik_wide.hpp's cooperative form: "same loads, same values, same
+// stores" of z[i] -= ... by all 64 lanes at once).  A wave that shares memory in that way registers it
+// (Wave::share): each lane then works on a copy of its own, and __syncthreads() -- the one point where
+// the device code hands data from lane to lane through that memory -- merges the copies: where one
+// lane's word differs from all the others', that lane's is the later value.  A word with any other
+// disagreement is a race in the device code: the emulation says so and aborts.
 //
 // Never part of the product: liboptik_amd.so is built without OPTIK_LANE_EMU, and nothing under
-// optik_amd/ or bench.py includes this file.  Compiled only by tests/emu/quad_emu.cpp (host
-// clang, -ffp-contract=off like both the kernels and the oracle).
+// optik_amd/ or bench.py includes this file.  Compiled only by tests/emu/quad_emu.cpp and
+// tests/emu/wide_emu.cpp (host clang, -ffp-contract=off like both the kernels and the oracle).
 #pragma once
 
 #include <atomic>
@@ -35,6 +45,15 @@ struct Wave {
     std::atomic<int> arrived{0};
     std::atomic<int> generation{0};
     unsigned long long xch[MAX_LANES];
+    int lane_xch[2][MAX_LANES];  // lane reads: alternating buffers, one barrier each
+    // memory the lanes update redundantly (see the header comment): a copy per lane
+    typedef unsigned long long __attribute__((may_alias)) word;
+    word *copy[MAX_LANES] = {};
+    size_t shared_words = 0;
+    void share(double *const *lane_copies, size_t doubles) {
+        for (int i = 0; i < lanes; ++i) copy[i] = reinterpret_cast<word *>(lane_copies[i]);
+        shared_words = doubles;
+    }
 };
 
 struct Dim3 {
@@ -89,6 +108,10 @@ inline T from_bits(unsigned long long b) {
 
 inline thread_local optik_emu::Dim3 threadIdx;
 inline thread_local optik_emu::Dim3 blockIdx;
+inline thread_local optik_emu::Dim3 blockDim;
+// the two HIP names the launch declarations of the device headers mention (nothing is launched here)
+typedef int hipError_t;
+typedef void *hipStream_t;
 inline unsigned optik_emu::threadIdx_x() { return threadIdx.x; }
 
 // ---- wave collectives (called by every emulated lane, in wave-uniform control flow) ----------
@@ -121,6 +144,63 @@ inline unsigned long long __ballot(bool p) {
     optik_emu::barrier();
     return m;
 }
+
+// ---- lane reads and the workgroup barrier (ik_wide.hpp's cooperative form) -------------------------------------
+namespace optik_emu {
+// v_readlane_b32: lane `src`'s value in every lane, `src` wave-uniform.  (Alternating buffers: a lane can be at most
+// one read ahead of the slowest one, so one barrier per read is enough.)
+inline int readlane(int v, int src) {
+    Wave &w = *t_wave;
+    if (src < 0 || src >= w.lanes) {
+        std::fprintf(stderr, "lane_emu: readlane from lane %d of a %d-lane wave\n", src, w.lanes);
+        std::abort();
+    }
+    static thread_local unsigned turn = 0;
+    int *buf = w.lane_xch[turn++ & 1u];
+    buf[threadIdx_x() & 63u] = v;
+    barrier();
+    return buf[src];
+}
+// __syncthreads() of a one-wave workgroup: a barrier, and where the wave shares memory (Wave::share) the merge of the
+// lanes' copies -- lane l merges its slice of the words.  Between two barriers the device code stores to a shared word
+// either from every lane (the redundant scalar recurrences: the same value) or from the one lane a dealt-out loop
+// gives it to -- also after every lane stored to it (f[i] formed by all, negated by lane i; s[i] formed by all, clamped
+// by lane i).  So the copies of a word either agree, or one lane's differs from all the others' and is the later
+// value.  Anything else has no lock-step reading that does not depend on the order of the stores: a race in the
+// device code.
+inline void sync_threads() {
+    Wave &w = *t_wave;
+    barrier();
+    if (!w.shared_words) return;
+    const size_t lane = threadIdx_x() & 63u;
+    const size_t lo = lane * w.shared_words / (size_t)w.lanes, hi = (lane + 1) * w.shared_words / (size_t)w.lanes;
+    for (size_t k = lo; k < hi; ++k) {
+        const unsigned long long v0 = w.copy[0][k];
+        unsigned long long v1 = v0;
+        int n0 = 0, n1 = 0;
+        bool third = false;
+        for (int i = 0; i < w.lanes; ++i) {
+            const unsigned long long p = w.copy[i][k];
+            if (p == v0) ++n0;
+            else if (n1 == 0 || p == v1) { v1 = p; ++n1; }
+            else third = true;
+        }
+        if (n1 == 0) continue;
+        if (third || (n0 != 1 && n1 != 1) || w.lanes < 3) {
+            std::fprintf(stderr, "lane_emu: the lanes hold more than one lane's own value of shared word %zu at a "
+                                 "__syncthreads() (%d / %d lanes): a race in the device code\n", k, n0, n1);
+            std::abort();
+        }
+        const unsigned long long v = n1 == 1 ? v1 : v0;
+        for (int i = 0; i < w.lanes; ++i) w.copy[i][k] = v;
+    }
+    barrier();
+}
+}  // namespace optik_emu
+#define __builtin_amdgcn_readlane(v, src) optik_emu::readlane((v), (src))
+// (called under wave-uniform control flow only, like every collective here: the first active lane is lane 0)
+#define __builtin_amdgcn_readfirstlane(v) optik_emu::readlane((v), 0)
+inline void __syncthreads() { optik_emu::sync_threads(); }
 
 // ---- the DPP moves and lane counters of optik_amd/csrc/ik_lane.hpp, under their device names -------------------
 // __builtin_amdgcn_update_dpp(old, v, dpp_ctrl, row_mask, bank_mask, bound_ctrl) with a quad_perm control (dpp_ctrl
@@ -171,6 +251,7 @@ inline int __double2loint(double d) { return (int)(optik_emu::to_bits(d) & 0xfff
 inline double __hiloint2double(int hi, int lo) {
     return optik_emu::from_bits<double>(((unsigned long long)(unsigned)hi << 32) | (unsigned long long)(unsigned)lo);
 }
+inline long long __double_as_longlong(double d) { return (long long)optik_emu::to_bits(d); }
 inline double __longlong_as_double(long long v) { return optik_emu::from_bits<double>((unsigned long long)v); }
 inline unsigned long long wall_clock64() { return 0ull; }
 

@@ -58,7 +58,7 @@ NOT_REQUIRED = {
 REQUIRED = tuple(k for k in ANCHORS if k not in NOT_REQUIRED)
 # Reached only on the way to the evaluation cap, so only by entries the GPU never runs.
 CAP_ONLY = ("line_search_nonfinite", "evaluation_cap")
-EMU_RESTARTS = 16  # of each n <= 8 entry's range, from its begin: what the host emulation of the tuned kernels runs
+EMU_RESTARTS = 16  # of each entry's range, from its begin: what the host emulations (tests/emu) of the solvers run
 
 
 def emu_window(sc):

@@ -13,7 +13,9 @@ import pytest
 import solver_edge_util as u
 
 RES_FAILURE, RES_ROUNDOFF, RES_FTOL, RES_XTOL, RES_ITER_CAP = -1, -4, 3, 4, -100
-EMULATED = ("n<=7", "n=8")  # the groups the host emulation takes (tests/test_quad_emulation_solver_edge.py)
+# the groups the host emulation takes (tests/test_quad_emulation_solver_edge.py; n >= 9: the general solver,
+# tests/test_wide_emulation_solver_edge.py)
+EMULATED = ("n<=7", "n=8", "n>=9")
 
 
 @pytest.fixture(scope="module")
@@ -69,9 +71,10 @@ def test_each_group_alone_takes_every_required_branch(census, group):
 
 @pytest.mark.parametrize("group", EMULATED)
 def test_the_emulated_windows_alone_take_every_required_branch(census, group):
-    """tests/test_quad_emulation_solver_edge.py compares the first EMU_RESTARTS restarts of every n <= 8 entry: those
-    windows alone take every required branch, also the ones no status names (rnorm <= 0 against the LDP's dual test,
-    NNLS's rejected column, the relaxed x test, the repaired t)."""
+    """tests/test_quad_emulation_solver_edge.py compares the first EMU_RESTARTS restarts of every n <= 8 entry, and
+    tests/test_wide_emulation_solver_edge.py those of every n >= 9 entry on the general solver: those windows alone
+    take every required branch, also the ones no status names (rnorm <= 0 against the LDP's dual test, NNLS's
+    rejected column, the relaxed x test, the repaired t) and the two on the way to the evaluation cap."""
     counts = census[group + " emu"][1]
     missed = [k for k in u.REQUIRED if counts[k][0] == 0]
     assert not missed, f"the emulated windows of group {group} never take {missed}"
