@@ -4,7 +4,7 @@
 //
 // The solvers are launched from here and defined in their own translation units: the lane-per-restart form
 // (ik_lane_kernel.hip), the quad solver (ik_quad_kernel.hip), the general run-time-n solver (ik_wide_kernel.hip);
-// optik_hip_ik_batch picks one by launch size and joint count.  The key pass of solution modes 3 and 4: ik_manip.hip;
+// which one a launch gets, and its grid, is plan_launch's decision (ik_launch_plan.hpp).  The key pass of solution modes 3 and 4: ik_manip.hip;
 // that of the collision filter: ik_collision.hip.
 // The selection kernels: ik_select.hip,
 // ik_solutions.hip and ik_path.hip; the batch operators: ik_batch_ops.hip.  No CPU fallback exists: every entry point fails loudly without a device.
@@ -50,15 +50,39 @@ namespace {
 
 int default_range_rule() { return opt().range_rule; }
 
-void set_chain_scales(optik_hip_chain *ch, int rule) {
+// ch->scale under `rule` (a wide chain's table holds a copy: fill_wide_chain)
+void set_chain_scales(optik_hip_chain *ch, const double *lb, const double *ub, int rule) {
     ch->range_rule = rule;
-    for (int k = 0; k < ch->n; ++k) {
-        const double lb = ch->wide ? ch->whost.lb[k] : ch->host.lb[k], ub = ch->wide ? ch->whost.ub[k] : ch->host.ub[k];
-        // infinite limits (continuous joints) make random_range panic in the
-        // reference (quirk Q5); restarts > 0 are refused at launch time instead.
-        ch->scale[k] = (std::isfinite(lb) && std::isfinite(ub)) ? uniform_scale(lb, ub, rule) : NAN;
-        if (ch->wide) ch->whost.scale[k] = ch->scale[k];
-    }
+    // infinite limits (continuous joints) make random_range panic in the
+    // reference (quirk Q5); restarts > 0 are refused at launch time instead.
+    for (int k = 0; k < ch->n; ++k)
+        ch->scale[k] = (std::isfinite(lb[k]) && std::isfinite(ub[k])) ? uniform_scale(lb[k], ub[k], rule) : NAN;
+}
+
+// The chain table of either layout (ChainDev: n <= 8, the tuned solvers; WideChainDev: the general kernels) from
+// origins [n + tip][7], axes [n][3] and the limits [n].
+template <class Table>
+void fill_chain_table(Table &t, const double *origins, const double *axes, const double *lb, const double *ub, int n,
+                      bool tip) {
+    std::memset(&t, 0, sizeof t);
+    t.n_pos = n;
+    t.has_tip = tip;
+    std::memcpy(t.origin, origins, sizeof(double) * 7 * (size_t)(n + (tip ? 1 : 0)));
+    std::memcpy(t.axis, axes, sizeof(double) * 3 * (size_t)n);
+    std::memcpy(t.lb, lb, sizeof(double) * (size_t)n);
+    std::memcpy(t.ub, ub, sizeof(double) * (size_t)n);
+}
+// the general kernels' table: the restart scales are part of it
+void fill_wide_chain(WideChainDev &w, const double *origins, const double *axes, const double *lb, const double *ub,
+                     int n, bool tip, const double *scales) {
+    fill_chain_table(w, origins, axes, lb, ub, n, tip);
+    std::memcpy(w.scale, scales, sizeof(double) * (size_t)n);
+}
+// a table to its device block, allocated at the first upload
+template <class Table>
+hipError_t upload_table(Table **dev, const Table &host) {
+    hipError_t e = *dev ? hipSuccess : hipMalloc(dev, sizeof(Table));
+    return e == hipSuccess ? hipMemcpy(*dev, &host, sizeof(Table), hipMemcpyHostToDevice) : e;
 }
 
 }  // namespace
@@ -96,58 +120,28 @@ int optik_hip_chain_create(const double *origins, const double *axes, const int3
     std::memset(&ch->host, 0, sizeof ch->host);
     std::memset(&ch->whost, 0, sizeof ch->whost);
     ch->n = n;
+    ch->n_joints = n_joints;
+    ch->tip = (n_joints == n + 1);
+    set_chain_scales(ch, lb, ub, default_range_rule());
+    seed_from_u64(42, ch->key);  // RNG_SEED, lib.rs:360
+    hipError_t e;
     if (n > MAX_DOF) {
         // 9 .. 16 joint positions: the general kernels of ik_wide.hpp (one table, joint count at run time)
         ch->wide = true;
-        ch->n_joints = n_joints;
-        ch->tip = (n_joints == n + 1);
-        WideChainDev &w = ch->whost;
-        w.n_pos = n;
-        w.has_tip = ch->tip;
-        for (int j = 0; j < n_joints; ++j)
-            for (int k = 0; k < 7; ++k) w.origin[j][k] = origins[j * 7 + k];
-        for (int j = 0; j < n; ++j)
-            for (int k = 0; k < 3; ++k) w.axis[j][k] = axes[j * 3 + k];
-        for (int k = 0; k < n; ++k) { w.lb[k] = lb[k]; w.ub[k] = ub[k]; }
-        set_chain_scales(ch, default_range_rule());
-        seed_from_u64(42, ch->key);  // RNG_SEED, lib.rs:360
-        hipError_t e = hipMalloc(&ch->wdev, sizeof(WideChainDev));
-        if (e == hipSuccess) e = hipMemcpy(ch->wdev, &ch->whost, sizeof(WideChainDev), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            if (ch->wdev) (void)hipFree(ch->wdev);
-            delete ch;
-            return fail(OPTIK_HIP_ENODEVICE, std::string("chain upload: ") + hipGetErrorString(e));
+        fill_wide_chain(ch->whost, origins, axes, lb, ub, n, ch->tip, ch->scale);
+        e = upload_table(&ch->wdev, ch->whost);
+    } else {
+        ch->prismatic = prismatic;
+        for (int j = 0; j < n_joints; ++j) {
+            ch->types[j] = types[j];
+            for (int k = 0; k < 3; ++k) ch->axis_all[j][k] = axes[j * 3 + k];
         }
-        int dev = 0;
-        hipGetDevice(&dev);
-        ch->device_id = dev;
-        hipDeviceGetAttribute(&ch->num_cus, hipDeviceAttributeMultiprocessorCount, dev);
-        hipDeviceGetAttribute(&ch->wall_clock_khz, hipDeviceAttributeWallClockRate, dev);
-        *out = ch;
-        return 0;
+        fill_chain_table(ch->host, origins, axes, lb, ub, n, ch->tip);
+        e = upload_table(&ch->dev, ch->host);
     }
-    ch->prismatic = prismatic;
-    ch->n_joints = n_joints;
-    for (int j = 0; j < n_joints; ++j) {
-        ch->types[j] = types[j];
-        for (int k = 0; k < 3; ++k) ch->axis_all[j][k] = axes[j * 3 + k];
-    }
-    ch->tip = (n_joints == n + 1);
-    ch->host.n_pos = n;
-    ch->host.has_tip = ch->tip;
-    for (int j = 0; j < n_joints; ++j)
-        for (int k = 0; k < 7; ++k) ch->host.origin[j][k] = origins[j * 7 + k];
-    for (int j = 0; j < n; ++j)
-        for (int k = 0; k < 3; ++k) ch->host.axis[j][k] = axes[j * 3 + k];
-    for (int k = 0; k < n; ++k) {
-        ch->host.lb[k] = lb[k];
-        ch->host.ub[k] = ub[k];
-    }
-    set_chain_scales(ch, default_range_rule());
-    seed_from_u64(42, ch->key);  // RNG_SEED, lib.rs:360
-    hipError_t e = hipMalloc(&ch->dev, sizeof(ChainDev));
-    if (e == hipSuccess) e = hipMemcpy(ch->dev, &ch->host, sizeof(ChainDev), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
+        if (ch->dev) (void)hipFree(ch->dev);
+        if (ch->wdev) (void)hipFree(ch->wdev);
         delete ch;
         return fail(OPTIK_HIP_ENODEVICE, std::string("chain upload: ") + hipGetErrorString(e));
     }
@@ -183,10 +177,11 @@ int optik_hip_chain_set_range_rule(optik_hip_chain *ch, int32_t rule) {
     if (!ch || (rule != OPTIK_HIP_RANGE_SINGLE_INCLUSIVE && rule != OPTIK_HIP_RANGE_NEW_INCLUSIVE))
         return fail(OPTIK_HIP_EINVAL, "bad argument");
     std::lock_guard<std::mutex> lock(ch->mu);
-    set_chain_scales(ch, rule);
+    set_chain_scales(ch, ch->wide ? ch->whost.lb : ch->host.lb, ch->wide ? ch->whost.ub : ch->host.ub, rule);
     if (ch->wide) {  // (the scales of a wide chain are part of its device table)
         BIND_DEVICE(ch);
-        HIP_TRY(hipMemcpy(ch->wdev, &ch->whost, sizeof(WideChainDev), hipMemcpyHostToDevice));
+        std::memcpy(ch->whost.scale, ch->scale, sizeof(double) * (size_t)ch->n);
+        HIP_TRY(upload_table(&ch->wdev, ch->whost));
     }
     return 0;
 }
@@ -205,74 +200,18 @@ struct SolvedLaunch {
     bool early;               // the launch used the first-success words
 };
 
+// The launch's selection kernel has put the work-item counter and the first-success words back: what a launch queued
+// behind it on `stream` may rely on.
+static void words_put_back(optik_hip_chain *ch, const SolvedLaunch &sl, hipStream_t stream) {
+    ch->queue_clean = true;
+    ch->fs_clean = sl.fs_clean_after;
+    ch->clean_stream = stream;
+}
+
 // The solver half of optik_hip_ik_batch and optik_hip_ik_solutions, with the chain's launch mutex held: argument
 // checks, workspace, the solver choice and its launch.  want_sel: a selection stage follows (the per-restart keys go
 // to scratch; need_x / need_f: it reads x / f, scratch for what the caller does not provide).  The selection stage
-// has to put the work-item counter (and, with sl->early, the first-success words) back and then set queue_clean /
-// fs_clean / clean_stream.
-static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, const double *d_targets,
-                        const double *d_x0, int32_t T, const double *ee_offset7, uint64_t restart_begin,
-                        uint64_t restart_end, uint32_t flags, double deadline_s, const optik_hip_ik_outputs *out,
-                        bool want_sel, bool need_x, bool need_f, hipStream_t stream, bool claim_request,
-                        bool *claim_armed, SolvedLaunch *sl);
-
-// optik_hip_ik_batch with the chain's launch mutex already held.
-static int ik_batch_locked(optik_hip_chain *ch, const optik_solver_config *cfg, const double *d_targets,
-                           const double *d_x0, int32_t T, const double *ee_offset7, uint64_t restart_begin,
-                           uint64_t restart_end, uint32_t flags, double deadline_s, const optik_hip_ik_outputs *out,
-                           void *stream_v, bool claim_request = false, bool *claim_armed = nullptr);
-
-extern "C" {
-
-int optik_hip_ik_batch(optik_hip_chain *ch, const optik_solver_config *cfg, const double *d_targets,
-                       const double *d_x0, int32_t T, const double *ee_offset7, uint64_t restart_begin,
-                       uint64_t restart_end, uint32_t flags, double deadline_s, const optik_hip_ik_outputs *out,
-                       void *stream_v) {
-    if (!ch) return fail(OPTIK_HIP_EINVAL, "bad argument");
-    std::lock_guard<std::mutex> lock(ch->mu);
-    return ik_batch_locked(ch, cfg, d_targets, d_x0, T, ee_offset7, restart_begin, restart_end, flags, deadline_s, out,
-                           stream_v);
-}
-
-}  // extern "C"
-
-static int ik_batch_locked(optik_hip_chain *ch, const optik_solver_config *cfg, const double *d_targets,
-                           const double *d_x0, int32_t T, const double *ee_offset7, uint64_t restart_begin,
-                           uint64_t restart_end, uint32_t flags, double deadline_s, const optik_hip_ik_outputs *out,
-                           void *stream_v, bool claim_request, bool *claim_armed) {
-    if (claim_armed) *claim_armed = false;
-    if (!out) return fail(OPTIK_HIP_EINVAL, "bad argument");
-    hipStream_t stream = (hipStream_t)stream_v;
-    const bool want_win = out->d_win_x || out->d_win_f || out->d_win_idx || out->d_win_key;
-    SolvedLaunch sl;
-    if (int rc = solve_locked(ch, cfg, d_targets, d_x0, T, ee_offset7, restart_begin, restart_end, flags, deadline_s,
-                              out, want_win, out->d_win_x != nullptr, out->d_win_f != nullptr, stream, claim_request,
-                              claim_armed, &sl))
-        return rc;
-    BIND_DEVICE(ch);
-    if (want_win) {
-        SelectLaunch s;
-        std::memset(&s, 0, sizeof s);
-        s.out_key = sl.pk; s.out_x = sl.px; s.out_f = sl.pf;
-        s.tile_recs = ch->tile_recs.get();
-        s.tiles_per_target = (int)sl.tiles_per_target;
-        s.tile = SEL_TILE;
-        s.n = ch->n;
-        s.restart_begin = restart_begin;
-        s.n_restarts = sl.R;
-        s.ld = sl.cols;
-        s.win_x = out->d_win_x; s.win_f = out->d_win_f;
-        s.win_idx = (unsigned long long *)out->d_win_idx; s.win_key = out->d_win_key;
-        s.reset_queue = ch->queue;
-        s.reset_fs = sl.early ? ch->first_success.get() : nullptr;
-        HIP_TRY(select_launch(s, T, stream));
-        ch->queue_clean = true;
-        ch->fs_clean = sl.fs_clean_after;
-        ch->clean_stream = stream;
-    }
-    return 0;
-}
-
+// has to put the work-item counter (and, with sl->early, the first-success words) back and then say so: words_put_back.
 static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, const double *d_targets,
                         const double *d_x0, int32_t T, const double *ee_offset7, uint64_t restart_begin,
                         uint64_t restart_end, uint32_t flags, double deadline_s, const optik_hip_ik_outputs *out,
@@ -297,28 +236,33 @@ static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, con
     if (ch->prismatic)
         return fail(OPTIK_HIP_EUNSUPPORTED,
                     "prismatic joints: only forward kinematics is available (the reference's Jacobian panics, kinematics.rs:185)");
+
+    // the plan: which solver, how many restarts per wave and in flight, the grid (ik_launch_plan.hpp)
+    PlanIn in{};
+    in.n = ch->n; in.wide = ch->wide; in.cus = ch->num_cus;
+    in.T = T; in.R = R; in.flags = flags; in.mode = mode; in.coll = coll;
+    in.solve_kernel = opt().solve_kernel; in.wide_form = opt().wide_form;
+    in.claim_request = claim_request; in.have_claim_block = ch->hw_claim != nullptr;
+    in.lane_waves = lane_solve_waves_per_cu(); in.quad_waves = quad_solve_waves_per_cu(ch->n);
+    in.latency_waves = 4; in.wide_waves = 8;  // one wave per SIMD; two
+    const LaunchPlan plan = plan_launch(in);
+    if (plan.error == PLAN_TOO_MANY_TILES)
+        return fail(OPTIK_HIP_EINVAL, "too many restarts / targets in one launch (2^24 or more selection tiles)");
+    const bool early = plan.early, wide_lds = plan.solver == WIDE_LDS, widek = wide_lds || plan.solver == WIDE_HBM;
+    const size_t cols = (size_t)plan.cols;
+
+    // the workspace
     BIND_DEVICE(ch);
     // (a single call that returned on its first success may have left its launch running on the null stream: a
     // launch on another stream shares the chain's workspace with it and waits; on the null stream it queues behind)
     // (on the null stream the flag stays: optik_hip_ik_host's staged path still has to know)
     if (ch->claim_pending && stream != nullptr) { HIP_TRY(hipStreamSynchronize(nullptr)); ch->claim_pending = false; }
-
-    // selection tiles: 4096 restarts per 256-thread block
-    const uint64_t tiles_per_target = (R + SEL_TILE - 1) / SEL_TILE;
-    const uint64_t n_tiles64 = tiles_per_target * (uint64_t)T;
-    // (HIP rejects a launch whose grid.x * block.x reaches 2^32: 256-thread tile blocks cap the tiles at 2^24 - 1)
-    if (n_tiles64 * 256ull >= (1ull << 32))
-        return fail(OPTIK_HIP_EINVAL, "too many restarts / targets in one launch (2^24 or more selection tiles)");
-    const int n_tiles = (int)n_tiles64;
-    const size_t cols = (size_t)T * (size_t)R;
-
-    HIP_TRY(ch->tile_recs.reserve((size_t)n_tiles));
+    HIP_TRY(ch->tile_recs.reserve((size_t)plan.n_tiles));
     if (!ch->queue) { HIP_TRY(hipMalloc(&ch->queue, sizeof(unsigned long long))); ch->queue_clean = false; }
     // (the words are only known to be clean to a launch queued behind the selection kernel that cleaned them)
     if (stream != ch->clean_stream) { ch->queue_clean = false; ch->fs_clean = 0; }
     if (!ch->queue_clean) HIP_TRY(hipMemsetAsync(ch->queue, 0, sizeof(unsigned long long), stream));
     ch->queue_clean = false;  // (until this launch's selection kernel has put it back)
-    const bool early = (flags & OPTIK_HIP_IK_EARLY_EXIT) && mode == OPTIK_MODE_SPEED && !coll;
     size_t fs_clean_after = ch->fs_clean;  // (a launch without early exit leaves the words alone)
     if (early) {
         if ((size_t)T > ch->first_success.capacity()) ch->fs_clean = 0;  // (a new block: no word of it is clean)
@@ -349,6 +293,16 @@ static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, con
         if (!pf && need_f) pf = ch->tmp_f.get();
     }
 
+    if (widek && !ch->wide) {
+        // the chain's table in the general kernels' layout (uploaded per call: a test path)
+        fill_wide_chain(ch->whost, &ch->host.origin[0][0], &ch->host.axis[0][0], ch->host.lb, ch->host.ub, ch->n, ch->tip,
+                        ch->scale);
+        HIP_TRY(upload_table(&ch->wdev, ch->whost));
+    }
+    // (the general solver's HBM form: every resident wave with its own block of the restart workspace, ik_wide.hpp)
+    if (plan.solver == WIDE_HBM) HIP_TRY(ch->wide_ws.reserve(wide_ws_doubles_per_wave() * (size_t)plan.grid));
+
+    // the launch
     SolveLaunch a;
     std::memset(&a, 0, sizeof a);
     a.chain = ch->dev;  // (null for a wide chain: its launch takes ch->wdev)
@@ -363,114 +317,32 @@ static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, con
     a.wq.targets = d_targets;
     a.wq.x0 = d_x0;
     a.wq.first_success = early ? ch->first_success.get() : nullptr;
-    a.wq.find_any = (early && (flags & OPTIK_HIP_IK_FIND_ANY)) ? 1 : 0;
-    a.wq.claim = nullptr;
-    a.wq.claim_seq = 0;
-    a.wq.restart_major = (flags & OPTIK_HIP_IK_RESTART_MAJOR) ? 1 : 0;
+    a.wq.find_any = plan.find_any ? 1 : 0;
+    a.wq.restart_major = plan.restart_major ? 1 : 0;
     a.wq.n_targets = (unsigned long long)T;
-    a.wq.deadline = 0;
-    a.wq.quality = (mode != OPTIK_MODE_SPEED);  // (modes 3 and 4: Quality's keys, replaced by the key pass below)
+    a.wq.quality = plan.quality;
+    a.wq.lanes = plan.lanes;
     a.wq.out_x = px;
     a.wq.out_f = pf;
     a.wq.out_key = pk;
     a.wq.out_status = out->d_status;
     a.wq.out_evals = out->d_evals;
-    a.wq.prof = nullptr;
 #ifdef OPTIK_PROFILE
     if (!ch->prof) HIP_TRY(hipMalloc(&ch->prof, 8 * sizeof(unsigned long long)));
     HIP_TRY(hipMemsetAsync(ch->prof, 0, 8 * sizeof(unsigned long long), stream));
     a.wq.prof = ch->prof;
 #endif
-    a.deadline_ticks = 0;
     if (deadline_s > 0.0) {
         const double khz = ch->wall_clock_khz > 0 ? (double)ch->wall_clock_khz : 100000.0;
         a.deadline_ticks = (unsigned long long)(deadline_s * khz * 1e3);
         if (a.deadline_ticks == 0) a.deadline_ticks = 1;
     }
-
-    // Which solver (option solve_kernel; same results, bit for bit): the quad solver of ik_quad.hpp (a restart per
-    // quad of lanes, its state spread over the quad, NNLS matrix in LDS; n <= 8), from one full load of the chip
-    // on the lane-per-restart form of ik_lane64.hpp (n <= 7), or -- `general` -- the run-time-n solver of
-    // ik_wide.hpp on a chain of at most 8 joints too: a third, independently written device solver for the parity
-    // tests; chains of 9 .. 16 joints always run on it.
-    const int sk = opt().solve_kernel;
-    bool widek = ch->wide || sk == SK_GENERAL;
-    if (widek && !ch->wide) {
-        // the chain's table in the general kernels' layout (uploaded per call: a test path)
-        WideChainDev &w = ch->whost;
-        std::memset(&w, 0, sizeof w);
-        w.n_pos = ch->n;
-        w.has_tip = ch->tip;
-        for (int j = 0; j < ch->n + (ch->tip ? 1 : 0); ++j)
-            for (int k = 0; k < 7; ++k) w.origin[j][k] = ch->host.origin[j][k];
-        for (int j = 0; j < ch->n; ++j) {
-            for (int k = 0; k < 3; ++k) w.axis[j][k] = ch->host.axis[j][k];
-            w.lb[j] = ch->host.lb[j]; w.ub[j] = ch->host.ub[j]; w.scale[j] = ch->scale[j];
-        }
-        if (!ch->wdev) HIP_TRY(hipMalloc(&ch->wdev, sizeof(WideChainDev)));
-        HIP_TRY(hipMemcpy(ch->wdev, &w, sizeof(WideChainDev), hipMemcpyHostToDevice));
-    }
-    const bool quadk = !widek;
-    // the throughput form for n <= 7: one restart per lane, bounded sub-problems in class order (ik_lane64.hpp)
-    // (the default from one full load of the chip on -- 64 restarts for each of its four waves per CU: below that a
-    // launch is as long as its longest restart, and the quad solver's trip is the shorter one; lane_vs_quad_probe.py (a rounds 3-5 tool: git history))
-    bool lanek = quadk && ch->n <= 7 && sk != SK_QUAD;
-    const bool lane_forced = lanek && sk == SK_LANE64;
-    // Persistent waves, each pulling work items until the queue is dry: as many as a CU holds
-    // (lane kernel: 2 workgroups, LDS-bound; cooperative kernel: 4, one per SIMD), times the CU count.
-    const int cus = ch->num_cus > 0 ? ch->num_cus : 256;
-    // (quad solver: a launch with no more work items than the chip has SIMDs runs one restart per wave on the
-    // one-wave-per-SIMD build -- no scratch, the lowest latency per iteration; anything bigger on the
-    // two-waves-per-SIMD build)
-    const long long wide_waves_per_cu = 8;  // resident waves per CU of the general solver (two per SIMD)
-    const bool quad_latency = quadk && (long long)cols <= (long long)cus * 4 && !lane_forced;
-    // (not for a Speed batch's latency-sized rounds: restart-major hand-out with early exit keeps a few restarts per
-    // target in flight and abandons most of the rest -- the quad solver's shorter trip wins there)
-    lanek = lanek && !quad_latency
-            && (lane_forced || ((long long)cols >= (long long)cus * lane_solve_waves_per_cu() * 64
-                                && !(early && (flags & OPTIK_HIP_IK_RESTART_MAJOR))));
-    long long cap = (long long)cus * (lanek ? lane_solve_waves_per_cu() : quadk ? (quad_latency ? 4 : quad_solve_waves_per_cu(ch->n)) : wide_waves_per_cu);
-    const long long per_wave_max = (quadk && !lanek) ? QUADS_PER_WAVE_HOST : WAVE;
-    // fewer work items than the chip holds: one restart per wave (or as few as fit).  A
-    // restart-major Speed batch keeps about eight restarts per target in flight: the waves pull
-    // the higher indices of the targets still unsolved as they go
-    long long resident = (long long)cols;
-    // (but never fewer than one restart per resident wave: a small batch has the chip to itself, and
-    // the more of a target's restarts run at once the sooner its first success comes)
-    const long long inflight = 8;  // restarts per target in flight
-    // (a few targets have the chip to themselves: two restarts per resident wave at least, 32 per
-    // target up to 256 targets -- measured: 64 targets 1.01 -> 0.79 ms, 256: 1.66 -> 1.47 ms, and the
-    // few hundred targets a big batch's first round leaves over 8 ms sooner)
-    if (early && (flags & OPTIK_HIP_IK_RESTART_MAJOR) && resident > (long long)T * inflight) {
-        const long long floor_res = std::max(2 * cap, (long long)T * 32);
-        resident = std::max((long long)T * inflight, std::min(resident, floor_res));
-    }
-    long long lanes = (resident + cap - 1) / cap;
-    if (lanes < 1) lanes = 1;
-    if (lanes > per_wave_max) lanes = per_wave_max;
-    // The general solver's two forms (ik_wide.hpp): one restart per wave with its arrays in LDS and the wave's 64
-    // lanes working on it together, or a restart per lane with the HBM workspace.  The first has the short
-    // dependent chain and no HBM traffic, the second 64 times the restarts in flight -- and the first wins at
-    // every size and joint count measured (wide_chain_bench.py (a rounds 3-5 tool: git history), 262 144 restarts: 1.31 / 0.88 / 0.83 / 1.26 M
-    // restarts/s at 9 / 10 / 12 / 16 joints against 1.05 / 0.66 / 0.42 / 0.40 M; a launch on the HBM form takes
-    // 50 - 100 ms however small it is).  Option wide_form = hbm selects the HBM form (tests, comparisons).
-    bool wide_lds = false;
-    if (widek) {
-        wide_lds = opt().wide_form != 1;
-        if (wide_lds) lanes = 1;
-    }
-    a.wq.lanes = (int)lanes;
-    // a single call under the first-success rule on the quad solver: the first success goes to the host at once
-    if (claim_request && quadk && !lanek && a.wq.find_any && T == 1 && ch->hw_claim) {
+    if (plan.arm_claim) {
         a.wq.claim = ch->hw_claim;
         a.wq.claim_seq = ++ch->claim_seq;
         if (claim_armed) *claim_armed = true;
         if (stream == nullptr) ch->claim_pending = true;  // (the caller may return before this launch has ended)
     }
-    long long grid_ll = (resident + lanes - 1) / lanes;
-    if (grid_ll > cap) grid_ll = cap;
-    const int grid = (int)grid_ll;
-
     const int ev_slot = ch->ev_count % optik_hip_chain::EV_POOL;
     if (ch->timing) {
         if (!ch->ev0[ev_slot]) { HIP_TRY(hipEventCreate(&ch->ev0[ev_slot])); HIP_TRY(hipEventCreate(&ch->ev1[ev_slot])); }
@@ -478,11 +350,8 @@ static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, con
     }
     int lds = 0;
     if (widek) {
-        // 9 .. 16 joint positions: one restart per lane on the general kernel, eight waves per CU, every
-        // resident wave with its own block of the restart workspace (ik_wide.hpp)
-        // (one restart per wave -- a single ik() call's rounds --: the restart's arrays in the wave's LDS)
-        const bool lds_form = wide_lds;
-        if (!lds_form) HIP_TRY(ch->wide_ws.reserve(wide_ws_doubles_per_wave() * (size_t)grid));
+        // the general kernel, eight waves per CU: one restart per wave with its arrays in the wave's LDS -- a single
+        // ik() call's rounds --, or one per lane on the HBM workspace
         WideSolveLaunch w;
         std::memset(&w, 0, sizeof w);
         w.chain = ch->wdev;
@@ -490,14 +359,13 @@ static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, con
         std::memcpy(w.key, ch->key, sizeof w.key);
         w.deadline_ticks = a.deadline_ticks;
         w.ws = ch->wide_ws.get();
-        lds = lds_form ? wide_lds_bytes() : (int)sizeof(WideChainDev);
-        HIP_TRY(wide_solve_launch(grid, stream, w, lds_form, opt().wide_form != 2));
-    } else if (lanek) {
-        HIP_TRY(lane_solve_launch(ch->n, ch->tip, grid, stream, a, &lds));
-    } else if (quadk) {
-        HIP_TRY(quad_solve_launch(ch->n, ch->tip, grid, stream, a, &lds, quad_latency));
+        lds = wide_lds ? wide_lds_bytes() : (int)sizeof(WideChainDev);
+        HIP_TRY(wide_solve_launch(plan.grid, stream, w, wide_lds, opt().wide_form != 2));
+    } else if (plan.solver == LANE) {
+        HIP_TRY(lane_solve_launch(ch->n, ch->tip, plan.grid, stream, a, &lds));
+    } else {
+        HIP_TRY(quad_solve_launch(ch->n, ch->tip, plan.grid, stream, a, &lds, plan.solver == QUAD_LATENCY));
     }
-    else return fail(OPTIK_HIP_EUNSUPPORTED, "no solver for this chain in this build");
     HIP_TRY(hipGetLastError());
     if (ch->timing) { HIP_TRY(hipEventRecord(ch->ev1[ev_slot], stream)); ch->ev_count += 1; }
     // modes 3 and 4: the successes' keys become -w / -c, on the same stream, before any selection kernel
@@ -506,18 +374,64 @@ static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, con
     // the collision filter: the successes that are not free get key +inf, behind the key pass above
     if (coll && pk)
         if (int rc = collision_key_launch(ch, ee_offset7, px, pk, cols, stream)) return rc;
-    ch->last.grid = grid; ch->last.block = WAVE; ch->last.lds_bytes = lds; ch->last.tiles = n_tiles;
+    ch->last.grid = plan.grid; ch->last.block = WAVE; ch->last.lds_bytes = lds; ch->last.tiles = plan.n_tiles;
 
     sl->px = px; sl->pf = pf; sl->pk = pk;
     sl->R = R;
-    sl->tiles_per_target = tiles_per_target;
+    sl->tiles_per_target = plan.tiles_per_target;
     sl->cols = cols;
     sl->fs_clean_after = fs_clean_after;
     sl->early = early;
     return 0;
 }
 
+// optik_hip_ik_batch with the chain's launch mutex already held.
+static int ik_batch_locked(optik_hip_chain *ch, const optik_solver_config *cfg, const double *d_targets,
+                           const double *d_x0, int32_t T, const double *ee_offset7, uint64_t restart_begin,
+                           uint64_t restart_end, uint32_t flags, double deadline_s, const optik_hip_ik_outputs *out,
+                           void *stream_v, bool claim_request = false, bool *claim_armed = nullptr) {
+    if (claim_armed) *claim_armed = false;
+    if (!out) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    hipStream_t stream = (hipStream_t)stream_v;
+    const bool want_win = out->d_win_x || out->d_win_f || out->d_win_idx || out->d_win_key;
+    SolvedLaunch sl;
+    if (int rc = solve_locked(ch, cfg, d_targets, d_x0, T, ee_offset7, restart_begin, restart_end, flags, deadline_s,
+                              out, want_win, out->d_win_x != nullptr, out->d_win_f != nullptr, stream, claim_request,
+                              claim_armed, &sl))
+        return rc;
+    BIND_DEVICE(ch);
+    if (want_win) {
+        SelectLaunch s;
+        std::memset(&s, 0, sizeof s);
+        s.out_key = sl.pk; s.out_x = sl.px; s.out_f = sl.pf;
+        s.tile_recs = ch->tile_recs.get();
+        s.tiles_per_target = (int)sl.tiles_per_target;
+        s.tile = SEL_TILE;
+        s.n = ch->n;
+        s.restart_begin = restart_begin;
+        s.n_restarts = sl.R;
+        s.ld = sl.cols;
+        s.win_x = out->d_win_x; s.win_f = out->d_win_f;
+        s.win_idx = (unsigned long long *)out->d_win_idx; s.win_key = out->d_win_key;
+        s.reset_queue = ch->queue;
+        s.reset_fs = sl.early ? ch->first_success.get() : nullptr;
+        HIP_TRY(select_launch(s, T, stream));
+        words_put_back(ch, sl, stream);
+    }
+    return 0;
+}
+
 extern "C" {
+
+int optik_hip_ik_batch(optik_hip_chain *ch, const optik_solver_config *cfg, const double *d_targets,
+                       const double *d_x0, int32_t T, const double *ee_offset7, uint64_t restart_begin,
+                       uint64_t restart_end, uint32_t flags, double deadline_s, const optik_hip_ik_outputs *out,
+                       void *stream_v) {
+    if (!ch) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    std::lock_guard<std::mutex> lock(ch->mu);
+    return ik_batch_locked(ch, cfg, d_targets, d_x0, T, ee_offset7, restart_begin, restart_end, flags, deadline_s, out,
+                           stream_v);
+}
 
 int optik_hip_ik_solutions(optik_hip_chain *ch, const optik_solver_config *cfg, const double *d_targets,
                            const double *d_x0, int32_t T, const double *ee_offset7, uint64_t restart_begin,
@@ -555,9 +469,7 @@ int optik_hip_ik_solutions(optik_hip_chain *ch, const optik_solver_config *cfg, 
     s.idx = (unsigned long long *)out->d_idx; s.key = out->d_key;
     s.reset_queue = ch->queue;
     HIP_TRY(solutions_launch(s, T, stream));
-    ch->queue_clean = true;
-    ch->fs_clean = sl.fs_clean_after;
-    ch->clean_stream = stream;
+    words_put_back(ch, sl, stream);
     return 0;
 }
 
@@ -625,9 +537,7 @@ int optik_hip_ik_path(optik_hip_chain *ch, const optik_solver_config *cfg, const
         s.reset_queue = ch->queue;
         s.reset_fs = sl.early ? ch->first_success.get() : nullptr;
         HIP_TRY(path_select_launch(s, P, stream));
-        ch->queue_clean = true;
-        ch->fs_clean = sl.fs_clean_after;
-        ch->clean_stream = stream;
+        words_put_back(ch, sl, stream);
     }
     return 0;
 }
@@ -635,27 +545,24 @@ int optik_hip_ik_path(optik_hip_chain *ch, const optik_solver_config *cfg, const
 /* Tuning options (tests, tools): see `struct Options` (ik_host.hpp).  Names: solve_kernel (0 auto, 1 quad, 2 lane64,
  * 3 general), wide_form (0 lds, 1 hbm), range_rule (of chains created afterwards), stop_x_legacy.  Not synchronised
  * with calls in flight. */
-static long long *option_slot(const char *name, int **islot) {
+static int *option_slot(const char *name) {
     Options &o = opt();
-    *islot = nullptr;
     if (!name) return nullptr;
-    if (!std::strcmp(name, "solve_kernel")) { *islot = &o.solve_kernel; return nullptr; }
-    if (!std::strcmp(name, "wide_form")) { *islot = &o.wide_form; return nullptr; }
-    if (!std::strcmp(name, "range_rule")) { *islot = &o.range_rule; return nullptr; }
-    if (!std::strcmp(name, "stop_x_legacy")) { *islot = &o.stop_x_legacy; return nullptr; }
+    if (!std::strcmp(name, "solve_kernel")) return &o.solve_kernel;
+    if (!std::strcmp(name, "wide_form")) return &o.wide_form;
+    if (!std::strcmp(name, "range_rule")) return &o.range_rule;
+    if (!std::strcmp(name, "stop_x_legacy")) return &o.stop_x_legacy;
     return nullptr;
 }
 int optik_hip_set_option(const char *name, long long value) {
-    int *is = nullptr;
-    long long *ls = option_slot(name, &is);
-    if (ls) { *ls = value; return 0; }
-    if (is) { *is = (int)value; return 0; }
-    return fail(OPTIK_HIP_EINVAL, "unknown option");
+    int *slot = option_slot(name);
+    if (!slot) return fail(OPTIK_HIP_EINVAL, "unknown option");
+    *slot = (int)value;
+    return 0;
 }
 long long optik_hip_get_option(const char *name) {
-    int *is = nullptr;
-    long long *ls = option_slot(name, &is);
-    return ls ? *ls : (is ? (long long)*is : -1);
+    const int *slot = option_slot(name);
+    return slot ? (long long)*slot : -1;
 }
 
 int optik_hip_ik_host(optik_hip_chain *ch, const optik_solver_config *cfg, const double *targets,
@@ -728,28 +635,25 @@ int optik_hip_ik_host(optik_hip_chain *ch, const optik_solver_config *cfg, const
     double *h_out = pin + n_in;
     if (!zero_copy) HIP_TRY(hipMemcpyAsync(h_out, d_wx, sizeof(double) * n_out, hipMemcpyDeviceToHost, nullptr));
     if (armed) {
-        volatile unsigned long long *cw = ch->hw_claim;
+        // this launch's first success is in the claim block: it goes to the caller's win_*
+        auto claimed = [&]() {
+            if (__atomic_load_n(ch->hw_claim, __ATOMIC_ACQUIRE) != seq) return false;
+            volatile unsigned long long *cw = ch->hw_claim;
+            if (win_x) std::memcpy(win_x, (const void *)(cw + 3), sizeof(double) * (size_t)n);
+            if (win_f) std::memcpy(win_f, (const void *)(cw + 2), sizeof(double));
+            if (win_idx) *win_idx = cw[1];
+            if (win_key) *win_key = (double)cw[1];
+            return true;
+        };
         for (unsigned spin = 1;; ++spin) {
-            if (__atomic_load_n(ch->hw_claim, __ATOMIC_ACQUIRE) == seq) {
-                if (win_x) std::memcpy(win_x, (const void *)(cw + 3), sizeof(double) * (size_t)n);
-                if (win_f) std::memcpy(win_f, (const void *)(cw + 2), sizeof(double));
-                if (win_idx) *win_idx = cw[1];
-                if (win_key) *win_key = (double)cw[1];
-                return 0;  // (claim_pending stays set: the launch ends behind the caller's back)
-            }
+            if (claimed()) return 0;  // (claim_pending stays set: the launch ends behind the caller's back)
             if ((spin & 63u) == 0) {
                 const hipError_t q = hipEventQuery(ch->claim_done);
                 if (q == hipSuccess) break;  // the launch is over and nobody succeeded (or the word is about to land)
                 if (q != hipErrorNotReady) HIP_TRY(q);
             }
         }
-        if (__atomic_load_n(ch->hw_claim, __ATOMIC_ACQUIRE) == seq) {
-            if (win_x) std::memcpy(win_x, (const void *)(cw + 3), sizeof(double) * (size_t)n);
-            if (win_f) std::memcpy(win_f, (const void *)(cw + 2), sizeof(double));
-            if (win_idx) *win_idx = cw[1];
-            if (win_key) *win_key = (double)cw[1];
-            return 0;
-        }
+        if (claimed()) return 0;
     }
     HIP_TRY(hipStreamSynchronize(nullptr));
     if (armed) {

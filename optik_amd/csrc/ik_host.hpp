@@ -2,6 +2,7 @@
 // options, error reporting and the (n, trailing fixed joint) dispatch.
 //
 //   ik_capi.hip        chains, options, optik_hip_ik_batch / optik_hip_ik_host, timing (the C ABI of optik_hip.h)
+//   ik_launch_plan.hpp which solver a restart launch runs on and its grid: plan_launch, plain C++ (the one place)
 //   ik_select.hip      the selection of lib.rs:397-413 over the per-restart keys
 //   ik_solutions.hip   up to K distinct solutions per target over the same keys (optik_hip_ik_solutions)
 //   ik_path.hip        the per-waypoint selection of warm-started paths (optik_hip_ik_path)
@@ -25,6 +26,7 @@
 #include "device_scope.hpp"
 #include "ik_host_params.hpp"
 #include "ik_launch.hpp"
+#include "ik_launch_plan.hpp"
 #include "ik_wide_launch.hpp"
 
 namespace optik {
@@ -33,8 +35,9 @@ struct ModelDev;  // collision_model.hpp
 }  // namespace coll
 namespace host {
 
-constexpr int WAVE = 64;
-constexpr int QUADS_PER_WAVE_HOST = 16;  // restarts a wave of the quad solver holds
+static_assert(PLAN_EARLY_EXIT == OPTIK_HIP_IK_EARLY_EXIT && PLAN_FIND_ANY == OPTIK_HIP_IK_FIND_ANY
+                  && PLAN_RESTART_MAJOR == OPTIK_HIP_IK_RESTART_MAJOR && PLAN_MODE_SPEED == OPTIK_MODE_SPEED,
+              "ik_launch_plan.hpp reads the flags and modes of optik_hip.h");
 
 // ---- selection (ik_select.hip) -----------------------------------------------------------------------------
 struct TileRec {
@@ -63,7 +66,6 @@ struct SelectLaunch {
     unsigned long long *reset_queue;
     unsigned long long *reset_fs;  // [T]
 };
-constexpr int SEL_TILE = 4096;  // restarts per 256-thread selection block
 static_assert(OPTIK_HIP_PATH_MAX_RESTARTS <= SEL_TILE, "ik_path selects each path's restarts in one block");
 // per-tile argmin + per-target reduction (one kernel when a target has a single tile); T blocks publish the winners
 hipError_t select_launch(const SelectLaunch &s, int T, hipStream_t stream);
@@ -144,10 +146,9 @@ int motion_key_launch(const optik_hip_chain *ch, const double *ee_offset7, const
 // Every tuning option of the kernel layer, in one place.  The defaults come from the environment ONCE, at the
 // first use (the OPTIK_* names below); tests and tools change them through optik_hip_set_option (optik_hip.h).
 // Nothing else in this library reads the environment (robot_host.hpp: OPTIK_HOST_THREADS, robot_host.cpp: OPTIK_DEVICES).
-enum : int { SK_AUTO = 0, SK_QUAD = 1, SK_LANE64 = 2, SK_GENERAL = 3 };
 struct Options {
     int solve_kernel = SK_AUTO;      // OPTIK_SOLVE_KERNEL = quad | lane64 | general: which single-launch solver (auto: by size)
-    int wide_form = 0;               // OPTIK_WIDE_FORM = lds | hbm: the general solver's form (9 .. 16 joints); 2: one-lane LDS form
+    int wide_form = WF_LDS;              // OPTIK_WIDE_FORM = lds | hbm: the general solver's form (9 .. 16 joints); 2: one-lane LDS form
     int range_rule = OPTIK_HIP_RANGE_SINGLE_INCLUSIVE;  // OPTIK_RANDOM_RANGE_RULE = new_inclusive: rand 0.9.2 reading of new chains
     int stop_x_legacy = 0;           // (no environment name) nlopt_stop_x of NLopt 2.5: no zero-step rule
 };
