@@ -205,6 +205,27 @@ int optik_robot_link_frames_batch(const optik_robot *robot, int64_t B, const dou
 /* x [B][n] -> clearance_out [B], free_out [B] (1 iff clearance >= margin); either may be NULL.  rc 0 or -1. */
 int optik_robot_collision_batch(const optik_robot *robot, int64_t B, const double *x, const double *ee_offset16,
                                 double *clearance_out, uint8_t *free_out);
+/* Which way is out (extension; include/optik_hip.h: optik_hip_collision_witness_batch).  x [B][n] -> per
+ * configuration the F = n + 2 witness rows, row-major: dist_out [B][F], grad_out [B][F][n], witness_out [B][F][3]
+ * (robot sphere, kind, index); any may be NULL.  On the robot's first device; rc 0, or -1: null argument, more than
+ * 8 joint positions, prismatic joints. */
+int optik_robot_collision_witness_batch(const optik_robot *robot, int64_t B, const double *x,
+                                        const double *ee_offset16, double *dist_out, double *grad_out,
+                                        int32_t *witness_out);
+/* Collision-avoiding diff_ik (extension; include/optik_hip.h: optik_hip_diff_ik_avoid_batch): optik_robot_diff_ik_ex
+ * with a velocity damper for each of the (up to 4) closest frames within `influence` of an obstacle or of another
+ * link.  rc 0 = solved, 1 = none (also: the dampers cannot be met within v_max; alpha and v are then zero), -1 =
+ * refused: what optik_robot_diff_ik_ex refuses, and unless influence > safety >= 0 and gain > 0, all finite.
+ * The single call is the batch with B = 1 (one launch of the fused kernel on the robot's first device), so row b of
+ * optik_robot_diff_ik_avoid_batch returns its bits.  Without a collision model both return what
+ * optik_robot_diff_ik_ex / _batch return, bit for bit. */
+int optik_robot_diff_ik_avoid(const optik_robot *robot, const double *x0, const double *V_WE6, const double *v_max,
+                              double influence, double safety, double gain, const double *ee_offset16,
+                              double *alpha_out, double *v_out);
+int optik_robot_diff_ik_avoid_batch(const optik_robot *robot, int64_t B, const double *x0, const double *V_WE6,
+                                    const double *v_max, double influence, double safety, double gain,
+                                    const double *ee_offset16, double *alpha_out, double *v_out,
+                                    int32_t *status_out);
 /* The motion check (extension; include/optik_hip.h: optik_hip_collision_motion_batch and what precedes it).  B segments
  * xa, xb [B][n] row-major at `resolution` (finite, > 0) -> clearance_out [B], free_out [B], first_out [B], steps_out
  * [B]; any may be NULL (clearance_out NULL: the call only classifies).  On the robot's first device, 65 536 segments

@@ -140,6 +140,38 @@ int optik_hip_diff_ik_batch(const optik_hip_chain *chain, const double *ee_offse
                             const double *d_V, int64_t ld_V, const double *d_vmax, int64_t ld_vmax,
                             int64_t B, double *d_alpha, double *d_v, int32_t *d_status, void *stream);
 
+/* Which way is out (extension; the arithmetic: csrc/collision_gradient.hpp).  For B
+ * configurations d_q [n][B] of a chain with a collision model, the witness table of each: one row per frame f of its
+ * F = n + 2 frames, the smallest term of the clearance that belongs to frame f (the robot spheres on f against the
+ * world spheres, boxes and grid; the self pairs whose higher frame is f; ties to the first in that order).
+ * d_dist [F][B] that term's distance (the minimum over f is optik_hip_collision_batch's clearance bit for bit),
+ * d_witness [F][3][B] int32 (robot sphere, kind, index) in the numbering the model and world were given in -- kind 0
+ * world sphere, 1 box, 2 grid (index 0), 3 self pair (robot sphere a, index of the pair) --, d_grad [F][n][B] the
+ * derivative of the distance with respect to the joint positions.  Any output may be NULL.  A row without a term (and
+ * every row of a chain without a model): dist +inf, grad 0, witness -1.  A configuration with a NaN frame: dist and
+ * grad NaN, witness -1 in every row.  One thread per configuration, no workspace, no allocation.
+ * OPTIK_HIP_EUNSUPPORTED, also when B = 0: prismatic joints, and chains of 9 .. 16 joint positions (not in this
+ * version). */
+int optik_hip_collision_witness_batch(const optik_hip_chain *chain, const double *ee_offset7, const double *d_q,
+                                      int64_t B, double *d_dist, double *d_grad, int32_t *d_witness, void *stream);
+
+/* Collision-avoiding diff_ik: optik_hip_diff_ik_batch (same arguments, same layout) with velocity dampers (Faverjon
+ * and Tournassoud 1987).  Every witness row with a finite dist < influence adds the half-space
+ *     grad . v >= -gain * (dist - safety) / (influence - safety)
+ * to the LP -- at most OPTIK_HIP_MAX_DAMPER_ROWS of them, the closest, ties to the lower frame (csrc/diff_ik_lp.hpp:
+ * diff_ik_lp_damped).  A term at `influence` may approach at `gain` m/s, a term at `safety` not at all, a term
+ * inside `safety` must recede.  d_status: 0 solved; 1 no solution (a bad v_max, a NaN frame of a chain with a model,
+ * or dampers that no velocity within the limits satisfies) with alpha and v zero.  A chain without a model, and a row
+ * with nothing inside `influence`, gets the bits of optik_hip_diff_ik_batch.  One fused kernel, no workspace, no
+ * allocation.
+ * OPTIK_HIP_EINVAL unless influence > safety >= 0 and gain > 0, all finite.  OPTIK_HIP_EUNSUPPORTED, also when B = 0:
+ * as optik_hip_diff_ik_batch (more than 8 joint positions -- 9 .. 16 are not in this version --, prismatic joints). */
+#define OPTIK_HIP_MAX_DAMPER_ROWS 4
+int optik_hip_diff_ik_avoid_batch(const optik_hip_chain *chain, const double *ee_offset7, const double *d_q,
+                                  const double *d_V, int64_t ld_V, const double *d_vmax, int64_t ld_vmax, int64_t B,
+                                  double influence, double safety, double gain, double *d_alpha, double *d_v,
+                                  int32_t *d_status, void *stream);
+
 /* The measures of solution modes 3 and 4 for B configurations d_q [n][B] (any chain of 1 .. 16 revolute joint
  * positions): d_w [B] manipulability w = sqrt(det G), d_c [B] condition c = sigma_min / sigma_max, both of the body
  * Jacobian fk_batch returns (ee_offset7 may be NULL).  Either output may be NULL.  A G that is not numerically

@@ -139,6 +139,9 @@ def lib():
     L.optik_hip_collision_motion_batch.argtypes = [vp, dp, vp, vp, C.c_int64, C.c_double, vp, vp, vp, vp, vp]
     L.optik_hip_chain_set_motion_resolution.argtypes = [vp, C.c_double]
     L.optik_hip_diff_ik_batch.argtypes = [vp, dp, vp, vp, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, vp, vp]
+    L.optik_hip_collision_witness_batch.argtypes = [vp, dp, vp, C.c_int64, vp, vp, vp, vp]
+    L.optik_hip_diff_ik_avoid_batch.argtypes = [vp, dp, vp, vp, C.c_int64, vp, C.c_int64, C.c_int64, C.c_double,
+                                                C.c_double, C.c_double, vp, vp, vp, vp]
     L.optik_hip_ik_batch.argtypes = [vp, C.POINTER(SolverConfigC), vp, vp, C.c_int32, dp,
                                      C.c_uint64, C.c_uint64, C.c_uint32, C.c_double,
                                      C.POINTER(IkOutputs), vp]

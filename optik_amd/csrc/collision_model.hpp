@@ -162,9 +162,11 @@ inline int check_cloud(int64_t N, int32_t E, std::string &err) {
 
 inline const char *bake_empty_msg() { return "world grid bake: the world has no spheres and no boxes"; }
 
-// The device layout of a checked model; returns the number of pair groups.
+// The device layout of a checked model; returns the number of pair groups.  `orig` (optional) receives the way back
+// from the layout to the caller's numbering, S + P entries: the caller's index of the sphere in slot i, then the
+// caller's index of the pair at position i (the witnesses of optik_hip_collision_witness_batch speak the caller's).
 inline int pack_model(int n, const int32_t *frames, const double *centers3, const double *radii, int32_t S,
-                      const int32_t *pairs2, int32_t P, ModelDev &m) {
+                      const int32_t *pairs2, int32_t P, ModelDev &m, std::vector<uint16_t> *orig = nullptr) {
     std::memset(&m, 0, sizeof m);
     const int nf = n + 2;
     std::vector<int> order((size_t)S), slot((size_t)S);
@@ -199,6 +201,11 @@ inline int pack_model(int n, const int32_t *frames, const double *centers3, cons
     }
     const int groups = g + 1;
     m.group_begin[groups] = (uint16_t)P;
+    if (orig) {
+        orig->resize((size_t)S + (size_t)P);
+        for (int i = 0; i < S; ++i) (*orig)[(size_t)i] = (uint16_t)order[(size_t)i];
+        for (int i = 0; i < P; ++i) (*orig)[(size_t)S + (size_t)i] = (uint16_t)porder[(size_t)i];
+    }
     return groups;
 }
 

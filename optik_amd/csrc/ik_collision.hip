@@ -194,9 +194,13 @@ int optik_hip_chain_set_collision_model(optik_hip_chain *ch, const int32_t *fram
         return 0;
     }
     std::vector<ModelDev> packed(1);
-    const int groups = coll::pack_model(ch->n, frames, centers3, radii, S, pairs2, P, packed[0]);
+    std::vector<uint16_t> orig;
+    const int groups = coll::pack_model(ch->n, frames, centers3, radii, S, pairs2, P, packed[0], &orig);
+    ch->coll_S = 0;  // (no model until both uploads are through: never old counts over new data)
     if (!ch->coll_dev) HIP_TRY(hipMalloc(&ch->coll_dev, sizeof(ModelDev)));
     HIP_TRY(hipMemcpy(ch->coll_dev, packed.data(), sizeof(ModelDev), hipMemcpyHostToDevice));
+    HIP_TRY(ch->coll_orig.reserve(orig.size()));
+    HIP_TRY(hipMemcpy(ch->coll_orig.get(), orig.data(), sizeof(uint16_t) * orig.size(), hipMemcpyHostToDevice));
     ch->coll_S = S; ch->coll_P = P; ch->coll_groups = groups; ch->coll_margin = margin;
     return 0;
 }

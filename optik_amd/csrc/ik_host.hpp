@@ -9,6 +9,7 @@
 //   ik_manip.hip       the manipulability / condition keys of solution modes 3 and 4, optik_hip_manip_batch
 //   ik_collision.hip   the collision filter: model and world, its key pass, link frames and clearance batches
 //   ik_motion.hip      the motion check: segments between configurations, the motion key pass of optik_hip_ik_path
+//   ik_avoid.hip       clearance witnesses and gradients, collision-avoiding diff_ik (velocity dampers)
 //   ik_occupancy.hip   occupancy grids and point clouds into distance-field worlds (distance transform, voxelize)
 //   ik_batch_ops.hip   objective / gradient, FK / Jacobian and seed batches, the test probes
 //   ik_lane_kernel.hip, ik_quad_kernel.hip, ik_wide_kernel.hip    the restart solvers (one restart loop each)
@@ -241,6 +242,8 @@ struct optik_hip_chain {
     int coll_S = 0, coll_P = 0, coll_groups = 0;
     double coll_margin = 0.0;
     optik::coll::ModelDev *coll_dev = nullptr;
+    // [coll_S + coll_P]: the caller's sphere / pair index of each slot of coll_dev (ik_avoid.hip)
+    optik::DeviceBuf<uint16_t> coll_orig;
     optik::DeviceBuf<double> world_dev;
     int world_Ms = 0, world_Mb = 0;
     // the distance-field world (optik_hip_chain_set_world_grid): float32 [nx][ny][nz]; null: no grid

@@ -1,6 +1,6 @@
-// robot_rows.cpp -- the row batches of the host API (diff_ik, manipulability, link frames, clearance, motion), each
-// one stage_rows over the robot's first device, and what they are checked against: the collision model, the worlds
-// and their builders.  (robot_host.hpp: the robot object and the shared plumbing.)
+// robot_rows.cpp -- the row batches of the host API (diff_ik, manipulability, link frames, clearance, witnesses,
+// motion), each one stage_rows over the robot's first device, and what they are checked against: the collision
+// model, the worlds and their builders.  (robot_host.hpp: the robot object and the shared plumbing.)
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -19,6 +19,7 @@ namespace {
 
 constexpr int64_t kRowChunk = (int64_t)1 << 18;     // rows per launch
 constexpr int64_t kMotionChunk = (int64_t)1 << 16;  // segments per launch (each is many samples)
+constexpr int64_t kWitnessChunk = (int64_t)1 << 15;  // rows per launch of the witness table (840 B a row at n = 8: 28 MB)
 
 }  // namespace
 
@@ -290,6 +291,99 @@ int optik_robot_collision_batch(const optik_robot *r, int64_t B, const double *x
             if (clearance_out) std::memcpy(clearance_out + b0, h_out, sizeof(double) * L);
             if (free_out) std::memcpy(free_out + b0, reinterpret_cast<const uint8_t *>(h_out + L), L);
         });
+}
+
+// The witness table of B configurations (optik_hip_collision_witness_batch), rows staged as the clearance's are.
+int optik_robot_collision_witness_batch(const optik_robot *r, int64_t B, const double *x, const double *ee16,
+                                        double *dist_out, double *grad_out, int32_t *witness_out) {
+    if (!r || !x) return set_err(-1, "null argument");
+    if (B < 0) return set_err(-1, "bad argument");
+    DeviceCtx *c0 = device_ctx(r);
+    if (!c0) return -1;
+    if (optik_hip_collision_witness_batch(c0->chain, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (B == 0 || (!dist_out && !grad_out && !witness_out)) return 0;
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    const size_t n = (size_t)r->n, nf = n + 2;
+    // per row: dist F | grad F n doubles, then the witness words F 3 int32 out
+    const RowInput in[] = {{x, n}};
+    return stage_rows(
+        c0, B, in, sizeof(double) * (nf + nf * n) + sizeof(int32_t) * 3 * nf, kWitnessChunk,
+        [&](optik_hip_chain *ch, const double *d_q, int64_t L, double *d_out) {
+            double *d_grad = d_out + nf * (size_t)L;
+            return optik_hip_collision_witness_batch(ch, ee16 ? ee7 : nullptr, d_q, L, d_out, d_grad,
+                                                     reinterpret_cast<int32_t *>(d_grad + nf * n * (size_t)L), nullptr);
+        },
+        [&](size_t b0, size_t L, const double *h_out) {
+            const double *h_grad = h_out + nf * L;
+            const int32_t *h_wit = reinterpret_cast<const int32_t *>(h_grad + nf * n * L);
+            parallel_ranges(L, [&](size_t k0, size_t k1) {
+                for (size_t k = k0; k < k1; ++k) {
+                    const size_t row = b0 + k;
+                    for (size_t f = 0; f < nf; ++f) {
+                        if (dist_out) dist_out[row * nf + f] = h_out[f * L + k];
+                        if (grad_out)
+                            for (size_t j = 0; j < n; ++j)
+                                grad_out[(row * nf + f) * n + j] = h_grad[(f * n + j) * L + k];
+                        if (witness_out)
+                            for (size_t i = 0; i < 3; ++i)
+                                witness_out[(row * nf + f) * 3 + i] = h_wit[(f * 3 + i) * L + k];
+                    }
+                }
+            });
+        });
+}
+
+// B collision-avoiding diff_ik calls (optik_hip_diff_ik_avoid_batch), staged as optik_robot_diff_ik_batch stages its
+// rows.  The single call is this with B = 1: one launch, the same kernel, so a row of a batch has its bits.
+int optik_robot_diff_ik_avoid_batch(const optik_robot *r, int64_t B, const double *x0, const double *V_WE,
+                                    const double *v_max, double influence, double safety, double gain,
+                                    const double *ee16, double *alpha_out, double *v_out, int32_t *status_out) {
+    if (!r || !x0 || !V_WE || !v_max) return set_err(-1, "null argument");
+    if (B < 0) return set_err(-1, "bad argument");
+    const int n = r->n;
+    if (n > 8) return set_err(-1, kDiffIkMaxNMsg);
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    // (B = 0: the kernel layer's refusals of the chain and of influence / safety / gain, before anything is staged)
+    if (optik_hip_diff_ik_avoid_batch(c->chain, nullptr, nullptr, nullptr, 0, nullptr, 0, 0, influence, safety, gain,
+                                      nullptr, nullptr, nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (B == 0) return 0;
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    const RowInput in[] = {{x0, (size_t)n}, {V_WE, 6}, {v_max, (size_t)n}};
+    return stage_rows(
+        c, B, in, sizeof(double) * (size_t)(n + 1) + sizeof(int32_t), kRowChunk,
+        [&](optik_hip_chain *ch, const double *d_q, int64_t L, double *d_a) {
+            const double *d_V = d_q + (size_t)n * L, *d_vm = d_V + 6 * L;
+            double *d_v = d_a + L;
+            return optik_hip_diff_ik_avoid_batch(ch, ee16 ? ee7 : nullptr, d_q, d_V, L, d_vm, L, L, influence, safety,
+                                                 gain, d_a, d_v, reinterpret_cast<int32_t *>(d_v + (size_t)n * L),
+                                                 nullptr);
+        },
+        [&](size_t b0, size_t L, const double *h_a) {
+            const double *h_v = h_a + L;
+            const int32_t *h_st = reinterpret_cast<const int32_t *>(h_v + (size_t)n * L);
+            parallel_ranges(L, [&](size_t k0, size_t k1) {
+                for (size_t k = k0; k < k1; ++k) {
+                    const size_t row = b0 + k;
+                    if (alpha_out) alpha_out[row] = h_a[k];
+                    if (v_out) for (int i = 0; i < n; ++i) v_out[row * n + i] = h_v[(size_t)i * L + k];
+                    if (status_out) status_out[row] = h_st[k];
+                }
+            });
+        });
+}
+
+int optik_robot_diff_ik_avoid(const optik_robot *r, const double *x0, const double *V_WE, const double *v_max,
+                              double influence, double safety, double gain, const double *ee16, double *alpha_out,
+                              double *v_out) {
+    int32_t status = 0;
+    const int rc = optik_robot_diff_ik_avoid_batch(r, 1, x0, V_WE, v_max, influence, safety, gain, ee16, alpha_out,
+                                                   v_out, &status);
+    return rc < 0 ? rc : status;
 }
 
 int optik_robot_set_motion_resolution(optik_robot *r, double h) {

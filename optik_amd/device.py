@@ -105,6 +105,38 @@ class HipChain:
             _ptr(v_max), B if v_max.dim() == 2 else 0, B, _ptr(alpha), _ptr(v), _ptr(status), _stream_ptr()))
         return alpha, v, status
 
+    def diff_ik_avoid_batch(self, q, V, v_max, influence, safety, gain=1.0, ee_offset7=None):
+        """diff_ik_batch with velocity dampers against the chain's collision model and world (optik_hip.h:
+        optik_hip_diff_ik_avoid_batch): the same arguments and returns; status 1 also where the dampers cannot be
+        met."""
+        assert q.is_cuda and q.dtype == torch.float64 and q.dim() == 2 and q.shape[0] == self.n and q.is_contiguous()
+        B = q.shape[1]
+        for t, rows in ((V, 6), (v_max, self.n)):
+            assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.device == q.device
+            assert tuple(t.shape) in ((rows,), (rows, B)), f"expected [{rows}] or [{rows}, {B}], got {tuple(t.shape)}"
+        alpha = torch.empty(B, dtype=torch.float64, device=q.device)
+        v = torch.empty((self.n, B), dtype=torch.float64, device=q.device)
+        status = torch.empty(B, dtype=torch.int32, device=q.device)
+        ee = np.ascontiguousarray(ee_offset7, dtype=np.float64) if ee_offset7 is not None else None
+        nat.check(nat.lib().optik_hip_diff_ik_avoid_batch(
+            self._h, _dp(ee) if ee is not None else None, _ptr(q), _ptr(V), B if V.dim() == 2 else 0,
+            _ptr(v_max), B if v_max.dim() == 2 else 0, B, float(influence), float(safety), float(gain),
+            _ptr(alpha), _ptr(v), _ptr(status), _stream_ptr()))
+        return alpha, v, status
+
+    def collision_witness_batch(self, q, ee_offset7=None):
+        """The witness table of every column of q [n, B] (optik_hip.h: optik_hip_collision_witness_batch):
+        (dist [n + 2, B], grad [n + 2, n, B], witness [n + 2, 3, B] int32).  Stream-ordered."""
+        assert q.is_cuda and q.dtype == torch.float64 and q.dim() == 2 and q.shape[0] == self.n and q.is_contiguous()
+        B, F = q.shape[1], self.n + 2
+        dist = torch.empty((F, B), dtype=torch.float64, device=q.device)
+        grad = torch.empty((F, self.n, B), dtype=torch.float64, device=q.device)
+        wit = torch.empty((F, 3, B), dtype=torch.int32, device=q.device)
+        ee = np.ascontiguousarray(ee_offset7, dtype=np.float64) if ee_offset7 is not None else None
+        nat.check(nat.lib().optik_hip_collision_witness_batch(self._h, _dp(ee) if ee is not None else None, _ptr(q), B,
+                                                              _ptr(dist), _ptr(grad), _ptr(wit), _stream_ptr()))
+        return dist, grad, wit
+
     def manip_batch(self, q, ee_offset7=None):
         """The measures of solution modes "manipulability" / "condition" for every column of q [n, B] (float64 cuda
         tensor): (w [B], c [B]) -- w = product of the min(n, 6) largest singular values of the body Jacobian, c =

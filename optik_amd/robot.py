@@ -56,6 +56,11 @@ def _bind(L):
     L.optik_robot_set_motion_resolution.argtypes = [vp, C.c_double]
     L.optik_robot_diff_ik_ex.argtypes = [vp, dp, dp, dp, dp, C.POINTER(C.c_double), dp]
     L.optik_robot_diff_ik_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_int32)]
+    L.optik_robot_collision_witness_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.POINTER(C.c_int32)]
+    L.optik_robot_diff_ik_avoid.argtypes = [vp, dp, dp, dp, C.c_double, C.c_double, C.c_double, dp,
+                                            C.POINTER(C.c_double), dp]
+    L.optik_robot_diff_ik_avoid_batch.argtypes = [vp, C.c_int64, dp, dp, dp, C.c_double, C.c_double, C.c_double, dp,
+                                                  dp, dp, C.POINTER(C.c_int32)]
     L.optik_robot_joint_jacobian_ex.argtypes = [vp, dp, dp, dp]
     L.optik_robot_set_devices.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32]
     L.optik_robot_num_devices.argtypes = [vp]
@@ -129,6 +134,11 @@ class SolverConfig:
                                0 if self.max_restarts >= U64_MAX else self.max_restarts,
                                self.tol_f, self.tol_df, self.tol_dx, self.linear_weight,
                                self.angular_weight)
+
+
+def _check_damper(influence, safety, gain):
+    if not (np.isfinite([influence, safety, gain]).all() and influence > safety >= 0.0 and gain > 0.0):
+        raise ValueError("diff_ik_avoid: needs influence > safety >= 0 and gain > 0, all finite")
 
 
 class Robot:
@@ -440,6 +450,69 @@ class Robot:
         alpha, v, found = self.diff_ik_batch_arrays(x0s, V_WE, v_max, ee_offset)
         al, vs = alpha.tolist(), v.tolist()
         return [(al[b], vs[b]) if ok else None for b, ok in enumerate(found.tolist())]
+
+    def diff_ik_avoid(self, x0, V_WE, v_max, influence, safety, gain=1.0, ee_offset=None):
+        """diff_ik() that does not drive into obstacles (extension): with the robot's collision model and world, every
+        frame whose closest term is within `influence` adds the velocity damper grad . v >= -gain * (dist - safety) /
+        (influence - safety) to the LP (the 4 closest frames at most).  Returns (alpha, v), or None when no velocity
+        within v_max meets the dampers (a configuration already inside `safety` that cannot back out).  Without a
+        collision model it returns what diff_ik() returns, bit for bit.  ValueError unless influence > safety >= 0
+        and gain > 0, all finite."""
+        x0 = self._check_x(x0)
+        n = self.num_positions()
+        V = np.ascontiguousarray(V_WE, dtype=np.float64).reshape(6)
+        vm = np.ascontiguousarray(v_max, dtype=np.float64).reshape(n)
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        _check_damper(influence, safety, gain)
+        alpha, v = C.c_double(0.0), np.zeros(n)
+        rc = self._L.optik_robot_diff_ik_avoid(self._h, _dp(x0), _dp(V), _dp(vm), influence, safety, gain,
+                                               _dp(ee) if ee is not None else None, C.byref(alpha), _dp(v))
+        if rc < 0:
+            raise RuntimeError(_err(self._L))
+        if rc == 1:
+            return None
+        return alpha.value, v.tolist()
+
+    def diff_ik_avoid_batch_arrays(self, x0s, V_WE, v_max, influence, safety, gain=1.0, ee_offset=None):
+        """Many diff_ik_avoid() calls at once, array form, as diff_ik_batch_arrays: -> (alpha [B], v [B, n], found [B]
+        bool); row b is what diff_ik_avoid(x0s[b], V_WE[b], v_max[b], ...) returns, bit for bit."""
+        n = self.num_positions()
+        x0s = np.asarray(x0s, dtype=np.float64)
+        if x0s.ndim != 2 or x0s.shape[1] != n:
+            raise ValueError("x0s must be [B, n]")
+        B = x0s.shape[0]
+        x0s = np.ascontiguousarray(x0s)
+        V = np.ascontiguousarray(np.broadcast_to(np.asarray(V_WE, dtype=np.float64), (B, 6)))
+        vm = np.ascontiguousarray(np.broadcast_to(np.asarray(v_max, dtype=np.float64), (B, n)))
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        _check_damper(influence, safety, gain)
+        alpha, v = np.zeros(B), np.zeros((B, n))
+        status = np.zeros(B, dtype=np.int32)
+        rc = self._L.optik_robot_diff_ik_avoid_batch(self._h, B, _dp(x0s), _dp(V), _dp(vm), influence, safety, gain,
+                                                     _dp(ee) if ee is not None else None, _dp(alpha), _dp(v),
+                                                     status.ctypes.data_as(C.POINTER(C.c_int32)))
+        if rc < 0:
+            raise RuntimeError(_err(self._L))
+        return alpha, v, status == 0
+
+    def collision_witness_batch_arrays(self, xs, ee_offset=None):
+        """Which term gives each frame its clearance, and which way is out (extension): `xs` [B, n] -> (dist [B, n + 2],
+        grad [B, n + 2, n], witness [B, n + 2, 3] int32).  Row f of a configuration is the smallest term of the
+        clearance on frame f: its distance, d dist / d q, and (robot sphere, kind, index) with kind 0 world sphere,
+        1 box, 2 grid, 3 self pair (robot sphere a, index of the pair).  dist.min(axis=1) is the clearance of
+        collision_clearance_batch_arrays bit for bit; a frame without a term has dist +inf, grad 0, witness -1."""
+        n = self.num_positions()
+        xs = np.ascontiguousarray(xs, dtype=np.float64)
+        if xs.ndim != 2 or xs.shape[1] != n:
+            raise ValueError("xs must be [B, n]")
+        B = xs.shape[0]
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        dist, grad = np.zeros((B, n + 2)), np.zeros((B, n + 2, n))
+        wit = np.zeros((B, n + 2, 3), dtype=np.int32)
+        if self._L.optik_robot_collision_witness_batch(self._h, B, _dp(xs), _dp(ee) if ee is not None else None,
+                                                       _dp(dist), _dp(grad), wit.ctypes.data_as(C.POINTER(C.c_int32))):
+            raise RuntimeError(_err(self._L))
+        return dist, grad, wit
 
     def manipulability_batch_arrays(self, xs, ee_offset=None):
         """The measures of solution modes "manipulability" and "condition" (extension) for B configurations:
