@@ -226,6 +226,14 @@ int optik_robot_diff_ik_avoid_batch(const optik_robot *robot, int64_t B, const d
                                     const double *v_max, double influence, double safety, double gain,
                                     const double *ee_offset16, double *alpha_out, double *v_out,
                                     int32_t *status_out);
+/* Bending paths out of collision (extension; include/optik_hip.h: optik_hip_path_optimize).  paths [P][L][n]
+ * row-major, 3 <= L <= 64 -> paths_out [P][L][n] (may be `paths`), cost_first_out and cost_last_out [P][3] = (U,
+ * F_smooth, F_obs), clearance_out [P], status_out [P] (0, or 1: the last cost is NaN); any output may be NULL.  On the
+ * robot's first device; rc 0, or -1: null argument, what optik_hip_path_optimize refuses. */
+int optik_robot_path_optimize(const optik_robot *robot, int64_t P, int32_t L, const double *paths, int32_t iters,
+                              double step, double w_smooth, double w_obs, double influence, double safety,
+                              const double *ee_offset16, double *paths_out, double *cost_first_out,
+                              double *cost_last_out, double *clearance_out, int32_t *status_out);
 /* The motion check (extension; include/optik_hip.h: optik_hip_collision_motion_batch and what precedes it).  B segments
  * xa, xb [B][n] row-major at `resolution` (finite, > 0) -> clearance_out [B], free_out [B], first_out [B], steps_out
  * [B]; any may be NULL (clearance_out NULL: the call only classifies).  On the robot's first device, 65 536 segments

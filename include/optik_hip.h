@@ -172,6 +172,31 @@ int optik_hip_diff_ik_avoid_batch(const optik_hip_chain *chain, const double *ee
                                   double influence, double safety, double gain, double *d_alpha, double *d_v,
                                   int32_t *d_status, void *stream);
 
+/* Bending paths out of collision (extension; the arithmetic and its operation order:
+ * csrc/path_optimize.hpp): covariant gradient smoothing, after CHOMP, of P joint-space paths of L waypoints each,
+ * 3 <= L <= OPTIK_HIP_PATH_OPTIMIZE_MAX_WAYPOINTS.  d_q_in [L][P][n] -- the layout optik_hip_ik_path writes its
+ * waypoint solutions d_x in, so its output is handed over as it is.  The first and the last waypoint never move.
+ * Each of `iters` updates steps every free waypoint by -step * Ainv * g from the same iterate, g the gradient of
+ *     U = w_smooth * F_smooth + w_obs * F_obs,
+ * F_smooth half the sum of the squared segment lengths, F_obs the sum over the free waypoints and their n + 2 witness
+ * rows (optik_hip_collision_witness_batch) of a hinge of dist - safety that reaches zero at `influence`, Ainv the
+ * inverse of the first-difference metric; then clamps to the chain's joint limits.  One more evaluation follows the
+ * last update: iters + 1 in all; iters = 0 copies the path and reports its costs.
+ * d_q_out [L][P][n] the final waypoints (may be d_q_in); d_cost_first, d_cost_last [P][3] = (U, F_smooth, F_obs) at
+ * the first and at the last iterate; d_clearance [P] the smallest witness distance over all L waypoints of the last
+ * iterate (+inf without a model, NaN with a NaN frame); d_status [P] int32: 0, or 1 when the last cost is NaN.  Any
+ * output may be NULL.  A chain without a model has F_obs = 0: the path relaxes towards the straight line.
+ * One wave per path, the whole loop in one launch; stream-ordered, no workspace, no allocation.  K updates in one
+ * call give the bits of K calls of one update, whatever P is.
+ * OPTIK_HIP_EINVAL before any device work: L outside 3 .. 64, P < 0 (P = 0: nothing to do), iters < 0, or unless
+ * step > 0, w_smooth >= 0, w_obs >= 0 and influence > safety >= 0, all finite.  OPTIK_HIP_EUNSUPPORTED, also when
+ * P = 0: prismatic joints, and chains of 9 .. 16 joint positions (not in this version). */
+#define OPTIK_HIP_PATH_OPTIMIZE_MAX_WAYPOINTS 64
+int optik_hip_path_optimize(const optik_hip_chain *chain, const double *ee_offset7, const double *d_q_in, int32_t L,
+                            int64_t P, int32_t iters, double step, double w_smooth, double w_obs, double influence,
+                            double safety, double *d_q_out, double *d_cost_first, double *d_cost_last,
+                            double *d_clearance, int32_t *d_status, void *stream);
+
 /* The measures of solution modes 3 and 4 for B configurations d_q [n][B] (any chain of 1 .. 16 revolute joint
  * positions): d_w [B] manipulability w = sqrt(det G), d_c [B] condition c = sigma_min / sigma_max, both of the body
  * Jacobian fk_batch returns (ee_offset7 may be NULL).  Either output may be NULL.  A G that is not numerically

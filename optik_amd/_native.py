@@ -142,6 +142,8 @@ def lib():
     L.optik_hip_collision_witness_batch.argtypes = [vp, dp, vp, C.c_int64, vp, vp, vp, vp]
     L.optik_hip_diff_ik_avoid_batch.argtypes = [vp, dp, vp, vp, C.c_int64, vp, C.c_int64, C.c_int64, C.c_double,
                                                 C.c_double, C.c_double, vp, vp, vp, vp]
+    L.optik_hip_path_optimize.argtypes = [vp, dp, vp, C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_double,
+                                          C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]
     L.optik_hip_ik_batch.argtypes = [vp, C.POINTER(SolverConfigC), vp, vp, C.c_int32, dp,
                                      C.c_uint64, C.c_uint64, C.c_uint32, C.c_double,
                                      C.POINTER(IkOutputs), vp]
@@ -171,6 +173,25 @@ def check_resolution(h, allow_zero=False):
     if not (math.isfinite(h) and (h > 0.0 or (allow_zero and h == 0.0))):
         raise ValueError("motion resolution must be finite and " + (">= 0" if allow_zero else "> 0") + f", got {h}")
     return h
+
+
+PATH_OPTIMIZE_MAX_WAYPOINTS = 64  # include/optik_hip.h: OPTIK_HIP_PATH_OPTIMIZE_MAX_WAYPOINTS
+# The values with which the host reference (csrc/path_optimize.hpp under g++) clears the L = 16 scene of
+# tests/test_path_optimize_host.py: that and nothing more.
+PATH_OPTIMIZE_ITERS, PATH_OPTIMIZE_STEP, PATH_OPTIMIZE_W_SMOOTH, PATH_OPTIMIZE_W_OBS = 100, 0.05, 1.0, 1.0
+
+
+def check_path_optimize_args(L, iters, step, w_smooth, w_obs, influence, safety):
+    """The argument rules of optik_hip_path_optimize, checked on the host."""
+    if not 3 <= int(L) <= PATH_OPTIMIZE_MAX_WAYPOINTS:
+        raise ValueError(f"a path has 3 .. {PATH_OPTIMIZE_MAX_WAYPOINTS} waypoints, got {L}")
+    if isinstance(iters, bool) or int(iters) != iters or int(iters) < 0 or int(iters) >= 1 << 31:
+        raise ValueError(f"iters must be an integer >= 0, got {iters!r}")
+    vals = [float(v) for v in (step, w_smooth, w_obs, influence, safety)]
+    if not (all(math.isfinite(v) for v in vals) and vals[0] > 0.0 and vals[1] >= 0.0 and vals[2] >= 0.0
+            and vals[3] > vals[4] >= 0.0):
+        raise ValueError("path_optimize: needs step > 0, w_smooth >= 0, w_obs >= 0 and influence > safety >= 0, "
+                         "all finite")
 
 
 def check(rc: int):

@@ -10,6 +10,7 @@
 //   ik_collision.hip   the collision filter: model and world, its key pass, link frames and clearance batches
 //   ik_motion.hip      the motion check: segments between configurations, the motion key pass of optik_hip_ik_path
 //   ik_avoid.hip       clearance witnesses and gradients, collision-avoiding diff_ik (velocity dampers)
+//   ik_path_optimize.hip  covariant gradient smoothing of joint paths against the same witnesses
 //   ik_occupancy.hip   occupancy grids and point clouds into distance-field worlds (distance transform, voxelize)
 //   ik_batch_ops.hip   objective / gradient, FK / Jacobian and seed batches, the test probes
 //   ik_lane_kernel.hip, ik_quad_kernel.hip, ik_wide_kernel.hip    the restart solvers (one restart loop each)

@@ -1,6 +1,7 @@
 // robot_rows.cpp -- the row batches of the host API (diff_ik, manipulability, link frames, clearance, witnesses,
-// motion), each one stage_rows over the robot's first device, and what they are checked against: the collision
-// model, the worlds and their builders.  (robot_host.hpp: the robot object and the shared plumbing.)
+// motion), each one stage_rows over the robot's first device; the path optimiser's batch of paths, which stages
+// through the same batch block with a transpose of its own; and what they are checked against: the collision model,
+// the worlds and their builders.  (robot_host.hpp: the robot object and the shared plumbing.)
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -20,6 +21,7 @@ namespace {
 constexpr int64_t kRowChunk = (int64_t)1 << 18;     // rows per launch
 constexpr int64_t kMotionChunk = (int64_t)1 << 16;  // segments per launch (each is many samples)
 constexpr int64_t kWitnessChunk = (int64_t)1 << 15;  // rows per launch of the witness table (840 B a row at n = 8: 28 MB)
+constexpr int64_t kPathChunk = (int64_t)1 << 13;     // paths per launch of the path optimiser (8 KB a path at L = 64, n = 8)
 
 }  // namespace
 
@@ -384,6 +386,68 @@ int optik_robot_diff_ik_avoid(const optik_robot *r, const double *x0, const doub
     const int rc = optik_robot_diff_ik_avoid_batch(r, 1, x0, V_WE, v_max, influence, safety, gain, ee16, alpha_out,
                                                    v_out, &status);
     return rc < 0 ? rc : status;
+}
+
+// P paths through optik_hip_path_optimize.  The kernel layer takes the waypoints as optik_hip_ik_path writes them,
+// [L][P][n], which is not the struct-of-arrays form stage_rows makes: the same steps here -- the batch block under
+// its guard, one upload, one launch, one download per chunk of paths --, with the waypoint-major transpose.
+int optik_robot_path_optimize(const optik_robot *r, int64_t P, int32_t L, const double *paths, int32_t iters,
+                              double step, double w_smooth, double w_obs, double influence, double safety,
+                              const double *ee16, double *paths_out, double *cost_first_out, double *cost_last_out,
+                              double *clearance_out, int32_t *status_out) {
+    if (!r || !paths) return set_err(-1, "null argument");
+    if (P < 0) return set_err(-1, "bad argument");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    // (P = 0: the kernel layer's refusals of the chain, of L, iters and the parameters, before anything is staged)
+    if (optik_hip_path_optimize(c->chain, nullptr, nullptr, L, 0, iters, step, w_smooth, w_obs, influence, safety,
+                                nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (P == 0 || (!paths_out && !cost_first_out && !cost_last_out && !clearance_out && !status_out)) return 0;
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    BatchGuard guard(c);
+    if (!guard.ok()) return set_err(-1, kSetDeviceMsg);
+    const size_t n = (size_t)r->n, nl = (size_t)L, w = nl * n;
+    const int64_t chunk = P < kPathChunk ? P : kPathChunk;
+    // per path: the waypoints in; the waypoints, cost_first 3, cost_last 3, the clearance, and the status word in
+    // the bytes of one more double out
+    if (!reserve_batch(c, (2 * w + 8) * (size_t)chunk)) return set_err(-1, kBatchAllocMsg);
+    for (int64_t b0 = 0; b0 < P; b0 += chunk) {
+        const size_t Lc = (size_t)(P - b0 < chunk ? P - b0 : chunk);
+        double *h_in = c->h_batch.get(), *h_out = h_in + w * Lc;
+        double *d_in = c->d_batch.get(), *d_out = d_in + w * Lc;
+        parallel_ranges(Lc, [&](size_t k0, size_t k1) {
+            for (size_t k = k0; k < k1; ++k)
+                for (size_t t = 0; t < nl; ++t)
+                    std::memcpy(h_in + (t * Lc + k) * n, paths + (((size_t)b0 + k) * nl + t) * n, sizeof(double) * n);
+        });
+        if (hipMemcpyAsync(d_in, h_in, sizeof(double) * w * Lc, hipMemcpyHostToDevice, nullptr) != hipSuccess)
+            return set_err(-1, "upload failed");
+        double *d_cf = d_out + w * Lc, *d_cl = d_cf + 3 * Lc, *d_clr = d_cl + 3 * Lc;
+        if (optik_hip_path_optimize(c->chain, ee16 ? ee7 : nullptr, d_in, L, (int64_t)Lc, iters, step, w_smooth, w_obs,
+                                    influence, safety, d_out, d_cf, d_cl, d_clr, reinterpret_cast<int32_t *>(d_clr + Lc),
+                                    nullptr))
+            return set_err(-1, optik_hip_last_error());
+        if (hipMemcpyAsync(h_out, d_out, sizeof(double) * (w + 8) * Lc, hipMemcpyDeviceToHost, nullptr) != hipSuccess
+            || hipStreamSynchronize(nullptr) != hipSuccess)
+            return set_err(-1, "download failed");
+        const double *h_cf = h_out + w * Lc, *h_cl = h_cf + 3 * Lc, *h_clr = h_cl + 3 * Lc;
+        const int32_t *h_st = reinterpret_cast<const int32_t *>(h_clr + Lc);
+        parallel_ranges(Lc, [&](size_t k0, size_t k1) {
+            for (size_t k = k0; k < k1; ++k) {
+                const size_t row = (size_t)b0 + k;
+                if (paths_out)
+                    for (size_t t = 0; t < nl; ++t)
+                        std::memcpy(paths_out + (row * nl + t) * n, h_out + (t * Lc + k) * n, sizeof(double) * n);
+                if (cost_first_out) std::memcpy(cost_first_out + 3 * row, h_cf + 3 * k, 3 * sizeof(double));
+                if (cost_last_out) std::memcpy(cost_last_out + 3 * row, h_cl + 3 * k, 3 * sizeof(double));
+                if (clearance_out) clearance_out[row] = h_clr[k];
+                if (status_out) status_out[row] = h_st[k];
+            }
+        });
+    }
+    return 0;
 }
 
 int optik_robot_set_motion_resolution(optik_robot *r, double h) {

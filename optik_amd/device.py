@@ -309,6 +309,33 @@ class HipChain:
         off, the default); it acts while a collision model is set.  Waits for the device."""
         nat.check(nat.lib().optik_hip_chain_set_motion_resolution(self._h, nat.check_resolution(h, allow_zero=True)))
 
+    # -- bending paths out of collision (include/optik_hip.h; DESIGN.md section 5.17) -----------------------------
+    def path_optimize(self, q, iters, step, w_smooth, w_obs, influence, safety, ee_offset7=None, out=None):
+        """Covariant gradient smoothing of P paths of L waypoints (optik_hip_path_optimize): q [L, P, n] float64 cuda
+        tensor -- ik_path's "x" as it is --, 3 <= L <= 64.  `out`: the tensor that receives the waypoints (q itself:
+        in place; default: a new one).  Stream-ordered on the current stream; returns a dict of device tensors: q
+        [L, P, n], cost_first [P, 3], cost_last [P, 3] = (U, F_smooth, F_obs), clearance [P], status [P] int32."""
+        if not (isinstance(q, torch.Tensor) and q.is_cuda and q.dtype == torch.float64 and q.dim() == 3
+                and q.shape[2] == self.n and q.is_contiguous()):
+            raise ValueError(f"q must be a contiguous float64 cuda tensor [L, P, n] with n = {self.n}")
+        L, P = int(q.shape[0]), int(q.shape[1])
+        nat.check_path_optimize_args(L, iters, step, w_smooth, w_obs, influence, safety)
+        if out is None:
+            out = torch.empty_like(q)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous()
+                  and out.shape == q.shape and out.device == q.device):
+            raise ValueError("out must be a contiguous float64 cuda tensor of q's shape and device")
+        ee = self._ee7(ee_offset7)
+        res = dict(q=out, cost_first=torch.empty((P, 3), dtype=torch.float64, device=q.device),
+                   cost_last=torch.empty((P, 3), dtype=torch.float64, device=q.device),
+                   clearance=torch.empty(P, dtype=torch.float64, device=q.device),
+                   status=torch.empty(P, dtype=torch.int32, device=q.device))
+        nat.check(nat.lib().optik_hip_path_optimize(
+            self._h, _dp(ee) if ee is not None else None, _ptr(q), L, P, int(iters), float(step), float(w_smooth),
+            float(w_obs), float(influence), float(safety), _ptr(out), _ptr(res["cost_first"]), _ptr(res["cost_last"]),
+            _ptr(res["clearance"]), _ptr(res["status"]), _stream_ptr()))
+        return res
+
     def seed_batch(self, first, count):
         q = torch.empty((self.n, count), dtype=torch.float64, device=self.device)
         nat.check(nat.lib().optik_hip_seed_batch(self._h, int(first), int(count), _ptr(q), _stream_ptr()))

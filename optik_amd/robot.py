@@ -61,6 +61,8 @@ def _bind(L):
                                             C.POINTER(C.c_double), dp]
     L.optik_robot_diff_ik_avoid_batch.argtypes = [vp, C.c_int64, dp, dp, dp, C.c_double, C.c_double, C.c_double, dp,
                                                   dp, dp, C.POINTER(C.c_int32)]
+    L.optik_robot_path_optimize.argtypes = [vp, C.c_int64, C.c_int32, dp, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                            C.c_double, C.c_double, dp, dp, dp, dp, dp, C.POINTER(C.c_int32)]
     L.optik_robot_joint_jacobian_ex.argtypes = [vp, dp, dp, dp]
     L.optik_robot_set_devices.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32]
     L.optik_robot_num_devices.argtypes = [vp]
@@ -682,6 +684,48 @@ class Robot:
         x = self._check_x(x)
         clr, _ = self.collision_clearance_batch_arrays(x[None], ee_offset)
         return float(clr[0])
+
+    # -- bending paths out of collision (extension; include/optik.h) ----------------------
+    def optimize_paths(self, paths, iters=nat.PATH_OPTIMIZE_ITERS, step=nat.PATH_OPTIMIZE_STEP,
+                       w_smooth=nat.PATH_OPTIMIZE_W_SMOOTH, w_obs=nat.PATH_OPTIMIZE_W_OBS, influence=0.2, safety=0.05,
+                       resolution=None, ee_offset=None):
+        """Covariant gradient smoothing (after CHOMP) of P joint-space paths `paths` [P, L, n], 3 <= L <= 64, against
+        the robot's collision model and world: `iters` updates, each a step of -step * Ainv * grad U from the same
+        iterate with U = w_smooth * F_smooth + w_obs * F_obs (csrc/path_optimize.hpp), then a clamp to the joint
+        limits; the first and the last waypoint never move.  F_obs is a hinge of (witness distance - safety) that is
+        zero from `influence` on.  Returns (paths [P, L, n], cost_first [P, 3], cost_last [P, 3], clearance [P],
+        status [P] int32): the costs (U, F_smooth, F_obs) of the input and of the result, the smallest witness
+        distance over the result's waypoints, and status 1 where the last cost is NaN.  With `resolution` it also
+        returns free [P] bool: every one of the L - 1 segments of the result passes collision_motion_batch_arrays at
+        that resolution.  Without a collision model the paths relax towards the straight line.
+        The defaults of iters, step and the weights are the values with which the host reference clears the L = 16
+        scene of tests/test_path_optimize_host.py; they are that and nothing more.  The rows of Ainv sum to about
+        L^2 / 8 in the middle of a path, so `step` has to shrink as L^2 grows: the default 0.05 is about 16 times as
+        aggressive at L = 64 as at L = 16 and may oscillate there.
+        ValueError for L outside 3 .. 64, iters < 0, or unless step > 0, the weights >= 0 and influence > safety
+        >= 0, all finite."""
+        n = self.num_positions()
+        paths = np.ascontiguousarray(paths, dtype=np.float64)
+        if paths.ndim != 3 or paths.shape[2] != n:
+            raise ValueError(f"paths must be [P, L, n] with n = {n}, got {list(paths.shape)}")
+        P, L = paths.shape[0], paths.shape[1]
+        nat.check_path_optimize_args(L, iters, step, w_smooth, w_obs, influence, safety)
+        if resolution is not None:
+            resolution = nat.check_resolution(resolution)
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        out = np.zeros((P, L, n))
+        first, last, clr = np.zeros((P, 3)), np.zeros((P, 3)), np.zeros(P)
+        status = np.zeros(P, dtype=np.int32)
+        if self._L.optik_robot_path_optimize(self._h, P, L, _dp(paths), int(iters), float(step), float(w_smooth),
+                                             float(w_obs), float(influence), float(safety),
+                                             _dp(ee) if ee is not None else None, _dp(out), _dp(first), _dp(last),
+                                             _dp(clr), status.ctypes.data_as(C.POINTER(C.c_int32))):
+            raise RuntimeError(_err(self._L))
+        if resolution is None:
+            return out, first, last, clr, status
+        seg_free = self.collision_motion_batch_arrays(out[:, :-1].reshape(-1, n), out[:, 1:].reshape(-1, n),
+                                                      resolution, ee_offset)[1]
+        return out, first, last, clr, status, seg_free.reshape(P, L - 1).all(axis=1)
 
     # -- the motion check (extension; include/optik.h, DESIGN.md section 5.13) ------------------------------------
     def collision_motion_batch_arrays(self, xa, xb, resolution, ee_offset=None):
