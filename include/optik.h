@@ -234,6 +234,26 @@ int optik_robot_path_optimize(const optik_robot *robot, int64_t P, int32_t L, co
                               double step, double w_smooth, double w_obs, double influence, double safety,
                               const double *ee_offset16, double *paths_out, double *cost_first_out,
                               double *cost_last_out, double *clearance_out, int32_t *status_out);
+/* Roadmap planning (extension; include/optik_hip.h: optik_hip_roadmap_knn and what follows it; DESIGN.md section
+ * 5.18): a way round what the motion check refuses.
+ * optik_robot_roadmap_build: N nodes (1 .. 8192) -- the seeds of restart indices first .. first + N - 1, the generator
+ * of the IK restarts, uniform inside the joint limits --, each node's k (1 .. 16) nearest others (L-infinity) and the
+ * motion node -> neighbour checked at `resolution` against the robot's model and world.  Nodes in collision are
+ * kept: they have no free edge.  The roadmap lives in the robot handle, on its first device, and replaces the one
+ * before.  Returns the number of free edges, or -1 (what the kernel layer refuses: N, k, the resolution, prismatic
+ * joints, infinite joint limits).
+ * optik_robot_roadmap_plan: starts, goals [Q][n] row-major -> paths_out [Q][Lmax][n], 2 <= Lmax <= 64 (start, the
+ * nodes of the route, goal, padded with the goal: what optik_robot_path_optimize takes), len_out [Q] the waypoints
+ * before the padding, cost_out [Q] the L-infinity length of the route, status_out [Q]: 0 found; 1 no route (cost +inf);
+ * 2 the route needs more than Lmax waypoints (the true cost); 3 a NaN in the query (cost NaN); unless 0 the path is
+ * the start, then the goal repeated.  Any output may be NULL.  Each start and goal is linked to its k nearest nodes
+ * and the direct motion start -> goal is checked too, all at the roadmap's resolution; ties go to the direct motion.
+ * rc 0, or -1: no roadmap; a stale roadmap -- optik_robot_set_collision_model, _set_world and _set_world_grid each
+ * make it stale, so a plan is never checked against a world that is gone: build it again --; a bad Lmax. */
+int64_t optik_robot_roadmap_build(optik_robot *robot, int32_t N, int32_t k, double resolution, uint64_t first);
+int optik_robot_roadmap_plan(const optik_robot *robot, const double *starts, const double *goals, int64_t Q,
+                             int32_t Lmax, double *paths_out, int32_t *len_out, double *cost_out,
+                             int32_t *status_out);
 /* The motion check (extension; include/optik_hip.h: optik_hip_collision_motion_batch and what precedes it).  B segments
  * xa, xb [B][n] row-major at `resolution` (finite, > 0) -> clearance_out [B], free_out [B], first_out [B], steps_out
  * [B]; any may be NULL (clearance_out NULL: the call only classifies).  On the robot's first device, 65 536 segments

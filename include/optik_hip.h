@@ -197,6 +197,60 @@ int optik_hip_path_optimize(const optik_hip_chain *chain, const double *ee_offse
                             double safety, double *d_q_out, double *d_cost_first, double *d_cost_last,
                             double *d_clearance, int32_t *d_status, void *stream);
 
+/* Roadmap planning (extension; the arithmetic and its operation order:
+ * csrc/roadmap_measure.hpp): a directed graph over N <= OPTIK_HIP_ROADMAP_MAX_NODES joint-space nodes, every edge a
+ * motion checked by optik_hip_collision_motion_batch in the direction it is used in, queried for many (start, goal)
+ * pairs at once.  The metric is L-infinity in radians: the weight of a -> b is max_i |b_i - a_i|, the d of the motion
+ * check.  Configurations are struct-of-arrays, [n][count], as every batch operator has them.  Any revolute chain of
+ * 1 .. 16 joint positions.  All three are stream-ordered with no host synchronisation.  Refused with
+ * OPTIK_HIP_EINVAL before any device work: k (ks, kg) outside 1 .. OPTIK_HIP_ROADMAP_MAX_K, N outside 1 ..
+ * OPTIK_HIP_ROADMAP_MAX_NODES (optik_hip_roadmap_edges: N < 1), Q < 0 (Q = 0 is a no-op) or above 2^30, Lmax outside
+ * 2 .. 64, a resolution that is not finite and > 0; with OPTIK_HIP_EUNSUPPORTED: chains with prismatic joints.
+ *
+ * optik_hip_roadmap_knn: queries d_q [n][Q] against d_nodes [n][N] -> d_idx [k][Q], d_dist [k][Q] (either may be
+ * NULL): the k first nodes of each query in the total order on (distance, index) -- a number before a NaN distance,
+ * then the smaller distance, then the smaller index --, best first; slots past the candidates hold index -1 and
+ * distance +inf.  exclude_self != 0 skips node j for query j (queries and nodes are the same array).  The result is
+ * defined by the order alone: not by the launch shape, the tile size or the order of the visits.
+ *
+ * optik_hip_roadmap_edges: the Q * k segments d_from[:, q] -> d_nodes[:, d_idx[s][q]] (reverse != 0: node -> from)
+ * are gathered, checked at `resolution` by the motion check's own code on the same stream (model, world and
+ * ee_offset7 as there; without a model every motion of finite length is free), and d_w [k][Q] receives the weight where the
+ * motion is free and +inf where it is not, where it is not sampled, or where the index is outside 0 .. N - 1.  The
+ * motion check samples qa + (j / K)(qb - qa), so a segment and its reverse have different samples: an edge holds in
+ * the direction it was checked in.  d_idx NULL pairs endpoint q with node q (k = 1, N = Q; N is not capped): the direct
+ * start -> goal check of a plan.  The gathered segments (16 n + 1 bytes each) are the chain's workspace, grown on
+ * demand, next to the motion check's: one call per chain handle at a time.
+ *
+ * optik_hip_roadmap_query: the graph d_nbr, d_w [k][N] (the out-edges v -> d_nbr[s][v], checked in that direction);
+ * per query its start and goal d_start, d_goal [n][Q], the start links d_sidx, d_sw [ks][Q] (start -> node), the goal
+ * links d_gidx, d_gw [kg][Q] (node -> goal, checked with reverse) and the direct weight d_direct [Q].  The distance
+ * to the goal d[u] starts as u's goal-link weight (+inf without one) and every node relaxes d[v] = min(d[v], w(v, u) +
+ * d[u]) over its own out-list until nothing changes: the values of Dijkstra's algorithm with each route summed from
+ * the goal backwards, whatever the sweep order.  A NaN or negative index is no edge; weights are >= 0.  The first hop
+ * is the direct edge if its weight is <= every d_sw[s] + d[d_sidx[s]] (ties to the direct edge, then to the lowest
+ * slot); the successor of a node is the goal if its goal-link weight equals d[v], else the lowest-index u of its
+ * out-list with w(v, u) + d[u] == d[v] exactly.  Outputs (any may be NULL): d_path [Lmax][Q][n] -- the layout
+ * optik_hip_path_optimize takes -- holds the start, the nodes walked and the goal, padded with the goal; d_len [Q]
+ * the waypoints before the padding; d_cost [Q]; d_status [Q]:
+ *   0 found; 1 no route (cost +inf); 2 the route needs more than Lmax waypoints (the true cost); 3 the start, the
+ *   goal, the direct weight or a link weight is NaN (cost NaN).  Unless 0: len 2, the start, then the goal repeated.
+ * The walk stops at Lmax waypoints whatever the successors say (a zero-weight cycle between duplicate nodes ends
+ * there, as status 2).  One workgroup per query, d in LDS -- two buffers of N doubles, which is where the cap on N
+ * comes from; a query's result does not depend on Q. */
+#define OPTIK_HIP_ROADMAP_MAX_NODES 8192
+#define OPTIK_HIP_ROADMAP_MAX_K 16
+int optik_hip_roadmap_knn(const optik_hip_chain *chain, const double *d_q, int64_t Q, const double *d_nodes, int32_t N,
+                          int32_t k, int32_t exclude_self, int32_t *d_idx, double *d_dist, void *stream);
+int optik_hip_roadmap_edges(optik_hip_chain *chain, const double *ee_offset7, const double *d_from, int64_t Q,
+                            const double *d_nodes, int32_t N, const int32_t *d_idx, int32_t k, double resolution,
+                            int32_t reverse, double *d_w, void *stream);
+int optik_hip_roadmap_query(const optik_hip_chain *chain, const double *d_nodes, int32_t N, const int32_t *d_nbr,
+                            const double *d_w, int32_t k, const double *d_start, const double *d_goal, int64_t Q,
+                            const int32_t *d_sidx, const double *d_sw, int32_t ks, const int32_t *d_gidx,
+                            const double *d_gw, int32_t kg, const double *d_direct, int32_t Lmax, double *d_path,
+                            int32_t *d_len, double *d_cost, int32_t *d_status, void *stream);
+
 /* The measures of solution modes 3 and 4 for B configurations d_q [n][B] (any chain of 1 .. 16 revolute joint
  * positions): d_w [B] manipulability w = sqrt(det G), d_c [B] condition c = sigma_min / sigma_max, both of the body
  * Jacobian fk_batch returns (ee_offset7 may be NULL).  Either output may be NULL.  A G that is not numerically

@@ -144,6 +144,11 @@ def lib():
                                                 C.c_double, C.c_double, vp, vp, vp, vp]
     L.optik_hip_path_optimize.argtypes = [vp, dp, vp, C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_double,
                                           C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]
+    L.optik_hip_roadmap_knn.argtypes = [vp, vp, C.c_int64, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]
+    L.optik_hip_roadmap_edges.argtypes = [vp, dp, vp, C.c_int64, vp, C.c_int32, vp, C.c_int32, C.c_double, C.c_int32,
+                                          vp, vp]
+    L.optik_hip_roadmap_query.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int64, vp, vp, C.c_int32,
+                                          vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
     L.optik_hip_ik_batch.argtypes = [vp, C.POINTER(SolverConfigC), vp, vp, C.c_int32, dp,
                                      C.c_uint64, C.c_uint64, C.c_uint32, C.c_double,
                                      C.POINTER(IkOutputs), vp]
@@ -192,6 +197,22 @@ def check_path_optimize_args(L, iters, step, w_smooth, w_obs, influence, safety)
             and vals[3] > vals[4] >= 0.0):
         raise ValueError("path_optimize: needs step > 0, w_smooth >= 0, w_obs >= 0 and influence > safety >= 0, "
                          "all finite")
+
+
+# include/optik_hip.h: OPTIK_HIP_ROADMAP_MAX_NODES, OPTIK_HIP_ROADMAP_MAX_K; the statuses of optik_hip_roadmap_query
+ROADMAP_MAX_NODES, ROADMAP_MAX_K = 8192, 16
+ROADMAP_FOUND, ROADMAP_NO_ROUTE, ROADMAP_TOO_LONG, ROADMAP_NAN = 0, 1, 2, 3
+# The values with which Robot.build_roadmap / plan_paths plan the wall scene of examples/plan_path.py on a Panda: that
+# and nothing more.
+ROADMAP_NODES, ROADMAP_K, ROADMAP_RESOLUTION = 512, 8, 0.05
+
+
+def check_roadmap_args(N=1, k=1, max_waypoints=2):
+    """The argument rules of the roadmap entry points, checked on the host."""
+    for name, v, lo, hi in (("N", N, 1, ROADMAP_MAX_NODES), ("k", k, 1, ROADMAP_MAX_K),
+                            ("max_waypoints", max_waypoints, 2, PATH_OPTIMIZE_MAX_WAYPOINTS)):
+        if isinstance(v, bool) or int(v) != v or not lo <= int(v) <= hi:
+            raise ValueError(f"{name} must be an integer in {lo} .. {hi}, got {v!r}")
 
 
 def check(rc: int):

@@ -3,7 +3,7 @@
 //
 //   robot_host.cpp   the robot object, devices, FK / Jacobian, ik / ik_batch / ik_solutions / ik_path and their scheduling
 //   robot_rows.cpp   the row batches (diff_ik, manipulability, link frames, clearance, motion), the collision model /
-//                    world / grid / motion-resolution setters, the world builders
+//                    world / grid / motion-resolution setters, the world builders, the roadmap
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -36,6 +36,13 @@ struct DeviceCtx {
     optik::DeviceBuf<double> d_batch;
     optik::PinnedBuf<double> h_batch;  // pinned mirror
     std::mutex batch_mu;               // one batch at a time per device
+    // the roadmap of optik_robot_roadmap_build (under batch_mu): nodes [n][N] | w [k][N], then nbr [k][N]; rm_N = 0:
+    // none.  rm_epoch: the robot's world_epoch the edges were checked under
+    optik::DeviceBuf<double> rm_graph;
+    optik::DeviceBuf<int32_t> rm_nbr;
+    int32_t rm_N = 0, rm_k = 0;
+    double rm_h = 0.0;
+    uint64_t rm_epoch = 0;
     ~DeviceCtx() { if (chain) optik_hip_chain_destroy(chain); }
 };
 
@@ -73,6 +80,9 @@ struct optik_robot {
     double grid_origin[3] = {0.0, 0.0, 0.0}, grid_voxel = 0.0;
     int32_t grid_n[3] = {0, 0, 0};
     double motion_h = 0.0;  // optik_robot_set_motion_resolution (0: off)
+    // counts the installs of a collision model, a world or a grid: a roadmap built under another count is stale
+    // (optik_robot_roadmap_plan)
+    std::atomic<uint64_t> world_epoch{0};
     bool collision_active() const {
         std::lock_guard<std::mutex> lock(mu);
         return !coll_frames.empty();

@@ -1,5 +1,5 @@
 // robot_rows.cpp -- the row batches of the host API (diff_ik, manipulability, link frames, clearance, witnesses,
-// motion), each one stage_rows over the robot's first device; the path optimiser's batch of paths, which stages
+// motion, roadmap plans), each one stage_rows over the robot's first device; the path optimiser's batch of paths, which stages
 // through the same batch block with a transpose of its own; and what they are checked against: the collision model,
 // the worlds and their builders.  (robot_host.hpp: the robot object and the shared plumbing.)
 #include <hip/hip_runtime.h>
@@ -22,6 +22,7 @@ constexpr int64_t kRowChunk = (int64_t)1 << 18;     // rows per launch
 constexpr int64_t kMotionChunk = (int64_t)1 << 16;  // segments per launch (each is many samples)
 constexpr int64_t kWitnessChunk = (int64_t)1 << 15;  // rows per launch of the witness table (840 B a row at n = 8: 28 MB)
 constexpr int64_t kPathChunk = (int64_t)1 << 13;     // paths per launch of the path optimiser (8 KB a path at L = 64, n = 8)
+constexpr int64_t kPlanChunk = (int64_t)1 << 12;     // queries per launch of a plan (one workgroup each; 8 KB of path at Lmax = 64, n = 16)
 
 }  // namespace
 
@@ -110,6 +111,7 @@ int optik_robot_set_collision_model(optik_robot *r, const int32_t *frames, const
             if (t == optik_host::PRISMATIC)
                 return set_err(-1, "collision: prismatic joints are not supported (IK refuses such chains)");
     std::lock_guard<std::mutex> lock(r->mu);
+    r->world_epoch.fetch_add(1);  // (a roadmap checked against what is replaced here is stale)
     if (S > 0) {
         r->coll_frames.assign(frames, frames + S);
         r->coll_centers.assign(centers3, centers3 + 3 * (size_t)S);
@@ -131,6 +133,7 @@ int optik_robot_set_world(optik_robot *r, const double *spheres4, int32_t Ms, co
     std::string err;
     if (optik::coll::check_world(spheres4, Ms, boxes10, Mb, err)) return set_err(-1, err);
     std::lock_guard<std::mutex> lock(r->mu);
+    r->world_epoch.fetch_add(1);  // (a roadmap checked against what is replaced here is stale)
     if (Ms > 0) r->world_spheres.assign(spheres4, spheres4 + 4 * (size_t)Ms);
     else r->world_spheres.clear();
     if (Mb > 0) r->world_boxes.assign(boxes10, boxes10 + 10 * (size_t)Mb);
@@ -147,6 +150,7 @@ int optik_robot_set_world_grid(optik_robot *r, const double *origin3, double vox
     std::string err;
     if (!clear && optik::coll::check_grid(origin3, voxel, nx, ny, nz, values, true, err)) return set_err(-1, err);
     std::lock_guard<std::mutex> lock(r->mu);
+    r->world_epoch.fetch_add(1);  // (a roadmap checked against what is replaced here is stale)
     if (clear) {
         r->grid_values.clear();
         r->grid_n[0] = r->grid_n[1] = r->grid_n[2] = 0;
@@ -448,6 +452,107 @@ int optik_robot_path_optimize(const optik_robot *r, int64_t P, int32_t L, const 
         });
     }
     return 0;
+}
+
+// The roadmap (include/optik.h): N seeds of the restart generator as nodes, their k nearest others and the checked
+// motions to them, kept in the first device's context.  Everything stays on the device but the weights' count.
+int64_t optik_robot_roadmap_build(optik_robot *r, int32_t N, int32_t k, double resolution, uint64_t first) {
+    if (!r) return set_err(-1, "null argument");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    // (Q = 0: the kernel layer's refusals of N, k, the resolution and the chain, before anything is allocated)
+    if (optik_hip_roadmap_knn(c->chain, nullptr, 0, nullptr, N, k, 1, nullptr, nullptr, nullptr)
+        || optik_hip_roadmap_edges(c->chain, nullptr, nullptr, 0, nullptr, N, nullptr, 1, resolution, 0, nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    BatchGuard guard(c);
+    if (!guard.ok()) return set_err(-1, kSetDeviceMsg);
+    const uint64_t epoch = r->world_epoch.load();
+    const size_t n = (size_t)r->n, cells = (size_t)k * (size_t)N;
+    c->rm_N = 0;
+    if (c->rm_graph.reserve(n * (size_t)N + cells) != hipSuccess || c->rm_nbr.reserve(cells) != hipSuccess
+        || !reserve_batch(c, cells))
+        return set_err(-1, kBatchAllocMsg);
+    double *d_nodes = c->rm_graph.get(), *d_w = d_nodes + n * (size_t)N;
+    if (optik_hip_seed_batch(c->chain, first, N, d_nodes, nullptr)
+        || optik_hip_roadmap_knn(c->chain, d_nodes, N, d_nodes, N, k, 1, c->rm_nbr.get(), nullptr, nullptr)
+        || optik_hip_roadmap_edges(c->chain, nullptr, d_nodes, N, d_nodes, N, c->rm_nbr.get(), k, resolution, 0, d_w,
+                                   nullptr))
+        return set_err(-1, optik_hip_last_error());
+    double *h_w = c->h_batch.get();
+    if (hipMemcpyAsync(h_w, d_w, sizeof(double) * cells, hipMemcpyDeviceToHost, nullptr) != hipSuccess
+        || hipStreamSynchronize(nullptr) != hipSuccess)
+        return set_err(-1, "download failed");
+    int64_t edges = 0;
+    for (size_t e = 0; e < cells; ++e) edges += std::isfinite(h_w[e]) ? 1 : 0;
+    c->rm_N = N; c->rm_k = k; c->rm_h = resolution; c->rm_epoch = epoch;
+    return edges;
+}
+
+// Q plans over the robot's roadmap: the rows are staged as every row batch stages them, and per chunk the two
+// neighbour searches, the three edge checks and the query run back to back on the device.
+int optik_robot_roadmap_plan(const optik_robot *r, const double *starts, const double *goals, int64_t Q, int32_t Lmax,
+                             double *paths_out, int32_t *len_out, double *cost_out, int32_t *status_out) {
+    if (!r || !starts || !goals) return set_err(-1, "null argument");
+    if (Q < 0) return set_err(-1, "bad argument");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    int32_t N, k;
+    double h;
+    {
+        // (the setters bump the epoch before they take this mutex for the chain: a plan either sees the new count
+        // here or has the chain to itself until it is done)
+        std::lock_guard<std::mutex> lock(c->batch_mu);
+        if (c->rm_N == 0) return set_err(-1, "roadmap_plan: no roadmap (call optik_robot_roadmap_build first)");
+        if (c->rm_epoch != r->world_epoch.load())
+            return set_err(-1, "roadmap_plan: the roadmap is stale: the collision model or the world changed since it "
+                               "was built (build it again)");
+        N = c->rm_N; k = c->rm_k; h = c->rm_h;
+    }
+    // (Q = 0: the kernel layer's refusal of Lmax)
+    if (optik_hip_roadmap_query(c->chain, nullptr, N, nullptr, nullptr, k, nullptr, nullptr, 0, nullptr, nullptr, k,
+                                nullptr, nullptr, k, nullptr, Lmax, nullptr, nullptr, nullptr, nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (Q == 0 || (!paths_out && !len_out && !cost_out && !status_out)) return 0;
+    const size_t n = (size_t)r->n, w = (size_t)Lmax * n, uk = (size_t)k;
+    bool stale = false;
+    // per query out: the path, the cost, then len and status in one more double; behind them the scratch of the
+    // chunk (downloaded with the rest, not looked at): direct 1 | sw k | gw k doubles, sidx k | gidx k int32
+    const RowInput in[] = {{starts, n}, {goals, n}};
+    const int rc = stage_rows(
+        c, Q, in, sizeof(double) * (w + 3 + 3 * uk), kPlanChunk,
+        [&](optik_hip_chain *ch, const double *d_s, int64_t L, double *d_out) -> int {
+            // (under the batch guard now: the roadmap this chunk reads is still the one checked above?)
+            if (c->rm_N != N || c->rm_k != k || c->rm_epoch != r->world_epoch.load()) { stale = true; return 1; }
+            const double *d_g = d_s + n * (size_t)L, *d_nodes = c->rm_graph.get(), *d_w = d_nodes + n * (size_t)N;
+            double *d_cost = d_out + w * (size_t)L;
+            int32_t *d_len = reinterpret_cast<int32_t *>(d_cost + L), *d_status = d_len + L;
+            double *d_direct = d_cost + 2 * L, *d_sw = d_direct + L, *d_gw = d_sw + uk * (size_t)L;
+            int32_t *d_sidx = reinterpret_cast<int32_t *>(d_gw + uk * (size_t)L), *d_gidx = d_sidx + uk * (size_t)L;
+            return (optik_hip_roadmap_knn(ch, d_s, L, d_nodes, N, k, 0, d_sidx, nullptr, nullptr)
+                   || optik_hip_roadmap_knn(ch, d_g, L, d_nodes, N, k, 0, d_gidx, nullptr, nullptr)
+                   || optik_hip_roadmap_edges(ch, nullptr, d_s, L, d_nodes, N, d_sidx, k, h, 0, d_sw, nullptr)
+                   || optik_hip_roadmap_edges(ch, nullptr, d_g, L, d_nodes, N, d_gidx, k, h, 1, d_gw, nullptr)
+                   || optik_hip_roadmap_edges(ch, nullptr, d_s, L, d_g, (int32_t)L, nullptr, 1, h, 0, d_direct, nullptr)
+                   || optik_hip_roadmap_query(ch, d_nodes, N, c->rm_nbr.get(), d_w, k, d_s, d_g, L, d_sidx, d_sw, k,
+                                              d_gidx, d_gw, k, d_direct, Lmax, d_out, d_len, d_cost, d_status, nullptr))
+                       ? 1 : 0;
+        },
+        [&](size_t b0, size_t L, const double *h_out) {
+            const double *h_cost = h_out + w * L;
+            const int32_t *h_len = reinterpret_cast<const int32_t *>(h_cost + L), *h_status = h_len + L;
+            if (paths_out)
+                parallel_ranges(L, [&](size_t k0, size_t k1) {
+                    for (size_t q = k0; q < k1; ++q)
+                        for (size_t t = 0; t < (size_t)Lmax; ++t)
+                            std::memcpy(paths_out + ((b0 + q) * (size_t)Lmax + t) * n, h_out + (t * L + q) * n,
+                                        sizeof(double) * n);
+                });
+            if (cost_out) std::memcpy(cost_out + b0, h_cost, sizeof(double) * L);
+            if (len_out) std::memcpy(len_out + b0, h_len, sizeof(int32_t) * L);
+            if (status_out) std::memcpy(status_out + b0, h_status, sizeof(int32_t) * L);
+        });
+    if (stale) return set_err(-1, "roadmap_plan: the roadmap changed or went stale during the call");
+    return rc;
 }
 
 int optik_robot_set_motion_resolution(optik_robot *r, double h) {

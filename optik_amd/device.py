@@ -336,6 +336,94 @@ class HipChain:
             _ptr(res["clearance"]), _ptr(res["status"]), _stream_ptr()))
         return res
 
+    # -- roadmap planning (include/optik_hip.h) -------------------------------------------
+    def _check_slots(self, t, Q, name, dtype):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.dim() == 2 and t.shape[1] == Q
+                and t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {dtype} cuda tensor [k, {Q}]")
+        nat.check_roadmap_args(k=int(t.shape[0]))
+        return int(t.shape[0])
+
+    def roadmap_knn(self, q, nodes, k, exclude_self=False):
+        """The k nearest nodes (L-infinity) of every query (optik_hip_roadmap_knn): q [n, Q], nodes [n, N] float64
+        cuda tensors -> (idx [k, Q] int32, dist [k, Q]), best first in the order (distance, index), a NaN distance
+        after every number; -1 / +inf past the candidates.  exclude_self skips node j for query j.  Stream-ordered."""
+        Q, N = self._check_q(q), self._check_q(nodes)
+        nat.check_roadmap_args(N=N, k=k)
+        idx = torch.empty((int(k), Q), dtype=torch.int32, device=q.device)
+        dist = torch.empty((int(k), Q), dtype=torch.float64, device=q.device)
+        nat.check(nat.lib().optik_hip_roadmap_knn(self._h, _ptr(q), Q, _ptr(nodes), N, int(k), 1 if exclude_self else 0,
+                                                  _ptr(idx), _ptr(dist), _stream_ptr()))
+        return idx, dist
+
+    def roadmap_edges(self, frm, nodes, idx, resolution, reverse=False, ee_offset7=None):
+        """The weights w [k, Q] of the motions frm[:, q] -> nodes[:, idx[s, q]] (reverse: node -> frm), checked at
+        `resolution` by the motion check against the chain's model and world (optik_hip_roadmap_edges): max_i of the
+        joint differences where the motion is free, +inf elsewhere and for index -1.  idx None pairs frm[:, q] with
+        nodes[:, q] ([1, Q]).  Stream-ordered; one call per chain at a time."""
+        Q, N = self._check_q(frm), self._check_q(nodes)
+        h = nat.check_resolution(resolution)
+        if idx is None:
+            if N != Q:
+                raise ValueError("without idx, frm and nodes must have the same shape")
+            k = 1
+        else:
+            k = self._check_slots(idx, Q, "idx", torch.int32)
+        ee = self._ee7(ee_offset7)
+        w = torch.empty((k, Q), dtype=torch.float64, device=frm.device)
+        nat.check(nat.lib().optik_hip_roadmap_edges(self._h, _dp(ee) if ee is not None else None, _ptr(frm), Q,
+                                                    _ptr(nodes), N, _ptr(idx), k, h, 1 if reverse else 0, _ptr(w),
+                                                    _stream_ptr()))
+        return w
+
+    def roadmap_query(self, nodes, nbr, w, start, goal, sidx, sw, gidx, gw, direct, Lmax):
+        """Shortest joint paths over one graph for Q (start, goal) pairs (optik_hip_roadmap_query): nodes [n, N], the
+        out-edges nbr [k, N] int32 and w [k, N], start and goal [n, Q], the start links sidx, sw [ks, Q], the goal
+        links gidx, gw [kg, Q], direct [Q].  Returns a dict of device tensors: path [Lmax, Q, n] (what path_optimize
+        takes), len [Q] int32, cost [Q], status [Q] int32 (nat.ROADMAP_*).  Stream-ordered."""
+        N, Q = self._check_q(nodes), self._check_q(start)
+        if self._check_q(goal) != Q:
+            raise ValueError("start and goal must have the same shape")
+        nat.check_roadmap_args(N=N, max_waypoints=Lmax)
+        k = self._check_slots(nbr, N, "nbr", torch.int32)
+        if self._check_slots(w, N, "w", torch.float64) != k:
+            raise ValueError("nbr and w must have the same shape")
+        ks, kg = self._check_slots(sidx, Q, "sidx", torch.int32), self._check_slots(gidx, Q, "gidx", torch.int32)
+        if self._check_slots(sw, Q, "sw", torch.float64) != ks or self._check_slots(gw, Q, "gw", torch.float64) != kg:
+            raise ValueError("a link's indices and weights must have the same shape")
+        if not (isinstance(direct, torch.Tensor) and direct.is_cuda and direct.dtype == torch.float64
+                and direct.numel() == Q and direct.is_contiguous()):
+            raise ValueError(f"direct must be a contiguous float64 cuda tensor of {Q} weights")
+        dev = nodes.device
+        res = dict(path=torch.empty((int(Lmax), Q, self.n), dtype=torch.float64, device=dev),
+                   len=torch.empty(Q, dtype=torch.int32, device=dev),
+                   cost=torch.empty(Q, dtype=torch.float64, device=dev),
+                   status=torch.empty(Q, dtype=torch.int32, device=dev))
+        nat.check(nat.lib().optik_hip_roadmap_query(
+            self._h, _ptr(nodes), N, _ptr(nbr), _ptr(w), k, _ptr(start), _ptr(goal), Q, _ptr(sidx), _ptr(sw), ks,
+            _ptr(gidx), _ptr(gw), kg, _ptr(direct), int(Lmax), _ptr(res["path"]), _ptr(res["len"]), _ptr(res["cost"]),
+            _ptr(res["status"]), _stream_ptr()))
+        return res
+
+    def roadmap_build(self, nodes, k, resolution, ee_offset7=None):
+        """The roadmap over nodes [n, N]: every node's k nearest others (roadmap_knn with exclude_self) and the
+        checked weights of the motions node -> neighbour (roadmap_edges).  Returns (nbr [k, N] int32, w [k, N])."""
+        nbr, _ = self.roadmap_knn(nodes, nodes, k, exclude_self=True)
+        return nbr, self.roadmap_edges(nodes, nodes, nbr, resolution, ee_offset7=ee_offset7)
+
+    def roadmap_plan(self, roadmap, starts, goals, ks, Lmax, resolution, ee_offset7=None):
+        """Plans starts[:, q] -> goals[:, q] ([n, Q]) over roadmap = (nodes, nbr, w): each start's and each goal's
+        ks nearest nodes, the links start -> node and node -> goal and the direct motion start -> goal checked at
+        `resolution`, then roadmap_query.  Six launches' worth of kernels on the current stream, no host
+        synchronisation in between.  Returns roadmap_query's dict."""
+        nodes, nbr, w = roadmap
+        sidx, _ = self.roadmap_knn(starts, nodes, ks)
+        gidx, _ = self.roadmap_knn(goals, nodes, ks)
+        sw = self.roadmap_edges(starts, nodes, sidx, resolution, ee_offset7=ee_offset7)
+        gw = self.roadmap_edges(goals, nodes, gidx, resolution, reverse=True, ee_offset7=ee_offset7)
+        direct = self.roadmap_edges(starts, goals, None, resolution, ee_offset7=ee_offset7)
+        return self.roadmap_query(nodes, nbr, w, starts, goals, sidx, sw, gidx, gw, direct, Lmax)
+
     def seed_batch(self, first, count):
         q = torch.empty((self.n, count), dtype=torch.float64, device=self.device)
         nat.check(nat.lib().optik_hip_seed_batch(self._h, int(first), int(count), _ptr(q), _stream_ptr()))

@@ -63,6 +63,9 @@ def _bind(L):
                                                   dp, dp, C.POINTER(C.c_int32)]
     L.optik_robot_path_optimize.argtypes = [vp, C.c_int64, C.c_int32, dp, C.c_int32, C.c_double, C.c_double, C.c_double,
                                             C.c_double, C.c_double, dp, dp, dp, dp, dp, C.POINTER(C.c_int32)]
+    L.optik_robot_roadmap_build.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_uint64]
+    L.optik_robot_roadmap_build.restype = C.c_int64
+    L.optik_robot_roadmap_plan.argtypes = [vp, dp, dp, C.c_int64, C.c_int32, dp, ip, dp, ip]
     L.optik_robot_joint_jacobian_ex.argtypes = [vp, dp, dp, dp]
     L.optik_robot_set_devices.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32]
     L.optik_robot_num_devices.argtypes = [vp]
@@ -726,6 +729,50 @@ class Robot:
         seg_free = self.collision_motion_batch_arrays(out[:, :-1].reshape(-1, n), out[:, 1:].reshape(-1, n),
                                                       resolution, ee_offset)[1]
         return out, first, last, clr, status, seg_free.reshape(P, L - 1).all(axis=1)
+
+    # -- roadmap planning (extension; include/optik.h) --------------------------------------
+    def build_roadmap(self, N=nat.ROADMAP_NODES, k=nat.ROADMAP_K, resolution=nat.ROADMAP_RESOLUTION, first=0):
+        """A probabilistic roadmap over the robot's joint space, kept in the robot: N nodes (1 .. 8192) drawn
+        uniformly inside the joint limits -- the IK restart seeds of indices first .. first + N - 1 --, each joined
+        to its k (1 .. 16) nearest others (L-infinity) by the motion node -> neighbour, checked at `resolution`
+        (radians) against the collision model and world as collision_motion_batch_arrays checks it.  Nodes in
+        collision are kept; they have no free edge.  Returns the number of free edges.
+        set_collision_model, set_world, set_world_grid and set_world_points make the roadmap stale: plan_paths then
+        raises until it is built again.
+        The defaults are the values with which the wall scene of examples/plan_path.py is planned on a Panda; they
+        are that and nothing more.  A cluttered world needs more nodes, a narrow passage a finer resolution.
+        ValueError for N, k or a resolution out of range."""
+        nat.check_roadmap_args(N=N, k=k)
+        h = nat.check_resolution(resolution)
+        edges = self._L.optik_robot_roadmap_build(self._h, int(N), int(k), h, int(first))
+        if edges < 0:
+            raise RuntimeError(_err(self._L))
+        return int(edges)
+
+    def plan_paths(self, starts, goals, max_waypoints=nat.PATH_OPTIMIZE_MAX_WAYPOINTS):
+        """Shortest joint-space paths over the roadmap of build_roadmap for Q pairs starts[q] -> goals[q] ([Q, n]
+        each), all on the GPU: each start and each goal is linked to its k nearest nodes by checked motions, the
+        direct motion is checked too (and wins ties), and the route of least L-infinity length is walked.  Returns a
+        dict: paths [Q, max_waypoints, n] -- start, the nodes of the route, goal, padded with the goal: what
+        optimize_paths takes --, len [Q] int32 (the waypoints before the padding), cost [Q] (the route's length in
+        radians; the move's duration under equal joint speed limits), status [Q] int32: 0 found, 1 no route (cost
+        inf), 2 the route needs more than max_waypoints (the true cost), 3 a NaN in the query (cost NaN); unless 0
+        the path is the start, then the goal repeated.  Every one of the len - 1 segments of a found path is a
+        motion that was checked free in the direction of travel at the roadmap's resolution.
+        RuntimeError without a roadmap or with a stale one; ValueError for max_waypoints outside 2 .. 64."""
+        starts, goals = self._check_xs(starts), self._check_xs(goals)
+        if starts.shape != goals.shape:
+            raise ValueError(f"starts and goals must have the same shape, got {list(starts.shape)} and "
+                             f"{list(goals.shape)}")
+        nat.check_roadmap_args(max_waypoints=max_waypoints)
+        Q, n, L = starts.shape[0], starts.shape[1], int(max_waypoints)
+        paths, cost = np.zeros((Q, L, n)), np.zeros(Q)
+        ln, status = np.zeros(Q, dtype=np.int32), np.zeros(Q, dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        if self._L.optik_robot_roadmap_plan(self._h, _dp(starts), _dp(goals), Q, L, _dp(paths), ln.ctypes.data_as(ip),
+                                            _dp(cost), status.ctypes.data_as(ip)):
+            raise RuntimeError(_err(self._L))
+        return dict(paths=paths, len=ln, cost=cost, status=status)
 
     # -- the motion check (extension; include/optik.h, DESIGN.md section 5.13) ------------------------------------
     def collision_motion_batch_arrays(self, xa, xb, resolution, ee_offset=None):
