@@ -254,6 +254,23 @@ int64_t optik_robot_roadmap_build(optik_robot *robot, int32_t N, int32_t k, doub
 int optik_robot_roadmap_plan(const optik_robot *robot, const double *starts, const double *goals, int64_t Q,
                              int32_t Lmax, double *paths_out, int32_t *len_out, double *cost_out,
                              int32_t *status_out);
+/* Shortcutting and resampling planned paths (extension; include/optik_hip.h: optik_hip_path_shortcut and
+ * optik_hip_path_resample).  paths [P][L][n] row-major with lens [P] waypoints each (NULL: L
+ * each), 2 <= L <= 64 -- optik_robot_roadmap_plan's paths_out and len_out as they are.
+ * optik_robot_path_shortcut: at most `vertices` (2 .. 64) vertices per path, every pair of them checked at
+ * `resolution`, the route of least length + hop_penalty per hop walked -> paths_out [P][Lout][n] padded with the goal,
+ * len_out [P], cost_out [P], cost_in_out [P], status_out [P]: 0 found; 1 no route; 2 a length outside 2 .. min(L,
+ * vertices) or a route of more than Lout waypoints; 3 a NaN or an infinity in the path; unless 0 the input comes back.
+ * optik_robot_path_resample: Lout (2 .. 64) waypoints at equal L-infinity arc length -> paths_out [P][Lout][n],
+ * status_out [P] (0; 2 a bad length; 3 a length that is NaN or infinite).  The resampled segments are not checked.
+ * Any output may be NULL.  On the robot's first device; neither reads the robot's roadmap.  rc 0, or -1: null
+ * argument, what the kernel layer refuses. */
+int optik_robot_path_shortcut(const optik_robot *robot, int64_t P, int32_t L, const double *paths, const int32_t *lens,
+                              int32_t vertices, double resolution, double hop_penalty, int32_t Lout,
+                              const double *ee_offset16, double *paths_out, int32_t *len_out, double *cost_out,
+                              double *cost_in_out, int32_t *status_out);
+int optik_robot_path_resample(const optik_robot *robot, int64_t P, int32_t L, const double *paths, const int32_t *lens,
+                              int32_t Lout, double *paths_out, int32_t *status_out);
 /* The motion check (extension; include/optik_hip.h: optik_hip_collision_motion_batch and what precedes it).  B segments
  * xa, xb [B][n] row-major at `resolution` (finite, > 0) -> clearance_out [B], free_out [B], first_out [B], steps_out
  * [B]; any may be NULL (clearance_out NULL: the call only classifies).  On the robot's first device, 65 536 segments

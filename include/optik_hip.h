@@ -251,6 +251,53 @@ int optik_hip_roadmap_query(const optik_hip_chain *chain, const double *d_nodes,
                             const double *d_gw, int32_t kg, const double *d_direct, int32_t Lmax, double *d_path,
                             int32_t *d_len, double *d_cost, int32_t *d_status, void *stream);
 
+/* Path shortcutting and equal-spacing resampling (extension; the arithmetic and its operation
+ * order: csrc/shortcut_measure.hpp).  Paths are d_path [Lin][P][n] -- the layout optik_hip_roadmap_query writes and
+ * optik_hip_path_optimize reads --, path p having d_len[p] waypoints (d_len NULL: Lin each) and padding behind them
+ * that is not looked at.  Any revolute chain of 1 .. 16 joint positions; the metric is L-infinity in radians.
+ *
+ * optik_hip_path_shortcut: each path's polyline is subdivided into at most V vertices -- its own waypoints, bit for
+ * bit, plus interior points of the motion check's interpolation at a spacing of about length / (V - len) --, EVERY
+ * pair i < j of them is checked as the motion vertex i -> vertex j at `resolution` by the motion check's own code
+ * (classify form, same stream; model, world and ee_offset7 as there; without a model every finite motion is free), and
+ * the route 0 -> last that minimises the sum of (length + hop_penalty) per hop over that visibility graph is walked: the
+ * optimum over all vertex shortcuts, deterministic.  Exact ties go to the hop that reaches furthest.  hop_penalty >= 0,
+ * in radians, keeps a detour through a collinear vertex -- equal to the direct hop up to one rounding in this metric
+ * -- from deciding the waypoint count.  Outputs, any may be NULL: d_out [Lout][P][n] the route's vertices padded with
+ * the goal; d_len_out [P] the waypoints before the padding; d_cost [P] the route's pure length summed from the goal
+ * backwards, without penalties; d_cost_in [P] the same for the input; d_status [P]:
+ *   0 route found (every hop a motion checked free in the direction of travel);
+ *   1 no route through the visibility graph (the input itself is blocked, or a piece's own samples find what its
+ *     parent segment's missed);
+ *   2 d_len[p] outside 2 .. min(Lin, V), or the route has more than Lout vertices (d_cost is then its true cost);
+ *   3 a NaN or an infinity among the path's waypoints.
+ * Unless 0 the input comes back: its waypoints (d_len[p] clamped into 2 .. Lin) padded with the goal if they fit Lout,
+ * else the start, then the goal repeated (len 2); d_cost = d_cost_in.  cost <= cost_in is not promised bit for bit
+ * (the sums round differently); the route minimises the objective above.
+ * Workspace: V (V - 1) / 2 segments per path at 16 n + 1 bytes each, the chain's, grown on demand, next to the motion
+ * check's 24 bytes per segment; the paths are processed in chunks of at most OPTIK_HIP_PATH_SHORTCUT_CHUNK_BYTES of
+ * it (optik_hip_path_shortcut_chunk: that many paths), back to back on the stream with no host synchronisation.  A
+ * path's result does not depend on P, on the chunking or on the launch shape.  One call per chain handle at a time.
+ *
+ * optik_hip_path_resample: Lout waypoints at equal arc length along each polyline: waypoint j at j / (Lout - 1) of the
+ * total length, on the segment that holds it; the ends are copied.  d_out [Lout][P][n]; d_status [P] (may be NULL): 0;
+ * 2 for d_len[p] outside 2 .. Lin (resampled as clamped); 3 for a NaN or infinite length (the start, then the goal
+ * repeated).  The new waypoints lie on the input, the new segments cut its corners: they are NOT checked.  One thread
+ * per (path, waypoint), no workspace.
+ *
+ * Both refuse with OPTIK_HIP_EINVAL before any device work: V, Lin or Lout outside 2 .. 64, P < 0 (P = 0 is a no-op)
+ * or above 2^30, a resolution that is not finite and > 0, a hop_penalty that is NaN, negative or infinite; with
+ * OPTIK_HIP_EUNSUPPORTED, also when P = 0: chains with prismatic joints. */
+#define OPTIK_HIP_PATH_SHORTCUT_MAX_VERTICES 64
+#define OPTIK_HIP_PATH_SHORTCUT_CHUNK_BYTES (256ll << 20)
+int optik_hip_path_shortcut(optik_hip_chain *chain, const double *ee_offset7, const double *d_path,
+                            const int32_t *d_len, int32_t Lin, int64_t P, int32_t V, double resolution,
+                            double hop_penalty, int32_t Lout, double *d_out, int32_t *d_len_out, double *d_cost,
+                            double *d_cost_in, int32_t *d_status, void *stream);
+int optik_hip_path_resample(const optik_hip_chain *chain, const double *d_path, const int32_t *d_len, int32_t Lin,
+                            int64_t P, int32_t Lout, double *d_out, int32_t *d_status, void *stream);
+int64_t optik_hip_path_shortcut_chunk(const optik_hip_chain *chain, int32_t V);
+
 /* The measures of solution modes 3 and 4 for B configurations d_q [n][B] (any chain of 1 .. 16 revolute joint
  * positions): d_w [B] manipulability w = sqrt(det G), d_c [B] condition c = sigma_min / sigma_max, both of the body
  * Jacobian fk_batch returns (ee_offset7 may be NULL).  Either output may be NULL.  A G that is not numerically

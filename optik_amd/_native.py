@@ -149,6 +149,11 @@ def lib():
                                           vp, vp]
     L.optik_hip_roadmap_query.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int64, vp, vp, C.c_int32,
                                           vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
+    L.optik_hip_path_shortcut.argtypes = [vp, dp, vp, vp, C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_double,
+                                          C.c_int32, vp, vp, vp, vp, vp, vp]
+    L.optik_hip_path_resample.argtypes = [vp, vp, vp, C.c_int32, C.c_int64, C.c_int32, vp, vp, vp]
+    L.optik_hip_path_shortcut_chunk.argtypes = [vp, C.c_int32]
+    L.optik_hip_path_shortcut_chunk.restype = C.c_int64
     L.optik_hip_ik_batch.argtypes = [vp, C.POINTER(SolverConfigC), vp, vp, C.c_int32, dp,
                                      C.c_uint64, C.c_uint64, C.c_uint32, C.c_double,
                                      C.POINTER(IkOutputs), vp]
@@ -213,6 +218,36 @@ def check_roadmap_args(N=1, k=1, max_waypoints=2):
                             ("max_waypoints", max_waypoints, 2, PATH_OPTIMIZE_MAX_WAYPOINTS)):
         if isinstance(v, bool) or int(v) != v or not lo <= int(v) <= hi:
             raise ValueError(f"{name} must be an integer in {lo} .. {hi}, got {v!r}")
+
+
+# include/optik_hip.h: OPTIK_HIP_PATH_SHORTCUT_MAX_VERTICES; the statuses of optik_hip_path_shortcut / _path_resample
+PATH_SHORTCUT_MAX_VERTICES = 64
+SHORTCUT_FOUND, SHORTCUT_NO_ROUTE, SHORTCUT_BAD_LENGTH, SHORTCUT_NAN = 0, 1, 2, 3
+# All-pairs visibility samples about V^2 / 6 times the path's own length: 32 vertices cost a quarter of 64
+# (profiles/shortcut_cost.txt).
+SHORTCUT_VERTICES, SHORTCUT_RESOLUTION, RESAMPLE_WAYPOINTS = 32, 0.05, 32
+
+
+def check_shortcut_args(L=2, vertices=2, max_waypoints=2, resolution=1.0, hop_penalty=0.0):
+    """The argument rules of optik_hip_path_shortcut and optik_hip_path_resample, checked on the host; returns
+    (resolution, hop_penalty) as floats, hop_penalty None meaning the resolution: a length difference below what the
+    check samples is not one the check can see."""
+    for name, v in (("L", L), ("vertices", vertices), ("max_waypoints", max_waypoints)):
+        if isinstance(v, bool) or int(v) != v or not 2 <= int(v) <= PATH_SHORTCUT_MAX_VERTICES:
+            raise ValueError(f"{name} must be an integer in 2 .. {PATH_SHORTCUT_MAX_VERTICES}, got {v!r}")
+    h = check_resolution(resolution)
+    hop = h if hop_penalty is None else float(hop_penalty)
+    if not (math.isfinite(hop) and hop >= 0.0):
+        raise ValueError(f"hop_penalty must be finite and >= 0, got {hop_penalty!r}")
+    return h, hop
+
+
+def path_shortcut_chunk(chain_handle, vertices):
+    """The paths optik_hip_path_shortcut processes per chunk of its workspace for this chain and vertex budget."""
+    c = int(lib().optik_hip_path_shortcut_chunk(chain_handle, int(vertices)))
+    if c < 1:
+        check(c)
+    return c
 
 
 def check(rc: int):

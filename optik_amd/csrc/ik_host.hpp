@@ -12,6 +12,7 @@
 //   ik_avoid.hip       clearance witnesses and gradients, collision-avoiding diff_ik (velocity dampers)
 //   ik_path_optimize.hip  covariant gradient smoothing of joint paths against the same witnesses
 //   ik_roadmap.hip     roadmap planning: nearest neighbours, motion-checked edges, shortest-path queries
+//   ik_shortcut.hip    path shortcutting over all-pairs visibility, equal-spacing resampling
 //   ik_occupancy.hip   occupancy grids and point clouds into distance-field worlds (distance transform, voxelize)
 //   ik_batch_ops.hip   objective / gradient, FK / Jacobian and seed batches, the test probes
 //   ik_lane_kernel.hip, ik_quad_kernel.hip, ik_wide_kernel.hip    the restart solvers (one restart loop each)
@@ -259,6 +260,8 @@ struct optik_hip_chain {
     optik::DeviceBuf<unsigned char> motion_ws;  // bytes
     // optik_hip_roadmap_edges (ik_roadmap.hip): the gathered segments [n][B] twice and their free flags [B]
     optik::DeviceBuf<unsigned char> roadmap_ws;  // bytes
+    // optik_hip_path_shortcut (ik_shortcut.hip): one chunk's vertex pairs as segments [n][B] twice, their free flags [B]
+    optik::DeviceBuf<unsigned char> shortcut_ws;  // bytes
     // (what the last launch's selection kernel left behind: the work-item counter at 0, this many leading
     // first-success words at ~0 -- a launch that finds them so skips its fill commands)
     // (host-side knowledge that holds for launches ORDERED behind that selection kernel: the stream it ran on is kept

@@ -1,6 +1,6 @@
 // robot_rows.cpp -- the row batches of the host API (diff_ik, manipulability, link frames, clearance, witnesses,
-// motion, roadmap plans), each one stage_rows over the robot's first device; the path optimiser's batch of paths, which stages
-// through the same batch block with a transpose of its own; and what they are checked against: the collision model,
+// motion, roadmap plans), each one stage_rows over the robot's first device; the batches of paths (the optimiser's,
+// shortcutting, resampling), which stage through the same batch block with a transpose of their own; and what they are checked against: the collision model,
 // the worlds and their builders.  (robot_host.hpp: the robot object and the shared plumbing.)
 #include <hip/hip_runtime.h>
 
@@ -23,6 +23,48 @@ constexpr int64_t kMotionChunk = (int64_t)1 << 16;  // segments per launch (each
 constexpr int64_t kWitnessChunk = (int64_t)1 << 15;  // rows per launch of the witness table (840 B a row at n = 8: 28 MB)
 constexpr int64_t kPathChunk = (int64_t)1 << 13;     // paths per launch of the path optimiser (8 KB a path at L = 64, n = 8)
 constexpr int64_t kPlanChunk = (int64_t)1 << 12;     // queries per launch of a plan (one workgroup each; 8 KB of path at Lmax = 64, n = 16)
+
+// A chunk of paths [P][L][n] with their lengths through the batch block, waypoint-major on the device ([L][chunk][n],
+// the transpose optik_robot_path_optimize makes), the int32 lengths behind them; `out_doubles` doubles per path come
+// back.  launch(d_paths, d_lens or null, Lc, d_out) queues the device work, scatter(b0, Lc, h_out) takes the results.
+template <class Launch, class Scatter>
+int stage_paths(DeviceCtx *c, const double *paths, const int32_t *lens, int64_t P, size_t nl, size_t n,
+                size_t out_doubles, Launch &&launch, Scatter &&scatter) {
+    BatchGuard guard(c);
+    if (!guard.ok()) return set_err(-1, kSetDeviceMsg);
+    const size_t w = nl * n;
+    const int64_t chunk = P < kPathChunk ? P : kPathChunk;
+    if (!reserve_batch(c, (w + 1 + out_doubles) * (size_t)chunk)) return set_err(-1, kBatchAllocMsg);
+    for (int64_t b0 = 0; b0 < P; b0 += chunk) {
+        const size_t Lc = (size_t)(P - b0 < chunk ? P - b0 : chunk), in_doubles = w * Lc + (Lc + 1) / 2;
+        double *h_in = c->h_batch.get(), *h_out = h_in + in_doubles;
+        double *d_in = c->d_batch.get(), *d_out = d_in + in_doubles;
+        parallel_ranges(Lc, [&](size_t k0, size_t k1) {
+            for (size_t k = k0; k < k1; ++k)
+                for (size_t t = 0; t < nl; ++t)
+                    std::memcpy(h_in + (t * Lc + k) * n, paths + (((size_t)b0 + k) * nl + t) * n, sizeof(double) * n);
+        });
+        if (lens) std::memcpy(h_in + w * Lc, lens + b0, sizeof(int32_t) * Lc);
+        if (hipMemcpyAsync(d_in, h_in, sizeof(double) * in_doubles, hipMemcpyHostToDevice, nullptr) != hipSuccess)
+            return set_err(-1, "upload failed");
+        if (launch(d_in, lens ? reinterpret_cast<const int32_t *>(d_in + w * Lc) : nullptr, (int64_t)Lc, d_out))
+            return set_err(-1, optik_hip_last_error());
+        if (hipMemcpyAsync(h_out, d_out, sizeof(double) * out_doubles * Lc, hipMemcpyDeviceToHost, nullptr) != hipSuccess
+            || hipStreamSynchronize(nullptr) != hipSuccess)
+            return set_err(-1, "download failed");
+        scatter((size_t)b0, Lc, h_out);
+    }
+    return 0;
+}
+
+// waypoint-major [L][Lc][n] back to rows [P][L][n]
+void scatter_paths(double *paths_out, const double *h_out, size_t b0, size_t Lc, size_t nl, size_t n) {
+    parallel_ranges(Lc, [&](size_t k0, size_t k1) {
+        for (size_t k = k0; k < k1; ++k)
+            for (size_t t = 0; t < nl; ++t)
+                std::memcpy(paths_out + ((b0 + k) * nl + t) * n, h_out + (t * Lc + k) * n, sizeof(double) * n);
+    });
+}
 
 }  // namespace
 
@@ -452,6 +494,67 @@ int optik_robot_path_optimize(const optik_robot *r, int64_t P, int32_t L, const 
         });
     }
     return 0;
+}
+
+// P paths through optik_hip_path_shortcut, staged as optik_robot_path_optimize stages its paths.
+int optik_robot_path_shortcut(const optik_robot *r, int64_t P, int32_t L, const double *paths, const int32_t *lens,
+                              int32_t vertices, double resolution, double hop_penalty, int32_t Lout,
+                              const double *ee16, double *paths_out, int32_t *len_out, double *cost_out,
+                              double *cost_in_out, int32_t *status_out) {
+    if (!r || !paths) return set_err(-1, "null argument");
+    if (P < 0) return set_err(-1, "bad argument");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    // (P = 0: the kernel layer's refusals of the chain, the sizes, the resolution and the penalty)
+    if (optik_hip_path_shortcut(c->chain, nullptr, nullptr, nullptr, L, 0, vertices, resolution, hop_penalty, Lout,
+                                nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (P == 0 || (!paths_out && !len_out && !cost_out && !cost_in_out && !status_out)) return 0;
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    const size_t n = (size_t)r->n, wo = (size_t)Lout * n;
+    // per path out: the waypoints, cost, cost_in, then len and status in one more double
+    return stage_paths(
+        c, paths, lens, P, (size_t)L, n, wo + 3,
+        [&](const double *d_in, const int32_t *d_len, int64_t Lc, double *d_out) {
+            double *d_cost = d_out + wo * (size_t)Lc, *d_cin = d_cost + Lc;
+            int32_t *d_lo = reinterpret_cast<int32_t *>(d_cin + Lc);
+            return optik_hip_path_shortcut(c->chain, ee16 ? ee7 : nullptr, d_in, d_len, L, Lc, vertices, resolution,
+                                           hop_penalty, Lout, d_out, d_lo, d_cost, d_cin, d_lo + Lc, nullptr);
+        },
+        [&](size_t b0, size_t Lc, const double *h_out) {
+            const double *h_cost = h_out + wo * Lc, *h_cin = h_cost + Lc;
+            const int32_t *h_lo = reinterpret_cast<const int32_t *>(h_cin + Lc);
+            if (paths_out) scatter_paths(paths_out, h_out, b0, Lc, (size_t)Lout, n);
+            if (cost_out) std::memcpy(cost_out + b0, h_cost, sizeof(double) * Lc);
+            if (cost_in_out) std::memcpy(cost_in_out + b0, h_cin, sizeof(double) * Lc);
+            if (len_out) std::memcpy(len_out + b0, h_lo, sizeof(int32_t) * Lc);
+            if (status_out) std::memcpy(status_out + b0, h_lo + Lc, sizeof(int32_t) * Lc);
+        });
+}
+
+// P paths through optik_hip_path_resample.
+int optik_robot_path_resample(const optik_robot *r, int64_t P, int32_t L, const double *paths, const int32_t *lens,
+                              int32_t Lout, double *paths_out, int32_t *status_out) {
+    if (!r || !paths) return set_err(-1, "null argument");
+    if (P < 0) return set_err(-1, "bad argument");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    if (optik_hip_path_resample(c->chain, nullptr, nullptr, L, 0, Lout, nullptr, nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (P == 0 || (!paths_out && !status_out)) return 0;
+    const size_t n = (size_t)r->n, wo = (size_t)Lout * n;
+    // per path out: the waypoints, then the status word in the bytes of one more double
+    return stage_paths(
+        c, paths, lens, P, (size_t)L, n, wo + 1,
+        [&](const double *d_in, const int32_t *d_len, int64_t Lc, double *d_out) {
+            return optik_hip_path_resample(c->chain, d_in, d_len, L, Lc, Lout, d_out,
+                                           reinterpret_cast<int32_t *>(d_out + wo * (size_t)Lc), nullptr);
+        },
+        [&](size_t b0, size_t Lc, const double *h_out) {
+            if (paths_out) scatter_paths(paths_out, h_out, b0, Lc, (size_t)Lout, n);
+            if (status_out) std::memcpy(status_out + b0, h_out + wo * Lc, sizeof(int32_t) * Lc);
+        });
 }
 
 // The roadmap (include/optik.h): N seeds of the restart generator as nodes, their k nearest others and the checked

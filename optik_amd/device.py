@@ -424,6 +424,57 @@ class HipChain:
         direct = self.roadmap_edges(starts, goals, None, resolution, ee_offset7=ee_offset7)
         return self.roadmap_query(nodes, nbr, w, starts, goals, sidx, sw, gidx, gw, direct, Lmax)
 
+    # -- shortcutting and resampling (include/optik_hip.h) --------------------------------
+    def _check_paths(self, path, lens):
+        if not (isinstance(path, torch.Tensor) and path.is_cuda and path.dtype == torch.float64 and path.dim() == 3
+                and path.shape[2] == self.n and path.is_contiguous()):
+            raise ValueError(f"path must be a contiguous float64 cuda tensor [L, P, n] with n = {self.n}")
+        L, P = int(path.shape[0]), int(path.shape[1])
+        if lens is not None and not (isinstance(lens, torch.Tensor) and lens.is_cuda and lens.dtype == torch.int32
+                                     and lens.numel() == P and lens.is_contiguous() and lens.device == path.device):
+            raise ValueError(f"lens must be a contiguous int32 cuda tensor of {P} lengths on path's device")
+        return L, P
+
+    def path_shortcut(self, path, lens=None, resolution=nat.SHORTCUT_RESOLUTION, vertices=nat.SHORTCUT_VERTICES,
+                      hop_penalty=None, max_waypoints=None, ee_offset7=None):
+        """Shortcuts P paths over the all-pairs visibility of at most `vertices` vertices each
+        (optik_hip_path_shortcut): path [L, P, n] float64 cuda tensor and lens [P] int32 (None: L each) -- roadmap_plan's
+        "path" and "len" as they are.  hop_penalty None: the resolution.  max_waypoints None: L.  Stream-ordered on the
+        current stream; returns a dict of device tensors: path [max_waypoints, P, n] (what path_optimize takes), len
+        [P] int32, cost [P], cost_in [P], status [P] int32 (nat.SHORTCUT_*)."""
+        L, P = self._check_paths(path, lens)
+        Lout = L if max_waypoints is None else max_waypoints
+        h, hop = nat.check_shortcut_args(L, vertices, Lout, resolution, hop_penalty)
+        ee = self._ee7(ee_offset7)
+        dev = path.device
+        res = dict(path=torch.empty((int(Lout), P, self.n), dtype=torch.float64, device=dev),
+                   len=torch.empty(P, dtype=torch.int32, device=dev),
+                   cost=torch.empty(P, dtype=torch.float64, device=dev),
+                   cost_in=torch.empty(P, dtype=torch.float64, device=dev),
+                   status=torch.empty(P, dtype=torch.int32, device=dev))
+        nat.check(nat.lib().optik_hip_path_shortcut(
+            self._h, _dp(ee) if ee is not None else None, _ptr(path), _ptr(lens), L, P, int(vertices), h, hop,
+            int(Lout), _ptr(res["path"]), _ptr(res["len"]), _ptr(res["cost"]), _ptr(res["cost_in"]),
+            _ptr(res["status"]), _stream_ptr()))
+        return res
+
+    def path_resample(self, path, lens=None, waypoints=nat.RESAMPLE_WAYPOINTS):
+        """`waypoints` waypoints at equal arc length (L-infinity) along each of P polylines
+        (optik_hip_path_resample): path [L, P, n], lens [P] int32 or None as path_shortcut takes them.  Returns (path
+        [waypoints, P, n], status [P] int32).  The new segments cut the input's corners and are not checked.
+        Stream-ordered."""
+        L, P = self._check_paths(path, lens)
+        nat.check_shortcut_args(L, max_waypoints=waypoints)
+        out = torch.empty((int(waypoints), P, self.n), dtype=torch.float64, device=path.device)
+        status = torch.empty(P, dtype=torch.int32, device=path.device)
+        nat.check(nat.lib().optik_hip_path_resample(self._h, _ptr(path), _ptr(lens), L, P, int(waypoints), _ptr(out),
+                                                    _ptr(status), _stream_ptr()))
+        return out, status
+
+    def path_shortcut_chunk(self, vertices):
+        """The paths path_shortcut processes per chunk of its workspace (tests cross it)."""
+        return nat.path_shortcut_chunk(self._h, vertices)
+
     def seed_batch(self, first, count):
         q = torch.empty((self.n, count), dtype=torch.float64, device=self.device)
         nat.check(nat.lib().optik_hip_seed_batch(self._h, int(first), int(count), _ptr(q), _stream_ptr()))

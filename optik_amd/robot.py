@@ -66,6 +66,9 @@ def _bind(L):
     L.optik_robot_roadmap_build.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_uint64]
     L.optik_robot_roadmap_build.restype = C.c_int64
     L.optik_robot_roadmap_plan.argtypes = [vp, dp, dp, C.c_int64, C.c_int32, dp, ip, dp, ip]
+    L.optik_robot_path_shortcut.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, C.c_int32, C.c_double, C.c_double, C.c_int32,
+                                            dp, dp, ip, dp, dp, ip]
+    L.optik_robot_path_resample.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, C.c_int32, dp, ip]
     L.optik_robot_joint_jacobian_ex.argtypes = [vp, dp, dp, dp]
     L.optik_robot_set_devices.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32]
     L.optik_robot_num_devices.argtypes = [vp]
@@ -773,6 +776,75 @@ class Robot:
                                             _dp(cost), status.ctypes.data_as(ip)):
             raise RuntimeError(_err(self._L))
         return dict(paths=paths, len=ln, cost=cost, status=status)
+
+    # -- shortcutting and resampling (extension; include/optik.h) ---------------------------
+    def _check_paths(self, paths, lens):
+        n = self.num_positions()
+        paths = np.ascontiguousarray(paths, dtype=np.float64)
+        if paths.ndim != 3 or paths.shape[2] != n:
+            raise ValueError(f"paths must be [P, L, n] with n = {n}, got {list(paths.shape)}")
+        if lens is not None:
+            lens = np.ascontiguousarray(lens, dtype=np.int32)
+            if lens.shape != (paths.shape[0],):
+                raise ValueError(f"lens must be [P] with P = {paths.shape[0]}, got {list(lens.shape)}")
+        return paths, lens
+
+    def shortcut_paths(self, paths, lens=None, resolution=nat.SHORTCUT_RESOLUTION, vertices=nat.SHORTCUT_VERTICES,
+                       hop_penalty=None, max_waypoints=None, ee_offset=None):
+        """Shortcuts P joint-space paths `paths` [P, L, n] with `lens` [P] waypoints each (None: L each) -- plan_paths'
+        "paths" and "len" as they are --, all on the GPU: each polyline is subdivided into at most `vertices` (2 .. 64)
+        vertices, its own waypoints among them, EVERY pair of vertices is checked as a motion at `resolution` against
+        the collision model and world, and the route of least (L-infinity length + hop_penalty) per hop through that
+        visibility graph is walked: the optimum over all vertex shortcuts, deterministic.  hop_penalty (radians; None:
+        the resolution) keeps detours of equal length up to a rounding from adding waypoints.  Returns a dict: paths
+        [P, max_waypoints, n] (None: L) padded with the goal, len [P] int32, cost [P] and cost_in [P] (the route's
+        and the input's length, without penalties), status [P] int32: 0 found -- every segment a motion checked free
+        in the direction of travel --, 1 no route (the input is blocked at this resolution), 2 a length outside 2 ..
+        min(L, vertices) or a route of more than max_waypoints, 3 a NaN or an infinity; unless 0 the input comes back.
+        All-pairs visibility samples about vertices^2 / 6 times the path's own length: 64 vertices cost about four
+        times what 32 do (profiles/shortcut_cost.txt).  The stored roadmap is neither read nor required.
+        ValueError for L, vertices or max_waypoints outside 2 .. 64, a resolution that is not finite and > 0, a
+        hop_penalty that is NaN, negative or infinite."""
+        paths, lens = self._check_paths(paths, lens)
+        P, L, n = paths.shape
+        Lout = L if max_waypoints is None else max_waypoints
+        h, hop = nat.check_shortcut_args(L, vertices, Lout, resolution, hop_penalty)
+        Lout = int(Lout)
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        out, cost, cost_in = np.zeros((P, Lout, n)), np.zeros(P), np.zeros(P)
+        ln, status = np.zeros(P, dtype=np.int32), np.zeros(P, dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        if self._L.optik_robot_path_shortcut(self._h, P, L, _dp(paths), lens.ctypes.data_as(ip) if lens is not None else None,
+                                             int(vertices), h, hop, Lout, _dp(ee) if ee is not None else None,
+                                             _dp(out), ln.ctypes.data_as(ip), _dp(cost), _dp(cost_in),
+                                             status.ctypes.data_as(ip)):
+            raise RuntimeError(_err(self._L))
+        return dict(paths=out, len=ln, cost=cost, cost_in=cost_in, status=status)
+
+    def resample_paths(self, paths, lens=None, waypoints=nat.RESAMPLE_WAYPOINTS, resolution=None, ee_offset=None):
+        """`waypoints` (2 .. 64) waypoints at equal L-infinity arc length along each of P polylines `paths` [P, L, n]
+        with `lens` [P] waypoints each (None: L each): the dense, evenly spaced path optimize_paths and a controller
+        take.  The ends are copied; every other waypoint lies on the input.  Returns (paths [P, waypoints, n], status
+        [P] int32: 0, 2 for a length outside 2 .. L, 3 for a NaN or infinite length).  The new segments cut the
+        input's corners, so they are NOT free by construction: with `resolution` it also returns free [P] bool, whether
+        each of the waypoints - 1 new segments passes collision_motion_batch_arrays at that resolution.
+        ValueError for L or waypoints outside 2 .. 64 or a bad resolution."""
+        paths, lens = self._check_paths(paths, lens)
+        P, L, n = paths.shape
+        nat.check_shortcut_args(L, max_waypoints=waypoints)
+        if resolution is not None:
+            resolution = nat.check_resolution(resolution)
+        W = int(waypoints)
+        out, status = np.zeros((P, W, n)), np.zeros(P, dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        if self._L.optik_robot_path_resample(self._h, P, L, _dp(paths), lens.ctypes.data_as(ip) if lens is not None else None,
+                                             W, _dp(out), status.ctypes.data_as(ip)):
+            raise RuntimeError(_err(self._L))
+        if resolution is None:
+            return out, status
+        seg_free = self.collision_motion_batch_arrays(out[:, :-1].reshape(-1, n), out[:, 1:].reshape(-1, n),
+                                                      resolution, ee_offset)[1]
+        return out, status, seg_free.reshape(P, W - 1).all(axis=1)
 
     # -- the motion check (extension; include/optik.h, DESIGN.md section 5.13) ------------------------------------
     def collision_motion_batch_arrays(self, xa, xb, resolution, ee_offset=None):
