@@ -271,6 +271,26 @@ int optik_robot_path_shortcut(const optik_robot *robot, int64_t P, int32_t L, co
                               double *cost_in_out, int32_t *status_out);
 int optik_robot_path_resample(const optik_robot *robot, int64_t P, int32_t L, const double *paths, const int32_t *lens,
                               int32_t Lout, double *paths_out, int32_t *status_out);
+/* Timing planned paths and sampling the trajectory (extension; include/optik_hip.h: optik_hip_path_time and
+ * optik_hip_trajectory_sample).  paths [P][L][n] row-major with lens [P] waypoints each (NULL: L
+ * each), 3 <= L <= 64 -- optik_robot_path_resample's paths_out as it is.
+ * optik_robot_path_time: rest-to-rest timing under v_max [n] (> 0, may be +inf) and a_max [n] (finite, > 0) ->
+ * times_out [P][L], vel_out [P][L][n], acc_out [P][L][n], duration_out [P], status_out [P]: 0 timed; 1 stalled (a
+ * segment with zero speed at both ends); 2 a length outside 3 .. L or a stage that bounds nothing; 3 a NaN or an
+ * infinity in the path; unless 0 the times and the duration are NaN.
+ * optik_robot_trajectory_sample: T (1 .. 65 536) samples per path at k * dt by cubic Hermite interpolation over what
+ * optik_robot_path_time returned -> q_out [P][T][n], qd_out [P][T][n]; past the duration the goal at rest, for a status
+ * other than 0 the start at rest.  The samples are not checked for collision.
+ * optik_robot_velocity_limits: the URDF's <limit velocity=> of the n articulated joints, +inf where it is absent, 0
+ * or negative; a malloc'ed array of n doubles the caller frees.
+ * Any output may be NULL.  On the robot's first device.  rc 0, or -1: null argument, what the kernel layer refuses. */
+int optik_robot_path_time(const optik_robot *robot, int64_t P, int32_t L, const double *paths, const int32_t *lens,
+                          const double *v_max, const double *a_max, double *times_out, double *vel_out,
+                          double *acc_out, double *duration_out, int32_t *status_out);
+int optik_robot_trajectory_sample(const optik_robot *robot, int64_t P, int32_t L, const double *paths,
+                                  const int32_t *lens, const double *times, const double *velocities,
+                                  const int32_t *status, double dt, int32_t T, double *q_out, double *qd_out);
+const double *optik_robot_velocity_limits(const optik_robot *robot);
 /* The motion check (extension; include/optik_hip.h: optik_hip_collision_motion_batch and what precedes it).  B segments
  * xa, xb [B][n] row-major at `resolution` (finite, > 0) -> clearance_out [B], free_out [B], first_out [B], steps_out
  * [B]; any may be NULL (clearance_out NULL: the call only classifies).  On the robot's first device, 65 536 segments

@@ -298,6 +298,45 @@ int optik_hip_path_resample(const optik_hip_chain *chain, const double *d_path, 
                             int64_t P, int32_t Lout, double *d_out, int32_t *d_status, void *stream);
 int64_t optik_hip_path_shortcut_chunk(const optik_hip_chain *chain, int32_t V);
 
+/* Timing of joint paths under velocity and acceleration limits, and the sampling of the timed trajectory (extension;
+ * DESIGN.md section 5.20; the arithmetic and its operation order: csrc/time_measure.hpp).  Paths are d_path [L][P][n]
+ * as above, path p having d_len[p] waypoints (d_len NULL: L each), 3 <= d_len[p] <= L <= 64.  Any revolute chain of
+ * 1 .. 16 joint positions.
+ *
+ * optik_hip_path_time: time-optimal path parameterisation by reachability analysis (TOPP-RA) in its collocation form
+ * on the path's own waypoints, rest to rest, under d_vmax [n] (> 0, may be +inf) and d_amax [n] (finite, > 0), both
+ * in device memory.  One backward pass gives the largest admissible squared path speed per waypoint in closed form,
+ * one greedy forward pass the profile: always feasible, optimal where the path is dense and gently curved (every
+ * |second difference| <= |first difference| / 2); elsewhere it is longer than the optimum, stops at sharp corners,
+ * and on a jagged path two neighbouring stops give status 1 (about a third of unbiased random walks; time_measure.hpp).
+ * The grid step is the waypoint index, so evenly spaced input -- optik_hip_path_resample's -- is what it is
+ * meant for.  Outputs, any may be NULL: d_t [L][P] the time of each waypoint from t = 0; d_qd and d_qdd [L][P][n] the
+ * joint velocities and accelerations there; d_x [L][P] the squared path speed; d_duration [P]; d_status [P]:
+ *   0 timed (behind the path's own waypoints: the duration, zero velocity, acceleration and x);
+ *   1 a segment whose two ends both have x = 0, or a duration that is not finite;
+ *   2 d_len[p] outside 3 .. L, or a stage that bounds nothing (a waypoint repeated three times, or twice at the start);
+ *   3 a NaN or an infinity among the path's waypoints.
+ * Unless 0 every time and the duration are NaN; status 1 still writes its x, velocities and accelerations (they satisfy
+ * every limit, the profile just never leaves a waypoint), 2 and 3 write 0 for them.  One wave per path, no workspace; a path's
+ * result does not depend on P or on the launch shape and is bit for bit time_measure.hpp's serial reference.
+ *
+ * optik_hip_trajectory_sample: Tout samples of each timed path at tau = k * dt, k = 0 .. Tout - 1, by cubic Hermite
+ * interpolation in time over the waypoints' (time, position, velocity): d_q and d_qd_out [Tout][P][n].  tau >= the
+ * duration gives the goal with zero velocity; a path whose status is not 0 gives its start with zero velocity.  The
+ * curve leaves the polyline between waypoints: it is NOT checked here.  One thread per (path, sample).
+ *
+ * Both refuse with OPTIK_HIP_EINVAL before any device work: L outside 3 .. 64, P < 0 (P = 0 is a no-op) or above
+ * 2^30, a dt that is not finite and > 0, Tout outside 1 .. OPTIK_HIP_TRAJECTORY_MAX_SAMPLES; with
+ * OPTIK_HIP_EUNSUPPORTED, also when P = 0: chains with prismatic joints, whose limits are not radians. */
+#define OPTIK_HIP_PATH_TIME_MAX_WAYPOINTS 64
+#define OPTIK_HIP_TRAJECTORY_MAX_SAMPLES 65536
+int optik_hip_path_time(const optik_hip_chain *chain, const double *d_path, const int32_t *d_len, int32_t L, int64_t P,
+                        const double *d_vmax, const double *d_amax, double *d_t, double *d_qd, double *d_qdd,
+                        double *d_x, double *d_duration, int32_t *d_status, void *stream);
+int optik_hip_trajectory_sample(const optik_hip_chain *chain, const double *d_path, const int32_t *d_len, int32_t L,
+                                int64_t P, const double *d_t, const double *d_qd, const int32_t *d_status, double dt,
+                                int32_t Tout, double *d_q, double *d_qd_out, void *stream);
+
 /* The measures of solution modes 3 and 4 for B configurations d_q [n][B] (any chain of 1 .. 16 revolute joint
  * positions): d_w [B] manipulability w = sqrt(det G), d_c [B] condition c = sigma_min / sigma_max, both of the body
  * Jacobian fk_batch returns (ee_offset7 may be NULL).  Either output may be NULL.  A G that is not numerically

@@ -153,6 +153,9 @@ def lib():
                                           C.c_int32, vp, vp, vp, vp, vp, vp]
     L.optik_hip_path_resample.argtypes = [vp, vp, vp, C.c_int32, C.c_int64, C.c_int32, vp, vp, vp]
     L.optik_hip_path_shortcut_chunk.argtypes = [vp, C.c_int32]
+    L.optik_hip_path_time.argtypes = [vp, vp, vp, C.c_int32, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.optik_hip_trajectory_sample.argtypes = [vp, vp, vp, C.c_int32, C.c_int64, vp, vp, vp, C.c_double, C.c_int32, vp,
+                                              vp, vp]
     L.optik_hip_path_shortcut_chunk.restype = C.c_int64
     L.optik_hip_ik_batch.argtypes = [vp, C.POINTER(SolverConfigC), vp, vp, C.c_int32, dp,
                                      C.c_uint64, C.c_uint64, C.c_uint32, C.c_double,
@@ -248,6 +251,45 @@ def path_shortcut_chunk(chain_handle, vertices):
     if c < 1:
         check(c)
     return c
+
+
+# include/optik_hip.h: OPTIK_HIP_PATH_TIME_MAX_WAYPOINTS, OPTIK_HIP_TRAJECTORY_MAX_SAMPLES; optik_hip_path_time's statuses
+PATH_TIME_MIN_WAYPOINTS, PATH_TIME_MAX_WAYPOINTS, TRAJECTORY_MAX_SAMPLES = 3, 64, 65536
+TIME_TIMED, TIME_STALLED, TIME_BAD_LENGTH, TIME_NAN = 0, 1, 2, 3
+
+
+def check_time_args(n, L=3, a_max=1.0, v_max=math.inf, scale=1.0):
+    """The argument rules of optik_hip_path_time, checked on the host; returns (v_max [n], a_max [n]) as float64
+    arrays, each a scalar or n values, both multiplied by `scale` in (0, 1].  a_max must be finite and > 0, v_max > 0
+    (+inf: no velocity limit)."""
+    import numpy as np
+    if isinstance(L, bool) or int(L) != L or not PATH_TIME_MIN_WAYPOINTS <= int(L) <= PATH_TIME_MAX_WAYPOINTS:
+        raise ValueError(f"L must be an integer in {PATH_TIME_MIN_WAYPOINTS} .. {PATH_TIME_MAX_WAYPOINTS}, got {L!r}")
+    scale = float(scale)
+    if not 0.0 < scale <= 1.0:
+        raise ValueError(f"scale must be in (0, 1], got {scale!r}")
+    out = []
+    for name, v in (("v_max", v_max), ("a_max", a_max)):
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != n):
+            raise ValueError(f"{name} must be a scalar or [n] with n = {n}, got shape {list(a.shape)}")
+        out.append(np.ascontiguousarray(np.broadcast_to(a, (n,))) * scale)
+    v, a = out
+    if not np.all(v > 0.0):
+        raise ValueError(f"v_max must be > 0 (inf: no limit), got {v_max!r}")
+    if not np.all(np.isfinite(a) & (a > 0.0)):
+        raise ValueError(f"a_max must be finite and > 0, got {a_max!r}")
+    return v, a
+
+
+def check_sample_args(dt, T=1):
+    """The argument rules of optik_hip_trajectory_sample; returns dt as a float."""
+    dt = float(dt)
+    if not (math.isfinite(dt) and dt > 0.0):
+        raise ValueError(f"dt must be finite and > 0, got {dt!r}")
+    if isinstance(T, bool) or int(T) != T or not 1 <= int(T) <= TRAJECTORY_MAX_SAMPLES:
+        raise ValueError(f"a trajectory has 1 .. {TRAJECTORY_MAX_SAMPLES} samples, got {T!r}: raise dt")
+    return dt
 
 
 def check(rc: int):

@@ -1,0 +1,243 @@
+// ik_time.hip -- velocity- and acceleration-limited timing of joint paths and the sampling of the timed trajectory on
+// the device (time_measure.hpp: the arithmetic and its operation order).
+// optik_hip_path_time / _trajectory_sample (include/optik_hip.h).
+//
+//   path_time_kernel           one wave per path.  The waypoints are staged [joint][64] in LDS (lane t reads its own
+//                              column without a bank conflict, a stage's column is a broadcast); lane i forms d and c of
+//                              waypoint i, the stage's members [joint][64] and its cap.  Both passes are serial in i.  In
+//                              the backward pass the lanes split the (n + 1)^2 pairs of the stage -- 4 at n = 1, 289 at
+//                              n = 16 -- and a butterfly takes the minimum, which is exact in any order; in the forward
+//                              pass lane l holds joint l & 15, so every group of 16 lanes ends with the same minimum
+//                              after four butterfly steps.  The square roots and the segment times are the owning
+//                              lanes', the time prefix is lane 0's, in the header's order.  Dynamic LDS: (3 n + 5) * 64
+//                              doubles (4 608 bytes at n = 1, 13 824 at n = 7, 27 136 at n = 16); no workspace.
+//   trajectory_sample_kernel   one thread per (path, sample), the path running fastest so that a wave writes
+//                              neighbouring paths (beyond 2^28 samples a thread strides on); no LDS, no workspace.
+//
+// A path's block sees only that path, so nothing depends on P or on the launch shape.
+#include "collision_device.hpp"
+#include "time_measure.hpp"
+
+using namespace optik;
+using namespace optik::host;
+using namespace optik::colldev;
+
+static_assert(timing::MAX_POINTS == OPTIK_HIP_PATH_TIME_MAX_WAYPOINTS && timing::MAX_POINTS == 64,
+              "one lane of a wave per waypoint");
+static_assert(timing::MAX_JOINTS == WIDE_MAX_DOF && timing::MAX_JOINTS == 16,
+              "time_measure.hpp states the cap on the joint positions; the forward pass folds 16 lanes");
+
+namespace {
+
+constexpr int TM_WAVE = 64, SAMPLE_BLOCK = 256;
+constexpr int MP = timing::MAX_POINTS;
+constexpr long long MAX_PATHS = 1ll << 30;
+constexpr long long SAMPLE_MAX_GRID = 1ll << 20;  // blocks; a thread strides over the rest
+
+struct TimeLaunch {
+    const double *path;  // [L][P][n]
+    const int32_t *len;  // [P] or null: L
+    const double *vmax, *amax;  // [n]
+    long long P;
+    int n, L;
+    double *t;         // [L][P] or null
+    double *qd, *qdd;  // [L][P][n] or null
+    double *x;         // [L][P] or null
+    double *duration;  // [P] or null
+    int32_t *status;   // [P] or null
+};
+
+__device__ __forceinline__ double wave_min(double b, int first) {
+#pragma unroll
+    for (int o = first; o >= 1; o >>= 1) b = timing::take_min(b, __shfl_xor(b, o, TM_WAVE));
+    return b;
+}
+
+__global__ __launch_bounds__(TM_WAVE) void path_time_kernel(const TimeLaunch a) {
+    extern __shared__ double tm_lds[];
+    const int n = a.n, L = a.L, lane = threadIdx.x;
+    double *q = tm_lds;          // [n][64] joint j of waypoint t at q[j * 64 + t]
+    double *s = q + n * MP;      // [n][64] the members' slopes, stage i at s[j * 64 + i]
+    double *k = s + n * MP;      // [n][64] and offsets
+    double *bet = k + n * MP;    // [64] xcap, then beta
+    double *xs = bet + MP;       // [64]
+    double *rt = xs + MP;        // [64] sqrt x
+    double *seg = rt + MP;       // [64] segment times
+    double *ts = seg + MP;       // [64]
+    const long long p = blockIdx.x;
+    const double *path = a.path + p * n;
+    const long long st = a.P * n;
+    const int m = __builtin_amdgcn_readfirstlane(a.len ? a.len[p] : L);
+    int status = timing::TIMED;
+    if (!timing::length_ok(m, L)) status = timing::BAD_LENGTH;
+    if (status == timing::TIMED) {
+        bool fin = true;
+        if (lane < m)
+            for (int j = 0; j < n; ++j) {
+                const double v = path[lane * st + j];
+                q[j * MP + lane] = v;
+                fin = fin && timing::is_finite(v);
+            }
+        if (!__syncthreads_and(fin)) status = timing::PATH_NAN;
+    }
+    double duration = timing::nan();
+    double x_mine = 0.0;
+    if (status == timing::TIMED) {
+        // the stage of lane i: members and cap
+        if (lane < m - 1) {
+            double cap = timing::inf();
+            for (int j = 0; j < n; ++j) {
+                const double d = timing::deriv_d(q + j * MP, 1, m, lane), c = timing::deriv_c(q + j * MP, 1, m, lane);
+                const double aj = a.amax[j];
+                const timing::Member mb = timing::member(d, c, aj);
+                s[j * MP + lane] = mb.s;
+                k[j * MP + lane] = mb.k;
+                cap = timing::take_min(cap, timing::cap_term(d, c, a.vmax[j], aj));
+            }
+            bet[lane] = cap;
+        }
+        __syncthreads();
+        // backward
+        const int pairs = (n + 1) * (n + 1);
+        double bnext = 0.0, beta_mine = 0.0;  // beta_(m-1)
+        bool unbounded = false;
+        for (int i = m - 2; i >= 0; --i) {
+            double b = bet[i];
+            for (int e = lane; e < pairs; e += TM_WAVE)
+                b = timing::take_min(b, timing::stage_pair(n, s + i, k + i, MP, bnext, e));
+            b = wave_min(b, TM_WAVE / 2);
+            if (lane == i) beta_mine = b;
+            if (!(b < timing::inf())) unbounded = true;
+            bnext = b;
+        }
+        __syncthreads();
+        if (lane < m) bet[lane] = beta_mine;
+        __syncthreads();
+        if (unbounded) status = timing::UNBOUNDED;
+    }
+    if (status == timing::TIMED) {
+        // forward
+        const int j = lane & (timing::MAX_JOINTS - 1);
+        double xi = 0.0;
+        for (int i = 0; i < m - 1; ++i) {
+            double h = timing::inf();
+            if (j < n) h = timing::take_min(h, timing::hi_value(s[j * MP + i], k[j * MP + i], xi));
+            h = wave_min(h, timing::MAX_JOINTS / 2);
+            h = timing::take_min(h, bet[i + 1]);
+            xi = timing::clamp_x(h);
+            if (lane == i + 1) x_mine = xi;
+        }
+        if (lane < m) {
+            xs[lane] = x_mine;
+            rt[lane] = timing::tm_sqrt(x_mine);
+        }
+        __syncthreads();
+        bool bad = false;
+        if (lane < m - 1) {
+            bad = timing::segment_bad(rt[lane], rt[lane + 1]);
+            seg[lane] = timing::segment_time(rt[lane], rt[lane + 1]);
+        }
+        const bool any_bad = __syncthreads_or(bad) != 0;
+        if (lane == 0) {
+            double acc = 0.0;
+            ts[0] = acc;
+            for (int i = 0; i < m - 1; ++i) {
+                acc = acc + seg[i];
+                ts[i + 1] = acc;
+            }
+        }
+        __syncthreads();
+        duration = ts[m - 1];
+        if (any_bad || !timing::is_finite(duration)) status = timing::STALLED;
+    }
+    const bool timed = status == timing::TIMED;
+    if (!timed) duration = timing::nan();
+    if (lane == 0) {
+        if (a.duration) a.duration[p] = duration;
+        if (a.status) a.status[p] = status;
+    }
+    if (lane >= L) return;
+    const bool own = (timed || status == timing::STALLED) && lane < m;  // (STALLED: the profile is still written)
+    if (a.t) a.t[(long long)lane * a.P + p] = timed && lane < m ? ts[lane] : duration;
+    if (a.x) a.x[(long long)lane * a.P + p] = own ? x_mine : 0.0;
+    if (!a.qd && !a.qdd) return;
+    const long long o = ((long long)lane * a.P + p) * n;
+    for (int j = 0; j < n; ++j) {
+        double v = 0.0, acc = 0.0;
+        if (own) {
+            const double d = timing::deriv_d(q + j * MP, 1, m, lane), c = timing::deriv_c(q + j * MP, 1, m, lane);
+            v = timing::out_qd(d, rt[lane]);
+            if (lane < m - 1) acc = timing::out_qdd(d, timing::accel_u(x_mine, xs[lane + 1]), c, x_mine);
+        }
+        if (a.qd) a.qd[o + j] = v;
+        if (a.qdd) a.qdd[o + j] = acc;
+    }
+}
+
+struct SampleLaunch {
+    const double *path;     // [L][P][n]
+    const int32_t *len;     // [P] or null: L
+    const double *t;        // [L][P]
+    const double *qd;       // [L][P][n]
+    const int32_t *status;  // [P]
+    long long P;
+    int n, L, Tout;
+    double dt;
+    double *q_out, *v_out;  // [Tout][P][n]
+};
+
+__global__ __launch_bounds__(SAMPLE_BLOCK) void trajectory_sample_kernel(const SampleLaunch a) {
+    const long long total = a.P * a.Tout, stride = (long long)gridDim.x * SAMPLE_BLOCK;
+    for (long long g = (long long)blockIdx.x * SAMPLE_BLOCK + threadIdx.x; g < total; g += stride) {
+        const long long k = g / a.P, p = g % a.P;
+        const long long o = g * a.n;
+        timing::sample_waypoint(a.n, a.path + p * a.n, a.P * a.n, a.len ? a.len[p] : a.L, a.L, a.t + p, a.P,
+                                a.qd + p * a.n, a.status[p], a.dt, k, a.q_out + o, a.v_out + o, 1);
+    }
+}
+
+bool points_ok(int v) { return v >= timing::MIN_POINTS && v <= timing::MAX_POINTS; }
+
+}  // namespace
+
+extern "C" {
+
+int optik_hip_path_time(const optik_hip_chain *ch, const double *d_path, const int32_t *d_len, int32_t L, int64_t P,
+                        const double *d_vmax, const double *d_amax, double *d_t, double *d_qd, double *d_qdd,
+                        double *d_x, double *d_duration, int32_t *d_status, void *stream) {
+    if (!ch || P < 0) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    if (!points_ok(L)) return fail(OPTIK_HIP_EINVAL, "path_time: a path has 3 .. 64 waypoints");
+    if (P > MAX_PATHS) return fail(OPTIK_HIP_EINVAL, "path_time: more than 2^30 paths in one launch");
+    if (ch->prismatic) return fail(OPTIK_HIP_EUNSUPPORTED, prismatic_msg());
+    if (P == 0 || (!d_t && !d_qd && !d_qdd && !d_x && !d_duration && !d_status)) return 0;
+    if (!d_path || !d_vmax || !d_amax) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    BIND_DEVICE(ch);
+    TimeLaunch a{d_path, d_len, d_vmax, d_amax, P, ch->n, L, d_t, d_qd, d_qdd, d_x, d_duration, d_status};
+    const size_t lds = sizeof(double) * (size_t)(3 * ch->n + 5) * MP;
+    hipLaunchKernelGGL(path_time_kernel, dim3((unsigned)P), dim3(TM_WAVE), lds, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int optik_hip_trajectory_sample(const optik_hip_chain *ch, const double *d_path, const int32_t *d_len, int32_t L,
+                                int64_t P, const double *d_t, const double *d_qd, const int32_t *d_status, double dt,
+                                int32_t Tout, double *d_q, double *d_qd_out, void *stream) {
+    if (!ch || P < 0) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    if (!points_ok(L)) return fail(OPTIK_HIP_EINVAL, "trajectory_sample: a path has 3 .. 64 waypoints");
+    if (P > MAX_PATHS) return fail(OPTIK_HIP_EINVAL, "trajectory_sample: more than 2^30 paths in one launch");
+    if (!(dt > 0.0) || !std::isfinite(dt)) return fail(OPTIK_HIP_EINVAL, "trajectory_sample: dt must be finite and > 0");
+    if (Tout < 1 || Tout > OPTIK_HIP_TRAJECTORY_MAX_SAMPLES)
+        return fail(OPTIK_HIP_EINVAL, "trajectory_sample: 1 .. 65536 samples per path");
+    if (ch->prismatic) return fail(OPTIK_HIP_EUNSUPPORTED, prismatic_msg());
+    if (P == 0) return 0;
+    if (!d_path || !d_t || !d_qd || !d_status || !d_q || !d_qd_out) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    BIND_DEVICE(ch);
+    SampleLaunch a{d_path, d_len, d_t, d_qd, d_status, P, ch->n, L, Tout, dt, d_q, d_qd_out};
+    const long long blocks = (P * Tout + SAMPLE_BLOCK - 1) / SAMPLE_BLOCK;
+    const unsigned grid = (unsigned)(blocks < SAMPLE_MAX_GRID ? blocks : SAMPLE_MAX_GRID);
+    hipLaunchKernelGGL(trajectory_sample_kernel, dim3(grid), dim3(SAMPLE_BLOCK), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

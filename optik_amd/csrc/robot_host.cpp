@@ -80,6 +80,7 @@ optik_robot *make_robot(const std::string &urdf, const char *base, const char *e
         if (j.kind != optik_host::FIXED) {  // joint_limits(), lib.rs:78-84
             r->lb.push_back(j.lower);
             r->ub.push_back(j.upper);
+            r->vel.push_back(j.velocity);
         }
     }
     r->device_ids = devices_from_env();
@@ -577,6 +578,8 @@ const double *optik_robot_joint_limits(const optik_robot *r) {
     v.insert(v.end(), r->ub.begin(), r->ub.end());
     return malloc_copy(v.data(), v.size());
 }
+
+const double *optik_robot_velocity_limits(const optik_robot *r) { return malloc_copy(r->vel.data(), r->vel.size()); }
 
 int optik_robot_fk_ex(const optik_robot *r, const double *x, const double *ee16, double *pose16) {
     double p7[7];

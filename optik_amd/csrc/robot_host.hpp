@@ -50,6 +50,7 @@ struct optik_robot {
     optik_host::Chain chain;
     int n = 0;
     std::vector<double> lb, ub;
+    std::vector<double> vel;  // the URDF's velocity limits of the n joint positions (+inf: none)
     std::vector<double> origins, axes;  // n_joints x 7, n_joints x 3
     std::vector<int32_t> types;
     // set_parallelism (lib.rs:66-72).  The rayon pool size has no counterpart, but its one

@@ -1,6 +1,6 @@
 // robot_rows.cpp -- the row batches of the host API (diff_ik, manipulability, link frames, clearance, witnesses,
 // motion, roadmap plans), each one stage_rows over the robot's first device; the batches of paths (the optimiser's,
-// shortcutting, resampling), which stage through the same batch block with a transpose of their own; and what they are checked against: the collision model,
+// shortcutting, resampling, timing, sampling), which stage through the same batch block with a transpose of their own; and what they are checked against: the collision model,
 // the worlds and their builders.  (robot_host.hpp: the robot object and the shared plumbing.)
 #include <hip/hip_runtime.h>
 
@@ -22,21 +22,27 @@ constexpr int64_t kRowChunk = (int64_t)1 << 18;     // rows per launch
 constexpr int64_t kMotionChunk = (int64_t)1 << 16;  // segments per launch (each is many samples)
 constexpr int64_t kWitnessChunk = (int64_t)1 << 15;  // rows per launch of the witness table (840 B a row at n = 8: 28 MB)
 constexpr int64_t kPathChunk = (int64_t)1 << 13;     // paths per launch of the path optimiser (8 KB a path at L = 64, n = 8)
+constexpr size_t kSampleChunkDoubles = (size_t)1 << 25;  // doubles per chunk of optik_robot_trajectory_sample (256 MiB)
 constexpr int64_t kPlanChunk = (int64_t)1 << 12;     // queries per launch of a plan (one workgroup each; 8 KB of path at Lmax = 64, n = 16)
 
 // A chunk of paths [P][L][n] with their lengths through the batch block, waypoint-major on the device ([L][chunk][n],
 // the transpose optik_robot_path_optimize makes), the int32 lengths behind them; `out_doubles` doubles per path come
 // back.  launch(d_paths, d_lens or null, Lc, d_out) queues the device work, scatter(b0, Lc, h_out) takes the results.
+// `extra` (extra_doubles of them, may be none) is uploaded with every chunk, at d_paths + paths_extra_offset(nl, n, Lc).
+inline size_t paths_extra_offset(size_t nl, size_t n, size_t Lc) { return nl * n * Lc + (Lc + 1) / 2; }
+
 template <class Launch, class Scatter>
 int stage_paths(DeviceCtx *c, const double *paths, const int32_t *lens, int64_t P, size_t nl, size_t n,
-                size_t out_doubles, Launch &&launch, Scatter &&scatter) {
+                size_t out_doubles, Launch &&launch, Scatter &&scatter, const double *extra = nullptr,
+                size_t extra_doubles = 0) {
     BatchGuard guard(c);
     if (!guard.ok()) return set_err(-1, kSetDeviceMsg);
     const size_t w = nl * n;
     const int64_t chunk = P < kPathChunk ? P : kPathChunk;
-    if (!reserve_batch(c, (w + 1 + out_doubles) * (size_t)chunk)) return set_err(-1, kBatchAllocMsg);
+    if (!reserve_batch(c, (w + 1 + out_doubles) * (size_t)chunk + extra_doubles)) return set_err(-1, kBatchAllocMsg);
     for (int64_t b0 = 0; b0 < P; b0 += chunk) {
-        const size_t Lc = (size_t)(P - b0 < chunk ? P - b0 : chunk), in_doubles = w * Lc + (Lc + 1) / 2;
+        const size_t Lc = (size_t)(P - b0 < chunk ? P - b0 : chunk),
+                     in_doubles = paths_extra_offset(nl, n, Lc) + extra_doubles;
         double *h_in = c->h_batch.get(), *h_out = h_in + in_doubles;
         double *d_in = c->d_batch.get(), *d_out = d_in + in_doubles;
         parallel_ranges(Lc, [&](size_t k0, size_t k1) {
@@ -45,6 +51,7 @@ int stage_paths(DeviceCtx *c, const double *paths, const int32_t *lens, int64_t 
                     std::memcpy(h_in + (t * Lc + k) * n, paths + (((size_t)b0 + k) * nl + t) * n, sizeof(double) * n);
         });
         if (lens) std::memcpy(h_in + w * Lc, lens + b0, sizeof(int32_t) * Lc);
+        if (extra_doubles) std::memcpy(h_in + paths_extra_offset(nl, n, Lc), extra, sizeof(double) * extra_doubles);
         if (hipMemcpyAsync(d_in, h_in, sizeof(double) * in_doubles, hipMemcpyHostToDevice, nullptr) != hipSuccess)
             return set_err(-1, "upload failed");
         if (launch(d_in, lens ? reinterpret_cast<const int32_t *>(d_in + w * Lc) : nullptr, (int64_t)Lc, d_out))
@@ -555,6 +562,99 @@ int optik_robot_path_resample(const optik_robot *r, int64_t P, int32_t L, const 
             if (paths_out) scatter_paths(paths_out, h_out, b0, Lc, (size_t)Lout, n);
             if (status_out) std::memcpy(status_out + b0, h_out + wo * Lc, sizeof(int32_t) * Lc);
         });
+}
+
+// P paths through optik_hip_path_time; the limits travel behind the lengths in the batch block.
+int optik_robot_path_time(const optik_robot *r, int64_t P, int32_t L, const double *paths, const int32_t *lens,
+                          const double *v_max, const double *a_max, double *times_out, double *vel_out,
+                          double *acc_out, double *duration_out, int32_t *status_out) {
+    if (!r || !paths || !v_max || !a_max) return set_err(-1, "null argument");
+    if (P < 0) return set_err(-1, "bad argument");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    // (P = 0: the kernel layer's refusals of the chain and the sizes)
+    if (optik_hip_path_time(c->chain, nullptr, nullptr, L, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                            nullptr, nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (P == 0 || (!times_out && !vel_out && !acc_out && !duration_out && !status_out)) return 0;
+    const size_t n = (size_t)r->n, nl = (size_t)L, w = nl * n;
+    std::vector<double> limits(v_max, v_max + n);
+    limits.insert(limits.end(), a_max, a_max + n);
+    // per path out: times [L], velocities [L][n], accelerations [L][n], the duration, then the status in one more double
+    return stage_paths(
+        c, paths, lens, P, nl, n, nl + 2 * w + 2,
+        [&](const double *d_in, const int32_t *d_len, int64_t Lc, double *d_out) {
+            const double *d_lim = d_in + paths_extra_offset(nl, n, (size_t)Lc);
+            double *d_t = d_out, *d_qd = d_t + nl * (size_t)Lc, *d_qdd = d_qd + w * (size_t)Lc,
+                   *d_dur = d_qdd + w * (size_t)Lc;
+            return optik_hip_path_time(c->chain, d_in, d_len, L, Lc, d_lim, d_lim + n, d_t, d_qd, d_qdd, nullptr, d_dur,
+                                       reinterpret_cast<int32_t *>(d_dur + Lc), nullptr);
+        },
+        [&](size_t b0, size_t Lc, const double *h_out) {
+            const double *h_t = h_out, *h_qd = h_t + nl * Lc, *h_qdd = h_qd + w * Lc, *h_dur = h_qdd + w * Lc;
+            if (times_out) scatter_paths(times_out, h_t, b0, Lc, nl, 1);
+            if (vel_out) scatter_paths(vel_out, h_qd, b0, Lc, nl, n);
+            if (acc_out) scatter_paths(acc_out, h_qdd, b0, Lc, nl, n);
+            if (duration_out) std::memcpy(duration_out + b0, h_dur, sizeof(double) * Lc);
+            if (status_out) std::memcpy(status_out + b0, h_dur + Lc, sizeof(int32_t) * Lc);
+        },
+        limits.data(), limits.size());
+}
+
+// P timed paths through optik_hip_trajectory_sample.  A path's samples are 2 T n doubles -- 7 MB at T = 65 536, n = 7 --
+// so the chunk is sized by the bytes of its results (kSampleChunkDoubles), not by kPathChunk.
+int optik_robot_trajectory_sample(const optik_robot *r, int64_t P, int32_t L, const double *paths, const int32_t *lens,
+                                  const double *times, const double *velocities, const int32_t *status, double dt,
+                                  int32_t T, double *q_out, double *qd_out) {
+    if (!r || !paths || !times || !velocities || !status) return set_err(-1, "null argument");
+    if (P < 0) return set_err(-1, "bad argument");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    if (optik_hip_trajectory_sample(c->chain, nullptr, nullptr, L, 0, nullptr, nullptr, nullptr, dt, T, nullptr, nullptr,
+                                    nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (P == 0 || (!q_out && !qd_out)) return 0;
+    BatchGuard guard(c);
+    if (!guard.ok()) return set_err(-1, kSetDeviceMsg);
+    const size_t n = (size_t)r->n, nl = (size_t)L, w = nl * n, wo = (size_t)T * n;
+    const size_t per_path = 2 * w + nl + 1 + 2 * wo;
+    int64_t chunk = (int64_t)(kSampleChunkDoubles / per_path);
+    chunk = chunk < 1 ? 1 : (chunk > kPathChunk ? kPathChunk : chunk);
+    if (P < chunk) chunk = P;
+    if (!reserve_batch(c, per_path * (size_t)chunk)) return set_err(-1, kBatchAllocMsg);
+    for (int64_t b0 = 0; b0 < P; b0 += chunk) {
+        const size_t Lc = (size_t)(P - b0 < chunk ? P - b0 : chunk);
+        // in: paths [L][Lc][n] | velocities [L][Lc][n] | times [L][Lc] | lens [Lc], status [Lc] (int32)
+        const size_t in_doubles = 2 * w * Lc + nl * Lc + Lc;
+        double *h_in = c->h_batch.get(), *h_out = h_in + in_doubles;
+        double *d_in = c->d_batch.get(), *d_out = d_in + in_doubles;
+        double *h_qd = h_in + w * Lc, *h_t = h_qd + w * Lc;
+        int32_t *h_len = reinterpret_cast<int32_t *>(h_t + nl * Lc);
+        parallel_ranges(Lc, [&](size_t k0, size_t k1) {
+            for (size_t k = k0; k < k1; ++k)
+                for (size_t t = 0; t < nl; ++t) {
+                    const size_t src = ((size_t)b0 + k) * nl + t;
+                    std::memcpy(h_in + (t * Lc + k) * n, paths + src * n, sizeof(double) * n);
+                    std::memcpy(h_qd + (t * Lc + k) * n, velocities + src * n, sizeof(double) * n);
+                    h_t[t * Lc + k] = times[src];
+                }
+        });
+        for (size_t k = 0; k < Lc; ++k) h_len[k] = lens ? lens[(size_t)b0 + k] : L;
+        std::memcpy(h_len + Lc, status + b0, sizeof(int32_t) * Lc);
+        if (hipMemcpyAsync(d_in, h_in, sizeof(double) * in_doubles, hipMemcpyHostToDevice, nullptr) != hipSuccess)
+            return set_err(-1, "upload failed");
+        const double *d_qd = d_in + w * Lc, *d_t = d_qd + w * Lc;
+        const int32_t *d_len = reinterpret_cast<const int32_t *>(d_t + nl * Lc);
+        if (optik_hip_trajectory_sample(c->chain, d_in, d_len, L, (int64_t)Lc, d_t, d_qd, d_len + Lc, dt, T, d_out,
+                                        d_out + wo * Lc, nullptr))
+            return set_err(-1, optik_hip_last_error());
+        if (hipMemcpyAsync(h_out, d_out, sizeof(double) * 2 * wo * Lc, hipMemcpyDeviceToHost, nullptr) != hipSuccess
+            || hipStreamSynchronize(nullptr) != hipSuccess)
+            return set_err(-1, "download failed");
+        if (q_out) scatter_paths(q_out, h_out, (size_t)b0, Lc, (size_t)T, n);
+        if (qd_out) scatter_paths(qd_out, h_out + wo * Lc, (size_t)b0, Lc, (size_t)T, n);
+    }
+    return 0;
 }
 
 // The roadmap (include/optik.h): N seeds of the restart generator as nodes, their k nearest others and the checked

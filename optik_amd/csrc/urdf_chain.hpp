@@ -201,6 +201,7 @@ struct ChainJoint {
     double axis[3] = {0, 0, 0};
     bool has_limit = false;  // articulated joints carry one (lower, upper) pair
     double lower = 0, upper = 0;
+    double velocity = INFINITY;  // <limit velocity=>; absent, 0 or negative: none
     HPose origin;
 };
 
@@ -268,6 +269,9 @@ inline Chain chain_from_urdf(const std::string &urdf, const std::string &base_li
         e.joint.has_limit = true;
         if (upper - lower > 0.0) { e.joint.lower = lower; e.joint.upper = upper; }  // kinematics.rs:299-303
         else { e.joint.lower = -INFINITY; e.joint.upper = INFINITY; }
+        double velocity = 0;
+        parse_floats(c.child("limit"), "velocity", 1, &velocity, &velocity);
+        e.joint.velocity = velocity > 0.0 ? velocity : INFINITY;
         double xyz[3], rpy[3];
         parse_floats(c.child("origin"), "xyz", 3, zero3, xyz);
         parse_floats(c.child("origin"), "rpy", 3, zero3, rpy);

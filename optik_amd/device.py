@@ -475,6 +475,56 @@ class HipChain:
         """The paths path_shortcut processes per chunk of its workspace (tests cross it)."""
         return nat.path_shortcut_chunk(self._h, vertices)
 
+    # -- timing and sampling (include/optik_hip.h; DESIGN.md section 5.20) ------------------------------------------
+    def _limits(self, v, name, device):
+        if not (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.float64 and v.numel() == self.n
+                and v.is_contiguous() and v.device == device):
+            raise ValueError(f"{name} must be a contiguous float64 cuda tensor of {self.n} limits on path's device")
+        return v
+
+    def path_time(self, path, lens=None, v_max=None, a_max=None):
+        """Times P paths rest to rest under the joint velocity limits v_max [n] (> 0, inf allowed) and acceleration
+        limits a_max [n] (finite, > 0), both float64 cuda tensors (optik_hip_path_time): path [L, P, n] float64 cuda
+        tensor and lens [P] int32 (None: L each) -- path_resample's output as it is, 3 <= L <= 64.  Stream-ordered on
+        the current stream; returns a dict of device tensors: t [L, P], qd [L, P, n], qdd [L, P, n], x [L, P] (the
+        squared path speed), duration [P], status [P] int32 (nat.TIME_*)."""
+        L, P = self._check_paths(path, lens)
+        nat.check_time_args(self.n, L)
+        dev = path.device
+        v_max, a_max = self._limits(v_max, "v_max", dev), self._limits(a_max, "a_max", dev)
+        res = dict(t=torch.empty((L, P), dtype=torch.float64, device=dev),
+                   qd=torch.empty((L, P, self.n), dtype=torch.float64, device=dev),
+                   qdd=torch.empty((L, P, self.n), dtype=torch.float64, device=dev),
+                   x=torch.empty((L, P), dtype=torch.float64, device=dev),
+                   duration=torch.empty(P, dtype=torch.float64, device=dev),
+                   status=torch.empty(P, dtype=torch.int32, device=dev))
+        nat.check(nat.lib().optik_hip_path_time(self._h, _ptr(path), _ptr(lens), L, P, _ptr(v_max), _ptr(a_max),
+                                                _ptr(res["t"]), _ptr(res["qd"]), _ptr(res["qdd"]), _ptr(res["x"]),
+                                                _ptr(res["duration"]), _ptr(res["status"]), _stream_ptr()))
+        return res
+
+    def trajectory_sample(self, path, timing, dt, samples, lens=None):
+        """`samples` samples of each timed path at k * dt by cubic Hermite interpolation over the waypoints' times,
+        positions and velocities (optik_hip_trajectory_sample): path and lens as path_time took them, timing its
+        result.  Returns (q [samples, P, n], qd [samples, P, n]); past a path's duration its goal at rest, for a status
+        other than 0 its start at rest.  The curve leaves the polyline between waypoints and is not checked.
+        Stream-ordered."""
+        L, P = self._check_paths(path, lens)
+        nat.check_time_args(self.n, L)
+        dt = nat.check_sample_args(dt, samples)
+        t, qd, status = timing["t"], timing["qd"], timing["status"]
+        if not (t.shape == (L, P) and qd.shape == (L, P, self.n) and status.shape == (P,) and t.is_contiguous()
+                and qd.is_contiguous() and status.is_contiguous() and t.dtype == torch.float64
+                and qd.dtype == torch.float64 and status.dtype == torch.int32
+                and t.device == qd.device == status.device == path.device):
+            raise ValueError("timing must be path_time's result for this path")
+        q = torch.empty((int(samples), P, self.n), dtype=torch.float64, device=path.device)
+        v = torch.empty_like(q)
+        nat.check(nat.lib().optik_hip_trajectory_sample(self._h, _ptr(path), _ptr(lens), L, P, _ptr(t), _ptr(qd),
+                                                        _ptr(status), dt, int(samples), _ptr(q), _ptr(v),
+                                                        _stream_ptr()))
+        return q, v
+
     def seed_batch(self, first, count):
         q = torch.empty((self.n, count), dtype=torch.float64, device=self.device)
         nat.check(nat.lib().optik_hip_seed_batch(self._h, int(first), int(count), _ptr(q), _stream_ptr()))

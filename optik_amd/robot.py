@@ -69,6 +69,11 @@ def _bind(L):
     L.optik_robot_path_shortcut.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, C.c_int32, C.c_double, C.c_double, C.c_int32,
                                             dp, dp, ip, dp, dp, ip]
     L.optik_robot_path_resample.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, C.c_int32, dp, ip]
+    L.optik_robot_path_time.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, dp, dp, dp, dp, dp, dp, ip]
+    L.optik_robot_trajectory_sample.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, dp, dp, ip, C.c_double, C.c_int32, dp,
+                                                dp]
+    L.optik_robot_velocity_limits.argtypes = [vp]
+    L.optik_robot_velocity_limits.restype = C.POINTER(C.c_double)
     L.optik_robot_joint_jacobian_ex.argtypes = [vp, dp, dp, dp]
     L.optik_robot_set_devices.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32]
     L.optik_robot_num_devices.argtypes = [vp]
@@ -845,6 +850,82 @@ class Robot:
         seg_free = self.collision_motion_batch_arrays(out[:, :-1].reshape(-1, n), out[:, 1:].reshape(-1, n),
                                                       resolution, ee_offset)[1]
         return out, status, seg_free.reshape(P, W - 1).all(axis=1)
+
+    # -- timing and sampling (extension; include/optik.h) -----------------------------------
+    def velocity_limits(self):
+        """The URDF's <limit velocity=> of the n articulated joints [n]; inf where it is absent, 0 or negative."""
+        n = self.num_positions()
+        p = self._L.optik_robot_velocity_limits(self._h)
+        vals = np.array([p[i] for i in range(n)], dtype=np.float64)
+        C.CDLL(None).free(p)
+        return vals
+
+    def time_paths(self, paths, lens=None, a_max=None, v_max=None, scale=1.0):
+        """Times P joint-space paths `paths` [P, L, n] with `lens` [P] waypoints each (None: L each), 3 <= L <= 64, rest
+        to rest under joint velocity and acceleration limits, all on the GPU: time-optimal path parameterisation by
+        reachability analysis (TOPP-RA) on the path's own waypoints, so evenly spaced input -- resample_paths' -- is
+        what it is meant for.  a_max (rad/s^2; required: a URDF carries none) and v_max (rad/s; None: the URDF's,
+        velocity_limits()) are a scalar or [n]; `scale` in (0, 1] multiplies both.  Returns a dict: times [P, L] from
+        0, velocities and accelerations [P, L, n] at the waypoints, duration [P], status [P] int32: 0 timed; 1 stalled
+        (two neighbouring waypoints both at zero speed: the path is too jagged for its spacing); 2 a length outside 3
+        .. L or a waypoint repeated three times (twice at the start); 3 a NaN or an infinity; unless 0 the times and
+        the duration are NaN.  The result always respects the limits at the waypoints and is time-optimal where the
+        path is dense and gently curved (DESIGN.md section 5.20 says by how much it is longer elsewhere).
+        ValueError for an a_max that is not finite and > 0, a v_max that is <= 0 or NaN, L outside 3 .. 64, a scale
+        outside (0, 1]."""
+        paths, lens = self._check_paths(paths, lens)
+        P, L, n = paths.shape
+        if a_max is None:
+            raise ValueError("a_max is required: a URDF carries no acceleration limits")
+        v, a = nat.check_time_args(n, L, a_max, self.velocity_limits() if v_max is None else v_max, scale)
+        times, dur = np.zeros((P, L)), np.zeros(P)
+        vel, acc = np.zeros((P, L, n)), np.zeros((P, L, n))
+        status = np.zeros(P, dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        if self._L.optik_robot_path_time(self._h, P, L, _dp(paths), lens.ctypes.data_as(ip) if lens is not None else None,
+                                         _dp(v), _dp(a), _dp(times), _dp(vel), _dp(acc), _dp(dur),
+                                         status.ctypes.data_as(ip)):
+            raise RuntimeError(_err(self._L))
+        return dict(times=times, velocities=vel, accelerations=acc, duration=dur, status=status)
+
+    def sample_trajectories(self, paths, timing, dt, lens=None, resolution=None, ee_offset=None):
+        """Samples the trajectories time_paths timed (`timing`: its result for these `paths` and `lens`) every `dt`
+        seconds by cubic Hermite interpolation in time over the waypoints' positions and velocities -- what a
+        joint-trajectory controller does with them.  Returns (positions [P, T, n], velocities [P, T, n]) with
+        T = the largest ceil(duration / dt) + 1 over the paths with status 0 (1 if there is none): past its duration a
+        path holds its goal at rest; a path whose status is not 0 holds its start.  The Hermite curve leaves the
+        polyline between waypoints, as resample_paths' segments cut corners, so it is NOT free by construction: with
+        `resolution` the call also returns free [P] bool, whether every move between consecutive samples passes
+        collision_motion_batch_arrays at that resolution.  ValueError for a dt that is not finite and > 0 or a T above
+        65 536 (raise dt)."""
+        paths, lens = self._check_paths(paths, lens)
+        P, L, n = paths.shape
+        nat.check_time_args(n, L)
+        if resolution is not None:
+            resolution = nat.check_resolution(resolution)
+        times = np.ascontiguousarray(timing["times"], dtype=np.float64)
+        vel = np.ascontiguousarray(timing["velocities"], dtype=np.float64)
+        status = np.ascontiguousarray(timing["status"], dtype=np.int32)
+        dur = np.asarray(timing["duration"], dtype=np.float64)
+        if times.shape != (P, L) or vel.shape != (P, L, n) or status.shape != (P,) or dur.shape != (P,):
+            raise ValueError("timing must be time_paths' result for these paths")
+        dt = nat.check_sample_args(dt)
+        ok = status == nat.TIME_TIMED
+        T = int(np.ceil(dur[ok] / dt).max()) + 1 if ok.any() else 1
+        nat.check_sample_args(dt, T)
+        q, qd = np.zeros((P, T, n)), np.zeros((P, T, n))
+        ip = C.POINTER(C.c_int32)
+        if self._L.optik_robot_trajectory_sample(self._h, P, L, _dp(paths),
+                                                 lens.ctypes.data_as(ip) if lens is not None else None, _dp(times),
+                                                 _dp(vel), status.ctypes.data_as(ip), dt, T, _dp(q), _dp(qd)):
+            raise RuntimeError(_err(self._L))
+        if resolution is None:
+            return q, qd
+        if T < 2:
+            return q, qd, np.ones(P, dtype=bool)
+        seg_free = self.collision_motion_batch_arrays(q[:, :-1].reshape(-1, n), q[:, 1:].reshape(-1, n), resolution,
+                                                      ee_offset)[1]
+        return q, qd, seg_free.reshape(P, T - 1).all(axis=1)
 
     # -- the motion check (extension; include/optik.h, DESIGN.md section 5.13) ------------------------------------
     def collision_motion_batch_arrays(self, xa, xb, resolution, ee_offset=None):
