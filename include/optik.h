@@ -198,6 +198,13 @@ int optik_robot_world_grid_from_occupancy(const optik_robot *robot, double voxel
 int optik_robot_occupancy_from_points(const optik_robot *robot, const double *origin3, double voxel, int32_t nx,
                                       int32_t ny, int32_t nz, const double *points3, int64_t N,
                                       const double *exclude4, int32_t E, uint8_t *occupied);
+/* From a triangle mesh to that grid (extension; include/optik_hip.h: optik_hip_world_grid_from_mesh).  Host arrays,
+ * on the robot's first device; installs nothing.  tris9 [M][9]: the vertices a, b, c of each triangle in the base
+ * frame -> values_out (nx * ny * nz floats): the signed distance to the mesh, clamped to +-max_distance.  rc 0, or -1:
+ * the refusals of the kernel layer, and a NaN or infinite coordinate. */
+int optik_robot_world_grid_from_mesh(const optik_robot *robot, const double *origin3, double voxel, int32_t nx,
+                                     int32_t ny, int32_t nz, const double *tris9, int32_t M, double max_distance,
+                                     float *values_out);
 /* x [B][n] -> frames16_out [B][n + 2][16]: every frame as a column-major 4x4 (as optik_robot_fk_ex writes it; frame
  * n + 1 is fk's pose).  ee_offset16 may be NULL.  On the robot's first device; rc 0 or -1. */
 int optik_robot_link_frames_batch(const optik_robot *robot, int64_t B, const double *x, const double *ee_offset16,

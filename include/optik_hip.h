@@ -444,6 +444,33 @@ int optik_hip_occupancy_from_points(const optik_hip_chain *chain, const double *
                                     int32_t ny, int32_t nz, const double *d_points3, int64_t N,
                                     const double *d_exclude4, int32_t E, uint8_t *d_occupied, void *stream);
 
+/* From a triangle mesh to a distance-field world (extension; the arithmetic:
+ * csrc/mesh_measure.hpp).  d_tris9 is a triangle soup in device memory, [M][9] doubles: the vertices a, b, c of each
+ * triangle in the base frame; no connectivity, welding or closedness is needed.
+ *
+ * optik_hip_world_grid_from_mesh writes to d_values_out (nx * ny * nz floats, device memory) the signed distance of
+ * every node of the grid to the mesh: the exact point-to-triangle distance, minimised over the triangles, negative
+ * where the generalized winding number has magnitude >= 1/2 (so inward-oriented files work, and an open sheet reads
+ * as unsigned), clamped to +-max_distance.  This is the true distance: the only error of the resulting world is the
+ * sqrt(3) * voxel of the grid's interpolation.  Stream-ordered; it installs nothing: hand the values to
+ * optik_hip_chain_set_world_grid.  There is no culling: the cost is nx * ny * nz * M pair evaluations, issued as
+ * stream-ordered launches of a bounded number of pairs each.  Finite coordinates are the caller's promise here (the
+ * robot-level entry of optik.h checks its host arrays): a NaN or infinite coordinate gives NaN-free but meaningless
+ * values.
+ *
+ * Refused with OPTIK_HIP_EINVAL before any device work: a grid that set_world_grid would refuse for its geometry, M
+ * outside 1 .. OPTIK_HIP_MAX_MESH_TRIANGLES, a max_distance that is zero, negative, NaN or infinite, a null buffer.
+ *
+ * optik_hip_mesh_tile returns the number of triangles the kernel stages at a time.  optik_hip_mesh_pairs_per_launch is
+ * a test hook: pairs > 0 sets the launch bound for the process, 0 restores the built-in one, a negative value only
+ * asks; it returns the bound in force.  Neither changes a bit of any result. */
+#define OPTIK_HIP_MAX_MESH_TRIANGLES (1 << 20)
+int optik_hip_world_grid_from_mesh(const optik_hip_chain *chain, const double *origin3, double voxel, int32_t nx,
+                                   int32_t ny, int32_t nz, const double *d_tris9, int32_t M, double max_distance,
+                                   float *d_values_out, void *stream);
+int32_t optik_hip_mesh_tile(void);
+int64_t optik_hip_mesh_pairs_per_launch(int64_t pairs);
+
 /* The motion check (extension; the arithmetic: csrc/motion_measure.hpp): is the straight
  * joint-space segment qa -> qb free at a resolution h > 0 (L-infinity, radians)?  With d = max_i |qb_i - qa_i| the
  * segment has K = max(1, (int)ceil(d / h)) steps and K + 1 samples: sample 0 is qa and sample K is qb, copied, and

@@ -134,6 +134,11 @@ def lib():
                                                       vp, vp]
     L.optik_hip_occupancy_from_points.argtypes = [vp, dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64,
                                                   vp, C.c_int32, vp, vp]
+    L.optik_hip_world_grid_from_mesh.argtypes = [vp, dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32,
+                                                 C.c_double, vp, vp]
+    L.optik_hip_mesh_tile.restype = C.c_int32
+    L.optik_hip_mesh_pairs_per_launch.argtypes = [C.c_int64]
+    L.optik_hip_mesh_pairs_per_launch.restype = C.c_int64
     L.optik_hip_link_frames_batch.argtypes = [vp, dp, vp, C.c_int64, vp, vp]
     L.optik_hip_collision_batch.argtypes = [vp, dp, vp, C.c_int64, vp, vp, vp]
     L.optik_hip_collision_motion_batch.argtypes = [vp, dp, vp, vp, C.c_int64, C.c_double, vp, vp, vp, vp, vp]
@@ -186,6 +191,34 @@ def check_resolution(h, allow_zero=False):
     if not (math.isfinite(h) and (h > 0.0 or (allow_zero and h == 0.0))):
         raise ValueError("motion resolution must be finite and " + (">= 0" if allow_zero else "> 0") + f", got {h}")
     return h
+
+
+MAX_MESH_TRIANGLES = 1 << 20  # include/optik_hip.h: OPTIK_HIP_MAX_MESH_TRIANGLES
+
+
+def mesh_tile():
+    """MESH_TILE of csrc/mesh_measure.hpp: the triangles optik_hip_world_grid_from_mesh stages in LDS at a time."""
+    return int(lib().optik_hip_mesh_tile())
+
+
+class mesh_pairs_per_launch:
+    """``with mesh_pairs_per_launch(pairs): ...`` -- a test hook (include/optik_hip.h: optik_hip_mesh_pairs_per_launch):
+    within the block optik_hip_world_grid_from_mesh splits its nodes into launches of at most `pairs` (node, triangle)
+    pairs each instead of MESH_PAIRS_PER_LAUNCH; restored after it.  No result depends on it."""
+
+    def __init__(self, pairs):
+        self.pairs = int(pairs)
+        if self.pairs < 1:
+            raise ValueError("pairs must be >= 1")
+
+    def __enter__(self):
+        self.prev = int(lib().optik_hip_mesh_pairs_per_launch(-1))
+        lib().optik_hip_mesh_pairs_per_launch(self.pairs)
+        return self
+
+    def __exit__(self, *exc):
+        lib().optik_hip_mesh_pairs_per_launch(self.prev)
+        return False
 
 
 PATH_OPTIMIZE_MAX_WAYPOINTS = 64  # include/optik_hip.h: OPTIK_HIP_PATH_OPTIMIZE_MAX_WAYPOINTS

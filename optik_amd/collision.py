@@ -19,6 +19,7 @@ MAX_OBSTACLES = 65536  # OPTIK_HIP_MAX_WORLD_OBSTACLES, of each kind
 MAX_GRID_DIM = 1024    # OPTIK_HIP_MAX_GRID_DIM, per axis (at least 2)
 MAX_GRID_NODES = 1 << 24  # OPTIK_HIP_MAX_GRID_NODES
 MAX_EXCLUDE_SPHERES = 1024  # OPTIK_HIP_MAX_EXCLUDE_SPHERES
+MAX_MESH_TRIANGLES = 1 << 20  # OPTIK_HIP_MAX_MESH_TRIANGLES
 
 
 def auto_pairs(frames):
@@ -120,6 +121,67 @@ def cloud_arrays(points, exclude=None):
     if exclude.ndim != 2 or exclude.shape[1] != 4:
         raise ValueError(f"exclude must be [E, 4] (centre, radius), got {list(exclude.shape)}")
     return np.ascontiguousarray(points), np.ascontiguousarray(exclude)
+
+
+def mesh_arrays(vertices, triangles=None):
+    """A mesh as the triangle soup of the C ABI, float64 [M, 9] (the vertices a, b, c of each triangle, base frame),
+    C-contiguous.  Either `vertices` [V, 3] with `triangles` [M, 3] integer indices into it (range-checked here), or,
+    with `triangles` None, `vertices` [M, 3, 3] (or [M, 9]) as soup already.  Nothing is welded or repaired: the
+    winding number needs neither.  Shapes and indices are checked here; the triangle count and the coordinates'
+    finiteness by the C layer."""
+    v = np.asarray(vertices, dtype=np.float64)
+    if triangles is None:
+        if not ((v.ndim == 3 and v.shape[1:] == (3, 3)) or (v.ndim == 2 and v.shape[1] == 9)):
+            raise ValueError(f"without triangles, vertices must be [M, 3, 3] (a triangle soup), got {list(v.shape)}")
+        return np.ascontiguousarray(v.reshape(-1, 9))
+    if v.ndim != 2 or v.shape[1] != 3:
+        raise ValueError(f"vertices must be [V, 3], got {list(v.shape)}")
+    t = np.asarray(triangles)
+    if t.ndim != 2 or t.shape[1] != 3:
+        raise ValueError(f"triangles must be [M, 3] vertex indices, got {list(t.shape)}")
+    if not np.issubdtype(t.dtype, np.integer):
+        raise ValueError("triangles must hold integer vertex indices")
+    if t.size and (int(t.min()) < 0 or int(t.max()) >= len(v)):
+        raise ValueError(f"triangles: a vertex index is outside 0..{len(v) - 1}")
+    return np.ascontiguousarray(v[t.astype(np.int64)].reshape(-1, 9))
+
+
+def load_stl(path):
+    """The triangles of an STL file as float64 [M, 3, 3] (a soup: nothing is welded, the stored normals are ignored).
+    A file is binary (80-byte header, uint32 count, 50-byte records of 12 float32 and 2 attribute bytes) iff its size
+    is 84 + 50 * count -- the word "solid" decides nothing, binary files start with it too -- and ASCII otherwise.
+    ValueError for a file that is neither (a truncated one, for instance)."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    if len(data) >= 84:
+        count = int(np.frombuffer(data, dtype="<u4", count=1, offset=80)[0])
+        if 84 + 50 * count == len(data):
+            rec = np.frombuffer(data, dtype=np.dtype([("f", "<f4", (12,)), ("attr", "<u2")]), count=count, offset=84)
+            return rec["f"][:, 3:].astype(np.float64).reshape(count, 3, 3)
+    try:
+        words = data.decode("ascii").split()
+    except UnicodeDecodeError:
+        raise ValueError(f"{path}: neither a binary STL (84 + 50 * count bytes) nor an ASCII one") from None
+    if not words or words[0] != "solid" or "endsolid" not in words:
+        raise ValueError(f"{path}: neither a binary STL (84 + 50 * count bytes) nor an ASCII one")
+    coords = []
+    k, opened, closed = 0, 0, 0
+    while k < len(words):
+        if words[k] == "vertex":
+            try:
+                coords.append([float(w) for w in words[k + 1:k + 4]])
+            except ValueError:
+                raise ValueError(f"{path}: a vertex without three numbers") from None
+            if len(coords[-1]) != 3:
+                raise ValueError(f"{path}: a vertex without three numbers")
+            k += 4
+            continue
+        opened += words[k] == "facet"
+        closed += words[k] == "endfacet"
+        k += 1
+    if opened != closed or len(coords) != 3 * opened:
+        raise ValueError(f"{path}: {opened} facets, {closed} closed, {len(coords)} vertices: not three per facet")
+    return np.array(coords, dtype=np.float64).reshape(-1, 3, 3)
 
 
 def spheres_at(robot, x, frames, centers, radii, pad=0.0, ee_offset=None):

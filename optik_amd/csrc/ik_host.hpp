@@ -15,6 +15,7 @@
 //   ik_shortcut.hip    path shortcutting over all-pairs visibility, equal-spacing resampling
 //   ik_time.hip        timing of joint paths under velocity and acceleration limits, trajectory sampling
 //   ik_occupancy.hip   occupancy grids and point clouds into distance-field worlds (distance transform, voxelize)
+//   ik_mesh.hip        triangle meshes into distance-field worlds (exact distance, generalized winding number)
 //   ik_batch_ops.hip   objective / gradient, FK / Jacobian and seed batches, the test probes
 //   ik_lane_kernel.hip, ik_quad_kernel.hip, ik_wide_kernel.hip    the restart solvers (one restart loop each)
 #pragma once

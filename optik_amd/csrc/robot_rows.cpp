@@ -9,6 +9,7 @@
 #include <string>
 
 #include "collision_model.hpp"
+#include "mesh_measure.hpp"
 #include "pose_convert.hpp"
 #include "robot_host.hpp"
 
@@ -294,6 +295,34 @@ int optik_robot_occupancy_from_points(const optik_robot *r, const double *origin
                                         nullptr))
         return set_err(-1, optik_hip_last_error());
     if (hipMemcpy(occupied, d_occ, nodes, hipMemcpyDeviceToHost) != hipSuccess) return set_err(-1, "download failed");
+    return 0;
+}
+
+int optik_robot_world_grid_from_mesh(const optik_robot *r, const double *origin3, double voxel, int32_t nx, int32_t ny,
+                                     int32_t nz, const double *tris9, int32_t M, double max_distance,
+                                     float *values_out) {
+    if (!r || !tris9 || !values_out) return set_err(-1, "null argument");
+    std::string err;
+    if (optik::coll::check_grid(origin3, voxel, nx, ny, nz, nullptr, false, err)
+        || optik::coll::check_mesh(M, max_distance, tris9, err))
+        return set_err(-1, err);
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    BatchGuard guard(c);
+    if (!guard.ok()) return set_err(-1, kSetDeviceMsg);
+    const size_t nodes = (size_t)nx * (size_t)ny * (size_t)nz;
+    // one block: the triangles, then the values
+    optik::DeviceBuf<uint8_t> block;
+    if (block.reserve(sizeof(double) * 9 * (size_t)M + sizeof(float) * nodes) != hipSuccess)
+        return set_err(-1, "mesh buffer allocation failed");
+    double *d_tris = reinterpret_cast<double *>(block.get());
+    float *d_out = reinterpret_cast<float *>(d_tris + 9 * (size_t)M);
+    if (hipMemcpy(d_tris, tris9, sizeof(double) * 9 * (size_t)M, hipMemcpyHostToDevice) != hipSuccess)
+        return set_err(-1, "upload failed");
+    if (optik_hip_world_grid_from_mesh(c->chain, origin3, voxel, nx, ny, nz, d_tris, M, max_distance, d_out, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (hipMemcpy(values_out, d_out, sizeof(float) * nodes, hipMemcpyDeviceToHost) != hipSuccess)
+        return set_err(-1, "download failed");
     return 0;
 }
 

@@ -248,6 +248,27 @@ class HipChain:
                                                             _ptr(into), _stream_ptr()))
         return into
 
+    # -- from a triangle mesh to that grid (include/optik_hip.h) ------------------------------
+    def world_grid_from_mesh(self, origin, voxel, shape, triangles, max_distance=None):
+        """The signed distance field of a triangle soup (a contiguous float64 cuda tensor [M, 3, 3] or [M, 9]: the
+        vertices a, b, c of each triangle, base frame; finite coordinates are the caller's promise here) on the grid:
+        a float32 cuda tensor [nx, ny, nz], clamped to +-max_distance (default: the grid diagonal).  Stream-ordered;
+        installs nothing.  nx * ny * nz * M pair evaluations, no culling."""
+        from .collision import default_max_distance, grid_arrays
+        o, v, _, (nx, ny, nz) = grid_arrays(origin, voxel, shape=shape)
+        t = triangles
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+                and ((t.dim() == 3 and tuple(t.shape[1:]) == (3, 3)) or (t.dim() == 2 and t.shape[1] == 9))):
+            raise ValueError("triangles must be a contiguous float64 cuda tensor [M, 3, 3] or [M, 9]")
+        M = int(t.shape[0])
+        md = default_max_distance(v, (nx, ny, nz)) if max_distance is None else float(max_distance)
+        nodes = nx * ny * nz
+        out = torch.empty((nx, ny, nz) if 0 < nodes <= (1 << 24) else (1, 1, 1), dtype=torch.float32,
+                          device=self.device)
+        nat.check(nat.lib().optik_hip_world_grid_from_mesh(self._h, _dp(o), v, nx, ny, nz, _ptr(t) if M else None,
+                                                           min(M, (1 << 31) - 1), md, _ptr(out), _stream_ptr()))
+        return out
+
     def _check_q(self, q):
         if not (isinstance(q, torch.Tensor) and q.is_cuda and q.dtype == torch.float64 and q.dim() == 2
                 and q.shape[0] == self.n and q.is_contiguous()):

@@ -49,6 +49,8 @@ def _bind(L):
                                                         vp]
     L.optik_robot_occupancy_from_points.argtypes = [vp, dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64,
                                                     vp, C.c_int32, vp]
+    L.optik_robot_world_grid_from_mesh.argtypes = [vp, dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32,
+                                                   C.c_double, vp]
     L.optik_robot_link_frames_batch.argtypes = [vp, C.c_int64, dp, dp, dp]
     L.optik_robot_collision_batch.argtypes = [vp, C.c_int64, dp, dp, dp, C.POINTER(C.c_uint8)]
     L.optik_robot_collision_motion_batch.argtypes = [vp, C.c_int64, dp, dp, C.c_double, dp, dp, C.POINTER(C.c_uint8),
@@ -657,6 +659,39 @@ class Robot:
         world_grid_from_occupancy, then set_world_grid.  Returns the values it installed."""
         occ = self.occupancy_from_points(origin, voxel, shape, points, exclude)
         values = self.world_grid_from_occupancy(voxel, occ, max_distance)
+        self.set_world_grid(origin, voxel, values)
+        return values
+
+    # -- from a triangle mesh to that grid (extension; include/optik.h, DESIGN.md section 5.21) ------------------------
+    def world_grid_from_mesh(self, origin, voxel, shape, vertices, triangles=None, max_distance=None):
+        """The signed distance field of a triangle mesh on the grid (origin, voxel, shape = (nx, ny, nz)), computed on
+        the GPU: np.float32 [nx, ny, nz].  The mesh is `vertices` [V, 3] with `triangles` [M, 3] integer indices, or
+        `vertices` [M, 3, 3] as a soup when `triangles` is None (optik_amd.collision.load_stl returns that), in the
+        base frame.  Every value is the exact distance to the nearest triangle, negative where the generalized winding
+        number has magnitude >= 1/2: holes, unwelded vertices and inward-oriented files are fine, and an open sheet
+        reads as unsigned.  Clamped to +-max_distance (default: the grid diagonal).  This is the true distance, so a
+        conservative caller adds only set_world_grid's sqrt(3) * voxel to the margin.  No culling: the cost is
+        nx * ny * nz * M pair evaluations.  Installs nothing.  ValueError for a refused grid, mesh (no triangle, more
+        than 2^20, an index out of range, a NaN or infinite coordinate) or max_distance."""
+        from .collision import default_max_distance, grid_arrays, mesh_arrays
+        o, v, _, (nx, ny, nz) = grid_arrays(origin, voxel, shape=shape)
+        tris = mesh_arrays(vertices, triangles)
+        md = default_max_distance(v, (nx, ny, nz)) if max_distance is None else float(max_distance)
+        nodes = nx * ny * nz
+        out = np.zeros(nodes if 0 < nodes <= (1 << 24) else 1, dtype=np.float32)
+        M = len(tris) if len(tris) < (1 << 31) else (1 << 31) - 1
+        if self._L.optik_robot_world_grid_from_mesh(self._h, _dp(o), v, nx, ny, nz,
+                                                    C.c_void_p(tris.ctypes.data) if len(tris) else _dp(np.zeros(9)),
+                                                    M, md, C.c_void_p(out.ctypes.data)):
+            raise ValueError(_err(self._L))
+        return out.reshape(nx, ny, nz)
+
+    def set_world_mesh(self, origin, voxel, shape, vertices, triangles=None, max_distance=None):
+        """From a triangle mesh to the installed distance-field world: world_grid_from_mesh, then set_world_grid.
+        Returns the values it installed.  To combine the mesh with another field on the same grid (a bake of the
+        primitives, a point cloud's field, a second mesh), take np.minimum of the two value arrays and install that
+        with set_world_grid: the minimum of signed distances is the signed distance of the union outside it."""
+        values = self.world_grid_from_mesh(origin, voxel, shape, vertices, triangles, max_distance)
         self.set_world_grid(origin, voxel, values)
         return values
 
