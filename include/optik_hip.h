@@ -622,6 +622,11 @@ int optik_hip_ik_path(optik_hip_chain *chain, const optik_solver_config *cfg, co
  *   wide_form           OPTIK_WIDE_FORM = lds | hbm   form of the general solver (0 lds, 1 hbm)
  *   range_rule          OPTIK_RANDOM_RANGE_RULE = new_inclusive   OPTIK_HIP_RANGE_* of chains created afterwards
  *   stop_x_legacy       (none)                   1: nlopt_stop_x of NLopt 2.5 (no zero-step rule)
+ *   grid_cap            (none)                   a test hook: v >= 1 launches every grid-stride kernel (the batch
+ *                                                operators, the motion check, trajectory_sample; not the solvers) with
+ *                                                at most v blocks, so that a few hundred rows take the later trips of
+ *                                                its loop; 0 (the default) the device's own cap.  No result depends on
+ *                                                it.  A negative value is refused with OPTIK_HIP_EINVAL
  * The host layer (optik.h) reads OPTIK_HOST_THREADS and OPTIK_DEVICES; nothing else in the library reads the
  * environment.  Returns 0, or OPTIK_HIP_EINVAL for an unknown name; optik_hip_get_option returns -1 for one. */
 int optik_hip_set_option(const char *name, long long value);

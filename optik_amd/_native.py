@@ -374,7 +374,10 @@ def get_option(name):
 
 
 class options:
-    """``with options(solve_kernel="lane64"): ...`` -- set for the block, restored after it."""
+    """``with options(solve_kernel="lane64"): ...`` -- set for the block, restored after it.  The names are those of
+    optik_hip_set_option: solve_kernel, wide_form, range_rule, stop_x_legacy and grid_cap -- a test hook,
+    ``options(grid_cap=1)`` launches every grid-stride kernel with at most one block (0: the device's own cap), so
+    that a few hundred rows take the later trips of its loop; no result depends on it."""
 
     def __init__(self, **kw):
         self.kw = kw

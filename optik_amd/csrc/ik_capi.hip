@@ -543,8 +543,9 @@ int optik_hip_ik_path(optik_hip_chain *ch, const optik_solver_config *cfg, const
 }
 
 /* Tuning options (tests, tools): see `struct Options` (ik_host.hpp).  Names: solve_kernel (0 auto, 1 quad, 2 lane64,
- * 3 general), wide_form (0 lds, 1 hbm), range_rule (of chains created afterwards), stop_x_legacy.  Not synchronised
- * with calls in flight. */
+ * 3 general), wide_form (0 lds, 1 hbm), range_rule (of chains created afterwards), stop_x_legacy, grid_cap (0 the
+ * device's cap, v >= 1 at most v blocks per grid-stride launch; a negative value is refused).  Not synchronised with
+ * calls in flight. */
 static int *option_slot(const char *name) {
     Options &o = opt();
     if (!name) return nullptr;
@@ -552,11 +553,14 @@ static int *option_slot(const char *name) {
     if (!std::strcmp(name, "wide_form")) return &o.wide_form;
     if (!std::strcmp(name, "range_rule")) return &o.range_rule;
     if (!std::strcmp(name, "stop_x_legacy")) return &o.stop_x_legacy;
+    if (!std::strcmp(name, "grid_cap")) return &o.grid_cap;
     return nullptr;
 }
 int optik_hip_set_option(const char *name, long long value) {
     int *slot = option_slot(name);
     if (!slot) return fail(OPTIK_HIP_EINVAL, "unknown option");
+    if (slot == &opt().grid_cap && (value < 0 || value > 0x7fffffffll))
+        return fail(OPTIK_HIP_EINVAL, "grid_cap must be >= 0 (0: the device's cap)");
     *slot = (int)value;
     return 0;
 }

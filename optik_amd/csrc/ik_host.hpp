@@ -30,6 +30,7 @@
 #include "../../include/optik_hip.h"
 #include "device_buf.hpp"
 #include "device_scope.hpp"
+#include "ik_grid.hpp"
 #include "ik_host_params.hpp"
 #include "ik_launch.hpp"
 #include "ik_launch_plan.hpp"
@@ -157,6 +158,7 @@ struct Options {
     int wide_form = WF_LDS;              // OPTIK_WIDE_FORM = lds | hbm: the general solver's form (9 .. 16 joints); 2: one-lane LDS form
     int range_rule = OPTIK_HIP_RANGE_SINGLE_INCLUSIVE;  // OPTIK_RANDOM_RANGE_RULE = new_inclusive: rand 0.9.2 reading of new chains
     int stop_x_legacy = 0;           // (no environment name) nlopt_stop_x of NLopt 2.5: no zero-step rule
+    int grid_cap = 0;                // (no environment name) >= 1: at most this many blocks per grid-stride launch (tests); 0: the device's cap
 };
 Options &opt();  // (ik_capi.hip)
 
@@ -303,12 +305,10 @@ struct optik_hip_chain {
 namespace optik {
 namespace host {
 
+// The grid of a grid-stride launch over `work` items: per_cu blocks per CU fill the device (ik_grid.hpp).
 inline int grid_for(const optik_hip_chain *ch, long long work, int block, int per_cu) {
-    long long blocks = (work + block - 1) / block;
     const long long cap = (long long)(ch->num_cus > 0 ? ch->num_cus : 256) * per_cu;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    return (int)blocks;
+    return stride_grid(work > 0 ? (unsigned long long)work : 0ull, block, cap, opt().grid_cap);
 }
 
 }  // namespace host

@@ -296,11 +296,7 @@ int motion_launch(const optik_hip_chain *ch, MotionLaunch &a, bool classify, uns
     hipLaunchKernelGGL(motion_prep_kernel, dim3((unsigned)blocks), dim3(MBLOCK), 0, stream, a);
     hipLaunchKernelGGL(motion_scan_kernel, dim3(1), dim3(MBLOCK), 0, stream, a.bsum, blocks);
     hipLaunchKernelGGL(motion_flatten_kernel, dim3((unsigned)blocks), dim3(MBLOCK), 0, stream, a, blocks);
-    const long long cap = (long long)(ch->num_cus > 0 ? ch->num_cus : 256) * 8;
-    unsigned long long grid_ll = (items_bound + MBLOCK - 1) / MBLOCK;
-    if (grid_ll > (unsigned long long)cap) grid_ll = (unsigned long long)cap;
-    if (grid_ll < 1) grid_ll = 1;
-    const int grid = (int)grid_ll;
+    const int grid = grid_for(ch, (long long)items_bound, MBLOCK, 8);  // (items_bound < 2^43: motion_reserve)
     if (ch->wide) {
         if (classify) hipLaunchKernelGGL(wide_motion_kernel<true>, dim3(grid), dim3(MBLOCK), 0, stream, a);
         else hipLaunchKernelGGL(wide_motion_kernel<false>, dim3(grid), dim3(MBLOCK), 0, stream, a);

@@ -233,8 +233,8 @@ int optik_hip_trajectory_sample(const optik_hip_chain *ch, const double *d_path,
     if (!d_path || !d_t || !d_qd || !d_status || !d_q || !d_qd_out) return fail(OPTIK_HIP_EINVAL, "bad argument");
     BIND_DEVICE(ch);
     SampleLaunch a{d_path, d_len, d_t, d_qd, d_status, P, ch->n, L, Tout, dt, d_q, d_qd_out};
-    const long long blocks = (P * Tout + SAMPLE_BLOCK - 1) / SAMPLE_BLOCK;
-    const unsigned grid = (unsigned)(blocks < SAMPLE_MAX_GRID ? blocks : SAMPLE_MAX_GRID);
+    const unsigned grid =
+        (unsigned)stride_grid((unsigned long long)(P * Tout), SAMPLE_BLOCK, SAMPLE_MAX_GRID, opt().grid_cap);
     hipLaunchKernelGGL(trajectory_sample_kernel, dim3(grid), dim3(SAMPLE_BLOCK), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return 0;

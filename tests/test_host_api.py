@@ -226,3 +226,31 @@ int main(int argc, char **argv) {
     out = subprocess.check_output([str(exe), path, base, ee], text=True).split()
     assert out[0] == "7" and out[3] == "8"
     assert abs(float(out[1]) + 2.8973) < 1e-12 and abs(float(out[2]) - 2.8973) < 1e-12
+
+
+def test_grid_cap_option_round_trips_and_refuses_negative_values(built):
+    """The test hook of the grid-stride launches (include/optik_hip.h: grid_cap): the device's own cap by default, set
+    and read back, a negative value refused and the value before it kept, restored by options(); an unknown name is
+    still refused.  No device is needed: the option is a number on the host."""
+    from optik_amd import _native as nat
+    assert nat.get_option("grid_cap") == 0
+    for v in (1, 3, 2 ** 31 - 1, 0):
+        nat.set_option("grid_cap", v)
+        assert nat.get_option("grid_cap") == v
+    nat.set_option("grid_cap", 3)
+    for bad in (-1, -(2 ** 40), 2 ** 31):
+        assert built.optik_hip_set_option(b"grid_cap", bad) == -1  # OPTIK_HIP_EINVAL
+        assert b"grid_cap" in built.optik_hip_last_error()
+        with pytest.raises(nat.OptikHipError):
+            nat.set_option("grid_cap", bad)
+        assert nat.get_option("grid_cap") == 3
+    nat.set_option("grid_cap", 0)
+    with nat.options(grid_cap=1):
+        assert nat.get_option("grid_cap") == 1
+        with nat.options(grid_cap=3, stop_x_legacy=1):
+            assert nat.get_option("grid_cap") == 3 and nat.get_option("stop_x_legacy") == 1
+        assert nat.get_option("grid_cap") == 1 and nat.get_option("stop_x_legacy") == 0
+    assert nat.get_option("grid_cap") == 0
+    assert built.optik_hip_set_option(b"grid_caps", 1) == -1 and built.optik_hip_get_option(b"grid_caps") == -1
+    with pytest.raises(nat.OptikHipError, match="unknown option"):
+        nat.set_option("no_such_option", 1)
