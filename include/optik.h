@@ -310,6 +310,16 @@ int optik_robot_collision_motion_batch(const optik_robot *robot, int64_t B, cons
  * set.  Kept with the robot and applied to every device chain it has or creates later (optik_robot_set_devices
  * included).  The other IK entry points ignore it.  rc 0, or -1 for a NaN, negative or infinite h. */
 int optik_robot_set_motion_resolution(optik_robot *robot, double h);
+/* The certified motion check (extension; include/optik_hip.h: optik_hip_collision_motion_certify_batch and what
+ * precedes it).  B segments xa, xb [B][n] row-major -> status_out [B] (OPTIK_HIP_CERTIFY_*:
+ * 0 free along the whole segment down to margin - tol, 1 blocked at t_stop, 2 max_steps reached, 3 NaN), steps_out
+ * [B], t_stop_out [B], clearance_out [B]; any may be NULL.  On the robot's first device, 65 536 segments per launch.
+ * rc 0, or -1: null argument, B < 0, tol or grid_lipschitz not finite and > 0, max_steps outside 2 .. 65 536,
+ * prismatic joints. */
+int optik_robot_collision_motion_certify_batch(const optik_robot *robot, int64_t B, const double *xa,
+                                               const double *xb, double tol, double grid_lipschitz,
+                                               int32_t max_steps, const double *ee_offset16, int32_t *status_out,
+                                               int32_t *steps_out, double *t_stop_out, double *clearance_out);
 int optik_robot_fk_ex(const optik_robot *robot, const double *x, const double *ee_offset16,
                       double *pose16_out);
 int optik_robot_joint_jacobian_ex(const optik_robot *robot, const double *x,

@@ -506,6 +506,44 @@ int optik_hip_collision_motion_batch(optik_hip_chain *chain, const double *ee_of
                                      uint8_t *d_free, int32_t *d_first, int32_t *d_steps, void *stream);
 int optik_hip_chain_set_motion_resolution(optik_hip_chain *chain, double h);
 
+/* The certified motion check (extension; the arithmetic: csrc/advance_measure.hpp).  The
+ * sampled check above says "free at the samples"; this one walks the segment q(t) = qa + t (qb - qa), t in [0, 1], by
+ * conservative advancement: at every sample each distance term of the clearance gives the largest step of t after
+ * which it can still not be below margin - tol, from bounds on how fast it can shrink (the chain's fixed translations
+ * bound the speed of every robot sphere per radian of every joint; sphere and box distances are 1-Lipschitz, the grid
+ * term is grid_lipschitz-Lipschitz), and the walk advances by the smallest of them.
+ *
+ * Per segment: status (OPTIK_HIP_CERTIFY_*), steps = the samples evaluated, t_stop, and clearance = the minimum of the
+ * evaluated samples' clearances (optik_hip_collision_batch's bits for those configurations; +inf without a model).
+ *   FREE     for every t in [0, 1] the clearance is >= margin - tol, and >= margin at the evaluated samples; t_stop 1
+ *   BLOCKED  q(t_stop) is not free (clearance < margin there)
+ *   LIMIT    max_steps samples were evaluated and t_stop < 1: nothing is said (a long grazing motion with a small
+ *            tol; or, with a grid installed, a sphere outside the grid creeping up to a boundary behind which the
+ *            field is low)
+ *   NAN      a NaN frame at t_stop (clearance NaN); or a NaN or infinite joint in qa or qb: steps 0, t_stop NaN
+ * A motion whose true minimum clearance is below margin - tol never comes back FREE, one whose minimum is >= margin
+ * never comes back BLOCKED; in between either answer is right.  The statement is about the library's clearance
+ * function: with a grid world it inherits the trilinear field's sqrt(3) * voxel, it is only as true as grid_lipschitz
+ * (sqrt(3) is valid for every grid whose neighbouring nodes differ by at most one voxel, as those of a true distance
+ * field do), and the floating-point rounding of the bounds is not accounted for (tol is meant to be many orders
+ * above 1e-16).  A free segment takes at most about max(1, grid_lipschitz) * lam_max / tol samples, lam_max the
+ * largest speed bound of a robot sphere per unit of t.
+ *
+ * optik_hip_collision_motion_certify_batch: B segments d_qa, d_qb [n][B] -> d_status [B], d_steps [B], d_t_stop [B],
+ * d_clearance [B]; any output may be NULL.  One wave per segment; stream-ordered, no host synchronisation, no
+ * workspace.  Revolute chains of 1 .. 16 joint positions.  Refused with OPTIK_HIP_EINVAL before any device work
+ * unless tol is finite and > 0, grid_lipschitz is finite and > 0, 2 <= max_steps <= OPTIK_HIP_CERTIFY_MAX_STEPS and
+ * 0 <= B <= 2^30 (B = 0 is a no-op); with OPTIK_HIP_EUNSUPPORTED: chains with prismatic joints. */
+#define OPTIK_HIP_CERTIFY_FREE 0
+#define OPTIK_HIP_CERTIFY_BLOCKED 1
+#define OPTIK_HIP_CERTIFY_LIMIT 2
+#define OPTIK_HIP_CERTIFY_NAN 3
+#define OPTIK_HIP_CERTIFY_MAX_STEPS 65536
+int optik_hip_collision_motion_certify_batch(const optik_hip_chain *chain, const double *ee_offset7,
+                                             const double *d_qa, const double *d_qb, int64_t B, double tol,
+                                             double grid_lipschitz, int32_t max_steps, int32_t *d_status,
+                                             int32_t *d_steps, double *d_t_stop, double *d_clearance, void *stream);
+
 /* Restart seeds: ChaCha8Rng::seed_from_u64(42), set_stream(i), one uniform draw
  * per joint (lib.rs:358-370, 86-91) for i = first .. first+count-1 -> d_q [n][count]. */
 int optik_hip_seed_batch(const optik_hip_chain *chain, uint64_t first, int64_t count, double *d_q,

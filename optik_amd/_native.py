@@ -143,6 +143,8 @@ def lib():
     L.optik_hip_collision_batch.argtypes = [vp, dp, vp, C.c_int64, vp, vp, vp]
     L.optik_hip_collision_motion_batch.argtypes = [vp, dp, vp, vp, C.c_int64, C.c_double, vp, vp, vp, vp, vp]
     L.optik_hip_chain_set_motion_resolution.argtypes = [vp, C.c_double]
+    L.optik_hip_collision_motion_certify_batch.argtypes = [vp, dp, vp, vp, C.c_int64, C.c_double, C.c_double,
+                                                           C.c_int32, vp, vp, vp, vp, vp]
     L.optik_hip_diff_ik_batch.argtypes = [vp, dp, vp, vp, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, vp, vp]
     L.optik_hip_collision_witness_batch.argtypes = [vp, dp, vp, C.c_int64, vp, vp, vp, vp]
     L.optik_hip_diff_ik_avoid_batch.argtypes = [vp, dp, vp, vp, C.c_int64, vp, C.c_int64, C.c_int64, C.c_double,
@@ -191,6 +193,27 @@ def check_resolution(h, allow_zero=False):
     if not (math.isfinite(h) and (h > 0.0 or (allow_zero and h == 0.0))):
         raise ValueError("motion resolution must be finite and " + (">= 0" if allow_zero else "> 0") + f", got {h}")
     return h
+
+
+# include/optik_hip.h: OPTIK_HIP_CERTIFY_*; the statuses of optik_hip_collision_motion_certify_batch
+CERTIFY_FREE, CERTIFY_BLOCKED, CERTIFY_LIMIT, CERTIFY_NAN = 0, 1, 2, 3
+CERTIFY_MAX_STEPS = 65536
+CERTIFY_STEPS = 4096  # the default max_steps: tol = lam_max / 4000 on a segment that stays free
+CERTIFY_GRID_LIPSCHITZ = math.sqrt(3.0)  # valid for every true distance field (csrc/advance_measure.hpp)
+
+
+def check_certify_args(tol, grid_lipschitz=None, max_steps=CERTIFY_STEPS):
+    """The argument rules of optik_hip_collision_motion_certify_batch, checked on the host: (tol, grid_lipschitz,
+    max_steps) as float, float, int; grid_lipschitz None is sqrt(3)."""
+    tol = float(tol)
+    if not (math.isfinite(tol) and tol > 0.0):
+        raise ValueError(f"tol must be finite and > 0, got {tol!r}")
+    G = CERTIFY_GRID_LIPSCHITZ if grid_lipschitz is None else float(grid_lipschitz)
+    if not (math.isfinite(G) and G > 0.0):
+        raise ValueError(f"grid_lipschitz must be finite and > 0, got {grid_lipschitz!r}")
+    if isinstance(max_steps, bool) or int(max_steps) != max_steps or not 2 <= int(max_steps) <= CERTIFY_MAX_STEPS:
+        raise ValueError(f"max_steps must be an integer in 2 .. {CERTIFY_MAX_STEPS}, got {max_steps!r}")
+    return tol, G, int(max_steps)
 
 
 MAX_MESH_TRIANGLES = 1 << 20  # include/optik_hip.h: OPTIK_HIP_MAX_MESH_TRIANGLES

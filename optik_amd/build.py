@@ -18,7 +18,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "liboptik_amd.so")
-SOURCES = ["ik_capi.hip", "ik_select.hip", "ik_solutions.hip", "ik_path.hip", "ik_manip.hip", "ik_collision.hip", "ik_motion.hip", "ik_avoid.hip", "ik_path_optimize.hip", "ik_roadmap.hip", "ik_shortcut.hip", "ik_time.hip", "ik_occupancy.hip", "ik_mesh.hip", "ik_batch_ops.hip", "ik_quad_kernel.hip", "ik_lane_kernel.hip", "ik_wide_kernel.hip",
+SOURCES = ["ik_capi.hip", "ik_select.hip", "ik_solutions.hip", "ik_path.hip", "ik_manip.hip", "ik_collision.hip", "ik_motion.hip", "ik_advance.hip", "ik_avoid.hip", "ik_path_optimize.hip", "ik_roadmap.hip", "ik_shortcut.hip", "ik_time.hip", "ik_occupancy.hip", "ik_mesh.hip", "ik_batch_ops.hip", "ik_quad_kernel.hip", "ik_lane_kernel.hip", "ik_wide_kernel.hip",
            "robot_host.cpp", "robot_rows.cpp"]
 # translation units: (source, object, extra flags).  ik_quad_kernel.hip is compiled twice -- its
 # throughput form (two waves per SIMD) without the machine-LICM pass, which otherwise hoists constants and
@@ -31,6 +31,7 @@ UNITS = [("ik_capi.hip", "ik_capi.o", []),          # chains, options, the resta
          ("ik_manip.hip", "ik_manip.o", []),        # manipulability / condition keys and batch (modes 3, 4)
          ("ik_collision.hip", "ik_collision.o", []),  # collision filter: key pass, link frames, clearance batch
          ("ik_motion.hip", "ik_motion.o", []),      # motion check: segments between configurations, ik_path's key pass
+         ("ik_advance.hip", "ik_advance.o", []),    # certified motion check: conservative advancement, a wave per segment
          ("ik_avoid.hip", "ik_avoid.o", []),        # clearance witnesses and gradients, diff_ik with velocity dampers
          ("ik_path_optimize.hip", "ik_path_optimize.o", []),  # covariant gradient smoothing of joint paths
          ("ik_roadmap.hip", "ik_roadmap.o", []),    # roadmap planning: nearest neighbours, checked edges, path queries
@@ -93,6 +94,8 @@ RESOURCE_LIMITS = [
     # (kernel-name regex, {field: maximum})
     (r"^optik::ik_lane_kernel<7, (true|false)>$", {"scratch": 0, "registers": 512}),
     (r"^optik::ik_quad_kernel<7, (true|false), 2>$", {"scratch": 0, "vgpr": 256}),
+    # the certified motion check keeps a whole FK in registers per lane (ik_advance.hip): no scratch for n <= 8
+    (r"^advance_kernel<[1-8], (true|false)>$", {"scratch": 0}),
 ]
 
 

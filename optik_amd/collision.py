@@ -96,6 +96,25 @@ def grid_arrays(origin, voxel, values=None, shape=None):
     return origin, float(voxel), values, shape
 
 
+def grid_lipschitz(values, voxel):
+    """The Lipschitz constant of the trilinear field over `values` [nx, ny, nz] with spacing `voxel`: the square root
+    of the sum over the three axes of (the largest absolute difference of neighbouring nodes / voxel)^2 -- inside a
+    cell each partial derivative is a convex combination of such differences.  A true distance field gives at most
+    sqrt(3), the default of the certified motion check; this is the constant to pass as its
+    `grid_lipschitz` for a grid that is not one (a clamped, smoothed or hand-made field)."""
+    v = np.asarray(values, dtype=np.float64)
+    voxel = float(voxel)
+    if v.ndim != 3 or min(v.shape) < 2:
+        raise ValueError(f"values must be [nx, ny, nz] with at least 2 nodes per axis, got {list(v.shape)}")
+    if not (math.isfinite(voxel) and voxel > 0.0):
+        raise ValueError(f"voxel must be finite and > 0, got {voxel!r}")
+    total = 0.0
+    for axis in range(3):
+        g = float(np.abs(np.diff(v, axis=axis)).max()) / voxel
+        total += g * g
+    return math.sqrt(total)
+
+
 def default_max_distance(voxel, shape):
     """The grid diagonal voxel * sqrt(nx^2 + ny^2 + nz^2): the clamp of a distance transform that never clamps while
     the grid holds both occupied and free nodes (the largest distance in it is voxel * sqrt(sum (n - 1)^2))."""

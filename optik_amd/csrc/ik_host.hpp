@@ -9,6 +9,7 @@
 //   ik_manip.hip       the manipulability / condition keys of solution modes 3 and 4, optik_hip_manip_batch
 //   ik_collision.hip   the collision filter: model and world, its key pass, link frames and clearance batches
 //   ik_motion.hip      the motion check: segments between configurations, the motion key pass of optik_hip_ik_path
+//   ik_advance.hip     the certified motion check: conservative advancement, one wave per segment
 //   ik_avoid.hip       clearance witnesses and gradients, collision-avoiding diff_ik (velocity dampers)
 //   ik_path_optimize.hip  covariant gradient smoothing of joint paths against the same witnesses
 //   ik_roadmap.hip     roadmap planning: nearest neighbours, motion-checked edges, shortest-path queries

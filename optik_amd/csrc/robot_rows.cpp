@@ -839,4 +839,43 @@ int optik_robot_collision_motion_batch(const optik_robot *r, int64_t B, const do
         });
 }
 
+int optik_robot_collision_motion_certify_batch(const optik_robot *r, int64_t B, const double *xa, const double *xb,
+                                               double tol, double grid_lipschitz, int32_t max_steps,
+                                               const double *ee16, int32_t *status_out, int32_t *steps_out,
+                                               double *t_stop_out, double *clearance_out) {
+    if (!r || !xa || !xb) return set_err(-1, "null argument");
+    if (B < 0) return set_err(-1, "bad argument");
+    // (refused on the host, before a device context exists)
+    if (!(tol > 0.0) || !std::isfinite(tol)) return set_err(-1, "motion certify: tol must be finite and > 0");
+    if (!(grid_lipschitz > 0.0) || !std::isfinite(grid_lipschitz))
+        return set_err(-1, "motion certify: grid_lipschitz must be finite and > 0");
+    if (max_steps < 2 || max_steps > OPTIK_HIP_CERTIFY_MAX_STEPS)
+        return set_err(-1, "motion certify: max_steps must be in 2 .. 65536");
+    for (int32_t t : r->types)
+        if (t == optik_host::PRISMATIC)
+            return set_err(-1, "collision: prismatic joints are not supported (IK refuses such chains)");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    if (B == 0 || (!status_out && !steps_out && !t_stop_out && !clearance_out)) return 0;
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    // per segment: qa and qb (2 n doubles) in; t_stop, the clearance, then status and steps in a third double out
+    const RowInput in[] = {{xa, (size_t)r->n}, {xb, (size_t)r->n}};
+    return stage_rows(
+        c, B, in, 3 * sizeof(double), kMotionChunk,
+        [&](optik_hip_chain *ch, const double *d_q, int64_t L, double *d_out) {
+            int32_t *d_status = reinterpret_cast<int32_t *>(d_out + 2 * L);
+            return optik_hip_collision_motion_certify_batch(ch, ee16 ? ee7 : nullptr, d_q, d_q + (size_t)r->n * L, L,
+                                                            tol, grid_lipschitz, max_steps, d_status, d_status + L,
+                                                            d_out, d_out + L, nullptr);
+        },
+        [&](size_t b0, size_t L, const double *h_out) {
+            const int32_t *h_status = reinterpret_cast<const int32_t *>(h_out + 2 * L);
+            if (t_stop_out) std::memcpy(t_stop_out + b0, h_out, sizeof(double) * L);
+            if (clearance_out) std::memcpy(clearance_out + b0, h_out + L, sizeof(double) * L);
+            if (status_out) std::memcpy(status_out + b0, h_status, sizeof(int32_t) * L);
+            if (steps_out) std::memcpy(steps_out + b0, h_status + L, sizeof(int32_t) * L);
+        });
+}
+
 }  // extern "C"

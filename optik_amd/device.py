@@ -325,6 +325,29 @@ class HipChain:
             _ptr(first), _ptr(steps), _stream_ptr()))
         return clr, free.bool(), first, steps
 
+    # -- the certified motion check (include/optik_hip.h) ----------------------------------
+    def collision_motion_certify(self, qa, qb, tol, grid_lipschitz=None, max_steps=nat.CERTIFY_STEPS, ee_offset=None):
+        """Conservative advancement along the straight joint-space motions qa[:, b] -> qb[:, b] (float64 cuda tensors
+        [n, B]; csrc/advance_measure.hpp) against the chain's model and world: a dict of device tensors, status [B]
+        int32 (nat.CERTIFY_FREE: the clearance is >= margin - tol for EVERY t in [0, 1]; CERTIFY_BLOCKED: q(t_stop)
+        is not free; CERTIFY_LIMIT: max_steps samples were not enough, nothing is said; CERTIFY_NAN), steps [B] int32
+        (samples evaluated), t_stop [B] and clearance [B] (the minimum over the evaluated samples).  grid_lipschitz:
+        the Lipschitz constant of the installed grid's trilinear field (default sqrt(3): any true distance field;
+        collision.grid_lipschitz for another grid).  ee_offset: 7 numbers, as collision_batch.  Stream-ordered."""
+        B = self._check_q(qa)
+        if self._check_q(qb) != B or qb.device != qa.device:
+            raise ValueError(f"qa and qb must have the same shape and device, got {tuple(qa.shape)} and {tuple(qb.shape)}")
+        tol, G, max_steps = nat.check_certify_args(tol, grid_lipschitz, max_steps)
+        ee = self._ee7(ee_offset)
+        out = dict(status=torch.empty(B, dtype=torch.int32, device=qa.device),
+                   steps=torch.empty(B, dtype=torch.int32, device=qa.device),
+                   t_stop=torch.empty(B, dtype=torch.float64, device=qa.device),
+                   clearance=torch.empty(B, dtype=torch.float64, device=qa.device))
+        nat.check(nat.lib().optik_hip_collision_motion_certify_batch(
+            self._h, _dp(ee) if ee is not None else None, _ptr(qa), _ptr(qb), B, tol, G, max_steps,
+            _ptr(out["status"]), _ptr(out["steps"]), _ptr(out["t_stop"]), _ptr(out["clearance"]), _stream_ptr()))
+        return out
+
     def set_motion_resolution(self, h):
         """The resolution of ik_path's motion check between a path's seed and every candidate within max_step (0:
         off, the default); it acts while a collision model is set.  Waits for the device."""

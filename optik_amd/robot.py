@@ -56,6 +56,8 @@ def _bind(L):
     L.optik_robot_collision_motion_batch.argtypes = [vp, C.c_int64, dp, dp, C.c_double, dp, dp, C.POINTER(C.c_uint8),
                                                      ip, ip]
     L.optik_robot_set_motion_resolution.argtypes = [vp, C.c_double]
+    L.optik_robot_collision_motion_certify_batch.argtypes = [vp, C.c_int64, dp, dp, C.c_double, C.c_double, C.c_int32,
+                                                             dp, ip, ip, dp, dp]
     L.optik_robot_diff_ik_ex.argtypes = [vp, dp, dp, dp, dp, C.POINTER(C.c_double), dp]
     L.optik_robot_diff_ik_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_int32)]
     L.optik_robot_collision_witness_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.POINTER(C.c_int32)]
@@ -990,6 +992,78 @@ class Robot:
         xa, xb = self._check_x(xa), self._check_x(xb)
         clr, free, first, steps = self.collision_motion_batch_arrays(xa[None], xb[None], resolution, ee_offset)
         return float(clr[0]), bool(free[0]), int(first[0]), int(steps[0])
+
+    # -- the certified motion check (extension; include/optik.h) ------------------------------
+    def collision_motion_certify_batch_arrays(self, xa, xb, tol, grid_lipschitz=None, max_steps=nat.CERTIFY_STEPS,
+                                              ee_offset=None):
+        """Conservative advancement along the straight joint-space motions xa[b] -> xb[b] ([B, n] each) against the
+        model and world: a dict of status [B] int32, steps [B] int32, t_stop [B], clearance [B].  Where
+        collision_motion_batch_arrays says "free at the samples", status 0 (nat.CERTIFY_FREE) says that the clearance
+        is >= margin - tol for EVERY t in [0, 1] (and >= margin at the `steps` samples it evaluated); 1
+        (CERTIFY_BLOCKED) exhibits q(t_stop) = xa + t_stop (xb - xa), which is not free; 2 (CERTIFY_LIMIT) says
+        nothing: max_steps samples were not enough -- a long grazing motion with a small tol, or a sphere outside an
+        installed grid creeping up to a boundary behind which the field is low; 3 (CERTIFY_NAN): a NaN or infinite
+        joint (steps 0, t_stop NaN) or a NaN frame.  A motion whose true minimum clearance is below margin - tol never
+        comes back free, one whose minimum is >= margin never comes back blocked; in between either answer is right.
+        clearance is the minimum over the evaluated samples (+inf without a model).  The statement is about the
+        library's clearance function: with a grid world it inherits the trilinear field's sqrt(3) * voxel and is only
+        as true as grid_lipschitz (None: sqrt(3), valid for every true distance field; collision.grid_lipschitz gives
+        the constant of any other grid); floating-point rounding of the bounds is not accounted for, so tol is meant
+        to be many orders above 1e-16.  ValueError for a tol or grid_lipschitz that is not finite and > 0 or a
+        max_steps outside 2 .. 65 536."""
+        xa, xb = self._check_xs(xa), self._check_xs(xb)
+        if xa.shape != xb.shape:
+            raise ValueError(f"xa and xb must have the same shape, got {list(xa.shape)} and {list(xb.shape)}")
+        tol, G, max_steps = nat.check_certify_args(tol, grid_lipschitz, max_steps)
+        B = xa.shape[0]
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        status, steps = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        t_stop, clr = np.zeros(B), np.zeros(B)
+        ip = C.POINTER(C.c_int32)
+        if self._L.optik_robot_collision_motion_certify_batch(self._h, B, _dp(xa), _dp(xb), tol, G, max_steps,
+                                                              _dp(ee) if ee is not None else None,
+                                                              status.ctypes.data_as(ip), steps.ctypes.data_as(ip),
+                                                              _dp(t_stop), _dp(clr)):
+            raise RuntimeError(_err(self._L))
+        return dict(status=status, steps=steps, t_stop=t_stop, clearance=clr)
+
+    def collision_motion_certify(self, xa, xb, tol, grid_lipschitz=None, max_steps=nat.CERTIFY_STEPS, ee_offset=None):
+        """One motion: (status, steps, t_stop, clearance) as Python scalars (see
+        collision_motion_certify_batch_arrays)."""
+        xa, xb = self._check_x(xa), self._check_x(xb)
+        r = self.collision_motion_certify_batch_arrays(xa[None], xb[None], tol, grid_lipschitz, max_steps, ee_offset)
+        return int(r["status"][0]), int(r["steps"][0]), float(r["t_stop"][0]), float(r["clearance"][0])
+
+    def certify_paths(self, paths, lens=None, tol=0.01, grid_lipschitz=None, max_steps=nat.CERTIFY_STEPS,
+                      ee_offset=None):
+        """Certifies P joint-space paths `paths` [P, L, n] with `lens` [P] waypoints each (None: L each) -- plan_paths',
+        shortcut_paths' or resample_paths' "paths" and "len" as they are: the len - 1 segments of every path go through
+        ONE collision_motion_certify_batch_arrays call.  Returns a dict: status [P] int32, the worst of the path's
+        segments in the order CERTIFY_NAN > CERTIFY_BLOCKED > CERTIFY_LIMIT > CERTIFY_FREE (a path of fewer than two
+        waypoints has no segment: free); segment [P] int32, the first segment with that status, -1 when all are free;
+        clearance [P], the minimum over the path's segments (NaN if one of them is NaN, +inf without segments)."""
+        paths, lens = self._check_paths(paths, lens)
+        nat.check_certify_args(tol, grid_lipschitz, max_steps)
+        P, L, n = paths.shape
+        lens = np.full(P, L, dtype=np.int32) if lens is None else lens
+        nseg = max(L - 1, 0)
+        valid = np.arange(nseg)[None, :] < (np.clip(lens, 0, L)[:, None] - 1)
+        status = np.zeros((P, nseg), dtype=np.int32)
+        clr = np.full((P, nseg), np.inf)
+        if valid.any():
+            r = self.collision_motion_certify_batch_arrays(paths[:, :-1][valid], paths[:, 1:][valid], tol,
+                                                           grid_lipschitz, max_steps, ee_offset)
+            status[valid], clr[valid] = r["status"], r["clearance"]
+        # the order of badness: NAN 3 > BLOCKED 2 > LIMIT 1 > FREE 0
+        rank_of = np.array([0, 2, 1, 3])
+        rank = np.where(valid, rank_of[status], 0)
+        worst = rank.max(axis=1) if nseg else np.zeros(P, dtype=np.int64)
+        seg = np.where(worst > 0, (rank == worst[:, None]).argmax(axis=1) if nseg else 0, -1).astype(np.int32)
+        out_status = np.array([nat.CERTIFY_FREE, nat.CERTIFY_LIMIT, nat.CERTIFY_BLOCKED, nat.CERTIFY_NAN],
+                              dtype=np.int32)[worst]
+        with np.errstate(invalid="ignore"):
+            clearance = np.where(np.isnan(clr).any(axis=1), np.nan, clr.min(axis=1, initial=np.inf))
+        return dict(status=out_status, segment=seg, clearance=clearance)
 
     def set_motion_resolution(self, h):
         """The resolution of ik_path*'s motion check (0, the default: off).  While it is > 0 and a collision model is
