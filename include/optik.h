@@ -198,6 +198,22 @@ int optik_robot_world_grid_from_occupancy(const optik_robot *robot, double voxel
 int optik_robot_occupancy_from_points(const optik_robot *robot, const double *origin3, double voxel, int32_t nx,
                                       int32_t ny, int32_t nz, const double *points3, int64_t N,
                                       const double *exclude4, int32_t E, uint8_t *occupied);
+/* Depth-image worlds (extension; include/optik_hip.h: optik_hip_depth_integrate and optik_hip_occupancy_from_map;
+ * DESIGN.md section 5.23).  Host arrays, on the robot's first device; both install nothing and keep nothing: the
+ * caller owns the map.  optik_robot_depth_integrate: `map` (nx * ny * nz int16, OPTIK_HIP_MAP_UNKNOWN = -32768 where
+ * never observed; read, then written back) takes the evidence of the F images of `depth` ([F][H][W] floats, z-depth in
+ * metres) seen with intrinsics4 [F][4] (fx, fy, cx, cy) from poses16 [F][16] (column-major 4x4 each, as
+ * optik_robot_fk_ex writes them; x right, y down, z forward); pixels on the E exclude4 spheres carve and do not mark.
+ * optik_robot_occupancy_from_map: occupied (nx * ny * nz bytes) = unknown_occupied where the map is unknown, (e >=
+ * threshold) elsewhere; accumulate != 0 ORs that into what `occupied` holds.  rc 0, or -1: the refusals of the kernel
+ * layer, and a non-finite exclusion sphere. */
+int optik_robot_depth_integrate(const optik_robot *robot, const double *origin3, double voxel, int32_t nx, int32_t ny,
+                                int32_t nz, int16_t *map, const float *depth, int32_t F, int32_t H, int32_t W,
+                                const double *intrinsics4, const double *poses16, const double *exclude4, int32_t E,
+                                double z_near, double z_far, double band, int32_t hit, int32_t miss, int32_t e_min,
+                                int32_t e_max);
+int optik_robot_occupancy_from_map(const optik_robot *robot, int32_t nx, int32_t ny, int32_t nz, const int16_t *map,
+                                   int32_t threshold, int32_t unknown_occupied, int32_t accumulate, uint8_t *occupied);
 /* From a triangle mesh to that grid (extension; include/optik_hip.h: optik_hip_world_grid_from_mesh).  Host arrays,
  * on the robot's first device; installs nothing.  tris9 [M][9]: the vertices a, b, c of each triangle in the base
  * frame -> values_out (nx * ny * nz floats): the signed distance to the mesh, clamped to +-max_distance.  rc 0, or -1:

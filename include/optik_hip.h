@@ -444,6 +444,45 @@ int optik_hip_occupancy_from_points(const optik_hip_chain *chain, const double *
                                     int32_t ny, int32_t nz, const double *d_points3, int64_t N,
                                     const double *d_exclude4, int32_t E, uint8_t *d_occupied, void *stream);
 
+/* Depth-image worlds: a persistent evidence map with free-space carving (extension; the
+ * arithmetic: csrc/depth_measure.hpp).  The map is int16 [nx][ny][nz] in device memory on the nodes of a grid as above
+ * (z fastest), owned by the caller: OPTIK_HIP_MAP_UNKNOWN at a node that was never observed (a new map is all that),
+ * evidence in [e_min, e_max] elsewhere.  Both calls are stream-ordered and install nothing.
+ *
+ * optik_hip_depth_integrate applies F depth images (d_depth: [F][H][W] floats in device memory, z-depth in metres
+ * along the optical axis, pixel centres at integer coordinates, rectified) to d_map in place, in order.  intrinsics4
+ * ([F][4]: fx, fy, cx, cy) and poses16 ([F][16]: the camera in the base frame as a column-major 4x4, x right, y down,
+ * z forward) are HOST arrays, read before the call returns.  Every node is projected into each image and gathers the
+ * nearest pixel: a node in front of the surface by more than `band` loses `miss` (carved free; floor e_min), a node
+ * within `band` of it gains `hit` (ceiling e_max), a node behind it, outside the image, outside (z_near, z_far] or
+ * under an invalid pixel (NaN, infinite, <= z_near) keeps its value; a pixel beyond z_far carves up to z_far and marks
+ * nothing.  A pixel whose point lies in one of the E exclusion spheres of d_exclude4 ([E][4] doubles in device memory,
+ * base frame: the self-filter) carves in front of itself and marks nothing.  A call with F frames leaves the bits
+ * that F calls with one frame leave.  The cleaned images live in a workspace the chain owns (4 bytes per pixel of up
+ * to 8 frames, at most 256 MiB); it grows on demand, which waits for the device, and is freed with the chain.  One
+ * call per chain at a time.
+ *
+ * optik_hip_occupancy_from_map writes d_occupied[node] = unknown_occupied (as 0 / 1) where the map is unknown and
+ * (e >= threshold) elsewhere; with accumulate != 0 it ORs that into what d_occupied holds, so that a map and a point
+ * cloud (optik_hip_occupancy_from_points) feed one distance transform.
+ *
+ * Refused with OPTIK_HIP_EINVAL before any device work: a grid that set_world_grid would refuse for its geometry, F
+ * outside 1 .. OPTIK_HIP_MAX_DEPTH_FRAMES, H or W outside 1 .. OPTIK_HIP_MAX_DEPTH_DIM, E outside 0 ..
+ * OPTIK_HIP_MAX_EXCLUDE_SPHERES, unless 0 < z_near < z_far and band >= 0, all finite, hit or miss outside 1 .. 1024,
+ * e_min outside -32767 .. 0, e_max outside 0 .. 32767, intrinsics that are not finite with fx, fy > 0, a pose that is
+ * not finite, a threshold outside -32767 .. 32767, a null buffer that is needed. */
+#define OPTIK_HIP_MAP_UNKNOWN (-32768)
+#define OPTIK_HIP_MAX_DEPTH_FRAMES 64
+#define OPTIK_HIP_MAX_DEPTH_DIM 4096
+int optik_hip_depth_integrate(optik_hip_chain *chain, const double *origin3, double voxel, int32_t nx, int32_t ny,
+                              int32_t nz, int16_t *d_map, const float *d_depth, int32_t F, int32_t H, int32_t W,
+                              const double *intrinsics4, const double *poses16, const double *d_exclude4, int32_t E,
+                              double z_near, double z_far, double band, int32_t hit, int32_t miss, int32_t e_min,
+                              int32_t e_max, void *stream);
+int optik_hip_occupancy_from_map(const optik_hip_chain *chain, int32_t nx, int32_t ny, int32_t nz, const int16_t *d_map,
+                                 int32_t threshold, int32_t unknown_occupied, int32_t accumulate, uint8_t *d_occupied,
+                                 void *stream);
+
 /* From a triangle mesh to a distance-field world (extension; the arithmetic:
  * csrc/mesh_measure.hpp).  d_tris9 is a triangle soup in device memory, [M][9] doubles: the vertices a, b, c of each
  * triangle in the base frame; no connectivity, welding or closedness is needed.

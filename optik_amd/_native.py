@@ -134,6 +134,11 @@ def lib():
                                                       vp, vp]
     L.optik_hip_occupancy_from_points.argtypes = [vp, dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64,
                                                   vp, C.c_int32, vp, vp]
+    L.optik_hip_depth_integrate.argtypes = [vp, dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_int32,
+                                            C.c_int32, C.c_int32, dp, dp, vp, C.c_int32, C.c_double, C.c_double,
+                                            C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]
+    L.optik_hip_occupancy_from_map.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32,
+                                               vp, vp]
     L.optik_hip_world_grid_from_mesh.argtypes = [vp, dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32,
                                                  C.c_double, vp, vp]
     L.optik_hip_mesh_tile.restype = C.c_int32

@@ -142,6 +142,46 @@ def cloud_arrays(points, exclude=None):
     return np.ascontiguousarray(points), np.ascontiguousarray(exclude)
 
 
+MAP_UNKNOWN = -32768   # OPTIK_HIP_MAP_UNKNOWN: a node of an evidence map that was never observed
+MAX_DEPTH_FRAMES = 64  # OPTIK_HIP_MAX_DEPTH_FRAMES
+MAX_DEPTH_DIM = 4096   # OPTIK_HIP_MAX_DEPTH_DIM
+# The defaults of depth_integrate / set_world_depth: the values with which examples/ik_world_depth.py marks its box
+# in one frame and clears it in five, and nothing more -- no sensor was characterised to choose them.
+DEPTH_DEFAULTS = dict(z_near=0.1, z_far=4.0, hit=2, miss=1, e_min=-4, e_max=6)
+DEPTH_THRESHOLD = 2
+
+
+def camera_arrays(intrinsics, poses, frames=None):
+    """(intrinsics float64 [F, 4], poses float64 [F, 16], each pose a column-major 4x4) in the layout of the C ABI.
+    intrinsics: (fx, fy, cx, cy) per frame, [F, 4] or one row for every frame; poses: the camera in the base frame as
+    row-major 4x4 matrices (what Robot.fk returns), [F, 4, 4] or one [4, 4].  Shapes are checked here; the values by
+    the C layer."""
+    poses = np.asarray(poses, dtype=np.float64)
+    if poses.shape == (4, 4):
+        poses = poses[None]
+    if poses.ndim != 3 or poses.shape[1:] != (4, 4):
+        raise ValueError(f"poses must be [F, 4, 4] or one [4, 4], got {list(poses.shape)}")
+    F = len(poses) if frames is None else int(frames)
+    if len(poses) != F:
+        raise ValueError(f"{F} depth images need {F} camera poses, got {len(poses)}")
+    intrinsics = np.asarray(intrinsics, dtype=np.float64)
+    if intrinsics.shape == (4,):
+        intrinsics = np.broadcast_to(intrinsics, (F, 4))
+    if intrinsics.shape != (F, 4):
+        raise ValueError(f"intrinsics must be [F, 4] (fx, fy, cx, cy) or one such row, got {list(intrinsics.shape)}")
+    return np.ascontiguousarray(intrinsics), np.ascontiguousarray(poses.transpose(0, 2, 1)).reshape(F, 16)
+
+
+def depth_arrays(depth):
+    """float32 [F, H, W], C-contiguous, from a stack of depth images or one [H, W] image (F = 1)."""
+    depth = np.asarray(depth, dtype=np.float32)
+    if depth.ndim == 2:
+        depth = depth[None]
+    if depth.ndim != 3:
+        raise ValueError(f"depth must be [F, H, W] or one [H, W] image, got {list(depth.shape)}")
+    return np.ascontiguousarray(depth)
+
+
 def mesh_arrays(vertices, triangles=None):
     """A mesh as the triangle soup of the C ABI, float64 [M, 9] (the vertices a, b, c of each triangle, base frame),
     C-contiguous.  Either `vertices` [V, 3] with `triangles` [M, 3] integer indices into it (range-checked here), or,

@@ -160,6 +160,63 @@ inline int check_cloud(int64_t N, int32_t E, std::string &err) {
     return 0;
 }
 
+// The arguments of the evidence map beyond the grid's geometry (depth_measure.hpp): the image
+// stack, the ranges and the update constants ...
+inline int check_depth(int32_t F, int32_t H, int32_t W, int32_t E, double z_near, double z_far, double band, int32_t hit,
+                       int32_t miss, int32_t e_min, int32_t e_max, std::string &err) {
+    if (F < 1 || F > OPTIK_HIP_MAX_DEPTH_FRAMES) { err = "depth integrate: the frame count must be in 1..64"; return OPTIK_HIP_EINVAL; }
+    if (H < 1 || H > OPTIK_HIP_MAX_DEPTH_DIM || W < 1 || W > OPTIK_HIP_MAX_DEPTH_DIM) {
+        err = "depth integrate: the image height and width must be in 1..4096, got " + std::to_string(H) + " x "
+              + std::to_string(W);
+        return OPTIK_HIP_EINVAL;
+    }
+    if (E < 0 || E > OPTIK_HIP_MAX_EXCLUDE_SPHERES) {
+        err = "depth integrate: the exclusion sphere count must be in 0..1024";
+        return OPTIK_HIP_EINVAL;
+    }
+    if (!std::isfinite(z_near) || !std::isfinite(z_far) || !(z_near > 0.0) || !(z_far > z_near)) {
+        err = "depth integrate: z_near and z_far must be finite with 0 < z_near < z_far";
+        return OPTIK_HIP_EINVAL;
+    }
+    if (!std::isfinite(band) || !(band >= 0.0)) { err = "depth integrate: band must be finite and >= 0"; return OPTIK_HIP_EINVAL; }
+    if (hit < 1 || hit > 1024 || miss < 1 || miss > 1024) {
+        err = "depth integrate: hit and miss must be in 1..1024";
+        return OPTIK_HIP_EINVAL;
+    }
+    if (e_min < -32767 || e_min > 0 || e_max < 0 || e_max > 32767) {
+        err = "depth integrate: e_min must be in -32767..0 and e_max in 0..32767";
+        return OPTIK_HIP_EINVAL;
+    }
+    return 0;
+}
+
+// ... and the cameras, host arrays [F][4] and [F][16]: fx, fy > 0, everything finite.
+inline int check_cameras(int32_t F, const double *intrinsics4, const double *poses16, std::string &err) {
+    if (!intrinsics4 || !poses16) { err = "depth integrate: null intrinsics or poses"; return OPTIK_HIP_EINVAL; }
+    for (int32_t f = 0; f < F; ++f) {
+        const double *k = intrinsics4 + 4 * f;
+        if (!std::isfinite(k[0]) || !std::isfinite(k[1]) || !std::isfinite(k[2]) || !std::isfinite(k[3]) || !(k[0] > 0.0)
+            || !(k[1] > 0.0)) {
+            err = "depth integrate: the intrinsics of frame " + std::to_string(f) + " must be finite with fx, fy > 0";
+            return OPTIK_HIP_EINVAL;
+        }
+        for (int i = 0; i < 16; ++i)
+            if (!std::isfinite(poses16[16 * f + i])) {
+                err = "depth integrate: the camera pose of frame " + std::to_string(f) + " is not finite";
+                return OPTIK_HIP_EINVAL;
+            }
+    }
+    return 0;
+}
+
+inline int check_map_threshold(int32_t threshold, std::string &err) {
+    if (threshold < -32767 || threshold > 32767) {
+        err = "occupancy from map: the threshold must be in -32767..32767";
+        return OPTIK_HIP_EINVAL;
+    }
+    return 0;
+}
+
 inline const char *bake_empty_msg() { return "world grid bake: the world has no spheres and no boxes"; }
 
 // The device layout of a checked model; returns the number of pair groups.  `orig` (optional) receives the way back

@@ -301,6 +301,9 @@ struct optik_hip_chain {
     // the distance transform (ik_occupancy.hip): the two ping-pong buffers of optik_hip_world_grid_from_occupancy, 16
     // bytes per node (256 MiB at 2^24 nodes); grown on demand
     optik::DeviceBuf<unsigned char> edt_ws;  // bytes
+    // the evidence map (ik_depth.hip): the cleaned images of one launch of optik_hip_depth_integrate, 4 bytes per
+    // pixel of up to 8 frames; grown on demand
+    optik::DeviceBuf<float> depth_ws;
 };
 
 namespace optik {

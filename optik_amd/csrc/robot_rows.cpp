@@ -298,6 +298,72 @@ int optik_robot_occupancy_from_points(const optik_robot *r, const double *origin
     return 0;
 }
 
+int optik_robot_depth_integrate(const optik_robot *r, const double *origin3, double voxel, int32_t nx, int32_t ny,
+                                int32_t nz, int16_t *map, const float *depth, int32_t F, int32_t H, int32_t W,
+                                const double *intrinsics4, const double *poses16, const double *exclude4, int32_t E,
+                                double z_near, double z_far, double band, int32_t hit, int32_t miss, int32_t e_min,
+                                int32_t e_max) {
+    if (!r) return set_err(-1, "null argument");
+    std::string err;
+    if (optik::coll::check_grid(origin3, voxel, nx, ny, nz, nullptr, false, err)
+        || optik::coll::check_depth(F, H, W, E, z_near, z_far, band, hit, miss, e_min, e_max, err)
+        || optik::coll::check_cameras(F, intrinsics4, poses16, err))
+        return set_err(-1, err);
+    if (!map || !depth || (E > 0 && !exclude4)) return set_err(-1, "null argument");
+    for (int64_t k = 0; k < 4 * (int64_t)E; ++k)
+        if (!std::isfinite(exclude4[k])) return set_err(-1, "depth integrate: non-finite exclusion sphere");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    BatchGuard guard(c);
+    if (!guard.ok()) return set_err(-1, kSetDeviceMsg);
+    const size_t nodes = (size_t)nx * (size_t)ny * (size_t)nz, pixels = (size_t)F * (size_t)H * (size_t)W;
+    // one block: the exclusion spheres, the images, then the map
+    optik::DeviceBuf<uint8_t> block;
+    if (block.reserve(sizeof(double) * 4 * (size_t)E + sizeof(float) * pixels + sizeof(int16_t) * nodes) != hipSuccess)
+        return set_err(-1, "depth buffer allocation failed");
+    double *d_exc = reinterpret_cast<double *>(block.get());
+    float *d_depth = reinterpret_cast<float *>(d_exc + 4 * (size_t)E);
+    int16_t *d_map = reinterpret_cast<int16_t *>(d_depth + pixels);
+    if ((E > 0 && hipMemcpy(d_exc, exclude4, sizeof(double) * 4 * (size_t)E, hipMemcpyHostToDevice) != hipSuccess)
+        || hipMemcpy(d_depth, depth, sizeof(float) * pixels, hipMemcpyHostToDevice) != hipSuccess
+        || hipMemcpy(d_map, map, sizeof(int16_t) * nodes, hipMemcpyHostToDevice) != hipSuccess)
+        return set_err(-1, "upload failed");
+    if (optik_hip_depth_integrate(c->chain, origin3, voxel, nx, ny, nz, d_map, d_depth, F, H, W, intrinsics4, poses16,
+                                  E > 0 ? d_exc : nullptr, E, z_near, z_far, band, hit, miss, e_min, e_max, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (hipMemcpy(map, d_map, sizeof(int16_t) * nodes, hipMemcpyDeviceToHost) != hipSuccess)
+        return set_err(-1, "download failed");
+    return 0;
+}
+
+int optik_robot_occupancy_from_map(const optik_robot *r, int32_t nx, int32_t ny, int32_t nz, const int16_t *map,
+                                   int32_t threshold, int32_t unknown_occupied, int32_t accumulate, uint8_t *occupied) {
+    if (!r) return set_err(-1, "null argument");
+    std::string err;
+    const double zero3[3] = {0.0, 0.0, 0.0};
+    if (optik::coll::check_grid(zero3, 1.0, nx, ny, nz, nullptr, false, err)
+        || optik::coll::check_map_threshold(threshold, err))
+        return set_err(-1, err);
+    if (!map || !occupied) return set_err(-1, "null argument");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    BatchGuard guard(c);
+    if (!guard.ok()) return set_err(-1, kSetDeviceMsg);
+    const size_t nodes = (size_t)nx * (size_t)ny * (size_t)nz;
+    // one block: the map, then the occupancy bytes
+    optik::DeviceBuf<uint8_t> block;
+    if (block.reserve(3 * nodes) != hipSuccess) return set_err(-1, "map buffer allocation failed");
+    int16_t *d_map = reinterpret_cast<int16_t *>(block.get());
+    uint8_t *d_occ = reinterpret_cast<uint8_t *>(d_map + nodes);
+    if (hipMemcpy(d_map, map, sizeof(int16_t) * nodes, hipMemcpyHostToDevice) != hipSuccess
+        || (accumulate && hipMemcpy(d_occ, occupied, nodes, hipMemcpyHostToDevice) != hipSuccess))
+        return set_err(-1, "upload failed");
+    if (optik_hip_occupancy_from_map(c->chain, nx, ny, nz, d_map, threshold, unknown_occupied, accumulate, d_occ, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (hipMemcpy(occupied, d_occ, nodes, hipMemcpyDeviceToHost) != hipSuccess) return set_err(-1, "download failed");
+    return 0;
+}
+
 int optik_robot_world_grid_from_mesh(const optik_robot *r, const double *origin3, double voxel, int32_t nx, int32_t ny,
                                      int32_t nz, const double *tris9, int32_t M, double max_distance,
                                      float *values_out) {

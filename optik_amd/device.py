@@ -248,6 +248,62 @@ class HipChain:
                                                             _ptr(into), _stream_ptr()))
         return into
 
+    # -- depth-image worlds: the evidence map (include/optik_hip.h) ---------------------------
+    def depth_integrate(self, map, origin, voxel, depth, intrinsics, poses, exclude=None, z_near=None, z_far=None,
+                        band=None, hit=None, miss=None, e_min=None, e_max=None):
+        """Applies depth images to an evidence map, in place, and returns it.  map: a contiguous int16 cuda tensor
+        [nx, ny, nz], -32768 (optik_amd.collision.MAP_UNKNOWN) where nothing was ever observed; depth: a contiguous
+        float32 cuda tensor [F, H, W] or [H, W], z-depth in metres; intrinsics (fx, fy, cx, cy) [F, 4] or one row and
+        poses [F, 4, 4] or one [4, 4] (row-major, the camera in the base frame: x right, y down, z forward) are host
+        arrays; exclude: a float64 cuda tensor [E, 4], the self-filter's spheres.  Per frame every node gathers its
+        nearest pixel: more than `band` in front of the surface it loses `miss` (floor e_min), within `band` of it it
+        gains `hit` (ceiling e_max), behind it, out of view or under an invalid pixel it keeps its value.  band
+        defaults to voxel and the rest to optik_amd.collision.DEPTH_DEFAULTS (Robot.depth_integrate says what those
+        are).  Stream-ordered; the chain's workspace for the cleaned images grows on demand."""
+        from .collision import DEPTH_DEFAULTS, camera_arrays, grid_arrays
+        if not (isinstance(map, torch.Tensor) and map.is_cuda and map.dtype == torch.int16 and map.dim() == 3
+                and map.is_contiguous()):
+            raise ValueError("map must be a contiguous int16 cuda tensor [nx, ny, nz]")
+        o, v, _, (nx, ny, nz) = grid_arrays(origin, voxel, shape=tuple(map.shape))
+        if not (isinstance(depth, torch.Tensor) and depth.is_cuda and depth.dtype == torch.float32
+                and depth.dim() in (2, 3) and depth.is_contiguous()):
+            raise ValueError("depth must be a contiguous float32 cuda tensor [F, H, W] or [H, W]")
+        F, H, W = (1, *depth.shape) if depth.dim() == 2 else (int(s) for s in depth.shape)
+        k4, p16 = camera_arrays(intrinsics, poses, F)
+        E = 0
+        if exclude is not None:
+            if not (isinstance(exclude, torch.Tensor) and exclude.is_cuda and exclude.dtype == torch.float64
+                    and exclude.dim() == 2 and exclude.shape[1] == 4 and exclude.is_contiguous()):
+                raise ValueError("exclude must be a contiguous float64 cuda tensor [E, 4]")
+            E = int(exclude.shape[0])
+        a = {k: (DEPTH_DEFAULTS[k] if val is None else val) for k, val in
+             dict(z_near=z_near, z_far=z_far, hit=hit, miss=miss, e_min=e_min, e_max=e_max).items()}
+        nat.check(nat.lib().optik_hip_depth_integrate(
+            self._h, _dp(o), v, nx, ny, nz, _ptr(map), _ptr(depth), F, int(H), int(W), _dp(k4), _dp(p16),
+            _ptr(exclude) if E else None, E, float(a["z_near"]), float(a["z_far"]), v if band is None else float(band),
+            int(a["hit"]), int(a["miss"]), int(a["e_min"]), int(a["e_max"]), _stream_ptr()))
+        return map
+
+    def occupancy_from_map(self, map, threshold, unknown_occupied=False, into=None):
+        """The occupancy of an evidence map (a contiguous int16 cuda tensor [nx, ny, nz]): a uint8 cuda tensor of that
+        shape, 1 where the evidence is >= threshold, `unknown_occupied` where nothing was ever observed.  `into`: a
+        tensor of that kind to OR into, in place (it is also what is returned), as occupancy_from_points has -- a map
+        and a point cloud then feed one world_grid_from_occupancy.  Stream-ordered."""
+        if not (isinstance(map, torch.Tensor) and map.is_cuda and map.dtype == torch.int16 and map.dim() == 3
+                and map.is_contiguous()):
+            raise ValueError("map must be a contiguous int16 cuda tensor [nx, ny, nz]")
+        nx, ny, nz = (int(s) for s in map.shape)
+        accumulate = into is not None
+        if into is None:
+            into = torch.empty((nx, ny, nz), dtype=torch.uint8, device=map.device)
+        elif not (isinstance(into, torch.Tensor) and into.is_cuda and into.dtype == torch.uint8
+                  and tuple(into.shape) == (nx, ny, nz) and into.is_contiguous()):
+            raise ValueError("into must be a contiguous uint8 cuda tensor of the map's shape")
+        nat.check(nat.lib().optik_hip_occupancy_from_map(self._h, nx, ny, nz, _ptr(map), int(threshold),
+                                                         1 if unknown_occupied else 0, 1 if accumulate else 0,
+                                                         _ptr(into), _stream_ptr()))
+        return into
+
     # -- from a triangle mesh to that grid (include/optik_hip.h; DESIGN.md section 5.21) ------------------------------
     def world_grid_from_mesh(self, origin, voxel, shape, triangles, max_distance=None):
         """The signed distance field of a triangle soup (a contiguous float64 cuda tensor [M, 3, 3] or [M, 9]: the

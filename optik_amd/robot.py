@@ -49,6 +49,11 @@ def _bind(L):
                                                         vp]
     L.optik_robot_occupancy_from_points.argtypes = [vp, dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64,
                                                     vp, C.c_int32, vp]
+    L.optik_robot_depth_integrate.argtypes = [vp, dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_int32,
+                                              C.c_int32, C.c_int32, dp, dp, vp, C.c_int32, C.c_double, C.c_double,
+                                              C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    L.optik_robot_occupancy_from_map.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32,
+                                                 C.c_int32, vp]
     L.optik_robot_world_grid_from_mesh.argtypes = [vp, dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32,
                                                    C.c_double, vp]
     L.optik_robot_link_frames_batch.argtypes = [vp, C.c_int64, dp, dp, dp]
@@ -663,6 +668,96 @@ class Robot:
         values = self.world_grid_from_occupancy(voxel, occ, max_distance)
         self.set_world_grid(origin, voxel, values)
         return values
+
+    # -- depth-image worlds: the evidence map (extension; include/optik.h) --------------------
+    @staticmethod
+    def new_depth_map(shape):
+        """An evidence map in which nothing has been observed: np.int16 [nx, ny, nz], all
+        optik_amd.collision.MAP_UNKNOWN (-32768).  The caller owns it; depth_integrate returns the next one."""
+        from .collision import MAP_UNKNOWN
+        shape = tuple(int(v) for v in shape)
+        if len(shape) != 3:
+            raise ValueError("shape must be (nx, ny, nz)")
+        return np.full(shape, MAP_UNKNOWN, dtype=np.int16)
+
+    def depth_integrate(self, map, origin, voxel, depth, intrinsics, poses, exclude=None, z_near=None, z_far=None,
+                        band=None, hit=None, miss=None, e_min=None, e_max=None):
+        """The evidence map after `depth` has been seen, on the GPU: a new np.int16 [nx, ny, nz] (`map` is not
+        modified).  map: an earlier result or new_depth_map(shape), on the node lattice of set_world_grid (origin,
+        voxel); depth: [F, H, W] or one [H, W] image, z-depth in metres along the optical axis (what ROS and RealSense
+        depth images hold), rectified, pixel centres at integer coordinates; intrinsics: (fx, fy, cx, cy), [F, 4] or
+        one row for all frames; poses: the camera in the base frame, [F, 4, 4] or one [4, 4] as fk returns it (x
+        right, y down, z forward); exclude: [E, 4] spheres (centre, radius) in the base frame, the self-filter
+        (optik_amd.collision.spheres_at): a pixel on one of them sees the robot, which frees the space in front of it
+        and is no obstacle.
+
+        Per frame, in order, every node is projected into the image and reads its nearest pixel: a node more than
+        `band` in front of the surface loses `miss` (carved free; never below e_min), a node within `band` of it gains
+        `hit` (never above e_max), and a node behind the surface, outside the image, outside (z_near, z_far] or under
+        an invalid pixel (NaN, infinite, <= z_near) keeps what it has -- unknown (-32768) if it was never observed.  A
+        pixel beyond z_far carves up to z_far and marks nothing.  An unknown node counts from 0.
+
+        band defaults to voxel: a band of at least sqrt(3)/2 * voxel = 0.87 * voxel is needed for every surface point
+        to have a node within it (the farthest a point can be from its nearest node is half a cell diagonal), and
+        anything thinner than the band can be carved by a camera that sees behind it.  The other defaults
+        (optik_amd.collision.DEPTH_DEFAULTS: z_near 0.1, z_far 4.0, hit 2, miss 1, e_min -4, e_max 6) are the values
+        with which examples/ik_world_depth.py clears and re-marks its scene, and nothing more.
+        ValueError for a refused grid, image stack, range, constant, camera or exclusion sphere."""
+        from .collision import DEPTH_DEFAULTS, camera_arrays, cloud_arrays, depth_arrays, grid_arrays
+        m = np.array(map, dtype=np.int16, order="C")  # (a copy: the C layer reads it, then writes it back)
+        if m.ndim != 3:
+            raise ValueError(f"map must be [nx, ny, nz], got {list(m.shape)}")
+        o, v, _, (nx, ny, nz) = grid_arrays(origin, voxel, shape=m.shape)
+        d = depth_arrays(depth)
+        F, H, W = d.shape
+        k4, p16 = camera_arrays(intrinsics, poses, F)
+        _, exc = cloud_arrays(np.zeros((0, 3)), exclude)
+        a = {k: (DEPTH_DEFAULTS[k] if val is None else val) for k, val in
+             dict(z_near=z_near, z_far=z_far, hit=hit, miss=miss, e_min=e_min, e_max=e_max).items()}
+        if self._L.optik_robot_depth_integrate(
+                self._h, _dp(o), v, nx, ny, nz, C.c_void_p(m.ctypes.data), C.c_void_p(d.ctypes.data), F, H, W, _dp(k4),
+                _dp(p16), C.c_void_p(exc.ctypes.data) if len(exc) else None, len(exc), float(a["z_near"]),
+                float(a["z_far"]), v if band is None else float(band), int(a["hit"]), int(a["miss"]), int(a["e_min"]),
+                int(a["e_max"])):
+            raise ValueError(_err(self._L))
+        return m
+
+    def occupancy_from_map(self, map, threshold=None, unknown_occupied=False, into=None):
+        """The occupancy of an evidence map, on the GPU: a bool array [nx, ny, nz], True where the evidence is >=
+        threshold (default optik_amd.collision.DEPTH_THRESHOLD = 2: one hit at the default constants) and
+        `unknown_occupied` where nothing was ever observed.  `into`: an earlier occupancy to OR into (it is not
+        modified), as occupancy_from_points has: a map and a point cloud then feed one world_grid_from_occupancy."""
+        from .collision import DEPTH_THRESHOLD, occupancy_array
+        m = np.ascontiguousarray(map, dtype=np.int16)
+        if m.ndim != 3:
+            raise ValueError(f"map must be [nx, ny, nz], got {list(m.shape)}")
+        nx, ny, nz = m.shape
+        if into is not None:
+            occ = occupancy_array(into).copy()
+            if occ.shape != m.shape:
+                raise ValueError("into does not have the map's shape")
+        else:
+            occ = np.zeros(m.shape, dtype=np.uint8)
+        if self._L.optik_robot_occupancy_from_map(self._h, nx, ny, nz, C.c_void_p(m.ctypes.data),
+                                                  int(DEPTH_THRESHOLD if threshold is None else threshold),
+                                                  1 if unknown_occupied else 0, 1 if into is not None else 0,
+                                                  C.c_void_p(occ.ctypes.data)):
+            raise ValueError(_err(self._L))
+        return occ.view(bool)
+
+    def set_world_depth(self, map, origin, voxel, depth, intrinsics, poses, exclude=None, z_near=None, z_far=None,
+                        band=None, hit=None, miss=None, e_min=None, e_max=None, threshold=None,
+                        unknown_occupied=False, max_distance=None):
+        """From depth images to the installed distance-field world: depth_integrate, then occupancy_from_map, then
+        world_grid_from_occupancy, then set_world_grid.  Returns (map, values): the next evidence map, to be handed
+        back with the next images, and the values it installed.  The error bounds of set_world_grid and
+        world_grid_from_occupancy apply to that field as they stand."""
+        map = self.depth_integrate(map, origin, voxel, depth, intrinsics, poses, exclude, z_near, z_far, band, hit, miss,
+                                   e_min, e_max)
+        occ = self.occupancy_from_map(map, threshold, unknown_occupied)
+        values = self.world_grid_from_occupancy(voxel, occ, max_distance)
+        self.set_world_grid(origin, voxel, values)
+        return map, values
 
     # -- from a triangle mesh to that grid (extension; include/optik.h, DESIGN.md section 5.21) ------------------------
     def world_grid_from_mesh(self, origin, voxel, shape, vertices, triangles=None, max_distance=None):
