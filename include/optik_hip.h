@@ -615,7 +615,8 @@ typedef struct optik_hip_ik_outputs {
     double *d_win_x;      /* [T][n]                                           */
     double *d_win_f;      /* [T]                                              */
     uint64_t *d_win_idx;  /* [T] winning restart index, UINT64_MAX if none    */
-    double *d_win_key;    /* [T] Quality: ||x - x0||_2 ; Speed: (double)index ; Manipulability: -w ; Condition: -c */
+    double *d_win_key;    /* [T] Quality: ||x - x0||_2 ; Speed: (double)index ; Manipulability: -w ; Condition: -c ;
+                           *     +inf if none (d_win_x and d_win_f are NaN then), as optik_hip_ik_path's d_key */
 } optik_hip_ik_outputs;
 
 /* The hot path: for each of T targets run restarts restart_begin..restart_end-1
@@ -689,6 +690,30 @@ int optik_hip_ik_path(optik_hip_chain *chain, const optik_solver_config *cfg, co
                       const double *d_x0, int32_t P, int32_t L, const double *ee_offset7, uint64_t restart_begin,
                       uint64_t restart_end, uint32_t flags, double deadline_s, double max_step,
                       const optik_hip_ik_path_outputs *out, void *stream);
+
+/* Test hooks: the selection stage of the three entry points above on the caller's own per-restart arrays, with no
+ * solve in front -- what optik_hip_ik_batch, optik_hip_ik_solutions and one waypoint of optik_hip_ik_path launch behind
+ * their solver, from the same launch code and tile plan.  d_key [T*R] (+inf or NaN: no candidate), d_x [n][T*R],
+ * d_f [T*R], column t*R + (i - restart_begin); n is the chain's.  The selection order is (key, index): the smaller key,
+ * ties to the smaller index; -0.0 == +0.0 is a tie.  Stream-ordered; they take the chain's launch mutex and use its
+ * tile workspace, and leave its work-item counter and first-success words alone.
+ *   _select_from_keys     reads only the d_win_* fields of `out`; d_x / d_f may be NULL if d_win_x / d_win_f are.
+ *   _solutions_from_keys  d_key is scratch: eliminated candidates' keys become +inf (the multi-tile form, R > 4096).
+ *   _path_select_from_keys  d_seed [P][n]; out is one waypoint's (L = 1: [P][n], [P]; d_last a copy of d_carry);
+ *                           d_carry [P][n], not NULL, receives the next seeds and may be d_seed itself.
+ * Refused as the entry points refuse: T or P < 1, R < 1 or restart_begin + R above UINT64_MAX, 2^24 or more selection
+ * tiles, K outside 1..OPTIK_HIP_MAX_SOLUTIONS, a NaN, negative or infinite min_dist, R above
+ * OPTIK_HIP_PATH_MAX_RESTARTS or a NaN or negative max_step for the path form -- all before the chain is touched. */
+int optik_hip_select_from_keys(optik_hip_chain *chain, const double *d_key, const double *d_x, const double *d_f,
+                               int32_t T, uint64_t restart_begin, uint64_t R, const optik_hip_ik_outputs *out,
+                               void *stream);
+int optik_hip_solutions_from_keys(optik_hip_chain *chain, double *d_key, const double *d_x, const double *d_f,
+                                  int32_t T, uint64_t restart_begin, uint64_t R, int32_t K, double min_dist,
+                                  const optik_hip_ik_solutions_outputs *out, void *stream);
+int optik_hip_path_select_from_keys(optik_hip_chain *chain, const double *d_key, const double *d_x, const double *d_f,
+                                    const double *d_seed, int32_t P, uint64_t restart_begin, uint64_t R,
+                                    double max_step, const optik_hip_ik_path_outputs *out, double *d_carry,
+                                    void *stream);
 
 /* Tuning options of the kernel layer (diagnostics: tests and tools; the defaults are what the product runs with).
  * Each option's default comes from the environment variable named with it, read ONCE when the library first needs

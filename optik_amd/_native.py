@@ -177,6 +177,12 @@ def lib():
                                          C.POINTER(IkSolutionsOutputs), vp]
     L.optik_hip_ik_path.argtypes = [vp, C.POINTER(SolverConfigC), vp, vp, C.c_int32, C.c_int32, dp, C.c_uint64,
                                     C.c_uint64, C.c_uint32, C.c_double, C.c_double, C.POINTER(IkPathOutputs), vp]
+    # test hooks: the selection stages on the caller's own keys (include/optik_hip.h)
+    L.optik_hip_select_from_keys.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(IkOutputs), vp]
+    L.optik_hip_solutions_from_keys.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32,
+                                                C.c_double, C.POINTER(IkSolutionsOutputs), vp]
+    L.optik_hip_path_select_from_keys.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_double,
+                                                  C.POINTER(IkPathOutputs), vp, vp]
     L.optik_hip_ik_host.argtypes = [vp, C.POINTER(SolverConfigC), dp, dp, C.c_int32, dp,
                                     C.c_uint64, C.c_uint64, C.c_uint32, C.c_double, dp, dp,
                                     C.POINTER(C.c_uint64), dp]

@@ -385,6 +385,106 @@ static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, con
     return 0;
 }
 
+// The per-restart arrays a selection stage reads: key [cols], x [n][cols], f [cols] with cols = T * R, column
+// t * R + (i - restart_begin).  A solver launch's (SolvedLaunch), or a caller's own (the optik_hip_*_from_keys hooks).
+struct SelectionIn {
+    double *key;
+    const double *x, *f;
+    uint64_t restart_begin, R;
+    uint64_t tiles_per_target;  // of plan_selection_tiles
+    size_t cols;
+};
+
+static SelectionIn selection_in(const SolvedLaunch &sl, uint64_t restart_begin) {
+    return SelectionIn{sl.pk, sl.px, sl.pf, restart_begin, sl.R, sl.tiles_per_target, sl.cols};
+}
+
+// The launch structs of the three selection stages, filled in one place each: the product's entry points and the test
+// hooks below both launch what these return.  reset_queue / reset_fs: the work-item counter and first-success words
+// the stage's last kernel puts back (null: none).
+static SelectLaunch make_select_launch(optik_hip_chain *ch, const SelectionIn &in, const optik_hip_ik_outputs *out,
+                                       unsigned long long *reset_queue, unsigned long long *reset_fs) {
+    SelectLaunch s;
+    std::memset(&s, 0, sizeof s);
+    s.out_key = in.key; s.out_x = in.x; s.out_f = in.f;
+    s.tile_recs = ch->tile_recs.get();
+    s.tiles_per_target = (int)in.tiles_per_target;
+    s.tile = SEL_TILE;
+    s.n = ch->n;
+    s.restart_begin = in.restart_begin;
+    s.n_restarts = in.R;
+    s.ld = in.cols;
+    s.win_x = out->d_win_x; s.win_f = out->d_win_f;
+    s.win_idx = (unsigned long long *)out->d_win_idx; s.win_key = out->d_win_key;
+    s.reset_queue = reset_queue;
+    s.reset_fs = reset_fs;
+    return s;
+}
+
+static SolutionsLaunch make_solutions_launch(optik_hip_chain *ch, const SelectionIn &in, int32_t K, double min_dist,
+                                             const optik_hip_ik_solutions_outputs *out,
+                                             unsigned long long *reset_queue) {
+    SolutionsLaunch s;
+    std::memset(&s, 0, sizeof s);
+    s.out_key = in.key; s.out_x = in.x; s.out_f = in.f;
+    s.tile_recs = ch->tile_recs.get();
+    s.pick = ch->sol_pick.get();
+    s.tiles_per_target = (int)in.tiles_per_target;
+    s.tile = SEL_TILE;
+    s.n = ch->n;
+    s.K = K;
+    s.min_dist = min_dist;
+    s.restart_begin = in.restart_begin;
+    s.n_restarts = in.R;
+    s.ld = in.cols;
+    s.count = out->d_count; s.x = out->d_x; s.f = out->d_f;
+    s.idx = (unsigned long long *)out->d_idx; s.key = out->d_key;
+    s.reset_queue = reset_queue;
+    return s;
+}
+
+// One waypoint: `w` = its first slot in the [L][P] outputs, `last` = its seeds also go to out->d_last.
+static PathSelectLaunch make_path_select_launch(optik_hip_chain *ch, const SelectionIn &in, const double *seed,
+                                                double *carry, double max_step, const optik_hip_ik_path_outputs *out,
+                                                size_t w, bool last, unsigned long long *reset_queue,
+                                                unsigned long long *reset_fs) {
+    const size_t n = (size_t)ch->n;
+    PathSelectLaunch s;
+    std::memset(&s, 0, sizeof s);
+    s.out_key = in.key; s.out_x = in.x; s.out_f = in.f;
+    s.seed = seed;
+    s.carry = carry;
+    s.last = last ? out->d_last : nullptr;
+    s.n = ch->n;
+    s.filter = max_step < __builtin_huge_val() ? 1 : 0;
+    s.max_step = max_step;
+    s.restart_begin = in.restart_begin;
+    s.n_restarts = in.R;
+    s.ld = in.cols;
+    s.x = out->d_x ? out->d_x + w * n : nullptr;
+    s.f = out->d_f ? out->d_f + w : nullptr;
+    s.idx = out->d_idx ? (unsigned long long *)out->d_idx + w : nullptr;
+    s.key = out->d_key ? out->d_key + w : nullptr;
+    s.step = out->d_step ? out->d_step + w : nullptr;
+    s.reset_queue = reset_queue;
+    s.reset_fs = reset_fs;
+    return s;
+}
+
+// The argument rules optik_hip_ik_solutions and optik_hip_ik_path add to optik_hip_ik_batch's (0 or a fail() code).
+static int check_solutions_args(int32_t K, double min_dist) {
+    if (K < 1 || K > OPTIK_HIP_MAX_SOLUTIONS) return fail(OPTIK_HIP_EINVAL, "K must be in 1..256");
+    if (!(min_dist >= 0.0) || !std::isfinite(min_dist))
+        return fail(OPTIK_HIP_EINVAL, "min_dist must be finite and >= 0");
+    return 0;
+}
+static int check_path_args(uint64_t R, double max_step) {
+    if (R > (uint64_t)OPTIK_HIP_PATH_MAX_RESTARTS)
+        return fail(OPTIK_HIP_EINVAL, "ik_path: at most 4096 restarts per waypoint (one selection block per path)");
+    if (!(max_step >= 0.0)) return fail(OPTIK_HIP_EINVAL, "ik_path: max_step must be >= 0 (+inf: no limit)");
+    return 0;
+}
+
 // optik_hip_ik_batch with the chain's launch mutex already held.
 static int ik_batch_locked(optik_hip_chain *ch, const optik_solver_config *cfg, const double *d_targets,
                            const double *d_x0, int32_t T, const double *ee_offset7, uint64_t restart_begin,
@@ -401,20 +501,8 @@ static int ik_batch_locked(optik_hip_chain *ch, const optik_solver_config *cfg, 
         return rc;
     BIND_DEVICE(ch);
     if (want_win) {
-        SelectLaunch s;
-        std::memset(&s, 0, sizeof s);
-        s.out_key = sl.pk; s.out_x = sl.px; s.out_f = sl.pf;
-        s.tile_recs = ch->tile_recs.get();
-        s.tiles_per_target = (int)sl.tiles_per_target;
-        s.tile = SEL_TILE;
-        s.n = ch->n;
-        s.restart_begin = restart_begin;
-        s.n_restarts = sl.R;
-        s.ld = sl.cols;
-        s.win_x = out->d_win_x; s.win_f = out->d_win_f;
-        s.win_idx = (unsigned long long *)out->d_win_idx; s.win_key = out->d_win_key;
-        s.reset_queue = ch->queue;
-        s.reset_fs = sl.early ? ch->first_success.get() : nullptr;
+        const SelectLaunch s = make_select_launch(ch, selection_in(sl, restart_begin), out, ch->queue,
+                                                  sl.early ? ch->first_success.get() : nullptr);
         HIP_TRY(select_launch(s, T, stream));
         words_put_back(ch, sl, stream);
     }
@@ -438,9 +526,7 @@ int optik_hip_ik_solutions(optik_hip_chain *ch, const optik_solver_config *cfg, 
                            uint64_t restart_end, double deadline_s, int32_t K, double min_dist,
                            const optik_hip_ik_solutions_outputs *out, void *stream_v) {
     if (!ch || !out) return fail(OPTIK_HIP_EINVAL, "bad argument");
-    if (K < 1 || K > OPTIK_HIP_MAX_SOLUTIONS) return fail(OPTIK_HIP_EINVAL, "K must be in 1..256");
-    if (!(min_dist >= 0.0) || !std::isfinite(min_dist))
-        return fail(OPTIK_HIP_EINVAL, "min_dist must be finite and >= 0");
+    if (int rc = check_solutions_args(K, min_dist)) return rc;
     std::lock_guard<std::mutex> lock(ch->mu);
     hipStream_t stream = (hipStream_t)stream_v;
     // every restart runs to its end: no flags (no early exit, so the first-success words stay as they are)
@@ -452,22 +538,7 @@ int optik_hip_ik_solutions(optik_hip_chain *ch, const optik_solver_config *cfg, 
         return rc;
     BIND_DEVICE(ch);
     if (sl.tiles_per_target > 1) HIP_TRY(ch->sol_pick.reserve((size_t)T));  // (the multi-tile form's round-to-round acceptances)
-    SolutionsLaunch s;
-    std::memset(&s, 0, sizeof s);
-    s.out_key = sl.pk; s.out_x = sl.px; s.out_f = sl.pf;
-    s.tile_recs = ch->tile_recs.get();
-    s.pick = ch->sol_pick.get();
-    s.tiles_per_target = (int)sl.tiles_per_target;
-    s.tile = SEL_TILE;
-    s.n = ch->n;
-    s.K = K;
-    s.min_dist = min_dist;
-    s.restart_begin = restart_begin;
-    s.n_restarts = sl.R;
-    s.ld = sl.cols;
-    s.count = out->d_count; s.x = out->d_x; s.f = out->d_f;
-    s.idx = (unsigned long long *)out->d_idx; s.key = out->d_key;
-    s.reset_queue = ch->queue;
+    const SolutionsLaunch s = make_solutions_launch(ch, selection_in(sl, restart_begin), K, min_dist, out, ch->queue);
     HIP_TRY(solutions_launch(s, T, stream));
     words_put_back(ch, sl, stream);
     return 0;
@@ -479,11 +550,9 @@ int optik_hip_ik_path(optik_hip_chain *ch, const optik_solver_config *cfg, const
                       const optik_hip_ik_path_outputs *out, void *stream_v) {
     if (!ch || !cfg || !d_targets || !d_x0 || !out || P < 1 || L < 1) return fail(OPTIK_HIP_EINVAL, "bad argument");
     if (restart_end <= restart_begin) return fail(OPTIK_HIP_EINVAL, "empty restart range");
-    if (restart_end - restart_begin > (uint64_t)OPTIK_HIP_PATH_MAX_RESTARTS)
-        return fail(OPTIK_HIP_EINVAL, "ik_path: at most 4096 restarts per waypoint (one selection block per path)");
+    if (int rc = check_path_args(restart_end - restart_begin, max_step)) return rc;
     if (flags & ~(uint32_t)OPTIK_HIP_IK_RESTART_MAJOR)
         return fail(OPTIK_HIP_EINVAL, "ik_path: flags may only hold OPTIK_HIP_IK_RESTART_MAJOR");
-    if (!(max_step >= 0.0)) return fail(OPTIK_HIP_EINVAL, "ik_path: max_step must be >= 0 (+inf: no limit)");
     std::lock_guard<std::mutex> lock(ch->mu);
     hipStream_t stream = (hipStream_t)stream_v;
     const int n = ch->n;
@@ -516,29 +585,85 @@ int optik_hip_ik_path(optik_hip_chain *ch, const optik_solver_config *cfg, const
             if (int rc = motion_key_launch(ch, ee_offset7, seed, sl.px, sl.pk, P, (size_t)sl.R, filter ? 1 : 0, max_step,
                                            stream))
                 return rc;
-        const size_t w = (size_t)l * (size_t)P;
-        PathSelectLaunch s;
-        std::memset(&s, 0, sizeof s);
-        s.out_key = sl.pk; s.out_x = sl.px; s.out_f = sl.pf;
-        s.seed = seed;
-        s.carry = ch->path_carry.get();
-        s.last = l + 1 == L ? out->d_last : nullptr;
-        s.n = n;
-        s.filter = filter ? 1 : 0;
-        s.max_step = max_step;
-        s.restart_begin = restart_begin;
-        s.n_restarts = sl.R;
-        s.ld = sl.cols;
-        s.x = out->d_x ? out->d_x + w * (size_t)n : nullptr;
-        s.f = out->d_f ? out->d_f + w : nullptr;
-        s.idx = out->d_idx ? (unsigned long long *)out->d_idx + w : nullptr;
-        s.key = out->d_key ? out->d_key + w : nullptr;
-        s.step = out->d_step ? out->d_step + w : nullptr;
-        s.reset_queue = ch->queue;
-        s.reset_fs = sl.early ? ch->first_success.get() : nullptr;
+        const PathSelectLaunch s =
+            make_path_select_launch(ch, selection_in(sl, restart_begin), seed, ch->path_carry.get(), max_step, out,
+                                    (size_t)l * (size_t)P, l + 1 == L, ch->queue,
+                                    sl.early ? ch->first_success.get() : nullptr);
         HIP_TRY(path_select_launch(s, P, stream));
         words_put_back(ch, sl, stream);
     }
+    return 0;
+}
+
+/* Test hooks: the three selection stages on the caller's own keys, x and f, with no solve in front (optik_hip.h).
+ * Each fills its launch struct where the product does (make_*_launch) and plans its tiles with plan_selection_tiles;
+ * the work-item counter, the first-success words and what the chain knows of them (queue_clean, fs_clean) stay as they
+ * are. */
+// The rules the three share, checked before the chain is touched; the plan's tiles_per_target, n_tiles and cols.
+static int from_keys_plan(const optik_hip_chain *ch, const void *d_key, const void *out, int32_t T,
+                          uint64_t restart_begin, uint64_t R, LaunchPlan *plan) {
+    if (!d_key || !out || T < 1) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    // (the indices restart_begin .. restart_begin + R - 1 stay below ~0, "none")
+    if (R < 1 || R > UINT64_MAX - restart_begin) return fail(OPTIK_HIP_EINVAL, "empty restart range");
+    if (plan_selection_tiles(T, R, *plan) != PLAN_OK)
+        return fail(OPTIK_HIP_EINVAL, "too many restarts / targets in one launch (2^24 or more selection tiles)");
+    if (!ch) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    return 0;
+}
+// The selection workspace, as solve_locked reserves it (launch mutex held, device bound).
+static int from_keys_workspace(optik_hip_chain *ch, const LaunchPlan &plan, hipStream_t stream) {
+    if (ch->claim_pending && stream != nullptr) { HIP_TRY(hipStreamSynchronize(nullptr)); ch->claim_pending = false; }
+    HIP_TRY(ch->tile_recs.reserve((size_t)plan.n_tiles));
+    return 0;
+}
+
+int optik_hip_select_from_keys(optik_hip_chain *ch, const double *d_key, const double *d_x, const double *d_f,
+                               int32_t T, uint64_t restart_begin, uint64_t R, const optik_hip_ik_outputs *out,
+                               void *stream_v) {
+    LaunchPlan plan{};
+    if (int rc = from_keys_plan(ch, d_key, out, T, restart_begin, R, &plan)) return rc;
+    if ((out->d_win_x && !d_x) || (out->d_win_f && !d_f)) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    std::lock_guard<std::mutex> lock(ch->mu);
+    hipStream_t stream = (hipStream_t)stream_v;
+    BIND_DEVICE(ch);
+    if (int rc = from_keys_workspace(ch, plan, stream)) return rc;
+    const SelectionIn in{const_cast<double *>(d_key), d_x, d_f, restart_begin, R, plan.tiles_per_target, (size_t)plan.cols};
+    HIP_TRY(select_launch(make_select_launch(ch, in, out, nullptr, nullptr), T, stream));
+    return 0;
+}
+
+int optik_hip_solutions_from_keys(optik_hip_chain *ch, double *d_key, const double *d_x, const double *d_f, int32_t T,
+                                  uint64_t restart_begin, uint64_t R, int32_t K, double min_dist,
+                                  const optik_hip_ik_solutions_outputs *out, void *stream_v) {
+    if (int rc = check_solutions_args(K, min_dist)) return rc;
+    LaunchPlan plan{};
+    if (int rc = from_keys_plan(ch, d_key, out, T, restart_begin, R, &plan)) return rc;
+    if (!d_x || (out->d_f && !d_f)) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    std::lock_guard<std::mutex> lock(ch->mu);
+    hipStream_t stream = (hipStream_t)stream_v;
+    BIND_DEVICE(ch);
+    if (int rc = from_keys_workspace(ch, plan, stream)) return rc;
+    if (plan.tiles_per_target > 1) HIP_TRY(ch->sol_pick.reserve((size_t)T));
+    const SelectionIn in{d_key, d_x, d_f, restart_begin, R, plan.tiles_per_target, (size_t)plan.cols};
+    HIP_TRY(solutions_launch(make_solutions_launch(ch, in, K, min_dist, out, nullptr), T, stream));
+    return 0;
+}
+
+int optik_hip_path_select_from_keys(optik_hip_chain *ch, const double *d_key, const double *d_x, const double *d_f,
+                                    const double *d_seed, int32_t P, uint64_t restart_begin, uint64_t R,
+                                    double max_step, const optik_hip_ik_path_outputs *out, double *d_carry,
+                                    void *stream_v) {
+    if (int rc = check_path_args(R, max_step)) return rc;
+    LaunchPlan plan{};
+    if (int rc = from_keys_plan(ch, d_key, out, P, restart_begin, R, &plan)) return rc;
+    if (!d_x || !d_seed || !d_carry) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    std::lock_guard<std::mutex> lock(ch->mu);
+    hipStream_t stream = (hipStream_t)stream_v;
+    BIND_DEVICE(ch);
+    if (int rc = from_keys_workspace(ch, plan, stream)) return rc;
+    const SelectionIn in{const_cast<double *>(d_key), d_x, d_f, restart_begin, R, plan.tiles_per_target, (size_t)plan.cols};
+    HIP_TRY(path_select_launch(make_path_select_launch(ch, in, d_seed, d_carry, max_step, out, 0, true, nullptr, nullptr),
+                               P, stream));
     return 0;
 }
 

@@ -59,15 +59,26 @@ struct LaunchPlan {
     uint64_t cols;       // T * R
 };
 
+// The selection tiles of T targets with R restarts each: 4096 restarts per 256-thread block.  Fills tiles_per_target,
+// n_tiles and cols of `p`; PLAN_TOO_MANY_TILES (nothing filled) for 2^24 tiles or more.  What plan_launch plans with,
+// and all that the selection stage on its own (the optik_hip_*_from_keys test hooks) needs of a plan.
+inline PlanError plan_selection_tiles(int32_t T, uint64_t R, LaunchPlan &p) {
+    // (R beyond 2^36 is 2^24 tiles for one target already: refused before the sums below can wrap)
+    if (R > (1ull << 36)) return PLAN_TOO_MANY_TILES;
+    const uint64_t tiles_per_target = (R + SEL_TILE - 1) / SEL_TILE;
+    const uint64_t n_tiles64 = tiles_per_target * (uint64_t)T;
+    // (HIP rejects a launch whose grid.x * block.x reaches 2^32: 256-thread tile blocks cap the tiles at 2^24 - 1)
+    if (n_tiles64 * 256ull >= (1ull << 32)) return PLAN_TOO_MANY_TILES;
+    p.tiles_per_target = tiles_per_target;
+    p.n_tiles = (int)n_tiles64;
+    p.cols = (uint64_t)T * R;
+    return PLAN_OK;
+}
+
 inline LaunchPlan plan_launch(const PlanIn &in) {
     LaunchPlan p{};
-    // selection tiles: 4096 restarts per 256-thread block
-    p.tiles_per_target = (in.R + SEL_TILE - 1) / SEL_TILE;
-    const uint64_t n_tiles64 = p.tiles_per_target * (uint64_t)in.T;
-    // (HIP rejects a launch whose grid.x * block.x reaches 2^32: 256-thread tile blocks cap the tiles at 2^24 - 1)
-    if (n_tiles64 * 256ull >= (1ull << 32)) { p.error = PLAN_TOO_MANY_TILES; return p; }
-    p.n_tiles = (int)n_tiles64;
-    p.cols = (uint64_t)in.T * in.R;
+    p.error = plan_selection_tiles(in.T, in.R, p);
+    if (p.error != PLAN_OK) return p;
     const long long cols = (long long)p.cols, T = in.T;
 
     p.early = (in.flags & PLAN_EARLY_EXIT) && in.mode == PLAN_MODE_SPEED && !in.coll;

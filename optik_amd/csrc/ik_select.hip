@@ -54,9 +54,9 @@ __global__ __launch_bounds__(256) void ik_tile_argmin_kernel(const SelectLaunch 
 // The winner of target t goes out (one thread), and the launch's queue / first-success words go back to their
 // initial values for the next launch.
 __device__ void select_publish(const SelectLaunch &a, int t, double key, unsigned long long idx) {
-    if (a.win_idx) a.win_idx[t] = idx;
-    if (a.win_key) a.win_key[t] = key;
     const bool found = idx != ~0ull;
+    if (a.win_idx) a.win_idx[t] = idx;
+    if (a.win_key) a.win_key[t] = found ? key : __builtin_huge_val();  // (none: +inf, as ik_path.hip and ik_solutions.hip)
     const size_t col = (size_t)t * a.n_restarts + (found ? (size_t)(idx - a.restart_begin) : 0);
     if (a.win_f) a.win_f[t] = (found && a.out_f) ? a.out_f[col] : __builtin_nan("");
     if (a.win_x) {

@@ -23,7 +23,7 @@ from avoid_util import Scene, build_avoid, make_test_world
 from collision_util import build_measure as build_collision_measure
 from collision_util import small_scene
 from conftest import ROBOT_SPECS
-from gpu_util import assert_bit_equal
+from gpu_util import _out, _sentinels_left, assert_bit_equal
 from grid_util import build_grid_measure
 from manip_util import build_measure as build_manip_measure
 from motion_util import build_motion
@@ -39,7 +39,6 @@ CAPS = [1, 3]
 B = 805            # 3 * 256 + 37
 SIZES = [(B, CAPS), (37, [1])]  # (rows, caps): 37 rows under cap 1 are a single partial trip
 EE7 = np.array([0.01, -0.02, 0.05, 0.0, 0.0, math.sin(0.15), math.cos(0.15)])
-F64_SENTINEL, F32_SENTINEL, BYTE_SENTINEL = 0x7FF8000000005E17, 0x7FC05E17, 0x7F
 ROW_CHAINS = ["panda", "ur10", "panda1", "arm8", "arm10"]
 F64, F32, I32, I64, U8 = torch.float64, torch.float32, torch.int32, torch.int64, torch.uint8
 
@@ -59,26 +58,6 @@ def _dp(a):
 
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _out(shape, dtype):
-    t = torch.empty(shape, dtype=dtype, device="cuda")
-    if dtype == F64:
-        t.view(I64).fill_(F64_SENTINEL)
-    elif dtype == F32:
-        t.view(I32).fill_(F32_SENTINEL)
-    else:
-        t.view(U8).fill_(BYTE_SENTINEL)
-    return t
-
-
-def _sentinels_left(a):
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.float64:
-        return int((a.view(np.uint64) == F64_SENTINEL).sum())
-    if a.dtype == np.float32:
-        return int((a.view(np.uint32) == F32_SENTINEL).sum())
-    return int((a.view(np.uint8).reshape(a.shape + (a.itemsize,)) == BYTE_SENTINEL).all(axis=-1).sum())
 
 
 def _launch(cap, spec, call, what):
