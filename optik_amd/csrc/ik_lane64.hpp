@@ -103,6 +103,20 @@ constexpr int LANE64_CLASSES = OPTIK_LANE_CLASSES;  // predicted pass classes 1 
                                   // (with the reserve, round 5: 2 / 3 / 4 / 6 idle lanes 32.86 / 32.84 / 32.82 / 32.56 M: profiles/r5m_ab_refill_threshold.txt)
 #endif
 
+// load_pose (ik_eval.hpp) of a pose in global memory
+OPTIK_DEV Pose load_pose_global(const double *pose) {
+    const auto p = global_ptr(pose);
+    Pose o;
+    o.t = V3{p[0], p[1], p[2]};
+    o.q = Q4{p[3], p[4], p[5], p[6]};
+    return o;
+}
+
+#ifdef OPTIK_DEVICE_PROFILE
+// -DOPTIK_PROFILE: wave cycles of the refill by its parts, summed over all waves (lane64_wave: LANE_PROF_REFILL)
+__device__ unsigned long long g_lane_refill_prof[4];
+#endif
+
 // The wave's problems in rank order through its sixteen quads (ik_nnls_quad.hpp: Pipe): what lane64_wave hands to the
 // NNLS -- the answers of finished quads back to their owner lanes, the next problems into the idle quads.
 template <int N, class Expand, class ReadBack>
@@ -201,8 +215,25 @@ OPTIK_DEV void lane64_wave(const ChainDev &ch, const EvalParams &ep, const Solve
     unsigned long long lp_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long lt_ = __builtin_readcyclecounter();
 #define LANE_PROF(slot) do { const unsigned long long n_ = __builtin_readcyclecounter(); lp_[slot] += n_ - lt_; lt_ = n_; } while (0)
+    // (... and the refill by its parts, g_lane_refill_prof: 0 item hand-out + index arithmetic, 1 target load, 2 seed
+    // generation, 3 state reset + reserve atomic + the loop's exit test; each also counts into slot 0.  A time stamp
+    // taken inside a divergent branch would be a per-lane value: LANE_PROF_REFILL_SPLIT closes the two branches the
+    // lanes with a new item are in, takes the stamp with the wave converged and opens one branch for the same lanes
+    // again -- the product build, where the three macros are empty, keeps its one block)
+    unsigned long long lr_[4] = {0, 0, 0, 0};
+#define LANE_PROF_REFILL(part) do { const unsigned long long n_ = __builtin_readcyclecounter(); lp_[0] += n_ - lt_; lr_[part] += n_ - lt_; lt_ = n_; } while (0)
+#define LANE_PROF_REFILL_GOT(cond) const bool got_ = (cond)
+#ifdef OPTIK_PROFILE_TARGET_WAIT
+    // (the target load's latency in the load's own part instead of wherever the pose is first used)
+#define LANE_PROF_REFILL_SPLIT(part) } } if ((part) == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); LANE_PROF_REFILL(part); if (got_) { {
+#else
+#define LANE_PROF_REFILL_SPLIT(part) } } LANE_PROF_REFILL(part); if (got_) { {
+#endif
 #else
 #define LANE_PROF(slot)
+#define LANE_PROF_REFILL(part)
+#define LANE_PROF_REFILL_GOT(cond)
+#define LANE_PROF_REFILL_SPLIT(part)
 #endif
     for (;;) {
         // ---- refill: lanes without a restart pull the next work item ----------------------------------
@@ -231,30 +262,34 @@ OPTIK_DEV void lane64_wave(const ChainDev &ch, const EvalParams &ep, const Solve
 #else
             const unsigned long long it = fetch_items(wq.next_item, want);
 #endif
+#if OPTIK_LANE_KEEP_TARGET
+            const unsigned tprev = tslot;
+#endif
+            LANE_PROF_REFILL_GOT(want && it < wq.total_items);
             if (want) {
                 want = false;
                 if (it < wq.total_items) {
                     unsigned long long r;
-#if OPTIK_LANE_KEEP_TARGET
-                    const unsigned tprev = tslot;
-#endif
                     if (wq.restart_major) { r = it / wq.n_targets; tslot = (unsigned)(it - r * wq.n_targets); }
                     else { tslot = (unsigned)(it / wq.n_restarts); r = it - (unsigned long long)tslot * wq.n_restarts; }
                     item = (unsigned long long)tslot * wq.n_restarts + r;  // output column
                     index = wq.restart_begin + r;
+                    LANE_PROF_REFILL_SPLIT(0);
 #if OPTIK_LANE_KEEP_TARGET
                     // (a target-major launch: nearly every lane's next restart has the target of its last one)
-                    if (tslot != tprev) target = load_pose(wq.targets + (size_t)tslot * 7);
+                    if (tslot != tprev) target = load_pose_global(wq.targets + (size_t)tslot * 7);
 #else
-                    target = load_pose(wq.targets + (size_t)tslot * 7);
+                    target = load_pose_global(wq.targets + (size_t)tslot * 7);
 #endif
+                    LANE_PROF_REFILL_SPLIT(1);
                     // lib.rs:366-370: restart 0 starts from the caller's seed
                     restart_seed<N>(key, ch.lb, scale, index, x);
                     if (index == 0) {
-                        const double *x0p = wq.x0 + (size_t)tslot * N;
+                        const auto x0p = global_ptr(wq.x0) + (size_t)tslot * N;
 #pragma unroll
                         for (int i = 0; i < N; ++i) x[i] = x0p[i];
                     }
+                    LANE_PROF_REFILL_SPLIT(2);
 #pragma unroll
                     for (int i = 0; i < N; ++i) { xbest[i] = x[i]; xprev[i] = x[i]; x0[i] = x[i]; s[i] = 0.0; g[i] = 0.0; }
                     f = 0.0; f0 = 0.0; t0 = 0.0; h3 = 0.0; alpha = 1.0;
@@ -269,19 +304,19 @@ OPTIK_DEV void lane64_wave(const ChainDev &ch, const EvalParams &ep, const Solve
 #if OPTIK_LANE_RESERVE > 0
         // (the next refill's items are asked for NOW -- a trip or more before they are handed out)
         if (!r_pending && rbase == rend && !dry) {
-            if (lane == 0) pend = atomicAdd(wq.next_item, (unsigned long long)OPTIK_LANE_RESERVE);
+            if (lane == 0) pend = global_atomic_add(global_ptr(wq.next_item), (unsigned long long)OPTIK_LANE_RESERVE);
             r_pending = true;
         }
 #endif
         if (!wave_any(active)) break;
-        LANE_PROF(0);
+        LANE_PROF_REFILL(3);
 
         int32_t ret = 0;
         if (active) {
             // lib.rs:308: abandon when timed out or a lower-index restart succeeded
             bool stop = false;
             if (wq.first_success) {
-                const unsigned long long fs = __hip_atomic_load(wq.first_success + tslot, __ATOMIC_RELAXED,
+                const unsigned long long fs = __hip_atomic_load(global_ptr(wq.first_success) + tslot, __ATOMIC_RELAXED,
                                                                 __HIP_MEMORY_SCOPE_AGENT);
                 stop = wq.find_any ? (fs != ~0ull) : (fs < index);
             }
@@ -667,26 +702,26 @@ OPTIK_DEV void lane64_wave(const ChainDev &ch, const EvalParams &ep, const Solve
                                  || (sp.ok_xtol && ret == RES_XTOL_REACHED);
             if (wq.out_x) {
 #pragma unroll
-                for (int i = 0; i < N; ++i) wq.out_x[(size_t)i * wq.total_items + item] = xbest[i];
+                for (int i = 0; i < N; ++i) global_ptr(wq.out_x)[(size_t)i * wq.total_items + item] = xbest[i];
             }
-            if (wq.out_f) wq.out_f[item] = minf;
-            if (wq.out_status) wq.out_status[item] = ret;
-            if (wq.out_evals) wq.out_evals[item] = nevals;
+            if (wq.out_f) global_ptr(wq.out_f)[item] = minf;
+            if (wq.out_status) global_ptr(wq.out_status)[item] = ret;
+            if (wq.out_evals) global_ptr(wq.out_evals)[item] = nevals;
             // selection key (lib.rs:402-407): Quality = ||x - x0||_2, Speed = index
             double k = __builtin_huge_val();
             if (success) {
                 if (wq.quality) {
-                    const double *x0p = wq.x0 + (size_t)tslot * N;
+                    const auto x0p = global_ptr(wq.x0) + (size_t)tslot * N;
                     double acc = 0.0;
 #pragma unroll
                     for (int i = 0; i < N; ++i) { const double d = xbest[i] - x0p[i]; acc += d * d; }
                     k = __builtin_sqrt(acc);
                 } else {
                     k = (double)index;
-                    if (wq.first_success) atomicMin(wq.first_success + tslot, index);
+                    if (wq.first_success) global_atomic_min(global_ptr(wq.first_success) + tslot, index);
                 }
             }
-            if (wq.out_key) wq.out_key[item] = k;
+            if (wq.out_key) global_ptr(wq.out_key)[item] = k;
             active = false;
             want = true;
             again = false;
@@ -699,8 +734,15 @@ OPTIK_DEV void lane64_wave(const ChainDev &ch, const EvalParams &ep, const Solve
 #ifdef OPTIK_PROFILE
     if (wq.prof && (threadIdx.x & 63u) == 0)
         for (int i_ = 0; i_ < 8; ++i_) atomicAdd(wq.prof + i_, lp_[i_]);
+#ifdef OPTIK_DEVICE_PROFILE
+    if ((threadIdx.x & 63u) == 0)
+        for (int i_ = 0; i_ < 4; ++i_) atomicAdd(&g_lane_refill_prof[i_], lr_[i_]);
+#endif
 #endif
 #undef LANE_PROF
+#undef LANE_PROF_REFILL
+#undef LANE_PROF_REFILL_GOT
+#undef LANE_PROF_REFILL_SPLIT
 }
 
 }  // namespace optik

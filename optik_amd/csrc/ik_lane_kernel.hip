@@ -75,4 +75,11 @@ extern "C" int optik_hip_lane_nnls_cycles(unsigned long long *out26) {
     (void)hipMemcpyToSymbol(HIP_SYMBOL(optik::g_quad_nnls_prof), z, 8 * sizeof(unsigned long long));
     return hipMemcpyToSymbol(HIP_SYMBOL(optik::g_quad_nnls_tripcyc), z, sizeof z) == hipSuccess ? 0 : -1;
 }
+// ... and the refill's cycles by its parts (ik_lane64.hpp: g_lane_refill_prof), then reset
+extern "C" int optik_hip_lane_refill_split(unsigned long long *out4) {
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(out4, HIP_SYMBOL(optik::g_lane_refill_prof), 4 * sizeof(unsigned long long)) != hipSuccess) return -1;
+    unsigned long long z[4] = {0};
+    return hipMemcpyToSymbol(HIP_SYMBOL(optik::g_lane_refill_prof), z, sizeof z) == hipSuccess ? 0 : -1;
+}
 #endif

@@ -53,4 +53,27 @@ __device__ __forceinline__ const T *launder_lds(const T *p) {
 #endif
 }
 
+// A pointer to GLOBAL memory that the compiler cannot see to be one (it was read from a structure in LDS, say), told so:
+// the accesses through it become global_* instead of flat_* instructions.  A flat access counts on the LDS wait counter
+// as well as on the vector-memory one, so the next wait for ANY LDS result also waits for its round trip to memory; a
+// global access leaves the LDS counter alone and its latency can hide behind the work that follows.  (The pointer
+// keeps its address space in its type: cast back to a generic one it is a flat pointer again.)
+#ifdef OPTIK_LANE_EMU
+template <class T>
+__device__ __forceinline__ T *global_ptr(T *p) { return p; }
+__device__ __forceinline__ unsigned long long global_atomic_add(unsigned long long *p, unsigned long long v) { return atomicAdd(p, v); }
+__device__ __forceinline__ unsigned long long global_atomic_min(unsigned long long *p, unsigned long long v) { return atomicMin(p, v); }
+#else
+#define OPTIK_GLOBAL_AS __attribute__((address_space(1)))
+template <class T>
+__device__ __forceinline__ OPTIK_GLOBAL_AS T *global_ptr(T *p) { return (OPTIK_GLOBAL_AS T *)p; }
+// (atomicAdd / atomicMin of the HIP headers on such a pointer: relaxed, device scope)
+__device__ __forceinline__ unsigned long long global_atomic_add(OPTIK_GLOBAL_AS unsigned long long *p, unsigned long long v) {
+    return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ unsigned long long global_atomic_min(OPTIK_GLOBAL_AS unsigned long long *p, unsigned long long v) {
+    return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+#endif
+
 }  // namespace optik
