@@ -277,6 +277,27 @@ int64_t optik_robot_roadmap_build(optik_robot *robot, int32_t N, int32_t k, doub
 int optik_robot_roadmap_plan(const optik_robot *robot, const double *starts, const double *goals, int64_t Q,
                              int32_t Lmax, double *paths_out, int32_t *len_out, double *cost_out,
                              int32_t *status_out);
+/* Lazy roadmaps (extension; include/optik_hip.h: optik_hip_roadmap_lazy_plan): a roadmap
+ * that follows a changing world.  Its nodes and neighbour lists survive every optik_robot_set_world* and
+ * optik_robot_set_collision_model call; its edges are presumed free and checked only when a shortest route uses them,
+ * and the verdicts are forgotten when the world changes.  A lazy roadmap is never stale.
+ * optik_robot_roadmap_build_lazy: the nodes of optik_robot_roadmap_build (the same seeds) and their k nearest others;
+ * nothing is checked but the nodes themselves.  Replaces the robot's roadmap, eager or lazy.  Returns the number of
+ * slots that are not blocked (neither empty nor touching a node in collision), or -1.
+ * optik_robot_roadmap_plan_lazy: optik_robot_roadmap_plan's arguments and outputs, and `rounds` in 0 .. 4096: at most
+ * that many rounds of checking the unknown edges of the current routes.  With enough rounds every plan of status 0,
+ * 1 or 3 equals optik_robot_roadmap_plan over an eager roadmap of the same N, k, resolution, first and world, bit
+ * for bit.  Status 4: unsettled -- the route found last still holds an unchecked edge; len 2, the start, then the
+ * goal repeated, the cost a lower bound (as is the cost of status 2 here).  If the world changed since the last
+ * plan, the verdicts are reset first.  Queries run in chunks of 4 096 against the shared verdicts;
+ * *rounds_used_out and *checked_out (may be NULL) are the rounds made and the edges checked, added up over the
+ * chunks.  Concurrent callers are serialised.  rc 0, or -1.
+ * optik_robot_roadmap_plan on a lazy roadmap and optik_robot_roadmap_plan_lazy on an eager one fail, each naming the
+ * other. */
+int64_t optik_robot_roadmap_build_lazy(optik_robot *robot, int32_t N, int32_t k, double resolution, uint64_t first);
+int optik_robot_roadmap_plan_lazy(const optik_robot *robot, const double *starts, const double *goals, int64_t Q,
+                                  int32_t Lmax, int32_t rounds, double *paths_out, int32_t *len_out, double *cost_out,
+                                  int32_t *status_out, int32_t *rounds_used_out, int64_t *checked_out);
 /* Shortcutting and resampling planned paths (extension; include/optik_hip.h: optik_hip_path_shortcut and
  * optik_hip_path_resample).  paths [P][L][n] row-major with lens [P] waypoints each (NULL: L
  * each), 2 <= L <= 64 -- optik_robot_roadmap_plan's paths_out and len_out as they are.

@@ -251,6 +251,79 @@ int optik_hip_roadmap_query(const optik_hip_chain *chain, const double *d_nodes,
                             const double *d_gw, int32_t kg, const double *d_direct, int32_t Lmax, double *d_path,
                             int32_t *d_len, double *d_cost, int32_t *d_status, void *stream);
 
+/* Lazy roadmaps (extension; the rules: csrc/roadmap_lazy_measure.hpp): Lazy PRM.  The nodes
+ * and the neighbour lists of a roadmap depend on the joint limits alone, so they survive every change of the world.
+ * The edges are presumed free and checked -- by optik_hip_collision_motion_batch's own code, in the direction v ->
+ * d_nbr[s][v] -- only when a shortest route uses them; a verdict holds until the next reset.  The state, all [k][N]
+ * and caller-owned: the unchecked weights d_w0 (the motion's length; +inf for an empty slot or a length that is NaN
+ * or infinite), the int32 verdicts d_verdict (OPTIK_HIP_ROADMAP_UNKNOWN / _FREE / _BLOCKED) and the working weights
+ * d_w = d_w0 with +inf at the blocked slots: the graph optik_hip_roadmap_query sees.
+ *
+ * optik_hip_roadmap_query_route: optik_hip_roadmap_query with two more outputs [Lmax][Q] int32 (either may be NULL;
+ * both NULL: optik_hip_roadmap_query itself): d_route, the node of waypoint t for 1 <= t < len - 1 and -1 elsewhere;
+ * d_hop, the slot s of the graph hop that leaves waypoint t -- the LOWEST s with d_nbr[s][v] == u and d_w[s][v] +
+ * d[u] == d[v] --, -1 for the route's last node (it leaves by its goal link) and elsewhere.
+ *
+ * optik_hip_roadmap_lazy_reset: lengths != 0 first writes d_w0 from d_nodes and d_nbr (otherwise d_w0 is read as it
+ * is).  d_node_free [N] uint8 NULL: the nodes are classified by optik_hip_collision_batch against the chain's model
+ * and world (clearance >= margin; every node is free without a model).  A slot is BLOCKED if it is empty, if d_w0 is
+ * +inf or if either of its nodes is not free -- exactly the edges that the motion check refuses for their end points
+ * alone --, every other slot UNKNOWN.  Stream-ordered, no host synchronisation.
+ *
+ * optik_hip_roadmap_lazy_plan: the query's arguments (links and direct weight checked by the caller, as for
+ * optik_hip_roadmap_query) and `rounds` in 0 .. OPTIK_HIP_ROADMAP_LAZY_MAX_ROUNDS.  A pass is
+ * optik_hip_roadmap_query_route for all Q queries on d_w.  C is the set of UNKNOWN hop slots over the FOUND routes of
+ * the pass, each slot once.  If C is empty, or after `rounds` checks, the call ends; otherwise the motions of C are
+ * checked at `resolution`, a free one makes its slot FREE, any other BLOCKED with d_w = +inf, and the next pass
+ * follows.  Outputs as optik_hip_roadmap_query (any may be NULL) with one more status:
+ *   4 unsettled: the last pass found a route that still holds an UNKNOWN slot.  len 2, the start, then the goal
+ *   repeated; the cost is that route's, a lower bound.
+ * Status 2 keeps its meaning; its route is not walked, so none of it is checked, and its cost is a lower bound too.
+ * For status 0, 1 and 3 the status, len, cost and path are those of optik_hip_roadmap_query over the eagerly checked
+ * graph (optik_hip_roadmap_edges on every slot), bit for bit.  *rounds_used (the checks made) and *checked (the sizes
+ * of the C sets added up) are host words, may be NULL; like every output they do not depend on the order in which
+ * the device claims slots.  rounds = 0 makes one pass and checks nothing.
+ * The loop runs on the host: it reads one int32, the size of C, per round -- one synchronise of `stream` per round,
+ * none once `rounds` checks are made.  The routes, the claimed slots and their segments are the chain's workspace,
+ * grown on demand: one call per chain handle at a time; calls that share d_w and d_verdict must not overlap.
+ *
+ * optik_hip_roadmap_lazy_plan_from_flags (a test hook, as optik_hip_select_from_keys): the same loop with d_edge_free
+ * [k][N] uint8 in place of the motion check; d_node_free [N] uint8 not NULL runs the reset from it first (d_w0 is
+ * read), NULL continues with d_w and d_verdict as they are.
+ *
+ * All four refuse what optik_hip_roadmap_query and optik_hip_roadmap_edges refuse, with the same codes, and rounds
+ * outside 0 .. 4096 with OPTIK_HIP_EINVAL, before any device work. */
+#define OPTIK_HIP_ROADMAP_UNKNOWN 0
+#define OPTIK_HIP_ROADMAP_FREE 1
+#define OPTIK_HIP_ROADMAP_BLOCKED 2
+#define OPTIK_HIP_ROADMAP_UNSETTLED 4
+#define OPTIK_HIP_ROADMAP_LAZY_MAX_ROUNDS 4096
+int optik_hip_roadmap_query_route(const optik_hip_chain *chain, const double *d_nodes, int32_t N, const int32_t *d_nbr,
+                                  const double *d_w, int32_t k, const double *d_start, const double *d_goal, int64_t Q,
+                                  const int32_t *d_sidx, const double *d_sw, int32_t ks, const int32_t *d_gidx,
+                                  const double *d_gw, int32_t kg, const double *d_direct, int32_t Lmax, double *d_path,
+                                  int32_t *d_len, double *d_cost, int32_t *d_status, int32_t *d_route, int32_t *d_hop,
+                                  void *stream);
+int optik_hip_roadmap_lazy_reset(optik_hip_chain *chain, const double *ee_offset7, const double *d_nodes, int32_t N,
+                                 const int32_t *d_nbr, int32_t k, int32_t lengths, double *d_w0,
+                                 const uint8_t *d_node_free, int32_t *d_verdict, double *d_w, void *stream);
+int optik_hip_roadmap_lazy_plan(optik_hip_chain *chain, const double *ee_offset7, const double *d_nodes, int32_t N,
+                                const int32_t *d_nbr, double *d_w, int32_t *d_verdict, int32_t k, double resolution,
+                                const double *d_start, const double *d_goal, int64_t Q, const int32_t *d_sidx,
+                                const double *d_sw, int32_t ks, const int32_t *d_gidx, const double *d_gw, int32_t kg,
+                                const double *d_direct, int32_t Lmax, int32_t rounds, double *d_path, int32_t *d_len,
+                                double *d_cost, int32_t *d_status, int32_t *rounds_used, int64_t *checked,
+                                void *stream);
+int optik_hip_roadmap_lazy_plan_from_flags(optik_hip_chain *chain, const double *d_nodes, int32_t N,
+                                           const int32_t *d_nbr, double *d_w0, double *d_w, int32_t *d_verdict,
+                                           int32_t k, const uint8_t *d_edge_free, const uint8_t *d_node_free,
+                                           const double *d_start, const double *d_goal, int64_t Q,
+                                           const int32_t *d_sidx, const double *d_sw, int32_t ks,
+                                           const int32_t *d_gidx, const double *d_gw, int32_t kg,
+                                           const double *d_direct, int32_t Lmax, int32_t rounds, double *d_path,
+                                           int32_t *d_len, double *d_cost, int32_t *d_status, int32_t *rounds_used,
+                                           int64_t *checked, void *stream);
+
 /* Path shortcutting and equal-spacing resampling (extension; the arithmetic and its operation
  * order: csrc/shortcut_measure.hpp).  Paths are d_path [Lin][P][n] -- the layout optik_hip_roadmap_query writes and
  * optik_hip_path_optimize reads --, path p having d_len[p] waypoints (d_len NULL: Lin each) and padding behind them

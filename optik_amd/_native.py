@@ -161,6 +161,13 @@ def lib():
                                           vp, vp]
     L.optik_hip_roadmap_query.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int64, vp, vp, C.c_int32,
                                           vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
+    L.optik_hip_roadmap_query_route.argtypes = L.optik_hip_roadmap_query.argtypes[:-1] + [vp, vp, vp]
+    L.optik_hip_roadmap_lazy_reset.argtypes = [vp, dp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
+    query_args = [vp, vp, C.c_int64, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, vp,
+                  C.POINTER(C.c_int32), C.POINTER(C.c_int64), vp]
+    L.optik_hip_roadmap_lazy_plan.argtypes = [vp, dp, vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_double] + query_args
+    L.optik_hip_roadmap_lazy_plan_from_flags.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, C.c_int32, vp,
+                                                         vp] + query_args
     L.optik_hip_path_shortcut.argtypes = [vp, dp, vp, vp, C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_double,
                                           C.c_int32, vp, vp, vp, vp, vp, vp]
     L.optik_hip_path_resample.argtypes = [vp, vp, vp, C.c_int32, C.c_int64, C.c_int32, vp, vp, vp]
@@ -280,6 +287,23 @@ ROADMAP_FOUND, ROADMAP_NO_ROUTE, ROADMAP_TOO_LONG, ROADMAP_NAN = 0, 1, 2, 3
 # The values with which Robot.build_roadmap / plan_paths plan the wall scene of examples/plan_path.py on a Panda: that
 # and nothing more.
 ROADMAP_NODES, ROADMAP_K, ROADMAP_RESOLUTION = 512, 8, 0.05
+# include/optik_hip.h: OPTIK_HIP_ROADMAP_UNKNOWN .. _BLOCKED, the verdicts of a lazy roadmap's slots; the one more
+# status of optik_hip_roadmap_lazy_plan; OPTIK_HIP_ROADMAP_LAZY_MAX_ROUNDS
+ROADMAP_SLOT_UNKNOWN, ROADMAP_SLOT_FREE, ROADMAP_SLOT_BLOCKED = 0, 1, 2
+ROADMAP_UNSETTLED = 4
+ROADMAP_LAZY_MAX_ROUNDS = 4096
+# Twice the larger number of rounds that the wall scene of the tests and the scene of examples/plan_lazy.py took on
+# a Panda, rounded up to a power of two (DESIGN.md section 5.24 has the two figures): that and nothing more.
+ROADMAP_LAZY_ROUNDS = 8
+
+
+def check_lazy_rounds(rounds):
+    """`rounds` of a lazy plan as an int: None is ROADMAP_LAZY_ROUNDS; an integer in 0 .. 4096."""
+    if rounds is None:
+        return ROADMAP_LAZY_ROUNDS
+    if isinstance(rounds, bool) or int(rounds) != rounds or not 0 <= int(rounds) <= ROADMAP_LAZY_MAX_ROUNDS:
+        raise ValueError(f"rounds must be an integer in 0 .. {ROADMAP_LAZY_MAX_ROUNDS}, got {rounds!r}")
+    return int(rounds)
 
 
 def check_roadmap_args(N=1, k=1, max_waypoints=2):

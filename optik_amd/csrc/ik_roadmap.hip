@@ -17,8 +17,11 @@
 //                                  coalesced over the nodes, no atomics.  Thread 0 then takes the first hop and walks
 //                                  the successors (at most 62 nodes), and the block writes the path.  Three sizes:
 //                                  CAP 1024 (16 KiB, 256 threads), 4096 (64 KiB, 512) and 8192 (128 KiB, 1024).
+//                                  For a lazy roadmap (optik_hip_roadmap_query_route; ik_roadmap_lazy.hip) thread 0
+//                                  also looks up the slot of every graph hop while d is still in LDS, and the block
+//                                  writes the walked node indices and those slots.
 #include "collision_device.hpp"
-#include "roadmap_measure.hpp"
+#include "roadmap_lazy_measure.hpp"
 
 using namespace optik;
 using namespace optik::host;
@@ -129,12 +132,13 @@ struct QueryLaunch {
     int32_t *len;          // [Q] or null
     double *cost;          // [Q] or null
     int32_t *status;       // [Q] or null
+    int32_t *route, *hop;  // [Lmax][Q] or null: waypoint t's node, and the slot of the graph hop that leaves it
 };
 
 template <int CAP, int THREADS>
 __global__ __launch_bounds__(THREADS) void roadmap_query_kernel(const QueryLaunch a) {
     __shared__ double s_d[2][CAP];
-    __shared__ int s_nodes[roadmap::MAX_WAYPOINTS];
+    __shared__ int s_nodes[roadmap::MAX_WAYPOINTS], s_hops[roadmap::MAX_WAYPOINTS];
     __shared__ roadmap::Plan s_plan;
     const long long qi = blockIdx.x;
     const int tid = threadIdx.x, N = a.y.N;
@@ -163,10 +167,20 @@ __global__ __launch_bounds__(THREADS) void roadmap_query_kernel(const QueryLaunc
         if (a.len) a.len[qi] = p.len;
         if (a.cost) a.cost[qi] = p.cost;
         if (a.status) a.status[qi] = p.status;
+        if (a.hop)
+            for (int t = 0; t < p.len - 2; ++t)
+                s_hops[t] = t + 1 < p.len - 2 ? roadmap::hop_slot(y, s_d[cur], s_nodes[t], s_nodes[t + 1]) : -1;
     }
     __syncthreads();
-    if (!a.path) return;
     const int len = s_plan.len;
+    // (waypoint t, 1 <= t < len - 1, is node s_nodes[t - 1]; only a FOUND plan has len > 2)
+    if (a.route || a.hop)
+        for (int t = tid; t < y.Lmax; t += THREADS) {
+            const bool node = t >= 1 && t < len - 1;
+            if (a.route) a.route[(long long)t * a.Q + qi] = node ? s_nodes[t - 1] : -1;
+            if (a.hop) a.hop[(long long)t * a.Q + qi] = node ? s_hops[t - 1] : -1;
+        }
+    if (!a.path) return;
     for (int e = tid; e < y.Lmax * a.n; e += THREADS) {
         const int t = e / a.n, i = e % a.n;
         double v = a.goal[(long long)i * a.Q + qi];
@@ -267,12 +281,23 @@ int optik_hip_roadmap_query(const optik_hip_chain *ch, const double *d_nodes, in
                             const int32_t *d_sidx, const double *d_sw, int32_t ks, const int32_t *d_gidx,
                             const double *d_gw, int32_t kg, const double *d_direct, int32_t Lmax, double *d_path,
                             int32_t *d_len, double *d_cost, int32_t *d_status, void *stream) {
+    return optik_hip_roadmap_query_route(ch, d_nodes, N, d_nbr, d_w, k, d_start, d_goal, Q, d_sidx, d_sw, ks, d_gidx,
+                                         d_gw, kg, d_direct, Lmax, d_path, d_len, d_cost, d_status, nullptr, nullptr,
+                                         stream);
+}
+
+int optik_hip_roadmap_query_route(const optik_hip_chain *ch, const double *d_nodes, int32_t N, const int32_t *d_nbr,
+                                  const double *d_w, int32_t k, const double *d_start, const double *d_goal, int64_t Q,
+                                  const int32_t *d_sidx, const double *d_sw, int32_t ks, const int32_t *d_gidx,
+                                  const double *d_gw, int32_t kg, const double *d_direct, int32_t Lmax, double *d_path,
+                                  int32_t *d_len, double *d_cost, int32_t *d_status, int32_t *d_route, int32_t *d_hop,
+                                  void *stream) {
     if (int rc = check_graph(ch, Q, N, k, "roadmap_query")) return rc;
     if (ks < 1 || ks > roadmap::K_MAX || kg < 1 || kg > roadmap::K_MAX)
         return fail(OPTIK_HIP_EINVAL, "roadmap_query: ks and kg must be in 1 .. " + std::to_string(roadmap::K_MAX));
     if (Lmax < roadmap::MIN_WAYPOINTS || Lmax > roadmap::MAX_WAYPOINTS)
         return fail(OPTIK_HIP_EINVAL, "roadmap_query: a path has 2 .. 64 waypoints");
-    if (Q == 0 || (!d_path && !d_len && !d_cost && !d_status)) return 0;
+    if (Q == 0 || (!d_path && !d_len && !d_cost && !d_status && !d_route && !d_hop)) return 0;
     if (!d_nodes || !d_nbr || !d_w || !d_start || !d_goal || !d_sidx || !d_sw || !d_gidx || !d_gw || !d_direct)
         return fail(OPTIK_HIP_EINVAL, "bad argument");
     BIND_DEVICE(ch);
@@ -286,6 +311,7 @@ int optik_hip_roadmap_query(const optik_hip_chain *ch, const double *d_nodes, in
     a.Q = Q; a.n = ch->n;
     a.direct = d_direct;
     a.path = d_path; a.len = d_len; a.cost = d_cost; a.status = d_status;
+    a.route = d_route; a.hop = d_hop;
     const dim3 grid((unsigned)Q);
     if (N <= 1024)
         hipLaunchKernelGGL((roadmap_query_kernel<1024, 256>), grid, dim3(256), 0, (hipStream_t)stream, a);

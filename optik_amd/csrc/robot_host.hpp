@@ -43,6 +43,9 @@ struct DeviceCtx {
     int32_t rm_N = 0, rm_k = 0;
     double rm_h = 0.0;
     uint64_t rm_epoch = 0;
+    // a lazy roadmap (optik_robot_roadmap_build_lazy): w is the working weights, w0 [k][N] follows it and the int32
+    // verdicts [k][N] follow nbr; rm_epoch: the world_epoch the verdicts were reset under
+    bool rm_lazy = false;
     ~DeviceCtx() { if (chain) optik_hip_chain_destroy(chain); }
 };
 

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <string>
 
@@ -782,7 +783,7 @@ int64_t optik_robot_roadmap_build(optik_robot *r, int32_t N, int32_t k, double r
         return set_err(-1, "download failed");
     int64_t edges = 0;
     for (size_t e = 0; e < cells; ++e) edges += std::isfinite(h_w[e]) ? 1 : 0;
-    c->rm_N = N; c->rm_k = k; c->rm_h = resolution; c->rm_epoch = epoch;
+    c->rm_N = N; c->rm_k = k; c->rm_h = resolution; c->rm_epoch = epoch; c->rm_lazy = false;
     return edges;
 }
 
@@ -801,6 +802,8 @@ int optik_robot_roadmap_plan(const optik_robot *r, const double *starts, const d
         // here or has the chain to itself until it is done)
         std::lock_guard<std::mutex> lock(c->batch_mu);
         if (c->rm_N == 0) return set_err(-1, "roadmap_plan: no roadmap (call optik_robot_roadmap_build first)");
+        if (c->rm_lazy)
+            return set_err(-1, "roadmap_plan: the roadmap is a lazy one (call optik_robot_roadmap_plan_lazy)");
         if (c->rm_epoch != r->world_epoch.load())
             return set_err(-1, "roadmap_plan: the roadmap is stale: the collision model or the world changed since it "
                                "was built (build it again)");
@@ -820,7 +823,10 @@ int optik_robot_roadmap_plan(const optik_robot *r, const double *starts, const d
         c, Q, in, sizeof(double) * (w + 3 + 3 * uk), kPlanChunk,
         [&](optik_hip_chain *ch, const double *d_s, int64_t L, double *d_out) -> int {
             // (under the batch guard now: the roadmap this chunk reads is still the one checked above?)
-            if (c->rm_N != N || c->rm_k != k || c->rm_epoch != r->world_epoch.load()) { stale = true; return 1; }
+            if (c->rm_N != N || c->rm_k != k || c->rm_lazy || c->rm_epoch != r->world_epoch.load()) {
+                stale = true;
+                return 1;
+            }
             const double *d_g = d_s + n * (size_t)L, *d_nodes = c->rm_graph.get(), *d_w = d_nodes + n * (size_t)N;
             double *d_cost = d_out + w * (size_t)L;
             int32_t *d_len = reinterpret_cast<int32_t *>(d_cost + L), *d_status = d_len + L;
@@ -851,6 +857,164 @@ int optik_robot_roadmap_plan(const optik_robot *r, const double *starts, const d
         });
     if (stale) return set_err(-1, "roadmap_plan: the roadmap changed or went stale during the call");
     return rc;
+}
+
+namespace {
+
+// The verdicts and working weights of the lazy roadmap of context c from the chain's model and world as they are
+// (under the robot's mutex and the context's batch guard: no setter is half-way).  The count of slots left open
+// goes to *open_out (may be null).
+int lazy_reset(DeviceCtx *c, size_t n, bool lengths, int64_t *open_out) {
+    const int32_t N = c->rm_N, k = c->rm_k;
+    const size_t cells = (size_t)k * (size_t)N;
+    double *d_nodes = c->rm_graph.get(), *d_w = d_nodes + n * (size_t)N, *d_w0 = d_w + cells;
+    int32_t *d_verdict = c->rm_nbr.get() + cells;
+    if (optik_hip_roadmap_lazy_reset(c->chain, nullptr, d_nodes, N, c->rm_nbr.get(), k, lengths ? 1 : 0, d_w0, nullptr,
+                                     d_verdict, d_w, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (!open_out) return 0;
+    if (!reserve_batch(c, (cells + 1) / 2)) return set_err(-1, kBatchAllocMsg);
+    int32_t *h_verdict = reinterpret_cast<int32_t *>(c->h_batch.get());
+    if (hipMemcpyAsync(h_verdict, d_verdict, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, nullptr) != hipSuccess
+        || hipStreamSynchronize(nullptr) != hipSuccess)
+        return set_err(-1, "download failed");
+    int64_t open = 0;
+    for (size_t e = 0; e < cells; ++e) open += h_verdict[e] != OPTIK_HIP_ROADMAP_BLOCKED ? 1 : 0;
+    *open_out = open;
+    return 0;
+}
+
+}  // namespace
+
+// A lazy roadmap (include/optik.h): the nodes and neighbour lists of optik_robot_roadmap_build, the lengths of the
+// motions in place of their check, and the reset of the verdicts against the world as it is.
+int64_t optik_robot_roadmap_build_lazy(optik_robot *r, int32_t N, int32_t k, double resolution, uint64_t first) {
+    if (!r) return set_err(-1, "null argument");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    // (Q = 0: the kernel layer's refusals of N, k, the resolution and the chain, before anything is allocated)
+    if (optik_hip_roadmap_knn(c->chain, nullptr, 0, nullptr, N, k, 1, nullptr, nullptr, nullptr)
+        || optik_hip_roadmap_edges(c->chain, nullptr, nullptr, 0, nullptr, N, nullptr, 1, resolution, 0, nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    // (the setters hold the robot's mutex from the bump of the epoch to the last chain: under it the epoch read here
+    // is the epoch of the world the chain has)
+    std::lock_guard<std::mutex> world_lock(r->mu);
+    BatchGuard guard(c);
+    if (!guard.ok()) return set_err(-1, kSetDeviceMsg);
+    const size_t n = (size_t)r->n, cells = (size_t)k * (size_t)N;
+    c->rm_N = 0;
+    if (c->rm_graph.reserve(n * (size_t)N + 2 * cells) != hipSuccess || c->rm_nbr.reserve(2 * cells) != hipSuccess)
+        return set_err(-1, kBatchAllocMsg);
+    double *d_nodes = c->rm_graph.get();
+    if (optik_hip_seed_batch(c->chain, first, N, d_nodes, nullptr)
+        || optik_hip_roadmap_knn(c->chain, d_nodes, N, d_nodes, N, k, 1, c->rm_nbr.get(), nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    c->rm_N = N; c->rm_k = k;
+    int64_t open = 0;
+    if (lazy_reset(c, n, true, &open)) {
+        c->rm_N = 0;
+        return -1;
+    }
+    c->rm_h = resolution; c->rm_epoch = r->world_epoch.load(); c->rm_lazy = true;
+    return open;
+}
+
+// Q plans over the robot's lazy roadmap: optik_robot_roadmap_plan's staging, with the loop of
+// optik_hip_roadmap_lazy_plan in place of the query; the verdicts are shared by the chunks and by later calls.
+int optik_robot_roadmap_plan_lazy(const optik_robot *r, const double *starts, const double *goals, int64_t Q,
+                                  int32_t Lmax, int32_t rounds, double *paths_out, int32_t *len_out, double *cost_out,
+                                  int32_t *status_out, int32_t *rounds_used_out, int64_t *checked_out) {
+    if (!r || !starts || !goals) return set_err(-1, "null argument");
+    if (Q < 0) return set_err(-1, "bad argument");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    if (rounds_used_out) *rounds_used_out = 0;
+    if (checked_out) *checked_out = 0;
+    const size_t n = (size_t)r->n;
+    // (a world that changes between the reset and a chunk makes the call start again; each further attempt needs
+    // another setter call, so the bound is never met by a caller that does not race its own setters)
+    for (int attempt = 0; attempt < 8; ++attempt) {
+        int32_t N, k;
+        double h;
+        uint64_t epoch;
+        {
+            // (under the robot's mutex no setter is half-way: the epoch and the chain's world belong together)
+            std::lock_guard<std::mutex> world_lock(r->mu);
+            BatchGuard guard(c);
+            if (!guard.ok()) return set_err(-1, kSetDeviceMsg);
+            if (c->rm_N == 0)
+                return set_err(-1, "roadmap_plan_lazy: no roadmap (call optik_robot_roadmap_build_lazy first)");
+            if (!c->rm_lazy)
+                return set_err(-1, "roadmap_plan_lazy: the roadmap is an eager one (call optik_robot_roadmap_plan)");
+            N = c->rm_N; k = c->rm_k; h = c->rm_h;
+            // (Q = 0: the kernel layer's refusals of Lmax and rounds)
+            if (optik_hip_roadmap_lazy_plan(c->chain, nullptr, nullptr, N, nullptr, nullptr, nullptr, k, h, nullptr,
+                                            nullptr, 0, nullptr, nullptr, k, nullptr, nullptr, k, nullptr, Lmax, rounds,
+                                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))
+                return set_err(-1, optik_hip_last_error());
+            epoch = r->world_epoch.load();
+            if (c->rm_epoch != epoch) {
+                if (lazy_reset(c, n, false, nullptr)) return -1;
+                c->rm_epoch = epoch;
+            }
+        }
+        if (Q == 0) return 0;
+        const size_t w = (size_t)Lmax * n, uk = (size_t)k, cells = uk * (size_t)N;
+        bool changed = false;
+        int64_t used = 0, checked = 0;
+        // (per query out and the chunk's scratch behind it: as optik_robot_roadmap_plan)
+        const RowInput in[] = {{starts, n}, {goals, n}};
+        const int rc = stage_rows(
+            c, Q, in, sizeof(double) * (w + 3 + 3 * uk), kPlanChunk,
+            [&](optik_hip_chain *ch, const double *d_s, int64_t L, double *d_out) -> int {
+                if (c->rm_N != N || c->rm_k != k || !c->rm_lazy || c->rm_epoch != epoch
+                    || epoch != r->world_epoch.load()) {
+                    changed = true;
+                    return 1;
+                }
+                const double *d_g = d_s + n * (size_t)L, *d_nodes = c->rm_graph.get();
+                double *d_w = c->rm_graph.get() + n * (size_t)N;
+                int32_t *d_verdict = c->rm_nbr.get() + cells;
+                double *d_cost = d_out + w * (size_t)L;
+                int32_t *d_len = reinterpret_cast<int32_t *>(d_cost + L), *d_status = d_len + L;
+                double *d_direct = d_cost + 2 * L, *d_sw = d_direct + L, *d_gw = d_sw + uk * (size_t)L;
+                int32_t *d_sidx = reinterpret_cast<int32_t *>(d_gw + uk * (size_t)L), *d_gidx = d_sidx + uk * (size_t)L;
+                int32_t chunk_used = 0;
+                int64_t chunk_checked = 0;
+                if (optik_hip_roadmap_knn(ch, d_s, L, d_nodes, N, k, 0, d_sidx, nullptr, nullptr)
+                    || optik_hip_roadmap_knn(ch, d_g, L, d_nodes, N, k, 0, d_gidx, nullptr, nullptr)
+                    || optik_hip_roadmap_edges(ch, nullptr, d_s, L, d_nodes, N, d_sidx, k, h, 0, d_sw, nullptr)
+                    || optik_hip_roadmap_edges(ch, nullptr, d_g, L, d_nodes, N, d_gidx, k, h, 1, d_gw, nullptr)
+                    || optik_hip_roadmap_edges(ch, nullptr, d_s, L, d_g, (int32_t)L, nullptr, 1, h, 0, d_direct, nullptr)
+                    || optik_hip_roadmap_lazy_plan(ch, nullptr, d_nodes, N, c->rm_nbr.get(), d_w, d_verdict, k, h, d_s,
+                                                   d_g, L, d_sidx, d_sw, k, d_gidx, d_gw, k, d_direct, Lmax, rounds,
+                                                   d_out, d_len, d_cost, d_status, &chunk_used, &chunk_checked, nullptr))
+                    return 1;
+                used += chunk_used;
+                checked += chunk_checked;
+                return 0;
+            },
+            [&](size_t b0, size_t L, const double *h_out) {
+                const double *h_cost = h_out + w * L;
+                const int32_t *h_len = reinterpret_cast<const int32_t *>(h_cost + L), *h_status = h_len + L;
+                if (paths_out)
+                    parallel_ranges(L, [&](size_t k0, size_t k1) {
+                        for (size_t q = k0; q < k1; ++q)
+                            for (size_t t = 0; t < (size_t)Lmax; ++t)
+                                std::memcpy(paths_out + ((b0 + q) * (size_t)Lmax + t) * n, h_out + (t * L + q) * n,
+                                            sizeof(double) * n);
+                    });
+                if (cost_out) std::memcpy(cost_out + b0, h_cost, sizeof(double) * L);
+                if (len_out) std::memcpy(len_out + b0, h_len, sizeof(int32_t) * L);
+                if (status_out) std::memcpy(status_out + b0, h_status, sizeof(int32_t) * L);
+            });
+        if (changed) continue;
+        if (rc) return rc;
+        if (rounds_used_out) *rounds_used_out = (int32_t)(used > INT32_MAX ? INT32_MAX : used);
+        if (checked_out) *checked_out = checked;
+        return 0;
+    }
+    return set_err(-1, "roadmap_plan_lazy: the world or the roadmap kept changing during the call");
 }
 
 int optik_robot_set_motion_resolution(optik_robot *r, double h) {

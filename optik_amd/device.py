@@ -26,8 +26,24 @@ def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+class LazyRoadmap:
+    """The state of a lazy roadmap (HipChain.roadmap_build_lazy), device tensors: nodes
+    [n, N], nbr [k, N] int32, the unchecked weights w0 [k, N], the working weights w [k, N] (w0, +inf where blocked:
+    the graph roadmap_query sees), verdict [k, N] int32 (nat.ROADMAP_SLOT_UNKNOWN / _FREE / _BLOCKED), and the
+    resolution its edges are checked at.  roadmap_plan_lazy updates w and verdict in place."""
+
+    def __init__(self, nodes, nbr, w0, w, verdict, resolution):
+        self.nodes, self.nbr, self.w0, self.w, self.verdict = nodes, nbr, w0, w, verdict
+        self.resolution = float(resolution)
+
+
 class HipChain:
-    """A flat kinematic chain uploaded to the GPU (optik_hip_chain)."""
+    """A flat kinematic chain uploaded to the GPU (optik_hip_chain).
+
+    Every batch operator is stream-ordered on the current stream and returns without waiting for the device, with
+    one exception: roadmap_plan_lazy (and its test hook roadmap_plan_lazy_from_flags) runs its loop on the host
+    and reads one int32 per round, so it synchronises the current stream once per round of checks it makes.
+    roadmap_plan keeps its promise of no host synchronisation."""
 
     def __init__(self, types, origins, axes, lb, ub, device="cuda:0"):
         if not torch.cuda.is_available():
@@ -476,7 +492,7 @@ class HipChain:
                                                     _stream_ptr()))
         return w
 
-    def roadmap_query(self, nodes, nbr, w, start, goal, sidx, sw, gidx, gw, direct, Lmax):
+    def roadmap_query(self, nodes, nbr, w, start, goal, sidx, sw, gidx, gw, direct, Lmax, _route=(None, None)):
         """Shortest joint paths over one graph for Q (start, goal) pairs (optik_hip_roadmap_query): nodes [n, N], the
         out-edges nbr [k, N] int32 and w [k, N], start and goal [n, Q], the start links sidx, sw [ks, Q], the goal
         links gidx, gw [kg, Q], direct [Q].  Returns a dict of device tensors: path [Lmax, Q, n] (what path_optimize
@@ -499,10 +515,10 @@ class HipChain:
                    len=torch.empty(Q, dtype=torch.int32, device=dev),
                    cost=torch.empty(Q, dtype=torch.float64, device=dev),
                    status=torch.empty(Q, dtype=torch.int32, device=dev))
-        nat.check(nat.lib().optik_hip_roadmap_query(
+        nat.check(nat.lib().optik_hip_roadmap_query_route(
             self._h, _ptr(nodes), N, _ptr(nbr), _ptr(w), k, _ptr(start), _ptr(goal), Q, _ptr(sidx), _ptr(sw), ks,
             _ptr(gidx), _ptr(gw), kg, _ptr(direct), int(Lmax), _ptr(res["path"]), _ptr(res["len"]), _ptr(res["cost"]),
-            _ptr(res["status"]), _stream_ptr()))
+            _ptr(res["status"]), _ptr(_route[0]), _ptr(_route[1]), _stream_ptr()))
         return res
 
     def roadmap_build(self, nodes, k, resolution, ee_offset7=None):
@@ -523,6 +539,111 @@ class HipChain:
         gw = self.roadmap_edges(goals, nodes, gidx, resolution, reverse=True, ee_offset7=ee_offset7)
         direct = self.roadmap_edges(starts, goals, None, resolution, ee_offset7=ee_offset7)
         return self.roadmap_query(nodes, nbr, w, starts, goals, sidx, sw, gidx, gw, direct, Lmax)
+
+    # -- lazy roadmaps (include/optik_hip.h) ------------------------------------------------
+    def roadmap_query_route(self, nodes, nbr, w, start, goal, sidx, sw, gidx, gw, direct, Lmax):
+        """roadmap_query with two more tensors in its dict (optik_hip_roadmap_query_route): route [Lmax, Q] int32,
+        the node of waypoint t for 1 <= t < len - 1 and -1 elsewhere, and hop [Lmax, Q] int32, the slot of the graph
+        hop that leaves waypoint t (-1 for the route's last node and elsewhere).  Stream-ordered."""
+        Q = self._check_q(start)
+        route = torch.empty((int(Lmax), Q), dtype=torch.int32, device=nodes.device)
+        hop = torch.empty((int(Lmax), Q), dtype=torch.int32, device=nodes.device)
+        res = self.roadmap_query(nodes, nbr, w, start, goal, sidx, sw, gidx, gw, direct, Lmax, _route=(route, hop))
+        res["route"], res["hop"] = route, hop
+        return res
+
+    def roadmap_build_lazy(self, nodes, k, resolution, ee_offset7=None):
+        """A lazy roadmap over nodes [n, N]: every node's k nearest others, the lengths of the motions to them in
+        place of their check, and the reset against the chain's model and world.  Returns a LazyRoadmap: the device
+        tensors nodes, nbr [k, N] int32, w0 [k, N], verdict [k, N] int32 (nat.ROADMAP_SLOT_*) and w [k, N], with k and
+        the resolution.  Stream-ordered."""
+        h = nat.check_resolution(resolution)
+        nbr, _ = self.roadmap_knn(nodes, nodes, k, exclude_self=True)
+        rm = LazyRoadmap(nodes, nbr, torch.empty(nbr.shape, dtype=torch.float64, device=nodes.device),
+                         torch.empty(nbr.shape, dtype=torch.float64, device=nodes.device), torch.empty_like(nbr), h)
+        self.roadmap_lazy_reset(rm, ee_offset7=ee_offset7, lengths=True)
+        return rm
+
+    def roadmap_lazy_reset(self, roadmap, ee_offset7=None, node_free=None, lengths=False):
+        """Forgets the verdicts of a LazyRoadmap (optik_hip_roadmap_lazy_reset): what to call after the chain's model
+        or world changed.  A slot is blocked if it is empty or touches a node that is not free, unknown otherwise.
+        node_free [N] uint8 stands for the classification of the nodes (the tests); lengths=True writes w0 first.
+        Stream-ordered; returns the roadmap."""
+        rm = roadmap
+        N, k = self._check_q(rm.nodes), self._check_slots(rm.nbr, rm.nodes.shape[1], "nbr", torch.int32)
+        nat.check_roadmap_args(N=N, k=k)
+        for name, t, dt in (("w0", rm.w0, torch.float64), ("w", rm.w, torch.float64), ("verdict", rm.verdict, torch.int32)):
+            if self._check_slots(t, N, name, dt) != k:
+                raise ValueError(f"{name} must have nbr's shape")
+        if node_free is not None and not (isinstance(node_free, torch.Tensor) and node_free.is_cuda
+                                          and node_free.dtype == torch.uint8 and node_free.numel() == N
+                                          and node_free.is_contiguous()):
+            raise ValueError(f"node_free must be a contiguous uint8 cuda tensor of {N} flags")
+        ee = self._ee7(ee_offset7)
+        nat.check(nat.lib().optik_hip_roadmap_lazy_reset(
+            self._h, _dp(ee) if ee is not None else None, _ptr(rm.nodes), N, _ptr(rm.nbr), k, 1 if lengths else 0,
+            _ptr(rm.w0), _ptr(node_free), _ptr(rm.verdict), _ptr(rm.w), _stream_ptr()))
+        return rm
+
+    def _lazy_loop(self, rm, q, Lmax, rounds, call):
+        start, goal, sidx, sw, gidx, gw, direct = q
+        N, Q = self._check_q(rm.nodes), self._check_q(start)
+        if self._check_q(goal) != Q:
+            raise ValueError("start and goal must have the same shape")
+        nat.check_roadmap_args(N=N, max_waypoints=Lmax)
+        rounds = nat.check_lazy_rounds(rounds)
+        k = self._check_slots(rm.nbr, N, "nbr", torch.int32)
+        ks, kg = self._check_slots(sidx, Q, "sidx", torch.int32), self._check_slots(gidx, Q, "gidx", torch.int32)
+        if self._check_slots(sw, Q, "sw", torch.float64) != ks or self._check_slots(gw, Q, "gw", torch.float64) != kg:
+            raise ValueError("a link's indices and weights must have the same shape")
+        if not (isinstance(direct, torch.Tensor) and direct.is_cuda and direct.dtype == torch.float64
+                and direct.numel() == Q and direct.is_contiguous()):
+            raise ValueError(f"direct must be a contiguous float64 cuda tensor of {Q} weights")
+        dev = rm.nodes.device
+        res = dict(path=torch.empty((int(Lmax), Q, self.n), dtype=torch.float64, device=dev),
+                   len=torch.empty(Q, dtype=torch.int32, device=dev),
+                   cost=torch.empty(Q, dtype=torch.float64, device=dev),
+                   status=torch.empty(Q, dtype=torch.int32, device=dev))
+        used, checked = C.c_int32(0), C.c_int64(0)
+        nat.check(call(k, N, (_ptr(start), _ptr(goal), Q, _ptr(sidx), _ptr(sw), ks, _ptr(gidx), _ptr(gw), kg,
+                              _ptr(direct), int(Lmax), rounds, _ptr(res["path"]), _ptr(res["len"]), _ptr(res["cost"]),
+                              _ptr(res["status"]), C.byref(used), C.byref(checked), _stream_ptr())))
+        res["rounds"], res["checked"] = int(used.value), int(checked.value)
+        return res
+
+    def roadmap_plan_lazy(self, roadmap, starts, goals, ks, Lmax, rounds=None, ee_offset7=None):
+        """roadmap_plan over a LazyRoadmap (optik_hip_roadmap_lazy_plan): the links and the direct motion are checked
+        as roadmap_plan checks them, then passes of the query alternate with checks of the unknown edges that the
+        found routes use, at most `rounds` times (None: nat.ROADMAP_LAZY_ROUNDS); the verdicts stay in the roadmap.
+        Returns roadmap_query's dict with status 4 (nat.ROADMAP_UNSETTLED) for a route that still holds an unchecked
+        edge, and "rounds" and "checked" as Python ints.
+        Unlike roadmap_plan this call synchronises with the host: the loop reads one int32, the number of edges to
+        check, after every pass -- one stream synchronise per round made."""
+        rm = roadmap
+        h = rm.resolution
+        sidx, _ = self.roadmap_knn(starts, rm.nodes, ks)
+        gidx, _ = self.roadmap_knn(goals, rm.nodes, ks)
+        sw = self.roadmap_edges(starts, rm.nodes, sidx, h, ee_offset7=ee_offset7)
+        gw = self.roadmap_edges(goals, rm.nodes, gidx, h, reverse=True, ee_offset7=ee_offset7)
+        direct = self.roadmap_edges(starts, goals, None, h, ee_offset7=ee_offset7)
+        ee = self._ee7(ee_offset7)
+        return self._lazy_loop(rm, (starts, goals, sidx, sw, gidx, gw, direct), Lmax, rounds,
+                               lambda k, N, q: nat.lib().optik_hip_roadmap_lazy_plan(
+                                   self._h, _dp(ee) if ee is not None else None, _ptr(rm.nodes), N, _ptr(rm.nbr),
+                                   _ptr(rm.w), _ptr(rm.verdict), k, h, *q))
+
+    def roadmap_plan_lazy_from_flags(self, roadmap, edge_free, node_free, start, goal, sidx, sw, gidx, gw, direct,
+                                     Lmax, rounds):
+        """The loop of roadmap_plan_lazy with edge_free [k, N] uint8 in place of the motion check (a test hook:
+        optik_hip_roadmap_lazy_plan_from_flags); node_free [N] uint8 not None resets the roadmap from it first.  The
+        links and the direct weights are given, as for roadmap_query."""
+        rm = roadmap
+        if self._check_slots(edge_free, rm.nodes.shape[1], "edge_free", torch.uint8) != rm.nbr.shape[0]:
+            raise ValueError("edge_free must have nbr's shape")
+        return self._lazy_loop(rm, (start, goal, sidx, sw, gidx, gw, direct), Lmax, rounds,
+                               lambda k, N, q: nat.lib().optik_hip_roadmap_lazy_plan_from_flags(
+                                   self._h, _ptr(rm.nodes), N, _ptr(rm.nbr), _ptr(rm.w0), _ptr(rm.w), _ptr(rm.verdict),
+                                   k, _ptr(edge_free), _ptr(node_free), *q))
 
     # -- shortcutting and resampling (include/optik_hip.h; DESIGN.md section 5.19) --------------------------------
     def _check_paths(self, path, lens):

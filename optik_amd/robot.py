@@ -75,6 +75,10 @@ def _bind(L):
     L.optik_robot_roadmap_build.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_uint64]
     L.optik_robot_roadmap_build.restype = C.c_int64
     L.optik_robot_roadmap_plan.argtypes = [vp, dp, dp, C.c_int64, C.c_int32, dp, ip, dp, ip]
+    L.optik_robot_roadmap_build_lazy.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_uint64]
+    L.optik_robot_roadmap_build_lazy.restype = C.c_int64
+    L.optik_robot_roadmap_plan_lazy.argtypes = [vp, dp, dp, C.c_int64, C.c_int32, C.c_int32, dp, ip, dp, ip, ip,
+                                                C.POINTER(C.c_int64)]
     L.optik_robot_path_shortcut.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, C.c_int32, C.c_double, C.c_double, C.c_int32,
                                             dp, dp, ip, dp, dp, ip]
     L.optik_robot_path_resample.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, C.c_int32, dp, ip]
@@ -871,7 +875,8 @@ class Robot:
         return out, first, last, clr, status, seg_free.reshape(P, L - 1).all(axis=1)
 
     # -- roadmap planning (extension; include/optik.h) --------------------------------------
-    def build_roadmap(self, N=nat.ROADMAP_NODES, k=nat.ROADMAP_K, resolution=nat.ROADMAP_RESOLUTION, first=0):
+    def build_roadmap(self, N=nat.ROADMAP_NODES, k=nat.ROADMAP_K, resolution=nat.ROADMAP_RESOLUTION, first=0,
+                      lazy=False):
         """A probabilistic roadmap over the robot's joint space, kept in the robot: N nodes (1 .. 8192) drawn
         uniformly inside the joint limits -- the IK restart seeds of indices first .. first + N - 1 --, each joined
         to its k (1 .. 16) nearest others (L-infinity) by the motion node -> neighbour, checked at `resolution`
@@ -879,17 +884,24 @@ class Robot:
         collision are kept; they have no free edge.  Returns the number of free edges.
         set_collision_model, set_world, set_world_grid and set_world_points make the roadmap stale: plan_paths then
         raises until it is built again.
+        lazy=True builds a lazy roadmap instead: the same nodes and neighbours, but no edge
+        is checked now.  plan_paths checks the edges its routes use and keeps the verdicts; a change of the model or
+        the world only forgets the verdicts, so a lazy roadmap is never stale and plan_paths follows a world that
+        changes at camera rate without a rebuild.  Returns the number of edge slots that are not blocked outright
+        (empty, or touching a node in collision).
         The defaults are the values with which the wall scene of examples/plan_path.py is planned on a Panda; they
         are that and nothing more.  A cluttered world needs more nodes, a narrow passage a finer resolution.
         ValueError for N, k or a resolution out of range."""
         nat.check_roadmap_args(N=N, k=k)
         h = nat.check_resolution(resolution)
-        edges = self._L.optik_robot_roadmap_build(self._h, int(N), int(k), h, int(first))
+        build = self._L.optik_robot_roadmap_build_lazy if lazy else self._L.optik_robot_roadmap_build
+        edges = build(self._h, int(N), int(k), h, int(first))
         if edges < 0:
             raise RuntimeError(_err(self._L))
+        self._roadmap_lazy = bool(lazy)
         return int(edges)
 
-    def plan_paths(self, starts, goals, max_waypoints=nat.PATH_OPTIMIZE_MAX_WAYPOINTS):
+    def plan_paths(self, starts, goals, max_waypoints=nat.PATH_OPTIMIZE_MAX_WAYPOINTS, rounds=None):
         """Shortest joint-space paths over the roadmap of build_roadmap for Q pairs starts[q] -> goals[q] ([Q, n]
         each), all on the GPU: each start and each goal is linked to its k nearest nodes by checked motions, the
         direct motion is checked too (and wins ties), and the route of least L-infinity length is walked.  Returns a
@@ -899,20 +911,37 @@ class Robot:
         inf), 2 the route needs more than max_waypoints (the true cost), 3 a NaN in the query (cost NaN); unless 0
         the path is the start, then the goal repeated.  Every one of the len - 1 segments of a found path is a
         motion that was checked free in the direction of travel at the roadmap's resolution.
-        RuntimeError without a roadmap or with a stale one; ValueError for max_waypoints outside 2 .. 64."""
+        On a lazy roadmap (build_roadmap(lazy=True)) `rounds` (0 .. 4096; None: nat.ROADMAP_LAZY_ROUNDS) bounds the
+        rounds of checking the unknown edges of the current routes, and the dict gains "rounds" (the rounds made)
+        and "checked" (the edges checked).  One more status, 4: unsettled -- the route found last still holds an
+        unchecked edge; the path is the start, then the goal repeated, the cost a lower bound (as is the cost of
+        status 2 there).  Plans of status 0, 1 and 3 are those of an eager roadmap of the same arguments in the same
+        world, bit for bit.  A world that changed since the last call resets the verdicts first.
+        RuntimeError without a roadmap or with a stale one; ValueError for max_waypoints outside 2 .. 64, for rounds
+        out of range and for rounds on a roadmap that is not lazy."""
         starts, goals = self._check_xs(starts), self._check_xs(goals)
         if starts.shape != goals.shape:
             raise ValueError(f"starts and goals must have the same shape, got {list(starts.shape)} and "
                              f"{list(goals.shape)}")
         nat.check_roadmap_args(max_waypoints=max_waypoints)
+        lazy = getattr(self, "_roadmap_lazy", False)
+        if rounds is not None and not lazy:
+            raise ValueError("rounds is an argument of lazy roadmaps (build_roadmap(lazy=True))")
         Q, n, L = starts.shape[0], starts.shape[1], int(max_waypoints)
         paths, cost = np.zeros((Q, L, n)), np.zeros(Q)
         ln, status = np.zeros(Q, dtype=np.int32), np.zeros(Q, dtype=np.int32)
         ip = C.POINTER(C.c_int32)
-        if self._L.optik_robot_roadmap_plan(self._h, _dp(starts), _dp(goals), Q, L, _dp(paths), ln.ctypes.data_as(ip),
-                                            _dp(cost), status.ctypes.data_as(ip)):
+        if not lazy:
+            if self._L.optik_robot_roadmap_plan(self._h, _dp(starts), _dp(goals), Q, L, _dp(paths),
+                                                ln.ctypes.data_as(ip), _dp(cost), status.ctypes.data_as(ip)):
+                raise RuntimeError(_err(self._L))
+            return dict(paths=paths, len=ln, cost=cost, status=status)
+        used, checked = C.c_int32(0), C.c_int64(0)
+        if self._L.optik_robot_roadmap_plan_lazy(self._h, _dp(starts), _dp(goals), Q, L, nat.check_lazy_rounds(rounds),
+                                                 _dp(paths), ln.ctypes.data_as(ip), _dp(cost),
+                                                 status.ctypes.data_as(ip), C.byref(used), C.byref(checked)):
             raise RuntimeError(_err(self._L))
-        return dict(paths=paths, len=ln, cost=cost, status=status)
+        return dict(paths=paths, len=ln, cost=cost, status=status, rounds=int(used.value), checked=int(checked.value))
 
     # -- shortcutting and resampling (extension; include/optik.h, DESIGN.md section 5.19) ---------------------------
     def _check_paths(self, paths, lens):
