@@ -298,6 +298,19 @@ int64_t optik_robot_roadmap_build_lazy(optik_robot *robot, int32_t N, int32_t k,
 int optik_robot_roadmap_plan_lazy(const optik_robot *robot, const double *starts, const double *goals, int64_t Q,
                                   int32_t Lmax, int32_t rounds, double *paths_out, int32_t *len_out, double *cost_out,
                                   int32_t *status_out, int32_t *rounds_used_out, int64_t *checked_out);
+/* Goal-set planning (extension; include/optik_hip.h: optik_hip_roadmap_query_goals): the
+ * cheapest route to any of several goals -- the IK solutions of a pose, for one -- in one pass over the roadmap.
+ * optik_robot_roadmap_plan_goals: optik_robot_roadmap_plan with goals [Q][G][n] row-major, 1 <= G <= 16, and counts
+ * [Q] (NULL: G each): query q has the goals g < counts[q] only, nothing of the others is read (the NaN rows of
+ * optik_robot_ik_solutions past its count are harmless), and counts[q] = 0 is status 1.  Outputs as there, for the
+ * cheapest route over the counted goals (its cost is the minimum of optik_robot_roadmap_plan's costs to each, bit for
+ * bit), and goal_out [Q]: the goal reached for status 0, -1 otherwise.  A found path ends in that goal; any other is
+ * the start, then goal 0 repeated (the start repeated without goals).  Ties go to the direct motion to the lowest goal.
+ * Queries run in chunks of 4 096.  rc 0, or -1: what optik_robot_roadmap_plan refuses, G out of range, and a lazy
+ * roadmap -- goal sets are planned over eager roadmaps only. */
+int optik_robot_roadmap_plan_goals(const optik_robot *robot, const double *starts, const double *goals,
+                                   const int32_t *counts, int32_t G, int64_t Q, int32_t Lmax, double *paths_out,
+                                   int32_t *len_out, double *cost_out, int32_t *status_out, int32_t *goal_out);
 /* Shortcutting and resampling planned paths (extension; include/optik_hip.h: optik_hip_path_shortcut and
  * optik_hip_path_resample).  paths [P][L][n] row-major with lens [P] waypoints each (NULL: L
  * each), 2 <= L <= 64 -- optik_robot_roadmap_plan's paths_out and len_out as they are.

@@ -324,6 +324,32 @@ int optik_hip_roadmap_lazy_plan_from_flags(optik_hip_chain *chain, const double 
                                            int32_t *d_len, double *d_cost, int32_t *d_status, int32_t *rounds_used,
                                            int64_t *checked, void *stream);
 
+/* Goal-set planning (extension; the rules, the theorem and their operation order:
+ * csrc/roadmap_goals_measure.hpp): optik_hip_roadmap_query with G goal slots per query, 1 <= G <=
+ * OPTIK_HIP_ROADMAP_MAX_GOALS, in place of the one goal -- the IK solutions of a pose, for one.  d_goals [G][n][Q];
+ * d_gcount [Q] int32: only the goals g < gcount exist (a count outside 0 .. G is clamped), and NOTHING of the others is
+ * read, so the NaN rows optik_hip_ik_solutions leaves past its count are harmless.  Per goal its goal links d_gidx, d_gw
+ * [G][kg][Q] (node -> goal, checked with reverse) and its direct weight d_direct [G][Q]; the start links as before.
+ * The shortest-path tree grows from the goals, so d[u] starts as the minimum over the counted goals' link weights of u
+ * and one run of the relaxation serves all of them: the cost is the minimum over g < gcount of
+ * optik_hip_roadmap_query's cost to goal g, bit for bit, and where one goal alone attains it, status, len and path
+ * are that query's too.  Ties: the direct edge of the lowest goal, then the lowest start slot; a node's successor is
+ * the lowest goal whose own link weight equals d[v], then the lowest node index.  Outputs (any may be NULL): d_path,
+ * d_len, d_cost, d_status as optik_hip_roadmap_query (status 3: a NaN in the start, a start link weight, or a counted
+ * goal, its link weights or its direct weight; gcount = 0: status 1); d_which [Q] int32, the goal reached for status 0
+ * and -1 otherwise.  A found path ends in goal `which` and is padded with it; any other is the start, then goal 0
+ * repeated (the start repeated for gcount = 0).  d_route, d_hop [Lmax][Q] as optik_hip_roadmap_query_route.  With G =
+ * 1 and gcount = 1 every output equals optik_hip_roadmap_query_route's, bit for bit.  Refuses what
+ * optik_hip_roadmap_query refuses, with the same codes, and G outside 1 .. 16 with OPTIK_HIP_EINVAL, before any device
+ * work.  Stream-ordered, no host synchronisation; one workgroup per query, the counted links staged in LDS. */
+#define OPTIK_HIP_ROADMAP_MAX_GOALS 16
+int optik_hip_roadmap_query_goals(const optik_hip_chain *chain, const double *d_nodes, int32_t N, const int32_t *d_nbr,
+                                  const double *d_w, int32_t k, const double *d_start, const double *d_goals,
+                                  const int32_t *d_gcount, int32_t G, int64_t Q, const int32_t *d_sidx,
+                                  const double *d_sw, int32_t ks, const int32_t *d_gidx, const double *d_gw, int32_t kg,
+                                  const double *d_direct, int32_t Lmax, double *d_path, int32_t *d_len, double *d_cost,
+                                  int32_t *d_status, int32_t *d_which, int32_t *d_route, int32_t *d_hop, void *stream);
+
 /* Path shortcutting and equal-spacing resampling (extension; the arithmetic and its operation
  * order: csrc/shortcut_measure.hpp).  Paths are d_path [Lin][P][n] -- the layout optik_hip_roadmap_query writes and
  * optik_hip_path_optimize reads --, path p having d_len[p] waypoints (d_len NULL: Lin each) and padding behind them

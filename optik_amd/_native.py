@@ -162,6 +162,9 @@ def lib():
     L.optik_hip_roadmap_query.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int64, vp, vp, C.c_int32,
                                           vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
     L.optik_hip_roadmap_query_route.argtypes = L.optik_hip_roadmap_query.argtypes[:-1] + [vp, vp, vp]
+    L.optik_hip_roadmap_query_goals.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int64,
+                                                vp, vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp,
+                                                vp, vp, vp]
     L.optik_hip_roadmap_lazy_reset.argtypes = [vp, dp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
     query_args = [vp, vp, C.c_int64, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, vp,
                   C.POINTER(C.c_int32), C.POINTER(C.c_int64), vp]
@@ -295,6 +298,17 @@ ROADMAP_LAZY_MAX_ROUNDS = 4096
 # Twice the larger number of rounds that the wall scene of the tests and the scene of examples/plan_lazy.py took on
 # a Panda, rounded up to a power of two (DESIGN.md section 5.24 has the two figures): that and nothing more.
 ROADMAP_LAZY_ROUNDS = 8
+
+
+# include/optik_hip.h: OPTIK_HIP_ROADMAP_MAX_GOALS, the goal slots of a goal-set query
+ROADMAP_MAX_GOALS = 16
+
+
+def check_roadmap_goals(G):
+    """The number of goal slots of a goal-set plan as an int: an integer in 1 .. ROADMAP_MAX_GOALS."""
+    if isinstance(G, bool) or int(G) != G or not 1 <= int(G) <= ROADMAP_MAX_GOALS:
+        raise ValueError(f"a goal set has 1 .. {ROADMAP_MAX_GOALS} goals per query, got {G!r}")
+    return int(G)
 
 
 def check_lazy_rounds(rounds):

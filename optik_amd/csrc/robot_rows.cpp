@@ -859,6 +859,108 @@ int optik_robot_roadmap_plan(const optik_robot *r, const double *starts, const d
     return rc;
 }
 
+// Q goal-set plans over the robot's roadmap (include/optik.h): optik_robot_roadmap_plan's
+// staging and refusals with G goal rows per query.  Per chunk the searches and the edge checks of the goals run goal
+// slot by goal slot ([G][n][L] is how the rows are staged, and [G][k][L] is how the query takes the links), then
+// optik_hip_roadmap_query_goals.
+int optik_robot_roadmap_plan_goals(const optik_robot *r, const double *starts, const double *goals,
+                                   const int32_t *counts, int32_t G, int64_t Q, int32_t Lmax, double *paths_out,
+                                   int32_t *len_out, double *cost_out, int32_t *status_out, int32_t *goal_out) {
+    if (!r || !starts || !goals) return set_err(-1, "null argument");
+    if (Q < 0) return set_err(-1, "bad argument");
+    if (G < 1 || G > OPTIK_HIP_ROADMAP_MAX_GOALS)
+        return set_err(-1, "roadmap_plan_goals: G must be in 1 .. " + std::to_string(OPTIK_HIP_ROADMAP_MAX_GOALS)
+                               + " goals per query");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    int32_t N, k;
+    double h;
+    {
+        // (as optik_robot_roadmap_plan: the setters bump the epoch before they take this mutex for the chain)
+        std::lock_guard<std::mutex> lock(c->batch_mu);
+        if (c->rm_N == 0) return set_err(-1, "roadmap_plan_goals: no roadmap (call optik_robot_roadmap_build first)");
+        if (c->rm_lazy)
+            return set_err(-1, "roadmap_plan_goals: the roadmap is a lazy one; goal sets are planned over eager "
+                               "roadmaps only (optik_robot_roadmap_plan_lazy plans single goals)");
+        if (c->rm_epoch != r->world_epoch.load())
+            return set_err(-1, "roadmap_plan_goals: the roadmap is stale: the collision model or the world changed "
+                               "since it was built (build it again)");
+        N = c->rm_N; k = c->rm_k; h = c->rm_h;
+    }
+    // (Q = 0: the kernel layer's refusals of Lmax and G)
+    if (optik_hip_roadmap_query_goals(c->chain, nullptr, N, nullptr, nullptr, k, nullptr, nullptr, nullptr, G, 0,
+                                      nullptr, nullptr, k, nullptr, nullptr, k, nullptr, Lmax, nullptr, nullptr,
+                                      nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (Q == 0 || (!paths_out && !len_out && !cost_out && !status_out && !goal_out)) return 0;
+    const size_t n = (size_t)r->n, w = (size_t)Lmax * n, uk = (size_t)k, uG = (size_t)G;
+    bool stale = false, upload_failed = false;
+    int64_t done = 0;  // (the chunks come in order: the rows before this one)
+    const std::vector<int32_t> all((size_t)(Q < kPlanChunk ? Q : kPlanChunk), G);  // counts NULL: every goal exists
+    // per query out: the path, the cost, len and status in one more double, the goal reached and the goal count in
+    // another; behind them the scratch of the chunk (downloaded with the rest, not looked at): direct G | sw k |
+    // gw G k doubles, sidx k | gidx G k int32
+    const RowInput in[] = {{starts, n}, {goals, uG * n}};
+    const int rc = stage_rows(
+        c, Q, in, sizeof(double) * (w + 3 + uG + uk + uG * uk) + sizeof(int32_t) * (uk + uG * uk), kPlanChunk,
+        [&](optik_hip_chain *ch, const double *d_s, int64_t L, double *d_out) -> int {
+            // (under the batch guard now: the roadmap this chunk reads is still the one checked above?)
+            if (c->rm_N != N || c->rm_k != k || c->rm_lazy || c->rm_epoch != r->world_epoch.load()) {
+                stale = true;
+                return 1;
+            }
+            const size_t uL = (size_t)L;
+            const double *d_g = d_s + n * uL, *d_nodes = c->rm_graph.get(), *d_w = d_nodes + n * (size_t)N;
+            double *d_cost = d_out + w * uL;
+            int32_t *d_len = reinterpret_cast<int32_t *>(d_cost + uL), *d_status = d_len + uL;
+            int32_t *d_which = reinterpret_cast<int32_t *>(d_cost + 2 * uL), *d_gcount = d_which + uL;
+            double *d_direct = d_cost + 3 * uL, *d_sw = d_direct + uG * uL, *d_gw = d_sw + uk * uL;
+            int32_t *d_sidx = reinterpret_cast<int32_t *>(d_gw + uG * uk * uL), *d_gidx = d_sidx + uk * uL;
+            if (hipMemcpyAsync(d_gcount, counts ? counts + done : all.data(), sizeof(int32_t) * uL,
+                               hipMemcpyHostToDevice, nullptr) != hipSuccess) {
+                upload_failed = true;
+                return 1;
+            }
+            done += L;
+            if (optik_hip_roadmap_knn(ch, d_s, L, d_nodes, N, k, 0, d_sidx, nullptr, nullptr)
+                || optik_hip_roadmap_edges(ch, nullptr, d_s, L, d_nodes, N, d_sidx, k, h, 0, d_sw, nullptr))
+                return 1;
+            for (size_t g = 0; g < uG; ++g) {
+                const double *d_goal = d_g + g * n * uL;
+                int32_t *d_gi = d_gidx + g * uk * uL;
+                if (optik_hip_roadmap_knn(ch, d_goal, L, d_nodes, N, k, 0, d_gi, nullptr, nullptr)
+                    || optik_hip_roadmap_edges(ch, nullptr, d_goal, L, d_nodes, N, d_gi, k, h, 1, d_gw + g * uk * uL,
+                                               nullptr)
+                    || optik_hip_roadmap_edges(ch, nullptr, d_s, L, d_goal, (int32_t)L, nullptr, 1, h, 0,
+                                               d_direct + g * uL, nullptr))
+                    return 1;
+            }
+            return optik_hip_roadmap_query_goals(ch, d_nodes, N, c->rm_nbr.get(), d_w, k, d_s, d_g, d_gcount, G, L,
+                                                 d_sidx, d_sw, k, d_gidx, d_gw, k, d_direct, Lmax, d_out, d_len, d_cost,
+                                                 d_status, d_which, nullptr, nullptr, nullptr)
+                       ? 1 : 0;
+        },
+        [&](size_t b0, size_t L, const double *h_out) {
+            const double *h_cost = h_out + w * L;
+            const int32_t *h_len = reinterpret_cast<const int32_t *>(h_cost + L), *h_status = h_len + L;
+            const int32_t *h_which = reinterpret_cast<const int32_t *>(h_cost + 2 * L);
+            if (paths_out)
+                parallel_ranges(L, [&](size_t k0, size_t k1) {
+                    for (size_t q = k0; q < k1; ++q)
+                        for (size_t t = 0; t < (size_t)Lmax; ++t)
+                            std::memcpy(paths_out + ((b0 + q) * (size_t)Lmax + t) * n, h_out + (t * L + q) * n,
+                                        sizeof(double) * n);
+                });
+            if (cost_out) std::memcpy(cost_out + b0, h_cost, sizeof(double) * L);
+            if (len_out) std::memcpy(len_out + b0, h_len, sizeof(int32_t) * L);
+            if (status_out) std::memcpy(status_out + b0, h_status, sizeof(int32_t) * L);
+            if (goal_out) std::memcpy(goal_out + b0, h_which, sizeof(int32_t) * L);
+        });
+    if (stale) return set_err(-1, "roadmap_plan_goals: the roadmap changed or went stale during the call");
+    if (upload_failed) return set_err(-1, "upload failed");
+    return rc;
+}
+
 namespace {
 
 // The verdicts and working weights of the lazy roadmap of context c from the chain's model and world as they are

@@ -540,6 +540,99 @@ class HipChain:
         direct = self.roadmap_edges(starts, goals, None, resolution, ee_offset7=ee_offset7)
         return self.roadmap_query(nodes, nbr, w, starts, goals, sidx, sw, gidx, gw, direct, Lmax)
 
+    # -- goal-set planning (include/optik_hip.h) -------------------------------------------
+    def _check_goal_slots(self, t, G, Q, name, dtype):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.dim() == 3 and t.shape[0] == G
+                and t.shape[2] == Q and t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {dtype} cuda tensor [{G}, kg, {Q}]")
+        nat.check_roadmap_args(k=int(t.shape[1]))
+        return int(t.shape[1])
+
+    def roadmap_query_goals(self, nodes, nbr, w, start, goals, gcount, sidx, sw, gidx, gw, direct, Lmax, route=False):
+        """roadmap_query with G goal slots per query (optik_hip_roadmap_query_goals): goals [G, n, Q], gcount [Q]
+        int32 -- only the goals g < gcount exist, nothing of the others is read --, the goal links gidx, gw [G, kg, Q]
+        and the direct weights direct [G, Q]; nodes, nbr, w, start and the start links sidx, sw [ks, Q] as there.
+        Returns roadmap_query's dict for the cheapest route to any counted goal plus which [Q] int32, the goal reached
+        (-1 unless status 0); route=True adds route and hop [Lmax, Q] int32 as roadmap_query_route.  Stream-ordered."""
+        N, Q = self._check_q(nodes), self._check_q(start)
+        if not (isinstance(goals, torch.Tensor) and goals.is_cuda and goals.dtype == torch.float64 and goals.dim() == 3
+                and goals.shape[1] == self.n and goals.shape[2] == Q and goals.is_contiguous()):
+            raise ValueError(f"goals must be a contiguous float64 cuda tensor [G, n, Q] = [G, {self.n}, {Q}]")
+        G = nat.check_roadmap_goals(int(goals.shape[0]))
+        nat.check_roadmap_args(N=N, max_waypoints=Lmax)
+        if not (isinstance(gcount, torch.Tensor) and gcount.is_cuda and gcount.dtype == torch.int32
+                and tuple(gcount.shape) == (Q,) and gcount.is_contiguous()):
+            raise ValueError(f"gcount must be a contiguous int32 cuda tensor [{Q}]")
+        k = self._check_slots(nbr, N, "nbr", torch.int32)
+        if self._check_slots(w, N, "w", torch.float64) != k:
+            raise ValueError("nbr and w must have the same shape")
+        ks = self._check_slots(sidx, Q, "sidx", torch.int32)
+        kg = self._check_goal_slots(gidx, G, Q, "gidx", torch.int32)
+        if self._check_slots(sw, Q, "sw", torch.float64) != ks or self._check_goal_slots(gw, G, Q, "gw",
+                                                                                       torch.float64) != kg:
+            raise ValueError("a link's indices and weights must have the same shape")
+        if not (isinstance(direct, torch.Tensor) and direct.is_cuda and direct.dtype == torch.float64
+                and tuple(direct.shape) == (G, Q) and direct.is_contiguous()):
+            raise ValueError(f"direct must be a contiguous float64 cuda tensor [{G}, {Q}]")
+        dev = nodes.device
+        res = dict(path=torch.empty((int(Lmax), Q, self.n), dtype=torch.float64, device=dev),
+                   len=torch.empty(Q, dtype=torch.int32, device=dev),
+                   cost=torch.empty(Q, dtype=torch.float64, device=dev),
+                   status=torch.empty(Q, dtype=torch.int32, device=dev),
+                   which=torch.empty(Q, dtype=torch.int32, device=dev))
+        if route:
+            res["route"] = torch.empty((int(Lmax), Q), dtype=torch.int32, device=dev)
+            res["hop"] = torch.empty((int(Lmax), Q), dtype=torch.int32, device=dev)
+        nat.check(nat.lib().optik_hip_roadmap_query_goals(
+            self._h, _ptr(nodes), N, _ptr(nbr), _ptr(w), k, _ptr(start), _ptr(goals), _ptr(gcount), G, Q, _ptr(sidx),
+            _ptr(sw), ks, _ptr(gidx), _ptr(gw), kg, _ptr(direct), int(Lmax), _ptr(res["path"]), _ptr(res["len"]),
+            _ptr(res["cost"]), _ptr(res["status"]), _ptr(res["which"]), _ptr(res.get("route")), _ptr(res.get("hop")),
+            _stream_ptr()))
+        return res
+
+    def roadmap_plan_goals(self, roadmap, starts, goals, gcount, ks, Lmax, resolution, ee_offset7=None):
+        """Plans starts[:, q] ([n, Q]) to the nearest of goals[:gcount[q], :, q] ([G, n, Q], gcount [Q] int32) over
+        roadmap = (nodes, nbr, w): roadmap_plan's steps with the G * Q goal columns in one batch each -- the ks
+        nearest nodes of every start and every goal, the links start -> node and node -> goal, the direct motions
+        start -> goal g (the starts repeated G times) --, then roadmap_query_goals.  Existing entry points and the
+        goal-set query on the current stream, torch reshapes between them, no host synchronisation.  A goal past
+        gcount (the NaN rows of ik_solutions) goes through the searches and the motion check as it is -- a NaN segment
+        is not sampled and costs nothing -- and its results are never read.  Returns roadmap_query_goals' dict."""
+        nodes, nbr, w = roadmap
+        Q = self._check_q(starts)
+        if not (isinstance(goals, torch.Tensor) and goals.is_cuda and goals.dtype == torch.float64 and goals.dim() == 3
+                and goals.shape[1] == self.n and goals.shape[2] == Q and goals.is_contiguous()):
+            raise ValueError(f"goals must be a contiguous float64 cuda tensor [G, n, Q] = [G, {self.n}, {Q}]")
+        G = nat.check_roadmap_goals(int(goals.shape[0]))
+        cols = goals.permute(1, 0, 2).reshape(self.n, G * Q)  # [n, G * Q]: goal g of query q is column g * Q + q
+        sidx, _ = self.roadmap_knn(starts, nodes, ks)
+        gidx, _ = self.roadmap_knn(cols, nodes, ks)
+        sw = self.roadmap_edges(starts, nodes, sidx, resolution, ee_offset7=ee_offset7)
+        gw = self.roadmap_edges(cols, nodes, gidx, resolution, reverse=True, ee_offset7=ee_offset7)
+        direct = self.roadmap_edges(starts.repeat(1, G), cols, None, resolution, ee_offset7=ee_offset7)
+        ks = int(ks)
+        return self.roadmap_query_goals(nodes, nbr, w, starts, goals, gcount, sidx, sw,
+                                        gidx.reshape(ks, G, Q).permute(1, 0, 2).contiguous(),
+                                        gw.reshape(ks, G, Q).permute(1, 0, 2).contiguous(), direct.reshape(G, Q), Lmax)
+
+    def roadmap_plan_poses(self, roadmap, cfg, targets, starts, restart_begin, restart_end, K, min_dist, ks, Lmax,
+                           resolution, ee_offset7=None):
+        """Plans starts[:, q] ([n, Q]) to the poses targets [Q, 7]: ik_solutions with x0 = the starts and up to K <=
+        16 solutions per pose, whose count is the goal count and whose x [Q, K, n] becomes the goal set [K, n, Q],
+        then roadmap_plan_goals -- back to back on the current stream, no host synchronisation, the solutions never
+        leave the device.  With a collision model installed the solutions are the collision-free ones (DESIGN.md
+        section 5.12); in the Quality mode solution 0 is the one nearest the start.  Returns roadmap_plan_goals' dict
+        plus goals [K, n, Q] and count [Q] int32."""
+        K = nat.check_roadmap_goals(K)
+        Q = self._check_q(starts)
+        sol = self.ik_solutions(cfg, targets, starts.t().contiguous(), restart_begin, restart_end, K, min_dist,
+                                ee_offset7=ee_offset7)
+        goals = sol["x"].permute(1, 2, 0).contiguous()
+        res = self.roadmap_plan_goals(roadmap, starts, goals, sol["count"], ks, Lmax, resolution,
+                                      ee_offset7=ee_offset7)
+        res["goals"], res["count"] = goals, sol["count"]
+        return res
+
     # -- lazy roadmaps (include/optik_hip.h; DESIGN.md section 5.24) ------------------------------------------------
     def roadmap_query_route(self, nodes, nbr, w, start, goal, sidx, sw, gidx, gw, direct, Lmax):
         """roadmap_query with two more tensors in its dict (optik_hip_roadmap_query_route): route [Lmax, Q] int32,

@@ -75,6 +75,7 @@ def _bind(L):
     L.optik_robot_roadmap_build.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_uint64]
     L.optik_robot_roadmap_build.restype = C.c_int64
     L.optik_robot_roadmap_plan.argtypes = [vp, dp, dp, C.c_int64, C.c_int32, dp, ip, dp, ip]
+    L.optik_robot_roadmap_plan_goals.argtypes = [vp, dp, dp, ip, C.c_int32, C.c_int64, C.c_int32, dp, ip, dp, ip, ip]
     L.optik_robot_roadmap_build_lazy.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_uint64]
     L.optik_robot_roadmap_build_lazy.restype = C.c_int64
     L.optik_robot_roadmap_plan_lazy.argtypes = [vp, dp, dp, C.c_int64, C.c_int32, C.c_int32, dp, ip, dp, ip, ip,
@@ -942,6 +943,63 @@ class Robot:
                                                  status.ctypes.data_as(ip), C.byref(used), C.byref(checked)):
             raise RuntimeError(_err(self._L))
         return dict(paths=paths, len=ln, cost=cost, status=status, rounds=int(used.value), checked=int(checked.value))
+
+    # -- goal-set planning (extension; include/optik.h) --------------------------------------
+    _LAZY_GOALS_MSG = ("goal sets are planned over eager roadmaps only: the roadmap is a lazy one "
+                       "(build_roadmap(lazy=False), or plan to single goals with plan_paths)")
+
+    def plan_to_goals(self, starts, goals, counts=None, max_waypoints=nat.PATH_OPTIMIZE_MAX_WAYPOINTS):
+        """plan_paths to the nearest of several goals per query, in one pass over the roadmap: starts [Q, n], goals
+        [Q, G, n] with 1 <= G <= 16, counts [Q] (None: G each) -- query q has the goals g < counts[q] only, nothing
+        of the others is read (the NaN rows of ik_solutions_batch_arrays past its count are harmless), and a query
+        without goals has status 1.  Returns plan_paths' dict for the cheapest route over the counted goals -- its
+        cost is the minimum of plan_paths' costs to each of them, bit for bit -- plus "goal" [Q] int32: the index
+        into the goal set of the goal reached for status 0, -1 otherwise.  A found path ends in that goal; any other
+        is the start, then goal 0 repeated.  Ties go to the direct motion to the lowest goal.  "paths" and "len" go
+        into shortcut_paths, resample_paths and certify_paths as they are.
+        RuntimeError without a roadmap, with a stale one and with a lazy one; ValueError for the shapes, for G
+        outside 1 .. 16 and for max_waypoints outside 2 .. 64."""
+        starts = self._check_xs(starts)
+        Q, n = starts.shape
+        goals = np.ascontiguousarray(goals, dtype=np.float64)
+        if goals.ndim != 3 or goals.shape[0] != Q or goals.shape[2] != n:
+            raise ValueError(f"goals must be [Q, G, n] = [{Q}, G, {n}], got {list(goals.shape)}")
+        G = nat.check_roadmap_goals(goals.shape[1])
+        if counts is not None:
+            counts = np.ascontiguousarray(counts, dtype=np.int32)
+            if counts.shape != (Q,):
+                raise ValueError(f"counts must be [Q] = [{Q}], got {list(counts.shape)}")
+        nat.check_roadmap_args(max_waypoints=max_waypoints)
+        if getattr(self, "_roadmap_lazy", False):
+            raise RuntimeError(self._LAZY_GOALS_MSG)
+        L = int(max_waypoints)
+        paths, cost = np.zeros((Q, L, n)), np.zeros(Q)
+        ln, status, goal = (np.zeros(Q, dtype=np.int32) for _ in range(3))
+        ip = C.POINTER(C.c_int32)
+        if self._L.optik_robot_roadmap_plan_goals(self._h, _dp(starts), _dp(goals),
+                                                  counts.ctypes.data_as(ip) if counts is not None else None, G, Q, L,
+                                                  _dp(paths), ln.ctypes.data_as(ip), _dp(cost),
+                                                  status.ctypes.data_as(ip), goal.ctypes.data_as(ip)):
+            raise RuntimeError(_err(self._L))
+        return dict(paths=paths, len=ln, cost=cost, status=status, goal=goal)
+
+    def plan_to_poses(self, config: SolverConfig, starts, targets, k=8, min_dist=0.1,
+                      max_waypoints=nat.PATH_OPTIMIZE_MAX_WAYPOINTS, ee_offset=None):
+        """"Move the gripper to this pose": starts [Q, n], targets [Q, 4, 4] row-major poses.  ik_solutions_batch_arrays
+        with the starts as seeds gives up to k <= 16 distinct solutions per pose (with a collision model installed:
+        the collision-free ones; Quality: solution 0 is the one nearest the start), and plan_to_goals plans to the
+        nearest of them over the roadmap.  Returns plan_to_goals' dict plus "goals" [Q, k, n] (NaN past the count)
+        and "count" [Q] int32; an unreachable pose has count 0, status 1 and goal -1.  The solutions pass through
+        the host here; HipChain.roadmap_plan_poses keeps both stages on the device."""
+        k = nat.check_roadmap_goals(k)
+        if getattr(self, "_roadmap_lazy", False):
+            raise RuntimeError(self._LAZY_GOALS_MSG)
+        starts = self._check_xs(starts)
+        x, _, _, count = self.ik_solutions_batch_arrays(config, targets, starts, k=k, min_dist=min_dist,
+                                                        ee_offset=ee_offset)
+        res = self.plan_to_goals(starts, x, counts=count, max_waypoints=max_waypoints)
+        res["goals"], res["count"] = x, count
+        return res
 
     # -- shortcutting and resampling (extension; include/optik.h, DESIGN.md section 5.19) ---------------------------
     def _check_paths(self, paths, lens):
