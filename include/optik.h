@@ -311,6 +311,21 @@ int optik_robot_roadmap_plan_lazy(const optik_robot *robot, const double *starts
 int optik_robot_roadmap_plan_goals(const optik_robot *robot, const double *starts, const double *goals,
                                    const int32_t *counts, int32_t G, int64_t Q, int32_t Lmax, double *paths_out,
                                    int32_t *len_out, double *cost_out, int32_t *status_out, int32_t *goal_out);
+/* The bidirectional tree planner (extension; include/optik_hip.h: optik_hip_rrt_plan): what to
+ * run on the rows that optik_robot_roadmap_plan returns as status 1.  It reads no roadmap and keeps no state in the
+ * robot: starts, goals [Q][n] row-major; two trees per query of at most max_nodes (2 .. 4096) nodes grow from the
+ * query's own start and goal for at most iters (1 .. 65 536) iterations with steps of at most `step` radians
+ * (L-infinity) towards the restart seeds first, first + 1, ..., every motion checked at `resolution` in the direction
+ * the path travels it.  paths_out [Q][Lmax][n], 2 <= Lmax <= 64, len_out [Q], cost_out [Q], status_out [Q] as
+ * optik_robot_roadmap_plan writes them (0 found; 1 not found, or a start or goal in collision; 2 found with more than
+ * Lmax waypoints; 3 a NaN or an infinity in the query); iters_out [Q] the iterations run; nodes_out [Q][2] the sizes of
+ * the trees.  Any output may be NULL.  poll (1 .. 65 536): the iterations between two looks at the number of unfinished
+ * queries.  Queries run in chunks of 4 096; a query's result does not depend on the others.  On the robot's first
+ * device.  rc 0, or -1: null argument, what the kernel layer refuses. */
+int optik_robot_rrt_plan(const optik_robot *robot, const double *starts, const double *goals, int64_t Q, int32_t iters,
+                         double step, double resolution, uint64_t first, int32_t max_nodes, int32_t Lmax, int32_t poll,
+                         const double *ee_offset16, double *paths_out, int32_t *len_out, double *cost_out,
+                         int32_t *status_out, int32_t *iters_out, int32_t *nodes_out);
 /* Shortcutting and resampling planned paths (extension; include/optik_hip.h: optik_hip_path_shortcut and
  * optik_hip_path_resample).  paths [P][L][n] row-major with lens [P] waypoints each (NULL: L
  * each), 2 <= L <= 64 -- optik_robot_roadmap_plan's paths_out and len_out as they are.

@@ -350,6 +350,61 @@ int optik_hip_roadmap_query_goals(const optik_hip_chain *chain, const double *d_
                                   const double *d_direct, int32_t Lmax, double *d_path, int32_t *d_len, double *d_cost,
                                   int32_t *d_status, int32_t *d_which, int32_t *d_route, int32_t *d_hop, void *stream);
 
+/* The bidirectional tree planner (extension; the rules and their operation order:
+ * csrc/rrt_measure.hpp): RRT-Connect with one extension per tree and iteration, for the queries a roadmap returns as
+ * status 1 -- a start or goal in a pocket none of its nodes sees.  It needs no roadmap: each query grows tree 0 from
+ * its own start and tree 1 from its own goal, d_start, d_goal [n][Q].  Any revolute chain of 1 .. 16 joint positions;
+ * the metric is L-infinity in radians; every motion is checked at `resolution` by optik_hip_collision_motion_batch's
+ * own code (classify form, same stream; model, world and ee_offset7 as there) IN THE DIRECTION THE FINAL PATH TRAVELS
+ * IT: parent -> child in tree 0, child -> parent in tree 1, tree-0 node -> tree-1 node for a connection.
+ *
+ * The sample of iteration i is restart seed first + i (optik_hip_seed_batch) for EVERY query; the queries differ by
+ * their ends.  A tree holds at most max_nodes nodes, a configuration and a parent index each.
+ * Before iteration 0: a NaN or infinite joint in the start or goal gives status 3 (cost NaN); a start or goal that is
+ * not free by optik_hip_collision_batch status 1 (cost +inf); a free direct motion start -> goal status 0 with len 2.
+ * iters is 0 and the trees are empty (nodes 0) for all three.
+ * Iteration i, a = i & 1, b = 1 - a, r = sample i:
+ *   nearest  p = the node of tree a first in the total order on (distance to r, index): a number before a NaN, then
+ *            the smaller distance, then the smaller index (optik_hip_roadmap_knn's order with k = 1);
+ *   steer    d = that distance; nothing happens if d is 0, NaN or infinite; c = r copied if d <= step, otherwise
+ *            c_j = p_j + (step / d) * (r_j - p_j), the quotient, the difference, the product and the sum each rounded;
+ *            then if (c_j < lo_j) c_j = lo_j; if (c_j > hi_j) c_j = hi_j;
+ *   extend   nothing more happens if tree a is full or the motion between p and c is not free (or not sampled);
+ *            otherwise c joins tree a with parent p;
+ *   connect  m = the nearest node of tree b to c.  If the motion between c and m is free the query is found.  If not,
+ *            and the distance of m and c is > step and tree b is not full, e = steer from m towards c joins tree b with
+ *            parent m if the motion between m and e is free.
+ * A found path is tree 0 from its root to its junction node, then tree 1 from its junction node to its root: W
+ * waypoints, the cost the sum of their consecutive distances added from the start forwards.  Outputs (any may be
+ * NULL): d_path [Lmax][Q][n] -- the layout optik_hip_path_shortcut, _path_resample and _path_optimize take --,
+ * d_len [Q], d_cost [Q], d_status [Q]:
+ *   0 found, W <= Lmax: the waypoints padded with the goal; 1 no junction after `iters` iterations (cost +inf);
+ *   2 found with W > Lmax (the true cost); 3 as above.  Unless 0: len 2, the start, then the goal repeated.
+ * d_iters [Q]: the iterations run before the query ended (i + 1 when iteration i found it, `iters` for status 1);
+ * d_nodes [2][Q]: the sizes of the two trees.
+ * A query's result does not depend on Q, on how the queries are chunked, on `poll` or on a launch shape, and is bit
+ * for bit rrt_measure.hpp's serial reference given the same samples and motion verdicts.
+ * The loop over the iterations runs on the host, stream-ordered: per iteration one kernel of its own (one wave per
+ * query: the commit of the iteration before, both nearest searches and the steers) and the motion check over 3 Q
+ * segments; every `poll` iterations it reads one int32, the number of queries that have not ended, and stops at 0 --
+ * one synchronise of `stream` per poll.  Ended queries hand the motion check NaN segments, which it does not sample.
+ * The trees are the chain's workspace, grown on demand: 2 * max_nodes * (8 n + 4) bytes per query, the queries in
+ * chunks of at most OPTIK_HIP_RRT_CHUNK_BYTES of it (optik_hip_rrt_chunk: that many queries), one after the other on
+ * the stream.  One call per chain handle at a time.
+ * Refused with OPTIK_HIP_EINVAL before any device work: Q < 0 (Q = 0 is a no-op) or above 2^30, iters outside 1 ..
+ * OPTIK_HIP_RRT_MAX_ITERS, a step that is not finite and > 0, max_nodes outside 2 .. OPTIK_HIP_RRT_MAX_NODES, Lmax
+ * outside 2 .. 64, poll outside 1 .. OPTIK_HIP_RRT_MAX_POLL, a resolution that is not finite and > 0; with
+ * OPTIK_HIP_EUNSUPPORTED, also when Q = 0: chains with prismatic joints. */
+#define OPTIK_HIP_RRT_MAX_ITERS 65536
+#define OPTIK_HIP_RRT_MAX_NODES 4096
+#define OPTIK_HIP_RRT_MAX_POLL 65536
+#define OPTIK_HIP_RRT_CHUNK_BYTES (256ll << 20)
+int optik_hip_rrt_plan(optik_hip_chain *chain, const double *ee_offset7, const double *d_start, const double *d_goal,
+                       int64_t Q, int32_t iters, double step, double resolution, uint64_t first, int32_t max_nodes,
+                       int32_t Lmax, int32_t poll, double *d_path, int32_t *d_len, double *d_cost, int32_t *d_status,
+                       int32_t *d_iters, int32_t *d_nodes, void *stream);
+int64_t optik_hip_rrt_chunk(const optik_hip_chain *chain, int32_t max_nodes);
+
 /* Path shortcutting and equal-spacing resampling (extension; the arithmetic and its operation
  * order: csrc/shortcut_measure.hpp).  Paths are d_path [Lin][P][n] -- the layout optik_hip_roadmap_query writes and
  * optik_hip_path_optimize reads --, path p having d_len[p] waypoints (d_len NULL: Lin each) and padding behind them

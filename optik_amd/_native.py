@@ -171,6 +171,10 @@ def lib():
     L.optik_hip_roadmap_lazy_plan.argtypes = [vp, dp, vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_double] + query_args
     L.optik_hip_roadmap_lazy_plan_from_flags.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, C.c_int32, vp,
                                                          vp] + query_args
+    L.optik_hip_rrt_plan.argtypes = [vp, dp, vp, vp, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_uint64, C.c_int32,
+                                     C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
+    L.optik_hip_rrt_chunk.argtypes = [vp, C.c_int32]
+    L.optik_hip_rrt_chunk.restype = C.c_int64
     L.optik_hip_path_shortcut.argtypes = [vp, dp, vp, vp, C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_double,
                                           C.c_int32, vp, vp, vp, vp, vp, vp]
     L.optik_hip_path_resample.argtypes = [vp, vp, vp, C.c_int32, C.c_int64, C.c_int32, vp, vp, vp]
@@ -326,6 +330,40 @@ def check_roadmap_args(N=1, k=1, max_waypoints=2):
                             ("max_waypoints", max_waypoints, 2, PATH_OPTIMIZE_MAX_WAYPOINTS)):
         if isinstance(v, bool) or int(v) != v or not lo <= int(v) <= hi:
             raise ValueError(f"{name} must be an integer in {lo} .. {hi}, got {v!r}")
+
+
+# include/optik_hip.h: OPTIK_HIP_RRT_MAX_ITERS, _MAX_NODES, _MAX_POLL; the statuses of optik_hip_rrt_plan are the
+# roadmap query's (ROADMAP_FOUND .. ROADMAP_NAN)
+RRT_MAX_ITERS, RRT_MIN_NODES, RRT_MAX_NODES, RRT_MAX_POLL = 65536, 2, 4096, 65536
+# The values with which Robot.plan_rrt plans the pair of examples/plan_rrt.py on a Panda, a route the example's small
+# roadmap misses -- the serial reference joins the trees there after 33 iterations with 17 and 15 nodes, and the
+# budgets are the next powers of two times four: that and nothing more.
+RRT_ITERS, RRT_STEP, RRT_NODES, RRT_POLL = 256, 0.5, 256, 32
+
+
+def check_rrt_args(iters=1, step=1.0, max_nodes=2, max_waypoints=2, poll=1, first=0):
+    """The argument rules of optik_hip_rrt_plan, checked on the host; returns (iters, step, max_nodes, poll, first)
+    with None replaced by RRT_ITERS, RRT_STEP, RRT_NODES and RRT_POLL."""
+    iters = RRT_ITERS if iters is None else iters
+    max_nodes = RRT_NODES if max_nodes is None else max_nodes
+    poll = RRT_POLL if poll is None else poll
+    for name, v, lo, hi in (("iters", iters, 1, RRT_MAX_ITERS), ("max_nodes", max_nodes, RRT_MIN_NODES, RRT_MAX_NODES),
+                            ("max_waypoints", max_waypoints, 2, PATH_OPTIMIZE_MAX_WAYPOINTS),
+                            ("poll", poll, 1, RRT_MAX_POLL), ("first", first, 0, (1 << 64) - 1)):
+        if isinstance(v, bool) or int(v) != v or not lo <= int(v) <= hi:
+            raise ValueError(f"{name} must be an integer in {lo} .. {hi}, got {v!r}")
+    step = RRT_STEP if step is None else float(step)
+    if not (math.isfinite(step) and step > 0.0):
+        raise ValueError(f"step must be finite and > 0, got {step!r}")
+    return int(iters), step, int(max_nodes), int(poll), int(first)
+
+
+def rrt_chunk(chain_handle, max_nodes):
+    """The queries optik_hip_rrt_plan processes per chunk of its workspace for this chain and tree size."""
+    c = int(lib().optik_hip_rrt_chunk(chain_handle, int(max_nodes)))
+    if c < 1:
+        raise ValueError(f"max_nodes must be an integer in {RRT_MIN_NODES} .. {RRT_MAX_NODES}, got {max_nodes!r}")
+    return c
 
 
 # include/optik_hip.h: OPTIK_HIP_PATH_SHORTCUT_MAX_VERTICES; the statuses of optik_hip_path_shortcut / _path_resample

@@ -14,6 +14,7 @@
 //   ik_path_optimize.hip  covariant gradient smoothing of joint paths against the same witnesses
 //   ik_roadmap.hip     roadmap planning: nearest neighbours, motion-checked edges, shortest-path queries
 //   ik_roadmap_lazy.hip  lazy roadmaps: edges checked only when a route uses them, verdicts kept across plans
+//   ik_rrt.hip         the bidirectional tree planner: two trees per query, for the queries a roadmap misses
 //   ik_shortcut.hip    path shortcutting over all-pairs visibility, equal-spacing resampling
 //   ik_time.hip        timing of joint paths under velocity and acceleration limits, trajectory sampling
 //   ik_occupancy.hip   occupancy grids and point clouds into distance-field worlds (distance transform, voxelize)
@@ -269,6 +270,8 @@ struct optik_hip_chain {
     // optik_hip_roadmap_lazy_plan (ik_roadmap_lazy.hip): the round's counter, the routes' nodes and hop slots
     // [Lmax][Q] twice, the claimed slots, their segments [n][B] twice and free flags; _lazy_reset: the nodes' free flags
     optik::DeviceBuf<unsigned char> roadmap_lazy_ws;  // bytes
+    // optik_hip_rrt_plan (ik_rrt.hip): the samples, one chunk's ends, segments, flags, per-query state and trees
+    optik::DeviceBuf<unsigned char> rrt_ws;  // bytes
     // optik_hip_path_shortcut (ik_shortcut.hip): one chunk's vertex pairs as segments [n][B] twice, their free flags [B]
     optik::DeviceBuf<unsigned char> shortcut_ws;  // bytes
     // (what the last launch's selection kernel left behind: the work-item counter at 0, this many leading

@@ -1119,6 +1119,59 @@ int optik_robot_roadmap_plan_lazy(const optik_robot *r, const double *starts, co
     return set_err(-1, "roadmap_plan_lazy: the world or the roadmap kept changing during the call");
 }
 
+// Q queries through optik_hip_rrt_plan: no roadmap is read, so nothing can be stale.
+int optik_robot_rrt_plan(const optik_robot *r, const double *starts, const double *goals, int64_t Q, int32_t iters,
+                         double step, double resolution, uint64_t first, int32_t max_nodes, int32_t Lmax, int32_t poll,
+                         const double *ee16, double *paths_out, int32_t *len_out, double *cost_out,
+                         int32_t *status_out, int32_t *iters_out, int32_t *nodes_out) {
+    if (!r || !starts || !goals) return set_err(-1, "null argument");
+    if (Q < 0) return set_err(-1, "bad argument");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    // (Q = 0: the kernel layer's refusals of the chain, the sizes, the step and the resolution)
+    if (optik_hip_rrt_plan(c->chain, nullptr, nullptr, nullptr, 0, iters, step, resolution, first, max_nodes, Lmax, poll,
+                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (Q == 0 || (!paths_out && !len_out && !cost_out && !status_out && !iters_out && !nodes_out)) return 0;
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    const size_t n = (size_t)r->n, w = (size_t)Lmax * n;
+    // per query out: the path, the cost, then len and status in one more double, iters and a spare word in another,
+    // the two tree sizes in a last one
+    const RowInput in[] = {{starts, n}, {goals, n}};
+    return stage_rows(
+        c, Q, in, sizeof(double) * (w + 4), kPlanChunk,
+        [&](optik_hip_chain *ch, const double *d_s, int64_t L, double *d_out) {
+            double *d_cost = d_out + w * (size_t)L;
+            int32_t *d_len = reinterpret_cast<int32_t *>(d_cost + L), *d_status = d_len + L, *d_it = d_status + L,
+                    *d_nodes = d_it + 2 * L;
+            return optik_hip_rrt_plan(ch, ee16 ? ee7 : nullptr, d_s, d_s + n * (size_t)L, L, iters, step, resolution,
+                                      first, max_nodes, Lmax, poll, d_out, d_len, d_cost, d_status, d_it, d_nodes,
+                                      nullptr);
+        },
+        [&](size_t b0, size_t L, const double *h_out) {
+            const double *h_cost = h_out + w * L;
+            const int32_t *h_len = reinterpret_cast<const int32_t *>(h_cost + L), *h_status = h_len + L,
+                          *h_it = h_status + L, *h_nodes = h_it + 2 * L;
+            if (paths_out)
+                parallel_ranges(L, [&](size_t k0, size_t k1) {
+                    for (size_t q = k0; q < k1; ++q)
+                        for (size_t t = 0; t < (size_t)Lmax; ++t)
+                            std::memcpy(paths_out + ((b0 + q) * (size_t)Lmax + t) * n, h_out + (t * L + q) * n,
+                                        sizeof(double) * n);
+                });
+            if (cost_out) std::memcpy(cost_out + b0, h_cost, sizeof(double) * L);
+            if (len_out) std::memcpy(len_out + b0, h_len, sizeof(int32_t) * L);
+            if (status_out) std::memcpy(status_out + b0, h_status, sizeof(int32_t) * L);
+            if (iters_out) std::memcpy(iters_out + b0, h_it, sizeof(int32_t) * L);
+            if (nodes_out)
+                for (size_t q = 0; q < L; ++q) {
+                    nodes_out[2 * (b0 + q)] = h_nodes[q];
+                    nodes_out[2 * (b0 + q) + 1] = h_nodes[L + q];
+                }
+        });
+}
+
 int optik_robot_set_motion_resolution(optik_robot *r, double h) {
     if (!r) return set_err(-1, "null argument");
     if (!(h >= 0.0) || !std::isfinite(h))

@@ -738,6 +738,35 @@ class HipChain:
                                    self._h, _ptr(rm.nodes), N, _ptr(rm.nbr), _ptr(rm.w0), _ptr(rm.w), _ptr(rm.verdict),
                                    k, _ptr(edge_free), _ptr(node_free), *q))
 
+    # -- the bidirectional tree planner (include/optik_hip.h) -----------------------------
+    def rrt_plan(self, starts, goals, iters, step, resolution, first=0, max_nodes=nat.RRT_NODES, Lmax=64,
+                 poll=nat.RRT_POLL, ee_offset7=None):
+        """Plans starts[:, q] -> goals[:, q] ([n, Q] each) without a roadmap (optik_hip_rrt_plan): two trees per
+        query, grown from its own start and goal towards the samples first, first + 1, ... of seed_batch, every motion
+        checked at `resolution` in the direction the path travels it.  Returns a dict of device tensors: path [Lmax, Q,
+        n] (what path_shortcut, path_resample and path_optimize take), len [Q] int32, cost [Q], status [Q] int32
+        (nat.ROADMAP_FOUND .. ROADMAP_NAN), iters [Q] int32 and nodes [2, Q] int32.
+        Unlike roadmap_plan this call synchronises with the host: the loop over the iterations reads one int32, the
+        number of queries that have not ended, every `poll` iterations."""
+        Q = self._check_q(starts)
+        if self._check_q(goals) != Q:
+            raise ValueError("starts and goals must have the same shape")
+        iters, step, max_nodes, poll, first = nat.check_rrt_args(iters, step, max_nodes, Lmax, poll, first)
+        h = nat.check_resolution(resolution)
+        dev = starts.device
+        res = dict(path=torch.empty((int(Lmax), Q, self.n), dtype=torch.float64, device=dev),
+                   len=torch.empty(Q, dtype=torch.int32, device=dev),
+                   cost=torch.empty(Q, dtype=torch.float64, device=dev),
+                   status=torch.empty(Q, dtype=torch.int32, device=dev),
+                   iters=torch.empty(Q, dtype=torch.int32, device=dev),
+                   nodes=torch.empty((2, Q), dtype=torch.int32, device=dev))
+        ee = self._ee7(ee_offset7)
+        nat.check(nat.lib().optik_hip_rrt_plan(
+            self._h, _dp(ee) if ee is not None else None, _ptr(starts), _ptr(goals), Q, iters, step, h, first,
+            max_nodes, int(Lmax), poll, _ptr(res["path"]), _ptr(res["len"]), _ptr(res["cost"]), _ptr(res["status"]),
+            _ptr(res["iters"]), _ptr(res["nodes"]), _stream_ptr()))
+        return res
+
     # -- shortcutting and resampling (include/optik_hip.h; DESIGN.md section 5.19) --------------------------------
     def _check_paths(self, path, lens):
         if not (isinstance(path, torch.Tensor) and path.is_cuda and path.dtype == torch.float64 and path.dim() == 3

@@ -80,6 +80,8 @@ def _bind(L):
     L.optik_robot_roadmap_build_lazy.restype = C.c_int64
     L.optik_robot_roadmap_plan_lazy.argtypes = [vp, dp, dp, C.c_int64, C.c_int32, C.c_int32, dp, ip, dp, ip, ip,
                                                 C.POINTER(C.c_int64)]
+    L.optik_robot_rrt_plan.argtypes = [vp, dp, dp, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_uint64, C.c_int32,
+                                       C.c_int32, C.c_int32, dp, dp, ip, dp, ip, ip, ip]
     L.optik_robot_path_shortcut.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, C.c_int32, C.c_double, C.c_double, C.c_int32,
                                             dp, dp, ip, dp, dp, ip]
     L.optik_robot_path_resample.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, C.c_int32, dp, ip]
@@ -1000,6 +1002,48 @@ class Robot:
         res = self.plan_to_goals(starts, x, counts=count, max_waypoints=max_waypoints)
         res["goals"], res["count"] = x, count
         return res
+
+    # -- the bidirectional tree planner (extension; include/optik.h) --------------------------
+    def plan_rrt(self, starts, goals, iters=None, step=None, resolution=nat.ROADMAP_RESOLUTION, first=0, max_nodes=None,
+                 max_waypoints=nat.PATH_OPTIMIZE_MAX_WAYPOINTS, poll=nat.RRT_POLL, ee_offset=None):
+        """Single-query planning for the pairs a roadmap misses -- the rows plan_paths returns with status 1 because
+        the start or the goal sits in a pocket none of its nodes sees: for each of Q pairs starts[q] -> goals[q] ([Q,
+        n] each) two trees grow on the GPU, one from the start and one from the goal, towards the same uniform samples
+        (the IK restart seeds first, first + 1, ...) in steps of at most `step` radians (L-infinity), and are joined
+        by a free motion (bidirectional RRT with one extension per tree and iteration).  Every motion is checked at
+        `resolution` against the collision model and world, in the direction the path travels it, as
+        collision_motion_batch_arrays checks it.  Returns a dict: paths [Q, max_waypoints, n], len [Q] int32, cost [Q]
+        and status [Q] int32 as plan_paths returns them -- 0 found; 1 no junction within `iters` iterations, or a start
+        or goal in collision (cost inf); 2 found, but with more than max_waypoints waypoints (the true cost); 3 a NaN or
+        an infinity in the query (cost NaN); unless 0 the path is the start, then the goal repeated --, iters [Q] int32
+        (the iterations run before the query ended) and nodes [Q, 2] int32 (the sizes of the two trees, at most
+        max_nodes each).  "paths" and "len" go into shortcut_paths, resample_paths and certify_paths as they are; a
+        tree's path is jagged, so shortcut it.
+        It keeps no state in the robot and reads no roadmap, so nothing can be stale.  A query's result does not
+        depend on the other queries or on `poll`, the iterations between two looks at the number of unfinished
+        queries (each look synchronises with the GPU once).
+        The defaults of iters, step and max_nodes (nat.RRT_ITERS, RRT_STEP, RRT_NODES) are the values with which the
+        pair of examples/plan_rrt.py is planned on a Panda; they are that and nothing more.
+        ValueError for iters outside 1 .. 65536, max_nodes outside 2 .. 4096, max_waypoints outside 2 .. 64, poll
+        outside 1 .. 65536, a step or a resolution that is not finite and > 0."""
+        starts, goals = self._check_xs(starts), self._check_xs(goals)
+        if starts.shape != goals.shape:
+            raise ValueError(f"starts and goals must have the same shape, got {list(starts.shape)} and "
+                             f"{list(goals.shape)}")
+        iters, step, max_nodes, poll, first = nat.check_rrt_args(iters, step, max_nodes, max_waypoints, poll, first)
+        h = nat.check_resolution(resolution)
+        Q, n, L = starts.shape[0], starts.shape[1], int(max_waypoints)
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        paths, cost = np.zeros((Q, L, n)), np.zeros(Q)
+        ln, status, it = (np.zeros(Q, dtype=np.int32) for _ in range(3))
+        nodes = np.zeros((Q, 2), dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        if self._L.optik_robot_rrt_plan(self._h, _dp(starts), _dp(goals), Q, iters, step, h, first, max_nodes, L, poll,
+                                        _dp(ee) if ee is not None else None, _dp(paths), ln.ctypes.data_as(ip),
+                                        _dp(cost), status.ctypes.data_as(ip), it.ctypes.data_as(ip),
+                                        nodes.ctypes.data_as(ip)):
+            raise RuntimeError(_err(self._L))
+        return dict(paths=paths, len=ln, cost=cost, status=status, iters=it, nodes=nodes)
 
     # -- shortcutting and resampling (extension; include/optik.h, DESIGN.md section 5.19) ---------------------------
     def _check_paths(self, paths, lens):
