@@ -221,6 +221,15 @@ int optik_robot_occupancy_from_map(const optik_robot *robot, int32_t nx, int32_t
 int optik_robot_world_grid_from_mesh(const optik_robot *robot, const double *origin3, double voxel, int32_t nx,
                                      int32_t ny, int32_t nz, const double *tris9, int32_t M, double max_distance,
                                      float *values_out);
+/* From a solid to a sphere model (extension; include/optik_hip.h: optik_hip_sphere_fit).  Host arrays, on the robot's
+ * first device; installs nothing.  values (nx * ny * nz floats: a signed distance field of the solid, negative inside)
+ * and points3 [P][3] on its surface -> chosen_out int32 [K], centers_out [K][3], radii_out [K], gains_out int32 [K],
+ * count_uncovered_out int32 [2] (the spheres chosen, the points left uncovered); entries past the count are -1, NaN,
+ * NaN and 0.  rc 0, or -1: the refusals of the kernel layer, and a NaN or infinite point. */
+int optik_robot_sphere_fit(const optik_robot *robot, const double *origin3, double voxel, int32_t nx, int32_t ny,
+                           int32_t nz, const float *values, const double *points3, int64_t P, double pad, double slack,
+                           int32_t K, int32_t *chosen_out, double *centers_out, double *radii_out, int32_t *gains_out,
+                           int32_t *count_uncovered_out);
 /* x [B][n] -> frames16_out [B][n + 2][16]: every frame as a column-major 4x4 (as optik_robot_fk_ex writes it; frame
  * n + 1 is fk's pose).  ee_offset16 may be NULL.  On the robot's first device; rc 0 or -1. */
 int optik_robot_link_frames_batch(const optik_robot *robot, int64_t B, const double *x, const double *ee_offset16,

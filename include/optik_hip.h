@@ -664,6 +664,46 @@ int optik_hip_world_grid_from_mesh(const optik_hip_chain *chain, const double *o
 int32_t optik_hip_mesh_tile(void);
 int64_t optik_hip_mesh_pairs_per_launch(int64_t pairs);
 
+/* From a solid to a sphere model: a greedy sphere cover (extension; the arithmetic and the
+ * guarantee: csrc/spherefit_measure.hpp).  d_values is a signed distance field of the solid on a grid as above
+ * (nx * ny * nz floats in device memory, negative inside: what optik_hip_world_grid_from_mesh writes), d_points3 are P
+ * points sampled on its surface ([P][3] doubles in device memory, the grid's frame).
+ *
+ * Every node c of the grid is a candidate sphere: centre at the node, radius r = pad - value[c], a candidate iff
+ * r > slack and the value is finite; such a sphere reaches at most `pad` beyond the solid.  It covers a point that
+ * lies at least `slack` inside it.  K rounds: each picks the candidate that covers the most points not covered yet
+ * (ties: the lower node index) and marks them covered; from the first round whose best gain is 0 on, nothing is chosen.
+ * Outputs, device memory: d_chosen int32 [K] the node indices (-1 past the count), d_centers3 [K][3] and d_radii [K]
+ * (NaN past the count), d_gains int32 [K] the points each pick newly covered (0 past the count), d_count_uncovered
+ * int32 [2]: the number of spheres chosen and the points left uncovered.  With the grid around the points' bounding
+ * box and pad >= sqrt(3) * voxel + slack every point can be covered, so a K that is large enough leaves none.
+ * Everything decided is an integer: the result does not depend on the launch shape.
+ *
+ * Stream-ordered, no host synchronisation, and it allocates nothing: d_workspace is device memory of the caller's, at
+ * least optik_hip_sphere_fit_workspace_bytes(nx, ny, nz, P) bytes (4 bytes per node, 8 per point and 2 KiB), 4-byte
+ * aligned, in use until the call's work has run.  The cost is about 2 * nx * ny * nz * P pair tests, issued as
+ * stream-ordered launches of a bounded number of pairs each, and 4 short launches per round.  Finite coordinates are
+ * the caller's promise here (the robot-level entry of optik.h checks its host arrays): a NaN point is covered by
+ * nothing.  The fit does not read the chain's joints: any chain is accepted, it names the device.
+ *
+ * Refused with OPTIK_HIP_EINVAL before any device work: a grid that set_world_grid would refuse for its geometry, K
+ * outside 1 .. OPTIK_HIP_MAX_FIT_SPHERES, P outside 1 .. OPTIK_HIP_MAX_FIT_POINTS, a pad that is zero, negative, NaN
+ * or infinite, a slack that is negative, NaN or not below pad, a null buffer, a workspace that is too small.
+ *
+ * optik_hip_fit_tile returns the number of points the kernels stage at a time.  optik_hip_fit_pairs_per_launch is a
+ * test hook: pairs > 0 sets the launch bound for the process, 0 restores the built-in one, a negative value only asks;
+ * it returns the bound in force.  Neither changes an integer of any result. */
+#define OPTIK_HIP_MAX_FIT_SPHERES 256
+#define OPTIK_HIP_MAX_FIT_POINTS (1 << 20)
+int optik_hip_sphere_fit(const optik_hip_chain *chain, const double *origin3, double voxel, int32_t nx, int32_t ny,
+                         int32_t nz, const float *d_values, const double *d_points3, int64_t P, double pad,
+                         double slack, int32_t K, int32_t *d_chosen, double *d_centers3, double *d_radii,
+                         int32_t *d_gains, int32_t *d_count_uncovered, void *d_workspace, int64_t workspace_bytes,
+                         void *stream);
+int64_t optik_hip_sphere_fit_workspace_bytes(int32_t nx, int32_t ny, int32_t nz, int64_t P);
+int32_t optik_hip_fit_tile(void);
+int64_t optik_hip_fit_pairs_per_launch(int64_t pairs);
+
 /* The motion check (extension; the arithmetic: csrc/motion_measure.hpp): is the straight
  * joint-space segment qa -> qb free at a resolution h > 0 (L-infinity, radians)?  With d = max_i |qb_i - qa_i| the
  * segment has K = max(1, (int)ceil(d / h)) steps and K + 1 samples: sample 0 is qa and sample K is qb, copied, and

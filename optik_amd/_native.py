@@ -144,6 +144,13 @@ def lib():
     L.optik_hip_mesh_tile.restype = C.c_int32
     L.optik_hip_mesh_pairs_per_launch.argtypes = [C.c_int64]
     L.optik_hip_mesh_pairs_per_launch.restype = C.c_int64
+    L.optik_hip_sphere_fit.argtypes = [vp, dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_int64, C.c_double,
+                                       C.c_double, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int64, vp]
+    L.optik_hip_sphere_fit_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64]
+    L.optik_hip_sphere_fit_workspace_bytes.restype = C.c_int64
+    L.optik_hip_fit_tile.restype = C.c_int32
+    L.optik_hip_fit_pairs_per_launch.argtypes = [C.c_int64]
+    L.optik_hip_fit_pairs_per_launch.restype = C.c_int64
     L.optik_hip_link_frames_batch.argtypes = [vp, dp, vp, C.c_int64, vp, vp]
     L.optik_hip_collision_batch.argtypes = [vp, dp, vp, C.c_int64, vp, vp, vp]
     L.optik_hip_collision_motion_batch.argtypes = [vp, dp, vp, vp, C.c_int64, C.c_double, vp, vp, vp, vp, vp]
@@ -266,6 +273,35 @@ class mesh_pairs_per_launch:
 
     def __exit__(self, *exc):
         lib().optik_hip_mesh_pairs_per_launch(self.prev)
+        return False
+
+
+MAX_FIT_SPHERES = 256     # include/optik_hip.h: OPTIK_HIP_MAX_FIT_SPHERES
+MAX_FIT_POINTS = 1 << 20  # include/optik_hip.h: OPTIK_HIP_MAX_FIT_POINTS
+
+
+def fit_tile():
+    """FIT_TILE of csrc/spherefit_measure.hpp: the points optik_hip_sphere_fit stages in LDS at a time."""
+    return int(lib().optik_hip_fit_tile())
+
+
+class fit_pairs_per_launch:
+    """``with fit_pairs_per_launch(pairs): ...`` -- a test hook (include/optik_hip.h: optik_hip_fit_pairs_per_launch):
+    within the block optik_hip_sphere_fit cuts its candidates into launches of at most `pairs` (candidate, point) pair
+    tests each instead of FIT_PAIRS_PER_LAUNCH; restored after it.  No result depends on it."""
+
+    def __init__(self, pairs):
+        self.pairs = int(pairs)
+        if self.pairs < 1:
+            raise ValueError("pairs must be >= 1")
+
+    def __enter__(self):
+        self.prev = int(lib().optik_hip_fit_pairs_per_launch(-1))
+        lib().optik_hip_fit_pairs_per_launch(self.pairs)
+        return self
+
+    def __exit__(self, *exc):
+        lib().optik_hip_fit_pairs_per_launch(self.prev)
         return False
 
 

@@ -18,7 +18,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "liboptik_amd.so")
-SOURCES = ["ik_capi.hip", "ik_select.hip", "ik_solutions.hip", "ik_path.hip", "ik_manip.hip", "ik_collision.hip", "ik_motion.hip", "ik_advance.hip", "ik_avoid.hip", "ik_path_optimize.hip", "ik_roadmap.hip", "ik_roadmap_lazy.hip", "ik_roadmap_goals.hip", "ik_rrt.hip", "ik_shortcut.hip", "ik_time.hip", "ik_occupancy.hip", "ik_depth.hip", "ik_mesh.hip", "ik_batch_ops.hip", "ik_quad_kernel.hip", "ik_lane_kernel.hip", "ik_wide_kernel.hip",
+SOURCES = ["ik_capi.hip", "ik_select.hip", "ik_solutions.hip", "ik_path.hip", "ik_manip.hip", "ik_collision.hip", "ik_motion.hip", "ik_advance.hip", "ik_avoid.hip", "ik_path_optimize.hip", "ik_roadmap.hip", "ik_roadmap_lazy.hip", "ik_roadmap_goals.hip", "ik_rrt.hip", "ik_shortcut.hip", "ik_time.hip", "ik_occupancy.hip", "ik_depth.hip", "ik_mesh.hip", "ik_spherefit.hip", "ik_batch_ops.hip", "ik_quad_kernel.hip", "ik_lane_kernel.hip", "ik_wide_kernel.hip",
            "robot_host.cpp", "robot_rows.cpp"]
 # translation units: (source, object, extra flags).  ik_quad_kernel.hip is compiled twice -- its
 # throughput form (two waves per SIMD) without the machine-LICM pass, which otherwise hoists constants and
@@ -43,6 +43,7 @@ UNITS = [("ik_capi.hip", "ik_capi.o", []),          # chains, options, the resta
          ("ik_occupancy.hip", "ik_occupancy.o", []),  # occupancy grids and point clouds into distance-field worlds
          ("ik_depth.hip", "ik_depth.o", []),        # depth images into a persistent evidence map with free-space carving
          ("ik_mesh.hip", "ik_mesh.o", []),          # triangle meshes into distance-field worlds (distance, winding number)
+         ("ik_spherefit.hip", "ik_spherefit.o", []),  # sphere models from collision geometry: a greedy cover of a solid
          ("ik_batch_ops.hip", "ik_batch_ops.o", []),  # objective / FK / seed batches, probes
          # (the quad solver is issue-bound: the max-ILP scheduling strategy is worth +3 % restarts/s on the
          # throughput form and -3 % on a single ik()'s latency.  The iterative-ILP strategy the lane kernel is built

@@ -292,3 +292,357 @@ def spheres_along_chain(robot, radius, per_link):
     frames = np.array(frames, dtype=np.int32)
     centers = np.array(centers, dtype=np.float64).reshape(-1, 3)
     return frames, centers, np.full(len(frames), radius)
+
+
+# ---- sphere models from collision geometry ------------------------------------------------
+
+MAX_FIT_SPHERES = 256     # OPTIK_HIP_MAX_FIT_SPHERES: the spheres one fit may choose
+MAX_FIT_POINTS = 1 << 20  # OPTIK_HIP_MAX_FIT_POINTS: the surface points one fit may take
+# The tessellation of primitive_mesh: a cylinder is a prism over a regular polygon with this many sides, a sphere a
+# latitude / longitude polyhedron with this many meridians and half as many bands.  Both are CIRCUMSCRIBED: scaled so
+# that the polyhedron contains the true solid; it exceeds it by radius * (1 / cos(pi / 24) - 1) = 0.86 % of the radius
+# (cylinder), resp. 1.7 % (sphere).
+PRIMITIVE_SEGMENTS = 24
+# Robot.fit_spheres' default grid: the longest side of the solid's bounding box is this many voxels.  Nobody has
+# measured a good value.  10 makes pad (below) 0.225 of that side, which is coarse; it is chosen so that a handful of
+# spheres covers a simple solid completely (uncovered == 0, by the host reference: a 5 : 1 : 1 bar takes 4, a
+# cylinder 5, a cube 25 of which the first 8 hold 92 % of the samples).  A finer grid hugs the solid more closely and
+# needs many more spheres: at 24 voxels a 2 : 2 : 1 box takes 67.
+FIT_VOXELS_PER_EXTENT = 10
+
+
+def fit_defaults(extent, voxel=None, pad=None, spacing=None):
+    """(voxel, pad, spacing) of Robot.fit_spheres for a solid whose bounding box has the longest side `extent`:
+    voxel = extent / 10, spacing = voxel / 2, pad = 1.01 * (sqrt(3) * voxel + spacing) -- the 1 % keeps the
+    guarantee's condition pad >= sqrt(3) * voxel + spacing (csrc/spherefit_measure.hpp) clear of rounding.  At the
+    defaults pad = 0.225 * extent: that is how far a sphere may stick out of the solid.  Values that are given are
+    kept; ValueError where they break that condition."""
+    extent = float(extent)
+    if not (math.isfinite(extent) and extent > 0.0):
+        raise ValueError("fit: the solid's bounding box must have a finite, positive extent")
+    voxel = extent / FIT_VOXELS_PER_EXTENT if voxel is None else float(voxel)
+    if not (math.isfinite(voxel) and voxel > 0.0):
+        raise ValueError(f"fit: voxel must be finite and > 0, got {voxel!r}")
+    spacing = 0.5 * voxel if spacing is None else float(spacing)
+    if not (math.isfinite(spacing) and spacing > 0.0):
+        raise ValueError(f"fit: spacing must be finite and > 0, got {spacing!r}")
+    need = math.sqrt(3.0) * voxel + spacing
+    pad = 1.01 * need if pad is None else float(pad)
+    if not (math.isfinite(pad) and pad >= need):
+        raise ValueError(f"fit: pad must be >= sqrt(3) * voxel + spacing = {need!r} for every surface point to be "
+                         f"coverable, got {pad!r}")
+    return voxel, pad, spacing
+
+
+def fit_grid(lo, hi, voxel, pad):
+    """(origin [3], shape) of the grid of Robot.fit_spheres: it contains the bounding box [lo, hi] grown by `pad`."""
+    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    origin = lo - pad
+    shape = tuple(max(2, int(math.ceil(float(hi[a] + pad - origin[a]) / voxel)) + 1) for a in range(3))
+    return origin, shape
+
+
+def surface_points(vertices, triangles=None, spacing=None):
+    """Points on a mesh's surface no further apart than `spacing`, float64 [P, 3]: per triangle (a, b, c) the
+    barycentric lattice a + (i / m) (b - a) + (j / m) (c - a), i + j <= m, with m = ceil(longest edge / spacing)
+    subdivisions (at least 1).  The lattice cuts the triangle into similar triangles whose edges are at most
+    `spacing` long, so every point of the triangle is within `spacing` of a lattice point.  A zero-area triangle
+    contributes its vertices (and, where it has length, the lattice along it): nothing divides by an area.  Points
+    on shared edges repeat; nothing is merged.  The mesh is given as mesh_arrays takes it.  ValueError above 2^20
+    points: raise `spacing`."""
+    if spacing is None:
+        raise ValueError("surface_points: spacing is needed")
+    spacing = float(spacing)
+    if not (math.isfinite(spacing) and spacing > 0.0):
+        raise ValueError(f"surface_points: spacing must be finite and > 0, got {spacing!r}")
+    t = mesh_arrays(vertices, triangles).reshape(-1, 3, 3)
+    if not np.isfinite(t).all():
+        raise ValueError("surface_points: a NaN or infinite coordinate")
+    if len(t) == 0:
+        return np.zeros((0, 3))
+    a, b, c = t[:, 0], t[:, 1], t[:, 2]
+    longest = np.sqrt(np.maximum(np.maximum(((b - a) ** 2).sum(1), ((c - b) ** 2).sum(1)), ((a - c) ** 2).sum(1)))
+    m = np.maximum(np.ceil(longest / spacing), 1.0)
+    total = float(((m + 1.0) * (m + 2.0) / 2.0).sum())
+    if total > MAX_FIT_POINTS:
+        raise ValueError(f"surface_points: {total:.0f} points at spacing {spacing!r}, more than 2^20: raise spacing")
+    m = m.astype(np.int64)
+    out = []
+    for mm in np.unique(m):
+        sel = m == mm
+        i, j = np.meshgrid(np.arange(mm + 1), np.arange(mm + 1), indexing="ij")
+        keep = (i + j) <= mm
+        u, v = i[keep] / float(mm), j[keep] / float(mm)  # [L]
+        p = (a[sel][:, None, :] + u[None, :, None] * (b[sel] - a[sel])[:, None, :]
+             + v[None, :, None] * (c[sel] - a[sel])[:, None, :])
+        out.append((np.nonzero(sel)[0], p))
+    # in triangle order
+    order = np.argsort(np.concatenate([k for k, _ in out]), kind="stable")
+    chunks = [row for _, p in out for row in p]
+    return np.ascontiguousarray(np.concatenate([chunks[k] for k in order], axis=0))
+
+
+def _box_soup(half):
+    hx, hy, hz = (float(v) for v in half)
+    v = np.array([[(hx if k & 1 else -hx), (hy if k & 2 else -hy), (hz if k & 4 else -hz)] for k in range(8)])
+    quads = [(0, 4, 6, 2), (1, 3, 7, 5), (0, 1, 5, 4), (2, 6, 7, 3), (0, 2, 3, 1), (4, 5, 7, 6)]  # outward
+    return np.array([[v[i], v[j], v[k]] for q in quads for i, j, k in ((q[0], q[1], q[2]), (q[0], q[2], q[3]))])
+
+
+def primitive_mesh(kind, size):
+    """The triangle soup [M, 3, 3] of a URDF collision primitive in its own frame, outward oriented: "box" with size
+    (x, y, z) full extents, centred; "cylinder" with size (radius, length), its axis along z, centred; "sphere" with
+    size (radius,) or a number.  Cylinder and sphere are tessellated with PRIMITIVE_SEGMENTS = 24 segments and
+    circumscribed: the polyhedron contains the true solid (every face plane is at least `radius` from the axis,
+    resp. the centre), so a cover of the polyhedron covers the solid."""
+    size = np.atleast_1d(np.asarray(size, dtype=np.float64)).ravel()
+    if not (np.isfinite(size).all() and (size > 0.0).all()):
+        raise ValueError(f"primitive_mesh: {kind} needs finite, positive dimensions, got {size.tolist()}")
+    N = PRIMITIVE_SEGMENTS
+    if kind == "box":
+        if size.shape != (3,):
+            raise ValueError("primitive_mesh: a box has size (x, y, z)")
+        return _box_soup(0.5 * size)
+    if kind == "cylinder":
+        if size.shape != (2,):
+            raise ValueError("primitive_mesh: a cylinder has size (radius, length)")
+        R, h = size[0] / math.cos(math.pi / N), 0.5 * size[1]
+        ang = 2.0 * math.pi * np.arange(N) / N
+        ring = np.stack([R * np.cos(ang), R * np.sin(ang)], 1)
+        tris = []
+        for k in range(N):
+            (x0, y0), (x1, y1) = ring[k], ring[(k + 1) % N]
+            tris += [[[x0, y0, -h], [x1, y1, -h], [x1, y1, h]], [[x0, y0, -h], [x1, y1, h], [x0, y0, h]],
+                     [[0.0, 0.0, h], [x0, y0, h], [x1, y1, h]], [[0.0, 0.0, -h], [x1, y1, -h], [x0, y0, -h]]]
+        return np.array(tris)
+    if kind == "sphere":
+        if size.shape != (1,):
+            raise ValueError("primitive_mesh: a sphere has size (radius,)")
+        nb = N // 2
+        lat = math.pi * np.arange(nb + 1) / nb  # polar angle, 0 .. pi
+        lon = 2.0 * math.pi * np.arange(N) / N
+
+        def pt(i, k):
+            return [math.sin(lat[i]) * math.cos(lon[k % N]), math.sin(lat[i]) * math.sin(lon[k % N]), math.cos(lat[i])]
+        tris = []
+        for i in range(nb):
+            for k in range(N):
+                p00, p01, p10, p11 = pt(i, k), pt(i, k + 1), pt(i + 1, k), pt(i + 1, k + 1)
+                if i > 0:
+                    tris.append([p00, p11, p01])
+                if i < nb - 1:
+                    tris.append([p00, p10, p11])
+        t = np.array(tris)
+        # the polyhedron is convex (its quads are planar trapezoids): it contains the ball whose radius is the
+        # smallest distance of a face plane from the centre
+        n = np.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0])
+        d = (n * t[:, 0]).sum(1) / np.linalg.norm(n, axis=1)
+        return t * (size[0] / float(d.min()))
+    raise ValueError(f"primitive_mesh: kind must be 'box', 'cylinder' or 'sphere', got {kind!r}")
+
+
+def _rpy_matrix(xyz, rpy):
+    r, p, y = (float(v) for v in rpy)
+    cr, sr, cp, sp, cy, sy = math.cos(r), math.sin(r), math.cos(p), math.sin(p), math.cos(y), math.sin(y)
+    T = np.eye(4)
+    T[:3, :3] = [[cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr],
+                 [sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr],
+                 [-sp, cp * sr, cp * cr]]
+    T[:3, 3] = [float(v) for v in xyz]
+    return T
+
+
+def _origin_of(elem):
+    o = elem.find("origin") if elem is not None else None
+    if o is None:
+        return np.eye(4)
+    return _rpy_matrix((o.get("xyz") or "0 0 0").split(), (o.get("rpy") or "0 0 0").split())
+
+
+def default_mesh_resolver(mesh_dir=None):
+    """filename -> path: a leading file:// is dropped, a package://name/ prefix is stripped, and what is left is taken
+    relative to `mesh_dir` (absolute paths stay)."""
+    import os
+
+    def resolve(filename):
+        f = filename
+        if f.startswith("file://"):
+            f = f[len("file://"):]
+        if f.startswith("package://"):
+            f = f[len("package://"):]
+            f = f.split("/", 1)[1] if "/" in f else ""
+        return f if os.path.isabs(f) or mesh_dir is None else os.path.join(mesh_dir, f)
+    return resolve
+
+
+def urdf_collision_geometry(urdf_text, base_link, ee_link, mesh_resolver=None, mesh_dir=None, on_missing="raise"):
+    """The <collision> geometry of a URDF along the chain base_link -> ee_link, by the chain's frames: (geometry,
+    report).  geometry is a list of (frame, kind, T_frame_geom [4, 4], data): kind "box" with data (x, y, z),
+    "cylinder" with (radius, length), "sphere" with (radius,), "mesh" with a triangle soup [M, 3, 3] (scale applied,
+    in the geometry's own frame); T_frame_geom places the geometry in the frame.
+
+    Frame 0 is the base link and frame k the child link of the k-th moving joint on the path (Robot's frames:
+    link_frames_batch_arrays).  A link behind fixed joints belongs to the frame of the last moving joint before it,
+    with the fixed transforms accumulated in the URDF's order; where the chain ends in fixed joints, the end link is
+    frame n + 1.  Links off the path that hang on a chain link through fixed joints only are included in that link's
+    frame; a subtree behind an off-path moving joint (gripper fingers) is skipped and listed in report["skipped"].
+
+    <mesh filename> is resolved by mesh_resolver(filename) -> path (default: default_mesh_resolver(mesh_dir)); only
+    .stl is read (load_stl).  Another format or a file that is missing raises ValueError naming the link; with
+    on_missing="skip" that geometry is left out and listed in report["skipped"].
+
+    report: "links" (the link of each geometry item), "frames" ({link: frame} of every link that was visited),
+    "skipped" (a list of {"link", "reason"}), "joint_origins" ([J, 4, 4]: per moving joint -- and the fixed tip, if
+    any -- the transform from the frame before it, fixed joints accumulated in the URDF's order: what the geometry
+    is placed by), "fold_order_differs" (the moving joints where the chain loader's fold of fixed joints, which
+    multiplies in the other order, gives another origin than the URDF's: there the solver's chain is not the
+    URDF's, and the geometry follows the URDF)."""
+    import xml.etree.ElementTree as ET
+    if on_missing not in ("raise", "skip"):
+        raise ValueError("on_missing must be 'raise' or 'skip'")
+    resolver = mesh_resolver or default_mesh_resolver(mesh_dir)
+    root = ET.fromstring(urdf_text)
+    links = {ln.get("name"): ln for ln in root.findall("link")}
+    for name in (base_link, ee_link):
+        if name not in links:
+            raise ValueError(f"link '{name}' does not exist")
+    joints = []
+    for j in root.findall("joint"):
+        joints.append(dict(name=j.get("name"), type=j.get("type"), parent=j.find("parent").get("link"),
+                           child=j.find("child").get("link"), T=_origin_of(j)))
+    children = {}
+    for k, j in enumerate(joints):
+        children.setdefault(j["parent"], []).append(k)
+    # breadth-first path, as the chain loader finds it
+    via = {base_link: None}
+    queue = [base_link]
+    while queue and ee_link not in via:
+        u = queue.pop(0)
+        for k in children.get(u, []):
+            if joints[k]["child"] not in via:
+                via[joints[k]["child"]] = k
+                queue.append(joints[k]["child"])
+    if ee_link not in via:
+        raise ValueError("no path from base to EE link")
+    path = []
+    u = ee_link
+    while via[u] is not None:
+        path.insert(0, via[u])
+        u = joints[via[u]]["parent"]
+    on_path = set(path)
+    n = sum(joints[k]["type"] != "fixed" for k in path)
+
+    placed = [(base_link, 0, np.eye(4))]  # (link, frame, T_frame_link) along the path
+    frame, T = 0, np.eye(4)
+    acc_true, acc_loader = np.eye(4), np.eye(4)
+    joint_origins, differs = [], []
+    for k in path:
+        j = joints[k]
+        if j["type"] == "fixed":
+            T = T @ j["T"]
+            acc_true, acc_loader = acc_true @ j["T"], j["T"] @ acc_loader
+        else:
+            frame += 1
+            origin_true, origin_loader = acc_true @ j["T"], j["T"] @ acc_loader
+            joint_origins.append(origin_true)
+            if not np.allclose(origin_true, origin_loader, rtol=0.0, atol=1e-12):
+                differs.append(j["name"])
+            T, acc_true, acc_loader = np.eye(4), np.eye(4), np.eye(4)
+        placed.append((j["child"], frame, T.copy()))
+    if path and joints[path[-1]]["type"] == "fixed" and not np.array_equal(acc_loader, np.eye(4)):
+        # the chain's fixed tip: the end link is frame n + 1
+        joint_origins.append(acc_true)
+        if not np.allclose(acc_true, acc_loader, rtol=0.0, atol=1e-12):
+            differs.append(joints[path[-1]]["name"])
+        placed[-1] = (ee_link, n + 1, np.eye(4))
+
+    report = dict(links=[], frames={}, skipped=[], joint_origins=np.array(joint_origins).reshape(-1, 4, 4),
+                  fold_order_differs=differs)
+    visit = []
+    for link, f, Tl in placed:
+        visit.append((link, f, Tl))
+        stack = [(link, f, Tl)]
+        while stack:  # off-path subtrees
+            u, fu, Tu = stack.pop()
+            for k in children.get(u, []):
+                if k in on_path:
+                    continue
+                j = joints[k]
+                if j["type"] == "fixed":
+                    item = (j["child"], fu, Tu @ j["T"])
+                    visit.append(item)
+                    stack.append(item)
+                else:
+                    report["skipped"].append(dict(link=j["child"], reason=f"behind the off-chain {j['type']} joint "
+                                                                          f"'{j['name']}': moving links off the chain are not modelled"))
+    geometry = []
+    for link, f, Tl in visit:
+        report["frames"][link] = f
+        for col in links[link].findall("collision") if link in links else []:
+            g = col.find("geometry")
+            shape = list(g)[0] if g is not None and len(g) else None
+            if shape is None:
+                continue
+            Tg = Tl @ _origin_of(col)
+            if shape.tag == "box":
+                item = ("box", np.array([float(v) for v in shape.get("size").split()]))
+            elif shape.tag == "cylinder":
+                item = ("cylinder", np.array([float(shape.get("radius")), float(shape.get("length"))]))
+            elif shape.tag == "sphere":
+                item = ("sphere", np.array([float(shape.get("radius"))]))
+            elif shape.tag == "mesh":
+                import os
+                filename = shape.get("filename") or ""
+                path_ = resolver(filename)
+                why = None
+                if not filename.lower().endswith(".stl"):
+                    why = f"link '{link}': collision mesh '{filename}' is not an .stl file (the only format read)"
+                elif not (path_ and os.path.isfile(path_)):
+                    why = f"link '{link}': collision mesh '{filename}' not found (looked for {path_!r})"
+                if why:
+                    if on_missing == "raise":
+                        raise ValueError(why)
+                    report["skipped"].append(dict(link=link, reason=why))
+                    continue
+                soup = load_stl(path_)
+                scale = np.array([float(v) for v in (shape.get("scale") or "1 1 1").split()])
+                item = ("mesh", soup * scale)
+            else:
+                report["skipped"].append(dict(link=link, reason=f"link '{link}': unknown geometry <{shape.tag}>"))
+                continue
+            geometry.append((f, item[0], Tg, item[1]))
+            report["links"].append(link)
+    return geometry, report
+
+
+def geometry_soup(kind, T, data):
+    """One item of urdf_collision_geometry as a triangle soup [M, 3, 3] in its frame (primitive_mesh, resp. the mesh
+    itself, moved by T)."""
+    soup = np.asarray(data, dtype=np.float64).reshape(-1, 3, 3) if kind == "mesh" else primitive_mesh(kind, data)
+    T = np.asarray(T, dtype=np.float64)
+    return soup @ T[:3, :3].T + T[:3, 3]
+
+
+def mid_configuration(robot):
+    """The middle of the joint range, [n] (a joint without finite limits: 0)."""
+    lb, ub = (np.asarray(v, dtype=np.float64) for v in robot.joint_limits())
+    mid = 0.5 * (lb + ub)
+    return np.where(np.isfinite(mid), mid, 0.0)
+
+
+def prune_pairs(robot, frames, centers, radii, pairs, configs=None, margin=0.0):
+    """(kept [Pk, 2], dropped [Pd, 2]) int32: `pairs` without the sphere pairs that overlap -- their distance less
+    the two radii is below `margin` -- at any of the reference configurations `configs` [B, n] (default: the middle
+    of the joint range).  Padded spheres on frames two apart can overlap in every configuration; a model that keeps
+    such a pair is always in self-collision.  A pair that overlaps at a configuration the robot may take is taken to
+    be of that kind: the reference configurations have to be free of real self-collision.  The frames come from
+    link_frames_batch_arrays (the GPU); the rest is numpy."""
+    pairs = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+    configs = mid_configuration(robot)[None] if configs is None else np.asarray(configs, dtype=np.float64)
+    configs = configs.reshape(-1, robot.num_positions())
+    overlap = np.zeros(len(pairs), dtype=bool)
+    for x in configs:
+        s = spheres_at(robot, x, frames, centers, radii)
+        d = np.linalg.norm(s[pairs[:, 0], :3] - s[pairs[:, 1], :3], axis=1) - s[pairs[:, 0], 3] - s[pairs[:, 1], 3]
+        overlap |= d < float(margin)
+    return np.ascontiguousarray(pairs[~overlap]), np.ascontiguousarray(pairs[overlap])

@@ -13,6 +13,7 @@
 #include "mesh_measure.hpp"
 #include "pose_convert.hpp"
 #include "robot_host.hpp"
+#include "spherefit_measure.hpp"
 
 using namespace optik::robot;
 using optik::pose::mat16_from_pose7;
@@ -389,6 +390,47 @@ int optik_robot_world_grid_from_mesh(const optik_robot *r, const double *origin3
     if (optik_hip_world_grid_from_mesh(c->chain, origin3, voxel, nx, ny, nz, d_tris, M, max_distance, d_out, nullptr))
         return set_err(-1, optik_hip_last_error());
     if (hipMemcpy(values_out, d_out, sizeof(float) * nodes, hipMemcpyDeviceToHost) != hipSuccess)
+        return set_err(-1, "download failed");
+    return 0;
+}
+
+int optik_robot_sphere_fit(const optik_robot *r, const double *origin3, double voxel, int32_t nx, int32_t ny, int32_t nz,
+                           const float *values, const double *points3, int64_t P, double pad, double slack, int32_t K,
+                           int32_t *chosen_out, double *centers_out, double *radii_out, int32_t *gains_out,
+                           int32_t *count_uncovered_out) {
+    if (!r || !values || !points3 || !chosen_out || !centers_out || !radii_out || !gains_out || !count_uncovered_out)
+        return set_err(-1, "null argument");
+    std::string err;
+    if (optik::coll::check_grid(origin3, voxel, nx, ny, nz, nullptr, false, err)
+        || optik::coll::check_fit(P, pad, slack, K, points3, err))
+        return set_err(-1, err);
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    BatchGuard guard(c);
+    if (!guard.ok()) return set_err(-1, kSetDeviceMsg);
+    const size_t nodes = (size_t)nx * (size_t)ny * (size_t)nz, k = (size_t)K;
+    const size_t ws = optik::coll::fit_workspace_bytes((int64_t)nodes, P);
+    // one block: the points, the centres and radii (doubles), then the values, the int32 outputs and the workspace
+    optik::DeviceBuf<uint8_t> block;
+    if (block.reserve(sizeof(double) * (3 * (size_t)P + 4 * k) + sizeof(float) * nodes + sizeof(int32_t) * (2 * k + 2) + ws)
+        != hipSuccess)
+        return set_err(-1, "sphere fit buffer allocation failed");
+    double *d_pts = reinterpret_cast<double *>(block.get());
+    double *d_cen = d_pts + 3 * (size_t)P, *d_rad = d_cen + 3 * k;
+    float *d_val = reinterpret_cast<float *>(d_rad + k);
+    int32_t *d_cho = reinterpret_cast<int32_t *>(d_val + nodes), *d_gai = d_cho + k, *d_cu = d_gai + k;
+    void *d_ws = d_cu + 2;
+    if (hipMemcpy(d_pts, points3, sizeof(double) * 3 * (size_t)P, hipMemcpyHostToDevice) != hipSuccess
+        || hipMemcpy(d_val, values, sizeof(float) * nodes, hipMemcpyHostToDevice) != hipSuccess)
+        return set_err(-1, "upload failed");
+    if (optik_hip_sphere_fit(c->chain, origin3, voxel, nx, ny, nz, d_val, d_pts, P, pad, slack, K, d_cho, d_cen, d_rad,
+                             d_gai, d_cu, d_ws, (int64_t)ws, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (hipMemcpy(centers_out, d_cen, sizeof(double) * 3 * k, hipMemcpyDeviceToHost) != hipSuccess
+        || hipMemcpy(radii_out, d_rad, sizeof(double) * k, hipMemcpyDeviceToHost) != hipSuccess
+        || hipMemcpy(chosen_out, d_cho, sizeof(int32_t) * k, hipMemcpyDeviceToHost) != hipSuccess
+        || hipMemcpy(gains_out, d_gai, sizeof(int32_t) * k, hipMemcpyDeviceToHost) != hipSuccess
+        || hipMemcpy(count_uncovered_out, d_cu, sizeof(int32_t) * 2, hipMemcpyDeviceToHost) != hipSuccess)
         return set_err(-1, "download failed");
     return 0;
 }

@@ -341,6 +341,46 @@ class HipChain:
                                                            min(M, (1 << 31) - 1), md, _ptr(out), _stream_ptr()))
         return out
 
+    # -- from a solid to a sphere model (include/optik_hip.h) ---------------------------------
+    def sphere_fit(self, values, origin, voxel, points, pad, slack, k):
+        """A greedy sphere cover (csrc/spherefit_measure.hpp) of the solid whose signed distance field is `values` (a
+        contiguous float32 cuda tensor [nx, ny, nz] on the grid (origin, voxel): what world_grid_from_mesh returns)
+        and whose surface is sampled by `points` (a contiguous float64 cuda tensor [P, 3]): up to k spheres with their
+        centres on grid nodes, each reaching at most `pad` beyond the solid, chosen one after the other to hold the
+        most points not held yet at least `slack` inside.  Returns a dict of cuda tensors: chosen int32 [k] (node
+        indices, -1 past the count), centers [k, 3], radii [k] (NaN past the count), gains int32 [k], count_uncovered
+        int32 [2].  Stream-ordered, no host synchronisation; the workspace is a torch allocation."""
+        from .collision import grid_arrays
+        v_t, p_t = values, points
+        if not (isinstance(v_t, torch.Tensor) and v_t.is_cuda and v_t.dtype == torch.float32 and v_t.dim() == 3
+                and v_t.is_contiguous()):
+            raise ValueError("values must be a contiguous float32 cuda tensor [nx, ny, nz]")
+        if not (isinstance(p_t, torch.Tensor) and p_t.is_cuda and p_t.dtype == torch.float64 and p_t.dim() == 2
+                and p_t.shape[1] == 3 and p_t.is_contiguous()):
+            raise ValueError("points must be a contiguous float64 cuda tensor [P, 3]")
+        o, v, _, (nx, ny, nz) = grid_arrays(origin, voxel, shape=tuple(v_t.shape))
+        P, K = int(p_t.shape[0]), int(k)
+        kk = K if 1 <= K <= nat.MAX_FIT_SPHERES else 1
+        out = dict(chosen=torch.empty(kk, dtype=torch.int32, device=self.device),
+                   centers=torch.empty((kk, 3), dtype=torch.float64, device=self.device),
+                   radii=torch.empty(kk, dtype=torch.float64, device=self.device),
+                   gains=torch.empty(kk, dtype=torch.int32, device=self.device),
+                   count_uncovered=torch.empty(2, dtype=torch.int32, device=self.device))
+        return self.sphere_fit_into(v_t, o, v, p_t, pad, slack, K, out)
+
+    def sphere_fit_into(self, values, origin, voxel, points, pad, slack, k, out):
+        """sphere_fit into the caller's tensors (`out`: the dict sphere_fit returns); returns `out`."""
+        nx, ny, nz = (int(s) for s in values.shape)
+        P = int(points.shape[0])
+        o = np.ascontiguousarray(origin, dtype=np.float64)
+        ws_bytes = int(nat.lib().optik_hip_sphere_fit_workspace_bytes(nx, ny, nz, P))
+        ws = torch.empty(max(ws_bytes, 4) // 4, dtype=torch.int32, device=self.device)
+        nat.check(nat.lib().optik_hip_sphere_fit(
+            self._h, _dp(o), float(voxel), nx, ny, nz, _ptr(values), _ptr(points) if P else None, P, float(pad),
+            float(slack), int(k), _ptr(out["chosen"]), _ptr(out["centers"]), _ptr(out["radii"]), _ptr(out["gains"]),
+            _ptr(out["count_uncovered"]), _ptr(ws), ws_bytes, _stream_ptr()))
+        return out
+
     def _check_q(self, q):
         if not (isinstance(q, torch.Tensor) and q.is_cuda and q.dtype == torch.float64 and q.dim() == 2
                 and q.shape[0] == self.n and q.is_contiguous()):

@@ -56,6 +56,8 @@ def _bind(L):
                                                  C.c_int32, vp]
     L.optik_robot_world_grid_from_mesh.argtypes = [vp, dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32,
                                                    C.c_double, vp]
+    L.optik_robot_sphere_fit.argtypes = [vp, dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, vp, dp, C.c_int64,
+                                         C.c_double, C.c_double, C.c_int32, ip, dp, dp, ip, ip]
     L.optik_robot_link_frames_batch.argtypes = [vp, C.c_int64, dp, dp, dp]
     L.optik_robot_collision_batch.argtypes = [vp, C.c_int64, dp, dp, dp, C.POINTER(C.c_uint8)]
     L.optik_robot_collision_motion_batch.argtypes = [vp, C.c_int64, dp, dp, C.c_double, dp, dp, C.POINTER(C.c_uint8),
@@ -798,6 +800,133 @@ class Robot:
         values = self.world_grid_from_mesh(origin, voxel, shape, vertices, triangles, max_distance)
         self.set_world_grid(origin, voxel, values)
         return values
+
+    # -- sphere models from collision geometry (extension; include/optik.h) --------------------
+    def sphere_fit_arrays(self, values, origin, voxel, points, pad, slack, k):
+        """optik_robot_sphere_fit on host arrays (csrc/spherefit_measure.hpp): values [nx, ny, nz] float32, a signed
+        distance field on the grid (origin, voxel); points [P, 3] on the solid's surface.  Returns (chosen int32 [k],
+        centers [k, 3], radii [k], gains int32 [k], count, uncovered).  ValueError for a refusal."""
+        from .collision import cloud_arrays, grid_arrays
+        o, v, vals, (nx, ny, nz) = grid_arrays(origin, voxel, values)
+        pts, _ = cloud_arrays(points)
+        K = int(k)
+        kk = K if 1 <= K <= nat.MAX_FIT_SPHERES else 1
+        chosen, gains, cu = np.zeros(kk, dtype=np.int32), np.zeros(kk, dtype=np.int32), np.zeros(2, dtype=np.int32)
+        centers, radii = np.zeros((kk, 3)), np.zeros(kk)
+        ip = C.POINTER(C.c_int32)
+        if self._L.optik_robot_sphere_fit(self._h, _dp(o), v, nx, ny, nz, C.c_void_p(vals.ctypes.data),
+                                          _dp(pts) if len(pts) else _dp(np.zeros(3)), len(pts), float(pad),
+                                          float(slack), K, chosen.ctypes.data_as(ip), _dp(centers), _dp(radii),
+                                          gains.ctypes.data_as(ip), cu.ctypes.data_as(ip)):
+            raise ValueError(_err(self._L))
+        return chosen, centers, radii, gains, int(cu[0]), int(cu[1])
+
+    def fit_spheres(self, vertices, triangles=None, count=8, voxel=None, pad=None, spacing=None):
+        """From a closed triangle mesh (as world_grid_from_mesh takes it, in any frame) to at most `count` spheres
+        that contain its surface and stay within `pad` of the solid, on the GPU: (centers [S, 3], radii [S], info).
+        The steps: optik_amd.collision.surface_points samples the surface at `spacing`; the grid is the bounding box
+        grown by `pad` at `voxel`; world_grid_from_mesh gives the solid's signed distance there; the greedy cover of
+        csrc/spherefit_measure.hpp picks the spheres -- centres on grid nodes, radius pad - (the distance at the
+        node), each round the sphere that holds the most samples not held yet at least slack = spacing inside.
+
+        Defaults (optik_amd.collision.fit_defaults; nobody has measured better ones): voxel = the bounding box's
+        longest side / 10, spacing = voxel / 2, pad = 1.01 * (sqrt(3) * voxel + spacing) = 0.225 of that side: coarse,
+        so that a handful of spheres covers a simple solid (a bar 4, a cylinder 5, a cube 25 for uncovered == 0); a
+        smaller voxel hugs the solid and needs many more spheres.
+        pad >= sqrt(3) * voxel + spacing is required: with it every sample can be covered, and info["uncovered"] == 0
+        then means that the whole surface lies inside the spheres (every surface point is within `spacing` of a
+        sample that lies `spacing` inside a sphere) while no sphere reaches further than `pad` outside the solid, up
+        to the float32 rounding of the field.  With uncovered > 0 the model is NOT conservative: raise `count`, or
+        raise `voxel` (fewer, larger spheres that stick out further).  An open sheet has no inside: it gets spheres
+        of radius <= pad along it.
+
+        info: uncovered, points (the samples), gains (the samples each sphere newly held), voxel, pad, slack, origin
+        and shape of the grid, chosen (the node indices).  The fit does not read the chain.  ValueError for a refused
+        mesh, grid (more than 1024 nodes per axis or 2^24 in all: raise voxel), count outside 1..256 or more than
+        2^20 samples."""
+        from .collision import fit_defaults, fit_grid, mesh_arrays, surface_points
+        if not 1 <= int(count) <= nat.MAX_FIT_SPHERES:
+            raise ValueError(f"sphere fit: K must be in 1..256, got {count}")
+        tris = mesh_arrays(vertices, triangles)
+        if len(tris) == 0 or not np.isfinite(tris).all():
+            raise ValueError("fit_spheres: the mesh needs at least one triangle and finite coordinates")
+        v3 = tris.reshape(-1, 3)
+        lo, hi = v3.min(0), v3.max(0)
+        voxel, pad, spacing = fit_defaults(float((hi - lo).max()), voxel, pad, spacing)
+        origin, shape = fit_grid(lo, hi, voxel, pad)
+        pts = surface_points(tris, None, spacing)
+        values = self.world_grid_from_mesh(origin, voxel, shape, tris)
+        chosen, centers, radii, gains, cnt, unc = self.sphere_fit_arrays(values, origin, voxel, pts, pad, spacing, count)
+        info = dict(uncovered=unc, points=len(pts), gains=gains[:cnt].copy(), voxel=voxel, pad=pad, slack=spacing,
+                    origin=origin, shape=shape, chosen=chosen[:cnt].copy())
+        return centers[:cnt].copy(), radii[:cnt].copy(), info
+
+    def fit_collision_model(self, geometry, per_link=8, voxel=None, pad=None, spacing=None):
+        """From collision geometry by frame (optik_amd.collision.urdf_collision_geometry's list of (frame, kind,
+        T_frame_geom, data)) to a sphere model: (frames int32 [S], centers [S, 3], radii [S], report) for
+        set_collision_model.  All boxes, cylinders and meshes of one frame are merged into one triangle soup (cylinders
+        circumscribed: optik_amd.collision.primitive_mesh) and fitted once with fit_spheres(count=per_link; voxel, pad
+        and spacing as given, by default from that frame's own bounding box); a <sphere> is passed through as itself.
+        report: {frame: fit_spheres' info} under "fits", "uncovered" (the sum), "spheres_per_frame".  ValueError when
+        the model would have more than 256 spheres: lower per_link."""
+        from .collision import MAX_SPHERES, geometry_soup
+        by_frame = {}
+        for frame, kind, T, data in geometry:
+            by_frame.setdefault(int(frame), []).append((kind, np.asarray(T, dtype=np.float64), data))
+        frames, centers, radii = [], [], []
+        report = dict(fits={}, uncovered=0, spheres_per_frame={})
+        for frame in sorted(by_frame):
+            soups, before = [], len(frames)
+            for kind, T, data in by_frame[frame]:
+                if kind == "sphere":
+                    frames.append(frame)
+                    centers.append(T[:3, 3].copy())
+                    radii.append(float(np.atleast_1d(data)[0]))
+                else:
+                    soups.append(geometry_soup(kind, T, data))
+            if soups:
+                c, r, info = self.fit_spheres(np.concatenate(soups), None, per_link, voxel, pad, spacing)
+                frames += [frame] * len(r)
+                centers += list(c)
+                radii += list(r)
+                report["fits"][frame] = info
+                report["uncovered"] += info["uncovered"]
+            report["spheres_per_frame"][frame] = len(frames) - before
+        if len(frames) > MAX_SPHERES:
+            raise ValueError(f"fit_collision_model: {len(frames)} spheres, more than the {MAX_SPHERES} a collision model "
+                             f"may have: lower per_link (now {per_link})")
+        return (np.array(frames, dtype=np.int32), np.array(centers, dtype=np.float64).reshape(-1, 3),
+                np.array(radii, dtype=np.float64), report)
+
+    def set_collision_model_from_urdf(self, urdf_path, base_link, ee_link, per_link=8, margin=0.0, self_pairs="auto",
+                                      reference=None, mesh_dir=None, mesh_resolver=None, on_missing="raise",
+                                      voxel=None, pad=None, spacing=None):
+        """Reads the URDF's <collision> geometry along the chain (optik_amd.collision.urdf_collision_geometry; meshes
+        relative to mesh_dir, by default the URDF's directory), fits spheres to it frame by frame
+        (fit_collision_model) and installs them with set_collision_model.  self_pairs "auto": every pair whose frames
+        differ by >= 2, without those that overlap at the `reference` configurations ([B, n]; default: the middle of
+        the joint range) -- optik_amd.collision.prune_pairs: padded spheres around a joint overlap in every
+        configuration; None or [P, 2] as set_collision_model takes them.  Returns (frames, centers, radii, report);
+        report adds "geometry" (urdf_collision_geometry's report), "pairs" and "pairs_dropped"."""
+        import os
+        from .collision import auto_pairs, prune_pairs, urdf_collision_geometry
+        with open(urdf_path) as fh:
+            text = fh.read()
+        if mesh_dir is None:
+            mesh_dir = os.path.dirname(os.path.abspath(urdf_path))
+        geometry, greport = urdf_collision_geometry(text, base_link, ee_link, mesh_resolver, mesh_dir, on_missing)
+        if not geometry:
+            raise ValueError("set_collision_model_from_urdf: the chain's links have no collision geometry that was read")
+        frames, centers, radii, report = self.fit_collision_model(geometry, per_link, voxel, pad, spacing)
+        report["geometry"] = greport
+        if isinstance(self_pairs, str) and self_pairs == "auto":
+            pairs, dropped = prune_pairs(self, frames, centers, radii, auto_pairs(frames), reference, margin)
+        else:
+            pairs, dropped = self_pairs, np.zeros((0, 2), dtype=np.int32)
+        self.set_collision_model(frames, centers, radii, pairs, margin)
+        report["pairs"] = pairs
+        report["pairs_dropped"] = dropped
+        return frames, centers, radii, report
 
     def _check_xs(self, xs):
         n = self.num_positions()
