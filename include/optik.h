@@ -335,6 +335,21 @@ int optik_robot_rrt_plan(const optik_robot *robot, const double *starts, const d
                          double step, double resolution, uint64_t first, int32_t max_nodes, int32_t Lmax, int32_t poll,
                          const double *ee_offset16, double *paths_out, int32_t *len_out, double *cost_out,
                          int32_t *status_out, int32_t *iters_out, int32_t *nodes_out);
+/* The tree planner with a goal set (extension; include/optik_hip.h: optik_hip_rrt_plan_goals):
+ * optik_robot_rrt_plan with goals [Q][G][n] row-major, 1 <= G <= 16, and counts [Q] (NULL: G each): query q has the
+ * goals g < counts[q] only, nothing of the others influences an output (the NaN rows of optik_robot_ik_solutions past
+ * its count are the normal input), and counts[q] = 0 is status 1.  Tree 1 has one root per counted goal that is free;
+ * the query ends at the first junction with any of them -- past the direct motions, where the nearest free one wins and
+ * a tie goes to the lower goal, the answer is the goal joined first, not the cheapest.  max_nodes in max(2, G) ..
+ * 4096.  Outputs as optik_robot_rrt_plan's, and goal_out [Q]: the goal reached for status 0, -1 otherwise.  A found
+ * path ends in that goal; any other is the start, then goal 0 repeated (the start repeated without goals).  It reads no
+ * roadmap and keeps no state in the robot.  Queries run in chunks of 4 096.  rc 0, or -1: null argument, G out of
+ * range, what the kernel layer refuses. */
+int optik_robot_rrt_plan_goals(const optik_robot *robot, const double *starts, const double *goals,
+                               const int32_t *counts, int32_t G, int64_t Q, int32_t iters, double step,
+                               double resolution, uint64_t first, int32_t max_nodes, int32_t Lmax, int32_t poll,
+                               const double *ee_offset16, double *paths_out, int32_t *len_out, double *cost_out,
+                               int32_t *status_out, int32_t *iters_out, int32_t *nodes_out, int32_t *goal_out);
 /* Shortcutting and resampling planned paths (extension; include/optik_hip.h: optik_hip_path_shortcut and
  * optik_hip_path_resample).  paths [P][L][n] row-major with lens [P] waypoints each (NULL: L
  * each), 2 <= L <= 64 -- optik_robot_roadmap_plan's paths_out and len_out as they are.

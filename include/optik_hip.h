@@ -405,6 +405,41 @@ int optik_hip_rrt_plan(optik_hip_chain *chain, const double *ee_offset7, const d
                        int32_t *d_iters, int32_t *d_nodes, void *stream);
 int64_t optik_hip_rrt_chunk(const optik_hip_chain *chain, int32_t max_nodes);
 
+/* The tree planner with a goal set (extension; the rules and their operation order:
+ * csrc/rrt_goals_measure.hpp): optik_hip_rrt_plan with G goal slots per query, 1 <= G <= OPTIK_HIP_RRT_MAX_GOALS, in
+ * place of the one goal -- the IK solutions of a pose, for one.  d_goals [G][n][Q]; d_gcount [Q] int32: only the goals
+ * g < gcount exist (a count outside 0 .. G is clamped), and NOTHING of the others influences any output, so the NaN
+ * rows optik_hip_ik_solutions leaves past its count are the normal input.  Tree 1 has one root per counted goal that
+ * is free, and the query ends at the FIRST junction with any of them: past the direct motions the answer is the goal
+ * joined first, not the cheapest one.
+ * Before iteration 0, in this order: a NaN or infinite joint in the start or in any counted goal gives status 3 (cost
+ * NaN); gcount = 0 status 1; a start that is not free by optik_hip_collision_batch status 1; the counted goals that
+ * are free become the roots of tree 1 in ascending g, nodes 0 .. R - 1 with parent -1; R = 0 gives status 1; among the
+ * roots whose direct motion start -> goal is free the one with the smallest distance, a tie going to the lower g,
+ * gives status 0 with len 2 and which = that g.  iters is 0 and the trees are empty (nodes 0) in all of these.
+ * The iterations are optik_hip_rrt_plan's, by the same kernel: nearest, steer, extend, connect and the
+ * back-extension.  A tree holds at most max_nodes nodes and the roots count, so a tree 1 full of roots never grows.
+ * A found path is tree 0 from its root to its junction node, then tree 1 from its junction node up the parent links to
+ * a root; d_which [Q] int32 is the goal slot of that root for status 0 and -1 otherwise (also for status 2, which
+ * keeps the cost).  The path is padded with goal `which` for status 0; any other is the start, then goal 0 repeated
+ * (the start repeated for gcount = 0), len 2.  The other outputs, the workspace, the chunks (optik_hip_rrt_chunk: the
+ * trees are the same size) and the polling are optik_hip_rrt_plan's; any output may be NULL.  With G = 1 and gcount =
+ * 1 every output equals optik_hip_rrt_plan's bit for bit, and which is 0 where the status is 0.  A query's result
+ * does not depend on Q, on the chunking, on `poll` or on a launch shape, and is bit for bit rrt_goals_measure.hpp's
+ * serial reference given the same samples and verdicts.
+ * Before iteration 0 the call classifies (1 + G) Q configurations in one optik_hip_collision_batch call -- a slot that
+ * is not counted goes in as the start again -- and G Q direct motions in one optik_hip_collision_motion_batch call, a
+ * slot that is not counted as a NaN segment, which is not sampled; no flag of such a slot is read.
+ * Refused with OPTIK_HIP_EINVAL before any device work: G outside 1 .. 16, max_nodes outside max(2, G) ..
+ * OPTIK_HIP_RRT_MAX_NODES, and what optik_hip_rrt_plan refuses; with OPTIK_HIP_EUNSUPPORTED, also when Q = 0: chains
+ * with prismatic joints.  Q = 0 is otherwise a no-op.  One call per chain handle at a time. */
+#define OPTIK_HIP_RRT_MAX_GOALS 16
+int optik_hip_rrt_plan_goals(optik_hip_chain *chain, const double *ee_offset7, const double *d_start,
+                             const double *d_goals, const int32_t *d_gcount, int64_t Q, int32_t G, int32_t iters,
+                             double step, double resolution, uint64_t first, int32_t max_nodes, int32_t Lmax,
+                             int32_t poll, double *d_path, int32_t *d_len, double *d_cost, int32_t *d_status,
+                             int32_t *d_iters, int32_t *d_nodes, int32_t *d_which, void *stream);
+
 /* Path shortcutting and equal-spacing resampling (extension; the arithmetic and its operation
  * order: csrc/shortcut_measure.hpp).  Paths are d_path [Lin][P][n] -- the layout optik_hip_roadmap_query writes and
  * optik_hip_path_optimize reads --, path p having d_len[p] waypoints (d_len NULL: Lin each) and padding behind them

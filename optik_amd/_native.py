@@ -180,6 +180,8 @@ def lib():
                                                          vp] + query_args
     L.optik_hip_rrt_plan.argtypes = [vp, dp, vp, vp, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_uint64, C.c_int32,
                                      C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
+    L.optik_hip_rrt_plan_goals.argtypes = [vp, dp, vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                           C.c_uint64, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.optik_hip_rrt_chunk.argtypes = [vp, C.c_int32]
     L.optik_hip_rrt_chunk.restype = C.c_int64
     L.optik_hip_path_shortcut.argtypes = [vp, dp, vp, vp, C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_double,
@@ -392,6 +394,21 @@ def check_rrt_args(iters=1, step=1.0, max_nodes=2, max_waypoints=2, poll=1, firs
     if not (math.isfinite(step) and step > 0.0):
         raise ValueError(f"step must be finite and > 0, got {step!r}")
     return int(iters), step, int(max_nodes), int(poll), int(first)
+
+
+# include/optik_hip.h: OPTIK_HIP_RRT_MAX_GOALS, the goal slots of optik_hip_rrt_plan_goals
+RRT_MAX_GOALS = 16
+
+
+def check_rrt_goals(G, max_nodes):
+    """The goal slots of a tree plan with a goal set as an int: an integer in 1 .. RRT_MAX_GOALS, and no more than
+    max_nodes (already checked by check_rrt_args), since every goal may be a root of tree 1."""
+    if isinstance(G, bool) or int(G) != G or not 1 <= int(G) <= RRT_MAX_GOALS:
+        raise ValueError(f"a goal set has 1 .. {RRT_MAX_GOALS} goals per query, got {G!r}")
+    if max_nodes < int(G):
+        raise ValueError(f"max_nodes must be an integer in max(2, G) = {max(2, int(G))} .. {RRT_MAX_NODES}, "
+                         f"got {max_nodes!r}")
+    return int(G)
 
 
 def rrt_chunk(chain_handle, max_nodes):

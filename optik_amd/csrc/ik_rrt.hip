@@ -25,14 +25,16 @@
 // iteration i + 1 are one kernel, so an iteration is that kernel and the motion check's five.  No kernel waits for
 // another workgroup; every loop's trip count is bounded by a tree's size, n or Lmax.  The loop over the iterations
 // runs on the host; every `poll` iterations it reads one int32, the count of the queries that have not ended.
+// The launch record and that loop (rrtdev::run_iterations, defined here) are declared in rrt_device.hpp:
+// ik_rrt_goals.hip runs the same loop, and so rrt_step_kernel as it is, on trees with several goal roots.
 #include <algorithm>
 
-#include "collision_device.hpp"
-#include "rrt_measure.hpp"
+#include "rrt_device.hpp"
 
 using namespace optik;
 using namespace optik::host;
 using namespace optik::colldev;
+using namespace optik::rrtdev;
 
 static_assert(rrt::MAX_NODES == OPTIK_HIP_RRT_MAX_NODES && rrt::MAX_ITERS == OPTIK_HIP_RRT_MAX_ITERS
                   && rrt::MAX_POLL == OPTIK_HIP_RRT_MAX_POLL
@@ -41,38 +43,7 @@ static_assert(rrt::MAX_NODES == OPTIK_HIP_RRT_MAX_NODES && rrt::MAX_ITERS == OPT
 
 namespace {
 
-constexpr int RRT_BLOCK = 256, RRT_WAVE = 64;
-constexpr long long MAX_QUERIES = 1ll << 30;
-
-struct RrtLaunch {
-    long long Q, q0, Qc;         // the call's queries; the chunk's first and its count
-    int n, M, Lmax, I, iter;
-    double eta;
-    const double *start, *goal;  // [n][Q] the caller's
-    const double *lo, *hi;       // [n] the joint limits (the chain's table)
-    const double *samples;       // [n][I]
-    double *s, *g;               // [n][Qc] the chunk's ends
-    const uint8_t *flags;        // begin: [3][Qc] start free, goal free, direct free; step: [3][Qc] the segments' flags
-    double *conf;                // [Qc][2][n][M]
-    int32_t *parent;             // [Qc][2][M]
-    int32_t *count;              // [2][Qc]
-    int32_t *state;              // [Qc] rrt::RUNNING or how the query ended
-    int32_t *junction;           // [2][Qc]
-    int32_t *used;               // [Qc]
-    int32_t *pend;               // [3][Qc] the iteration in flight: p (-1: none), m, whether tree b extends
-    double *qa, *qb;             // [n][3 Qc] the segments, column s * Qc + q
-    int32_t *unfinished;         // [1]
-    double *path;                // [Lmax][Q][n] or null
-    int32_t *len, *status, *iters, *nodes;  // [Q], nodes [2][Q]; or null
-    double *cost;
-};
-
-__device__ __forceinline__ double *tree_conf(const RrtLaunch &a, long long q, int t) {
-    return a.conf + ((size_t)q * 2 + t) * (size_t)a.n * a.M;
-}
-__device__ __forceinline__ int32_t *tree_parent(const RrtLaunch &a, long long q, int t) {
-    return a.parent + ((size_t)q * 2 + t) * (size_t)a.M;
-}
+// (the launch record RrtLaunch, tree_conf, tree_parent and clear_segments: rrt_device.hpp)
 
 __global__ __launch_bounds__(RRT_BLOCK) void rrt_gather_kernel(const RrtLaunch a) {
     const long long q = (long long)blockIdx.x * RRT_BLOCK + threadIdx.x;
@@ -80,15 +51,6 @@ __global__ __launch_bounds__(RRT_BLOCK) void rrt_gather_kernel(const RrtLaunch a
     for (int i = 0; i < a.n; ++i) {
         a.s[(long long)i * a.Qc + q] = a.start[(long long)i * a.Q + a.q0 + q];
         a.g[(long long)i * a.Qc + q] = a.goal[(long long)i * a.Q + a.q0 + q];
-    }
-}
-
-// every segment of query q is "not sampled" from here on
-__device__ __forceinline__ void clear_segments(const RrtLaunch &a, long long q, int i) {
-    const long long B = 3 * a.Qc;
-    for (int s = 0; s < 3; ++s) {
-        a.qa[(long long)i * B + s * a.Qc + q] = roadmap::nan_value();
-        a.qb[(long long)i * B + s * a.Qc + q] = roadmap::nan_value();
     }
 }
 
@@ -330,10 +292,11 @@ __global__ __launch_bounds__(RRT_WAVE) void rrt_walk_kernel(const RrtLaunch a) {
     }
 }
 
-inline unsigned blocks(long long work) { return (unsigned)((work + RRT_BLOCK - 1) / RRT_BLOCK); }
-inline size_t align16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+}  // namespace
 
-// what the call refuses before any device work; 0 to go on
+namespace optik {
+namespace rrtdev {
+
 int check_args(const optik_hip_chain *ch, int64_t Q, int32_t iters, double step, double resolution, int32_t max_nodes,
                int32_t Lmax, int32_t poll) {
     if (!ch || Q < 0) return fail(OPTIK_HIP_EINVAL, "bad argument");
@@ -352,7 +315,39 @@ int check_args(const optik_hip_chain *ch, int64_t Q, int32_t iters, double step,
                                             nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
-}  // namespace
+int run_iterations(optik_hip_chain *ch, const double *ee_offset7, RrtLaunch &a, int32_t iters, int32_t poll,
+                   double resolution, uint8_t *d_flags, hipStream_t stream) {
+    const long long L = a.Qc;
+    bool ended = false;
+    for (int32_t i = 0; i < iters; ++i) {
+        a.iter = i;
+        {
+            BIND_DEVICE(ch);
+            hipLaunchKernelGGL(rrt_step_kernel, dim3((unsigned)L), dim3(RRT_WAVE), 0, stream, a);
+            HIP_TRY(hipGetLastError());
+            if (i % poll == 0) {
+                // (the one synchronise of a poll: the host decides whether the iterations go on)
+                int32_t left = 0;
+                HIP_TRY(hipMemcpyAsync(&left, a.unfinished, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+                HIP_TRY(hipStreamSynchronize(stream));
+                if (left <= 0) { ended = true; break; }
+            }
+        }
+        if (int rc = optik_hip_collision_motion_batch(ch, ee_offset7, a.qa, a.qb, 3 * L, resolution, nullptr, d_flags,
+                                                      nullptr, nullptr, stream))
+            return rc;
+    }
+    BIND_DEVICE(ch);
+    if (!ended) {
+        a.iter = iters;  // (the last iteration's commit, and rule 6)
+        hipLaunchKernelGGL(rrt_step_kernel, dim3((unsigned)L), dim3(RRT_WAVE), 0, stream, a);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // namespace rrtdev
+}  // namespace optik
 
 extern "C" {
 
@@ -433,30 +428,8 @@ int optik_hip_rrt_plan(optik_hip_chain *ch, const double *ee_offset7, const doub
             hipLaunchKernelGGL(rrt_begin_kernel, dim3(blocks(L)), dim3(RRT_BLOCK), 0, stream, a);
             HIP_TRY(hipGetLastError());
         }
-        bool ended = false;
-        for (int32_t i = 0; i < iters; ++i) {
-            a.iter = i;
-            {
-                BIND_DEVICE(ch);
-                hipLaunchKernelGGL(rrt_step_kernel, dim3((unsigned)L), dim3(RRT_WAVE), 0, stream, a);
-                HIP_TRY(hipGetLastError());
-                if (i % poll == 0) {
-                    // (the one synchronise of a poll: the host decides whether the iterations go on)
-                    int32_t left = 0;
-                    HIP_TRY(hipMemcpyAsync(&left, a.unfinished, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-                    HIP_TRY(hipStreamSynchronize(stream));
-                    if (left <= 0) { ended = true; break; }
-                }
-            }
-            if (int rc = optik_hip_collision_motion_batch(ch, ee_offset7, a.qa, a.qb, 3 * L, resolution, nullptr,
-                                                          d_flags, nullptr, nullptr, stream))
-                return rc;
-        }
+        if (int rc = run_iterations(ch, ee_offset7, a, iters, poll, resolution, d_flags, stream)) return rc;
         BIND_DEVICE(ch);
-        if (!ended) {
-            a.iter = iters;  // (the last iteration's commit, and rule 6)
-            hipLaunchKernelGGL(rrt_step_kernel, dim3((unsigned)L), dim3(RRT_WAVE), 0, stream, a);
-        }
         hipLaunchKernelGGL(rrt_walk_kernel, dim3((unsigned)L), dim3(RRT_WAVE), 0, stream, a);
         HIP_TRY(hipGetLastError());
     }

@@ -126,6 +126,74 @@ inline void steer(int n, const double *p, const double *x, double d, double eta,
     for (int i = 0; i < n; ++i) c[i] = steer_joint(p[i], x[i], d, eta, lo[i], hi[i]);
 }
 
+// Rules 3 and 4 for the iterations 0 .. I - 1 over two trees that hold their roots (tree 1 may hold several:
+// rrt_goals_measure.hpp); motions_free as below.  Leaves the junction, iters_used and FOUND or NO_ROUTE in res.
+template <class MotionsFree>
+inline void grow_reference(Tree *tree, int n, const double *lo, const double *hi, const double *samples, int I,
+                           double eta, int M, MotionsFree &&motions_free, Result &res) {
+    double *seg = new double[6 * (size_t)n];
+    double *c = seg, *e = seg + n;             // the candidates
+    double *qa = seg + 2 * n, *qb = seg + 4 * n;  // two segments each
+    for (int i = 0; i < I && res.status == RUNNING; ++i) {
+        res.iters_used = i + 1;
+        const int a = i & 1, b = 1 - a;
+        const double *r = samples + (size_t)i * n;
+        double d;
+        const int p = tree[a].nearest(r, &d);
+        if (!steers(d) || tree[a].count >= M) continue;
+        steer(n, tree[a].node(p), r, d, eta, lo, hi, c);
+        unsigned char ok[2] = {0, 0};
+        for (int j = 0; j < n; ++j) {
+            qa[j] = a == 0 ? tree[a].node(p)[j] : c[j];
+            qb[j] = a == 0 ? c[j] : tree[a].node(p)[j];
+        }
+        motions_free(1, qa, qb, ok);
+        if (!ok[0]) continue;
+        double dm;
+        const int m = tree[b].nearest(c, &dm);  // (tree b as it was: c goes to tree a)
+        tree[a].append(c, p);
+        const double *qm = tree[b].node(m);
+        const bool back = extends_back(dm, eta, tree[b].count, M);
+        if (back) steer(n, qm, c, dm, eta, lo, hi, e);
+        for (int j = 0; j < n; ++j) {
+            qa[j] = a == 0 ? c[j] : qm[j];
+            qb[j] = a == 0 ? qm[j] : c[j];
+            // (tree b's travel direction is tree a's reversed)
+            qa[n + j] = b == 0 ? qm[j] : e[j];
+            qb[n + j] = b == 0 ? e[j] : qm[j];
+        }
+        ok[0] = ok[1] = 0;
+        motions_free(back ? 2 : 1, qa, qb, ok);
+        if (ok[0]) {
+            res.junction[a] = tree[a].count - 1;
+            res.junction[b] = m;
+            res.status = FOUND;
+        } else if (back && ok[1]) {
+            tree[b].append(e, m);
+        }
+    }
+    delete[] seg;
+    if (res.status == RUNNING) res.status = NO_ROUTE;
+}
+
+// Rule 5 for a query with a junction: order [2 M + 2] receives the waypoints, node v of tree 0 or M + v of tree 1, the
+// start first and the root that tree 1's branch ends in last; conf [2][M][n] the trees'.  Sets the cost and the
+// status; returns W.
+inline long long route_reference(const Tree *tree, int n, int M, int Lmax, const double *conf, Result &res, int *order) {
+    int d0 = 0;
+    for (int v = res.junction[0]; v >= 0; v = tree[0].parent[v]) ++d0;
+    int t = d0;
+    for (int v = res.junction[0]; v >= 0; v = tree[0].parent[v]) order[--t] = v;
+    long long W = d0;
+    for (int v = res.junction[1]; v >= 0; v = tree[1].parent[v]) order[W++] = M + v;
+    double cost = 0.0;
+    for (long long t2 = 0; t2 + 1 < W; ++t2)
+        cost = cost + motion::motion_distance(n, conf + (size_t)order[t2] * n, 1, conf + (size_t)order[t2 + 1] * n, 1);
+    res.cost = cost;
+    res.status = found_status(W, Lmax);
+    return W;
+}
+
 // config_free(q [n]) -> bool; motions_free(count, qa [count][n], qb [count][n], free_out [count]): the motion check of
 // qa -> qb, as given.  samples [I][n].  conf [2][M][n] and parent [2][M] receive the trees; path_out [Lmax][n].
 template <class ConfigFree, class MotionsFree>
@@ -145,49 +213,7 @@ inline Result plan_reference(int n, const double *lo, const double *hi, const do
     if (res.status == RUNNING) {
         tree[0].append(start, -1);
         tree[1].append(goal, -1);
-        double *seg = new double[6 * (size_t)n];
-        double *c = seg, *e = seg + n;             // the candidates
-        double *qa = seg + 2 * n, *qb = seg + 4 * n;  // two segments each
-        for (int i = 0; i < I && res.status == RUNNING; ++i) {
-            res.iters_used = i + 1;
-            const int a = i & 1, b = 1 - a;
-            const double *r = samples + (size_t)i * n;
-            double d;
-            const int p = tree[a].nearest(r, &d);
-            if (!steers(d) || tree[a].count >= M) continue;
-            steer(n, tree[a].node(p), r, d, eta, lo, hi, c);
-            unsigned char ok[2] = {0, 0};
-            for (int j = 0; j < n; ++j) {
-                qa[j] = a == 0 ? tree[a].node(p)[j] : c[j];
-                qb[j] = a == 0 ? c[j] : tree[a].node(p)[j];
-            }
-            motions_free(1, qa, qb, ok);
-            if (!ok[0]) continue;
-            double dm;
-            const int m = tree[b].nearest(c, &dm);  // (tree b as it was: c goes to tree a)
-            tree[a].append(c, p);
-            const double *qm = tree[b].node(m);
-            const bool back = extends_back(dm, eta, tree[b].count, M);
-            if (back) steer(n, qm, c, dm, eta, lo, hi, e);
-            for (int j = 0; j < n; ++j) {
-                qa[j] = a == 0 ? c[j] : qm[j];
-                qb[j] = a == 0 ? qm[j] : c[j];
-                // (tree b's travel direction is tree a's reversed)
-                qa[n + j] = b == 0 ? qm[j] : e[j];
-                qb[n + j] = b == 0 ? e[j] : qm[j];
-            }
-            ok[0] = ok[1] = 0;
-            motions_free(back ? 2 : 1, qa, qb, ok);
-            if (ok[0]) {
-                res.junction[a] = tree[a].count - 1;
-                res.junction[b] = m;
-                res.status = FOUND;
-            } else if (back && ok[1]) {
-                tree[b].append(e, m);
-            }
-        }
-        delete[] seg;
-        if (res.status == RUNNING) res.status = NO_ROUTE;
+        grow_reference(tree, n, lo, hi, samples, I, eta, M, motions_free, res);
     }
     res.nodes[0] = tree[0].count;
     res.nodes[1] = tree[1].count;
@@ -195,17 +221,7 @@ inline Result plan_reference(int n, const double *lo, const double *hi, const do
     int *order = new int[2 * (size_t)M + 2];  // (tree, node) of every waypoint, start first
     long long W = 2;
     if (res.junction[0] >= 0) {
-        int d0 = 0;
-        for (int v = res.junction[0]; v >= 0; v = tree[0].parent[v]) ++d0;
-        int t = d0;
-        for (int v = res.junction[0]; v >= 0; v = tree[0].parent[v]) order[--t] = v;
-        W = d0;
-        for (int v = res.junction[1]; v >= 0; v = tree[1].parent[v]) order[W++] = M + v;
-        double cost = 0.0;
-        for (long long t2 = 0; t2 + 1 < W; ++t2)
-            cost = cost + motion::motion_distance(n, conf + (size_t)order[t2] * n, 1, conf + (size_t)order[t2 + 1] * n, 1);
-        res.cost = cost;
-        res.status = found_status(W, Lmax);
+        W = route_reference(tree, n, M, Lmax, conf, res, order);
     } else if (res.status == FOUND) {
         res.cost = 0.0 + motion::motion_distance(n, start, 1, goal, 1);
         res.status = found_status(2, Lmax);

@@ -807,6 +807,59 @@ class HipChain:
             _ptr(res["iters"]), _ptr(res["nodes"]), _stream_ptr()))
         return res
 
+    # -- the tree planner with a goal set (include/optik_hip.h) ----------------------------
+    def rrt_plan_goals(self, starts, goals, gcount, iters, step, resolution, first=0, max_nodes=nat.RRT_NODES, Lmax=64,
+                       poll=nat.RRT_POLL, ee_offset7=None):
+        """rrt_plan with G goal slots per query (optik_hip_rrt_plan_goals): starts [n, Q], goals [G, n, Q], gcount [Q]
+        int32 -- only the goals g < gcount exist, nothing of the others influences an output (the NaN rows of
+        ik_solutions past its count are the normal input).  Tree 1 has one root per counted goal that is free and the
+        query ends at the first junction with any of them: past the direct motions (the nearest free one wins) the
+        answer is the goal joined first, not the cheapest.  Returns rrt_plan's dict plus which [Q] int32, the goal
+        reached (-1 unless status 0); a found path ends in that goal.  With G = 1 and gcount = 1 it is rrt_plan, bit
+        for bit.  max_nodes must be at least G.  Synchronises with the host as rrt_plan does, every `poll`
+        iterations."""
+        Q = self._check_q(starts)
+        if not (isinstance(goals, torch.Tensor) and goals.is_cuda and goals.dtype == torch.float64 and goals.dim() == 3
+                and goals.shape[1] == self.n and goals.shape[2] == Q and goals.is_contiguous()):
+            raise ValueError(f"goals must be a contiguous float64 cuda tensor [G, n, Q] = [G, {self.n}, {Q}]")
+        if not (isinstance(gcount, torch.Tensor) and gcount.is_cuda and gcount.dtype == torch.int32
+                and tuple(gcount.shape) == (Q,) and gcount.is_contiguous()):
+            raise ValueError(f"gcount must be a contiguous int32 cuda tensor [{Q}]")
+        iters, step, max_nodes, poll, first = nat.check_rrt_args(iters, step, max_nodes, Lmax, poll, first)
+        G = nat.check_rrt_goals(int(goals.shape[0]), max_nodes)
+        h = nat.check_resolution(resolution)
+        dev = starts.device
+        res = dict(path=torch.empty((int(Lmax), Q, self.n), dtype=torch.float64, device=dev),
+                   len=torch.empty(Q, dtype=torch.int32, device=dev),
+                   cost=torch.empty(Q, dtype=torch.float64, device=dev),
+                   status=torch.empty(Q, dtype=torch.int32, device=dev),
+                   iters=torch.empty(Q, dtype=torch.int32, device=dev),
+                   nodes=torch.empty((2, Q), dtype=torch.int32, device=dev),
+                   which=torch.empty(Q, dtype=torch.int32, device=dev))
+        ee = self._ee7(ee_offset7)
+        nat.check(nat.lib().optik_hip_rrt_plan_goals(
+            self._h, _dp(ee) if ee is not None else None, _ptr(starts), _ptr(goals), _ptr(gcount), Q, G, iters, step, h,
+            first, max_nodes, int(Lmax), poll, _ptr(res["path"]), _ptr(res["len"]), _ptr(res["cost"]),
+            _ptr(res["status"]), _ptr(res["iters"]), _ptr(res["nodes"]), _ptr(res["which"]), _stream_ptr()))
+        return res
+
+    def rrt_plan_poses(self, cfg, targets, starts, restart_begin, restart_end, K, min_dist, iters, step, resolution,
+                       first=0, max_nodes=nat.RRT_NODES, Lmax=64, poll=nat.RRT_POLL, ee_offset7=None):
+        """Plans starts[:, q] ([n, Q]) to the poses targets [Q, 7] without a roadmap: ik_solutions with x0 = the starts
+        and up to K <= 16 solutions per pose, whose count is the goal count and whose x [Q, K, n] becomes the goal set
+        [K, n, Q], then rrt_plan_goals -- back to back on the current stream, no host synchronisation between the two
+        stages, the solutions never leave the device.  It mirrors roadmap_plan_poses.  Returns rrt_plan_goals' dict
+        plus goals [K, n, Q] and count [Q] int32."""
+        K = nat.check_roadmap_goals(K)
+        self._check_q(starts)
+        sol = self.ik_solutions(cfg, targets, starts.t().contiguous(), restart_begin, restart_end, K, min_dist,
+                                ee_offset7=ee_offset7)
+        goals = sol["x"].permute(1, 2, 0).contiguous()
+        res = self.rrt_plan_goals(starts, goals, sol["count"], iters, step, resolution, first=first,
+                                  max_nodes=max_nodes, Lmax=Lmax, poll=poll, ee_offset7=ee_offset7)
+        res["goals"], res["count"] = goals, sol["count"]
+        return res
+
     # -- shortcutting and resampling (include/optik_hip.h; DESIGN.md section 5.19) --------------------------------
     def _check_paths(self, path, lens):
         if not (isinstance(path, torch.Tensor) and path.is_cuda and path.dtype == torch.float64 and path.dim() == 3

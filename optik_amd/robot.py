@@ -84,6 +84,8 @@ def _bind(L):
                                                 C.POINTER(C.c_int64)]
     L.optik_robot_rrt_plan.argtypes = [vp, dp, dp, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_uint64, C.c_int32,
                                        C.c_int32, C.c_int32, dp, dp, ip, dp, ip, ip, ip]
+    L.optik_robot_rrt_plan_goals.argtypes = [vp, dp, dp, ip, C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_double,
+                                             C.c_uint64, C.c_int32, C.c_int32, C.c_int32, dp, dp, ip, dp, ip, ip, ip, ip]
     L.optik_robot_path_shortcut.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, C.c_int32, C.c_double, C.c_double, C.c_int32,
                                             dp, dp, ip, dp, dp, ip]
     L.optik_robot_path_resample.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, C.c_int32, dp, ip]
@@ -1173,6 +1175,71 @@ class Robot:
                                         nodes.ctypes.data_as(ip)):
             raise RuntimeError(_err(self._L))
         return dict(paths=paths, len=ln, cost=cost, status=status, iters=it, nodes=nodes)
+
+    # -- the tree planner with a goal set (extension; include/optik.h) -----------------------
+    def plan_rrt_to_goals(self, starts, goals, counts=None, iters=None, step=None, resolution=nat.ROADMAP_RESOLUTION,
+                          first=0, max_nodes=None, max_waypoints=nat.PATH_OPTIMIZE_MAX_WAYPOINTS, poll=nat.RRT_POLL,
+                          ee_offset=None):
+        """plan_rrt to any of several goals per query: starts [Q, n], goals [Q, G, n] with 1 <= G <= 16, counts [Q]
+        (None: G each) -- query q has the goals g < counts[q] only, nothing of the others influences an output (the
+        NaN rows of ik_solutions_batch_arrays past its count are the normal input), and a query without goals has
+        status 1.  Tree 1 has one root per counted goal that is free, so a goal behind an obstacle costs its root
+        node and nothing more, and the query ends at the first junction with any of them.  If direct motions start
+        -> goal are free the nearest such goal wins (a tie: the lower index); past that the answer is the goal
+        joined FIRST, not the cheapest one.  Returns plan_rrt's dict plus "goal" [Q] int32: the index into the goal
+        set of the goal reached for status 0, -1 otherwise.  A found path ends in that goal; any other is the start,
+        then goal 0 repeated.  With one goal per query it is plan_rrt, bit for bit.  "paths" and "len" go into
+        shortcut_paths, resample_paths and certify_paths as they are.
+        It keeps no state in the robot and reads no roadmap: it works whatever roadmap the robot holds -- none, an
+        eager one, a lazy one, a stale one.  The defaults are plan_rrt's.
+        ValueError for the shapes, for G outside 1 .. 16, for max_nodes outside max(2, G) .. 4096 and for what
+        plan_rrt refuses."""
+        starts = self._check_xs(starts)
+        Q, n = starts.shape
+        goals = np.ascontiguousarray(goals, dtype=np.float64)
+        if goals.ndim != 3 or goals.shape[0] != Q or goals.shape[2] != n:
+            raise ValueError(f"goals must be [Q, G, n] = [{Q}, G, {n}], got {list(goals.shape)}")
+        if counts is not None:
+            counts = np.ascontiguousarray(counts, dtype=np.int32)
+            if counts.shape != (Q,):
+                raise ValueError(f"counts must be [Q] = [{Q}], got {list(counts.shape)}")
+        iters, step, max_nodes, poll, first = nat.check_rrt_args(iters, step, max_nodes, max_waypoints, poll, first)
+        G = nat.check_rrt_goals(goals.shape[1], max_nodes)
+        h = nat.check_resolution(resolution)
+        L = int(max_waypoints)
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        paths, cost = np.zeros((Q, L, n)), np.zeros(Q)
+        ln, status, it, goal = (np.zeros(Q, dtype=np.int32) for _ in range(4))
+        nodes = np.zeros((Q, 2), dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        if self._L.optik_robot_rrt_plan_goals(self._h, _dp(starts), _dp(goals),
+                                              counts.ctypes.data_as(ip) if counts is not None else None, G, Q, iters,
+                                              step, h, first, max_nodes, L, poll, _dp(ee) if ee is not None else None,
+                                              _dp(paths), ln.ctypes.data_as(ip), _dp(cost), status.ctypes.data_as(ip),
+                                              it.ctypes.data_as(ip), nodes.ctypes.data_as(ip), goal.ctypes.data_as(ip)):
+            raise RuntimeError(_err(self._L))
+        return dict(paths=paths, len=ln, cost=cost, status=status, iters=it, nodes=nodes, goal=goal)
+
+    def plan_rrt_to_poses(self, config: SolverConfig, starts, targets, k=8, min_dist=0.1, iters=None, step=None,
+                          resolution=nat.ROADMAP_RESOLUTION, first=0, max_nodes=None,
+                          max_waypoints=nat.PATH_OPTIMIZE_MAX_WAYPOINTS, poll=nat.RRT_POLL, ee_offset=None):
+        """"Move the gripper to this pose" without a roadmap: starts [Q, n], targets [Q, 4, 4] row-major poses.
+        ik_solutions_batch_arrays with the starts as seeds gives up to k <= 16 distinct solutions per pose (with a
+        collision model installed: the collision-free ones), and plan_rrt_to_goals grows one tree from the start and
+        one from all of them at once -- what to run on the rows plan_to_poses returns with status 1, and the way to
+        plan to a pose beside a lazy roadmap, which plan_to_poses refuses.  Returns plan_rrt_to_goals' dict plus
+        "goals" [Q, k, n] (NaN past the count) and "count" [Q] int32; an unreachable pose has count 0, status 1 and
+        goal -1.  The goal reached is the one joined first, not the cheapest.  The solutions pass through the host
+        here; HipChain.rrt_plan_poses keeps both stages on the device."""
+        k = nat.check_roadmap_goals(k)
+        starts = self._check_xs(starts)
+        x, _, _, count = self.ik_solutions_batch_arrays(config, targets, starts, k=k, min_dist=min_dist,
+                                                        ee_offset=ee_offset)
+        res = self.plan_rrt_to_goals(starts, x, counts=count, iters=iters, step=step, resolution=resolution,
+                                     first=first, max_nodes=max_nodes, max_waypoints=max_waypoints, poll=poll,
+                                     ee_offset=ee_offset)
+        res["goals"], res["count"] = x, count
+        return res
 
     # -- shortcutting and resampling (extension; include/optik.h, DESIGN.md section 5.19) ---------------------------
     def _check_paths(self, paths, lens):
