@@ -409,7 +409,8 @@ int64_t optik_hip_rrt_chunk(const optik_hip_chain *chain, int32_t max_nodes);
  * csrc/rrt_goals_measure.hpp): optik_hip_rrt_plan with G goal slots per query, 1 <= G <= OPTIK_HIP_RRT_MAX_GOALS, in
  * place of the one goal -- the IK solutions of a pose, for one.  d_goals [G][n][Q]; d_gcount [Q] int32: only the goals
  * g < gcount exist (a count outside 0 .. G is clamped), and NOTHING of the others influences any output, so the NaN
- * rows optik_hip_ik_solutions leaves past its count are the normal input.  Tree 1 has one root per counted goal that
+ * rows optik_hip_ik_solutions leaves past its count are the normal input.  d_gcount NULL: every query's count is G,
+ * all slots exist.  Tree 1 has one root per counted goal that
  * is free, and the query ends at the FIRST junction with any of them: past the direct motions the answer is the goal
  * joined first, not the cheapest one.
  * Before iteration 0, in this order: a NaN or infinite joint in the start or in any counted goal gives status 3 (cost
@@ -424,7 +425,9 @@ int64_t optik_hip_rrt_chunk(const optik_hip_chain *chain, int32_t max_nodes);
  * keeps the cost).  The path is padded with goal `which` for status 0; any other is the start, then goal 0 repeated
  * (the start repeated for gcount = 0), len 2.  The other outputs, the workspace, the chunks (optik_hip_rrt_chunk: the
  * trees are the same size) and the polling are optik_hip_rrt_plan's; any output may be NULL.  With G = 1 and gcount =
- * 1 every output equals optik_hip_rrt_plan's bit for bit, and which is 0 where the status is 0.  A query's result
+ * 1 every output equals optik_hip_rrt_plan's bit for bit, and which is 0 where the status is 0: optik_hip_rrt_plan IS
+ * this call with G = 1, d_goals = d_goal ([1][n][Q] is [n][Q]), d_gcount NULL and d_which NULL, behind its own
+ * refusals.  A query's result
  * does not depend on Q, on the chunking, on `poll` or on a launch shape, and is bit for bit rrt_goals_measure.hpp's
  * serial reference given the same samples and verdicts.
  * Before iteration 0 the call classifies (1 + G) Q configurations in one optik_hip_collision_batch call -- a slot that

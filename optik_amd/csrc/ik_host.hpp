@@ -14,8 +14,8 @@
 //   ik_path_optimize.hip  covariant gradient smoothing of joint paths against the same witnesses
 //   ik_roadmap.hip     roadmap planning: nearest neighbours, motion-checked edges, shortest-path queries
 //   ik_roadmap_lazy.hip  lazy roadmaps: edges checked only when a route uses them, verdicts kept across plans
-//   ik_rrt.hip         the bidirectional tree planner: two trees per query, for the queries a roadmap misses
-//   ik_rrt_goals.hip   the tree planner with a goal set: tree 1 rooted at every free goal (the IK solutions of a pose)
+//   ik_rrt.hip         the bidirectional tree planner: two trees per query, for the queries a roadmap misses; tree 1
+//                      rooted at the goal, or at every free goal of a goal set (the IK solutions of a pose)
 //   ik_shortcut.hip    path shortcutting over all-pairs visibility, equal-spacing resampling
 //   ik_time.hip        timing of joint paths under velocity and acceleration limits, trajectory sampling
 //   ik_occupancy.hip   occupancy grids and point clouds into distance-field worlds (distance transform, voxelize)

@@ -1,11 +1,20 @@
-// ik_rrt.hip -- the bidirectional tree planner on the device (rrt_measure.hpp: the rules and their operation order;
-// DESIGN.md section 5.26): for the queries a roadmap misses, two trees per query grown from the query's own start and
-// goal.  optik_hip_rrt_plan (include/optik_hip.h).
+// ik_rrt.hip -- the bidirectional tree planner on the device (rrt_measure.hpp and rrt_goals_measure.hpp: the rules and
+// their operation order; DESIGN.md sections 5.26 and 5.28): for the queries a roadmap misses, two trees per query,
+// tree 0 grown from the query's start and tree 1 from one root per counted goal that is free; the query ends at the
+// first junction with any of them.  One set of kernels and one planner body (plan): optik_hip_rrt_plan_goals calls
+// it, and optik_hip_rrt_plan is its call with G = 1 and every slot counted -- [G][n][Q] with G = 1 is [n][Q], and the
+// rules of rrt_goals_measure.hpp with one counted goal are rrt_measure.hpp's bit for bit (include/optik_hip.h).
 //
-//   rrt_gather_kernel   one thread per query of the chunk: its start and goal into the workspace, [n][Qc], as the
-//                       collision and motion checks take their configurations
-//   (optik_hip_collision_batch on both, optik_hip_collision_motion_batch on start -> goal, same stream)
-//   rrt_begin_kernel    one thread per query: rule 0, the two roots, and the count of the queries that go on
+//   rrt_gather_kernel   one thread per query of the chunk: its clamped goal count (no counts: G); the 1 + G
+//                       configurations that rule 0 classifies, [n][(1 + G) Qc] -- the start, then per slot the goal if it
+//                       is counted and the start again if it is not --; and the G direct motions in travel direction,
+//                       start -> goal g, [n][G Qc] twice -- NaN on both ends for a slot that is not counted, which the
+//                       motion check answers "not sampled" without reading a model.  The second of the two arrays is
+//                       where the later kernels read a counted goal from.
+//   (optik_hip_collision_batch on the 1 + G columns, optik_hip_collision_motion_batch on the G segments, same stream)
+//   rrt_begin_kernel    one thread per query: rule 0 -- the roots of tree 1 in ascending g with the root -> goal table,
+//                       the nearest free direct motion --, and the count of the queries that go on.  Only the flags of
+//                       counted slots are read.
 //   rrt_step_kernel     one wave per query, both trees in turn (the nearest node of tree b is the nearest to the
 //                       candidate that the search in tree a gives, so the two searches of a query cannot overlap).
 //                       First it commits the iteration before from the motion check's free flags (append, junction,
@@ -15,73 +24,167 @@
 //                       of rrt::nearer) leaves the winner in every lane.  Lane j < n then steers joint j and writes
 //                       the iteration's three segments in travel direction: p - c, c - m and m - e.  A query that is
 //                       frozen, and a segment that the rules do not ask for, is NaN: the motion check answers it
-//                       "not sampled" without reading a model.
+//                       "not sampled" without reading a model.  It needs no rule for the goal set: a tree 1 with R
+//                       roots is a tree with R nodes to it.
 //   (optik_hip_collision_motion_batch, classify form, on the same stream: the motion check's own code, 3 Qc segments)
 //   rrt_walk_kernel     one wave per query: lane 0 reverses the parent links of tree 0's branch in place (the trees are
-//                       scratch by then), walks start -> junction -> goal adding the cost forwards, and the wave
-//                       writes the path.
+//                       scratch by then), walks start -> junction -> root adding the cost forwards, and the wave
+//                       writes the path; the goal slot of the root that tree 1's branch ends in is `which`, and the
+//                       path is padded with that goal.
 //
 // Two launches of this unit's own per iteration would be one too many: the commit of iteration i and the search of
 // iteration i + 1 are one kernel, so an iteration is that kernel and the motion check's five.  No kernel waits for
-// another workgroup; every loop's trip count is bounded by a tree's size, n or Lmax.  The loop over the iterations
-// runs on the host; every `poll` iterations it reads one int32, the count of the queries that have not ended.
-// The launch record and that loop (rrtdev::run_iterations, defined here) are declared in rrt_device.hpp:
-// ik_rrt_goals.hip runs the same loop, and so rrt_step_kernel as it is, on trees with several goal roots.
+// another workgroup; every loop's trip count is bounded by a tree's size, n, G or Lmax; no private array is indexed
+// dynamically; the atomics are vector atomics on the count of running queries, the begin kernel's atomicAdd and the
+// atomicSub of a query that ends in rrt_step_kernel.  The loop over the iterations runs on the host (run_iterations);
+// every `poll` iterations it reads one int32, the count of the queries that have not ended.
 #include <algorithm>
 
-#include "rrt_device.hpp"
+#include "collision_device.hpp"
+#include "rrt_goals_measure.hpp"
 
 using namespace optik;
 using namespace optik::host;
 using namespace optik::colldev;
-using namespace optik::rrtdev;
 
 static_assert(rrt::MAX_NODES == OPTIK_HIP_RRT_MAX_NODES && rrt::MAX_ITERS == OPTIK_HIP_RRT_MAX_ITERS
                   && rrt::MAX_POLL == OPTIK_HIP_RRT_MAX_POLL
                   && roadmap::MAX_WAYPOINTS == OPTIK_HIP_PATH_OPTIMIZE_MAX_WAYPOINTS,
               "optik_hip.h states the caps of rrt_measure.hpp; a plan is a path path_optimize takes");
+static_assert(rrt::MAX_GOALS == OPTIK_HIP_RRT_MAX_GOALS && OPTIK_HIP_RRT_MAX_GOALS == OPTIK_HIP_ROADMAP_MAX_GOALS,
+              "optik_hip.h states the cap of rrt_goals_measure.hpp; a goal set is what ik_solutions and the roadmap's "
+              "goal-set query take");
 
 namespace {
 
-// (the launch record RrtLaunch, tree_conf, tree_parent and clear_segments: rrt_device.hpp)
+constexpr int RRT_BLOCK = 256, RRT_WAVE = 64;
+constexpr long long MAX_QUERIES = 1ll << 30;
+
+struct RrtLaunch {
+    long long Q, q0, Qc;         // the call's queries; the chunk's first and its count
+    int n, M, Lmax, I, iter, G;
+    double eta;
+    const double *start;         // [n][Q] the caller's
+    const double *goals;         // [G][n][Q] the caller's
+    const int32_t *gcount;       // [Q] the caller's, or null: G each
+    const double *lo, *hi;       // [n] the joint limits (the chain's table)
+    const double *samples;       // [n][I]
+    double *cfg;                 // [n][(1 + G) Qc] column q: the start; column (1 + g) Qc + q: goal g, or the start
+    double *da, *db;             // [n][G Qc] column g Qc + q: start -> goal g, NaN if the slot is not counted
+    int32_t *gc;                 // [Qc] the clamped counts
+    int32_t *root_goal;          // [G][Qc] the goal slot of root r
+    int32_t *direct;             // [Qc] rule 0's direct goal, or -1
+    uint8_t *flags;              // [3][Qc] the motion check's flags of the iteration's segments
+    uint8_t *cflags;             // [(1 + G) Qc] optik_hip_collision_batch's flags of cfg
+    uint8_t *mflags;             // [G Qc] the motion check's flags of the direct motions
+    double *conf;                // [Qc][2][n][M]
+    int32_t *parent;             // [Qc][2][M]
+    int32_t *count;              // [2][Qc]
+    int32_t *state;              // [Qc] rrt::RUNNING or how the query ended
+    int32_t *junction;           // [2][Qc]
+    int32_t *used;               // [Qc]
+    int32_t *pend;               // [3][Qc] the iteration in flight: p (-1: none), m, whether tree b extends
+    double *qa, *qb;             // [n][3 Qc] the segments, column s * Qc + q
+    int32_t *unfinished;         // [1]
+    double *path;                // [Lmax][Q][n] or null
+    int32_t *len, *status, *iters, *nodes, *which;  // [Q], nodes [2][Q]; or null
+    double *cost;
+};
+
+__device__ __forceinline__ double *tree_conf(const RrtLaunch &a, long long q, int t) {
+    return a.conf + ((size_t)q * 2 + t) * (size_t)a.n * a.M;
+}
+__device__ __forceinline__ int32_t *tree_parent(const RrtLaunch &a, long long q, int t) {
+    return a.parent + ((size_t)q * 2 + t) * (size_t)a.M;
+}
+
+// every segment of query q is "not sampled" from here on
+__device__ __forceinline__ void clear_segments(const RrtLaunch &a, long long q, int i) {
+    const long long B = 3 * a.Qc;
+    for (int s = 0; s < 3; ++s) {
+        a.qa[(long long)i * B + s * a.Qc + q] = roadmap::nan_value();
+        a.qb[(long long)i * B + s * a.Qc + q] = roadmap::nan_value();
+    }
+}
+
+__device__ __forceinline__ double start_joint(const RrtLaunch &a, long long q, int i) {
+    return a.cfg[(long long)i * (1 + a.G) * a.Qc + q];
+}
+// (of a counted goal only: the other slots hold NaN)
+__device__ __forceinline__ double goal_joint(const RrtLaunch &a, long long q, int g, int i) {
+    return a.db[(long long)i * a.G * a.Qc + (long long)g * a.Qc + q];
+}
+
+inline unsigned blocks(long long work) { return (unsigned)((work + RRT_BLOCK - 1) / RRT_BLOCK); }
 
 __global__ __launch_bounds__(RRT_BLOCK) void rrt_gather_kernel(const RrtLaunch a) {
-    const long long q = (long long)blockIdx.x * RRT_BLOCK + threadIdx.x;
-    if (q >= a.Qc) return;
-    for (int i = 0; i < a.n; ++i) {
-        a.s[(long long)i * a.Qc + q] = a.start[(long long)i * a.Q + a.q0 + q];
-        a.g[(long long)i * a.Qc + q] = a.goal[(long long)i * a.Q + a.q0 + q];
+    const long long q = (long long)blockIdx.x * RRT_BLOCK + threadIdx.x, Qc = a.Qc;
+    if (q >= Qc) return;
+    const int n = a.n, G = a.G;
+    const int gc = rrt::clamp_count(a.gcount ? a.gcount[a.q0 + q] : G, G);
+    a.gc[q] = gc;
+    for (int i = 0; i < n; ++i) {
+        const double s = a.start[(long long)i * a.Q + a.q0 + q];
+        double *cfg = a.cfg + (long long)i * (1 + G) * Qc + q;
+        double *da = a.da + (long long)i * G * Qc + q, *db = a.db + (long long)i * G * Qc + q;
+        cfg[0] = s;
+        for (int g = 0; g < G; ++g) {
+            const bool counted = g < gc;
+            // (a slot that is not counted is not read at all)
+            const double v = counted ? a.goals[((long long)g * n + i) * a.Q + a.q0 + q] : roadmap::nan_value();
+            cfg[(long long)(1 + g) * Qc] = counted ? v : s;
+            da[(long long)g * Qc] = counted ? s : roadmap::nan_value();
+            db[(long long)g * Qc] = v;
+        }
     }
 }
 
 __global__ __launch_bounds__(RRT_BLOCK) void rrt_begin_kernel(const RrtLaunch a) {
-    const long long q = (long long)blockIdx.x * RRT_BLOCK + threadIdx.x;
-    if (q >= a.Qc) return;
+    const long long q = (long long)blockIdx.x * RRT_BLOCK + threadIdx.x, Qc = a.Qc;
+    if (q >= Qc) return;
+    const int n = a.n, G = a.G, M = a.M, gc = a.gc[q];
     bool ends_finite = true;
-    for (int i = 0; i < a.n; ++i)
-        ends_finite = ends_finite && rrt::finite(a.s[(long long)i * a.Qc + q]) && rrt::finite(a.g[(long long)i * a.Qc + q]);
-    const int state = rrt::begin(ends_finite, a.flags[q] != 0, a.flags[a.Qc + q] != 0, a.flags[2 * a.Qc + q] != 0);
+    for (int i = 0; i < n; ++i) ends_finite = ends_finite && rrt::finite(start_joint(a, q, i));
+    for (int g = 0; g < gc; ++g)
+        for (int i = 0; i < n; ++i) ends_finite = ends_finite && rrt::finite(goal_joint(a, q, g, i));
+    const bool start_free = a.cflags[q] != 0;
+    // the roots in ascending g and, among those whose direct motion is free, the nearest (a tie: the lower g)
+    int R = 0, direct = -1;
+    double bd = roadmap::inf();
+    for (int g = 0; g < gc; ++g) {
+        if (a.cflags[(long long)(1 + g) * Qc + q] == 0) continue;
+        if (R < G) a.root_goal[(long long)R * Qc + q] = g;
+        R += 1;
+        if (a.mflags[(long long)g * Qc + q] == 0) continue;
+        const double d = motion::motion_distance(n, a.cfg + q, (1 + G) * Qc, a.db + (long long)g * Qc + q, G * Qc);
+        if (rrt::direct_better(d, bd, direct)) { bd = d; direct = g; }
+    }
+    const int state = rrt::begin_goals(ends_finite, gc, start_free, R, direct);
     const bool run = state == rrt::RUNNING;
     if (run) {
+        // (R <= G <= M: the call refuses a max_nodes below G)
         double *c0 = tree_conf(a, q, 0), *c1 = tree_conf(a, q, 1);
-        for (int i = 0; i < a.n; ++i) {
-            c0[(size_t)i * a.M] = a.s[(long long)i * a.Qc + q];
-            c1[(size_t)i * a.M] = a.g[(long long)i * a.Qc + q];
+        int32_t *par1 = tree_parent(a, q, 1);
+        for (int i = 0; i < n; ++i) c0[(size_t)i * M] = start_joint(a, q, i);
+        for (int r = 0; r < R && r < M; ++r) {
+            const int g = a.root_goal[(long long)r * Qc + q];
+            for (int i = 0; i < n; ++i) c1[(size_t)i * M + r] = goal_joint(a, q, g, i);
+            par1[r] = -1;
         }
         tree_parent(a, q, 0)[0] = -1;
-        tree_parent(a, q, 1)[0] = -1;
         atomicAdd(a.unfinished, 1);
     }
     a.count[q] = run ? 1 : 0;
-    a.count[a.Qc + q] = run ? 1 : 0;
+    a.count[Qc + q] = run ? (R < M ? R : M) : 0;
     a.state[q] = state;
+    a.direct[q] = state == rrt::FOUND ? direct : -1;
     a.junction[q] = -1;
-    a.junction[a.Qc + q] = -1;
+    a.junction[Qc + q] = -1;
     a.used[q] = 0;
     a.pend[q] = -1;
-    a.pend[a.Qc + q] = -1;
-    a.pend[2 * a.Qc + q] = 0;
-    for (int i = 0; i < a.n; ++i) clear_segments(a, q, i);
+    a.pend[Qc + q] = -1;
+    a.pend[2 * Qc + q] = 0;
+    for (int i = 0; i < n; ++i) clear_segments(a, q, i);
 }
 
 // Rule 1 over one tree: every lane ends with the winner.  conf [n][M], x in LDS.
@@ -217,19 +320,24 @@ __global__ __launch_bounds__(RRT_WAVE) void rrt_step_kernel(const RrtLaunch a) {
 
 __global__ __launch_bounds__(RRT_WAVE) void rrt_walk_kernel(const RrtLaunch a) {
     __shared__ int s_way[roadmap::MAX_WAYPOINTS];  // waypoint t: node v of tree 0, or M + v of tree 1
-    __shared__ int s_len;
-    const long long q = blockIdx.x, qo = a.q0 + q;
-    const int lane = threadIdx.x, n = a.n, M = a.M;
+    __shared__ int s_len, s_pad;                   // s_pad: the goal slot the path is padded with, -1 for the start
+    const long long q = blockIdx.x, qo = a.q0 + q, Qc = a.Qc;
+    const int lane = threadIdx.x, n = a.n, M = a.M, G = a.G;
     if (lane == 0) {
-        const int state = a.state[q], j0 = a.junction[q], j1 = a.junction[a.Qc + q];
-        const int c0 = a.count[q], c1 = a.count[a.Qc + q];
-        int status = state == rrt::RUNNING ? rrt::NO_ROUTE : state, len = 2;
+        const int state = a.state[q], j0 = a.junction[q], j1 = a.junction[Qc + q];
+        const int c0 = a.count[q], c1 = a.count[Qc + q], gc = a.gc[q], direct = a.direct[q];
+        int status = state == rrt::RUNNING ? rrt::NO_ROUTE : state, len = 2, which = -1;
         double cost = roadmap::inf();
         if (state == rrt::QUERY_NAN) cost = roadmap::nan_value();
         if (state == rrt::FOUND && !(j0 >= 0 && j0 < c0 && j1 >= 0 && j1 < c1)) {
-            // the direct motion (rule 0)
-            cost = 0.0 + motion::motion_distance(n, a.s + q, a.Qc, a.g + q, a.Qc);
-            status = rrt::found_status(2, a.Lmax);
+            if (direct >= 0 && direct < gc) {
+                // the direct motion (rule 0)
+                cost = 0.0 + motion::motion_distance(n, a.cfg + q, (1 + G) * Qc, a.db + (long long)direct * Qc + q, G * Qc);
+                status = rrt::found_status(2, a.Lmax);
+                if (status == rrt::FOUND) which = direct;
+            } else {
+                status = rrt::NO_ROUTE;  // (rule 0 chose no goal and there is no junction: cannot happen)
+            }
         } else if (state == rrt::FOUND) {
             const double *conf0 = tree_conf(a, q, 0), *conf1 = tree_conf(a, q, 1);
             int32_t *par0 = tree_parent(a, q, 0);
@@ -263,10 +371,17 @@ __global__ __launch_bounds__(RRT_WAVE) void rrt_walk_kernel(const RrtLaunch a) {
                 cost = cost + motion::motion_distance(n, conf1 + v, M, conf1 + up, M);
                 v = up;
             }
-            status = rrt::found_status(W, a.Lmax);
-            if (status == rrt::FOUND) len = W;
+            // (v is the root the branch ends in: one of the first R <= G nodes)
+            const int g = v >= 0 && v < G ? a.root_goal[(long long)v * Qc + q] : -1;
+            status = g >= 0 && g < gc ? rrt::found_status(W, a.Lmax) : rrt::NO_ROUTE;
+            if (status == rrt::FOUND) {
+                len = W;
+                which = g;
+            }
+            if (status == rrt::NO_ROUTE) cost = roadmap::inf();
         }
         s_len = len;
+        s_pad = status == rrt::FOUND ? which : (gc > 0 ? 0 : -1);
         if (a.len) a.len[qo] = len;
         if (a.cost) a.cost[qo] = cost;
         if (a.status) a.status[qo] = status;
@@ -275,15 +390,16 @@ __global__ __launch_bounds__(RRT_WAVE) void rrt_walk_kernel(const RrtLaunch a) {
             a.nodes[qo] = c0;
             a.nodes[a.Q + qo] = c1;
         }
+        if (a.which) a.which[qo] = which;
     }
     __syncthreads();
     if (!a.path) return;
-    const int len = s_len;
+    const int len = s_len, pad = s_pad;
     const double *conf = tree_conf(a, q, 0);  // (tree 1 follows tree 0: node M + v)
     for (int e = lane; e < a.Lmax * n; e += RRT_WAVE) {
         const int t = e / n, i = e % n;
-        double v = a.g[(long long)i * a.Qc + q];
-        if (t == 0) v = a.s[(long long)i * a.Qc + q];
+        double v = pad >= 0 ? goal_joint(a, q, pad, i) : start_joint(a, q, i);
+        if (t == 0) v = start_joint(a, q, i);
         else if (t < len - 1) {
             const int w = s_way[t];
             v = conf[(size_t)(w / M) * n * M + (size_t)i * M + (w % M)];
@@ -292,11 +408,7 @@ __global__ __launch_bounds__(RRT_WAVE) void rrt_walk_kernel(const RrtLaunch a) {
     }
 }
 
-}  // namespace
-
-namespace optik {
-namespace rrtdev {
-
+// what both calls refuse before any device work, in optik_hip_rrt_plan's words; 0 to go on
 int check_args(const optik_hip_chain *ch, int64_t Q, int32_t iters, double step, double resolution, int32_t max_nodes,
                int32_t Lmax, int32_t poll) {
     if (!ch || Q < 0) return fail(OPTIK_HIP_EINVAL, "bad argument");
@@ -315,8 +427,11 @@ int check_args(const optik_hip_chain *ch, int64_t Q, int32_t iters, double step,
                                             nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
+// The iterations of the chunk a.q0, a.Qc whose begin kernel has run on `stream`: rrt_step_kernel and the motion check
+// over the 3 a.Qc segments per iteration, one read of *a.unfinished every `poll` iterations, and the last commit with
+// rule 6.  The walk kernel comes next on the stream.
 int run_iterations(optik_hip_chain *ch, const double *ee_offset7, RrtLaunch &a, int32_t iters, int32_t poll,
-                   double resolution, uint8_t *d_flags, hipStream_t stream) {
+                   double resolution, hipStream_t stream) {
     const long long L = a.Qc;
     bool ended = false;
     for (int32_t i = 0; i < iters; ++i) {
@@ -333,7 +448,7 @@ int run_iterations(optik_hip_chain *ch, const double *ee_offset7, RrtLaunch &a, 
                 if (left <= 0) { ended = true; break; }
             }
         }
-        if (int rc = optik_hip_collision_motion_batch(ch, ee_offset7, a.qa, a.qb, 3 * L, resolution, nullptr, d_flags,
+        if (int rc = optik_hip_collision_motion_batch(ch, ee_offset7, a.qa, a.qb, 3 * L, resolution, nullptr, a.flags,
                                                       nullptr, nullptr, stream))
             return rc;
     }
@@ -346,8 +461,97 @@ int run_iterations(optik_hip_chain *ch, const double *ee_offset7, RrtLaunch &a, 
     return 0;
 }
 
-}  // namespace rrtdev
-}  // namespace optik
+// The arrays of a workspace one after the other, each on a 16-byte boundary.  With base 0 the same sequence of
+// take() calls gives the size to reserve.
+struct Carve {
+    uintptr_t base;
+    size_t at = 0;
+    template <class T> void take(T *&array, size_t count) {
+        array = reinterpret_cast<T *>(base + at);
+        at += (sizeof(T) * count + 15) & ~(size_t)15;
+    }
+};
+
+// The workspace of a call in chunks of Qc queries -- the samples, rule 0's configurations, direct motions and flags,
+// the iteration's segments and flags, the per-query state and the trees -- into the record; returns its size.
+// (a chunk's arrays are [..][L] with L <= Qc: a later chunk may be shorter, never longer)
+size_t carve_workspace(RrtLaunch &a, unsigned char *ws, size_t Qc) {
+    const size_t n = (size_t)a.n, M = (size_t)a.M, I = (size_t)a.I, G = (size_t)a.G;
+    Carve c{reinterpret_cast<uintptr_t>(ws)};
+    c.take(a.unfinished, 1);
+    c.take(a.samples, n * I);
+    c.take(a.cfg, n * (1 + G) * Qc);
+    c.take(a.da, n * G * Qc);
+    c.take(a.db, n * G * Qc);
+    c.take(a.qa, n * 3 * Qc);
+    c.take(a.qb, n * 3 * Qc);
+    c.take(a.flags, 3 * Qc + (1 + 2 * G) * Qc);  // (the iterations' three flags per query, then rule 0's 1 + 2 G)
+    a.cflags = a.flags + 3 * Qc;
+    c.take(a.count, 2 * Qc);
+    c.take(a.state, Qc);
+    c.take(a.junction, 2 * Qc);
+    c.take(a.used, Qc);
+    c.take(a.pend, 3 * Qc);
+    c.take(a.gc, Qc);
+    c.take(a.direct, Qc);
+    c.take(a.root_goal, G * Qc);
+    c.take(a.parent, 2 * M * Qc);
+    c.take(a.conf, 2 * n * M * Qc);
+    return c.at;
+}
+
+// The planner of both calls, their arguments checked: d_goals [G][n][Q]; d_gcount null: G each; d_which may be null.
+int plan(optik_hip_chain *ch, const double *ee_offset7, const double *d_start, const double *d_goals,
+         const int32_t *d_gcount, int64_t Q, int32_t G, int32_t iters, double step, double resolution, uint64_t first,
+         int32_t max_nodes, int32_t Lmax, int32_t poll, double *d_path, int32_t *d_len, double *d_cost,
+         int32_t *d_status, int32_t *d_iters, int32_t *d_nodes, int32_t *d_which, hipStream_t stream) {
+    const size_t Qc = (size_t)std::min<int64_t>(Q, optik_hip_rrt_chunk(ch, max_nodes)), uG = (size_t)G;
+    RrtLaunch a;
+    std::memset(&a, 0, sizeof a);
+    a.Q = Q; a.n = ch->n; a.M = max_nodes; a.Lmax = Lmax; a.I = iters; a.G = G; a.eta = step;
+    a.start = d_start; a.goals = d_goals; a.gcount = d_gcount;
+    a.lo = ch->wide ? ch->wdev->lb : ch->dev->lb;
+    a.hi = ch->wide ? ch->wdev->ub : ch->dev->ub;
+    a.path = d_path; a.len = d_len; a.cost = d_cost; a.status = d_status; a.iters = d_iters; a.nodes = d_nodes;
+    a.which = d_which;
+    const size_t bytes = carve_workspace(a, nullptr, Qc);
+    {
+        std::lock_guard<std::mutex> lock(ch->mu);
+        BIND_DEVICE(ch);
+        HIP_TRY(ch->rrt_ws.reserve(bytes));
+        carve_workspace(a, ch->rrt_ws.get(), Qc);
+    }
+    // (the samples of the whole call: iteration i reads restart seed first + i, whatever the query)
+    if (int rc = optik_hip_seed_batch(ch, first, iters, const_cast<double *>(a.samples), stream)) return rc;
+    for (int64_t q0 = 0; q0 < Q; q0 += (int64_t)Qc) {
+        const long long L = std::min<int64_t>((int64_t)Qc, Q - q0);
+        a.q0 = q0; a.Qc = L;
+        a.qb = a.qa + (size_t)a.n * 3 * (size_t)L;
+        a.mflags = a.cflags + (1 + uG) * (size_t)L;
+        {
+            BIND_DEVICE(ch);
+            HIP_TRY(hipMemsetAsync(a.unfinished, 0, sizeof(int32_t), stream));
+            hipLaunchKernelGGL(rrt_gather_kernel, dim3(blocks(L)), dim3(RRT_BLOCK), 0, stream, a);
+            HIP_TRY(hipGetLastError());
+        }
+        if (int rc = optik_hip_collision_batch(ch, ee_offset7, a.cfg, (1 + G) * L, nullptr, a.cflags, stream)) return rc;
+        if (int rc = optik_hip_collision_motion_batch(ch, ee_offset7, a.da, a.db, G * L, resolution, nullptr, a.mflags,
+                                                      nullptr, nullptr, stream))
+            return rc;
+        {
+            BIND_DEVICE(ch);
+            hipLaunchKernelGGL(rrt_begin_kernel, dim3(blocks(L)), dim3(RRT_BLOCK), 0, stream, a);
+            HIP_TRY(hipGetLastError());
+        }
+        if (int rc = run_iterations(ch, ee_offset7, a, iters, poll, resolution, stream)) return rc;
+        BIND_DEVICE(ch);
+        hipLaunchKernelGGL(rrt_walk_kernel, dim3((unsigned)L), dim3(RRT_WAVE), 0, stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -366,74 +570,29 @@ int optik_hip_rrt_plan(optik_hip_chain *ch, const double *ee_offset7, const doub
         return fail(OPTIK_HIP_EUNSUPPORTED, "rrt_plan: chains of 1 .. 16 joint positions");
     if (Q == 0 || (!d_path && !d_len && !d_cost && !d_status && !d_iters && !d_nodes)) return 0;
     if (!d_start || !d_goal) return fail(OPTIK_HIP_EINVAL, "bad argument");
-    hipStream_t stream = (hipStream_t)stream_;
-    const size_t n = (size_t)ch->n, M = (size_t)max_nodes, I = (size_t)iters;
-    const size_t Qc = (size_t)std::min<int64_t>(Q, optik_hip_rrt_chunk(ch, max_nodes));
-    const size_t o_samples = 16, o_s = o_samples + align16(8 * n * I), o_g = o_s + align16(8 * n * Qc),
-                 o_qa = o_g + align16(8 * n * Qc), o_qb = o_qa + align16(8 * n * 3 * Qc),
-                 o_flags = o_qb + align16(8 * n * 3 * Qc), o_count = o_flags + align16(3 * Qc),
-                 o_state = o_count + align16(4 * 2 * Qc), o_junction = o_state + align16(4 * Qc),
-                 o_used = o_junction + align16(4 * 2 * Qc), o_pend = o_used + align16(4 * Qc),
-                 o_parent = o_pend + align16(4 * 3 * Qc), o_conf = o_parent + align16(4 * 2 * M * Qc),
-                 bytes = o_conf + 8 * 2 * n * M * Qc;
-    unsigned char *ws = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(ch->mu);
-        BIND_DEVICE(ch);
-        HIP_TRY(ch->rrt_ws.reserve(bytes));
-        ws = ch->rrt_ws.get();
-    }
-    RrtLaunch a;
-    std::memset(&a, 0, sizeof a);
-    a.Q = Q; a.n = ch->n; a.M = max_nodes; a.Lmax = Lmax; a.I = iters; a.eta = step;
-    a.start = d_start; a.goal = d_goal;
-    a.lo = ch->wide ? ch->wdev->lb : ch->dev->lb;
-    a.hi = ch->wide ? ch->wdev->ub : ch->dev->ub;
-    a.unfinished = reinterpret_cast<int32_t *>(ws);
-    a.samples = reinterpret_cast<double *>(ws + o_samples);
-    a.s = reinterpret_cast<double *>(ws + o_s);
-    a.g = reinterpret_cast<double *>(ws + o_g);
-    a.qa = reinterpret_cast<double *>(ws + o_qa);
-    a.qb = reinterpret_cast<double *>(ws + o_qb);
-    a.flags = ws + o_flags;
-    a.count = reinterpret_cast<int32_t *>(ws + o_count);
-    a.state = reinterpret_cast<int32_t *>(ws + o_state);
-    a.junction = reinterpret_cast<int32_t *>(ws + o_junction);
-    a.used = reinterpret_cast<int32_t *>(ws + o_used);
-    a.pend = reinterpret_cast<int32_t *>(ws + o_pend);
-    a.parent = reinterpret_cast<int32_t *>(ws + o_parent);
-    a.conf = reinterpret_cast<double *>(ws + o_conf);
-    a.path = d_path; a.len = d_len; a.cost = d_cost; a.status = d_status; a.iters = d_iters; a.nodes = d_nodes;
-    uint8_t *d_flags = ws + o_flags;
-    // (the samples of the whole call: iteration i reads restart seed first + i, whatever the query)
-    if (int rc = optik_hip_seed_batch(ch, first, iters, const_cast<double *>(a.samples), stream)) return rc;
-    for (int64_t q0 = 0; q0 < Q; q0 += (int64_t)Qc) {
-        const long long L = std::min<int64_t>((int64_t)Qc, Q - q0);
-        a.q0 = q0; a.Qc = L;
-        // (a chunk's arrays are [..][L]: the offsets above leave room for Qc >= L)
-        a.qb = a.qa + n * 3 * (size_t)L;
-        {
-            BIND_DEVICE(ch);
-            HIP_TRY(hipMemsetAsync(a.unfinished, 0, sizeof(int32_t), stream));
-            hipLaunchKernelGGL(rrt_gather_kernel, dim3(blocks(L)), dim3(RRT_BLOCK), 0, stream, a);
-            HIP_TRY(hipGetLastError());
-        }
-        if (int rc = optik_hip_collision_batch(ch, ee_offset7, a.s, L, nullptr, d_flags, stream)) return rc;
-        if (int rc = optik_hip_collision_batch(ch, ee_offset7, a.g, L, nullptr, d_flags + L, stream)) return rc;
-        if (int rc = optik_hip_collision_motion_batch(ch, ee_offset7, a.s, a.g, L, resolution, nullptr, d_flags + 2 * L,
-                                                      nullptr, nullptr, stream))
-            return rc;
-        {
-            BIND_DEVICE(ch);
-            hipLaunchKernelGGL(rrt_begin_kernel, dim3(blocks(L)), dim3(RRT_BLOCK), 0, stream, a);
-            HIP_TRY(hipGetLastError());
-        }
-        if (int rc = run_iterations(ch, ee_offset7, a, iters, poll, resolution, d_flags, stream)) return rc;
-        BIND_DEVICE(ch);
-        hipLaunchKernelGGL(rrt_walk_kernel, dim3((unsigned)L), dim3(RRT_WAVE), 0, stream, a);
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
+    // (one goal slot, counted: [G][n][Q] with G = 1 is d_goal's [n][Q])
+    return plan(ch, ee_offset7, d_start, d_goal, nullptr, Q, 1, iters, step, resolution, first, max_nodes, Lmax, poll,
+                d_path, d_len, d_cost, d_status, d_iters, d_nodes, nullptr, (hipStream_t)stream_);
+}
+
+int optik_hip_rrt_plan_goals(optik_hip_chain *ch, const double *ee_offset7, const double *d_start,
+                             const double *d_goals, const int32_t *d_gcount, int64_t Q, int32_t G, int32_t iters,
+                             double step, double resolution, uint64_t first, int32_t max_nodes, int32_t Lmax,
+                             int32_t poll, double *d_path, int32_t *d_len, double *d_cost, int32_t *d_status,
+                             int32_t *d_iters, int32_t *d_nodes, int32_t *d_which, void *stream_) {
+    if (G < 1 || G > rrt::MAX_GOALS)
+        return fail(OPTIK_HIP_EINVAL, "rrt_plan_goals: G must be in 1 .. " + std::to_string(rrt::MAX_GOALS)
+                                          + " goals per query");
+    if (max_nodes < rrt::min_nodes(G) || max_nodes > rrt::MAX_NODES)
+        return fail(OPTIK_HIP_EINVAL, "rrt_plan_goals: max_nodes must be in max(2, G) .. "
+                                          + std::to_string(rrt::MAX_NODES) + ": every goal may be a root");
+    if (int rc = check_args(ch, Q, iters, step, resolution, max_nodes, Lmax, poll)) return rc;
+    if (ch->n < 1 || ch->n > OPTIK_HIP_MAX_DOF)
+        return fail(OPTIK_HIP_EUNSUPPORTED, "rrt_plan_goals: chains of 1 .. 16 joint positions");
+    if (Q == 0 || (!d_path && !d_len && !d_cost && !d_status && !d_iters && !d_nodes && !d_which)) return 0;
+    if (!d_start || !d_goals) return fail(OPTIK_HIP_EINVAL, "bad argument");  // (d_gcount null: G each)
+    return plan(ch, ee_offset7, d_start, d_goals, d_gcount, Q, G, iters, step, resolution, first, max_nodes, Lmax, poll,
+                d_path, d_len, d_cost, d_status, d_iters, d_nodes, d_which, (hipStream_t)stream_);
 }
 
 }  // extern "C"

@@ -76,6 +76,19 @@ void scatter_paths(double *paths_out, const double *h_out, size_t b0, size_t Lc,
     });
 }
 
+// What every plan wrapper downloads first per chunk -- the paths [Lmax][L][n], the costs [L], then len [L] and status
+// [L] int32 -- to the caller's rows b0 .. b0 + L (any may be null).  Returns the int32 words behind the status.
+const int32_t *scatter_plans(const double *h_out, size_t b0, size_t L, size_t Lmax, size_t n, double *paths_out,
+                             int32_t *len_out, double *cost_out, int32_t *status_out) {
+    const double *h_cost = h_out + Lmax * n * L;
+    const int32_t *h_len = reinterpret_cast<const int32_t *>(h_cost + L), *h_status = h_len + L;
+    if (paths_out) scatter_paths(paths_out, h_out, b0, L, Lmax, n);
+    if (cost_out) std::memcpy(cost_out + b0, h_cost, sizeof(double) * L);
+    if (len_out) std::memcpy(len_out + b0, h_len, sizeof(int32_t) * L);
+    if (status_out) std::memcpy(status_out + b0, h_status, sizeof(int32_t) * L);
+    return h_status + L;
+}
+
 }  // namespace
 
 extern "C" {
@@ -884,18 +897,7 @@ int optik_robot_roadmap_plan(const optik_robot *r, const double *starts, const d
                        ? 1 : 0;
         },
         [&](size_t b0, size_t L, const double *h_out) {
-            const double *h_cost = h_out + w * L;
-            const int32_t *h_len = reinterpret_cast<const int32_t *>(h_cost + L), *h_status = h_len + L;
-            if (paths_out)
-                parallel_ranges(L, [&](size_t k0, size_t k1) {
-                    for (size_t q = k0; q < k1; ++q)
-                        for (size_t t = 0; t < (size_t)Lmax; ++t)
-                            std::memcpy(paths_out + ((b0 + q) * (size_t)Lmax + t) * n, h_out + (t * L + q) * n,
-                                        sizeof(double) * n);
-                });
-            if (cost_out) std::memcpy(cost_out + b0, h_cost, sizeof(double) * L);
-            if (len_out) std::memcpy(len_out + b0, h_len, sizeof(int32_t) * L);
-            if (status_out) std::memcpy(status_out + b0, h_status, sizeof(int32_t) * L);
+            scatter_plans(h_out, b0, L, (size_t)Lmax, n, paths_out, len_out, cost_out, status_out);
         });
     if (stale) return set_err(-1, "roadmap_plan: the roadmap changed or went stale during the call");
     return rc;
@@ -983,19 +985,8 @@ int optik_robot_roadmap_plan_goals(const optik_robot *r, const double *starts, c
                        ? 1 : 0;
         },
         [&](size_t b0, size_t L, const double *h_out) {
-            const double *h_cost = h_out + w * L;
-            const int32_t *h_len = reinterpret_cast<const int32_t *>(h_cost + L), *h_status = h_len + L;
-            const int32_t *h_which = reinterpret_cast<const int32_t *>(h_cost + 2 * L);
-            if (paths_out)
-                parallel_ranges(L, [&](size_t k0, size_t k1) {
-                    for (size_t q = k0; q < k1; ++q)
-                        for (size_t t = 0; t < (size_t)Lmax; ++t)
-                            std::memcpy(paths_out + ((b0 + q) * (size_t)Lmax + t) * n, h_out + (t * L + q) * n,
-                                        sizeof(double) * n);
-                });
-            if (cost_out) std::memcpy(cost_out + b0, h_cost, sizeof(double) * L);
-            if (len_out) std::memcpy(len_out + b0, h_len, sizeof(int32_t) * L);
-            if (status_out) std::memcpy(status_out + b0, h_status, sizeof(int32_t) * L);
+            const int32_t *h_which =
+                scatter_plans(h_out, b0, L, (size_t)Lmax, n, paths_out, len_out, cost_out, status_out);
             if (goal_out) std::memcpy(goal_out + b0, h_which, sizeof(int32_t) * L);
         });
     if (stale) return set_err(-1, "roadmap_plan_goals: the roadmap changed or went stale during the call");
@@ -1139,18 +1130,7 @@ int optik_robot_roadmap_plan_lazy(const optik_robot *r, const double *starts, co
                 return 0;
             },
             [&](size_t b0, size_t L, const double *h_out) {
-                const double *h_cost = h_out + w * L;
-                const int32_t *h_len = reinterpret_cast<const int32_t *>(h_cost + L), *h_status = h_len + L;
-                if (paths_out)
-                    parallel_ranges(L, [&](size_t k0, size_t k1) {
-                        for (size_t q = k0; q < k1; ++q)
-                            for (size_t t = 0; t < (size_t)Lmax; ++t)
-                                std::memcpy(paths_out + ((b0 + q) * (size_t)Lmax + t) * n, h_out + (t * L + q) * n,
-                                            sizeof(double) * n);
-                    });
-                if (cost_out) std::memcpy(cost_out + b0, h_cost, sizeof(double) * L);
-                if (len_out) std::memcpy(len_out + b0, h_len, sizeof(int32_t) * L);
-                if (status_out) std::memcpy(status_out + b0, h_status, sizeof(int32_t) * L);
+                scatter_plans(h_out, b0, L, (size_t)Lmax, n, paths_out, len_out, cost_out, status_out);
             });
         if (changed) continue;
         if (rc) return rc;
@@ -1161,7 +1141,60 @@ int optik_robot_roadmap_plan_lazy(const optik_robot *r, const double *starts, co
     return set_err(-1, "roadmap_plan_lazy: the world or the roadmap kept changing during the call");
 }
 
-// Q queries through optik_hip_rrt_plan: no roadmap is read, so nothing can be stale.
+namespace {
+
+// The staging of both tree-planner wrappers, their arguments checked: G goal rows per query -- staged as [G][n][L],
+// which is how optik_hip_rrt_plan_goals takes them -- and the counts (null: every goal exists, nothing is uploaded).
+// No roadmap is read, so nothing can be stale.
+int rrt_plan_rows(const optik_robot *r, DeviceCtx *c, const double *starts, const double *goals, const int32_t *counts,
+                  int32_t G, int64_t Q, int32_t iters, double step, double resolution, uint64_t first,
+                  int32_t max_nodes, int32_t Lmax, int32_t poll, const double *ee16, double *paths_out,
+                  int32_t *len_out, double *cost_out, int32_t *status_out, int32_t *iters_out, int32_t *nodes_out,
+                  int32_t *goal_out) {
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    const size_t n = (size_t)r->n, w = (size_t)Lmax * n, uG = (size_t)G;
+    bool upload_failed = false;
+    int64_t done = 0;  // (the chunks come in order: the rows before this one)
+    // per query out: the path, the cost, then len and status in one more double, iters and the goal reached in
+    // another, the two tree sizes in a third; with counts the goal count and a spare word in a last one
+    const RowInput in[] = {{starts, n}, {goals, uG * n}};
+    const int rc = stage_rows(
+        c, Q, in, sizeof(double) * (w + (counts ? 5 : 4)), kPlanChunk,
+        [&](optik_hip_chain *ch, const double *d_s, int64_t L, double *d_out) -> int {
+            double *d_cost = d_out + w * (size_t)L;
+            int32_t *d_len = reinterpret_cast<int32_t *>(d_cost + L), *d_status = d_len + L, *d_it = d_status + L,
+                    *d_which = d_it + L, *d_nodes = d_which + L, *d_gcount = counts ? d_nodes + 2 * L : nullptr;
+            if (counts
+                && hipMemcpyAsync(d_gcount, counts + done, sizeof(int32_t) * (size_t)L, hipMemcpyHostToDevice, nullptr)
+                       != hipSuccess) {
+                upload_failed = true;
+                return 1;
+            }
+            done += L;
+            return optik_hip_rrt_plan_goals(ch, ee16 ? ee7 : nullptr, d_s, d_s + n * (size_t)L, d_gcount, L, G, iters,
+                                            step, resolution, first, max_nodes, Lmax, poll, d_out, d_len, d_cost,
+                                            d_status, d_it, d_nodes, d_which, nullptr);
+        },
+        [&](size_t b0, size_t L, const double *h_out) {
+            const int32_t *h_it = scatter_plans(h_out, b0, L, (size_t)Lmax, n, paths_out, len_out, cost_out, status_out),
+                          *h_which = h_it + L, *h_nodes = h_which + L;
+            if (iters_out) std::memcpy(iters_out + b0, h_it, sizeof(int32_t) * L);
+            if (goal_out) std::memcpy(goal_out + b0, h_which, sizeof(int32_t) * L);
+            if (nodes_out)
+                for (size_t q = 0; q < L; ++q) {
+                    nodes_out[2 * (b0 + q)] = h_nodes[q];
+                    nodes_out[2 * (b0 + q) + 1] = h_nodes[L + q];
+                }
+        });
+    if (upload_failed) return set_err(-1, "upload failed");
+    return rc;
+}
+
+}  // namespace
+
+// Q queries through the tree planner (include/optik.h): one goal row per query, every one
+// counted.
 int optik_robot_rrt_plan(const optik_robot *r, const double *starts, const double *goals, int64_t Q, int32_t iters,
                          double step, double resolution, uint64_t first, int32_t max_nodes, int32_t Lmax, int32_t poll,
                          const double *ee16, double *paths_out, int32_t *len_out, double *cost_out,
@@ -1175,47 +1208,11 @@ int optik_robot_rrt_plan(const optik_robot *r, const double *starts, const doubl
                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))
         return set_err(-1, optik_hip_last_error());
     if (Q == 0 || (!paths_out && !len_out && !cost_out && !status_out && !iters_out && !nodes_out)) return 0;
-    double ee7[7];
-    if (ee16) pose7_from_mat16(ee16, ee7);
-    const size_t n = (size_t)r->n, w = (size_t)Lmax * n;
-    // per query out: the path, the cost, then len and status in one more double, iters and a spare word in another,
-    // the two tree sizes in a last one
-    const RowInput in[] = {{starts, n}, {goals, n}};
-    return stage_rows(
-        c, Q, in, sizeof(double) * (w + 4), kPlanChunk,
-        [&](optik_hip_chain *ch, const double *d_s, int64_t L, double *d_out) {
-            double *d_cost = d_out + w * (size_t)L;
-            int32_t *d_len = reinterpret_cast<int32_t *>(d_cost + L), *d_status = d_len + L, *d_it = d_status + L,
-                    *d_nodes = d_it + 2 * L;
-            return optik_hip_rrt_plan(ch, ee16 ? ee7 : nullptr, d_s, d_s + n * (size_t)L, L, iters, step, resolution,
-                                      first, max_nodes, Lmax, poll, d_out, d_len, d_cost, d_status, d_it, d_nodes,
-                                      nullptr);
-        },
-        [&](size_t b0, size_t L, const double *h_out) {
-            const double *h_cost = h_out + w * L;
-            const int32_t *h_len = reinterpret_cast<const int32_t *>(h_cost + L), *h_status = h_len + L,
-                          *h_it = h_status + L, *h_nodes = h_it + 2 * L;
-            if (paths_out)
-                parallel_ranges(L, [&](size_t k0, size_t k1) {
-                    for (size_t q = k0; q < k1; ++q)
-                        for (size_t t = 0; t < (size_t)Lmax; ++t)
-                            std::memcpy(paths_out + ((b0 + q) * (size_t)Lmax + t) * n, h_out + (t * L + q) * n,
-                                        sizeof(double) * n);
-                });
-            if (cost_out) std::memcpy(cost_out + b0, h_cost, sizeof(double) * L);
-            if (len_out) std::memcpy(len_out + b0, h_len, sizeof(int32_t) * L);
-            if (status_out) std::memcpy(status_out + b0, h_status, sizeof(int32_t) * L);
-            if (iters_out) std::memcpy(iters_out + b0, h_it, sizeof(int32_t) * L);
-            if (nodes_out)
-                for (size_t q = 0; q < L; ++q) {
-                    nodes_out[2 * (b0 + q)] = h_nodes[q];
-                    nodes_out[2 * (b0 + q) + 1] = h_nodes[L + q];
-                }
-        });
+    return rrt_plan_rows(r, c, starts, goals, nullptr, 1, Q, iters, step, resolution, first, max_nodes, Lmax, poll, ee16,
+                         paths_out, len_out, cost_out, status_out, iters_out, nodes_out, nullptr);
 }
 
-// Q goal-set queries through optik_hip_rrt_plan_goals (include/optik.h): optik_robot_rrt_plan's
-// staging with G goal rows per query -- staged as [G][n][L], which is how the call takes them -- and the counts.
+// Q goal-set queries through optik_hip_rrt_plan_goals (include/optik.h).
 int optik_robot_rrt_plan_goals(const optik_robot *r, const double *starts, const double *goals, const int32_t *counts,
                                int32_t G, int64_t Q, int32_t iters, double step, double resolution, uint64_t first,
                                int32_t max_nodes, int32_t Lmax, int32_t poll, const double *ee16, double *paths_out,
@@ -1232,55 +1229,8 @@ int optik_robot_rrt_plan_goals(const optik_robot *r, const double *starts, const
         return set_err(-1, optik_hip_last_error());
     if (Q == 0 || (!paths_out && !len_out && !cost_out && !status_out && !iters_out && !nodes_out && !goal_out))
         return 0;
-    double ee7[7];
-    if (ee16) pose7_from_mat16(ee16, ee7);
-    const size_t n = (size_t)r->n, w = (size_t)Lmax * n, uG = (size_t)G;
-    bool upload_failed = false;
-    int64_t done = 0;  // (the chunks come in order: the rows before this one)
-    const std::vector<int32_t> all((size_t)(Q < kPlanChunk ? Q : kPlanChunk), G);  // counts NULL: every goal exists
-    // per query out: the path, the cost, then len and status in one more double, iters and the goal reached in
-    // another, the two tree sizes in a third, the goal count and a spare word in a last one
-    const RowInput in[] = {{starts, n}, {goals, uG * n}};
-    const int rc = stage_rows(
-        c, Q, in, sizeof(double) * (w + 5), kPlanChunk,
-        [&](optik_hip_chain *ch, const double *d_s, int64_t L, double *d_out) -> int {
-            double *d_cost = d_out + w * (size_t)L;
-            int32_t *d_len = reinterpret_cast<int32_t *>(d_cost + L), *d_status = d_len + L, *d_it = d_status + L,
-                    *d_which = d_it + L, *d_nodes = d_which + L, *d_gcount = d_nodes + 2 * L;
-            if (hipMemcpyAsync(d_gcount, counts ? counts + done : all.data(), sizeof(int32_t) * (size_t)L,
-                               hipMemcpyHostToDevice, nullptr) != hipSuccess) {
-                upload_failed = true;
-                return 1;
-            }
-            done += L;
-            return optik_hip_rrt_plan_goals(ch, ee16 ? ee7 : nullptr, d_s, d_s + n * (size_t)L, d_gcount, L, G, iters,
-                                            step, resolution, first, max_nodes, Lmax, poll, d_out, d_len, d_cost,
-                                            d_status, d_it, d_nodes, d_which, nullptr);
-        },
-        [&](size_t b0, size_t L, const double *h_out) {
-            const double *h_cost = h_out + w * L;
-            const int32_t *h_len = reinterpret_cast<const int32_t *>(h_cost + L), *h_status = h_len + L,
-                          *h_it = h_status + L, *h_which = h_it + L, *h_nodes = h_which + L;
-            if (paths_out)
-                parallel_ranges(L, [&](size_t k0, size_t k1) {
-                    for (size_t q = k0; q < k1; ++q)
-                        for (size_t t = 0; t < (size_t)Lmax; ++t)
-                            std::memcpy(paths_out + ((b0 + q) * (size_t)Lmax + t) * n, h_out + (t * L + q) * n,
-                                        sizeof(double) * n);
-                });
-            if (cost_out) std::memcpy(cost_out + b0, h_cost, sizeof(double) * L);
-            if (len_out) std::memcpy(len_out + b0, h_len, sizeof(int32_t) * L);
-            if (status_out) std::memcpy(status_out + b0, h_status, sizeof(int32_t) * L);
-            if (iters_out) std::memcpy(iters_out + b0, h_it, sizeof(int32_t) * L);
-            if (goal_out) std::memcpy(goal_out + b0, h_which, sizeof(int32_t) * L);
-            if (nodes_out)
-                for (size_t q = 0; q < L; ++q) {
-                    nodes_out[2 * (b0 + q)] = h_nodes[q];
-                    nodes_out[2 * (b0 + q) + 1] = h_nodes[L + q];
-                }
-        });
-    if (upload_failed) return set_err(-1, "upload failed");
-    return rc;
+    return rrt_plan_rows(r, c, starts, goals, counts, G, Q, iters, step, resolution, first, max_nodes, Lmax, poll, ee16,
+                         paths_out, len_out, cost_out, status_out, iters_out, nodes_out, goal_out);
 }
 
 int optik_robot_set_motion_resolution(optik_robot *r, double h) {

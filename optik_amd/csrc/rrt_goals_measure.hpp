@@ -1,5 +1,5 @@
 // rrt_goals_measure.hpp -- the rules of the bidirectional tree planner with a goal set, one source for the host and
-// the device (optik_hip_rrt_plan_goals, optik_hip.h; ik_rrt_goals.hip).
+// the device (optik_hip_rrt_plan_goals, optik_hip.h; ik_rrt.hip).
 //
 // rrt_measure.hpp's planner with G goal slots per query, 1 <= G <= 16, in place of the one goal -- the IK solutions of
 // a pose, for one: goals [G][n] and a count, clamped to 0 .. G (clamp_count).  Only the goals g < count exist; NOTHING

@@ -812,7 +812,7 @@ class HipChain:
                        poll=nat.RRT_POLL, ee_offset7=None):
         """rrt_plan with G goal slots per query (optik_hip_rrt_plan_goals): starts [n, Q], goals [G, n, Q], gcount [Q]
         int32 -- only the goals g < gcount exist, nothing of the others influences an output (the NaN rows of
-        ik_solutions past its count are the normal input).  Tree 1 has one root per counted goal that is free and the
+        ik_solutions past its count are the normal input); gcount None: G each.  Tree 1 has one root per counted goal that is free and the
         query ends at the first junction with any of them: past the direct motions (the nearest free one wins) the
         answer is the goal joined first, not the cheapest.  Returns rrt_plan's dict plus which [Q] int32, the goal
         reached (-1 unless status 0); a found path ends in that goal.  With G = 1 and gcount = 1 it is rrt_plan, bit
@@ -822,8 +822,9 @@ class HipChain:
         if not (isinstance(goals, torch.Tensor) and goals.is_cuda and goals.dtype == torch.float64 and goals.dim() == 3
                 and goals.shape[1] == self.n and goals.shape[2] == Q and goals.is_contiguous()):
             raise ValueError(f"goals must be a contiguous float64 cuda tensor [G, n, Q] = [G, {self.n}, {Q}]")
-        if not (isinstance(gcount, torch.Tensor) and gcount.is_cuda and gcount.dtype == torch.int32
-                and tuple(gcount.shape) == (Q,) and gcount.is_contiguous()):
+        if gcount is not None and not (isinstance(gcount, torch.Tensor) and gcount.is_cuda
+                                       and gcount.dtype == torch.int32 and tuple(gcount.shape) == (Q,)
+                                       and gcount.is_contiguous()):
             raise ValueError(f"gcount must be a contiguous int32 cuda tensor [{Q}]")
         iters, step, max_nodes, poll, first = nat.check_rrt_args(iters, step, max_nodes, Lmax, poll, first)
         G = nat.check_rrt_goals(int(goals.shape[0]), max_nodes)

@@ -212,6 +212,73 @@ def test_two_chunks(torch_dev, wall):
     _install(wall, model=False)
 
 
+def test_no_counts_is_every_slot_counted(torch_dev, wall):
+    """gcount None (a null d_gcount: every query's count is G) against gcount full of G, Q = 5, G = 3: every output
+    equal bit for bit (torch.equal on the words: query 4's cost and path are NaN).  A chunk holds hundreds of queries
+    whatever the arguments (optik_hip_rrt_chunk has no knob), so the run that splits the five puts them across the
+    border of a call's first chunk, behind and before rows whose start is in collision, which end before iteration 0."""
+    from optik_amd import _native as nat
+    torch, hc = torch_dev, wall["hc"]
+    _install(wall)
+    start, goal = wall["start"], wall["goal"]
+    inside, inside2, near, nan_goal = start.copy(), start.copy(), start.copy(), goal.copy()
+    inside[0], inside2[0], nan_goal[3] = 0.0, 0.05, math.nan
+    near[0] -= 0.2
+    goal2 = goal + np.array([0.2, 0.1, 0, 0.2, 0, 0, 0])
+    goals = np.array([[inside, goal, goal2],        # 0, 1: two far-side roots behind and before a blocked goal
+                      [goal2, goal, inside],
+                      [inside, near, goal],         # 2: a directly visible goal
+                      [inside, inside2, inside],    # 3: all goals in collision
+                      [goal, nan_goal, near]])      # 4: a NaN in a goal, which is counted here
+    starts = np.tile(start, (5, 1))
+
+    def both(S, Gs, **args):
+        s = torch.from_numpy(np.ascontiguousarray(S.T)).cuda()
+        g = torch.from_numpy(np.ascontiguousarray(Gs.transpose(1, 2, 0))).cuda()
+        full = torch.full((len(S),), 3, dtype=torch.int32, device="cuda")
+        none, given = (hc.rrt_plan_goals(s, g, c, resolution=wall["h"], Lmax=64, **args) for c in (None, full))
+        torch.cuda.synchronize()
+        assert set(none) == set(given) == set(KEYS)
+        for key in KEYS:
+            a, b = none[key], given[key]
+            if a.dtype == torch.float64:
+                a, b = a.view(torch.int64), b.view(torch.int64)
+            assert torch.equal(a, b), key
+        return none
+
+    res = both(starts, goals, **WALL)
+    status, which = res["status"].cpu().numpy(), res["which"].cpu().numpy()
+    print("no counts: status", status, "which", which, "iters", res["iters"].cpu().numpy())
+    assert status.tolist() == [tu.FOUND, tu.FOUND, tu.FOUND, tu.NO_ROUTE, tu.QUERY_NAN]
+    assert which[2] == 1 and which[0] in (1, 2) and which[1] in (0, 1) and (res["len"][:2] > 2).all()
+    # the five across two chunks of one call
+    chunk = nat.rrt_chunk(hc._h, 4096)
+    Q, at = chunk + 3, chunk - 2
+    S, Gs = np.tile(inside, (Q, 1)), np.tile(goals[3], (Q, 1, 1))
+    S[at:at + 5], Gs[at:at + 5] = starts, goals
+    split = both(S, Gs, **dict(WALL, max_nodes=4096))
+    alone = both(starts, goals, **dict(WALL, max_nodes=4096))
+    for key in KEYS:
+        a = split[key][:, at:at + 5] if split[key].dim() > 1 else split[key][at:at + 5]
+        if a.dtype == torch.float64:
+            a, alone[key] = a.contiguous().view(torch.int64), alone[key].view(torch.int64)
+        assert torch.equal(a, alone[key]), key
+    rest = np.ones(Q, dtype=bool)
+    rest[at:at + 5] = False
+    assert (split["status"].cpu().numpy()[rest] == tu.NO_ROUTE).all()
+    # the host-row entry point: counts None uploads nothing
+    robot = wall["robot"]
+    none, given = (robot.plan_rrt_to_goals(starts, goals, counts=c, resolution=wall["h"], max_waypoints=64, **WALL)
+                   for c in (None, [3] * 5))
+    assert set(none) == set(given)
+    for key in none:
+        assert torch.equal(torch.from_numpy(none[key].view(np.uint8)), torch.from_numpy(given[key].view(np.uint8))), key
+        dev = res["path" if key == "paths" else "which" if key == "goal" else key].cpu().numpy()
+        dev = dev.transpose(1, 0, 2) if key == "paths" else dev.T if key == "nodes" else dev
+        assert np.array_equal(np.ascontiguousarray(dev).view(np.uint8), none[key].view(np.uint8)), key
+    _install(wall, model=False)
+
+
 def test_caps(torch_dev, wall, sets_want):
     _install(wall)
     starts, goals, counts = _goal_sets(wall)
