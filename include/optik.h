@@ -409,6 +409,26 @@ int optik_robot_collision_motion_certify_batch(const optik_robot *robot, int64_t
                                                const double *xb, double tol, double grid_lipschitz,
                                                int32_t max_steps, const double *ee_offset16, int32_t *status_out,
                                                int32_t *steps_out, double *t_stop_out, double *clearance_out);
+/* Pose constraints (extension; include/optik_hip.h: optik_hip_constraint_batch and what precedes it; DESIGN.md section
+ * 5.29).  The constraint is ref7 (t, quaternion i j k w), lo6, hi6 with every call; rows x, xa, xb [B][n] row-major.
+ * optik_robot_constraint_batch -> residual_out [B][6], violation_out [B]; optik_robot_constraint_project_batch ->
+ * x_out [B][n], violation_out [B], status_out [B] (OPTIK_HIP_CONSTRAINT_*), iterations_out [B];
+ * optik_robot_constraint_motion_batch -> violation_out [B], ok_out [B], first_out [B], steps_out [B].  Any output may
+ * be NULL.  On the robot's first device through the staging loop of the other row batches, 262 144 rows (65 536
+ * segments) per launch.  rc 0, or -1: null argument, B < 0, and what the kernel layer refuses -- a reference that is
+ * not finite or whose quaternion is not of unit norm, lo <= hi false on an axis, tol not finite and >= 0, iters
+ * outside 0 .. 4096, damping < 0, max_step or resolution not finite and > 0, prismatic joints. */
+int optik_robot_constraint_batch(const optik_robot *robot, int64_t B, const double *x, const double *ref7,
+                                 const double *lo6, const double *hi6, const double *ee_offset16,
+                                 double *residual_out, double *violation_out);
+int optik_robot_constraint_project_batch(const optik_robot *robot, int64_t B, const double *x, const double *ref7,
+                                         const double *lo6, const double *hi6, double tol, int32_t iters,
+                                         double damping, double max_step, const double *ee_offset16, double *x_out,
+                                         double *violation_out, int32_t *status_out, int32_t *iterations_out);
+int optik_robot_constraint_motion_batch(const optik_robot *robot, int64_t B, const double *xa, const double *xb,
+                                        double resolution, const double *ref7, const double *lo6, const double *hi6,
+                                        double tol, const double *ee_offset16, double *violation_out, uint8_t *ok_out,
+                                        int32_t *first_out, int32_t *steps_out);
 int optik_robot_fk_ex(const optik_robot *robot, const double *x, const double *ee_offset16,
                       double *pose16_out);
 int optik_robot_joint_jacobian_ex(const optik_robot *robot, const double *x,

@@ -815,6 +815,53 @@ int optik_hip_collision_motion_certify_batch(const optik_hip_chain *chain, const
                                              double grid_lipschitz, int32_t max_steps, int32_t *d_status,
                                              int32_t *d_steps, double *d_t_stop, double *d_clearance, void *stream);
 
+/* Pose constraints (extension; csrc/constraint_measure.hpp states the arithmetic line by line).
+ *
+ * A pose constraint is a reference pose ref7 (t, quaternion i j k w) and a box lo6, hi6 on the pose error
+ * e(x) = (se3 log linear xyz, so3 log xyz) of X = ref^-1 * FK(x) * ee_offset -- the six numbers the IK objective forms
+ * before it weights them, with ref in the place of the target.  The residual is r_i = e_i - min(max(e_i, lo_i), hi_i),
+ * the violation max_i |r_i| (NaN if any e_i is NaN); lo_i = -inf and hi_i = +inf free an axis; x satisfies the
+ * constraint at tol >= 0 iff its violation is <= tol.  The constraint is an argument of every call (host pointers, read
+ * before the call returns); the chain keeps nothing of it.
+ *
+ * optik_hip_constraint_batch: d_q [n][B] -> d_residual [6][B], d_violation [B].
+ * optik_hip_constraint_project_batch: damped Gauss-Newton onto the constraint set from d_q [n][B], at most `iters`
+ *   steps of at most max_step (L-infinity, radians) each, every iterate clamped to the joint limits -> d_x [n][B],
+ *   d_violation [B] (at d_x), d_status [B] (OPTIK_HIP_CONSTRAINT_*: 0 projected -- the violation is <= tol and d_x lies
+ *   within the limits --, 1 the iterations are spent, 2 a NaN or infinite joint -- the row comes back as it went in --
+ *   or a failed factorisation), d_iterations [B] (steps taken; a row that satisfies the constraint comes back unchanged
+ *   after 0).  OPTIK_HIP_CONSTRAINT_ITERS, _DAMPING and _MAX_STEP are the defaults of the layers above (DESIGN.md
+ *   section 5.29 has the table they were read from).
+ * optik_hip_constraint_motion_batch: the segments d_qa, d_qb [n][B] sampled as optik_hip_collision_motion_batch samples
+ *   them at `resolution` -> d_violation [B] (the maximum over the samples, NaN if any sample's is), d_ok [B] (every
+ *   sample <= tol), d_first [B] (the lowest violating sample, -1: none), d_steps [B]; a motion that is not sampled gives
+ *   NaN, 0, -1, -1.  Nothing is projected: it says what holds at the samples.
+ *
+ * Any output may be NULL.  One row per lane, grid-stride, stream-ordered, no host synchronisation, no workspace, no
+ * atomics.  Revolute chains of 1 .. 16 joint positions.  Refused with OPTIK_HIP_EINVAL before any device work, also
+ * when B = 0: a NULL or non-finite ref7, a quaternion whose squared norm is further than 100 machine epsilons from 1,
+ * lo_i <= hi_i false on an axis (a NaN included), tol not finite and >= 0, B < 0, iters outside 0 ..
+ * OPTIK_HIP_CONSTRAINT_MAX_ITERS, damping not finite and >= 0, max_step or resolution not finite and > 0; with
+ * OPTIK_HIP_EUNSUPPORTED, also when B = 0: chains with prismatic joints (the motion check's message). */
+#define OPTIK_HIP_CONSTRAINT_PROJECTED 0
+#define OPTIK_HIP_CONSTRAINT_BUDGET 1
+#define OPTIK_HIP_CONSTRAINT_FAILED 2
+#define OPTIK_HIP_CONSTRAINT_MAX_ITERS 4096
+#define OPTIK_HIP_CONSTRAINT_ITERS 256
+#define OPTIK_HIP_CONSTRAINT_DAMPING 1e-6
+#define OPTIK_HIP_CONSTRAINT_MAX_STEP 0.5
+int optik_hip_constraint_batch(const optik_hip_chain *chain, const double *ee_offset7, const double *ref7,
+                               const double *lo6, const double *hi6, const double *d_q, int64_t B,
+                               double *d_residual, double *d_violation, void *stream);
+int optik_hip_constraint_project_batch(const optik_hip_chain *chain, const double *ee_offset7, const double *ref7,
+                                       const double *lo6, const double *hi6, const double *d_q, int64_t B, double tol,
+                                       int32_t iters, double damping, double max_step, double *d_x,
+                                       double *d_violation, int32_t *d_status, int32_t *d_iterations, void *stream);
+int optik_hip_constraint_motion_batch(const optik_hip_chain *chain, const double *ee_offset7, const double *ref7,
+                                      const double *lo6, const double *hi6, const double *d_qa, const double *d_qb,
+                                      int64_t B, double resolution, double tol, double *d_violation, uint8_t *d_ok,
+                                      int32_t *d_first, int32_t *d_steps, void *stream);
+
 /* Restart seeds: ChaCha8Rng::seed_from_u64(42), set_stream(i), one uniform draw
  * per joint (lib.rs:358-370, 86-91) for i = first .. first+count-1 -> d_q [n][count]. */
 int optik_hip_seed_batch(const optik_hip_chain *chain, uint64_t first, int64_t count, double *d_q,

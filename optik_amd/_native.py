@@ -157,6 +157,11 @@ def lib():
     L.optik_hip_chain_set_motion_resolution.argtypes = [vp, C.c_double]
     L.optik_hip_collision_motion_certify_batch.argtypes = [vp, dp, vp, vp, C.c_int64, C.c_double, C.c_double,
                                                            C.c_int32, vp, vp, vp, vp, vp]
+    L.optik_hip_constraint_batch.argtypes = [vp, dp, dp, dp, dp, vp, C.c_int64, vp, vp, vp]
+    L.optik_hip_constraint_project_batch.argtypes = [vp, dp, dp, dp, dp, vp, C.c_int64, C.c_double, C.c_int32,
+                                                     C.c_double, C.c_double, vp, vp, vp, vp, vp]
+    L.optik_hip_constraint_motion_batch.argtypes = [vp, dp, dp, dp, dp, vp, vp, C.c_int64, C.c_double, C.c_double, vp,
+                                                    vp, vp, vp, vp]
     L.optik_hip_diff_ik_batch.argtypes = [vp, dp, vp, vp, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, vp, vp]
     L.optik_hip_collision_witness_batch.argtypes = [vp, dp, vp, C.c_int64, vp, vp, vp, vp]
     L.optik_hip_diff_ik_avoid_batch.argtypes = [vp, dp, vp, vp, C.c_int64, vp, C.c_int64, C.c_int64, C.c_double,
@@ -227,6 +232,29 @@ def check_resolution(h, allow_zero=False):
     if not (math.isfinite(h) and (h > 0.0 or (allow_zero and h == 0.0))):
         raise ValueError("motion resolution must be finite and " + (">= 0" if allow_zero else "> 0") + f", got {h}")
     return h
+
+
+# include/optik_hip.h: OPTIK_HIP_CONSTRAINT_*; the statuses and defaults of optik_hip_constraint_project_batch
+CONSTRAINT_PROJECTED, CONSTRAINT_BUDGET, CONSTRAINT_FAILED = 0, 1, 2
+CONSTRAINT_MAX_ITERS = 4096
+CONSTRAINT_ITERS, CONSTRAINT_DAMPING, CONSTRAINT_MAX_STEP = 256, 1e-6, 0.5  # (the table)
+CONSTRAINT_TOL = 1e-6  # the default tol of the projection and the checks above it
+
+
+def check_constraint_tol(tol):
+    tol = float(tol)
+    if not (math.isfinite(tol) and tol >= 0.0):
+        raise ValueError(f"pose constraint: tol must be finite and >= 0, got {tol}")
+    return tol
+
+
+def check_project_args(tol, iters, damping, max_step):
+    tol, iters, damping, max_step = check_constraint_tol(tol), int(iters), float(damping), float(max_step)
+    if not 0 <= iters <= CONSTRAINT_MAX_ITERS:
+        raise ValueError(f"pose constraint: iters must be 0 .. {CONSTRAINT_MAX_ITERS}, got {iters}")
+    if not (math.isfinite(damping) and damping >= 0.0 and math.isfinite(max_step) and max_step > 0.0):
+        raise ValueError("pose constraint: needs damping >= 0 and max_step > 0, both finite")
+    return tol, iters, damping, max_step
 
 
 # include/optik_hip.h: OPTIK_HIP_CERTIFY_*; the statuses of optik_hip_collision_motion_certify_batch

@@ -18,8 +18,8 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "liboptik_amd.so")
-SOURCES = ["ik_capi.hip", "ik_select.hip", "ik_solutions.hip", "ik_path.hip", "ik_manip.hip", "ik_collision.hip", "ik_motion.hip", "ik_advance.hip", "ik_avoid.hip", "ik_path_optimize.hip", "ik_roadmap.hip", "ik_roadmap_lazy.hip", "ik_roadmap_goals.hip", "ik_rrt.hip", "ik_shortcut.hip", "ik_time.hip", "ik_occupancy.hip", "ik_depth.hip", "ik_mesh.hip", "ik_spherefit.hip", "ik_batch_ops.hip", "ik_quad_kernel.hip", "ik_lane_kernel.hip", "ik_wide_kernel.hip",
-           "robot_host.cpp", "robot_rows.cpp"]
+SOURCES = ["ik_capi.hip", "ik_select.hip", "ik_solutions.hip", "ik_path.hip", "ik_manip.hip", "ik_collision.hip", "ik_motion.hip", "ik_constraint.hip", "ik_advance.hip", "ik_avoid.hip", "ik_path_optimize.hip", "ik_roadmap.hip", "ik_roadmap_lazy.hip", "ik_roadmap_goals.hip", "ik_rrt.hip", "ik_shortcut.hip", "ik_time.hip", "ik_occupancy.hip", "ik_depth.hip", "ik_mesh.hip", "ik_spherefit.hip", "ik_batch_ops.hip", "ik_quad_kernel.hip", "ik_lane_kernel.hip", "ik_wide_kernel.hip",
+           "robot_host.cpp", "robot_rows.cpp", "robot_constraint.cpp"]
 # translation units: (source, object, extra flags).  ik_quad_kernel.hip is compiled twice -- its
 # throughput form (two waves per SIMD) without the machine-LICM pass, which otherwise hoists constants and
 # LDS addresses out of the solver loop only for the register allocator to spill them to scratch
@@ -31,6 +31,7 @@ UNITS = [("ik_capi.hip", "ik_capi.o", []),          # chains, options, the resta
          ("ik_manip.hip", "ik_manip.o", []),        # manipulability / condition keys and batch (modes 3, 4)
          ("ik_collision.hip", "ik_collision.o", []),  # collision filter: key pass, link frames, clearance batch
          ("ik_motion.hip", "ik_motion.o", []),      # motion check: segments between configurations, ik_path's key pass
+         ("ik_constraint.hip", "ik_constraint.o", []),  # pose constraints: residual, projection, check along a motion
          ("ik_advance.hip", "ik_advance.o", []),    # certified motion check: conservative advancement, a wave per segment
          ("ik_avoid.hip", "ik_avoid.o", []),        # clearance witnesses and gradients, diff_ik with velocity dampers
          ("ik_path_optimize.hip", "ik_path_optimize.o", []),  # covariant gradient smoothing of joint paths
@@ -66,7 +67,8 @@ UNITS = [("ik_capi.hip", "ik_capi.o", []),          # chains, options, the resta
          # chains with 9 .. 16 joint positions: one run-time-n body per kernel (ik_wide.hpp)
          ("ik_wide_kernel.hip", "ik_wide_kernel.o", []),
          ("robot_host.cpp", "robot_host.o", []),    # the robot object, devices, FK / Jacobian, ik and its batches
-         ("robot_rows.cpp", "robot_rows.o", [])]    # row batches, collision model / world setters, world builders
+         ("robot_rows.cpp", "robot_rows.o", []),    # row batches, collision model / world setters, world builders
+         ("robot_constraint.cpp", "robot_constraint.o", [])]  # the row batches of pose constraints
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
          "-Wno-unused-value", "-pthread"]
 # What a translation unit depends on is what the compiler says it read: every object is compiled with

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from .constraint import constraint_arrays
 
 
 def _stream_ptr():
@@ -579,6 +580,102 @@ class HipChain:
         gw = self.roadmap_edges(goals, nodes, gidx, resolution, reverse=True, ee_offset7=ee_offset7)
         direct = self.roadmap_edges(starts, goals, None, resolution, ee_offset7=ee_offset7)
         return self.roadmap_query(nodes, nbr, w, starts, goals, sidx, sw, gidx, gw, direct, Lmax)
+
+    # -- pose constraints (include/optik_hip.h) -------------------------------------------
+    def constraint_batch(self, q, c, ee_offset7=None):
+        """The residual [6, B] and the violation [B] of every column of q [n, B] against the pose constraint c
+        (optik_amd.PoseConstraint; csrc/constraint_measure.hpp).  Stream-ordered."""
+        B = self._check_q(q)
+        ref7, lo, hi = constraint_arrays(c)
+        ee = self._ee7(ee_offset7)
+        r = torch.empty((6, B), dtype=torch.float64, device=q.device)
+        v = torch.empty(B, dtype=torch.float64, device=q.device)
+        nat.check(nat.lib().optik_hip_constraint_batch(self._h, _dp(ee) if ee is not None else None, _dp(ref7), _dp(lo),
+                                                       _dp(hi), _ptr(q), B, _ptr(r), _ptr(v), _stream_ptr()))
+        return r, v
+
+    def constraint_project_batch(self, q, c, tol=nat.CONSTRAINT_TOL, iters=nat.CONSTRAINT_ITERS,
+                                 damping=nat.CONSTRAINT_DAMPING, max_step=nat.CONSTRAINT_MAX_STEP, ee_offset7=None):
+        """Damped Gauss-Newton from every column of q [n, B] onto the set where c holds at tol, inside the joint
+        limits: a dict of device tensors x [n, B], violation [B] (at x), status [B] int32 (nat.CONSTRAINT_PROJECTED:
+        the violation is <= tol and x lies within the limits; CONSTRAINT_BUDGET: `iters` steps were not enough;
+        CONSTRAINT_FAILED: a NaN or infinite joint, or a failed factorisation) and iterations [B] int32.  A column
+        that satisfies c comes back unchanged after 0 iterations.  Stream-ordered."""
+        B = self._check_q(q)
+        ref7, lo, hi = constraint_arrays(c)
+        tol, iters, damping, max_step = nat.check_project_args(tol, iters, damping, max_step)
+        ee = self._ee7(ee_offset7)
+        out = dict(x=torch.empty_like(q), violation=torch.empty(B, dtype=torch.float64, device=q.device),
+                   status=torch.empty(B, dtype=torch.int32, device=q.device),
+                   iterations=torch.empty(B, dtype=torch.int32, device=q.device))
+        nat.check(nat.lib().optik_hip_constraint_project_batch(
+            self._h, _dp(ee) if ee is not None else None, _dp(ref7), _dp(lo), _dp(hi), _ptr(q), B, tol, iters, damping,
+            max_step, _ptr(out["x"]), _ptr(out["violation"]), _ptr(out["status"]), _ptr(out["iterations"]),
+            _stream_ptr()))
+        return out
+
+    def constraint_motion_batch(self, qa, qb, resolution, c, tol=nat.CONSTRAINT_TOL, ee_offset7=None):
+        """The straight joint-space motions qa[:, b] -> qb[:, b] ([n, B]) sampled as collision_motion_batch samples
+        them, against the pose constraint c: (violation [B], ok [B] bool, first [B] int32, steps [B] int32) -- the
+        largest violation over the samples (NaN if any sample's is), whether every sample's is <= tol, the lowest
+        sample index that is not (-1: none), the number of steps K (-1: not sampled, then NaN and False).  One pass,
+        no projection: it says what holds at the samples.  Stream-ordered."""
+        B = self._check_q(qa)
+        if self._check_q(qb) != B or qb.device != qa.device:
+            raise ValueError(f"qa and qb must have the same shape and device, got {tuple(qa.shape)} and {tuple(qb.shape)}")
+        h = nat.check_resolution(resolution)
+        ref7, lo, hi = constraint_arrays(c)
+        tol = nat.check_constraint_tol(tol)
+        ee = self._ee7(ee_offset7)
+        v = torch.empty(B, dtype=torch.float64, device=qa.device)
+        ok = torch.empty(B, dtype=torch.uint8, device=qa.device)
+        first = torch.empty(B, dtype=torch.int32, device=qa.device)
+        steps = torch.empty(B, dtype=torch.int32, device=qa.device)
+        nat.check(nat.lib().optik_hip_constraint_motion_batch(
+            self._h, _dp(ee) if ee is not None else None, _dp(ref7), _dp(lo), _dp(hi), _ptr(qa), _ptr(qb), B, h, tol,
+            _ptr(v), _ptr(ok), _ptr(first), _ptr(steps), _stream_ptr()))
+        return v, ok.bool(), first, steps
+
+    def _constraint_mask(self, w, frm, nodes, idx, resolution, c, tol, reverse=False, ee_offset7=None):
+        """w [k, Q] with +inf wherever the motion frm[:, q] -> nodes[:, idx[s, q]] (reverse: node -> frm; idx None:
+        frm[:, q] -> nodes[:, q]) does not pass constraint_motion_batch.  Slots without a node (-1) keep their +inf;
+        device gathers, no host synchronisation."""
+        n, Q = frm.shape
+        if idx is None:
+            a, b = frm, nodes
+        else:
+            k = idx.shape[0]
+            a = frm.unsqueeze(1).expand(n, k, Q).reshape(n, k * Q).contiguous()
+            b = nodes[:, idx.clamp(min=0).reshape(-1).long()].contiguous()
+        if reverse:
+            a, b = b, a
+        ok = self.constraint_motion_batch(a, b, resolution, c, tol, ee_offset7=ee_offset7)[1].reshape(w.shape)
+        return torch.where(ok, w, torch.full_like(w, float("inf")))
+
+    def roadmap_build_constrained(self, nodes, k, resolution, c, tol=nat.CONSTRAINT_TOL, ee_offset7=None):
+        """roadmap_build with w = +inf wherever the motion node -> neighbour does not pass constraint_motion_batch at
+        tol.  The nodes are the caller's -- projected onto c, say; a NaN column joins nothing: roadmap_knn orders it
+        last and neither check samples it.  Returns (nbr [k, N] int32, w [k, N]).  No host synchronisation."""
+        nbr, w = self.roadmap_build(nodes, k, resolution, ee_offset7=ee_offset7)
+        return nbr, self._constraint_mask(w, nodes, nodes, nbr, resolution, c, tol, ee_offset7=ee_offset7)
+
+    def roadmap_plan_constrained(self, roadmap, starts, goals, ks, Lmax, resolution, c, tol=nat.CONSTRAINT_TOL,
+                                 ee_offset7=None):
+        """roadmap_plan's sequence over roadmap = (nodes, nbr, w) of roadmap_build_constrained, with the same mask
+        on the start links (start -> node), the goal links (node -> goal) and the direct motion.  So every segment of
+        a found path is a motion that passed the collision check and the constraint check in the direction of
+        travel, at the samples; a start or goal that violates c has no link and comes back with status 1.  Returns
+        roadmap_query's dict.  No host synchronisation."""
+        nodes, nbr, w = roadmap
+        sidx, _ = self.roadmap_knn(starts, nodes, ks)
+        gidx, _ = self.roadmap_knn(goals, nodes, ks)
+        sw = self.roadmap_edges(starts, nodes, sidx, resolution, ee_offset7=ee_offset7)
+        gw = self.roadmap_edges(goals, nodes, gidx, resolution, reverse=True, ee_offset7=ee_offset7)
+        direct = self.roadmap_edges(starts, goals, None, resolution, ee_offset7=ee_offset7)
+        sw = self._constraint_mask(sw, starts, nodes, sidx, resolution, c, tol, ee_offset7=ee_offset7)
+        gw = self._constraint_mask(gw, goals, nodes, gidx, resolution, c, tol, reverse=True, ee_offset7=ee_offset7)
+        direct = self._constraint_mask(direct, starts, goals, None, resolution, c, tol, ee_offset7=ee_offset7)
+        return self.roadmap_query(nodes, nbr, w, starts, goals, sidx, sw, gidx, gw, direct.reshape(-1), Lmax)
 
     # -- goal-set planning (include/optik_hip.h; DESIGN.md section 5.25) -------------------------------------------
     def _check_goal_slots(self, t, G, Q, name, dtype):

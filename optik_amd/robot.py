@@ -13,6 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _native as nat
+from .constraint import constraint_arrays
 
 U64_MAX = 0xFFFFFFFFFFFFFFFF
 
@@ -63,6 +64,11 @@ def _bind(L):
     L.optik_robot_collision_motion_batch.argtypes = [vp, C.c_int64, dp, dp, C.c_double, dp, dp, C.POINTER(C.c_uint8),
                                                      ip, ip]
     L.optik_robot_set_motion_resolution.argtypes = [vp, C.c_double]
+    L.optik_robot_constraint_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, dp, dp, dp]
+    L.optik_robot_constraint_project_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_double, C.c_int32,
+                                                       C.c_double, C.c_double, dp, dp, dp, ip, ip]
+    L.optik_robot_constraint_motion_batch.argtypes = [vp, C.c_int64, dp, dp, C.c_double, dp, dp, dp, C.c_double, dp,
+                                                      dp, C.POINTER(C.c_uint8), ip, ip]
     L.optik_robot_collision_motion_certify_batch.argtypes = [vp, C.c_int64, dp, dp, C.c_double, C.c_double, C.c_int32,
                                                              dp, ip, ip, dp, dp]
     L.optik_robot_diff_ik_ex.argtypes = [vp, dp, dp, dp, dp, C.POINTER(C.c_double), dp]
@@ -1486,6 +1492,164 @@ class Robot:
         with np.errstate(invalid="ignore"):
             clearance = np.where(np.isnan(clr).any(axis=1), np.nan, clr.min(axis=1, initial=np.inf))
         return dict(status=out_status, segment=seg, clearance=clearance)
+
+    # -- pose constraints (extension; include/optik.h) -------------------------------------
+    def constraint_batch_arrays(self, xs, c, ee_offset=None):
+        """(residual [B, 6], violation [B]) of B configurations xs [B, n] against the pose constraint c
+        (optik_amd.PoseConstraint): r_i = e_i - min(max(e_i, lo_i), hi_i) of the pose error against c's reference,
+        and max_i |r_i| (NaN for a NaN row).  x satisfies c at tol iff its violation is <= tol."""
+        xs = self._check_xs(xs)
+        ref7, lo, hi = constraint_arrays(c)
+        B = xs.shape[0]
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        r, v = np.zeros((B, 6)), np.zeros(B)
+        if self._L.optik_robot_constraint_batch(self._h, B, _dp(xs), _dp(ref7), _dp(lo), _dp(hi),
+                                                _dp(ee) if ee is not None else None, _dp(r), _dp(v)):
+            raise RuntimeError(_err(self._L))
+        return r, v
+
+    def constraint_project_batch_arrays(self, xs, c, tol=nat.CONSTRAINT_TOL, iters=nat.CONSTRAINT_ITERS,
+                                        damping=nat.CONSTRAINT_DAMPING, max_step=nat.CONSTRAINT_MAX_STEP,
+                                        ee_offset=None):
+        """Projects B configurations xs [B, n] onto the set where c holds at tol, inside the joint limits, by damped
+        Gauss-Newton (at most `iters` steps of at most max_step radians per joint): a dict of x [B, n], violation [B]
+        (at x), status [B] int32 -- 0 projected: the violation is <= tol and x lies within the limits; 1 the steps
+        are spent; 2 a NaN or infinite joint (the row comes back as it went in) or a failed factorisation -- and
+        iterations [B] int32.  A row that satisfies c comes back unchanged after 0 iterations.  The defaults of iters,
+        damping and max_step are the values read from one table (uniform Panda samples onto
+        upright(home, 0.1)); they are that and nothing more.  ValueError for a tol, iters, damping or max_step out of
+        range."""
+        xs = self._check_xs(xs)
+        ref7, lo, hi = constraint_arrays(c)
+        tol, iters, damping, max_step = nat.check_project_args(tol, iters, damping, max_step)
+        B, n = xs.shape
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        x, v = np.zeros((B, n)), np.zeros(B)
+        status, its = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        if self._L.optik_robot_constraint_project_batch(self._h, B, _dp(xs), _dp(ref7), _dp(lo), _dp(hi), tol, iters,
+                                                        damping, max_step, _dp(ee) if ee is not None else None,
+                                                        _dp(x), _dp(v), status.ctypes.data_as(ip),
+                                                        its.ctypes.data_as(ip)):
+            raise RuntimeError(_err(self._L))
+        return dict(x=x, violation=v, status=status, iterations=its)
+
+    def constraint_motion_batch_arrays(self, xa, xb, resolution, c, tol=nat.CONSTRAINT_TOL, ee_offset=None):
+        """The straight joint-space motions xa[b] -> xb[b] ([B, n] each), sampled as collision_motion_batch_arrays
+        samples them, against the pose constraint c: (violation [B], ok [B] bool, first [B] int32, steps [B] int32)
+        -- the largest violation over the samples (NaN if any sample's is), whether every sample's is <= tol, the
+        lowest sample index that is not (-1: none), and the number of steps (-1: not sampled; violation NaN, ok
+        False).  Nothing is projected: it says what holds at the samples."""
+        xa, xb = self._check_xs(xa), self._check_xs(xb)
+        if xa.shape != xb.shape:
+            raise ValueError(f"xa and xb must have the same shape, got {list(xa.shape)} and {list(xb.shape)}")
+        h = nat.check_resolution(resolution)
+        ref7, lo, hi = constraint_arrays(c)
+        tol = nat.check_constraint_tol(tol)
+        B = xa.shape[0]
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        v, ok = np.zeros(B), np.zeros(B, dtype=np.uint8)
+        first, steps = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        if self._L.optik_robot_constraint_motion_batch(self._h, B, _dp(xa), _dp(xb), h, _dp(ref7), _dp(lo), _dp(hi),
+                                                       tol, _dp(ee) if ee is not None else None, _dp(v),
+                                                       ok.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                       first.ctypes.data_as(ip), steps.ctypes.data_as(ip)):
+            raise RuntimeError(_err(self._L))
+        return v, ok.astype(bool), first, steps
+
+    def check_paths_constraint(self, paths, lens, c, tol=nat.CONSTRAINT_TOL, resolution=nat.ROADMAP_RESOLUTION,
+                               ee_offset=None):
+        """Whether P joint-space paths `paths` [P, L, n] with `lens` [P] waypoints each (None: L each) keep the pose
+        constraint c: the len - 1 segments of every path go through ONE constraint_motion_batch_arrays call.
+        shortcut_paths, resample_paths and optimize_paths know nothing of constraints; this tells whether their output
+        can still be used.  Returns a dict: violation [P], the largest over the path's segments (NaN if one of them is
+        NaN or not sampled, 0 without segments); ok [P] bool, every segment ok; segment [P] int32, the first segment
+        that is not, -1 when all are."""
+        paths, lens = self._check_paths(paths, lens)
+        P, L, n = paths.shape
+        lens = np.full(P, L, dtype=np.int32) if lens is None else lens
+        nseg = max(L - 1, 0)
+        valid = np.arange(nseg)[None, :] < (np.clip(lens, 0, L)[:, None] - 1)
+        v, ok = np.zeros((P, nseg)), np.ones((P, nseg), dtype=bool)
+        if valid.any():
+            sv, sok, _, _ = self.constraint_motion_batch_arrays(paths[:, :-1][valid], paths[:, 1:][valid], resolution,
+                                                                c, tol, ee_offset)
+            v[valid], ok[valid] = sv, sok
+        with np.errstate(invalid="ignore"):
+            worst = np.where(np.isnan(v).any(axis=1), np.nan, v.max(axis=1, initial=0.0))
+        bad = ~ok
+        seg = np.where(bad.any(axis=1), bad.argmax(axis=1) if nseg else 0, -1).astype(np.int32)
+        return dict(violation=worst, ok=~bad.any(axis=1), segment=seg)
+
+    def _device_chain(self):
+        """The robot's own device chain (optik_robot_hip_chain) behind the HipChain interface: it carries the
+        collision model and the world installed in the robot, which hip_chain()'s separate chain does not.  Borrowed:
+        the robot owns it."""
+        from .device import HipChain
+        hc = getattr(self, "_own_chain", None)
+        if hc is None:
+            import torch
+            h = self._L.optik_robot_hip_chain(self._h)
+            if not h:
+                raise RuntimeError(_err(self._L))
+
+            class _Borrowed(HipChain):
+                def close(self):
+                    self._h = C.c_void_p()
+
+            hc = _Borrowed.__new__(_Borrowed)
+            hc.device = torch.device("cuda", torch.cuda.current_device())
+            lb, ub = (np.ascontiguousarray(v, dtype=np.float64) for v in self.joint_limits())
+            hc.n, hc.lb, hc.ub, hc._h = len(lb), lb, ub, C.c_void_p(h)
+            self._own_chain = hc
+        return hc
+
+    def build_constrained_roadmap(self, c, tol=nat.CONSTRAINT_TOL, N=nat.ROADMAP_NODES, k=nat.ROADMAP_K,
+                                  resolution=nat.ROADMAP_RESOLUTION, first=0, **project):
+        """A roadmap whose every edge keeps the pose constraint c at tol, at the samples of `resolution`: N nodes
+        drawn as build_roadmap draws them (the IK restart seeds first .. first + N - 1), each projected onto c
+        (constraint_project_batch_arrays' method; **project: iters, damping, max_step), the ones that did not project
+        dropped (NaN columns: they join nothing), the rest joined to their k nearest others where the motion node ->
+        neighbour passes the collision check against the robot's model and world AND the constraint check.  Edges stay
+        straight in joint space; nothing between the samples is projected.
+        Returns the roadmap (optik_amd.constraint.ConstrainedRoadmap: device tensors, N, k, resolution, constraint,
+        tol, projected).  It is the caller's object, as a depth map is: a change of the world, the collision model or
+        the constraint needs a new one, and NO staleness guard exists here -- plan_constrained_paths plans over
+        whatever it is given.  It does not touch the roadmap of build_roadmap."""
+        import torch
+        from .constraint import ConstrainedRoadmap
+        nat.check_roadmap_args(N=N, k=k)
+        h = nat.check_resolution(resolution)
+        hc = self._device_chain()
+        seeds = hc.seed_batch(int(first), int(N))
+        p = hc.constraint_project_batch(seeds, c, tol, **project)
+        okp = p["status"] == nat.CONSTRAINT_PROJECTED
+        nodes = torch.where(okp[None, :], p["x"], torch.full_like(p["x"], float("nan"))).contiguous()
+        nbr, w = hc.roadmap_build_constrained(nodes, int(k), h, c, tol)
+        return ConstrainedRoadmap(nodes, nbr, w, h, c, tol, int(okp.sum().item()))
+
+    def plan_constrained_paths(self, roadmap, starts, goals, max_waypoints=nat.PATH_OPTIMIZE_MAX_WAYPOINTS):
+        """plan_paths over a roadmap of build_constrained_roadmap, for Q pairs starts[q] -> goals[q] ([Q, n] each):
+        the start links, the goal links and the direct motion pass the collision check and the roadmap's constraint
+        check, as its edges did.  So every segment of a found path is a motion that passed both checks in the
+        direction of travel, at the samples; a start or a goal that violates the constraint has no link and comes
+        back with status 1.  Returns plan_paths' dict (paths [Q, max_waypoints, n], len, cost, status).  The roadmap
+        is used as it is: rebuild it after a change of the world or the model."""
+        import torch
+        starts, goals = self._check_xs(starts), self._check_xs(goals)
+        if starts.shape != goals.shape:
+            raise ValueError(f"starts and goals must have the same shape, got {list(starts.shape)} and "
+                             f"{list(goals.shape)}")
+        nat.check_roadmap_args(max_waypoints=max_waypoints)
+        hc = self._device_chain()
+        dev = roadmap.nodes.device
+        s = torch.from_numpy(np.ascontiguousarray(starts.T)).to(dev)
+        g = torch.from_numpy(np.ascontiguousarray(goals.T)).to(dev)
+        r = hc.roadmap_plan_constrained((roadmap.nodes, roadmap.nbr, roadmap.w), s, g, min(roadmap.k, roadmap.N),
+                                        int(max_waypoints), roadmap.resolution, roadmap.constraint, roadmap.tol)
+        return dict(paths=np.ascontiguousarray(r["path"].cpu().numpy().transpose(1, 0, 2)),
+                    len=r["len"].cpu().numpy(), cost=r["cost"].cpu().numpy(), status=r["status"].cpu().numpy())
 
     def set_motion_resolution(self, h):
         """The resolution of ik_path*'s motion check (0, the default: off).  While it is > 0 and a collision model is
