@@ -350,6 +350,21 @@ int optik_robot_rrt_plan_goals(const optik_robot *robot, const double *starts, c
                                double resolution, uint64_t first, int32_t max_nodes, int32_t Lmax, int32_t poll,
                                const double *ee_offset16, double *paths_out, int32_t *len_out, double *cost_out,
                                int32_t *status_out, int32_t *iters_out, int32_t *nodes_out, int32_t *goal_out);
+/* The tree planner under a pose constraint (extension; include/optik_hip.h: optik_hip_rrt_plan_constrained; DESIGN.md
+ * section 5.30): optik_robot_rrt_plan_goals with every tree node projected onto the pose constraint (ref7, lo6, hi6:
+ * optik_robot_constraint_batch's) at ptol within piters iterations (damping, max_step: the projection's), and every
+ * motion checked against the collision model and against the constraint at tol, in the direction of travel.  A start
+ * that violates the constraint at tol gives status 1; a goal that does is not a root.  Outputs as
+ * optik_robot_rrt_plan_goals', and projected_out [Q][2]: the projections attempted and the ones that ended projected.
+ * One goal per query: G = 1, counts NULL.  rc 0, or -1: null argument, what the kernel layer refuses. */
+int optik_robot_rrt_plan_constrained(const optik_robot *robot, const double *starts, const double *goals,
+                                     const int32_t *counts, int32_t G, int64_t Q, const double *ref7, const double *lo6,
+                                     const double *hi6, double tol, double ptol, int32_t piters, double damping,
+                                     double max_step, int32_t iters, double step, double resolution, uint64_t first,
+                                     int32_t max_nodes, int32_t Lmax, int32_t poll, const double *ee_offset16,
+                                     double *paths_out, int32_t *len_out, double *cost_out, int32_t *status_out,
+                                     int32_t *iters_out, int32_t *nodes_out, int32_t *goal_out,
+                                     int32_t *projected_out);
 /* Shortcutting and resampling planned paths (extension; include/optik_hip.h: optik_hip_path_shortcut and
  * optik_hip_path_resample).  paths [P][L][n] row-major with lens [P] waypoints each (NULL: L
  * each), 2 <= L <= 64 -- optik_robot_roadmap_plan's paths_out and len_out as they are.

@@ -443,6 +443,51 @@ int optik_hip_rrt_plan_goals(optik_hip_chain *chain, const double *ee_offset7, c
                              int32_t poll, double *d_path, int32_t *d_len, double *d_cost, int32_t *d_status,
                              int32_t *d_iters, int32_t *d_nodes, int32_t *d_which, void *stream);
 
+/* The tree planner under a pose constraint (extension; the rules and their operation order:
+ * csrc/rrt_constrained_measure.hpp): optik_hip_rrt_plan_goals with every node projected onto the pose constraint
+ * (ref7, lo6, hi6: the constraint calls' below) before it joins a tree, and every motion judged by
+ * optik_hip_collision_motion_batch AND by optik_hip_constraint_motion_batch at tol, in the direction the path travels
+ * it -- a constrained bidirectional RRT, the fallback of a constrained roadmap's status-1 rows.  The rules are
+ * optik_hip_rrt_plan_goals' with these changes and no others:
+ *  - Before iteration 0 a configuration is free if it is free by optik_hip_collision_batch and its violation
+ *    (optik_hip_constraint_batch) is <= tol; a direct motion is free if both motion checks pass.  So a start that
+ *    violates the constraint gives status 1 and a counted goal that violates it is not a root; the order of the cases
+ *    is unchanged.
+ *  - The steered, clamped candidate c is projected: optik_hip_constraint_project_batch's method with tol = ptol,
+ *    iters = piters, damping, max_step.  The iteration does nothing if the status is not
+ *    OPTIK_HIP_CONSTRAINT_PROJECTED, or if the projection ran at least one iteration and its result equals the node p
+ *    it was steered from in every joint.  Otherwise the projected c' replaces c everywhere: the motion p - c' must pass
+ *    both checks, m is the nearest node of the other tree to c', a connection c' - m that passes both ends the query.
+ *  - The back-extension e = steer(m, c'), under optik_hip_rrt_plan's conditions on the distance of m and c', is
+ *    projected the same way; a projection that is not taken means no back-extension; the motion m - e' must pass both.
+ *  - The samples are the restart seeds first + i, not projected; route, status and padding are unchanged.
+ * d_projected [2][Q] int32: the projections attempted and those that ended OPTIK_HIP_CONSTRAINT_PROJECTED, candidates
+ * and back-extensions together, 0 where the iterations never began.  The other outputs are
+ * optik_hip_rrt_plan_goals'; any may be NULL.  The single-goal call is this one with G = 1, d_gcount NULL and d_which
+ * NULL.  With a box that is free on all six axes (lo = -inf, hi = +inf) every projection returns its input after 0
+ * iterations and every constraint verdict is ok wherever the motion is sampled: every shared output equals
+ * optik_hip_rrt_plan_goals' bit for bit.  Every node but the roots has violation <= ptol and lies inside the joint
+ * limits; between the nodes holds what the motion check found at its samples with tol -- edge interiors are not
+ * projected, so tol is the caller's statement and has no default.  OPTIK_HIP_RRT_PROJECT_ITERS is the default piters
+ * of the layers above (the table).
+ * An iteration is seven launches: this planner's step kernel with the projection inside, the motion check's five and
+ * optik_hip_constraint_motion_batch's one on the same 3 Q segments.  The extra workspace is a few bytes per query;
+ * optik_hip_rrt_chunk keeps its meaning.  A query's result does not depend on Q, on the chunking, on `poll` or on a
+ * launch shape, and is bit for bit rrt_constrained_measure.hpp's serial reference given the same samples, verdicts
+ * and projections.
+ * Refused before any device work: what optik_hip_rrt_plan_goals refuses; what the constraint calls refuse of the
+ * reference, the bounds and tol; ptol not finite and >= 0; piters outside 0 .. OPTIK_HIP_CONSTRAINT_MAX_ITERS; damping
+ * not finite and >= 0; max_step not finite and > 0; with OPTIK_HIP_EUNSUPPORTED, also when Q = 0: chains with prismatic
+ * joints.  Q = 0 is otherwise a no-op.  One call per chain handle at a time. */
+#define OPTIK_HIP_RRT_PROJECT_ITERS 16
+int optik_hip_rrt_plan_constrained(optik_hip_chain *chain, const double *ee_offset7, const double *ref7,
+                                   const double *lo6, const double *hi6, double tol, double ptol, int32_t piters,
+                                   double damping, double max_step, const double *d_start, const double *d_goals,
+                                   const int32_t *d_gcount, int64_t Q, int32_t G, int32_t iters, double step,
+                                   double resolution, uint64_t first, int32_t max_nodes, int32_t Lmax, int32_t poll,
+                                   double *d_path, int32_t *d_len, double *d_cost, int32_t *d_status, int32_t *d_iters,
+                                   int32_t *d_nodes, int32_t *d_which, int32_t *d_projected, void *stream);
+
 /* Path shortcutting and equal-spacing resampling (extension; the arithmetic and its operation
  * order: csrc/shortcut_measure.hpp).  Paths are d_path [Lin][P][n] -- the layout optik_hip_roadmap_query writes and
  * optik_hip_path_optimize reads --, path p having d_len[p] waypoints (d_len NULL: Lin each) and padding behind them

@@ -187,6 +187,10 @@ def lib():
                                      C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
     L.optik_hip_rrt_plan_goals.argtypes = [vp, dp, vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                            C.c_uint64, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.optik_hip_rrt_plan_constrained.argtypes = [vp, dp, dp, dp, dp, C.c_double, C.c_double, C.c_int32, C.c_double,
+                                                 C.c_double, vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, C.c_double,
+                                                 C.c_double, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp,
+                                                 vp, vp, vp, vp, vp]
     L.optik_hip_rrt_chunk.argtypes = [vp, C.c_int32]
     L.optik_hip_rrt_chunk.restype = C.c_int64
     L.optik_hip_path_shortcut.argtypes = [vp, dp, vp, vp, C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_double,
@@ -437,6 +441,11 @@ def check_rrt_goals(G, max_nodes):
         raise ValueError(f"max_nodes must be an integer in max(2, G) = {max(2, int(G))} .. {RRT_MAX_NODES}, "
                          f"got {max_nodes!r}")
     return int(G)
+
+
+# include/optik_hip.h: OPTIK_HIP_RRT_PROJECT_ITERS, the default budget of a projection inside the constrained tree
+# planner's extension (the table, and nothing more)
+RRT_PROJECT_ITERS = 16
 
 
 def rrt_chunk(chain_handle, max_nodes):

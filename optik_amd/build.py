@@ -38,7 +38,7 @@ UNITS = [("ik_capi.hip", "ik_capi.o", []),          # chains, options, the resta
          ("ik_roadmap.hip", "ik_roadmap.o", []),    # roadmap planning: nearest neighbours, checked edges, path queries
          ("ik_roadmap_lazy.hip", "ik_roadmap_lazy.o", []),  # lazy roadmaps: edges checked when a route uses them
          ("ik_roadmap_goals.hip", "ik_roadmap_goals.o", []),  # goal-set planning: routes to the nearest of several goals
-         ("ik_rrt.hip", "ik_rrt.o", []),            # bidirectional tree planner: two trees per query, one goal or a goal set
+         ("ik_rrt.hip", "ik_rrt.o", []),            # bidirectional tree planner: two trees per query, one goal or a goal set, under a pose constraint too
          ("ik_shortcut.hip", "ik_shortcut.o", []),  # path shortcutting over all-pairs visibility, resampling
          ("ik_time.hip", "ik_time.o", []),          # timing of joint paths under velocity / acceleration limits, sampling
          ("ik_occupancy.hip", "ik_occupancy.o", []),  # occupancy grids and point clouds into distance-field worlds

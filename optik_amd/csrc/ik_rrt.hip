@@ -32,6 +32,21 @@
 //                       writes the path; the goal slot of the root that tree 1's branch ends in is `which`, and the
 //                       path is padded with that goal.
 //
+// Under a pose constraint (rrt_constrained_measure.hpp; optik_hip_rrt_plan_constrained) the
+// same planner body runs with a constraint record (RrtConstraint), which swaps one kernel and adds two:
+//   rrt_mask_kernel     one thread per flag of rule 0: a configuration's collision flag is cleared where its violation
+//                       (optik_hip_constraint_batch on the same 1 + G columns) is not <= tol, a direct motion's where
+//                       optik_hip_constraint_motion_batch's ok byte is 0.  gather and begin stay as they are.
+//   rrt_cstep_kernel<CH>  rrt_step_kernel with the projection inside: CH is ChainDev or WideChainDev, the chain table
+//                       staged in LDS as ik_constraint.hip stages it.  The commit counts a segment only if the motion
+//                       check's flag AND constraint_motion's ok byte are set.  After the steer lane 0 runs
+//                       constraint::project on the candidate in LDS -- the header's own function, no barrier inside --
+//                       and leaves the verdict (rrt::takes) in LDS; every lane reads it after the barrier, so every
+//                       early exit stays wave-uniform.  The second search runs against the projected candidate, the
+//                       back-extension is projected the same way, and the two counters of d_projected are bumped by
+//                       lane 0 (one wave per query and one kernel after the other: no atomics).
+//   (optik_hip_constraint_motion_batch after the motion check, on the same 3 Qc segments: seven launches an iteration)
+//
 // Two launches of this unit's own per iteration would be one too many: the commit of iteration i and the search of
 // iteration i + 1 are one kernel, so an iteration is that kernel and the motion check's five.  No kernel waits for
 // another workgroup; every loop's trip count is bounded by a tree's size, n, G or Lmax; no private array is indexed
@@ -41,10 +56,12 @@
 #include <algorithm>
 
 #include "collision_device.hpp"
-#include "rrt_goals_measure.hpp"
+#include "constraint_measure.hpp"
+#include "rrt_constrained_measure.hpp"
 
 using namespace optik;
 using namespace optik::host;
+using namespace optik::hostparams;
 using namespace optik::colldev;
 
 static_assert(rrt::MAX_NODES == OPTIK_HIP_RRT_MAX_NODES && rrt::MAX_ITERS == OPTIK_HIP_RRT_MAX_ITERS
@@ -54,6 +71,9 @@ static_assert(rrt::MAX_NODES == OPTIK_HIP_RRT_MAX_NODES && rrt::MAX_ITERS == OPT
 static_assert(rrt::MAX_GOALS == OPTIK_HIP_RRT_MAX_GOALS && OPTIK_HIP_RRT_MAX_GOALS == OPTIK_HIP_ROADMAP_MAX_GOALS,
               "optik_hip.h states the cap of rrt_goals_measure.hpp; a goal set is what ik_solutions and the roadmap's "
               "goal-set query take");
+
+static_assert(rrt::PROJECTION_OK == constraint::PROJECTED && constraint::PROJECTED == OPTIK_HIP_CONSTRAINT_PROJECTED,
+              "rrt_constrained_measure.hpp names the projection's status without including constraint_measure.hpp");
 
 namespace {
 
@@ -90,6 +110,34 @@ struct RrtLaunch {
     int32_t *len, *status, *iters, *nodes, *which;  // [Q], nodes [2][Q]; or null
     double *cost;
 };
+
+// What a constrained call adds to the launch (kernel arguments of rrt_cstep_kernel and rrt_mask_kernel only: the
+// record above, and with it the kernels of the unconstrained planner, stay as they are).
+struct RrtConstraint {
+    const ChainDev *chain;       // n <= 8
+    const WideChainDev *wchain;  // 9 .. 16 joint positions
+    EvalParams ep;               // only the ee_offset part is used
+    constraint::Box c;
+    double tol, ptol, damping, max_step;
+    int piters;
+    double *viol;                // [(1 + G) Qc] optik_hip_constraint_batch's violations of cfg
+    uint8_t *cok;                // [3][Qc] optik_hip_constraint_motion_batch's ok bytes of the iteration's segments
+    uint8_t *cok0;               // [G Qc] and of the direct motions
+    int32_t *projected;          // [2][Q] the caller's, or null
+};
+
+// The host's side of it: the pointers the constraint entries take.
+struct ConstraintCall {
+    const double *ref7, *lo6, *hi6;
+    RrtConstraint k;
+};
+
+template <class CH>
+__device__ __forceinline__ const CH *table_of(const RrtConstraint &k);
+template <>
+__device__ __forceinline__ const ChainDev *table_of<ChainDev>(const RrtConstraint &k) { return k.chain; }
+template <>
+__device__ __forceinline__ const WideChainDev *table_of<WideChainDev>(const RrtConstraint &k) { return k.wchain; }
 
 __device__ __forceinline__ double *tree_conf(const RrtLaunch &a, long long q, int t) {
     return a.conf + ((size_t)q * 2 + t) * (size_t)a.n * a.M;
@@ -318,6 +366,187 @@ __global__ __launch_bounds__(RRT_WAVE) void rrt_step_kernel(const RrtLaunch a) {
     }
 }
 
+// Rule 0 under a constraint: "free" is free AND within the constraint.  (a NaN segment has both flags at 0 already)
+__global__ __launch_bounds__(RRT_BLOCK) void rrt_mask_kernel(const RrtLaunch a, const RrtConstraint k) {
+    const long long j = (long long)blockIdx.x * RRT_BLOCK + threadIdx.x;
+    const long long nc = (1 + a.G) * a.Qc, nm = (long long)a.G * a.Qc;
+    if (j < nc) {
+        if (!(k.viol[j] <= k.tol)) a.cflags[j] = 0;
+    } else if (j < nc + nm) {
+        if (k.cok0[j - nc] == 0) a.mflags[j - nc] = 0;
+    }
+}
+
+// Lane 0: project s_v [n] in place, and whether the result is taken as a node steered from column `from` of conf
+// [n][M] (rrt::takes).  s_take[0] = taken, s_take[1] = the projection ended PROJECTED.
+template <class CH>
+__device__ __forceinline__ void project_candidate(const CH &sch, const RrtConstraint &k, int n, int M,
+                                                  const double *conf, int from, double *s_v, int *s_take) {
+    const constraint::Projected pr =
+        constraint::project(sch, k.ep, k.c, n, k.ptol, k.piters, k.damping, k.max_step, s_v);
+    bool same = true;
+    for (int i = 0; i < n; ++i) same = same && s_v[i] == conf[(size_t)i * M + from];
+    s_take[0] = rrt::takes(pr.status, pr.iterations, same) ? 1 : 0;
+    s_take[1] = pr.status == constraint::PROJECTED ? 1 : 0;
+}
+
+__device__ __forceinline__ void count_projections(const RrtLaunch &a, const RrtConstraint &k, long long q,
+                                                  int attempted, int ended) {
+    if (!k.projected) return;
+    k.projected[a.q0 + q] += attempted;
+    k.projected[a.Q + a.q0 + q] += ended;
+}
+
+template <class CH>
+__global__ __launch_bounds__(RRT_WAVE) void rrt_cstep_kernel(const RrtLaunch a, const RrtConstraint k) {
+    __shared__ CH sch;
+    __shared__ double s_x[OPTIK_HIP_MAX_DOF], s_c[OPTIK_HIP_MAX_DOF], s_e[OPTIK_HIP_MAX_DOF];
+    __shared__ int s_take[4];
+    const long long q = blockIdx.x;
+    const int lane = threadIdx.x, n = a.n, M = a.M;
+    if (a.state[q] != rrt::RUNNING) return;  // (frozen: its segments are NaN already)
+    const long long B = 3 * a.Qc;
+    int cnt0 = a.count[q], cnt1 = a.count[a.Qc + q];
+    const bool joint = lane < n;
+    // ---- the iteration before: what the two checks said (rules 3 and 4) ----
+    if (a.iter > 0) {
+        const int pa = (a.iter - 1) & 1, pb = 1 - pa;
+        const int p = a.pend[q], m = a.pend[a.Qc + q], back = a.pend[2 * a.Qc + q];
+        const bool ok0 = a.flags[q] != 0 && k.cok[q] != 0, ok1 = a.flags[a.Qc + q] != 0 && k.cok[a.Qc + q] != 0,
+                   ok2 = a.flags[2 * a.Qc + q] != 0 && k.cok[2 * a.Qc + q] != 0;
+        int cnt_a = pa == 0 ? cnt0 : cnt1, cnt_b = pa == 0 ? cnt1 : cnt0;
+        if (p >= 0 && p < cnt_a && m >= 0 && m < cnt_b && cnt_a < M && ok0) {
+            // (segment 0 is p -> c for tree 0 and c -> p for tree 1)
+            if (joint) {
+                const double c = (pa == 0 ? a.qb : a.qa)[(long long)lane * B + q];
+                tree_conf(a, q, pa)[(size_t)lane * M + cnt_a] = c;
+            }
+            if (lane == 0) tree_parent(a, q, pa)[cnt_a] = p;
+            cnt_a += 1;
+            if (ok1) {
+                if (lane == 0) {
+                    a.junction[pa * a.Qc + q] = cnt_a - 1;
+                    a.junction[pb * a.Qc + q] = m;
+                    a.count[pa * a.Qc + q] = cnt_a;
+                    a.state[q] = rrt::FOUND;
+                    a.used[q] = a.iter;
+                    atomicSub(a.unfinished, 1);
+                }
+                if (joint) clear_segments(a, q, lane);
+                return;
+            }
+            if (back && ok2 && cnt_b < M) {
+                // (segment 2 is m -> e for tree 0 and e -> m for tree 1)
+                if (joint) {
+                    const double e = (pb == 0 ? a.qb : a.qa)[(long long)lane * B + 2 * a.Qc + q];
+                    tree_conf(a, q, pb)[(size_t)lane * M + cnt_b] = e;
+                }
+                if (lane == 0) tree_parent(a, q, pb)[cnt_b] = m;
+                cnt_b += 1;
+            }
+            cnt0 = pa == 0 ? cnt_a : cnt_b;
+            cnt1 = pa == 0 ? cnt_b : cnt_a;
+            if (lane == 0) {
+                a.count[q] = cnt0;
+                a.count[a.Qc + q] = cnt1;
+            }
+        }
+    }
+    if (a.iter >= a.I) {
+        // rule 6
+        if (lane == 0) {
+            a.state[q] = rrt::NO_ROUTE;
+            a.used[q] = a.I;
+            atomicSub(a.unfinished, 1);
+        }
+        if (joint) clear_segments(a, q, lane);
+        return;
+    }
+    // ---- this iteration: rules 1 to 4 ----
+    const int ta = a.iter & 1, tb = 1 - ta;
+    const int cnt_a = ta == 0 ? cnt0 : cnt1, cnt_b = ta == 0 ? cnt1 : cnt0;
+    const double *conf_a = tree_conf(a, q, ta), *conf_b = tree_conf(a, q, tb);
+    {
+        // the chain table (ik_constraint.hip's stage_table)
+        constexpr int ND = (int)(sizeof(CH) / sizeof(double));
+        static_assert(sizeof(CH) % sizeof(double) == 0, "the chain table is a whole number of doubles");
+        const double *src = reinterpret_cast<const double *>(table_of<CH>(k));
+        double *dst = reinterpret_cast<double *>(&sch);
+        for (int i = lane; i < ND; i += RRT_WAVE) dst[i] = src[i];
+    }
+    if (joint) s_x[lane] = a.samples[(long long)lane * a.I + a.iter];
+    __syncthreads();  // (also: the nodes appended above are visible to every lane)
+    double d, dm;
+    int p, m;
+    wave_nearest(conf_a, n, M, cnt_a, s_x, lane, d, p);
+    if (!rrt::steers(d) || cnt_a >= M || p < 0) {
+        if (lane == 0) a.pend[q] = -1;
+        if (joint) clear_segments(a, q, lane);
+        return;
+    }
+    double pj = 0.0, cj = 0.0, lo = 0.0, hi = 0.0;
+    if (joint) {
+        pj = conf_a[(size_t)lane * M + p];
+        lo = a.lo[lane];
+        hi = a.hi[lane];
+        s_c[lane] = rrt::steer_joint(pj, s_x[lane], d, a.eta, lo, hi);
+    }
+    __syncthreads();
+    if (lane == 0) project_candidate(sch, k, n, M, conf_a, p, s_c, s_take);
+    __syncthreads();
+    // (every lane reads the verdict from LDS before it branches on it)
+    if (s_take[0] == 0) {
+        if (lane == 0) {
+            a.pend[q] = -1;
+            count_projections(a, k, q, 1, s_take[1]);
+        }
+        if (joint) clear_segments(a, q, lane);
+        return;
+    }
+    if (joint) cj = s_c[lane];
+    wave_nearest(conf_b, n, M, cnt_b, s_c, lane, dm, m);
+    if (m < 0) {  // (a tree has its root: cannot happen)
+        if (lane == 0) {
+            a.pend[q] = -1;
+            count_projections(a, k, q, 1, s_take[1]);
+        }
+        if (joint) clear_segments(a, q, lane);
+        return;
+    }
+    bool back = rrt::extends_back(dm, a.eta, cnt_b, M);  // (wave-uniform: dm and cnt_b are)
+    int attempted = 1, ended = s_take[1];
+    double mj = 0.0, ej = roadmap::nan_value();
+    if (joint) mj = conf_b[(size_t)lane * M + m];
+    if (back) {
+        if (joint) s_e[lane] = rrt::steer_joint(mj, cj, dm, a.eta, lo, hi);
+        __syncthreads();
+        if (lane == 0) project_candidate(sch, k, n, M, conf_b, m, s_e, s_take + 2);
+        __syncthreads();
+        back = s_take[2] != 0;
+        attempted += 1;
+        ended += s_take[3];
+        if (back && joint) ej = s_e[lane];
+    }
+    if (joint) {
+        const double mb = back ? mj : roadmap::nan_value();
+        if (!back) ej = roadmap::nan_value();
+        double *qa = a.qa + (long long)lane * B + q, *qb = a.qb + (long long)lane * B + q;
+        // travel direction: tree 0 is walked parent -> child, tree 1 child -> parent, a connection tree 0 -> tree 1
+        qa[0] = ta == 0 ? pj : cj;
+        qb[0] = ta == 0 ? cj : pj;
+        qa[a.Qc] = ta == 0 ? cj : mj;
+        qb[a.Qc] = ta == 0 ? mj : cj;
+        qa[2 * a.Qc] = tb == 0 ? mb : ej;
+        qb[2 * a.Qc] = tb == 0 ? ej : mb;
+    }
+    if (lane == 0) {
+        a.pend[q] = p;
+        a.pend[a.Qc + q] = m;
+        a.pend[2 * a.Qc + q] = back ? 1 : 0;
+        count_projections(a, k, q, attempted, ended);
+    }
+}
+
 __global__ __launch_bounds__(RRT_WAVE) void rrt_walk_kernel(const RrtLaunch a) {
     __shared__ int s_way[roadmap::MAX_WAYPOINTS];  // waypoint t: node v of tree 0, or M + v of tree 1
     __shared__ int s_len, s_pad;                   // s_pad: the goal slot the path is padded with, -1 for the start
@@ -430,15 +659,22 @@ int check_args(const optik_hip_chain *ch, int64_t Q, int32_t iters, double step,
 // The iterations of the chunk a.q0, a.Qc whose begin kernel has run on `stream`: rrt_step_kernel and the motion check
 // over the 3 a.Qc segments per iteration, one read of *a.unfinished every `poll` iterations, and the last commit with
 // rule 6.  The walk kernel comes next on the stream.
-int run_iterations(optik_hip_chain *ch, const double *ee_offset7, RrtLaunch &a, int32_t iters, int32_t poll,
-                   double resolution, hipStream_t stream) {
+// Under a constraint (cc not null): rrt_cstep_kernel in its place and optik_hip_constraint_motion_batch after the motion check.
+int run_iterations(optik_hip_chain *ch, const double *ee_offset7, RrtLaunch &a, const ConstraintCall *cc, int32_t iters,
+                   int32_t poll, double resolution, hipStream_t stream) {
     const long long L = a.Qc;
     bool ended = false;
+    auto step = [&]() {
+        if (!cc) hipLaunchKernelGGL(rrt_step_kernel, dim3((unsigned)L), dim3(RRT_WAVE), 0, stream, a);
+        else if (ch->wide)
+            hipLaunchKernelGGL(rrt_cstep_kernel<WideChainDev>, dim3((unsigned)L), dim3(RRT_WAVE), 0, stream, a, cc->k);
+        else hipLaunchKernelGGL(rrt_cstep_kernel<ChainDev>, dim3((unsigned)L), dim3(RRT_WAVE), 0, stream, a, cc->k);
+    };
     for (int32_t i = 0; i < iters; ++i) {
         a.iter = i;
         {
             BIND_DEVICE(ch);
-            hipLaunchKernelGGL(rrt_step_kernel, dim3((unsigned)L), dim3(RRT_WAVE), 0, stream, a);
+            step();
             HIP_TRY(hipGetLastError());
             if (i % poll == 0) {
                 // (the one synchronise of a poll: the host decides whether the iterations go on)
@@ -451,11 +687,16 @@ int run_iterations(optik_hip_chain *ch, const double *ee_offset7, RrtLaunch &a, 
         if (int rc = optik_hip_collision_motion_batch(ch, ee_offset7, a.qa, a.qb, 3 * L, resolution, nullptr, a.flags,
                                                       nullptr, nullptr, stream))
             return rc;
+        if (cc)
+            if (int rc = optik_hip_constraint_motion_batch(ch, ee_offset7, cc->ref7, cc->lo6, cc->hi6, a.qa, a.qb, 3 * L,
+                                                           resolution, cc->k.tol, nullptr, cc->k.cok, nullptr, nullptr,
+                                                           stream))
+                return rc;
     }
     BIND_DEVICE(ch);
     if (!ended) {
         a.iter = iters;  // (the last iteration's commit, and rule 6)
-        hipLaunchKernelGGL(rrt_step_kernel, dim3((unsigned)L), dim3(RRT_WAVE), 0, stream, a);
+        step();
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -475,7 +716,8 @@ struct Carve {
 // The workspace of a call in chunks of Qc queries -- the samples, rule 0's configurations, direct motions and flags,
 // the iteration's segments and flags, the per-query state and the trees -- into the record; returns its size.
 // (a chunk's arrays are [..][L] with L <= Qc: a later chunk may be shorter, never longer)
-size_t carve_workspace(RrtLaunch &a, unsigned char *ws, size_t Qc) {
+// Under a constraint its few bytes per query follow: the violations of rule 0's configurations and the ok bytes.
+size_t carve_workspace(RrtLaunch &a, ConstraintCall *cc, unsigned char *ws, size_t Qc) {
     const size_t n = (size_t)a.n, M = (size_t)a.M, I = (size_t)a.I, G = (size_t)a.G;
     Carve c{reinterpret_cast<uintptr_t>(ws)};
     c.take(a.unfinished, 1);
@@ -497,11 +739,16 @@ size_t carve_workspace(RrtLaunch &a, unsigned char *ws, size_t Qc) {
     c.take(a.root_goal, G * Qc);
     c.take(a.parent, 2 * M * Qc);
     c.take(a.conf, 2 * n * M * Qc);
+    if (cc) {
+        c.take(cc->k.viol, (1 + G) * Qc);
+        c.take(cc->k.cok, 3 * Qc + G * Qc);  // (the iterations' three ok bytes per query, then rule 0's G)
+    }
     return c.at;
 }
 
-// The planner of both calls, their arguments checked: d_goals [G][n][Q]; d_gcount null: G each; d_which may be null.
-int plan(optik_hip_chain *ch, const double *ee_offset7, const double *d_start, const double *d_goals,
+// The planner of all three calls, their arguments checked: d_goals [G][n][Q]; d_gcount null: G each; d_which may be
+// null; cc null: no constraint.
+int plan(optik_hip_chain *ch, const double *ee_offset7, ConstraintCall *cc, const double *d_start, const double *d_goals,
          const int32_t *d_gcount, int64_t Q, int32_t G, int32_t iters, double step, double resolution, uint64_t first,
          int32_t max_nodes, int32_t Lmax, int32_t poll, double *d_path, int32_t *d_len, double *d_cost,
          int32_t *d_status, int32_t *d_iters, int32_t *d_nodes, int32_t *d_which, hipStream_t stream) {
@@ -514,12 +761,14 @@ int plan(optik_hip_chain *ch, const double *ee_offset7, const double *d_start, c
     a.hi = ch->wide ? ch->wdev->ub : ch->dev->ub;
     a.path = d_path; a.len = d_len; a.cost = d_cost; a.status = d_status; a.iters = d_iters; a.nodes = d_nodes;
     a.which = d_which;
-    const size_t bytes = carve_workspace(a, nullptr, Qc);
+    const size_t bytes = carve_workspace(a, cc, nullptr, Qc);
     {
         std::lock_guard<std::mutex> lock(ch->mu);
         BIND_DEVICE(ch);
         HIP_TRY(ch->rrt_ws.reserve(bytes));
-        carve_workspace(a, ch->rrt_ws.get(), Qc);
+        carve_workspace(a, cc, ch->rrt_ws.get(), Qc);
+        // (0 where the iterations never begin; rrt_cstep_kernel adds to it)
+        if (cc && cc->k.projected) HIP_TRY(hipMemsetAsync(cc->k.projected, 0, sizeof(int32_t) * 2 * (size_t)Q, stream));
     }
     // (the samples of the whole call: iteration i reads restart seed first + i, whatever the query)
     if (int rc = optik_hip_seed_batch(ch, first, iters, const_cast<double *>(a.samples), stream)) return rc;
@@ -528,6 +777,7 @@ int plan(optik_hip_chain *ch, const double *ee_offset7, const double *d_start, c
         a.q0 = q0; a.Qc = L;
         a.qb = a.qa + (size_t)a.n * 3 * (size_t)L;
         a.mflags = a.cflags + (1 + uG) * (size_t)L;
+        if (cc) cc->k.cok0 = cc->k.cok + 3 * (size_t)L;
         {
             BIND_DEVICE(ch);
             HIP_TRY(hipMemsetAsync(a.unfinished, 0, sizeof(int32_t), stream));
@@ -538,12 +788,25 @@ int plan(optik_hip_chain *ch, const double *ee_offset7, const double *d_start, c
         if (int rc = optik_hip_collision_motion_batch(ch, ee_offset7, a.da, a.db, G * L, resolution, nullptr, a.mflags,
                                                       nullptr, nullptr, stream))
             return rc;
+        if (cc) {
+            if (int rc = optik_hip_constraint_batch(ch, ee_offset7, cc->ref7, cc->lo6, cc->hi6, a.cfg, (1 + G) * L, nullptr,
+                                                    cc->k.viol, stream))
+                return rc;
+            if (int rc = optik_hip_constraint_motion_batch(ch, ee_offset7, cc->ref7, cc->lo6, cc->hi6, a.da, a.db, G * L,
+                                                           resolution, cc->k.tol, nullptr, cc->k.cok0, nullptr, nullptr,
+                                                           stream))
+                return rc;
+            BIND_DEVICE(ch);
+            hipLaunchKernelGGL(rrt_mask_kernel, dim3(blocks((1 + 2 * (long long)G) * L)), dim3(RRT_BLOCK), 0, stream, a,
+                               cc->k);
+            HIP_TRY(hipGetLastError());
+        }
         {
             BIND_DEVICE(ch);
             hipLaunchKernelGGL(rrt_begin_kernel, dim3(blocks(L)), dim3(RRT_BLOCK), 0, stream, a);
             HIP_TRY(hipGetLastError());
         }
-        if (int rc = run_iterations(ch, ee_offset7, a, iters, poll, resolution, stream)) return rc;
+        if (int rc = run_iterations(ch, ee_offset7, a, cc, iters, poll, resolution, stream)) return rc;
         BIND_DEVICE(ch);
         hipLaunchKernelGGL(rrt_walk_kernel, dim3((unsigned)L), dim3(RRT_WAVE), 0, stream, a);
         HIP_TRY(hipGetLastError());
@@ -571,7 +834,7 @@ int optik_hip_rrt_plan(optik_hip_chain *ch, const double *ee_offset7, const doub
     if (Q == 0 || (!d_path && !d_len && !d_cost && !d_status && !d_iters && !d_nodes)) return 0;
     if (!d_start || !d_goal) return fail(OPTIK_HIP_EINVAL, "bad argument");
     // (one goal slot, counted: [G][n][Q] with G = 1 is d_goal's [n][Q])
-    return plan(ch, ee_offset7, d_start, d_goal, nullptr, Q, 1, iters, step, resolution, first, max_nodes, Lmax, poll,
+    return plan(ch, ee_offset7, nullptr, d_start, d_goal, nullptr, Q, 1, iters, step, resolution, first, max_nodes, Lmax, poll,
                 d_path, d_len, d_cost, d_status, d_iters, d_nodes, nullptr, (hipStream_t)stream_);
 }
 
@@ -591,8 +854,51 @@ int optik_hip_rrt_plan_goals(optik_hip_chain *ch, const double *ee_offset7, cons
         return fail(OPTIK_HIP_EUNSUPPORTED, "rrt_plan_goals: chains of 1 .. 16 joint positions");
     if (Q == 0 || (!d_path && !d_len && !d_cost && !d_status && !d_iters && !d_nodes && !d_which)) return 0;
     if (!d_start || !d_goals) return fail(OPTIK_HIP_EINVAL, "bad argument");  // (d_gcount null: G each)
-    return plan(ch, ee_offset7, d_start, d_goals, d_gcount, Q, G, iters, step, resolution, first, max_nodes, Lmax, poll,
-                d_path, d_len, d_cost, d_status, d_iters, d_nodes, d_which, (hipStream_t)stream_);
+    return plan(ch, ee_offset7, nullptr, d_start, d_goals, d_gcount, Q, G, iters, step, resolution, first, max_nodes,
+                Lmax, poll, d_path, d_len, d_cost, d_status, d_iters, d_nodes, d_which, (hipStream_t)stream_);
+}
+
+int optik_hip_rrt_plan_constrained(optik_hip_chain *ch, const double *ee_offset7, const double *ref7, const double *lo6,
+                                   const double *hi6, double tol, double ptol, int32_t piters, double damping,
+                                   double max_step, const double *d_start, const double *d_goals,
+                                   const int32_t *d_gcount, int64_t Q, int32_t G, int32_t iters, double step,
+                                   double resolution, uint64_t first, int32_t max_nodes, int32_t Lmax, int32_t poll,
+                                   double *d_path, int32_t *d_len, double *d_cost, int32_t *d_status, int32_t *d_iters,
+                                   int32_t *d_nodes, int32_t *d_which, int32_t *d_projected, void *stream_) {
+    if (G < 1 || G > rrt::MAX_GOALS)
+        return fail(OPTIK_HIP_EINVAL, "rrt_plan_constrained: G must be in 1 .. " + std::to_string(rrt::MAX_GOALS)
+                                          + " goals per query");
+    if (max_nodes < rrt::min_nodes(G) || max_nodes > rrt::MAX_NODES)
+        return fail(OPTIK_HIP_EINVAL, "rrt_plan_constrained: max_nodes must be in max(2, G) .. "
+                                          + std::to_string(rrt::MAX_NODES) + ": every goal may be a root");
+    if (int rc = check_args(ch, Q, iters, step, resolution, max_nodes, Lmax, poll)) return rc;
+    // (B = 0: the constraint entries' own refusals -- the reference, the bounds, tol; ptol, piters, damping, max_step)
+    if (int rc = optik_hip_constraint_motion_batch(ch, nullptr, ref7, lo6, hi6, nullptr, nullptr, 0, resolution, tol,
+                                                   nullptr, nullptr, nullptr, nullptr, nullptr))
+        return rc;
+    if (int rc = optik_hip_constraint_project_batch(ch, nullptr, ref7, lo6, hi6, nullptr, 0, ptol, piters, damping,
+                                                    max_step, nullptr, nullptr, nullptr, nullptr, nullptr))
+        return rc;
+    if (ch->n < 1 || ch->n > OPTIK_HIP_MAX_DOF)
+        return fail(OPTIK_HIP_EUNSUPPORTED, "rrt_plan_constrained: chains of 1 .. 16 joint positions");
+    if (Q == 0
+        || (!d_path && !d_len && !d_cost && !d_status && !d_iters && !d_nodes && !d_which && !d_projected))
+        return 0;
+    if (!d_start || !d_goals) return fail(OPTIK_HIP_EINVAL, "bad argument");  // (d_gcount null: G each)
+    ConstraintCall cc;
+    std::memset(&cc, 0, sizeof cc);
+    cc.ref7 = ref7; cc.lo6 = lo6; cc.hi6 = hi6;
+    cc.k.chain = ch->dev;
+    cc.k.wchain = ch->wdev;
+    const double one[3] = {1, 1, 1};
+    make_eval_params(one, one, ee_offset7, cc.k.ep);
+    std::memcpy(cc.k.c.ref, ref7, sizeof cc.k.c.ref);
+    std::memcpy(cc.k.c.lo, lo6, sizeof cc.k.c.lo);
+    std::memcpy(cc.k.c.hi, hi6, sizeof cc.k.c.hi);
+    cc.k.tol = tol; cc.k.ptol = ptol; cc.k.piters = piters; cc.k.damping = damping; cc.k.max_step = max_step;
+    cc.k.projected = d_projected;
+    return plan(ch, ee_offset7, &cc, d_start, d_goals, d_gcount, Q, G, iters, step, resolution, first, max_nodes, Lmax,
+                poll, d_path, d_len, d_cost, d_status, d_iters, d_nodes, d_which, (hipStream_t)stream_);
 }
 
 }  // extern "C"

@@ -1145,8 +1145,17 @@ namespace {
 
 // The staging of both tree-planner wrappers, their arguments checked: G goal rows per query -- staged as [G][n][L],
 // which is how optik_hip_rrt_plan_goals takes them -- and the counts (null: every goal exists, nothing is uploaded).
-// No roadmap is read, so nothing can be stale.
-int rrt_plan_rows(const optik_robot *r, DeviceCtx *c, const double *starts, const double *goals, const int32_t *counts,
+// No roadmap is read, so nothing can be stale.  With a constraint (con not null) the call is
+// optik_hip_rrt_plan_constrained and every query has one more double out, its two projection counters.
+struct RrtRowsConstraint {
+    const double *ref7, *lo6, *hi6;
+    double tol, ptol, damping, max_step;
+    int32_t piters;
+    int32_t *projected_out;  // [Q][2] or null
+};
+
+int rrt_plan_rows(const optik_robot *r, DeviceCtx *c, const RrtRowsConstraint *con, const double *starts,
+                  const double *goals, const int32_t *counts,
                   int32_t G, int64_t Q, int32_t iters, double step, double resolution, uint64_t first,
                   int32_t max_nodes, int32_t Lmax, int32_t poll, const double *ee16, double *paths_out,
                   int32_t *len_out, double *cost_out, int32_t *status_out, int32_t *iters_out, int32_t *nodes_out,
@@ -1160,7 +1169,7 @@ int rrt_plan_rows(const optik_robot *r, DeviceCtx *c, const double *starts, cons
     // another, the two tree sizes in a third; with counts the goal count and a spare word in a last one
     const RowInput in[] = {{starts, n}, {goals, uG * n}};
     const int rc = stage_rows(
-        c, Q, in, sizeof(double) * (w + (counts ? 5 : 4)), kPlanChunk,
+        c, Q, in, sizeof(double) * (w + (counts ? 5 : 4) + (con ? 1 : 0)), kPlanChunk,
         [&](optik_hip_chain *ch, const double *d_s, int64_t L, double *d_out) -> int {
             double *d_cost = d_out + w * (size_t)L;
             int32_t *d_len = reinterpret_cast<int32_t *>(d_cost + L), *d_status = d_len + L, *d_it = d_status + L,
@@ -1172,6 +1181,12 @@ int rrt_plan_rows(const optik_robot *r, DeviceCtx *c, const double *starts, cons
                 return 1;
             }
             done += L;
+            if (con)
+                return optik_hip_rrt_plan_constrained(ch, ee16 ? ee7 : nullptr, con->ref7, con->lo6, con->hi6, con->tol,
+                                                      con->ptol, con->piters, con->damping, con->max_step, d_s,
+                                                      d_s + n * (size_t)L, d_gcount, L, G, iters, step, resolution, first,
+                                                      max_nodes, Lmax, poll, d_out, d_len, d_cost, d_status, d_it,
+                                                      d_nodes, d_which, d_nodes + (counts ? 4 : 2) * L, nullptr);
             return optik_hip_rrt_plan_goals(ch, ee16 ? ee7 : nullptr, d_s, d_s + n * (size_t)L, d_gcount, L, G, iters,
                                             step, resolution, first, max_nodes, Lmax, poll, d_out, d_len, d_cost,
                                             d_status, d_it, d_nodes, d_which, nullptr);
@@ -1186,6 +1201,13 @@ int rrt_plan_rows(const optik_robot *r, DeviceCtx *c, const double *starts, cons
                     nodes_out[2 * (b0 + q)] = h_nodes[q];
                     nodes_out[2 * (b0 + q) + 1] = h_nodes[L + q];
                 }
+            if (con && con->projected_out) {
+                const int32_t *h_proj = h_nodes + (counts ? 4 : 2) * L;
+                for (size_t q = 0; q < L; ++q) {
+                    con->projected_out[2 * (b0 + q)] = h_proj[q];
+                    con->projected_out[2 * (b0 + q) + 1] = h_proj[L + q];
+                }
+            }
         });
     if (upload_failed) return set_err(-1, "upload failed");
     return rc;
@@ -1208,7 +1230,7 @@ int optik_robot_rrt_plan(const optik_robot *r, const double *starts, const doubl
                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))
         return set_err(-1, optik_hip_last_error());
     if (Q == 0 || (!paths_out && !len_out && !cost_out && !status_out && !iters_out && !nodes_out)) return 0;
-    return rrt_plan_rows(r, c, starts, goals, nullptr, 1, Q, iters, step, resolution, first, max_nodes, Lmax, poll, ee16,
+    return rrt_plan_rows(r, c, nullptr, starts, goals, nullptr, 1, Q, iters, step, resolution, first, max_nodes, Lmax, poll, ee16,
                          paths_out, len_out, cost_out, status_out, iters_out, nodes_out, nullptr);
 }
 
@@ -1229,8 +1251,35 @@ int optik_robot_rrt_plan_goals(const optik_robot *r, const double *starts, const
         return set_err(-1, optik_hip_last_error());
     if (Q == 0 || (!paths_out && !len_out && !cost_out && !status_out && !iters_out && !nodes_out && !goal_out))
         return 0;
-    return rrt_plan_rows(r, c, starts, goals, counts, G, Q, iters, step, resolution, first, max_nodes, Lmax, poll, ee16,
-                         paths_out, len_out, cost_out, status_out, iters_out, nodes_out, goal_out);
+    return rrt_plan_rows(r, c, nullptr, starts, goals, counts, G, Q, iters, step, resolution, first, max_nodes, Lmax, poll,
+                         ee16, paths_out, len_out, cost_out, status_out, iters_out, nodes_out, goal_out);
+}
+
+// Q goal-set queries through optik_hip_rrt_plan_constrained (include/optik.h).
+int optik_robot_rrt_plan_constrained(const optik_robot *r, const double *starts, const double *goals,
+                                     const int32_t *counts, int32_t G, int64_t Q, const double *ref7, const double *lo6,
+                                     const double *hi6, double tol, double ptol, int32_t piters, double damping,
+                                     double max_step, int32_t iters, double step, double resolution, uint64_t first,
+                                     int32_t max_nodes, int32_t Lmax, int32_t poll, const double *ee16,
+                                     double *paths_out, int32_t *len_out, double *cost_out, int32_t *status_out,
+                                     int32_t *iters_out, int32_t *nodes_out, int32_t *goal_out,
+                                     int32_t *projected_out) {
+    if (!r || !starts || !goals) return set_err(-1, "null argument");
+    if (Q < 0) return set_err(-1, "bad argument");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    // (Q = 0: the kernel layer's refusals of the chain, G, the sizes, the step, the resolution and the constraint)
+    if (optik_hip_rrt_plan_constrained(c->chain, nullptr, ref7, lo6, hi6, tol, ptol, piters, damping, max_step, nullptr,
+                                       nullptr, nullptr, 0, G, iters, step, resolution, first, max_nodes, Lmax, poll,
+                                       nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (Q == 0
+        || (!paths_out && !len_out && !cost_out && !status_out && !iters_out && !nodes_out && !goal_out
+            && !projected_out))
+        return 0;
+    const RrtRowsConstraint con{ref7, lo6, hi6, tol, ptol, damping, max_step, piters, projected_out};
+    return rrt_plan_rows(r, c, &con, starts, goals, counts, G, Q, iters, step, resolution, first, max_nodes, Lmax, poll,
+                         ee16, paths_out, len_out, cost_out, status_out, iters_out, nodes_out, goal_out);
 }
 
 int optik_robot_set_motion_resolution(optik_robot *r, double h) {

@@ -941,6 +941,50 @@ class HipChain:
             _ptr(res["status"]), _ptr(res["iters"]), _ptr(res["nodes"]), _ptr(res["which"]), _stream_ptr()))
         return res
 
+    # -- the tree planner under a pose constraint (include/optik_hip.h) --------------------
+    def rrt_plan_constrained(self, starts, goals, gcount, c, tol, iters, step, resolution, first=0,
+                             max_nodes=nat.RRT_NODES, Lmax=64, poll=nat.RRT_POLL, ptol=nat.CONSTRAINT_TOL,
+                             piters=nat.RRT_PROJECT_ITERS, damping=nat.CONSTRAINT_DAMPING,
+                             max_step=nat.CONSTRAINT_MAX_STEP, ee_offset7=None):
+        """rrt_plan_goals under the pose constraint c (optik_hip_rrt_plan_constrained; csrc/rrt_constrained_measure.hpp):
+        starts [n, Q], goals [G, n, Q], gcount [Q] int32 or None (G each).  Every node a tree takes is first projected
+        onto c (constraint_project_batch's method at ptol, piters, damping, max_step) and every motion has passed
+        collision_motion_batch and constraint_motion_batch at tol, in the direction the path travels it; a start that
+        violates c at tol gives status 1, a goal that does is not a root.  Returns rrt_plan_goals' dict plus projected
+        [2, Q] int32: the projections attempted and those that ended CONSTRAINT_PROJECTED.  With a box that is free on
+        all six axes every shared output is rrt_plan_goals', bit for bit.  tol has no default: it says how far the
+        straight motion between two projected nodes may leave c.  Synchronises with the host as rrt_plan does."""
+        Q = self._check_q(starts)
+        if not (isinstance(goals, torch.Tensor) and goals.is_cuda and goals.dtype == torch.float64 and goals.dim() == 3
+                and goals.shape[1] == self.n and goals.shape[2] == Q and goals.is_contiguous()):
+            raise ValueError(f"goals must be a contiguous float64 cuda tensor [G, n, Q] = [G, {self.n}, {Q}]")
+        if gcount is not None and not (isinstance(gcount, torch.Tensor) and gcount.is_cuda
+                                       and gcount.dtype == torch.int32 and tuple(gcount.shape) == (Q,)
+                                       and gcount.is_contiguous()):
+            raise ValueError(f"gcount must be a contiguous int32 cuda tensor [{Q}]")
+        iters, step, max_nodes, poll, first = nat.check_rrt_args(iters, step, max_nodes, Lmax, poll, first)
+        G = nat.check_rrt_goals(int(goals.shape[0]), max_nodes)
+        h = nat.check_resolution(resolution)
+        ref7, lo, hi = constraint_arrays(c)
+        tol = nat.check_constraint_tol(tol)
+        ptol, piters, damping, max_step = nat.check_project_args(ptol, piters, damping, max_step)
+        dev = starts.device
+        res = dict(path=torch.empty((int(Lmax), Q, self.n), dtype=torch.float64, device=dev),
+                   len=torch.empty(Q, dtype=torch.int32, device=dev),
+                   cost=torch.empty(Q, dtype=torch.float64, device=dev),
+                   status=torch.empty(Q, dtype=torch.int32, device=dev),
+                   iters=torch.empty(Q, dtype=torch.int32, device=dev),
+                   nodes=torch.empty((2, Q), dtype=torch.int32, device=dev),
+                   which=torch.empty(Q, dtype=torch.int32, device=dev),
+                   projected=torch.empty((2, Q), dtype=torch.int32, device=dev))
+        ee = self._ee7(ee_offset7)
+        nat.check(nat.lib().optik_hip_rrt_plan_constrained(
+            self._h, _dp(ee) if ee is not None else None, _dp(ref7), _dp(lo), _dp(hi), tol, ptol, piters, damping,
+            max_step, _ptr(starts), _ptr(goals), _ptr(gcount), Q, G, iters, step, h, first, max_nodes, int(Lmax), poll,
+            _ptr(res["path"]), _ptr(res["len"]), _ptr(res["cost"]), _ptr(res["status"]), _ptr(res["iters"]),
+            _ptr(res["nodes"]), _ptr(res["which"]), _ptr(res["projected"]), _stream_ptr()))
+        return res
+
     def rrt_plan_poses(self, cfg, targets, starts, restart_begin, restart_end, K, min_dist, iters, step, resolution,
                        first=0, max_nodes=nat.RRT_NODES, Lmax=64, poll=nat.RRT_POLL, ee_offset7=None):
         """Plans starts[:, q] ([n, Q]) to the poses targets [Q, 7] without a roadmap: ik_solutions with x0 = the starts

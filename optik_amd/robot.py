@@ -92,6 +92,10 @@ def _bind(L):
                                        C.c_int32, C.c_int32, dp, dp, ip, dp, ip, ip, ip]
     L.optik_robot_rrt_plan_goals.argtypes = [vp, dp, dp, ip, C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_double,
                                              C.c_uint64, C.c_int32, C.c_int32, C.c_int32, dp, dp, ip, dp, ip, ip, ip, ip]
+    L.optik_robot_rrt_plan_constrained.argtypes = [vp, dp, dp, ip, C.c_int32, C.c_int64, dp, dp, dp, C.c_double,
+                                                   C.c_double, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double,
+                                                   C.c_double, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, dp, dp, ip,
+                                                   dp, ip, ip, ip, ip, ip]
     L.optik_robot_path_shortcut.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, C.c_int32, C.c_double, C.c_double, C.c_int32,
                                             dp, dp, ip, dp, dp, ip]
     L.optik_robot_path_resample.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, C.c_int32, dp, ip]
@@ -1650,6 +1654,73 @@ class Robot:
                                         int(max_waypoints), roadmap.resolution, roadmap.constraint, roadmap.tol)
         return dict(paths=np.ascontiguousarray(r["path"].cpu().numpy().transpose(1, 0, 2)),
                     len=r["len"].cpu().numpy(), cost=r["cost"].cpu().numpy(), status=r["status"].cpu().numpy())
+
+    # -- the tree planner under a pose constraint (extension; include/optik.h) --------------
+    def plan_rrt_to_goals_constrained(self, starts, goals, c, counts=None, *, tol, iters=None, step=None,
+                                      resolution=nat.ROADMAP_RESOLUTION, first=0, max_nodes=None,
+                                      max_waypoints=nat.PATH_OPTIMIZE_MAX_WAYPOINTS, poll=nat.RRT_POLL,
+                                      ptol=nat.CONSTRAINT_TOL, piters=nat.RRT_PROJECT_ITERS,
+                                      damping=nat.CONSTRAINT_DAMPING, max_step=nat.CONSTRAINT_MAX_STEP, ee_offset=None):
+        """plan_rrt_to_goals under the pose constraint c ("carry the glass upright"): the fallback for the rows
+        plan_constrained_paths returns with status 1.  starts [Q, n], goals [Q, G, n], counts [Q] or None as there.
+        Two trees per query grow as plan_rrt's do, but every candidate node is first projected onto c
+        (constraint_project_batch_arrays' method at ptol, at most piters iterations, damping, max_step) and a
+        projection that fails costs the iteration; every motion a tree or the junction takes has passed the collision
+        check AND constraint_motion_batch_arrays at tol, at `resolution`, in the direction the path travels it.  A
+        start that violates c at tol gives status 1; a goal that does is no root.  tol has no default: as for
+        build_constrained_roadmap it is the caller's statement of how far the straight joint-space motion between two
+        nodes on the constraint may leave it -- edge interiors are not projected.
+        Returns plan_rrt_to_goals' dict plus "projected" [Q, 2] int32: the projections attempted and the ones that
+        ended projected.  With a box that is free on all six axes the shared outputs are plan_rrt_to_goals', bit for
+        bit.  "paths" and "len" go into check_paths_constraint, certify_paths and time_paths as they are; a tree's
+        path has a corner at every waypoint, so give time_paths a v_max the corners can be taken at (its status 1
+        says the limits were too fast for them; DESIGN.md section 5.30 has the example's figures).
+        shortcut_paths, resample_paths and optimize_paths still know nothing of constraints: check their output with
+        check_paths_constraint before using it.
+        It keeps no state in the robot and reads no roadmap.  The default of piters (nat.RRT_PROJECT_ITERS) is read
+        from one table and is that and nothing more; the other defaults are plan_rrt's and
+        the projection's.  ValueError for what plan_rrt_to_goals and the constraint calls refuse."""
+        starts = self._check_xs(starts)
+        Q, n = starts.shape
+        goals = np.ascontiguousarray(goals, dtype=np.float64)
+        if goals.ndim != 3 or goals.shape[0] != Q or goals.shape[2] != n:
+            raise ValueError(f"goals must be [Q, G, n] = [{Q}, G, {n}], got {list(goals.shape)}")
+        if counts is not None:
+            counts = np.ascontiguousarray(counts, dtype=np.int32)
+            if counts.shape != (Q,):
+                raise ValueError(f"counts must be [Q] = [{Q}], got {list(counts.shape)}")
+        iters, step, max_nodes, poll, first = nat.check_rrt_args(iters, step, max_nodes, max_waypoints, poll, first)
+        G = nat.check_rrt_goals(goals.shape[1], max_nodes)
+        h = nat.check_resolution(resolution)
+        ref7, lo, hi = constraint_arrays(c)
+        tol = nat.check_constraint_tol(tol)
+        ptol, piters, damping, max_step = nat.check_project_args(ptol, piters, damping, max_step)
+        L = int(max_waypoints)
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        paths, cost = np.zeros((Q, L, n)), np.zeros(Q)
+        ln, status, it, goal = (np.zeros(Q, dtype=np.int32) for _ in range(4))
+        nodes, projected = np.zeros((Q, 2), dtype=np.int32), np.zeros((Q, 2), dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        if self._L.optik_robot_rrt_plan_constrained(
+                self._h, _dp(starts), _dp(goals), counts.ctypes.data_as(ip) if counts is not None else None, G, Q,
+                _dp(ref7), _dp(lo), _dp(hi), tol, ptol, piters, damping, max_step, iters, step, h, first, max_nodes, L,
+                poll, _dp(ee) if ee is not None else None, _dp(paths), ln.ctypes.data_as(ip), _dp(cost),
+                status.ctypes.data_as(ip), it.ctypes.data_as(ip), nodes.ctypes.data_as(ip), goal.ctypes.data_as(ip),
+                projected.ctypes.data_as(ip)):
+            raise RuntimeError(_err(self._L))
+        return dict(paths=paths, len=ln, cost=cost, status=status, iters=it, nodes=nodes, goal=goal,
+                    projected=projected)
+
+    def plan_rrt_constrained(self, starts, goals, c, *, tol, **kwargs):
+        """plan_rrt under the pose constraint c, for Q pairs starts[q] -> goals[q] ([Q, n] each):
+        plan_rrt_to_goals_constrained with one goal per query (its keyword arguments, its dict: "goal" is 0 where
+        the status is 0).  Its paths go into check_paths_constraint, certify_paths and time_paths as they are;
+        shortcut_paths, resample_paths and optimize_paths still know nothing of constraints."""
+        starts, goals = self._check_xs(starts), self._check_xs(goals)
+        if starts.shape != goals.shape:
+            raise ValueError(f"starts and goals must have the same shape, got {list(starts.shape)} and "
+                             f"{list(goals.shape)}")
+        return self.plan_rrt_to_goals_constrained(starts, goals[:, None, :], c, None, tol=tol, **kwargs)
 
     def set_motion_resolution(self, h):
         """The resolution of ik_path*'s motion check (0, the default: off).  While it is > 0 and a collision model is
