@@ -382,6 +382,26 @@ int optik_robot_path_shortcut(const optik_robot *robot, int64_t P, int32_t L, co
                               double *cost_in_out, int32_t *status_out);
 int optik_robot_path_resample(const optik_robot *robot, int64_t P, int32_t L, const double *paths, const int32_t *lens,
                               int32_t Lout, double *paths_out, int32_t *status_out);
+/* Shortcutting and resampling that keep a pose constraint (extension; include/optik_hip.h:
+ * optik_hip_path_shortcut_constrained and optik_hip_path_resample_constrained).  The two entries
+ * above with the constraint ref7 (t, quaternion i j k w), lo6, hi6: every new vertex / interior waypoint is projected
+ * onto it at ptol (at most piters iterations, damping, max_step), the input's own waypoints and the two ends never
+ * move, and a shortcut's pairs must pass the motion check AND the constraint's check along the motion at tol.
+ * projected_out [P][2]: the projections attempted and those that ended projected.  optik_robot_path_resample_constrained's
+ * status_out adds 4: an interior waypoint could not be projected and kept its interpolated value.  Any output may be
+ * NULL.  rc 0, or -1: null argument, what the kernel layer refuses. */
+int optik_robot_path_shortcut_constrained(const optik_robot *robot, int64_t P, int32_t L, const double *paths,
+                                          const int32_t *lens, int32_t vertices, double resolution, double hop_penalty,
+                                          int32_t Lout, const double *ref7, const double *lo6, const double *hi6,
+                                          double tol, double ptol, int32_t piters, double damping, double max_step,
+                                          const double *ee_offset16, double *paths_out, int32_t *len_out,
+                                          double *cost_out, double *cost_in_out, int32_t *status_out,
+                                          int32_t *projected_out);
+int optik_robot_path_resample_constrained(const optik_robot *robot, int64_t P, int32_t L, const double *paths,
+                                          const int32_t *lens, int32_t Lout, const double *ref7, const double *lo6,
+                                          const double *hi6, double ptol, int32_t piters, double damping,
+                                          double max_step, const double *ee_offset16, double *paths_out,
+                                          int32_t *status_out, int32_t *projected_out);
 /* Timing planned paths and sampling the trajectory (extension; include/optik_hip.h: optik_hip_path_time and
  * optik_hip_trajectory_sample).  paths [P][L][n] row-major with lens [P] waypoints each (NULL: L
  * each), 3 <= L <= 64 -- optik_robot_path_resample's paths_out as it is.

@@ -535,6 +535,59 @@ int optik_hip_path_resample(const optik_hip_chain *chain, const double *d_path, 
                             int64_t P, int32_t Lout, double *d_out, int32_t *d_status, void *stream);
 int64_t optik_hip_path_shortcut_chunk(const optik_hip_chain *chain, int32_t V);
 
+/* Shortcutting and resampling that keep a pose constraint (extension; the rules and their
+ * operation order: csrc/shortcut_constrained_measure.hpp).  The constraint is ref7, lo6, hi6 as optik_hip_constraint_batch
+ * takes it and travels with the call; paths, lengths and outputs are optik_hip_path_shortcut's and _path_resample's.
+ *
+ * optik_hip_path_shortcut_constrained: optik_hip_path_shortcut with every subdivision vertex that is not one of the
+ * input's own waypoints projected onto the constraint (optik_hip_constraint_project_batch's method at ptol, piters,
+ * damping, max_step; one vertex per lane) -- a vertex whose projection does not end OPTIK_HIP_CONSTRAINT_PROJECTED is
+ * dead: NaN, in no pair, on no route -- and every pair i < j open only where the motion vertex i -> vertex j is free
+ * by the motion check AND ok by optik_hip_constraint_motion_batch's rule at `resolution`, tol.  The input's waypoints,
+ * the start and the goal among them, are copied bit for bit and never move.  So on a route of status 0 every vertex
+ * that is not an input waypoint has violation <= ptol and lies within the joint limits, and every hop has passed both
+ * checks in the direction of travel, at the samples; hop interiors are not projected, tol says how far they may leave
+ * the constraint.  d_cost may exceed d_cost_in: projected vertices leave the polyline.  d_projected [2][P] (may be
+ * NULL): the projections attempted and those that ended projected, both 0 for the statuses 2 and 3 of a bad input.
+ * With a box that is free on all six axes and paths within the joint limits every shared output equals
+ * optik_hip_path_shortcut's bit for bit.
+ * Per chunk, back to back on the stream with no host synchronisation: a gather kernel that builds and projects the
+ * vertices, stores them ([n][Pc V] doubles of the workspace) and writes the pair segments; the motion check (classify
+ * form); optik_hip_constraint_motion_mask on the same segments and flags; a route kernel that reads the stored
+ * vertices -- nothing is projected twice.  Workspace: optik_hip_path_shortcut's plus 8 n V bytes per path
+ * (optik_hip_path_shortcut_constrained_chunk: the paths per chunk).  A path's result does not depend on P, on the
+ * chunking or on the launch shape.  One call per chain handle at a time.
+ *
+ * optik_hip_path_resample_constrained: optik_hip_path_resample with every waypoint 0 < j < Lout - 1 projected the same
+ * way; one wave per path, lane j = waypoint j.  A projection that does not end projected leaves the interpolated
+ * waypoint and gives the path status 4 (OPTIK_HIP_PATH_RESAMPLE_UNPROJECTED), which ranks below 2 and 3; a path of
+ * status 3 is not projected.  The spacing is equal before the projection and only approximately equal after it; the
+ * new segments are NOT checked.  d_projected [2][P] as above.
+ *
+ * optik_hip_constraint_motion_mask: d_flag [B] in and out: a segment whose flag is 0 is not sampled and stays 0; every
+ * other flag becomes optik_hip_constraint_motion_batch's ok byte for d_qa -> d_qb ([n][B]).  One segment per lane,
+ * grid-stride, no atomics.
+ *
+ * Refusals, before any device work and also when P = 0: optik_hip_path_shortcut's / _path_resample's, then
+ * optik_hip_constraint_motion_batch's for the constraint, tol (shortcut and mask only) and the chain, then
+ * optik_hip_constraint_project_batch's for ptol, piters, damping and max_step. */
+#define OPTIK_HIP_PATH_RESAMPLE_UNPROJECTED 4
+int optik_hip_path_shortcut_constrained(optik_hip_chain *chain, const double *ee_offset7, const double *d_path,
+                                        const int32_t *d_len, int32_t Lin, int64_t P, int32_t V, double resolution,
+                                        double hop_penalty, int32_t Lout, const double *ref7, const double *lo6,
+                                        const double *hi6, double tol, double ptol, int32_t piters, double damping,
+                                        double max_step, double *d_out, int32_t *d_len_out, double *d_cost,
+                                        double *d_cost_in, int32_t *d_status, int32_t *d_projected, void *stream);
+int optik_hip_path_resample_constrained(const optik_hip_chain *chain, const double *ee_offset7, const double *d_path,
+                                        const int32_t *d_len, int32_t Lin, int64_t P, int32_t Lout, const double *ref7,
+                                        const double *lo6, const double *hi6, double ptol, int32_t piters,
+                                        double damping, double max_step, double *d_out, int32_t *d_status,
+                                        int32_t *d_projected, void *stream);
+int optik_hip_constraint_motion_mask(const optik_hip_chain *chain, const double *ee_offset7, const double *ref7,
+                                     const double *lo6, const double *hi6, const double *d_qa, const double *d_qb,
+                                     int64_t B, double resolution, double tol, uint8_t *d_flag, void *stream);
+int64_t optik_hip_path_shortcut_constrained_chunk(const optik_hip_chain *chain, int32_t V);
+
 /* Timing of joint paths under velocity and acceleration limits, and the sampling of the timed trajectory (extension;
  * DESIGN.md section 5.20; the arithmetic and its operation order: csrc/time_measure.hpp).  Paths are d_path [L][P][n]
  * as above, path p having d_len[p] waypoints (d_len NULL: L each), 3 <= d_len[p] <= L <= 64.  Any revolute chain of

@@ -197,6 +197,14 @@ def lib():
                                           C.c_int32, vp, vp, vp, vp, vp, vp]
     L.optik_hip_path_resample.argtypes = [vp, vp, vp, C.c_int32, C.c_int64, C.c_int32, vp, vp, vp]
     L.optik_hip_path_shortcut_chunk.argtypes = [vp, C.c_int32]
+    L.optik_hip_path_shortcut_constrained.argtypes = [vp, dp, vp, vp, C.c_int32, C.c_int64, C.c_int32, C.c_double,
+                                                      C.c_double, C.c_int32, dp, dp, dp, C.c_double, C.c_double,
+                                                      C.c_int32, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp, vp]
+    L.optik_hip_path_resample_constrained.argtypes = [vp, dp, vp, vp, C.c_int32, C.c_int64, C.c_int32, dp, dp, dp,
+                                                      C.c_double, C.c_int32, C.c_double, C.c_double, vp, vp, vp, vp]
+    L.optik_hip_constraint_motion_mask.argtypes = [vp, dp, dp, dp, dp, vp, vp, C.c_int64, C.c_double, C.c_double, vp, vp]
+    L.optik_hip_path_shortcut_constrained_chunk.argtypes = [vp, C.c_int32]
+    L.optik_hip_path_shortcut_constrained_chunk.restype = C.c_int64
     L.optik_hip_path_time.argtypes = [vp, vp, vp, C.c_int32, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.optik_hip_trajectory_sample.argtypes = [vp, vp, vp, C.c_int32, C.c_int64, vp, vp, vp, C.c_double, C.c_int32, vp,
                                               vp, vp]
@@ -459,6 +467,8 @@ def rrt_chunk(chain_handle, max_nodes):
 # include/optik_hip.h: OPTIK_HIP_PATH_SHORTCUT_MAX_VERTICES; the statuses of optik_hip_path_shortcut / _path_resample
 PATH_SHORTCUT_MAX_VERTICES = 64
 SHORTCUT_FOUND, SHORTCUT_NO_ROUTE, SHORTCUT_BAD_LENGTH, SHORTCUT_NAN = 0, 1, 2, 3
+# OPTIK_HIP_PATH_RESAMPLE_UNPROJECTED: optik_hip_path_resample_constrained left an interior waypoint as interpolated
+RESAMPLE_UNPROJECTED = 4
 # All-pairs visibility samples about V^2 / 6 times the path's own length: 32 vertices cost a quarter of 64
 # (profiles/shortcut_cost.txt).
 SHORTCUT_VERTICES, SHORTCUT_RESOLUTION, RESAMPLE_WAYPOINTS = 32, 0.05, 32
@@ -481,6 +491,15 @@ def check_shortcut_args(L=2, vertices=2, max_waypoints=2, resolution=1.0, hop_pe
 def path_shortcut_chunk(chain_handle, vertices):
     """The paths optik_hip_path_shortcut processes per chunk of its workspace for this chain and vertex budget."""
     c = int(lib().optik_hip_path_shortcut_chunk(chain_handle, int(vertices)))
+    if c < 1:
+        check(c)
+    return c
+
+
+def path_shortcut_constrained_chunk(chain_handle, vertices):
+    """The paths optik_hip_path_shortcut_constrained processes per chunk of its workspace for this chain and vertex
+    budget."""
+    c = int(lib().optik_hip_path_shortcut_constrained_chunk(chain_handle, int(vertices)))
     if c < 1:
         check(c)
     return c

@@ -14,18 +14,42 @@
 //                              lane i takes the result.  Lane 0 walks the route and the wave writes the path.
 //   shortcut_resample_kernel   one thread per (path, output waypoint); no LDS, no workspace.
 //
+// Under a pose constraint (shortcut_constrained_measure.hpp; optik_hip_path_shortcut_constrained /
+// _path_resample_constrained) the same chunk loop runs four kernels per chunk:
+//   shortcut_cgather_kernel<CH>       one block of 256 per path, the chain table staged in LDS as ik_constraint.hip
+//                                     stages it.  The first wave builds the vertices as above, then lane u projects
+//                                     vertex u unless it is one of the input's waypoints (constraint::project, the
+//                                     header's own function; lanes whose loops differ in length cost the wave the
+//                                     longest of them and nothing else); a vertex that did not project becomes NaN.
+//                                     The block stores the final vertices [n][Pc * V] behind the segments in the
+//                                     workspace, counts the projections and writes the pair segments as above.
+//   (the motion check, classify form, as above)
+//   constraint_motion_mask_kernel<CH> one pair per lane, grid-stride, no atomics: a pair whose flag is 0 already is not
+//                                     sampled, every other flag becomes constraint::motion's ok.
+//   shortcut_route_stored_kernel      shortcut_route_kernel's body (route_path) with the vertices read from the
+//                                     stored block: nothing is projected twice.
+//   shortcut_cresample_kernel<CH>     one wave per path, lane j = output waypoint j: resample, project, then the
+//                                     wave's ballots give the status and the two counts.
+// CH is ChainDev (n <= 8) or WideChainDev (9 .. 16).
+//
 // The paths of a call are processed in chunks of at most OPTIK_HIP_PATH_SHORTCUT_CHUNK_BYTES of workspace, launched
 // one after the other on the stream; a path's blocks see only that path, so nothing depends on P or on the chunking.
 #include "collision_device.hpp"
-#include "shortcut_measure.hpp"
+#include "constraint_measure.hpp"
+#include "shortcut_constrained_measure.hpp"
 
 using namespace optik;
 using namespace optik::host;
+using namespace optik::hostparams;
 using namespace optik::colldev;
 
 static_assert(shortcut::MAX_POINTS == OPTIK_HIP_PATH_OPTIMIZE_MAX_WAYPOINTS && shortcut::MAX_POINTS == 64,
               "a shortcut path is a path path_optimize takes; one lane of a wave per vertex");
 static_assert(shortcut::MAX_JOINTS == WIDE_MAX_DOF, "shortcut_measure.hpp states the cap on the joint positions");
+static_assert(shortcut::PROJECTION_OK == constraint::PROJECTED && constraint::PROJECTED == OPTIK_HIP_CONSTRAINT_PROJECTED,
+              "shortcut_constrained_measure.hpp names the projection's status without including constraint_measure.hpp");
+static_assert(shortcut::UNPROJECTED == OPTIK_HIP_PATH_RESAMPLE_UNPROJECTED, "optik_hip.h states the status");
+static_assert(shortcut::MAX_JOINTS == constraint::MAXN, "a vertex is a configuration the projection takes");
 
 namespace {
 
@@ -56,8 +80,11 @@ struct PathLds {
     shortcut::Prepared prep;
 };
 
-// Steps 1 and 2 of the header by the first wave of the block; every thread of the block calls it.
-__device__ __forceinline__ void build_vertices(const ShortcutLaunch &a, long long p, PathLds &s) {
+// Steps 1 and 2 of the header by the first wave of the block; every thread of the block calls it.  STORED: the
+// vertices are not interpolated but read from `stored` [n][Pc * V], where shortcut_cgather_kernel left them.
+template <bool STORED>
+__device__ __forceinline__ void build_vertices(const ShortcutLaunch &a, long long p, PathLds &s,
+                                               const double *stored = nullptr) {
     const int tid = threadIdx.x;
     const double *path = a.path + p * a.n;
     const long long st = a.P * a.n;
@@ -70,16 +97,19 @@ __device__ __forceinline__ void build_vertices(const ShortcutLaunch &a, long lon
     if (tid == 0) s.prep = shortcut::prepare(len, a.Lin, a.V, all_finite, s.w, s.m, s.off);
     __syncthreads();
     if (tid < s.prep.nv) {
-        const int seg = shortcut::vertex_segment(le, s.off, tid);
-        for (int i = 0; i < a.n; ++i) s.v[i * MP + tid] = shortcut::vertex_joint(path, st, s.m, s.off, seg, tid, i);
+        if constexpr (STORED) {
+            const long long SV = a.Pc * a.V, u = (p - a.p0) * a.V + tid;
+            for (int i = 0; i < a.n; ++i) s.v[i * MP + tid] = stored[(long long)i * SV + u];
+        } else {
+            const int seg = shortcut::vertex_segment(le, s.off, tid);
+            for (int i = 0; i < a.n; ++i) s.v[i * MP + tid] = shortcut::vertex_joint(path, st, s.m, s.off, seg, tid, i);
+        }
     }
     __syncthreads();
 }
 
-__global__ __launch_bounds__(GATHER_BLOCK) void shortcut_gather_kernel(const ShortcutLaunch a) {
-    __shared__ PathLds s;
-    const long long pc = blockIdx.x;
-    build_vertices(a, a.p0 + pc, s);
+// The segments vertex i -> vertex j, i < j, of the path in LDS into the workspace (every thread of the block).
+__device__ __forceinline__ void write_pairs(const ShortcutLaunch &a, long long pc, const PathLds &s) {
     const int V = a.V, nv = s.prep.nv, pairs = shortcut::pair_count(V);
     const long long B = a.Pc * pairs;
     for (int e = threadIdx.x; e < V * V; e += GATHER_BLOCK) {
@@ -94,13 +124,22 @@ __global__ __launch_bounds__(GATHER_BLOCK) void shortcut_gather_kernel(const Sho
     }
 }
 
-__global__ __launch_bounds__(SC_WAVE) void shortcut_route_kernel(const ShortcutLaunch a) {
+__global__ __launch_bounds__(GATHER_BLOCK) void shortcut_gather_kernel(const ShortcutLaunch a) {
+    __shared__ PathLds s;
+    const long long pc = blockIdx.x;
+    build_vertices<false>(a, a.p0 + pc, s);
+    write_pairs(a, pc, s);
+}
+
+// The route of one path by one wave (steps 4 to 6); STORED as build_vertices takes it.
+template <bool STORED>
+__device__ __forceinline__ void route_path(const ShortcutLaunch &a, const double *stored) {
     __shared__ PathLds s;
     __shared__ int s_succ[MP], s_route[MP];
     __shared__ shortcut::Result s_res;
     const long long pc = blockIdx.x, p = a.p0 + pc;
     const int lane = threadIdx.x;
-    build_vertices(a, p, s);
+    build_vertices<STORED>(a, p, s, stored);
     const shortcut::Prepared prep = s.prep;
     const int V = a.V, nv = prep.nv;
     double d_lane = shortcut::inf();  // d[lane]
@@ -151,6 +190,12 @@ __global__ __launch_bounds__(SC_WAVE) void shortcut_route_kernel(const ShortcutL
     }
 }
 
+__global__ __launch_bounds__(SC_WAVE) void shortcut_route_kernel(const ShortcutLaunch a) { route_path<false>(a, nullptr); }
+
+__global__ __launch_bounds__(SC_WAVE) void shortcut_route_stored_kernel(const ShortcutLaunch a, const double *stored) {
+    route_path<true>(a, stored);
+}
+
 struct ResampleLaunch {
     const double *path;  // [Lin][P][n]
     const int32_t *len;  // [P] or null: Lin
@@ -171,7 +216,156 @@ __global__ __launch_bounds__(RESAMPLE_BLOCK) void shortcut_resample_kernel(const
     if (j == 0 && a.status) a.status[p] = st;
 }
 
+// ---- under a pose constraint (shortcut_constrained_measure.hpp) -------------------------------------------------
+
+// The constraint's side of a launch: it travels with the call, the chain handle keeps nothing of it.
+struct ConLaunch {
+    const ChainDev *chain;       // n <= 8
+    const WideChainDev *wchain;  // 9 .. 16 joint positions
+    EvalParams ep;               // only the ee_offset part is used
+    constraint::Box c;
+    double h, tol;               // the check along a motion
+    double ptol, damping, max_step;  // the projection
+    int piters;
+    double *verts;               // [n][Pc * V] the chunk's final vertices (shortcut)
+    int32_t *projected;          // [2][P] or null
+};
+
+template <class CH>
+__device__ __forceinline__ const CH *table_of(const ConLaunch &k);
+template <>
+__device__ __forceinline__ const ChainDev *table_of<ChainDev>(const ConLaunch &k) { return k.chain; }
+template <>
+__device__ __forceinline__ const WideChainDev *table_of<WideChainDev>(const ConLaunch &k) { return k.wchain; }
+
+// (ik_constraint.hip's stage_table)
+template <class CH>
+__device__ __forceinline__ void stage_table(CH &dst, const CH *src) {
+    constexpr int ND = (int)(sizeof(CH) / sizeof(double));
+    static_assert(sizeof(CH) % sizeof(double) == 0, "the chain table is a whole number of doubles");
+    const double *s = reinterpret_cast<const double *>(src);
+    double *d = reinterpret_cast<double *>(&dst);
+    for (int i = threadIdx.x; i < ND; i += blockDim.x) d[i] = s[i];
+    __syncthreads();
+}
+
+template <class CH>
+__global__ __launch_bounds__(GATHER_BLOCK) void shortcut_cgather_kernel(const ShortcutLaunch a, const ConLaunch k) {
+    __shared__ PathLds s;
+    __shared__ CH sch;
+    const long long pc = blockIdx.x, p = a.p0 + pc;
+    const int tid = threadIdx.x, n = a.n;
+    stage_table(sch, table_of<CH>(k));
+    build_vertices<false>(a, p, s);
+    const int nv = s.prep.nv;
+    // rule 2': lane u projects vertex u, in its own column of the LDS block
+    bool tried = false, ended = false;
+    if (tid < nv && !shortcut::is_waypoint(s.off, shortcut::vertex_segment(s.prep.le, s.off, tid), tid)) {
+        double x[constraint::MAXN];
+        for (int i = 0; i < n; ++i) x[i] = s.v[i * MP + tid];
+        const constraint::Projected pr =
+            constraint::project(sch, k.ep, k.c, n, k.ptol, k.piters, k.damping, k.max_step, x);
+        tried = true;
+        ended = pr.status == constraint::PROJECTED;
+        for (int i = 0; i < n; ++i) s.v[i * MP + tid] = shortcut::vertex_after(pr.status, x[i]);
+    }
+    // (the barriers also publish the projected columns)
+    const int n_tried = __syncthreads_count(tried), n_ended = __syncthreads_count(ended);
+    if (tid == 0 && k.projected) {
+        k.projected[p] = n_tried;
+        k.projected[a.P + p] = n_ended;
+    }
+    const long long SV = a.Pc * a.V;
+    for (int e = tid; e < a.V * n; e += GATHER_BLOCK) {
+        const int i = e / a.V, u = e % a.V;
+        k.verts[(long long)i * SV + pc * a.V + u] = u < nv ? s.v[i * MP + u] : __builtin_nan("");
+    }
+    write_pairs(a, pc, s);
+}
+
+template <class CH>
+__global__ __launch_bounds__(256) void constraint_motion_mask_kernel(const ConLaunch k, const double *qa,
+                                                                     const double *qb, long long B, uint8_t *flag) {
+    __shared__ CH sch;
+    stage_table(sch, table_of<CH>(k));
+    const int n = sch.n_pos;
+    for (long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x; b < B;
+         b += (long long)gridDim.x * blockDim.x) {
+        if (flag[b] == 0) continue;  // (rule 3': the verdict is the AND; the skip only saves the samples)
+        flag[b] = (uint8_t)constraint::motion(sch, k.ep, k.c, n, qa + b, B, qb + b, B, k.h, k.tol).ok;
+    }
+}
+
+template <class CH>
+__global__ __launch_bounds__(SC_WAVE) void shortcut_cresample_kernel(const ResampleLaunch a, const ConLaunch k) {
+    __shared__ CH sch;
+    stage_table(sch, table_of<CH>(k));
+    const long long p = blockIdx.x;
+    const int j = threadIdx.x, n = a.n;
+    bool tried = false, ended = false;
+    int st = 0;
+    if (j < a.Lout) {
+        const int len = a.len ? a.len[p] : a.Lin;
+        double x[constraint::MAXN], y[constraint::MAXN];
+        st = shortcut::resample_waypoint(n, a.path + p * n, a.P * n, len, a.Lin, a.Lout, j, x, 1);
+        if (shortcut::projects(st, a.Lout, j)) {
+            for (int i = 0; i < n; ++i) y[i] = x[i];
+            const constraint::Projected pr =
+                constraint::project(sch, k.ep, k.c, n, k.ptol, k.piters, k.damping, k.max_step, y);
+            tried = true;
+            ended = pr.status == constraint::PROJECTED;
+            if (ended)
+                for (int i = 0; i < n; ++i) x[i] = y[i];
+        }
+        double *out = a.out + ((long long)j * a.P + p) * n;
+        for (int i = 0; i < n; ++i) out[i] = x[i];
+    }
+    // rule 7' and 8 over the wave (lane 0 holds the path's status: it does not depend on j)
+    const int n_tried = __popcll(__ballot(tried)), n_ended = __popcll(__ballot(ended));
+    if (j == 0) {
+        if (a.status) a.status[p] = shortcut::resample_status(st, n_tried != n_ended);
+        if (k.projected) {
+            k.projected[p] = n_tried;
+            k.projected[a.P + p] = n_ended;
+        }
+    }
+}
+
+void fill_con(const optik_hip_chain *ch, const double *ee_offset7, const double *ref7, const double *lo6,
+              const double *hi6, ConLaunch &k) {
+    std::memset(&k, 0, sizeof k);
+    k.chain = ch->dev;
+    k.wchain = ch->wdev;
+    const double one[3] = {1, 1, 1};
+    make_eval_params(one, one, ee_offset7, k.ep);
+    std::memcpy(k.c.ref, ref7, sizeof k.c.ref);
+    std::memcpy(k.c.lo, lo6, sizeof k.c.lo);
+    std::memcpy(k.c.hi, hi6, sizeof k.c.hi);
+}
+
+// The refusals of the constraint entries, in ik_constraint.hip's order (B = 0 there): the constraint, tol and the
+// chain with with_tol; then ptol, piters, damping and max_step.
+int check_con(const optik_hip_chain *ch, const double *ref7, const double *lo6, const double *hi6, bool with_tol,
+              double resolution, double tol, double ptol, int32_t piters, double damping, double max_step) {
+    if (with_tol)
+        if (int rc = optik_hip_constraint_motion_batch(ch, nullptr, ref7, lo6, hi6, nullptr, nullptr, 0, resolution, tol,
+                                                       nullptr, nullptr, nullptr, nullptr, nullptr))
+            return rc;
+    return optik_hip_constraint_project_batch(ch, nullptr, ref7, lo6, hi6, nullptr, 0, ptol, piters, damping, max_step,
+                                              nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
 bool points_ok(int v) { return v >= shortcut::MIN_POINTS && v <= shortcut::MAX_POINTS; }
+
+// per path under a constraint: what bytes_per_path counts and the stored vertices
+size_t bytes_per_path_constrained(int n, int V) {
+    return (size_t)shortcut::pair_count(V) * (sizeof(double) * 2 * (size_t)n + 1 + 24) + sizeof(double) * (size_t)n * V;
+}
+
+long long chunk_paths_constrained(int n, int V) {
+    const long long c = (long long)((size_t)OPTIK_HIP_PATH_SHORTCUT_CHUNK_BYTES / bytes_per_path_constrained(n, V));
+    return c < 1 ? 1 : c;
+}
 
 // per path: the gathered segments, their free flags, and the motion check's own words
 size_t bytes_per_path(int n, int V) {
@@ -259,6 +453,124 @@ int optik_hip_path_resample(const optik_hip_chain *ch, const double *d_path, con
     const unsigned grid = (unsigned)((P * Lout + RESAMPLE_BLOCK - 1) / RESAMPLE_BLOCK);
     hipLaunchKernelGGL(shortcut_resample_kernel, dim3(grid), dim3(RESAMPLE_BLOCK), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- under a pose constraint ------------------------------------------------------------------------------------
+
+#define CON_LAUNCH(KERNEL, CHAIN, GRID, BLOCK, STREAM, ...)                                                        \
+    do {                                                                                                           \
+        if ((CHAIN)->wide) hipLaunchKernelGGL(KERNEL<WideChainDev>, dim3(GRID), dim3(BLOCK), 0, (STREAM), __VA_ARGS__); \
+        else hipLaunchKernelGGL(KERNEL<ChainDev>, dim3(GRID), dim3(BLOCK), 0, (STREAM), __VA_ARGS__);              \
+        HIP_TRY(hipGetLastError());                                                                                \
+    } while (0)
+
+int64_t optik_hip_path_shortcut_constrained_chunk(const optik_hip_chain *ch, int32_t V) {
+    if (!ch || !points_ok(V)) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    return chunk_paths_constrained(ch->n, V);
+}
+
+int optik_hip_constraint_motion_mask(const optik_hip_chain *ch, const double *ee_offset7, const double *ref7,
+                                     const double *lo6, const double *hi6, const double *d_qa, const double *d_qb,
+                                     int64_t B, double resolution, double tol, uint8_t *d_flag, void *stream) {
+    // (B = 0: optik_hip_constraint_motion_batch's own refusals)
+    if (int rc = optik_hip_constraint_motion_batch(ch, nullptr, ref7, lo6, hi6, nullptr, nullptr, 0, resolution, tol,
+                                                   nullptr, nullptr, nullptr, nullptr, nullptr))
+        return rc;
+    if (B < 0) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    if (B == 0) return 0;
+    if (!d_qa || !d_qb || !d_flag) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    BIND_DEVICE(ch);
+    ConLaunch k;
+    fill_con(ch, ee_offset7, ref7, lo6, hi6, k);
+    k.h = resolution;
+    k.tol = tol;
+    const int grid = grid_for(ch, B, 256, 8);
+    CON_LAUNCH(constraint_motion_mask_kernel, ch, grid, 256, (hipStream_t)stream, k, d_qa, d_qb, (long long)B, d_flag);
+    return 0;
+}
+
+int optik_hip_path_shortcut_constrained(optik_hip_chain *ch, const double *ee_offset7, const double *d_path,
+                                        const int32_t *d_len, int32_t Lin, int64_t P, int32_t V, double resolution,
+                                        double hop_penalty, int32_t Lout, const double *ref7, const double *lo6,
+                                        const double *hi6, double tol, double ptol, int32_t piters, double damping,
+                                        double max_step, double *d_out, int32_t *d_len_out, double *d_cost,
+                                        double *d_cost_in, int32_t *d_status, int32_t *d_projected, void *stream) {
+    if (!ch || P < 0) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    if (P > MAX_PATHS) return fail(OPTIK_HIP_EINVAL, "path_shortcut: more than 2^30 paths in one launch");
+    // (P = 0: optik_hip_path_shortcut's own refusals -- the sizes, the penalty, the resolution, prismatic joints)
+    if (int rc = optik_hip_path_shortcut(ch, nullptr, nullptr, nullptr, Lin, 0, V, resolution, hop_penalty, Lout, nullptr,
+                                         nullptr, nullptr, nullptr, nullptr, nullptr))
+        return rc;
+    if (int rc = check_con(ch, ref7, lo6, hi6, true, resolution, tol, ptol, piters, damping, max_step)) return rc;
+    if (P == 0 || (!d_out && !d_len_out && !d_cost && !d_cost_in && !d_status && !d_projected)) return 0;
+    if (!d_path) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    const size_t n = (size_t)ch->n;
+    const long long pairs = shortcut::pair_count(V);
+    const long long chunk = P < chunk_paths_constrained(ch->n, V) ? P : chunk_paths_constrained(ch->n, V);
+    ShortcutLaunch a;
+    std::memset(&a, 0, sizeof a);
+    ConLaunch k;
+    fill_con(ch, ee_offset7, ref7, lo6, hi6, k);
+    k.h = resolution; k.tol = tol;
+    k.ptol = ptol; k.piters = piters; k.damping = damping; k.max_step = max_step;
+    k.projected = d_projected;
+    {
+        std::lock_guard<std::mutex> lock(ch->mu);
+        BIND_DEVICE(ch);
+        // (every chunk is at most the first one's size; the doubles first: the segments twice, then the vertices)
+        HIP_TRY(ch->shortcut_ws.reserve((sizeof(double) * 2 * n + 1) * (size_t)(chunk * pairs)
+                                        + sizeof(double) * n * (size_t)(chunk * V)));
+        a.qa = reinterpret_cast<double *>(ch->shortcut_ws.get());
+    }
+    a.path = d_path; a.len = d_len; a.P = P;
+    a.n = ch->n; a.Lin = Lin; a.V = V; a.Lout = Lout;
+    a.hop = hop_penalty;
+    a.out = d_out; a.len_out = d_len_out; a.cost = d_cost; a.cost_in = d_cost_in; a.status = d_status;
+    for (long long p0 = 0; p0 < P; p0 += chunk) {
+        const long long Pc = P - p0 < chunk ? P - p0 : chunk, B = Pc * pairs;
+        a.p0 = p0; a.Pc = Pc;
+        a.qb = a.qa + n * (size_t)B;
+        k.verts = a.qb + n * (size_t)B;
+        uint8_t *d_free = reinterpret_cast<uint8_t *>(k.verts + n * (size_t)(Pc * V));
+        a.free_flag = d_free;
+        {
+            BIND_DEVICE(ch);
+            CON_LAUNCH(shortcut_cgather_kernel, ch, (unsigned)Pc, GATHER_BLOCK, (hipStream_t)stream, a, k);
+        }
+        if (int rc = optik_hip_collision_motion_batch(ch, ee_offset7, a.qa, a.qb, B, resolution, nullptr, d_free,
+                                                      nullptr, nullptr, stream))
+            return rc;
+        BIND_DEVICE(ch);
+        const int grid = grid_for(ch, B, 256, 8);
+        CON_LAUNCH(constraint_motion_mask_kernel, ch, grid, 256, (hipStream_t)stream, k, (const double *)a.qa,
+                   (const double *)a.qb, B, d_free);
+        hipLaunchKernelGGL(shortcut_route_stored_kernel, dim3((unsigned)Pc), dim3(SC_WAVE), 0, (hipStream_t)stream, a,
+                           (const double *)k.verts);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+int optik_hip_path_resample_constrained(const optik_hip_chain *ch, const double *ee_offset7, const double *d_path,
+                                        const int32_t *d_len, int32_t Lin, int64_t P, int32_t Lout, const double *ref7,
+                                        const double *lo6, const double *hi6, double ptol, int32_t piters,
+                                        double damping, double max_step, double *d_out, int32_t *d_status,
+                                        int32_t *d_projected, void *stream) {
+    if (!ch || P < 0) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    if (P > MAX_PATHS) return fail(OPTIK_HIP_EINVAL, "path_resample: more than 2^30 paths in one launch");
+    // (P = 0: optik_hip_path_resample's own refusals -- the sizes, prismatic joints)
+    if (int rc = optik_hip_path_resample(ch, nullptr, nullptr, Lin, 0, Lout, nullptr, nullptr, nullptr)) return rc;
+    if (int rc = check_con(ch, ref7, lo6, hi6, false, 0.0, 0.0, ptol, piters, damping, max_step)) return rc;
+    if (P == 0 || (!d_out && !d_status && !d_projected)) return 0;
+    if (!d_path || !d_out) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    BIND_DEVICE(ch);
+    ResampleLaunch a{d_path, d_len, P, ch->n, Lin, Lout, d_out, d_status};
+    ConLaunch k;
+    fill_con(ch, ee_offset7, ref7, lo6, hi6, k);
+    k.ptol = ptol; k.piters = piters; k.damping = damping; k.max_step = max_step;
+    k.projected = d_projected;
+    CON_LAUNCH(shortcut_cresample_kernel, ch, (unsigned)P, SC_WAVE, (hipStream_t)stream, a, k);
     return 0;
 }
 

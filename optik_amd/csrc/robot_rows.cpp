@@ -715,6 +715,92 @@ int optik_robot_path_resample(const optik_robot *r, int64_t P, int32_t L, const 
         });
 }
 
+// P paths through optik_hip_path_shortcut_constrained: optik_robot_path_shortcut's staging with one more double out per
+// path, its two projection counters.
+int optik_robot_path_shortcut_constrained(const optik_robot *r, int64_t P, int32_t L, const double *paths,
+                                          const int32_t *lens, int32_t vertices, double resolution, double hop_penalty,
+                                          int32_t Lout, const double *ref7, const double *lo6, const double *hi6,
+                                          double tol, double ptol, int32_t piters, double damping, double max_step,
+                                          const double *ee16, double *paths_out, int32_t *len_out, double *cost_out,
+                                          double *cost_in_out, int32_t *status_out, int32_t *projected_out) {
+    if (!r || !paths || !ref7 || !lo6 || !hi6) return set_err(-1, "null argument");
+    if (P < 0) return set_err(-1, "bad argument");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    // (P = 0: the kernel layer's refusals of the chain, the sizes, the resolution, the penalty and the constraint)
+    if (optik_hip_path_shortcut_constrained(c->chain, nullptr, nullptr, nullptr, L, 0, vertices, resolution, hop_penalty,
+                                            Lout, ref7, lo6, hi6, tol, ptol, piters, damping, max_step, nullptr, nullptr,
+                                            nullptr, nullptr, nullptr, nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (P == 0 || (!paths_out && !len_out && !cost_out && !cost_in_out && !status_out && !projected_out)) return 0;
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    const size_t n = (size_t)r->n, wo = (size_t)Lout * n;
+    // per path out: the waypoints, cost, cost_in, then len and status in one more double, the counters in another
+    return stage_paths(
+        c, paths, lens, P, (size_t)L, n, wo + 4,
+        [&](const double *d_in, const int32_t *d_len, int64_t Lc, double *d_out) {
+            double *d_cost = d_out + wo * (size_t)Lc, *d_cin = d_cost + Lc;
+            int32_t *d_lo = reinterpret_cast<int32_t *>(d_cin + Lc);
+            return optik_hip_path_shortcut_constrained(c->chain, ee16 ? ee7 : nullptr, d_in, d_len, L, Lc, vertices,
+                                                       resolution, hop_penalty, Lout, ref7, lo6, hi6, tol, ptol, piters,
+                                                       damping, max_step, d_out, d_lo, d_cost, d_cin, d_lo + Lc,
+                                                       d_lo + 2 * Lc, nullptr);
+        },
+        [&](size_t b0, size_t Lc, const double *h_out) {
+            const double *h_cost = h_out + wo * Lc, *h_cin = h_cost + Lc;
+            const int32_t *h_lo = reinterpret_cast<const int32_t *>(h_cin + Lc), *h_pr = h_lo + 2 * Lc;
+            if (paths_out) scatter_paths(paths_out, h_out, b0, Lc, (size_t)Lout, n);
+            if (cost_out) std::memcpy(cost_out + b0, h_cost, sizeof(double) * Lc);
+            if (cost_in_out) std::memcpy(cost_in_out + b0, h_cin, sizeof(double) * Lc);
+            if (len_out) std::memcpy(len_out + b0, h_lo, sizeof(int32_t) * Lc);
+            if (status_out) std::memcpy(status_out + b0, h_lo + Lc, sizeof(int32_t) * Lc);
+            if (projected_out)
+                for (size_t k = 0; k < Lc; ++k) {
+                    projected_out[2 * (b0 + k)] = h_pr[k];
+                    projected_out[2 * (b0 + k) + 1] = h_pr[Lc + k];
+                }
+        });
+}
+
+// P paths through optik_hip_path_resample_constrained.
+int optik_robot_path_resample_constrained(const optik_robot *r, int64_t P, int32_t L, const double *paths,
+                                          const int32_t *lens, int32_t Lout, const double *ref7, const double *lo6,
+                                          const double *hi6, double ptol, int32_t piters, double damping,
+                                          double max_step, const double *ee16, double *paths_out, int32_t *status_out,
+                                          int32_t *projected_out) {
+    if (!r || !paths || !ref7 || !lo6 || !hi6) return set_err(-1, "null argument");
+    if (P < 0) return set_err(-1, "bad argument");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    if (optik_hip_path_resample_constrained(c->chain, nullptr, nullptr, nullptr, L, 0, Lout, ref7, lo6, hi6, ptol, piters,
+                                            damping, max_step, nullptr, nullptr, nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (P == 0 || (!paths_out && !status_out && !projected_out)) return 0;
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    const size_t n = (size_t)r->n, wo = (size_t)Lout * n;
+    // per path out: the waypoints, then the status word and the two counters in the bytes of two more doubles
+    return stage_paths(
+        c, paths, lens, P, (size_t)L, n, wo + 2,
+        [&](const double *d_in, const int32_t *d_len, int64_t Lc, double *d_out) {
+            int32_t *d_st = reinterpret_cast<int32_t *>(d_out + wo * (size_t)Lc);
+            return optik_hip_path_resample_constrained(c->chain, ee16 ? ee7 : nullptr, d_in, d_len, L, Lc, Lout, ref7,
+                                                       lo6, hi6, ptol, piters, damping, max_step, d_out, d_st,
+                                                       d_st + Lc, nullptr);
+        },
+        [&](size_t b0, size_t Lc, const double *h_out) {
+            const int32_t *h_st = reinterpret_cast<const int32_t *>(h_out + wo * Lc), *h_pr = h_st + Lc;
+            if (paths_out) scatter_paths(paths_out, h_out, b0, Lc, (size_t)Lout, n);
+            if (status_out) std::memcpy(status_out + b0, h_st, sizeof(int32_t) * Lc);
+            if (projected_out)
+                for (size_t k = 0; k < Lc; ++k) {
+                    projected_out[2 * (b0 + k)] = h_pr[k];
+                    projected_out[2 * (b0 + k) + 1] = h_pr[Lc + k];
+                }
+        });
+}
+
 // P paths through optik_hip_path_time; the limits travel behind the lengths in the batch block.
 int optik_robot_path_time(const optik_robot *r, int64_t P, int32_t L, const double *paths, const int32_t *lens,
                           const double *v_max, const double *a_max, double *times_out, double *vel_out,

@@ -1053,6 +1053,88 @@ class HipChain:
         """The paths path_shortcut processes per chunk of its workspace (tests cross it)."""
         return nat.path_shortcut_chunk(self._h, vertices)
 
+    # -- shortcutting and resampling under a pose constraint (include/optik_hip.h; DESIGN.md section 5.31) ---------
+    def path_shortcut_constrained(self, path, lens, c, tol, ptol=nat.CONSTRAINT_TOL, piters=nat.CONSTRAINT_ITERS,
+                                  damping=nat.CONSTRAINT_DAMPING, max_step=nat.CONSTRAINT_MAX_STEP,
+                                  resolution=nat.SHORTCUT_RESOLUTION, vertices=nat.SHORTCUT_VERTICES, hop_penalty=None,
+                                  max_waypoints=None, ee_offset7=None):
+        """path_shortcut under the pose constraint c (optik_hip_path_shortcut_constrained;
+        csrc/shortcut_constrained_measure.hpp): every subdivision vertex that is not one of the input's own waypoints
+        is projected onto c (constraint_project_batch's method at ptol, piters, damping, max_step; a vertex that does
+        not project is dead), and a pair of vertices is open only where the motion between them passes
+        collision_motion_batch AND constraint_motion_batch at `resolution`, tol, in the direction of travel.  The
+        input's waypoints never move.  Returns path_shortcut's dict plus projected [2, P] int32: the projections
+        attempted and those that ended CONSTRAINT_PROJECTED.  cost may exceed cost_in.  With a box that is free on all
+        six axes and paths within the joint limits every shared output is path_shortcut's, bit for bit.  tol has no
+        default: it says how far the straight motion between two vertices may leave c.  Stream-ordered."""
+        L, P = self._check_paths(path, lens)
+        Lout = L if max_waypoints is None else max_waypoints
+        h, hop = nat.check_shortcut_args(L, vertices, Lout, resolution, hop_penalty)
+        ref7, lo, hi = constraint_arrays(c)
+        tol = nat.check_constraint_tol(tol)
+        ptol, piters, damping, max_step = nat.check_project_args(ptol, piters, damping, max_step)
+        ee = self._ee7(ee_offset7)
+        dev = path.device
+        res = dict(path=torch.empty((int(Lout), P, self.n), dtype=torch.float64, device=dev),
+                   len=torch.empty(P, dtype=torch.int32, device=dev),
+                   cost=torch.empty(P, dtype=torch.float64, device=dev),
+                   cost_in=torch.empty(P, dtype=torch.float64, device=dev),
+                   status=torch.empty(P, dtype=torch.int32, device=dev),
+                   projected=torch.empty((2, P), dtype=torch.int32, device=dev))
+        nat.check(nat.lib().optik_hip_path_shortcut_constrained(
+            self._h, _dp(ee) if ee is not None else None, _ptr(path), _ptr(lens), L, P, int(vertices), h, hop,
+            int(Lout), _dp(ref7), _dp(lo), _dp(hi), tol, ptol, piters, damping, max_step, _ptr(res["path"]),
+            _ptr(res["len"]), _ptr(res["cost"]), _ptr(res["cost_in"]), _ptr(res["status"]), _ptr(res["projected"]),
+            _stream_ptr()))
+        return res
+
+    def path_resample_constrained(self, path, lens, c, waypoints=nat.RESAMPLE_WAYPOINTS, ptol=nat.CONSTRAINT_TOL,
+                                  piters=nat.CONSTRAINT_ITERS, damping=nat.CONSTRAINT_DAMPING,
+                                  max_step=nat.CONSTRAINT_MAX_STEP, ee_offset7=None):
+        """path_resample with every waypoint between the two ends projected onto the pose constraint c
+        (optik_hip_path_resample_constrained): returns (path [waypoints, P, n], status [P] int32, projected [2, P]
+        int32).  Status nat.RESAMPLE_UNPROJECTED (4): a projection did not end CONSTRAINT_PROJECTED and the waypoint
+        kept its interpolated value; it ranks below 2 and 3, and a path of status 3 is not projected.  The spacing is
+        equal before the projection and only approximately equal after it; the new segments are not checked.
+        Stream-ordered."""
+        L, P = self._check_paths(path, lens)
+        nat.check_shortcut_args(L, max_waypoints=waypoints)
+        ref7, lo, hi = constraint_arrays(c)
+        ptol, piters, damping, max_step = nat.check_project_args(ptol, piters, damping, max_step)
+        ee = self._ee7(ee_offset7)
+        out = torch.empty((int(waypoints), P, self.n), dtype=torch.float64, device=path.device)
+        status = torch.empty(P, dtype=torch.int32, device=path.device)
+        projected = torch.empty((2, P), dtype=torch.int32, device=path.device)
+        nat.check(nat.lib().optik_hip_path_resample_constrained(
+            self._h, _dp(ee) if ee is not None else None, _ptr(path), _ptr(lens), L, P, int(waypoints), _dp(ref7),
+            _dp(lo), _dp(hi), ptol, piters, damping, max_step, _ptr(out), _ptr(status), _ptr(projected),
+            _stream_ptr()))
+        return out, status, projected
+
+    def constraint_motion_mask(self, qa, qb, resolution, c, tol, flag, ee_offset7=None):
+        """Masks flag [B] uint8 in place with constraint_motion_batch's verdicts of qa[:, b] -> qb[:, b] ([n, B]): a
+        segment whose flag is 0 is not sampled and stays 0, every other flag becomes the ok byte
+        (optik_hip_constraint_motion_mask: what path_shortcut_constrained runs behind the motion check).  Returns
+        flag.  Stream-ordered."""
+        B = self._check_q(qa)
+        if self._check_q(qb) != B or qb.device != qa.device:
+            raise ValueError(f"qa and qb must have the same shape and device, got {tuple(qa.shape)} and {tuple(qb.shape)}")
+        if not (isinstance(flag, torch.Tensor) and flag.is_cuda and flag.dtype == torch.uint8 and flag.numel() == B
+                and flag.is_contiguous() and flag.device == qa.device):
+            raise ValueError(f"flag must be a contiguous uint8 cuda tensor of {B} flags on qa's device")
+        h = nat.check_resolution(resolution)
+        ref7, lo, hi = constraint_arrays(c)
+        tol = nat.check_constraint_tol(tol)
+        ee = self._ee7(ee_offset7)
+        nat.check(nat.lib().optik_hip_constraint_motion_mask(
+            self._h, _dp(ee) if ee is not None else None, _dp(ref7), _dp(lo), _dp(hi), _ptr(qa), _ptr(qb), B, h, tol,
+            _ptr(flag), _stream_ptr()))
+        return flag
+
+    def path_shortcut_constrained_chunk(self, vertices):
+        """The paths path_shortcut_constrained processes per chunk of its workspace (tests cross it)."""
+        return nat.path_shortcut_constrained_chunk(self._h, vertices)
+
     # -- timing and sampling (include/optik_hip.h; DESIGN.md section 5.20) ------------------------------------------
     def _limits(self, v, name, device):
         if not (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.float64 and v.numel() == self.n

@@ -99,6 +99,11 @@ def _bind(L):
     L.optik_robot_path_shortcut.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, C.c_int32, C.c_double, C.c_double, C.c_int32,
                                             dp, dp, ip, dp, dp, ip]
     L.optik_robot_path_resample.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, C.c_int32, dp, ip]
+    L.optik_robot_path_shortcut_constrained.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, C.c_int32, C.c_double,
+                                                        C.c_double, C.c_int32, dp, dp, dp, C.c_double, C.c_double,
+                                                        C.c_int32, C.c_double, C.c_double, dp, dp, ip, dp, dp, ip, ip]
+    L.optik_robot_path_resample_constrained.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, C.c_int32, dp, dp, dp,
+                                                        C.c_double, C.c_int32, C.c_double, C.c_double, dp, dp, ip, ip]
     L.optik_robot_path_time.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, dp, dp, dp, dp, dp, dp, ip]
     L.optik_robot_trajectory_sample.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, dp, dp, ip, C.c_double, C.c_int32, dp,
                                                 dp]
@@ -1567,7 +1572,8 @@ class Robot:
         """Whether P joint-space paths `paths` [P, L, n] with `lens` [P] waypoints each (None: L each) keep the pose
         constraint c: the len - 1 segments of every path go through ONE constraint_motion_batch_arrays call.
         shortcut_paths, resample_paths and optimize_paths know nothing of constraints; this tells whether their output
-        can still be used.  Returns a dict: violation [P], the largest over the path's segments (NaN if one of them is
+        can still be used (shortcut_paths_constrained and resample_paths_constrained keep one; optimize_paths has no
+        such form).  Returns a dict: violation [P], the largest over the path's segments (NaN if one of them is
         NaN or not sampled, 0 without segments); ok [P] bool, every segment ok; segment [P] int32, the first segment
         that is not, -1 when all are."""
         paths, lens = self._check_paths(paths, lens)
@@ -1675,8 +1681,9 @@ class Robot:
         bit.  "paths" and "len" go into check_paths_constraint, certify_paths and time_paths as they are; a tree's
         path has a corner at every waypoint, so give time_paths a v_max the corners can be taken at (its status 1
         says the limits were too fast for them; DESIGN.md section 5.30 has the example's figures).
-        shortcut_paths, resample_paths and optimize_paths still know nothing of constraints: check their output with
-        check_paths_constraint before using it.
+        shortcut_paths_constrained and resample_paths_constrained shorten and respace it with c kept;
+        shortcut_paths, resample_paths and optimize_paths know nothing of constraints (optimize_paths has no
+        constrained form): check their output with check_paths_constraint before using it.
         It keeps no state in the robot and reads no roadmap.  The default of piters (nat.RRT_PROJECT_ITERS) is read
         from one table and is that and nothing more; the other defaults are plan_rrt's and
         the projection's.  ValueError for what plan_rrt_to_goals and the constraint calls refuse."""
@@ -1714,13 +1721,94 @@ class Robot:
     def plan_rrt_constrained(self, starts, goals, c, *, tol, **kwargs):
         """plan_rrt under the pose constraint c, for Q pairs starts[q] -> goals[q] ([Q, n] each):
         plan_rrt_to_goals_constrained with one goal per query (its keyword arguments, its dict: "goal" is 0 where
-        the status is 0).  Its paths go into check_paths_constraint, certify_paths and time_paths as they are;
-        shortcut_paths, resample_paths and optimize_paths still know nothing of constraints."""
+        the status is 0).  Its paths go into shortcut_paths_constrained, resample_paths_constrained,
+        check_paths_constraint, certify_paths and time_paths as they are; optimize_paths still knows nothing of
+        constraints."""
         starts, goals = self._check_xs(starts), self._check_xs(goals)
         if starts.shape != goals.shape:
             raise ValueError(f"starts and goals must have the same shape, got {list(starts.shape)} and "
                              f"{list(goals.shape)}")
         return self.plan_rrt_to_goals_constrained(starts, goals[:, None, :], c, None, tol=tol, **kwargs)
+
+    # -- shortcutting and resampling under a pose constraint (extension; include/optik.h, DESIGN.md section 5.31) ----
+    def shortcut_paths_constrained(self, paths, lens, c, *, tol, resolution=nat.SHORTCUT_RESOLUTION,
+                                   vertices=nat.SHORTCUT_VERTICES, hop_penalty=None, max_waypoints=None,
+                                   ptol=nat.CONSTRAINT_TOL, iters=nat.CONSTRAINT_ITERS, damping=nat.CONSTRAINT_DAMPING,
+                                   max_step=nat.CONSTRAINT_MAX_STEP, ee_offset=None):
+        """shortcut_paths under the pose constraint c: what follows plan_rrt_constrained or plan_constrained_paths.
+        paths [P, L, n], lens [P] or None as there.  Each polyline is subdivided as shortcut_paths subdivides it; the
+        input's own waypoints, the start and the goal among them, are vertices as they are and never move; every other
+        vertex is projected onto c (constraint_project_batch_arrays' method at ptol, at most `iters` iterations,
+        damping, max_step) and a vertex that does not project is dropped.  A pair of vertices is joined only where the
+        motion between them passes the collision check AND constraint_motion_batch_arrays at `resolution`, tol, in the
+        direction of travel; the route of least (length + hop_penalty) per hop is walked.  So with status 0 every
+        new vertex has violation <= ptol and lies within the joint limits, and every segment has passed both checks at
+        the samples -- check_paths_constraint at the same tol and resolution says ok.  tol has no default: as for
+        plan_rrt_constrained it is the caller's statement of how far the straight motion between two vertices on the
+        constraint may leave it; segment interiors are not projected.
+        Returns shortcut_paths' dict plus "projected" [P, 2] int32: the projections attempted and the ones that ended
+        projected.  cost can exceed cost_in, because projected vertices leave the input's polyline: compare the two.
+        With a box that is free on all six axes and paths within the joint limits the shared outputs are
+        shortcut_paths', bit for bit.  ValueError for what shortcut_paths and the constraint calls refuse."""
+        paths, lens = self._check_paths(paths, lens)
+        P, L, n = paths.shape
+        Lout = L if max_waypoints is None else max_waypoints
+        h, hop = nat.check_shortcut_args(L, vertices, Lout, resolution, hop_penalty)
+        Lout = int(Lout)
+        ref7, lo, hi = constraint_arrays(c)
+        tol = nat.check_constraint_tol(tol)
+        ptol, iters, damping, max_step = nat.check_project_args(ptol, iters, damping, max_step)
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        out, cost, cost_in = np.zeros((P, Lout, n)), np.zeros(P), np.zeros(P)
+        ln, status = np.zeros(P, dtype=np.int32), np.zeros(P, dtype=np.int32)
+        projected = np.zeros((P, 2), dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        if self._L.optik_robot_path_shortcut_constrained(
+                self._h, P, L, _dp(paths), lens.ctypes.data_as(ip) if lens is not None else None, int(vertices), h, hop,
+                Lout, _dp(ref7), _dp(lo), _dp(hi), tol, ptol, iters, damping, max_step,
+                _dp(ee) if ee is not None else None, _dp(out), ln.ctypes.data_as(ip), _dp(cost), _dp(cost_in),
+                status.ctypes.data_as(ip), projected.ctypes.data_as(ip)):
+            raise RuntimeError(_err(self._L))
+        return dict(paths=out, len=ln, cost=cost, cost_in=cost_in, status=status, projected=projected)
+
+    def resample_paths_constrained(self, paths, lens, c, waypoints=nat.RESAMPLE_WAYPOINTS, resolution=None, tol=None,
+                                   ptol=nat.CONSTRAINT_TOL, iters=nat.CONSTRAINT_ITERS, damping=nat.CONSTRAINT_DAMPING,
+                                   max_step=nat.CONSTRAINT_MAX_STEP, ee_offset=None):
+        """resample_paths with every waypoint between the two ends projected onto the pose constraint c
+        (constraint_project_batch_arrays' method at ptol, `iters`, damping, max_step): the dense path time_paths and a
+        controller take, its waypoints on the constraint.  The ends are copied.  The spacing is equal before the
+        projection and only approximately equal after it.  Returns (paths [P, waypoints, n], status [P] int32,
+        projected [P, 2] int32): status 0; 2 a length outside 2 .. L; 3 a NaN or infinite length (nothing is
+        projected); 4 an interior waypoint could not be projected and kept its interpolated value (it ranks below 2
+        and 3); projected as in shortcut_paths_constrained.  The new segments are NOT checked by construction: with
+        `resolution` and `tol` (both or neither) it also returns free [P] bool and ok [P] bool, whether each of the
+        waypoints - 1 new segments passes collision_motion_batch_arrays and constraint_motion_batch_arrays at tol.
+        ValueError for what resample_paths and the constraint calls refuse."""
+        paths, lens = self._check_paths(paths, lens)
+        P, L, n = paths.shape
+        nat.check_shortcut_args(L, max_waypoints=waypoints)
+        if (resolution is None) != (tol is None):
+            raise ValueError("resolution and tol go together: give both for the two checks of the new segments, or neither")
+        if resolution is not None:
+            resolution, tol = nat.check_resolution(resolution), nat.check_constraint_tol(tol)
+        ref7, lo, hi = constraint_arrays(c)
+        ptol, iters, damping, max_step = nat.check_project_args(ptol, iters, damping, max_step)
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        W = int(waypoints)
+        out, status = np.zeros((P, W, n)), np.zeros(P, dtype=np.int32)
+        projected = np.zeros((P, 2), dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        if self._L.optik_robot_path_resample_constrained(
+                self._h, P, L, _dp(paths), lens.ctypes.data_as(ip) if lens is not None else None, W, _dp(ref7), _dp(lo),
+                _dp(hi), ptol, iters, damping, max_step, _dp(ee) if ee is not None else None, _dp(out),
+                status.ctypes.data_as(ip), projected.ctypes.data_as(ip)):
+            raise RuntimeError(_err(self._L))
+        if resolution is None:
+            return out, status, projected
+        qa, qb = out[:, :-1].reshape(-1, n), out[:, 1:].reshape(-1, n)
+        seg_free = self.collision_motion_batch_arrays(qa, qb, resolution, ee_offset)[1]
+        seg_ok = self.constraint_motion_batch_arrays(qa, qb, resolution, c, tol, ee_offset)[1]
+        return out, status, projected, seg_free.reshape(P, W - 1).all(axis=1), seg_ok.reshape(P, W - 1).all(axis=1)
 
     def set_motion_resolution(self, h):
         """The resolution of ik_path*'s motion check (0, the default: off).  While it is > 0 and a collision model is
