@@ -402,6 +402,19 @@ int optik_robot_path_resample_constrained(const optik_robot *robot, int64_t P, i
                                           const double *hi6, double ptol, int32_t piters, double damping,
                                           double max_step, const double *ee_offset16, double *paths_out,
                                           int32_t *status_out, int32_t *projected_out);
+/* Path optimisation that keeps a pose constraint (extension; include/optik_hip.h: optik_hip_path_optimize_constrained;
+ * DESIGN.md section 5.32).  optik_robot_path_optimize with the constraint ref7, lo6, hi6: after every update each
+ * interior waypoint is projected back onto it at ptol (at most piters iterations, damping, max_step) and keeps its old
+ * value where that fails.  violation_out [P]: the largest violation over the waypoints of the result; projected_out
+ * [P][2]: the projections attempted and those that ended projected.  Any output may be NULL.  rc 0, or -1: null
+ * argument, what the kernel layer refuses. */
+int optik_robot_path_optimize_constrained(const optik_robot *robot, int64_t P, int32_t L, const double *paths,
+                                          int32_t iters, double step, double w_smooth, double w_obs, double influence,
+                                          double safety, const double *ref7, const double *lo6, const double *hi6,
+                                          double ptol, int32_t piters, double damping, double max_step,
+                                          const double *ee_offset16, double *paths_out, double *cost_first_out,
+                                          double *cost_last_out, double *clearance_out, int32_t *status_out,
+                                          double *violation_out, int32_t *projected_out);
 /* Timing planned paths and sampling the trajectory (extension; include/optik_hip.h: optik_hip_path_time and
  * optik_hip_trajectory_sample).  paths [P][L][n] row-major with lens [P] waypoints each (NULL: L
  * each), 3 <= L <= 64 -- optik_robot_path_resample's paths_out as it is.

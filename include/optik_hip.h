@@ -588,6 +588,32 @@ int optik_hip_constraint_motion_mask(const optik_hip_chain *chain, const double 
                                      int64_t B, double resolution, double tol, uint8_t *d_flag, void *stream);
 int64_t optik_hip_path_shortcut_constrained_chunk(const optik_hip_chain *chain, int32_t V);
 
+/* Path optimisation that keeps a pose constraint (extension; the rule and its operation order:
+ * csrc/path_optimize.hpp step 7 on top of csrc/constraint_measure.hpp).  optik_hip_path_optimize with the constraint
+ * ref7, lo6, hi6 of optik_hip_constraint_batch: projected covariant gradient smoothing.  Each of the `iters` updates is
+ * optik_hip_path_optimize's update, the clamp included, and then every interior waypoint on its own is projected back
+ * onto the constraint with optik_hip_constraint_project_batch's method at ptol (at most piters iterations, damping,
+ * max_step).  A projection that does not end OPTIK_HIP_CONSTRAINT_PROJECTED leaves the waypoint at its value of the
+ * previous iterate, bit for bit: an interior waypoint that satisfies the constraint at ptol on input satisfies it in
+ * every iterate.  The two ends never move and are never projected.  It is projection after the step, not a projection
+ * in the metric; the segments between the waypoints are not looked at (optik_hip_constraint_motion_batch checks them).
+ * With a box that is free on all six axes nothing is projected and the shared outputs are optik_hip_path_optimize's,
+ * bit for bit.
+ * Outputs as there, plus d_violation [P]: the largest violation (optik_hip_constraint_batch's) over all L waypoints of
+ * the last iterate, the two ends included, NaN if one of them is; and d_projected [2][P] int32: the projections
+ * attempted over all updates, then those that ended projected.  Any output may be NULL.
+ * One wave per path, the whole loop in one launch, the projections one waypoint per lane; stream-ordered, no
+ * workspace, no allocation.  K updates in one call give the bits of K calls of one update (the counters add up),
+ * whatever P is.
+ * Refusals, before any device work and also when P = 0: optik_hip_path_optimize's, then
+ * optik_hip_constraint_project_batch's for the reference, the bounds, ptol, piters, damping and max_step. */
+int optik_hip_path_optimize_constrained(const optik_hip_chain *chain, const double *ee_offset7, const double *d_q_in,
+                                        int32_t L, int64_t P, int32_t iters, double step, double w_smooth, double w_obs,
+                                        double influence, double safety, const double *ref7, const double *lo6,
+                                        const double *hi6, double ptol, int32_t piters, double damping, double max_step,
+                                        double *d_q_out, double *d_cost_first, double *d_cost_last, double *d_clearance,
+                                        int32_t *d_status, double *d_violation, int32_t *d_projected, void *stream);
+
 /* Timing of joint paths under velocity and acceleration limits, and the sampling of the timed trajectory (extension;
  * DESIGN.md section 5.20; the arithmetic and its operation order: csrc/time_measure.hpp).  Paths are d_path [L][P][n]
  * as above, path p having d_len[p] waypoints (d_len NULL: L each), 3 <= d_len[p] <= L <= 64.  Any revolute chain of

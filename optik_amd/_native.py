@@ -168,6 +168,10 @@ def lib():
                                                 C.c_double, C.c_double, vp, vp, vp, vp]
     L.optik_hip_path_optimize.argtypes = [vp, dp, vp, C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_double,
                                           C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]
+    L.optik_hip_path_optimize_constrained.argtypes = [vp, dp, vp, C.c_int32, C.c_int64, C.c_int32, C.c_double,
+                                                      C.c_double, C.c_double, C.c_double, C.c_double, dp, dp, dp,
+                                                      C.c_double, C.c_int32, C.c_double, C.c_double, vp, vp, vp, vp, vp,
+                                                      vp, vp, vp]
     L.optik_hip_roadmap_knn.argtypes = [vp, vp, C.c_int64, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]
     L.optik_hip_roadmap_edges.argtypes = [vp, dp, vp, C.c_int64, vp, C.c_int32, vp, C.c_int32, C.c_double, C.c_int32,
                                           vp, vp]

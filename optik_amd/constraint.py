@@ -75,6 +75,17 @@ def constraint_arrays(c):
     return ref7, lo, hi
 
 
+def checked_constraint_arrays(c):
+    """constraint_arrays(c), with what PoseConstraint's constructor checks of the numbers checked again for an
+    object that did not come from it: a finite reference and lo <= hi without a NaN.  ValueError otherwise."""
+    ref7, lo, hi = constraint_arrays(c)
+    if not np.isfinite(ref7).all():
+        raise ValueError("pose constraint: the reference pose must be finite")
+    if not (lo <= hi).all():
+        raise ValueError("pose constraint: needs lo <= hi on every axis, no NaN")
+    return ref7, lo, hi
+
+
 class ConstrainedRoadmap:
     """What Robot.build_constrained_roadmap returns and Robot.plan_constrained_paths takes: the device tensors
     nodes [n, N] (a node whose projection failed is a NaN column), nbr [k, N] int32, w [k, N], and N, k, the

@@ -33,6 +33,18 @@
 //         y_i,j = ((0.0 + Ainv(i, 1) * g_1,j) + Ainv(i, 2) * g_2,j) + ...              (k ascending: no serial solve)
 //         x = q_i,j - step * y_i,j
 //         q_i,j <- x < lb_j ? lb_j : (x > ub_j ? ub_j : x)                            (a NaN stays a NaN)
+//  7. Under a pose constraint (constraint_measure.hpp: a box lo[6], hi[6] about a reference pose; DESIGN.md section
+//     5.32) an update is step 6 and then, for every interior waypoint i on its own, from x_j = the stepped and clamped
+//     value of step 6 for every joint j:
+//         the box free on every axis (lo_a == -inf and hi_a == +inf, a = 0 .. 5):   q_i <- x; nothing is evaluated and
+//             no counter moves (box_is_free, settle)
+//         otherwise constraint::project(.., ptol, piters, damping, max_step, x) as it is, attempted = attempted + 1:
+//             it ends PROJECTED:        q_i <- x as projected, ended = ended + 1
+//             any other status:         q_i keeps its old value, copied bit for bit
+//     The two end waypoints are never projected.  So a waypoint that satisfies the constraint at ptol in one iterate
+//     satisfies it in the next.  Steps 1 - 5 are unchanged; the path's violation is v = 0.0, then
+//     v = constraint::max_take(v, violation of q_t) (constraint::measure) for t = 0 .. L - 1 of the last iterate.
+//     This header does not include constraint_measure.hpp (g++ compiles it alone): the projection comes in as a callable.
 //
 // Plain host C++ compiles this header too (no HIP runtime): tests/path_optimize_util.py drives path_step with g++.
 #pragma once
@@ -102,6 +114,23 @@ OPTIK_CM_HD inline double ainv(int i, int k, int M) {
 OPTIK_CM_HD inline double stepped(const Params &p, double q, double y, double lb, double ub) {
     const double x = q - p.step * y;
     return x < lb ? lb : (x > ub ? ub : x);
+}
+
+// Step 7.
+OPTIK_CM_HD inline bool box_is_free(const double *lo6, const double *hi6) {
+    bool free_box = true;
+    for (int a = 0; a < 6; ++a) free_box = free_box && lo6[a] == -INFINITY && hi6[a] == INFINITY;
+    return free_box;
+}
+// x: step 6's values of one interior waypoint in, projected in place by project(x), which says whether it ended
+// PROJECTED.  True: q_i <- x; false: q_i keeps its old value (x is then of no use).
+template <class Project>
+OPTIK_CM_HD inline bool settle(bool free_box, double *x, Project &&project, int &attempted, int &ended) {
+    if (free_box) return true;
+    attempted = attempted + 1;
+    if (!project(x)) return false;
+    ended = ended + 1;
+    return true;
 }
 
 // The reference form (the tests' g++ driver): one evaluation of a path and, with q_new, one update.

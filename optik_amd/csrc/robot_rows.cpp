@@ -654,6 +654,58 @@ int optik_robot_path_optimize(const optik_robot *r, int64_t P, int32_t L, const 
     return 0;
 }
 
+// P paths through optik_hip_path_optimize_constrained, staged as optik_robot_path_optimize stages its paths.
+int optik_robot_path_optimize_constrained(const optik_robot *r, int64_t P, int32_t L, const double *paths,
+                                          int32_t iters, double step, double w_smooth, double w_obs, double influence,
+                                          double safety, const double *ref7, const double *lo6, const double *hi6,
+                                          double ptol, int32_t piters, double damping, double max_step,
+                                          const double *ee16, double *paths_out, double *cost_first_out,
+                                          double *cost_last_out, double *clearance_out, int32_t *status_out,
+                                          double *violation_out, int32_t *projected_out) {
+    if (!r || !paths || !ref7 || !lo6 || !hi6) return set_err(-1, "null argument");
+    if (P < 0) return set_err(-1, "bad argument");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    // (P = 0: the kernel layer's refusals of the chain, of L, iters, the parameters and the constraint)
+    if (optik_hip_path_optimize_constrained(c->chain, nullptr, nullptr, L, 0, iters, step, w_smooth, w_obs, influence,
+                                            safety, ref7, lo6, hi6, ptol, piters, damping, max_step, nullptr, nullptr,
+                                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (P == 0
+        || (!paths_out && !cost_first_out && !cost_last_out && !clearance_out && !status_out && !violation_out
+            && !projected_out))
+        return 0;
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    const size_t n = (size_t)r->n, w = (size_t)L * n;
+    // per path out: the waypoints, cost_first 3, cost_last 3, the clearance, the violation, then the status word and
+    // the two counters in the bytes of two more doubles
+    return stage_paths(
+        c, paths, nullptr, P, (size_t)L, n, w + 10,
+        [&](const double *d_in, const int32_t *, int64_t Lc, double *d_out) {
+            double *d_cf = d_out + w * (size_t)Lc, *d_cl = d_cf + 3 * Lc, *d_clr = d_cl + 3 * Lc, *d_v = d_clr + Lc;
+            int32_t *d_st = reinterpret_cast<int32_t *>(d_v + Lc);
+            return optik_hip_path_optimize_constrained(c->chain, ee16 ? ee7 : nullptr, d_in, L, Lc, iters, step, w_smooth,
+                                                       w_obs, influence, safety, ref7, lo6, hi6, ptol, piters, damping,
+                                                       max_step, d_out, d_cf, d_cl, d_clr, d_st, d_v, d_st + Lc, nullptr);
+        },
+        [&](size_t b0, size_t Lc, const double *h_out) {
+            const double *h_cf = h_out + w * Lc, *h_cl = h_cf + 3 * Lc, *h_clr = h_cl + 3 * Lc, *h_v = h_clr + Lc;
+            const int32_t *h_st = reinterpret_cast<const int32_t *>(h_v + Lc), *h_pr = h_st + Lc;
+            if (paths_out) scatter_paths(paths_out, h_out, b0, Lc, (size_t)L, n);
+            if (cost_first_out) std::memcpy(cost_first_out + 3 * b0, h_cf, sizeof(double) * 3 * Lc);
+            if (cost_last_out) std::memcpy(cost_last_out + 3 * b0, h_cl, sizeof(double) * 3 * Lc);
+            if (clearance_out) std::memcpy(clearance_out + b0, h_clr, sizeof(double) * Lc);
+            if (violation_out) std::memcpy(violation_out + b0, h_v, sizeof(double) * Lc);
+            if (status_out) std::memcpy(status_out + b0, h_st, sizeof(int32_t) * Lc);
+            if (projected_out)
+                for (size_t k = 0; k < Lc; ++k) {
+                    projected_out[2 * (b0 + k)] = h_pr[k];
+                    projected_out[2 * (b0 + k) + 1] = h_pr[Lc + k];
+                }
+        });
+}
+
 // P paths through optik_hip_path_shortcut, staged as optik_robot_path_optimize stages its paths.
 int optik_robot_path_shortcut(const optik_robot *r, int64_t P, int32_t L, const double *paths, const int32_t *lens,
                               int32_t vertices, double resolution, double hop_penalty, int32_t Lout,

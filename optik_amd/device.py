@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .constraint import constraint_arrays
+from .constraint import checked_constraint_arrays, constraint_arrays
 
 
 def _stream_ptr():
@@ -491,6 +491,43 @@ class HipChain:
             self._h, _dp(ee) if ee is not None else None, _ptr(q), L, P, int(iters), float(step), float(w_smooth),
             float(w_obs), float(influence), float(safety), _ptr(out), _ptr(res["cost_first"]), _ptr(res["cost_last"]),
             _ptr(res["clearance"]), _ptr(res["status"]), _stream_ptr()))
+        return res
+
+    def path_optimize_constrained(self, q, c, iters, step, w_smooth, w_obs, influence, safety, ptol=nat.CONSTRAINT_TOL,
+                                  piters=nat.CONSTRAINT_ITERS, damping=nat.CONSTRAINT_DAMPING,
+                                  max_step=nat.CONSTRAINT_MAX_STEP, ee_offset7=None, out=None):
+        """path_optimize under the pose constraint c (optik_hip_path_optimize_constrained; csrc/path_optimize.hpp step
+        7): after every update each interior waypoint is projected back onto c
+        (constraint_project_batch's method at ptol, piters, damping, max_step) and keeps its value of the previous
+        iterate, bit for bit, where the projection does not end CONSTRAINT_PROJECTED.  The ends never move.  Projection
+        after the step, not in the metric; the segments between the waypoints are not checked.  q, out and the
+        other arguments as path_optimize takes them.  Returns path_optimize's dict plus violation [P] (the largest
+        over the L waypoints of the result) and projected [2, P] int32 (attempted, ended projected).  With a box
+        that is free on all six axes the shared outputs are path_optimize's, bit for bit.  Stream-ordered."""
+        if not (isinstance(q, torch.Tensor) and q.is_cuda and q.dtype == torch.float64 and q.dim() == 3
+                and q.shape[2] == self.n and q.is_contiguous()):
+            raise ValueError(f"q must be a contiguous float64 cuda tensor [L, P, n] with n = {self.n}")
+        L, P = int(q.shape[0]), int(q.shape[1])
+        nat.check_path_optimize_args(L, iters, step, w_smooth, w_obs, influence, safety)
+        ref7, lo, hi = checked_constraint_arrays(c)
+        ptol, piters, damping, max_step = nat.check_project_args(ptol, piters, damping, max_step)
+        if out is None:
+            out = torch.empty_like(q)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous()
+                  and out.shape == q.shape and out.device == q.device):
+            raise ValueError("out must be a contiguous float64 cuda tensor of q's shape and device")
+        ee = self._ee7(ee_offset7)
+        res = dict(q=out, cost_first=torch.empty((P, 3), dtype=torch.float64, device=q.device),
+                   cost_last=torch.empty((P, 3), dtype=torch.float64, device=q.device),
+                   clearance=torch.empty(P, dtype=torch.float64, device=q.device),
+                   status=torch.empty(P, dtype=torch.int32, device=q.device),
+                   violation=torch.empty(P, dtype=torch.float64, device=q.device),
+                   projected=torch.empty((2, P), dtype=torch.int32, device=q.device))
+        nat.check(nat.lib().optik_hip_path_optimize_constrained(
+            self._h, _dp(ee) if ee is not None else None, _ptr(q), L, P, int(iters), float(step), float(w_smooth),
+            float(w_obs), float(influence), float(safety), _dp(ref7), _dp(lo), _dp(hi), ptol, piters, damping, max_step,
+            _ptr(out), _ptr(res["cost_first"]), _ptr(res["cost_last"]), _ptr(res["clearance"]), _ptr(res["status"]),
+            _ptr(res["violation"]), _ptr(res["projected"]), _stream_ptr()))
         return res
 
     # -- roadmap planning (include/optik_hip.h; DESIGN.md section 5.18) -------------------------------------------

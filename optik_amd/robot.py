@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _native as nat
-from .constraint import constraint_arrays
+from .constraint import checked_constraint_arrays, constraint_arrays
 
 U64_MAX = 0xFFFFFFFFFFFFFFFF
 
@@ -104,6 +104,9 @@ def _bind(L):
                                                         C.c_int32, C.c_double, C.c_double, dp, dp, ip, dp, dp, ip, ip]
     L.optik_robot_path_resample_constrained.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, C.c_int32, dp, dp, dp,
                                                         C.c_double, C.c_int32, C.c_double, C.c_double, dp, dp, ip, ip]
+    L.optik_robot_path_optimize_constrained.argtypes = [vp, C.c_int64, C.c_int32, dp, C.c_int32, C.c_double, C.c_double,
+                                                        C.c_double, C.c_double, C.c_double, dp, dp, dp, C.c_double,
+                                                        C.c_int32, C.c_double, C.c_double, dp, dp, dp, dp, dp, ip, dp, ip]
     L.optik_robot_path_time.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, dp, dp, dp, dp, dp, dp, ip]
     L.optik_robot_trajectory_sample.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, dp, dp, ip, C.c_double, C.c_int32, dp,
                                                 dp]
@@ -1572,8 +1575,8 @@ class Robot:
         """Whether P joint-space paths `paths` [P, L, n] with `lens` [P] waypoints each (None: L each) keep the pose
         constraint c: the len - 1 segments of every path go through ONE constraint_motion_batch_arrays call.
         shortcut_paths, resample_paths and optimize_paths know nothing of constraints; this tells whether their output
-        can still be used (shortcut_paths_constrained and resample_paths_constrained keep one; optimize_paths has no
-        such form).  Returns a dict: violation [P], the largest over the path's segments (NaN if one of them is
+        can still be used (shortcut_paths_constrained, resample_paths_constrained and optimize_paths_constrained
+        keep one).  Returns a dict: violation [P], the largest over the path's segments (NaN if one of them is
         NaN or not sampled, 0 without segments); ok [P] bool, every segment ok; segment [P] int32, the first segment
         that is not, -1 when all are."""
         paths, lens = self._check_paths(paths, lens)
@@ -1681,9 +1684,9 @@ class Robot:
         bit.  "paths" and "len" go into check_paths_constraint, certify_paths and time_paths as they are; a tree's
         path has a corner at every waypoint, so give time_paths a v_max the corners can be taken at (its status 1
         says the limits were too fast for them; DESIGN.md section 5.30 has the example's figures).
-        shortcut_paths_constrained and resample_paths_constrained shorten and respace it with c kept;
-        shortcut_paths, resample_paths and optimize_paths know nothing of constraints (optimize_paths has no
-        constrained form): check their output with check_paths_constraint before using it.
+        shortcut_paths_constrained, resample_paths_constrained and optimize_paths_constrained shorten, respace and
+        smooth it with c kept; shortcut_paths, resample_paths and optimize_paths know nothing of constraints: check
+        their output with check_paths_constraint before using it.
         It keeps no state in the robot and reads no roadmap.  The default of piters (nat.RRT_PROJECT_ITERS) is read
         from one table and is that and nothing more; the other defaults are plan_rrt's and
         the projection's.  ValueError for what plan_rrt_to_goals and the constraint calls refuse."""
@@ -1722,8 +1725,8 @@ class Robot:
         """plan_rrt under the pose constraint c, for Q pairs starts[q] -> goals[q] ([Q, n] each):
         plan_rrt_to_goals_constrained with one goal per query (its keyword arguments, its dict: "goal" is 0 where
         the status is 0).  Its paths go into shortcut_paths_constrained, resample_paths_constrained,
-        check_paths_constraint, certify_paths and time_paths as they are; optimize_paths still knows nothing of
-        constraints."""
+        check_paths_constraint, certify_paths and time_paths as they are, and what resample_paths_constrained makes
+        of them into optimize_paths_constrained."""
         starts, goals = self._check_xs(starts), self._check_xs(goals)
         if starts.shape != goals.shape:
             raise ValueError(f"starts and goals must have the same shape, got {list(starts.shape)} and "
@@ -1809,6 +1812,65 @@ class Robot:
         seg_free = self.collision_motion_batch_arrays(qa, qb, resolution, ee_offset)[1]
         seg_ok = self.constraint_motion_batch_arrays(qa, qb, resolution, c, tol, ee_offset)[1]
         return out, status, projected, seg_free.reshape(P, W - 1).all(axis=1), seg_ok.reshape(P, W - 1).all(axis=1)
+
+    # -- path optimisation under a pose constraint (extension; include/optik.h) ---------------
+    def optimize_paths_constrained(self, paths, c, iters=nat.PATH_OPTIMIZE_ITERS, step=nat.PATH_OPTIMIZE_STEP,
+                                   w_smooth=nat.PATH_OPTIMIZE_W_SMOOTH, w_obs=nat.PATH_OPTIMIZE_W_OBS, influence=0.2,
+                                   safety=0.05, resolution=None, tol=None, ptol=nat.CONSTRAINT_TOL,
+                                   iters_project=nat.CONSTRAINT_ITERS, damping=nat.CONSTRAINT_DAMPING,
+                                   max_step=nat.CONSTRAINT_MAX_STEP, ee_offset=None):
+        """optimize_paths under the pose constraint c: what follows resample_paths_constrained.  Projected covariant
+        gradient smoothing: each of the `iters` updates is optimize_paths' update, the clamp to the joint limits
+        included, and then every interior waypoint is projected back onto c (constraint_project_batch_arrays' method at
+        ptol, at most `iters_project` iterations, damping, max_step).  A waypoint whose projection does not end
+        projected keeps its value of the previous iterate, so an interior waypoint that satisfies c at ptol on input
+        satisfies it in the result; the two ends never move and are never projected.
+        What it is not: the projection follows the step, it is not constrained CHOMP's projection in the metric, so
+        the projected update is no longer the covariant one.  The waypoints satisfy c at ptol; the segments BETWEEN
+        them are straight in joint space, are not projected and are only checked on request.  `step` has
+        optimize_paths' caveats (it has to shrink as L^2 grows).
+        Returns a dict: paths [P, L, n], cost_first [P, 3], cost_last [P, 3], clearance [P], status [P] int32 as
+        optimize_paths returns them; violation [P], the largest violation over all L waypoints of the result (NaN if
+        one is); projected [P, 2] int32, the projections attempted over all updates and those that ended projected.
+        With `resolution` also free [P] bool: every segment of the result passes collision_motion_batch_arrays.  With
+        `resolution` and `tol` also keeps [P] bool: every segment passes check_paths_constraint at tol (tol without
+        a resolution is a ValueError).  With a box that is free on all six axes nothing is projected and the shared
+        outputs are optimize_paths', bit for bit.
+        ValueError for what optimize_paths and the constraint calls refuse."""
+        n = self.num_positions()
+        paths = np.ascontiguousarray(paths, dtype=np.float64)
+        if paths.ndim != 3 or paths.shape[2] != n:
+            raise ValueError(f"paths must be [P, L, n] with n = {n}, got {list(paths.shape)}")
+        P, L = paths.shape[0], paths.shape[1]
+        nat.check_path_optimize_args(L, iters, step, w_smooth, w_obs, influence, safety)
+        if tol is not None and resolution is None:
+            raise ValueError("tol needs a resolution: the segments are checked at its samples")
+        if resolution is not None:
+            resolution = nat.check_resolution(resolution)
+        if tol is not None:
+            tol = nat.check_constraint_tol(tol)
+        ref7, lo, hi = checked_constraint_arrays(c)
+        ptol, piters, damping, max_step = nat.check_project_args(ptol, iters_project, damping, max_step)
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        out = np.zeros((P, L, n))
+        first, last, clr, viol = np.zeros((P, 3)), np.zeros((P, 3)), np.zeros(P), np.zeros(P)
+        status, projected = np.zeros(P, dtype=np.int32), np.zeros((P, 2), dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        if self._L.optik_robot_path_optimize_constrained(
+                self._h, P, L, _dp(paths), int(iters), float(step), float(w_smooth), float(w_obs), float(influence),
+                float(safety), _dp(ref7), _dp(lo), _dp(hi), ptol, piters, damping, max_step,
+                _dp(ee) if ee is not None else None, _dp(out), _dp(first), _dp(last), _dp(clr),
+                status.ctypes.data_as(ip), _dp(viol), projected.ctypes.data_as(ip)):
+            raise RuntimeError(_err(self._L))
+        res = dict(paths=out, cost_first=first, cost_last=last, clearance=clr, violation=viol, projected=projected,
+                   status=status)
+        if resolution is not None:
+            seg_free = self.collision_motion_batch_arrays(out[:, :-1].reshape(-1, n), out[:, 1:].reshape(-1, n),
+                                                          resolution, ee_offset)[1]
+            res["free"] = seg_free.reshape(P, L - 1).all(axis=1)
+            if tol is not None:
+                res["keeps"] = self.check_paths_constraint(out, None, c, tol, resolution, ee_offset)["ok"]
+        return res
 
     def set_motion_resolution(self, h):
         """The resolution of ik_path*'s motion check (0, the default: off).  While it is > 0 and a collision model is
