@@ -477,6 +477,20 @@ int optik_robot_constraint_motion_batch(const optik_robot *robot, int64_t B, con
                                         double resolution, const double *ref7, const double *lo6, const double *hi6,
                                         double tol, const double *ee_offset16, double *violation_out, uint8_t *ok_out,
                                         int32_t *first_out, int32_t *steps_out);
+/* Up to K distinct configurations per pose region (extension; include/optik_hip.h: optik_hip_ik_region; DESIGN.md
+ * section 5.33).  regions19 [T][19] row-major, per region ref[7] (t, quaternion i j k w), lo[6], hi[6]; x0 [T][n].
+ * Every restart index in [0, restarts) runs (1 .. 2^22); tol, iters, damping, max_step as
+ * optik_robot_constraint_project_batch; mode an OPTIK_MODE_*; keep_ref7 / keep_lo6 / keep_hi6 / keep_tol a second box
+ * that every returned row must satisfy (all NULL: none).  Outputs, any may be NULL: count_out [T], x_out [T][K][n] (NaN
+ * past count), violation_out [T][K] (NaN), idx_out [T][K] (UINT64_MAX), key_out [T][K] (+inf).  On the robot's first
+ * device, whole regions of about 4 M restarts per launch.  rc 0, or -1: null argument, T < 0, restarts out of range,
+ * a region that is not valid -- a reference that is not finite or whose quaternion is not of unit norm, lo <= hi false
+ * on an axis; the message names the row --, and what the kernel layer refuses. */
+int optik_robot_ik_region(const optik_robot *robot, int32_t T, const double *regions19, const double *x0,
+                          uint64_t restarts, double tol, int32_t iters, double damping, double max_step, int32_t mode,
+                          const double *keep_ref7, const double *keep_lo6, const double *keep_hi6, double keep_tol,
+                          int32_t K, double min_dist, const double *ee_offset16, int32_t *count_out, double *x_out,
+                          double *violation_out, uint64_t *idx_out, double *key_out);
 int optik_robot_fk_ex(const optik_robot *robot, const double *x, const double *ee_offset16,
                       double *pose16_out);
 int optik_robot_joint_jacobian_ex(const optik_robot *robot, const double *x,

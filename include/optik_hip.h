@@ -1094,6 +1094,50 @@ int optik_hip_ik_path(optik_hip_chain *chain, const optik_solver_config *cfg, co
                       uint64_t restart_end, uint32_t flags, double deadline_s, double max_step,
                       const optik_hip_ik_path_outputs *out, void *stream);
 
+/* Up to K distinct configurations per pose REGION (csrc/region_measure.hpp): optik_hip_ik_solutions
+ * with a box on the pose error in the place of the exact pose, and the projection of
+ * optik_hip_constraint_project_batch in the place of the SLSQP solver.  d_regions [T][19] is DEVICE data, per region
+ * ref[7] (t, quaternion i j k w), lo[6], hi[6]; it is not validated here: by the header's rules a NaN in a reference
+ * yields OPTIK_HIP_CONSTRAINT_FAILED rows (key +inf, count 0), and a NaN bound bounds nothing on its side (the
+ * residual's comparisons are false).  The host API (optik_robot_ik_region) validates every region.  d_x0 [T][n].
+ * Restart i of region t (column t*R + (i - restart_begin), R = restart_end - restart_begin) starts at d_x0[t] for
+ * i = 0 and at the restart seed of ChaCha stream i otherwise (optik_hip_seed_batch's row, the same for every region),
+ * is projected onto the region at tol (at most iters steps, damping, max_step: optik_hip_constraint_project_batch's
+ * method and its outputs x, violation, status, iterations), and gets the key +inf unless it ended
+ * OPTIK_HIP_CONSTRAINT_PROJECTED, else (double)i for OPTIK_MODE_SPEED and ||x - x0[t]||_2 (squares summed left to
+ * right) for every other mode.  keep_ref7 / keep_lo6 / keep_hi6 (host pointers, all NULL: none) name a second box that
+ * is only measured: the key becomes +inf where the violation of the projected x against it is not <= keep_tol.
+ * Then, stream-ordered and without host synchronisation, what optik_hip_ik_solutions runs behind its solver: the key
+ * pass of modes OPTIK_MODE_MANIPULABILITY / _CONDITION, the collision filter when a model is installed, and the
+ * greedy selection of up to K rows more than min_dist (L-infinity) apart in (key, index) order.  Every returned row
+ * satisfies the region at tol, lies within the joint limits and is free when a model is installed.  Nothing is promised
+ * about how well the rows cover the region's solution manifold.
+ * Outputs, any pointer may be NULL; the per-restart arrays the selection needs live in the chain's launch workspace
+ * when they are.  Refused before any device work, at T = 0 too (a T = 0 call that passes returns 0): a null chain or
+ * out, T < 0, an empty restart range, random restarts with infinite joint limits, mode outside 1..4, what
+ * optik_hip_constraint_project_batch refuses for tol, iters, damping and max_step, what optik_hip_ik_solutions refuses
+ * for K, min_dist and the selection tiles, a keep box given in part or one optik_hip_constraint_batch would refuse, a
+ * keep_tol that is not finite and >= 0, and chains with prismatic joints.  Uses the chain's launch workspace like
+ * optik_hip_ik_solutions. */
+#define OPTIK_HIP_REGION_DOUBLES 19
+typedef struct optik_hip_ik_region_outputs {
+    double *d_x;              /* [n][T*R]   per restart: the projected configuration */
+    double *d_violation;      /* [T*R]      its violation of the region             */
+    int32_t *d_status;        /* [T*R]      OPTIK_HIP_CONSTRAINT_*                  */
+    int32_t *d_iterations;    /* [T*R]                                              */
+    double *d_key;            /* [T*R]      after the key passes, before selection  */
+    int32_t *d_count;         /* [T]                                                */
+    double *d_sol_x;          /* [T][K][n]  NaN past count                          */
+    double *d_sol_violation;  /* [T][K]     NaN past count                          */
+    uint64_t *d_sol_idx;      /* [T][K]     UINT64_MAX past count                   */
+    double *d_sol_key;        /* [T][K]     +inf past count                         */
+} optik_hip_ik_region_outputs;
+int optik_hip_ik_region(optik_hip_chain *chain, const double *ee_offset7, const double *d_regions, const double *d_x0,
+                        int32_t T, uint64_t restart_begin, uint64_t restart_end, double tol, int32_t iters,
+                        double damping, double max_step, int32_t mode, const double *keep_ref7, const double *keep_lo6,
+                        const double *keep_hi6, double keep_tol, int32_t K, double min_dist,
+                        const optik_hip_ik_region_outputs *out, void *stream);
+
 /* Test hooks: the selection stage of the three entry points above on the caller's own per-restart arrays, with no
  * solve in front -- what optik_hip_ik_batch, optik_hip_ik_solutions and one waypoint of optik_hip_ik_path launch behind
  * their solver, from the same launch code and tile plan.  d_key [T*R] (+inf or NaN: no candidate), d_x [n][T*R],

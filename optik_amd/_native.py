@@ -75,6 +75,24 @@ def check_solutions_args(k, min_dist):
     return int(k), min_dist
 
 
+class IkRegionOutputs(C.Structure):
+    """optik_hip_ik_region_outputs (include/optik_hip.h)."""
+    _fields_ = [("d_x", C.c_void_p), ("d_violation", C.c_void_p), ("d_status", C.c_void_p),
+                ("d_iterations", C.c_void_p), ("d_key", C.c_void_p), ("d_count", C.c_void_p), ("d_sol_x", C.c_void_p),
+                ("d_sol_violation", C.c_void_p), ("d_sol_idx", C.c_void_p), ("d_sol_key", C.c_void_p)]
+
+
+REGION_DOUBLES = 19  # OPTIK_HIP_REGION_DOUBLES: ref[7], lo[6], hi[6]
+REGION_RESTARTS = 256  # the default restarts of ik_region (DESIGN.md section 5.33: the table)
+
+
+def check_region_restarts(restarts):
+    """The restart count of Robot.ik_region*: an integer in 1 .. MAX_SOLUTION_RESTARTS."""
+    if isinstance(restarts, bool) or int(restarts) != restarts or not 1 <= int(restarts) <= MAX_SOLUTION_RESTARTS:
+        raise ValueError(f"restarts must be an integer in 1..{MAX_SOLUTION_RESTARTS}, got {restarts!r}")
+    return int(restarts)
+
+
 class IkPathOutputs(C.Structure):
     """optik_hip_ik_path_outputs (include/optik_hip.h)."""
     _fields_ = [("d_x", C.c_void_p), ("d_f", C.c_void_p), ("d_idx", C.c_void_p), ("d_key", C.c_void_p),
@@ -221,6 +239,9 @@ def lib():
                                          C.POINTER(IkSolutionsOutputs), vp]
     L.optik_hip_ik_path.argtypes = [vp, C.POINTER(SolverConfigC), vp, vp, C.c_int32, C.c_int32, dp, C.c_uint64,
                                     C.c_uint64, C.c_uint32, C.c_double, C.c_double, C.POINTER(IkPathOutputs), vp]
+    L.optik_hip_ik_region.argtypes = [vp, dp, vp, vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_double, C.c_int32,
+                                      C.c_double, C.c_double, C.c_int32, dp, dp, dp, C.c_double, C.c_int32, C.c_double,
+                                      C.POINTER(IkRegionOutputs), vp]
     # test hooks: the selection stages on the caller's own keys (include/optik_hip.h)
     L.optik_hip_select_from_keys.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(IkOutputs), vp]
     L.optik_hip_solutions_from_keys.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32,

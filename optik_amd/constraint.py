@@ -62,6 +62,46 @@ class PoseConstraint:
         b, inf = tilt / math.sqrt(2.0), math.inf
         return PoseConstraint(reference, [-inf, -inf, -inf, -b, -b, -inf], [inf, inf, inf, b, b, inf])
 
+    # -- goal regions (Robot.ik_region and the plan_*_to_region planners) --------------------
+    @staticmethod
+    def _tol(name, v):
+        v = float(v)
+        if not (math.isfinite(v) and v >= 0.0):
+            raise ValueError(f"pose constraint: {name} must be finite and >= 0")
+        return v
+
+    @staticmethod
+    def position_only(pose, pos_tol=0.0):
+        """"Reach this point, any orientation": the three linear components within +-pos_tol, the angular ones free.
+        With pos_tol = 0 the end effector's origin is the pose's exactly (the linear error V^-1 t is zero iff t is).
+        With pos_tol > 0 the box is on the linear part of the se3 logarithm, not on t itself: V scales no vector up
+        (its singular values are 1 along the rotation axis and 2 sin(theta / 2) / theta <= 1 across it), so
+        |t| <= |V^-1 t| <= sqrt(3) pos_tol -- the origin lies within that distance of the pose's."""
+        p, inf = PoseConstraint._tol("pos_tol", pos_tol), math.inf
+        return PoseConstraint(pose, [-p, -p, -p, -inf, -inf, -inf], [p, p, p, inf, inf, inf])
+
+    @staticmethod
+    def axis_free(pose, axis="z", pos_tol=0.0, rot_tol=0.0):
+        """"Drill here, any angle about the tool axis": the angular component about `axis` ("x", "y" or "z", of the
+        pose's own frame) free, the two others within +-rot_tol, the linear ones within +-pos_tol.
+        With both tolerances 0 the set is exactly {pose * R_axis(theta)}: the five pinned components say that X =
+        pose^-1 * fk(x) has the rotation vector w = theta * axis and the linear logarithm V(w)^-1 t = 0, that is
+        t = 0, so X = R_axis(theta); and every R_axis(theta), theta in (-pi, pi], has that error."""
+        k = {"x": 0, "y": 1, "z": 2}.get(axis)
+        if k is None:
+            raise ValueError(f"pose constraint: axis must be 'x', 'y' or 'z', got {axis!r}")
+        p, r = PoseConstraint._tol("pos_tol", pos_tol), PoseConstraint._tol("rot_tol", rot_tol)
+        lo, hi = [-p, -p, -p, -r, -r, -r], [p, p, p, r, r, r]
+        lo[3 + k], hi[3 + k] = -math.inf, math.inf
+        return PoseConstraint(pose, lo, hi)
+
+    @staticmethod
+    def around(pose, pos_tol, rot_tol):
+        """The pose within tolerances (what TRAC-IK takes as bounds): the linear components of the error within
+        +-pos_tol, the angular ones within +-rot_tol.  Both 0 pins the pose."""
+        p, r = PoseConstraint._tol("pos_tol", pos_tol), PoseConstraint._tol("rot_tol", rot_tol)
+        return PoseConstraint(pose, [-p, -p, -p, -r, -r, -r], [p, p, p, r, r, r])
+
     def __repr__(self):
         return f"PoseConstraint(ref7={self.ref7.tolist()}, lo={self.lo.tolist()}, hi={self.hi.tolist()})"
 
@@ -84,6 +124,43 @@ def checked_constraint_arrays(c):
     if not (lo <= hi).all():
         raise ValueError("pose constraint: needs lo <= hi on every axis, no NaN")
     return ref7, lo, hi
+
+
+def region_rows(regions, T):
+    """regions -- one PoseConstraint (or anything with ref7, lo, hi), broadcast over T rows, or a sequence of T of
+    them -- as the [T, 19] float64 array optik_hip_ik_region reads: per row ref7, lo, hi.  Each is validated as
+    checked_constraint_arrays validates it, and its quaternion for unit norm within 100 machine epsilons; ValueError
+    naming the row otherwise."""
+    one = hasattr(regions, "ref7")
+    seq = [regions] if one else list(regions)
+    if not one and len(seq) != T:
+        raise ValueError(f"regions must be one PoseConstraint or a sequence of T = {T}, got {len(seq)}")
+    rows = np.empty((len(seq), 19), dtype=np.float64)
+    for t, c in enumerate(seq):
+        try:
+            ref7, lo, hi = checked_constraint_arrays(c)
+            if not abs(float(ref7[3:] @ ref7[3:]) - 1.0) <= 100.0 * np.finfo(np.float64).eps:
+                raise ValueError("pose constraint: the reference quaternion must have unit norm")
+        except (ValueError, AttributeError) as e:
+            raise ValueError(f"region {t}: {e}") from None
+        rows[t, :7], rows[t, 7:13], rows[t, 13:] = ref7, lo, hi
+    return np.ascontiguousarray(np.broadcast_to(rows, (T, 19))) if one else rows
+
+
+def keep_arrays(keep):
+    """keep = (PoseConstraint, tol) or None -> (ref7, lo, hi, tol) or None, validated; ValueError otherwise."""
+    if keep is None:
+        return None
+    try:
+        c, tol = keep
+    except (TypeError, ValueError):
+        raise ValueError("keep must be (PoseConstraint, tol)") from None
+    if not hasattr(c, "ref7"):
+        raise ValueError("keep must be (PoseConstraint, tol)")
+    tol = float(tol)
+    if not (math.isfinite(tol) and tol >= 0.0):
+        raise ValueError(f"pose constraint: tol must be finite and >= 0, got {tol}")
+    return (*checked_constraint_arrays(c), tol)
 
 
 class ConstrainedRoadmap:

@@ -385,16 +385,6 @@ static int solve_locked(optik_hip_chain *ch, const optik_solver_config *cfg, con
     return 0;
 }
 
-// The per-restart arrays a selection stage reads: key [cols], x [n][cols], f [cols] with cols = T * R, column
-// t * R + (i - restart_begin).  A solver launch's (SolvedLaunch), or a caller's own (the optik_hip_*_from_keys hooks).
-struct SelectionIn {
-    double *key;
-    const double *x, *f;
-    uint64_t restart_begin, R;
-    uint64_t tiles_per_target;  // of plan_selection_tiles
-    size_t cols;
-};
-
 static SelectionIn selection_in(const SolvedLaunch &sl, uint64_t restart_begin) {
     return SelectionIn{sl.pk, sl.px, sl.pf, restart_begin, sl.R, sl.tiles_per_target, sl.cols};
 }
@@ -421,7 +411,7 @@ static SelectLaunch make_select_launch(optik_hip_chain *ch, const SelectionIn &i
     return s;
 }
 
-static SolutionsLaunch make_solutions_launch(optik_hip_chain *ch, const SelectionIn &in, int32_t K, double min_dist,
+SolutionsLaunch optik::host::make_solutions_launch(optik_hip_chain *ch, const SelectionIn &in, int32_t K, double min_dist,
                                              const optik_hip_ik_solutions_outputs *out,
                                              unsigned long long *reset_queue) {
     SolutionsLaunch s;

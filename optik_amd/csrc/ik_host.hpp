@@ -323,5 +323,21 @@ inline int grid_for(const optik_hip_chain *ch, long long work, int block, int pe
     return stride_grid(work > 0 ? (unsigned long long)work : 0ull, block, cap, opt().grid_cap);
 }
 
+// The per-restart arrays a selection stage reads: key [cols], x [n][cols], f [cols] with cols = T * R, column
+// t * R + (i - restart_begin).  A solver launch's, a caller's own (the optik_hip_*_from_keys hooks) or those of
+// optik_hip_ik_region (ik_region.hip).
+struct SelectionIn {
+    double *key;
+    const double *x, *f;
+    uint64_t restart_begin, R;
+    uint64_t tiles_per_target;  // of plan_selection_tiles
+    size_t cols;
+};
+// The launch struct of the solution-set selection, filled in one place (ik_capi.hip): optik_hip_ik_solutions, its test
+// hook and optik_hip_ik_region launch what it returns.  reset_queue: the work-item counter the last kernel puts back
+// (null: none).
+SolutionsLaunch make_solutions_launch(optik_hip_chain *ch, const SelectionIn &in, int32_t K, double min_dist,
+                                      const optik_hip_ik_solutions_outputs *out, unsigned long long *reset_queue);
+
 }  // namespace host
 }  // namespace optik

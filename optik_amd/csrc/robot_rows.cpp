@@ -1,9 +1,11 @@
 // robot_rows.cpp -- the row batches of the host API (diff_ik, manipulability, link frames, clearance, witnesses,
 // motion, roadmap plans), each one stage_rows over the robot's first device; the batches of paths (the optimiser's,
 // shortcutting, resampling, timing, sampling), which stage through the same batch block with a transpose of their own; and what they are checked against: the collision model,
-// the worlds and their builders.  (robot_host.hpp: the robot object and the shared plumbing.)
+// the worlds and their builders; and IK into pose regions (optik_robot_ik_region), chunks of whole regions through the
+// same batch block.  (robot_host.hpp: the robot object and the shared plumbing.)
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -1509,6 +1511,80 @@ int optik_robot_collision_motion_certify_batch(const optik_robot *r, int64_t B, 
             if (status_out) std::memcpy(status_out + b0, h_status, sizeof(int32_t) * L);
             if (steps_out) std::memcpy(steps_out + b0, h_status + L, sizeof(int32_t) * L);
         });
+}
+
+
+// A region as ik_constraint.hip validates a constraint; the message names the row.
+static int check_region_row(int64_t t, const double *reg) {
+    const std::string row = "ik_region: region " + std::to_string(t) + ": ";
+    double n2 = 0.0;
+    for (int i = 0; i < 7; ++i) {
+        if (!std::isfinite(reg[i])) return set_err(-1, row + "the reference pose must be finite");
+        if (i >= 3) n2 += reg[i] * reg[i];
+    }
+    if (!(std::fabs(n2 - 1.0) <= 100.0 * 2.220446049250313e-16))
+        return set_err(-1, row + "the reference quaternion must have unit norm");
+    for (int i = 0; i < 6; ++i)
+        if (!(reg[7 + i] <= reg[13 + i])) return set_err(-1, row + "needs lo <= hi on every axis, no NaN");
+    return 0;
+}
+
+int optik_robot_ik_region(const optik_robot *r, int32_t T, const double *regions19, const double *x0,
+                          uint64_t restarts, double tol, int32_t iters, double damping, double max_step, int32_t mode,
+                          const double *keep_ref7, const double *keep_lo6, const double *keep_hi6, double keep_tol,
+                          int32_t K, double min_dist, const double *ee16, int32_t *count_out, double *x_out,
+                          double *violation_out, uint64_t *idx_out, double *key_out) {
+    if (!r || T < 0 || (T > 0 && (!regions19 || !x0))) return set_err(-1, "null argument");
+    if (restarts < 1 || restarts > ((uint64_t)1 << 22))
+        return set_err(-1, "ik_region: restarts must be in 1 .. 2^22 (every restart index in [0, restarts) runs)");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    optik_hip_ik_region_outputs o;
+    std::memset(&o, 0, sizeof o);
+    // (T = 0: the kernel layer's refusals, before anything is staged)
+    if (optik_hip_ik_region(c->chain, nullptr, nullptr, nullptr, 0, 0, restarts, tol, iters, damping, max_step, mode,
+                            keep_ref7, keep_lo6, keep_hi6, keep_tol, K, min_dist, &o, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    for (int64_t t = 0; t < T; ++t)
+        if (int rc = check_region_row(t, regions19 + (size_t)t * OPTIK_HIP_REGION_DOUBLES)) return rc;
+    if (T == 0) return 0;
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    const size_t n = (size_t)r->n, W = OPTIK_HIP_REGION_DOUBLES;
+    // chunks of whole regions, about 4 M (region, restart) items a launch at most (as optik_robot_ik_solutions).  The
+    // robot's batch block: in = regions [C][19] | x0 [C][n]; out = x [C][K][n] | violation, key, idx [C][K] | count [C]
+    const size_t chunk = (size_t)std::min<uint64_t>((uint64_t)T, std::max<uint64_t>(1, ((uint64_t)4 << 20) / restarts));
+    BatchGuard guard(c);
+    if (!guard.ok()) return set_err(-1, kSetDeviceMsg);
+    if (!reserve_batch(c, (W + n) * chunk + (size_t)K * chunk * (n + 3) + chunk)) return set_err(-1, kBatchAllocMsg);
+    for (size_t t0 = 0; t0 < (size_t)T; t0 += chunk) {
+        const size_t L = std::min(chunk, (size_t)T - t0), KL = (size_t)K * L, n_in = (W + n) * L;
+        double *h_in = c->h_batch.get(), *h_out = h_in + n_in;
+        double *d_in = c->d_batch.get(), *d_x = d_in + n_in, *d_v = d_x + KL * n, *d_key = d_v + KL;
+        uint64_t *d_idx = reinterpret_cast<uint64_t *>(d_key + KL);
+        int32_t *d_count = reinterpret_cast<int32_t *>(d_idx + KL);
+        std::memcpy(h_in, regions19 + t0 * W, sizeof(double) * W * L);
+        std::memcpy(h_in + W * L, x0 + t0 * n, sizeof(double) * n * L);
+        if (hipMemcpyAsync(d_in, h_in, sizeof(double) * n_in, hipMemcpyHostToDevice, nullptr) != hipSuccess)
+            return set_err(-1, "upload failed");
+        o.d_count = d_count; o.d_sol_x = d_x; o.d_sol_violation = d_v; o.d_sol_idx = d_idx; o.d_sol_key = d_key;
+        if (optik_hip_ik_region(c->chain, ee16 ? ee7 : nullptr, d_in, d_in + W * L, (int32_t)L, 0, restarts, tol, iters,
+                                damping, max_step, mode, keep_ref7, keep_lo6, keep_hi6, keep_tol, K, min_dist, &o,
+                                nullptr))
+            return set_err(-1, optik_hip_last_error());
+        if (hipMemcpyAsync(h_out, d_x, sizeof(double) * (KL * (n + 3) + L), hipMemcpyDeviceToHost, nullptr) != hipSuccess
+            || hipStreamSynchronize(nullptr) != hipSuccess)
+            return set_err(-1, "download failed");
+        const double *hx = h_out, *hv = hx + KL * n, *hk = hv + KL;
+        const uint64_t *hi = reinterpret_cast<const uint64_t *>(hk + KL);
+        const int32_t *hc = reinterpret_cast<const int32_t *>(hi + KL);
+        if (x_out) std::memcpy(x_out + t0 * (size_t)K * n, hx, sizeof(double) * KL * n);
+        if (violation_out) std::memcpy(violation_out + t0 * (size_t)K, hv, sizeof(double) * KL);
+        if (key_out) std::memcpy(key_out + t0 * (size_t)K, hk, sizeof(double) * KL);
+        if (idx_out) std::memcpy(idx_out + t0 * (size_t)K, hi, sizeof(uint64_t) * KL);
+        if (count_out) std::memcpy(count_out + t0, hc, sizeof(int32_t) * L);
+    }
+    return 0;
 }
 
 }  // extern "C"

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .constraint import checked_constraint_arrays, constraint_arrays
+from .constraint import checked_constraint_arrays, constraint_arrays, keep_arrays
 
 
 def _stream_ptr():
@@ -1297,6 +1297,107 @@ class HipChain:
             self._h, C.byref(cfg), _ptr(targets), _ptr(x0), T, _dp(ee) if ee is not None else None,
             int(restart_begin), int(restart_end), float(deadline_s), k, min_dist, C.byref(o), _stream_ptr()))
         return bufs
+
+    # -- IK into pose regions (include/optik_hip.h) ----------------------------------------
+    def ik_region(self, regions, x0, restart_begin, restart_end, k, min_dist, tol=nat.CONSTRAINT_TOL,
+                  iters=nat.CONSTRAINT_ITERS, damping=nat.CONSTRAINT_DAMPING, max_step=nat.CONSTRAINT_MAX_STEP,
+                  mode="quality", keep=None, ee_offset7=None, per_restart=False):
+        """Up to k distinct configurations per pose region (optik_hip_ik_region; csrc/region_measure.hpp): regions
+        [T, 19] (per row ref7, lo, hi -- optik_amd.constraint.region_rows makes it; device data, not validated here:
+        a NaN in a row's reference gives it count 0) and x0 [T, n], float64 cuda tensors.  Restart i of [restart_begin,
+        restart_end) starts at x0[t] (i = 0) or at seed_batch's row i and is projected onto the region as
+        constraint_project_batch projects (tol, iters, damping, max_step); the rows that projected are taken in (key,
+        index) order -- mode "quality": ||x - x0[t]||, "speed": the index, "manipulability" / "condition": -w / -c --,
+        without the ones in collision when a model is installed and without the ones that violate keep = (constraint,
+        tol), and kept if their largest joint difference to every row kept before is > min_dist.  Stream-ordered;
+        returns a dict of device tensors: count [T] int32, x [T, k, n] (NaN past count), violation [T, k] (NaN), idx
+        [T, k] int64 (-1), key [T, k] (+inf); with per_restart also restart_x [n, T * R], restart_violation,
+        restart_key [T * R], restart_status, restart_iterations [T * R] int32 (column t * R + i - restart_begin)."""
+        k, min_dist = nat.check_solutions_args(k, min_dist)
+        tol, iters, damping, max_step = nat.check_project_args(tol, iters, damping, max_step)
+        mode = nat.solution_mode_code(mode) if isinstance(mode, str) else int(mode)
+        kp = keep_arrays(keep)
+        if not (isinstance(regions, torch.Tensor) and regions.is_cuda and regions.dtype == torch.float64
+                and regions.is_contiguous() and regions.dim() == 2 and regions.shape[1] == nat.REGION_DOUBLES):
+            raise ValueError("regions must be a contiguous float64 cuda tensor [T, 19]")
+        T = int(regions.shape[0])
+        if not (isinstance(x0, torch.Tensor) and x0.is_cuda and x0.dtype == torch.float64 and x0.is_contiguous()
+                and tuple(x0.shape) == (T, self.n)):
+            raise ValueError(f"x0 must be a contiguous float64 cuda tensor [T, n] = [{T}, {self.n}]")
+        b, e = int(restart_begin), int(restart_end)
+        if b < 0 or e <= b:
+            raise ValueError("empty restart range")
+        dev, cols = regions.device, T * (e - b)
+        res = dict(count=torch.empty(T, dtype=torch.int32, device=dev),
+                   x=torch.empty((T, k, self.n), dtype=torch.float64, device=dev),
+                   violation=torch.empty((T, k), dtype=torch.float64, device=dev),
+                   idx=torch.empty((T, k), dtype=torch.int64, device=dev),
+                   key=torch.empty((T, k), dtype=torch.float64, device=dev))
+        o = nat.IkRegionOutputs()
+        if per_restart:
+            res.update(restart_x=torch.empty((self.n, cols), dtype=torch.float64, device=dev),
+                       restart_violation=torch.empty(cols, dtype=torch.float64, device=dev),
+                       restart_status=torch.empty(cols, dtype=torch.int32, device=dev),
+                       restart_iterations=torch.empty(cols, dtype=torch.int32, device=dev),
+                       restart_key=torch.empty(cols, dtype=torch.float64, device=dev))
+            o.d_x, o.d_violation = _ptr(res["restart_x"]), _ptr(res["restart_violation"])
+            o.d_status, o.d_iterations = _ptr(res["restart_status"]), _ptr(res["restart_iterations"])
+            o.d_key = _ptr(res["restart_key"])
+        o.d_count, o.d_sol_x, o.d_sol_violation = _ptr(res["count"]), _ptr(res["x"]), _ptr(res["violation"])
+        o.d_sol_idx, o.d_sol_key = _ptr(res["idx"]), _ptr(res["key"])
+        ee = self._ee7(ee_offset7)
+        nat.check(nat.lib().optik_hip_ik_region(
+            self._h, _dp(ee) if ee is not None else None, _ptr(regions), _ptr(x0), T, b, e, tol, iters, damping,
+            max_step, mode, _dp(kp[0]) if kp else None, _dp(kp[1]) if kp else None, _dp(kp[2]) if kp else None,
+            kp[3] if kp else 0.0, k, min_dist, C.byref(o), _stream_ptr()))
+        return res
+
+    def _region_goals(self, regions, starts, restart_begin, restart_end, K, min_dist, region_args):
+        K = nat.check_roadmap_goals(K)
+        self._check_q(starts)
+        sol = self.ik_region(regions, starts.t().contiguous(), restart_begin, restart_end, K, min_dist, **region_args)
+        return sol["x"].permute(1, 2, 0).contiguous(), sol["count"]
+
+    def rrt_plan_region(self, regions, starts, restart_begin, restart_end, K, min_dist, iters, step, resolution,
+                        first=0, max_nodes=nat.RRT_NODES, Lmax=64, poll=nat.RRT_POLL, ee_offset7=None,
+                        region_args=None):
+        """rrt_plan_poses with pose regions [Q, 19] in the place of the poses: ik_region with x0 = the starts and up
+        to K <= 16 rows per region (region_args: a dict of its tol, iters, damping, max_step, mode, keep), then
+        rrt_plan_goals
+        -- back to back on the current stream, no host synchronisation between the two stages.  Returns
+        rrt_plan_goals' dict plus goals [K, n, Q] and count [Q] int32."""
+        goals, count = self._region_goals(regions, starts, restart_begin, restart_end, K, min_dist,
+                                          dict(region_args or {}, ee_offset7=ee_offset7))
+        res = self.rrt_plan_goals(starts, goals, count, iters, step, resolution, first=first, max_nodes=max_nodes,
+                                  Lmax=Lmax, poll=poll, ee_offset7=ee_offset7)
+        res["goals"], res["count"] = goals, count
+        return res
+
+    def roadmap_plan_region(self, roadmap, regions, starts, restart_begin, restart_end, K, min_dist, ks, Lmax,
+                            resolution, ee_offset7=None, region_args=None):
+        """roadmap_plan_poses with pose regions [Q, 19] in the place of the poses: ik_region with x0 = the starts
+        (region_args: a dict of its own arguments), then roadmap_plan_goals, back to back on the current stream.
+        Returns roadmap_plan_goals' dict plus goals [K, n, Q] and count [Q] int32."""
+        goals, count = self._region_goals(regions, starts, restart_begin, restart_end, K, min_dist,
+                                          dict(region_args or {}, ee_offset7=ee_offset7))
+        res = self.roadmap_plan_goals(roadmap, starts, goals, count, ks, Lmax, resolution, ee_offset7=ee_offset7)
+        res["goals"], res["count"] = goals, count
+        return res
+
+    def rrt_plan_region_constrained(self, regions, starts, c, tol, restart_begin, restart_end, K, min_dist, iters,
+                                    step, resolution, first=0, max_nodes=nat.RRT_NODES, Lmax=64, poll=nat.RRT_POLL,
+                                    ee_offset7=None, region_args=None, **constrained_args):
+        """rrt_plan_region under the path constraint c at tol: ik_region with keep = (c, tol), so every goal
+        satisfies the path constraint, then rrt_plan_constrained (**constrained_args: its ptol, piters, damping,
+        max_step; region_args: a dict of ik_region's own).  Returns rrt_plan_constrained's dict plus goals [K, n, Q]
+        and count [Q] int32."""
+        goals, count = self._region_goals(regions, starts, restart_begin, restart_end, K, min_dist,
+                                          dict(region_args or {}, keep=(c, tol), ee_offset7=ee_offset7))
+        res = self.rrt_plan_constrained(starts, goals, count, c, tol, iters, step, resolution, first=first,
+                                        max_nodes=max_nodes, Lmax=Lmax, poll=poll, ee_offset7=ee_offset7,
+                                        **constrained_args)
+        res["goals"], res["count"] = goals, count
+        return res
 
     def ik_path(self, cfg, targets, x0, restart_begin, restart_end, max_step=float("inf"), flags=0, deadline_s=0.0,
                 ee_offset7=None, bufs=None):

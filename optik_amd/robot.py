@@ -67,6 +67,9 @@ def _bind(L):
     L.optik_robot_constraint_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, dp, dp, dp]
     L.optik_robot_constraint_project_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_double, C.c_int32,
                                                        C.c_double, C.c_double, dp, dp, dp, ip, ip]
+    L.optik_robot_ik_region.argtypes = [vp, C.c_int32, dp, dp, C.c_uint64, C.c_double, C.c_int32, C.c_double, C.c_double,
+                                        C.c_int32, dp, dp, dp, C.c_double, C.c_int32, C.c_double, dp, ip, dp, dp,
+                                        C.POINTER(C.c_uint64), dp]
     L.optik_robot_constraint_motion_batch.argtypes = [vp, C.c_int64, dp, dp, C.c_double, dp, dp, dp, C.c_double, dp,
                                                       dp, C.POINTER(C.c_uint8), ip, ip]
     L.optik_robot_collision_motion_certify_batch.argtypes = [vp, C.c_int64, dp, dp, C.c_double, C.c_double, C.c_int32,
@@ -1732,6 +1735,103 @@ class Robot:
             raise ValueError(f"starts and goals must have the same shape, got {list(starts.shape)} and "
                              f"{list(goals.shape)}")
         return self.plan_rrt_to_goals_constrained(starts, goals[:, None, :], c, None, tol=tol, **kwargs)
+
+    # -- IK into pose regions and planning to them (extension; include/optik.h) --------------
+    def ik_region_batch_arrays(self, config: SolverConfig, regions, x0s, k=8, min_dist=0.1,
+                               restarts=nat.REGION_RESTARTS, tol=nat.CONSTRAINT_TOL, iters=nat.CONSTRAINT_ITERS,
+                               damping=nat.CONSTRAINT_DAMPING, max_step=nat.CONSTRAINT_MAX_STEP, keep=None,
+                               ee_offset=None):
+        """Up to k distinct configurations per pose REGION: ik_solutions_batch_arrays whose target is a box on the
+        pose error (optik_amd.PoseConstraint -- position_only, axis_free, around, upright or any box) instead of an
+        exact pose.  regions: one PoseConstraint, broadcast over the rows of x0s [T, n], or a sequence of T.  Every
+        restart index in [0, restarts) runs: restart 0 from x0s[t], restart i > 0 from the IK restart seed i, each
+        projected onto the region by constraint_project_batch_arrays' method (tol, iters, damping, max_step).  The
+        rows that projected are ranked by config.solution_mode (quality: nearest x0s[t] first; speed: lowest index;
+        manipulability / condition), and taken greedily if more than min_dist (L-infinity) from every row taken
+        before.  With a collision model installed only free rows are taken; keep = (PoseConstraint, tol) drops the
+        rows that violate that second constraint at tol (nothing is projected onto it).  Only solution_mode is read
+        of config.
+        Returns a dict: count [T] int32, x [T, k, n] (NaN past count), violation [T, k] (NaN), idx [T, k] uint64
+        (2^64 - 1), key [T, k] (+inf).  Every returned row satisfies its region at tol, lies within the joint limits,
+        is collision-free under a model, and is more than min_dist from the rows before it.  Gauss-Newton from a seed
+        is not the SLSQP solver of ik(): it may miss what ik() finds on a pinned region, and nothing is promised
+        about how the rows cover the region's solution manifold.  ValueError for a bad region (naming the row), k,
+        min_dist, restarts, keep or projection argument."""
+        from .constraint import keep_arrays, region_rows
+        x0s = self._check_xs(x0s)
+        T, n = x0s.shape
+        reg = region_rows(regions, T)
+        k, min_dist = nat.check_solutions_args(k, min_dist)
+        restarts = nat.check_region_restarts(restarts)
+        tol, iters, damping, max_step = nat.check_project_args(tol, iters, damping, max_step)
+        kp = keep_arrays(keep)
+        mode = nat.solution_mode_code(config.solution_mode)
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        count = np.zeros(T, dtype=np.int32)
+        x, v, key = np.full((T, k, n), np.nan), np.full((T, k), np.nan), np.full((T, k), np.inf)
+        idx = np.full((T, k), U64_MAX, dtype=np.uint64)
+        if self._L.optik_robot_ik_region(
+                self._h, T, _dp(reg), _dp(x0s), restarts, tol, iters, damping, max_step, mode,
+                _dp(kp[0]) if kp else None, _dp(kp[1]) if kp else None, _dp(kp[2]) if kp else None,
+                kp[3] if kp else 0.0, k, min_dist, _dp(ee) if ee is not None else None,
+                count.ctypes.data_as(C.POINTER(C.c_int32)), _dp(x), _dp(v), idx.ctypes.data_as(C.POINTER(C.c_uint64)),
+                _dp(key)):
+            raise RuntimeError(_err(self._L))
+        return dict(count=count, x=x, violation=v, idx=idx, key=key)
+
+    def ik_region(self, config: SolverConfig, region, x0, **kwargs):
+        """The single-region form of ik_region_batch_arrays (its keyword arguments): a list of up to k
+        configurations inside `region`, best first; empty when no restart projected."""
+        r = self.ik_region_batch_arrays(config, region, np.asarray(x0, dtype=np.float64)[None], **kwargs)
+        return [r["x"][0, j].copy() for j in range(int(r["count"][0]))]
+
+    def _region_goals(self, config, starts, regions, k, min_dist, region_args):
+        k = nat.check_roadmap_goals(k)
+        starts = self._check_xs(starts)
+        r = self.ik_region_batch_arrays(config, regions, starts, k=k, min_dist=min_dist, **region_args)
+        return starts, r["x"], r["count"]
+
+    def plan_to_region(self, config: SolverConfig, starts, regions, k=8, min_dist=0.1,
+                       max_waypoints=nat.PATH_OPTIMIZE_MAX_WAYPOINTS, ee_offset=None, region_args=None):
+        """plan_to_poses with pose regions in the place of the poses ("put it anywhere on this shelf"): starts [Q, n],
+        regions one PoseConstraint or Q of them.  ik_region_batch_arrays with the starts as x0s gives up to k <= 16
+        goals per region (region_args: a dict of its restarts, tol, iters, damping, max_step, keep), and plan_to_goals
+        plans to the nearest of them over the roadmap.  Returns plan_to_goals' dict plus "goals" [Q, k, n] and "count" [Q];
+        a region nothing projected onto has count 0, status 1 and goal -1.  Eager roadmaps only, as plan_to_goals."""
+        if getattr(self, "_roadmap_lazy", False):
+            raise RuntimeError(self._LAZY_GOALS_MSG)
+        starts, x, count = self._region_goals(config, starts, regions, k, min_dist,
+                                              dict(region_args or {}, ee_offset=ee_offset))
+        res = self.plan_to_goals(starts, x, counts=count, max_waypoints=max_waypoints)
+        res["goals"], res["count"] = x, count
+        return res
+
+    def plan_rrt_to_region(self, config: SolverConfig, starts, regions, k=8, min_dist=0.1, iters=None, step=None,
+                           resolution=nat.ROADMAP_RESOLUTION, first=0, max_nodes=None,
+                           max_waypoints=nat.PATH_OPTIMIZE_MAX_WAYPOINTS, poll=nat.RRT_POLL, ee_offset=None,
+                           region_args=None):
+        """plan_rrt_to_poses with pose regions in the place of the poses: ik_region_batch_arrays with the starts as
+        x0s (region_args: a dict of its restarts, tol, iters, damping, max_step, keep), then plan_rrt_to_goals.
+        Returns plan_rrt_to_goals' dict plus "goals" [Q, k, n] and "count" [Q] int32; count 0 is status 1 and goal -1."""
+        starts, x, count = self._region_goals(config, starts, regions, k, min_dist,
+                                              dict(region_args or {}, ee_offset=ee_offset))
+        res = self.plan_rrt_to_goals(starts, x, counts=count, iters=iters, step=step, resolution=resolution,
+                                     first=first, max_nodes=max_nodes, max_waypoints=max_waypoints, poll=poll,
+                                     ee_offset=ee_offset)
+        res["goals"], res["count"] = x, count
+        return res
+
+    def plan_rrt_to_region_constrained(self, config: SolverConfig, starts, regions, c, *, tol, k=8, min_dist=0.1,
+                                       region_args=None, ee_offset=None, **kwargs):
+        """plan_rrt_to_region under the path constraint c at tol ("carry the glass upright to anywhere on the
+        shelf"): ik_region_batch_arrays with keep = (c, tol), so every goal satisfies the path constraint, then
+        plan_rrt_to_goals_constrained (**kwargs: its iters, step, resolution, ptol, piters, ...; region_args: a dict
+        of ik_region_batch_arrays' own).  Returns plan_rrt_to_goals_constrained's dict plus "goals" and "count"."""
+        starts, x, count = self._region_goals(config, starts, regions, k, min_dist,
+                                              dict(region_args or {}, keep=(c, tol), ee_offset=ee_offset))
+        res = self.plan_rrt_to_goals_constrained(starts, x, c, count, tol=tol, ee_offset=ee_offset, **kwargs)
+        res["goals"], res["count"] = x, count
+        return res
 
     # -- shortcutting and resampling under a pose constraint (extension; include/optik.h, DESIGN.md section 5.31) ----
     def shortcut_paths_constrained(self, paths, lens, c, *, tol, resolution=nat.SHORTCUT_RESOLUTION,
