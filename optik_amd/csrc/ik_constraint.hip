@@ -1,70 +1,54 @@
 // ik_constraint.hip -- pose constraints on the device (constraint_measure.hpp): the residual
 // and violation of configurations against a box on the pose error, their projection onto it, and the check of the box
-// along straight joint-space motions.  optik_hip_constraint_batch, optik_hip_constraint_project_batch and
-// optik_hip_constraint_motion_batch (include/optik_hip.h).
+// along straight joint-space motions.  optik_hip_constraint_batch, optik_hip_constraint_project_batch,
+// optik_hip_constraint_motion_batch and optik_hip_constraint_motion_mask (include/optik_hip.h).
 //
 //   constraint_kernel<CH>          one row per lane: FK, error, residual [6][B], violation [B]
 //   constraint_project_kernel<CH>  one row per lane: the damped Gauss-Newton loop of the header, x [n][B], violation,
 //                                  status, iterations [B]
 //   constraint_motion_kernel<CH>   one segment per lane: its K + 1 samples in turn, violation, ok, first, steps [B]
-// CH is ChainDev (n <= 8) or WideChainDev (9 .. 16): one run-time-n body each, the chain table staged in LDS.  All three
+//   constraint_motion_mask_kernel<CH>  the same body (motion_body) with another store: a segment whose flag is 0
+//                                  already is not sampled, every other flag becomes the motion's ok.  The shortcutter
+//                                  reaches it through constraint_mask_launch (ik_host.hpp).
+// CH is ChainDev (n <= 8) or WideChainDev (9 .. 16): one run-time-n body each, the chain table staged in LDS.  All four
 // are grid-stride row kernels without atomics; no lane waits for another, so rows whose loops differ in length (the
-// projection's iterations, a motion's samples) cost their wave the longest of them and nothing else.  The constraint
-// travels with the launch (kernel arguments); the chain handle keeps nothing of it.
-#include "collision_device.hpp"
-#include "constraint_measure.hpp"
+// projection's iterations, a motion's samples) cost their wave the longest of them and nothing else.  The record's
+// head, the refusals of a box and the dispatch on CH are constraint_device.hpp's, shared with the other users of a
+// constraint.
+#include "constraint_device.hpp"
 
 using namespace optik;
 using namespace optik::host;
 using namespace optik::hostparams;
+using namespace optik::condev;
 
 namespace {
 
 struct ConstraintLaunch {
-    const ChainDev *chain;       // n <= 8
-    const WideChainDev *wchain;  // 9 .. 16 joint positions
-    EvalParams ep;               // only the ee_offset part is used
-    constraint::Box c;
+    ConstraintDev d;
     const double *q;             // [n][B]: the configurations (motion: qa)
     const double *qb;            // motion: [n][B]
     long long B;
-    double tol, damping, max_step, h;
-    int iters;
+    ProjectArgs p;               // project
+    double h, tol;               // motion: the resolution, the violation a sample may have
     double *residual;            // [6][B]
     double *violation;           // [B]
     double *x;                   // project: [n][B]
     int32_t *status, *iterations;  // project: [B]
-    uint8_t *ok;                 // motion: [B]
+    uint8_t *ok;                 // motion: [B]; the mask form reads it first
     int32_t *first, *steps;      // motion: [B]
 };
 
 template <class CH>
-__device__ __forceinline__ const CH *table_of(const ConstraintLaunch &a);
-template <>
-__device__ __forceinline__ const ChainDev *table_of<ChainDev>(const ConstraintLaunch &a) { return a.chain; }
-template <>
-__device__ __forceinline__ const WideChainDev *table_of<WideChainDev>(const ConstraintLaunch &a) { return a.wchain; }
-
-template <class CH>
-__device__ __forceinline__ void stage_table(CH &dst, const CH *src) {
-    constexpr int ND = (int)(sizeof(CH) / sizeof(double));
-    static_assert(sizeof(CH) % sizeof(double) == 0, "the chain table is a whole number of doubles");
-    const double *s = reinterpret_cast<const double *>(src);
-    double *d = reinterpret_cast<double *>(&dst);
-    for (int i = threadIdx.x; i < ND; i += blockDim.x) d[i] = s[i];
-    __syncthreads();
-}
-
-template <class CH>
 __global__ __launch_bounds__(256) void constraint_kernel(const ConstraintLaunch a) {
     __shared__ CH sch;
-    stage_table(sch, table_of<CH>(a));
+    stage_table(sch, table_of<CH>(a.d));
     const int n = sch.n_pos;
     for (long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x; b < a.B;
          b += (long long)gridDim.x * blockDim.x) {
         double q[constraint::MAXN], r[6];
         for (int i = 0; i < n; ++i) q[i] = a.q[(size_t)i * a.B + b];
-        const double v = constraint::measure(sch, a.ep, a.c, n, q, r);
+        const double v = constraint::measure(sch, a.d.ep, a.d.c, n, q, r);
         if (a.residual)
             for (int i = 0; i < 6; ++i) a.residual[(size_t)i * a.B + b] = r[i];
         if (a.violation) a.violation[b] = v;
@@ -74,14 +58,13 @@ __global__ __launch_bounds__(256) void constraint_kernel(const ConstraintLaunch 
 template <class CH>
 __global__ __launch_bounds__(256) void constraint_project_kernel(const ConstraintLaunch a) {
     __shared__ CH sch;
-    stage_table(sch, table_of<CH>(a));
+    stage_table(sch, table_of<CH>(a.d));
     const int n = sch.n_pos;
     for (long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x; b < a.B;
          b += (long long)gridDim.x * blockDim.x) {
         double x[constraint::MAXN];
         for (int i = 0; i < n; ++i) x[i] = a.q[(size_t)i * a.B + b];
-        const constraint::Projected p =
-            constraint::project(sch, a.ep, a.c, n, a.tol, a.iters, a.damping, a.max_step, x);
+        const constraint::Projected p = project(sch, a.d, a.p, n, x);
         if (a.x)
             for (int i = 0; i < n; ++i) a.x[(size_t)i * a.B + b] = x[i];
         if (a.violation) a.violation[b] = p.violation;
@@ -90,39 +73,41 @@ __global__ __launch_bounds__(256) void constraint_project_kernel(const Constrain
     }
 }
 
-template <class CH>
-__global__ __launch_bounds__(256) void constraint_motion_kernel(const ConstraintLaunch a) {
+// MASK: a.ok [B] is read and written in place, nothing else is stored.
+template <class CH, bool MASK>
+__device__ __forceinline__ void motion_body(const ConstraintLaunch &a) {
     __shared__ CH sch;
-    stage_table(sch, table_of<CH>(a));
+    stage_table(sch, table_of<CH>(a.d));
     const int n = sch.n_pos;
     for (long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x; b < a.B;
          b += (long long)gridDim.x * blockDim.x) {
+        if constexpr (MASK)
+            if (a.ok[b] == 0) continue;  // (the verdict is the AND; the skip only saves the samples)
         const constraint::MotionResult m =
-            constraint::motion(sch, a.ep, a.c, n, a.q + b, a.B, a.qb + b, a.B, a.h, a.tol);
-        if (a.violation) a.violation[b] = m.violation;
-        if (a.ok) a.ok[b] = (uint8_t)m.ok;
-        if (a.first) a.first[b] = m.first;
-        if (a.steps) a.steps[b] = m.steps;
+            constraint::motion(sch, a.d.ep, a.d.c, n, a.q + b, a.B, a.qb + b, a.B, a.h, a.tol);
+        if constexpr (MASK) {
+            a.ok[b] = (uint8_t)m.ok;
+        } else {
+            if (a.violation) a.violation[b] = m.violation;
+            if (a.ok) a.ok[b] = (uint8_t)m.ok;
+            if (a.first) a.first[b] = m.first;
+            if (a.steps) a.steps[b] = m.steps;
+        }
     }
 }
+
+template <class CH>
+__global__ __launch_bounds__(256) void constraint_motion_kernel(const ConstraintLaunch a) { motion_body<CH, false>(a); }
+
+template <class CH>
+__global__ __launch_bounds__(256) void constraint_motion_mask_kernel(const ConstraintLaunch a) { motion_body<CH, true>(a); }
 
 // The refusals every entry shares, in this order: the handle, the constraint, tol, the chain.  0 or a fail() code.
 int check_call(const optik_hip_chain *ch, const double *ref7, const double *lo6, const double *hi6, double tol,
                int64_t B) {
     if (!ch || B < 0) return fail(OPTIK_HIP_EINVAL, "bad argument");
-    if (!ref7 || !lo6 || !hi6) return fail(OPTIK_HIP_EINVAL, "pose constraint: null reference or bounds");
-    double n2 = 0.0;
-    for (int i = 0; i < 7; ++i) {
-        if (!std::isfinite(ref7[i])) return fail(OPTIK_HIP_EINVAL, "pose constraint: the reference pose must be finite");
-        if (i >= 3) n2 += ref7[i] * ref7[i];
-    }
-    // (the tolerance the Python layer applies to a target's rotation: 100 machine epsilons)
-    if (!(std::fabs(n2 - 1.0) <= 100.0 * 2.220446049250313e-16))
-        return fail(OPTIK_HIP_EINVAL, "pose constraint: the reference quaternion must have unit norm");
-    for (int i = 0; i < 6; ++i)
-        if (!(lo6[i] <= hi6[i])) return fail(OPTIK_HIP_EINVAL, "pose constraint: needs lo <= hi on every axis, no NaN");
-    if (!(tol >= 0.0) || !std::isfinite(tol))
-        return fail(OPTIK_HIP_EINVAL, "pose constraint: tol must be finite and >= 0");
+    if (int rc = check_box(ref7, lo6, hi6)) return rc;
+    if (int rc = check_tol(tol)) return rc;
     if (ch->prismatic) return fail(OPTIK_HIP_EUNSUPPORTED, colldev::prismatic_msg());
     return 0;
 }
@@ -130,25 +115,32 @@ int check_call(const optik_hip_chain *ch, const double *ref7, const double *lo6,
 void fill(const optik_hip_chain *ch, const double *ee_offset7, const double *ref7, const double *lo6,
           const double *hi6, int64_t B, ConstraintLaunch &a) {
     std::memset(&a, 0, sizeof a);
-    a.chain = ch->dev;
-    a.wchain = ch->wdev;
-    const double one[3] = {1, 1, 1};
-    make_eval_params(one, one, ee_offset7, a.ep);
-    std::memcpy(a.c.ref, ref7, sizeof a.c.ref);
-    std::memcpy(a.c.lo, lo6, sizeof a.c.lo);
-    std::memcpy(a.c.hi, hi6, sizeof a.c.hi);
+    fill_constraint(ch, ee_offset7, ref7, lo6, hi6, a.d);
     a.B = B;
 }
 
-#define CONSTRAINT_LAUNCH(KERNEL, CHAIN, A, STREAM)                                                              \
-    do {                                                                                                         \
-        const int grid_ = grid_for((CHAIN), (A).B, 256, 8);                                                      \
-        if ((CHAIN)->wide) hipLaunchKernelGGL(KERNEL<WideChainDev>, dim3(grid_), dim3(256), 0, (STREAM), (A));   \
-        else hipLaunchKernelGGL(KERNEL<ChainDev>, dim3(grid_), dim3(256), 0, (STREAM), (A));                     \
-        HIP_TRY(hipGetLastError());                                                                              \
-    } while (0)
-
 }  // namespace
+
+namespace optik {
+namespace host {
+
+int constraint_mask_launch(const optik_hip_chain *ch, const double *ee_offset7, const double *ref7, const double *lo6,
+                           const double *hi6, const double *qa, const double *qb, long long B, double resolution,
+                           double tol, uint8_t *flag, hipStream_t stream) {
+    BIND_DEVICE(ch);
+    ConstraintLaunch a;
+    fill(ch, ee_offset7, ref7, lo6, hi6, B, a);
+    a.q = qa;
+    a.qb = qb;
+    a.h = resolution;
+    a.tol = tol;
+    a.ok = flag;
+    CONSTRAINT_LAUNCH(constraint_motion_mask_kernel, ch, grid_for(ch, B, 256, 8), 256, stream, a);
+    return 0;
+}
+
+}  // namespace host
+}  // namespace optik
 
 extern "C" {
 
@@ -164,7 +156,7 @@ int optik_hip_constraint_batch(const optik_hip_chain *ch, const double *ee_offse
     a.q = d_q;
     a.residual = d_residual;
     a.violation = d_violation;
-    CONSTRAINT_LAUNCH(constraint_kernel, ch, a, (hipStream_t)stream);
+    CONSTRAINT_LAUNCH(constraint_kernel, ch, grid_for(ch, B, 256, 8), 256, (hipStream_t)stream, a);
     return 0;
 }
 
@@ -173,25 +165,19 @@ int optik_hip_constraint_project_batch(const optik_hip_chain *ch, const double *
                                        int32_t iters, double damping, double max_step, double *d_x,
                                        double *d_violation, int32_t *d_status, int32_t *d_iterations, void *stream) {
     if (int rc = check_call(ch, ref7, lo6, hi6, tol, B)) return rc;
-    if (iters < 0 || iters > OPTIK_HIP_CONSTRAINT_MAX_ITERS)
-        return fail(OPTIK_HIP_EINVAL, "pose constraint: iters must be 0 .. 4096");
-    if (!(damping >= 0.0) || !std::isfinite(damping) || !(max_step > 0.0) || !std::isfinite(max_step))
-        return fail(OPTIK_HIP_EINVAL, "pose constraint: needs damping >= 0 and max_step > 0, both finite");
+    if (int rc = check_project_args(tol, iters, damping, max_step)) return rc;
     if (B == 0 || (!d_x && !d_violation && !d_status && !d_iterations)) return 0;
     if (!d_q) return fail(OPTIK_HIP_EINVAL, "bad argument");
     BIND_DEVICE(ch);
     ConstraintLaunch a;
     fill(ch, ee_offset7, ref7, lo6, hi6, B, a);
     a.q = d_q;
-    a.tol = tol;
-    a.iters = iters;
-    a.damping = damping;
-    a.max_step = max_step;
+    a.p = ProjectArgs{tol, damping, max_step, iters};
     a.x = d_x;
     a.violation = d_violation;
     a.status = d_status;
     a.iterations = d_iterations;
-    CONSTRAINT_LAUNCH(constraint_project_kernel, ch, a, (hipStream_t)stream);
+    CONSTRAINT_LAUNCH(constraint_project_kernel, ch, grid_for(ch, B, 256, 8), 256, (hipStream_t)stream, a);
     return 0;
 }
 
@@ -215,8 +201,22 @@ int optik_hip_constraint_motion_batch(const optik_hip_chain *ch, const double *e
     a.ok = d_ok;
     a.first = d_first;
     a.steps = d_steps;
-    CONSTRAINT_LAUNCH(constraint_motion_kernel, ch, a, (hipStream_t)stream);
+    CONSTRAINT_LAUNCH(constraint_motion_kernel, ch, grid_for(ch, B, 256, 8), 256, (hipStream_t)stream, a);
     return 0;
+}
+
+int optik_hip_constraint_motion_mask(const optik_hip_chain *ch, const double *ee_offset7, const double *ref7,
+                                     const double *lo6, const double *hi6, const double *d_qa, const double *d_qb,
+                                     int64_t B, double resolution, double tol, uint8_t *d_flag, void *stream) {
+    // (B = 0: optik_hip_constraint_motion_batch's own refusals)
+    if (int rc = optik_hip_constraint_motion_batch(ch, nullptr, ref7, lo6, hi6, nullptr, nullptr, 0, resolution, tol,
+                                                   nullptr, nullptr, nullptr, nullptr, nullptr))
+        return rc;
+    if (B < 0) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    if (B == 0) return 0;
+    if (!d_qa || !d_qb || !d_flag) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    return constraint_mask_launch(ch, ee_offset7, ref7, lo6, hi6, d_qa, d_qb, B, resolution, tol, d_flag,
+                                  (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -153,6 +153,14 @@ int motion_reserve(optik_hip_chain *ch, long long segments);
 int motion_key_launch(const optik_hip_chain *ch, const double *ee_offset7, const double *seed, const double *x,
                       double *key, int P, size_t R, int filter, double max_step, hipStream_t stream);
 
+// ---- pose constraints (ik_constraint.hip) ----------------------------------------------------------------------
+// The mask form of the check along a motion, for a caller that has validated its arguments: of the B segments qa -> qb
+// ([n][B] each) every one whose flag is not 0 already is sampled at `resolution` against the box (ref7, lo6, hi6), and
+// its flag becomes whether every sample's violation is <= tol; one kernel on `stream`.  0 or a fail() code.
+int constraint_mask_launch(const optik_hip_chain *ch, const double *ee_offset7, const double *ref7, const double *lo6,
+                           const double *hi6, const double *qa, const double *qb, long long B, double resolution,
+                           double tol, uint8_t *flag, hipStream_t stream);
+
 // ---- options ---------------------------------------------------------------------------------------------
 // Every tuning option of the kernel layer, in one place.  The defaults come from the environment ONCE, at the
 // first use (the OPTIK_* names below); tests and tools change them through optik_hip_set_option (optik_hip.h).

@@ -40,13 +40,6 @@ __device__ __forceinline__ void wide_jacobian_column(const WideChainDev &sch, co
 }
 
 // A wide chain's table into the block's LDS copy.
-__device__ __forceinline__ void stage_wide_chain(WideChainDev &dst, const WideChainDev *src) {
-    constexpr int ND = (int)(sizeof(WideChainDev) / sizeof(double));
-    static_assert(sizeof(WideChainDev) % sizeof(double) == 0, "WideChainDev is a whole number of doubles");
-    const double *s = reinterpret_cast<const double *>(src);
-    double *d = reinterpret_cast<double *>(&dst);
-    for (int i = threadIdx.x; i < ND; i += blockDim.x) d[i] = s[i];
-    __syncthreads();
-}
+__device__ __forceinline__ void stage_wide_chain(WideChainDev &dst, const WideChainDev *src) { stage_table(dst, src); }
 
 }  // namespace optik

@@ -18,14 +18,24 @@ struct SolveLaunch {
     unsigned long long deadline_ticks;  // relative to kernel start, 0 = none
 };
 
-__device__ __forceinline__ void stage_chain(ChainDev &dst, const ChainDev *src) {
-    constexpr int ND = (int)(sizeof(ChainDev) / sizeof(double));
-    static_assert(sizeof(ChainDev) % sizeof(double) == 0, "ChainDev is a whole number of doubles");
+// A chain table (ChainDev, or WideChainDev of ik_wide_launch.hpp) into the block's LDS copy, by every thread of the
+// block.  copy_table leaves the barrier to a caller that has one of its own coming.
+template <class CH>
+__device__ __forceinline__ void copy_table(CH &dst, const CH *src) {
+    constexpr int ND = (int)(sizeof(CH) / sizeof(double));
+    static_assert(sizeof(CH) % sizeof(double) == 0, "the chain table is a whole number of doubles");
     const double *s = reinterpret_cast<const double *>(src);
     double *d = reinterpret_cast<double *>(&dst);
     for (int i = threadIdx.x; i < ND; i += blockDim.x) d[i] = s[i];
+}
+
+template <class CH>
+__device__ __forceinline__ void stage_table(CH &dst, const CH *src) {
+    copy_table(dst, src);
     __syncthreads();
 }
+
+__device__ __forceinline__ void stage_chain(ChainDev &dst, const ChainDev *src) { stage_table(dst, src); }
 
 // ik_quad_kernel.hip: the quad-distributed solver (ik_quad.hpp), n <= 8.  Launches `grid` single-wave
 // workgroups on `stream`; *lds_bytes = static LDS of the kernel.  latency_form: the one-wave-per-SIMD

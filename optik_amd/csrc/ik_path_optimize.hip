@@ -4,7 +4,9 @@
 //   path_optimize_kernel<N, TIP>   one wave per path, lane t = waypoint t (lanes >= L idle), the whole iteration
 //                                  loop in one launch
 //   path_optimize_constrained_kernel<N, TIP>   the same loop under a pose constraint (path_optimize.hpp step 7;
-//                                  DESIGN.md section 5.32): after the step every interior lane projects its own
+//                                  DESIGN.md section 5.32), kept as a kernel of its own: one body for both moved
+//                                  the plain kernel's register record (profiles/constraint_plumbing_refactor.txt).
+//                                  After the step every interior lane projects its own
 //                                  waypoint back onto the box (constraint::project, the header's own function, as
 //                                  shortcut_cgather_kernel calls it) and keeps the old one where that fails; the
 //                                  last evaluation also measures every waypoint's violation.  The projection reads
@@ -13,20 +15,21 @@
 // 256 threads = 4 paths per block, grid-stride over the paths; the chain table and the model are staged in LDS once
 // per block as collision_witness_kernel stages them.  A wave keeps its path's iterate and its gradient g in LDS,
 // [N][64] doubles each (joint-major: a lane reads its neighbours' waypoints and the wave-uniform g_k without bank
-// conflicts), and three [64] rows of per-waypoint partial sums.  Per evaluation every lane runs FK and the witness
-// distance pass of its own waypoint (collision_witness_device.hpp, unchanged), folds the rows' hinge and gradients
-// into o_t and gobs_t, and reads its neighbours from LDS for s_t and g_t; the update is the closed-form Ainv sum, M
-// terms read from LDS per lane, no serial solve.  Lane 0 sums the partials in ascending order at the first and the
+// conflicts), and three [64] rows of per-waypoint partial sums (four under a constraint: the violation).  Per
+// evaluation every lane runs FK and the witness distance pass of its own waypoint (collision_witness_device.hpp,
+// unchanged), folds the rows' hinge and gradients into o_t and gobs_t, and reads its neighbours from LDS for s_t and
+// g_t; the update is the closed-form Ainv sum, M terms read from LDS per lane, no serial solve.  Lane 0 sums the partials in ascending order at the first and the
 // last evaluation.  Nothing crosses a wave: after the staging barrier the waves of a block never meet again, so the
 // result does not depend on the launch shape.
 #include "collision_witness_device.hpp"
-#include "constraint_measure.hpp"
+#include "constraint_device.hpp"
 #include "path_optimize.hpp"
 
 using namespace optik;
 using namespace optik::host;
 using namespace optik::hostparams;
 using namespace optik::colldev;
+using namespace optik::condev;
 
 static_assert(pathopt::MAX_WAYPOINTS == OPTIK_HIP_PATH_OPTIMIZE_MAX_WAYPOINTS && pathopt::MAX_WAYPOINTS == 64,
               "one lane of a wave per waypoint; optik_hip.h states the cap of path_optimize.hpp");
@@ -173,12 +176,10 @@ __global__ __launch_bounds__(64 * WAVES) void path_optimize_kernel(const PathOpt
     }
 }
 
-// The constraint's side of a constrained launch (ik_shortcut.hip's ConLaunch, without the parts of a motion check): it
-// travels with the call, the chain handle keeps nothing of it.
+// The constraint's side of a constrained launch: it travels with the call, the chain handle keeps nothing of it.
 struct PathConLaunch {
-    constraint::Box c;
-    double ptol, damping, max_step;  // the projection
-    int piters;
+    constraint::Box c;               // (the chain and ee_offset of a ConstraintDev are PathOptLaunch's already)
+    ProjectArgs p;
     double *violation;               // [P] or null
     int32_t *projected;              // [2][P] or null
 };
@@ -304,8 +305,8 @@ __global__ __launch_bounds__(64 * WAVES) void path_optimize_constrained_kernel(c
 #pragma unroll
                 for (int j = 0; j < N; ++j) x[j] = pathopt::stepped(a.p, q[j], y[j], sch.lb[j], sch.ub[j]);
                 const bool take = pathopt::settle(free_box, x, [&](double *z) {
-                    return constraint::project(sch, a.c.ep, con.c, N, con.ptol, con.piters, con.damping, con.max_step, z).status
-                           == constraint::PROJECTED;
+                    return constraint::project(sch, a.c.ep, con.c, N, con.p.tol, con.p.iters, con.p.damping, con.p.max_step,
+                                               z).status == constraint::PROJECTED;
                 }, attempted, ended);
                 // (q itself is never handed to the projection: it stays in registers, and the fallback is a select)
 #pragma unroll
@@ -329,6 +330,20 @@ __global__ __launch_bounds__(64 * WAVES) void path_optimize_constrained_kernel(c
         }
         wave_lds_sync();
     }
+}
+
+// What both entries put into the record, their arguments checked.
+void fill_path_launch(const optik_hip_chain *ch, const double *ee_offset7, const double *d_q_in, int32_t L, int64_t P,
+                      int32_t iters, const pathopt::Params &prm, double *d_q_out, double *d_cost_first,
+                      double *d_cost_last, double *d_clearance, int32_t *d_status, PathOptLaunch &a) {
+    std::memset(&a, 0, sizeof a);
+    fill_launch(ch, ee_offset7, nullptr, P, a.c);
+    a.orig = ch->coll_orig.get();
+    a.q_in = d_q_in; a.q_out = d_q_out;
+    a.P = P; a.L = L; a.iters = iters;
+    a.p = prm;
+    a.cost_first = d_cost_first; a.cost_last = d_cost_last;
+    a.clearance = d_clearance; a.status = d_status;
 }
 
 const char *const kPathOptWideMsg = "path_optimize: chains of more than 8 joint positions are not supported";
@@ -356,14 +371,8 @@ int optik_hip_path_optimize(const optik_hip_chain *ch, const double *ee_offset7,
     if (!d_q_in) return fail(OPTIK_HIP_EINVAL, "bad argument");
     BIND_DEVICE(ch);
     PathOptLaunch a;
-    std::memset(&a, 0, sizeof a);
-    fill_launch(ch, ee_offset7, nullptr, P, a.c);
-    a.orig = ch->coll_orig.get();
-    a.q_in = d_q_in; a.q_out = d_q_out;
-    a.P = P; a.L = L; a.iters = iters;
-    a.p = prm;
-    a.cost_first = d_cost_first; a.cost_last = d_cost_last;
-    a.clearance = d_clearance; a.status = d_status;
+    fill_path_launch(ch, ee_offset7, d_q_in, L, P, iters, prm, d_q_out, d_cost_first, d_cost_last, d_clearance, d_status,
+                     a);
     const int grid = grid_for(ch, P * 64, 64 * WAVES, 8);
 #define CALL(NN, TT) hipLaunchKernelGGL((path_optimize_kernel<NN, TT>), dim3(grid), dim3(64 * WAVES), 0, (hipStream_t)stream, a)
     OPTIK_DISPATCH(ch, CALL);
@@ -394,20 +403,13 @@ int optik_hip_path_optimize_constrained(const optik_hip_chain *ch, const double 
     if (!d_q_in) return fail(OPTIK_HIP_EINVAL, "bad argument");
     BIND_DEVICE(ch);
     PathOptLaunch a;
-    std::memset(&a, 0, sizeof a);
-    fill_launch(ch, ee_offset7, nullptr, P, a.c);
-    a.orig = ch->coll_orig.get();
-    a.q_in = d_q_in; a.q_out = d_q_out;
-    a.P = P; a.L = L; a.iters = iters;
-    a.p = pathopt::Params{step, w_smooth, w_obs, influence, safety};
-    a.cost_first = d_cost_first; a.cost_last = d_cost_last;
-    a.clearance = d_clearance; a.status = d_status;
-    PathConLaunch con;
-    std::memset(&con, 0, sizeof con);
-    std::memcpy(con.c.ref, ref7, sizeof con.c.ref);
-    std::memcpy(con.c.lo, lo6, sizeof con.c.lo);
-    std::memcpy(con.c.hi, hi6, sizeof con.c.hi);
-    con.ptol = ptol; con.piters = piters; con.damping = damping; con.max_step = max_step;
+    fill_path_launch(ch, ee_offset7, d_q_in, L, P, iters, pathopt::Params{step, w_smooth, w_obs, influence, safety},
+                     d_q_out, d_cost_first, d_cost_last, d_clearance, d_status, a);
+    ConstraintDev d;
+    fill_constraint(ch, ee_offset7, ref7, lo6, hi6, d);
+    PathConLaunch con{};
+    con.c = d.c;
+    con.p = ProjectArgs{ptol, damping, max_step, piters};
     con.violation = d_violation; con.projected = d_projected;
     const int grid = grid_for(ch, P * 64, 64 * WAVES, 8);
 #define CALL(NN, TT) hipLaunchKernelGGL((path_optimize_constrained_kernel<NN, TT>), dim3(grid), dim3(64 * WAVES), 0, (hipStream_t)stream, a, con)

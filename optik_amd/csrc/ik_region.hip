@@ -7,57 +7,42 @@
 // CH is ChainDev (n <= 8) or WideChainDev (9 .. 16): one run-time-n body each, the chain table staged in LDS, as
 // constraint_project_kernel (ik_constraint.hip).  A grid-stride row kernel without atomics; no lane waits for
 // another, so restarts whose projections differ in length cost their wave the longest of them and nothing else.  The
-// region of a row is read from device memory ([T][19]); the keep box travels with the launch (kernel arguments).
+// region of a row is read from device memory ([T][19]); the keep box travels with the launch (kernel arguments) as the
+// box of the record's ConstraintDev head (constraint_device.hpp, whose refusals validate it).
 // Behind the kernel, on the same stream: the key pass of modes 3 and 4 (ik_manip.hip), the collision filter
 // (ik_collision.hip) and the selection of ik_solutions.hip, in the order ik_capi.hip runs them behind its solver.
-#include "collision_device.hpp"
+#include "constraint_device.hpp"
 #include "region_measure.hpp"
 
 using namespace optik;
 using namespace optik::host;
 using namespace optik::hostparams;
+using namespace optik::condev;
 
 namespace {
 
 struct RegionLaunch {
-    const ChainDev *chain;       // n <= 8
-    const WideChainDev *wchain;  // 9 .. 16 joint positions
-    EvalParams ep;               // only the ee_offset part is used
-    region::Keep keep;
+    ConstraintDev d;             // d.c: the keep box (keep_on != 0)
+    int keep_on;
+    double keep_tol;
     uint32_t key[8];
     double scale[WIDE_MAX_DOF];
     const double *regions;       // [T][19]
     const double *x0;            // [T][n]
     unsigned long long cols, R, restart_begin;
-    double tol, damping, max_step;
-    int iters, mode;
+    ProjectArgs p;
+    int mode;
     double *x;                   // [n][cols]
     double *violation, *out_key;  // [cols]
     int32_t *status, *iterations;  // [cols]
 };
 
 template <class CH>
-__device__ __forceinline__ const CH *table_of(const RegionLaunch &a);
-template <>
-__device__ __forceinline__ const ChainDev *table_of<ChainDev>(const RegionLaunch &a) { return a.chain; }
-template <>
-__device__ __forceinline__ const WideChainDev *table_of<WideChainDev>(const RegionLaunch &a) { return a.wchain; }
-
-template <class CH>
-__device__ __forceinline__ void stage_table(CH &dst, const CH *src) {
-    constexpr int ND = (int)(sizeof(CH) / sizeof(double));
-    static_assert(sizeof(CH) % sizeof(double) == 0, "the chain table is a whole number of doubles");
-    const double *s = reinterpret_cast<const double *>(src);
-    double *d = reinterpret_cast<double *>(&dst);
-    for (int i = threadIdx.x; i < ND; i += blockDim.x) d[i] = s[i];
-    __syncthreads();
-}
-
-template <class CH>
 __global__ __launch_bounds__(256) void ik_region_kernel(const RegionLaunch a) {
     __shared__ CH sch;
-    stage_table(sch, table_of<CH>(a));
+    stage_table(sch, table_of<CH>(a.d));
     const int n = sch.n_pos;
+    const region::Keep keep{a.keep_on, a.d.c, a.keep_tol};
     for (unsigned long long b = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; b < a.cols;
          b += (unsigned long long)gridDim.x * blockDim.x) {
         const unsigned long long t = b / a.R;
@@ -66,8 +51,8 @@ __global__ __launch_bounds__(256) void ik_region_kernel(const RegionLaunch a) {
         region::load_box(a.regions + (size_t)t * region::DOUBLES, box);
         double x0[constraint::MAXN], x[constraint::MAXN];
         for (int i = 0; i < n; ++i) x0[i] = a.x0[(size_t)t * n + i];
-        const region::Row r = region::restart(sch, a.ep, box, a.keep, a.key, a.scale, x0, index, n, a.tol, a.iters,
-                                              a.damping, a.max_step, a.mode, x);
+        const region::Row r = region::restart(sch, a.d.ep, box, keep, a.key, a.scale, x0, index, n, a.p.tol, a.p.iters,
+                                              a.p.damping, a.p.max_step, a.mode, x);
         if (a.x)
             for (int i = 0; i < n; ++i) a.x[(size_t)i * a.cols + b] = x[i];
         if (a.violation) a.violation[b] = r.violation;
@@ -75,20 +60,6 @@ __global__ __launch_bounds__(256) void ik_region_kernel(const RegionLaunch a) {
         if (a.iterations) a.iterations[b] = r.iterations;
         if (a.out_key) a.out_key[b] = r.key;
     }
-}
-
-// A box as ik_constraint.hip's check_call validates one (0 or a fail() code).
-int check_box(const double *ref7, const double *lo6, const double *hi6) {
-    double n2 = 0.0;
-    for (int i = 0; i < 7; ++i) {
-        if (!std::isfinite(ref7[i])) return fail(OPTIK_HIP_EINVAL, "pose constraint: the reference pose must be finite");
-        if (i >= 3) n2 += ref7[i] * ref7[i];
-    }
-    if (!(std::fabs(n2 - 1.0) <= 100.0 * 2.220446049250313e-16))
-        return fail(OPTIK_HIP_EINVAL, "pose constraint: the reference quaternion must have unit norm");
-    for (int i = 0; i < 6; ++i)
-        if (!(lo6[i] <= hi6[i])) return fail(OPTIK_HIP_EINVAL, "pose constraint: needs lo <= hi on every axis, no NaN");
-    return 0;
 }
 
 }  // namespace
@@ -106,12 +77,7 @@ int optik_hip_ik_region(optik_hip_chain *ch, const double *ee_offset7, const dou
         return fail(OPTIK_HIP_EINVAL,
                     "solution_mode must be 1 (Quality), 2 (Speed), 3 (Manipulability) or 4 (Condition)");
     // the projection's rules (optik_hip_constraint_project_batch)
-    if (!(tol >= 0.0) || !std::isfinite(tol))
-        return fail(OPTIK_HIP_EINVAL, "pose constraint: tol must be finite and >= 0");
-    if (iters < 0 || iters > OPTIK_HIP_CONSTRAINT_MAX_ITERS)
-        return fail(OPTIK_HIP_EINVAL, "pose constraint: iters must be 0 .. 4096");
-    if (!(damping >= 0.0) || !std::isfinite(damping) || !(max_step > 0.0) || !std::isfinite(max_step))
-        return fail(OPTIK_HIP_EINVAL, "pose constraint: needs damping >= 0 and max_step > 0, both finite");
+    if (int rc = check_project_args(tol, iters, damping, max_step)) return rc;
     // the selection's rules (optik_hip_ik_solutions)
     if (K < 1 || K > OPTIK_HIP_MAX_SOLUTIONS) return fail(OPTIK_HIP_EINVAL, "K must be in 1..256");
     if (!(min_dist >= 0.0) || !std::isfinite(min_dist))
@@ -123,11 +89,8 @@ int optik_hip_ik_region(optik_hip_chain *ch, const double *ee_offset7, const dou
     // the keep box
     const bool keep = keep_ref7 || keep_lo6 || keep_hi6;
     if (keep) {
-        if (!keep_ref7 || !keep_lo6 || !keep_hi6)
-            return fail(OPTIK_HIP_EINVAL, "pose constraint: null reference or bounds");
         if (int rc = check_box(keep_ref7, keep_lo6, keep_hi6)) return rc;
-        if (!(keep_tol >= 0.0) || !std::isfinite(keep_tol))
-            return fail(OPTIK_HIP_EINVAL, "pose constraint: tol must be finite and >= 0");
+        if (int rc = check_tol(keep_tol)) return rc;
     }
     if (restart_end > 1)
         for (int k = 0; k < ch->n; ++k)
@@ -163,17 +126,9 @@ int optik_hip_ik_region(optik_hip_chain *ch, const double *ee_offset7, const dou
 
     RegionLaunch a;
     std::memset(&a, 0, sizeof a);
-    a.chain = ch->dev;
-    a.wchain = ch->wdev;
-    const double one[3] = {1, 1, 1};
-    make_eval_params(one, one, ee_offset7, a.ep);
-    if (keep) {
-        a.keep.on = 1;
-        std::memcpy(a.keep.box.ref, keep_ref7, sizeof a.keep.box.ref);
-        std::memcpy(a.keep.box.lo, keep_lo6, sizeof a.keep.box.lo);
-        std::memcpy(a.keep.box.hi, keep_hi6, sizeof a.keep.box.hi);
-        a.keep.tol = keep_tol;
-    }
+    fill_constraint(ch, ee_offset7, keep ? keep_ref7 : nullptr, keep_lo6, keep_hi6, a.d);
+    a.keep_on = keep ? 1 : 0;
+    a.keep_tol = keep ? keep_tol : 0.0;
     std::memcpy(a.key, ch->key, sizeof a.key);
     std::memcpy(a.scale, ch->scale, sizeof a.scale);
     a.regions = d_regions;
@@ -181,14 +136,12 @@ int optik_hip_ik_region(optik_hip_chain *ch, const double *ee_offset7, const dou
     a.cols = (unsigned long long)cols;
     a.R = R;
     a.restart_begin = restart_begin;
-    a.tol = tol; a.damping = damping; a.max_step = max_step;
-    a.iters = iters; a.mode = mode;
+    a.p = ProjectArgs{tol, damping, max_step, iters};
+    a.mode = mode;
     a.x = px; a.violation = pv; a.out_key = pk;
     a.status = out->d_status; a.iterations = out->d_iterations;
     const int grid = grid_for(ch, (long long)cols, 256, 8);
-    if (ch->wide) hipLaunchKernelGGL(ik_region_kernel<WideChainDev>, dim3(grid), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL(ik_region_kernel<ChainDev>, dim3(grid), dim3(256), 0, stream, a);
-    HIP_TRY(hipGetLastError());
+    CONSTRAINT_LAUNCH(ik_region_kernel, ch, grid, 256, stream, a);
     // the key passes, in ik_capi.hip's order: modes 3 and 4, then the collision filter
     if (manip)
         if (int rc = manip_key_launch(ch, mode, ee_offset7, px, pk, cols, stream)) return rc;

@@ -15,7 +15,7 @@
 //   rrt_begin_kernel    one thread per query: rule 0 -- the roots of tree 1 in ascending g with the root -> goal table,
 //                       the nearest free direct motion --, and the count of the queries that go on.  Only the flags of
 //                       counted slots are read.
-//   rrt_step_kernel     one wave per query, both trees in turn (the nearest node of tree b is the nearest to the
+//   rrt_step_kernel     (rrt_step_body without a constraint) one wave per query, both trees in turn (the nearest node of tree b is the nearest to the
 //                       candidate that the search in tree a gives, so the two searches of a query cannot overlap).
 //                       First it commits the iteration before from the motion check's free flags (append, junction,
 //                       freeze), then it runs rules 1 to 4 of this iteration: lanes stride over the nodes of a tree,
@@ -37,9 +37,11 @@
 //   rrt_mask_kernel     one thread per flag of rule 0: a configuration's collision flag is cleared where its violation
 //                       (optik_hip_constraint_batch on the same 1 + G columns) is not <= tol, a direct motion's where
 //                       optik_hip_constraint_motion_batch's ok byte is 0.  gather and begin stay as they are.
-//   rrt_cstep_kernel<CH>  rrt_step_kernel with the projection inside: CH is ChainDev or WideChainDev, the chain table
-//                       staged in LDS as ik_constraint.hip stages it.  The commit counts a segment only if the motion
-//                       check's flag AND constraint_motion's ok byte are set.  After the steer lane 0 runs
+//   rrt_cstep_kernel<CH>  rrt_step_body with the projection inside -- the one body of both step kernels, the constraint's
+//                       parts under `if constexpr`, so the commit, rule 6 and the segment write exist once.  CH is
+//                       ChainDev or WideChainDev, the chain table staged in LDS (copy_table, ik_launch.hpp; the record's
+//                       head and the dispatch on CH are constraint_device.hpp's).  The commit counts a segment only if
+//                       the motion check's flag AND constraint_motion's ok byte are set.  After the steer lane 0 runs
 //                       constraint::project on the candidate in LDS -- the header's own function, no barrier inside --
 //                       and leaves the verdict (rrt::takes) in LDS; every lane reads it after the barrier, so every
 //                       early exit stays wave-uniform.  The second search runs against the projected candidate, the
@@ -54,15 +56,16 @@
 // atomicSub of a query that ends in rrt_step_kernel.  The loop over the iterations runs on the host (run_iterations);
 // every `poll` iterations it reads one int32, the count of the queries that have not ended.
 #include <algorithm>
+#include <type_traits>
 
-#include "collision_device.hpp"
-#include "constraint_measure.hpp"
+#include "constraint_device.hpp"
 #include "rrt_constrained_measure.hpp"
 
 using namespace optik;
 using namespace optik::host;
 using namespace optik::hostparams;
 using namespace optik::colldev;
+using namespace optik::condev;
 
 static_assert(rrt::MAX_NODES == OPTIK_HIP_RRT_MAX_NODES && rrt::MAX_ITERS == OPTIK_HIP_RRT_MAX_ITERS
                   && rrt::MAX_POLL == OPTIK_HIP_RRT_MAX_POLL
@@ -114,12 +117,9 @@ struct RrtLaunch {
 // What a constrained call adds to the launch (kernel arguments of rrt_cstep_kernel and rrt_mask_kernel only: the
 // record above, and with it the kernels of the unconstrained planner, stay as they are).
 struct RrtConstraint {
-    const ChainDev *chain;       // n <= 8
-    const WideChainDev *wchain;  // 9 .. 16 joint positions
-    EvalParams ep;               // only the ee_offset part is used
-    constraint::Box c;
-    double tol, ptol, damping, max_step;
-    int piters;
+    ConstraintDev d;
+    ProjectArgs p;
+    double tol;                  // the violation rule 0 and a sample of a motion may have
     double *viol;                // [(1 + G) Qc] optik_hip_constraint_batch's violations of cfg
     uint8_t *cok;                // [3][Qc] optik_hip_constraint_motion_batch's ok bytes of the iteration's segments
     uint8_t *cok0;               // [G Qc] and of the direct motions
@@ -131,13 +131,6 @@ struct ConstraintCall {
     const double *ref7, *lo6, *hi6;
     RrtConstraint k;
 };
-
-template <class CH>
-__device__ __forceinline__ const CH *table_of(const RrtConstraint &k);
-template <>
-__device__ __forceinline__ const ChainDev *table_of<ChainDev>(const RrtConstraint &k) { return k.chain; }
-template <>
-__device__ __forceinline__ const WideChainDev *table_of<WideChainDev>(const RrtConstraint &k) { return k.wchain; }
 
 __device__ __forceinline__ double *tree_conf(const RrtLaunch &a, long long q, int t) {
     return a.conf + ((size_t)q * 2 + t) * (size_t)a.n * a.M;
@@ -255,117 +248,6 @@ __device__ __forceinline__ void wave_nearest(const double *conf, int n, int M, i
     index = bi;
 }
 
-__global__ __launch_bounds__(RRT_WAVE) void rrt_step_kernel(const RrtLaunch a) {
-    __shared__ double s_x[OPTIK_HIP_MAX_DOF], s_c[OPTIK_HIP_MAX_DOF];
-    const long long q = blockIdx.x;
-    const int lane = threadIdx.x, n = a.n, M = a.M;
-    if (a.state[q] != rrt::RUNNING) return;  // (frozen: its segments are NaN already)
-    const long long B = 3 * a.Qc;
-    int cnt0 = a.count[q], cnt1 = a.count[a.Qc + q];
-    const bool joint = lane < n;
-    // ---- the iteration before: what the motion check said (rules 3 and 4) ----
-    if (a.iter > 0) {
-        const int pa = (a.iter - 1) & 1, pb = 1 - pa;
-        const int p = a.pend[q], m = a.pend[a.Qc + q], back = a.pend[2 * a.Qc + q];
-        const bool ok0 = a.flags[q] != 0, ok1 = a.flags[a.Qc + q] != 0, ok2 = a.flags[2 * a.Qc + q] != 0;
-        int cnt_a = pa == 0 ? cnt0 : cnt1, cnt_b = pa == 0 ? cnt1 : cnt0;
-        if (p >= 0 && p < cnt_a && m >= 0 && m < cnt_b && cnt_a < M && ok0) {
-            // (segment 0 is p -> c for tree 0 and c -> p for tree 1)
-            if (joint) {
-                const double c = (pa == 0 ? a.qb : a.qa)[(long long)lane * B + q];
-                tree_conf(a, q, pa)[(size_t)lane * M + cnt_a] = c;
-            }
-            if (lane == 0) tree_parent(a, q, pa)[cnt_a] = p;
-            cnt_a += 1;
-            if (ok1) {
-                if (lane == 0) {
-                    a.junction[pa * a.Qc + q] = cnt_a - 1;
-                    a.junction[pb * a.Qc + q] = m;
-                    a.count[pa * a.Qc + q] = cnt_a;
-                    a.state[q] = rrt::FOUND;
-                    a.used[q] = a.iter;
-                    atomicSub(a.unfinished, 1);
-                }
-                if (joint) clear_segments(a, q, lane);
-                return;
-            }
-            if (back && ok2 && cnt_b < M) {
-                // (segment 2 is m -> e for tree 0 and e -> m for tree 1)
-                if (joint) {
-                    const double e = (pb == 0 ? a.qb : a.qa)[(long long)lane * B + 2 * a.Qc + q];
-                    tree_conf(a, q, pb)[(size_t)lane * M + cnt_b] = e;
-                }
-                if (lane == 0) tree_parent(a, q, pb)[cnt_b] = m;
-                cnt_b += 1;
-            }
-            cnt0 = pa == 0 ? cnt_a : cnt_b;
-            cnt1 = pa == 0 ? cnt_b : cnt_a;
-            if (lane == 0) {
-                a.count[q] = cnt0;
-                a.count[a.Qc + q] = cnt1;
-            }
-        }
-    }
-    if (a.iter >= a.I) {
-        // rule 6
-        if (lane == 0) {
-            a.state[q] = rrt::NO_ROUTE;
-            a.used[q] = a.I;
-            atomicSub(a.unfinished, 1);
-        }
-        if (joint) clear_segments(a, q, lane);
-        return;
-    }
-    // ---- this iteration: rules 1 to 4 ----
-    const int ta = a.iter & 1, tb = 1 - ta;
-    const int cnt_a = ta == 0 ? cnt0 : cnt1, cnt_b = ta == 0 ? cnt1 : cnt0;
-    const double *conf_a = tree_conf(a, q, ta), *conf_b = tree_conf(a, q, tb);
-    if (joint) s_x[lane] = a.samples[(long long)lane * a.I + a.iter];
-    __syncthreads();  // (also: the nodes appended above are visible to every lane)
-    double d, dm;
-    int p, m;
-    wave_nearest(conf_a, n, M, cnt_a, s_x, lane, d, p);
-    if (!rrt::steers(d) || cnt_a >= M || p < 0) {
-        if (lane == 0) a.pend[q] = -1;
-        if (joint) clear_segments(a, q, lane);
-        return;
-    }
-    double pj = 0.0, cj = 0.0, lo = 0.0, hi = 0.0;
-    if (joint) {
-        pj = conf_a[(size_t)lane * M + p];
-        lo = a.lo[lane];
-        hi = a.hi[lane];
-        cj = rrt::steer_joint(pj, s_x[lane], d, a.eta, lo, hi);
-        s_c[lane] = cj;
-    }
-    __syncthreads();
-    wave_nearest(conf_b, n, M, cnt_b, s_c, lane, dm, m);
-    if (m < 0) {  // (a tree has its root: cannot happen)
-        if (lane == 0) a.pend[q] = -1;
-        if (joint) clear_segments(a, q, lane);
-        return;
-    }
-    const bool back = rrt::extends_back(dm, a.eta, cnt_b, M);
-    if (joint) {
-        const double mj = conf_b[(size_t)lane * M + m];
-        const double ej = back ? rrt::steer_joint(mj, cj, dm, a.eta, lo, hi) : roadmap::nan_value();
-        const double mb = back ? mj : roadmap::nan_value();
-        double *qa = a.qa + (long long)lane * B + q, *qb = a.qb + (long long)lane * B + q;
-        // travel direction: tree 0 is walked parent -> child, tree 1 child -> parent, a connection tree 0 -> tree 1
-        qa[0] = ta == 0 ? pj : cj;
-        qb[0] = ta == 0 ? cj : pj;
-        qa[a.Qc] = ta == 0 ? cj : mj;
-        qb[a.Qc] = ta == 0 ? mj : cj;
-        qa[2 * a.Qc] = tb == 0 ? mb : ej;
-        qb[2 * a.Qc] = tb == 0 ? ej : mb;
-    }
-    if (lane == 0) {
-        a.pend[q] = p;
-        a.pend[a.Qc + q] = m;
-        a.pend[2 * a.Qc + q] = back ? 1 : 0;
-    }
-}
-
 // Rule 0 under a constraint: "free" is free AND within the constraint.  (a NaN segment has both flags at 0 already)
 __global__ __launch_bounds__(RRT_BLOCK) void rrt_mask_kernel(const RrtLaunch a, const RrtConstraint k) {
     const long long j = (long long)blockIdx.x * RRT_BLOCK + threadIdx.x;
@@ -382,8 +264,7 @@ __global__ __launch_bounds__(RRT_BLOCK) void rrt_mask_kernel(const RrtLaunch a, 
 template <class CH>
 __device__ __forceinline__ void project_candidate(const CH &sch, const RrtConstraint &k, int n, int M,
                                                   const double *conf, int from, double *s_v, int *s_take) {
-    const constraint::Projected pr =
-        constraint::project(sch, k.ep, k.c, n, k.ptol, k.piters, k.damping, k.max_step, s_v);
+    const constraint::Projected pr = project(sch, k.d, k.p, n, s_v);
     bool same = true;
     for (int i = 0; i < n; ++i) same = same && s_v[i] == conf[(size_t)i * M + from];
     s_take[0] = rrt::takes(pr.status, pr.iterations, same) ? 1 : 0;
@@ -392,15 +273,22 @@ __device__ __forceinline__ void project_candidate(const CH &sch, const RrtConstr
 
 __device__ __forceinline__ void count_projections(const RrtLaunch &a, const RrtConstraint &k, long long q,
                                                   int attempted, int ended) {
-    if (!k.projected) return;
+    if (!k.projected || attempted == 0) return;
     k.projected[a.q0 + q] += attempted;
     k.projected[a.Q + a.q0 + q] += ended;
 }
 
+// CH of a step without a constraint: no table, no projection, k is not read.
+struct NoChain {};
+
+// The step of both planners: rrt_step_kernel (CH = NoChain) and rrt_cstep_kernel<CH>.
 template <class CH>
-__global__ __launch_bounds__(RRT_WAVE) void rrt_cstep_kernel(const RrtLaunch a, const RrtConstraint k) {
+__device__ __forceinline__ void rrt_step_body(const RrtLaunch &a, const RrtConstraint *k) {
+    constexpr bool CON = !std::is_same<CH, NoChain>::value;
+    __shared__ double s_x[OPTIK_HIP_MAX_DOF], s_c[OPTIK_HIP_MAX_DOF];
+    // (the projections' own: never used without a constraint, and so not allocated)
     __shared__ CH sch;
-    __shared__ double s_x[OPTIK_HIP_MAX_DOF], s_c[OPTIK_HIP_MAX_DOF], s_e[OPTIK_HIP_MAX_DOF];
+    __shared__ double s_e[OPTIK_HIP_MAX_DOF];
     __shared__ int s_take[4];
     const long long q = blockIdx.x;
     const int lane = threadIdx.x, n = a.n, M = a.M;
@@ -408,12 +296,16 @@ __global__ __launch_bounds__(RRT_WAVE) void rrt_cstep_kernel(const RrtLaunch a, 
     const long long B = 3 * a.Qc;
     int cnt0 = a.count[q], cnt1 = a.count[a.Qc + q];
     const bool joint = lane < n;
-    // ---- the iteration before: what the two checks said (rules 3 and 4) ----
+    // ---- the iteration before: what the motion check (and the constraint's) said (rules 3 and 4) ----
     if (a.iter > 0) {
         const int pa = (a.iter - 1) & 1, pb = 1 - pa;
         const int p = a.pend[q], m = a.pend[a.Qc + q], back = a.pend[2 * a.Qc + q];
-        const bool ok0 = a.flags[q] != 0 && k.cok[q] != 0, ok1 = a.flags[a.Qc + q] != 0 && k.cok[a.Qc + q] != 0,
-                   ok2 = a.flags[2 * a.Qc + q] != 0 && k.cok[2 * a.Qc + q] != 0;
+        bool ok0 = a.flags[q] != 0, ok1 = a.flags[a.Qc + q] != 0, ok2 = a.flags[2 * a.Qc + q] != 0;
+        if constexpr (CON) {
+            ok0 = ok0 && k->cok[q] != 0;
+            ok1 = ok1 && k->cok[a.Qc + q] != 0;
+            ok2 = ok2 && k->cok[2 * a.Qc + q] != 0;
+        }
         int cnt_a = pa == 0 ? cnt0 : cnt1, cnt_b = pa == 0 ? cnt1 : cnt0;
         if (p >= 0 && p < cnt_a && m >= 0 && m < cnt_b && cnt_a < M && ok0) {
             // (segment 0 is p -> c for tree 0 and c -> p for tree 1)
@@ -466,70 +358,60 @@ __global__ __launch_bounds__(RRT_WAVE) void rrt_cstep_kernel(const RrtLaunch a, 
     const int ta = a.iter & 1, tb = 1 - ta;
     const int cnt_a = ta == 0 ? cnt0 : cnt1, cnt_b = ta == 0 ? cnt1 : cnt0;
     const double *conf_a = tree_conf(a, q, ta), *conf_b = tree_conf(a, q, tb);
-    {
-        // the chain table (ik_constraint.hip's stage_table)
-        constexpr int ND = (int)(sizeof(CH) / sizeof(double));
-        static_assert(sizeof(CH) % sizeof(double) == 0, "the chain table is a whole number of doubles");
-        const double *src = reinterpret_cast<const double *>(table_of<CH>(k));
-        double *dst = reinterpret_cast<double *>(&sch);
-        for (int i = lane; i < ND; i += RRT_WAVE) dst[i] = src[i];
-    }
+    if constexpr (CON) copy_table(sch, table_of<CH>(k->d));
     if (joint) s_x[lane] = a.samples[(long long)lane * a.I + a.iter];
     __syncthreads();  // (also: the nodes appended above are visible to every lane)
+    int attempted = 0, ended = 0;  // the projections of this step
+    // the exit of a step that leaves no segments behind
+    auto give_up = [&]() {
+        if (lane == 0) {
+            a.pend[q] = -1;
+            if constexpr (CON) count_projections(a, *k, q, attempted, ended);
+        }
+        if (joint) clear_segments(a, q, lane);
+    };
     double d, dm;
     int p, m;
     wave_nearest(conf_a, n, M, cnt_a, s_x, lane, d, p);
-    if (!rrt::steers(d) || cnt_a >= M || p < 0) {
-        if (lane == 0) a.pend[q] = -1;
-        if (joint) clear_segments(a, q, lane);
-        return;
-    }
+    if (!rrt::steers(d) || cnt_a >= M || p < 0) return give_up();
     double pj = 0.0, cj = 0.0, lo = 0.0, hi = 0.0;
     if (joint) {
         pj = conf_a[(size_t)lane * M + p];
         lo = a.lo[lane];
         hi = a.hi[lane];
-        s_c[lane] = rrt::steer_joint(pj, s_x[lane], d, a.eta, lo, hi);
+        cj = rrt::steer_joint(pj, s_x[lane], d, a.eta, lo, hi);
+        s_c[lane] = cj;
     }
     __syncthreads();
-    if (lane == 0) project_candidate(sch, k, n, M, conf_a, p, s_c, s_take);
-    __syncthreads();
-    // (every lane reads the verdict from LDS before it branches on it)
-    if (s_take[0] == 0) {
-        if (lane == 0) {
-            a.pend[q] = -1;
-            count_projections(a, k, q, 1, s_take[1]);
-        }
-        if (joint) clear_segments(a, q, lane);
-        return;
+    if constexpr (CON) {
+        if (lane == 0) project_candidate(sch, *k, n, M, conf_a, p, s_c, s_take);
+        __syncthreads();
+        // (every lane reads the verdict from LDS before it branches on it)
+        attempted = 1;
+        ended = s_take[1];
+        if (s_take[0] == 0) return give_up();
+        if (joint) cj = s_c[lane];
     }
-    if (joint) cj = s_c[lane];
     wave_nearest(conf_b, n, M, cnt_b, s_c, lane, dm, m);
-    if (m < 0) {  // (a tree has its root: cannot happen)
-        if (lane == 0) {
-            a.pend[q] = -1;
-            count_projections(a, k, q, 1, s_take[1]);
-        }
-        if (joint) clear_segments(a, q, lane);
-        return;
-    }
+    if (m < 0) return give_up();  // (a tree has its root: cannot happen)
     bool back = rrt::extends_back(dm, a.eta, cnt_b, M);  // (wave-uniform: dm and cnt_b are)
-    int attempted = 1, ended = s_take[1];
-    double mj = 0.0, ej = roadmap::nan_value();
-    if (joint) mj = conf_b[(size_t)lane * M + m];
-    if (back) {
-        if (joint) s_e[lane] = rrt::steer_joint(mj, cj, dm, a.eta, lo, hi);
-        __syncthreads();
-        if (lane == 0) project_candidate(sch, k, n, M, conf_b, m, s_e, s_take + 2);
-        __syncthreads();
-        back = s_take[2] != 0;
-        attempted += 1;
-        ended += s_take[3];
-        if (back && joint) ej = s_e[lane];
+    if constexpr (CON) {
+        if (back) {
+            if (joint) s_e[lane] = rrt::steer_joint(conf_b[(size_t)lane * M + m], cj, dm, a.eta, lo, hi);
+            __syncthreads();
+            if (lane == 0) project_candidate(sch, *k, n, M, conf_b, m, s_e, s_take + 2);
+            __syncthreads();
+            back = s_take[2] != 0;
+            attempted += 1;
+            ended += s_take[3];
+        }
     }
     if (joint) {
+        const double mj = conf_b[(size_t)lane * M + m];
+        double ej;
+        if constexpr (CON) ej = back ? s_e[lane] : roadmap::nan_value();
+        else ej = back ? rrt::steer_joint(mj, cj, dm, a.eta, lo, hi) : roadmap::nan_value();
         const double mb = back ? mj : roadmap::nan_value();
-        if (!back) ej = roadmap::nan_value();
         double *qa = a.qa + (long long)lane * B + q, *qb = a.qb + (long long)lane * B + q;
         // travel direction: tree 0 is walked parent -> child, tree 1 child -> parent, a connection tree 0 -> tree 1
         qa[0] = ta == 0 ? pj : cj;
@@ -543,8 +425,15 @@ __global__ __launch_bounds__(RRT_WAVE) void rrt_cstep_kernel(const RrtLaunch a, 
         a.pend[q] = p;
         a.pend[a.Qc + q] = m;
         a.pend[2 * a.Qc + q] = back ? 1 : 0;
-        count_projections(a, k, q, attempted, ended);
+        if constexpr (CON) count_projections(a, *k, q, attempted, ended);
     }
+}
+
+__global__ __launch_bounds__(RRT_WAVE) void rrt_step_kernel(const RrtLaunch a) { rrt_step_body<NoChain>(a, nullptr); }
+
+template <class CH>
+__global__ __launch_bounds__(RRT_WAVE) void rrt_cstep_kernel(const RrtLaunch a, const RrtConstraint k) {
+    rrt_step_body<CH>(a, &k);
 }
 
 __global__ __launch_bounds__(RRT_WAVE) void rrt_walk_kernel(const RrtLaunch a) {
@@ -664,18 +553,20 @@ int run_iterations(optik_hip_chain *ch, const double *ee_offset7, RrtLaunch &a, 
                    int32_t poll, double resolution, hipStream_t stream) {
     const long long L = a.Qc;
     bool ended = false;
-    auto step = [&]() {
-        if (!cc) hipLaunchKernelGGL(rrt_step_kernel, dim3((unsigned)L), dim3(RRT_WAVE), 0, stream, a);
-        else if (ch->wide)
-            hipLaunchKernelGGL(rrt_cstep_kernel<WideChainDev>, dim3((unsigned)L), dim3(RRT_WAVE), 0, stream, a, cc->k);
-        else hipLaunchKernelGGL(rrt_cstep_kernel<ChainDev>, dim3((unsigned)L), dim3(RRT_WAVE), 0, stream, a, cc->k);
+    auto step = [&]() -> int {
+        if (cc) {
+            CONSTRAINT_LAUNCH(rrt_cstep_kernel, ch, (unsigned)L, RRT_WAVE, stream, a, cc->k);
+        } else {
+            hipLaunchKernelGGL(rrt_step_kernel, dim3((unsigned)L), dim3(RRT_WAVE), 0, stream, a);
+            HIP_TRY(hipGetLastError());
+        }
+        return 0;
     };
     for (int32_t i = 0; i < iters; ++i) {
         a.iter = i;
         {
             BIND_DEVICE(ch);
-            step();
-            HIP_TRY(hipGetLastError());
+            if (int rc = step()) return rc;
             if (i % poll == 0) {
                 // (the one synchronise of a poll: the host decides whether the iterations go on)
                 int32_t left = 0;
@@ -696,9 +587,8 @@ int run_iterations(optik_hip_chain *ch, const double *ee_offset7, RrtLaunch &a, 
     BIND_DEVICE(ch);
     if (!ended) {
         a.iter = iters;  // (the last iteration's commit, and rule 6)
-        step();
+        if (int rc = step()) return rc;
     }
-    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -888,14 +778,9 @@ int optik_hip_rrt_plan_constrained(optik_hip_chain *ch, const double *ee_offset7
     ConstraintCall cc;
     std::memset(&cc, 0, sizeof cc);
     cc.ref7 = ref7; cc.lo6 = lo6; cc.hi6 = hi6;
-    cc.k.chain = ch->dev;
-    cc.k.wchain = ch->wdev;
-    const double one[3] = {1, 1, 1};
-    make_eval_params(one, one, ee_offset7, cc.k.ep);
-    std::memcpy(cc.k.c.ref, ref7, sizeof cc.k.c.ref);
-    std::memcpy(cc.k.c.lo, lo6, sizeof cc.k.c.lo);
-    std::memcpy(cc.k.c.hi, hi6, sizeof cc.k.c.hi);
-    cc.k.tol = tol; cc.k.ptol = ptol; cc.k.piters = piters; cc.k.damping = damping; cc.k.max_step = max_step;
+    fill_constraint(ch, ee_offset7, ref7, lo6, hi6, cc.k.d);
+    cc.k.p = ProjectArgs{ptol, damping, max_step, piters};
+    cc.k.tol = tol;
     cc.k.projected = d_projected;
     return plan(ch, ee_offset7, &cc, d_start, d_goals, d_gcount, Q, G, iters, step, resolution, first, max_nodes, Lmax,
                 poll, d_path, d_len, d_cost, d_status, d_iters, d_nodes, d_which, (hipStream_t)stream_);

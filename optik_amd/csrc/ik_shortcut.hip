@@ -15,33 +15,34 @@
 //   shortcut_resample_kernel   one thread per (path, output waypoint); no LDS, no workspace.
 //
 // Under a pose constraint (shortcut_constrained_measure.hpp; optik_hip_path_shortcut_constrained /
-// _path_resample_constrained) the same chunk loop runs four kernels per chunk:
-//   shortcut_cgather_kernel<CH>       one block of 256 per path, the chain table staged in LDS as ik_constraint.hip
-//                                     stages it.  The first wave builds the vertices as above, then lane u projects
+// _path_resample_constrained) the same chunk loop (shortcut_chunks) runs four kernels per chunk:
+//   shortcut_cgather_kernel<CH>       one block of 256 per path, the chain table staged in LDS (stage_table,
+//                                     ik_launch.hpp).  The first wave builds the vertices as above, then lane u projects
 //                                     vertex u unless it is one of the input's waypoints (constraint::project, the
 //                                     header's own function; lanes whose loops differ in length cost the wave the
 //                                     longest of them and nothing else); a vertex that did not project becomes NaN.
 //                                     The block stores the final vertices [n][Pc * V] behind the segments in the
 //                                     workspace, counts the projections and writes the pair segments as above.
 //   (the motion check, classify form, as above)
-//   constraint_motion_mask_kernel<CH> one pair per lane, grid-stride, no atomics: a pair whose flag is 0 already is not
-//                                     sampled, every other flag becomes constraint::motion's ok.
+//   (constraint_mask_launch, ik_host.hpp: ik_constraint.hip's check along a motion in its mask form -- a pair whose
+//   flag is 0 already is not sampled, every other flag becomes constraint::motion's ok)
 //   shortcut_route_stored_kernel      shortcut_route_kernel's body (route_path) with the vertices read from the
 //                                     stored block: nothing is projected twice.
 //   shortcut_cresample_kernel<CH>     one wave per path, lane j = output waypoint j: resample, project, then the
 //                                     wave's ballots give the status and the two counts.
-// CH is ChainDev (n <= 8) or WideChainDev (9 .. 16).
+// CH is ChainDev (n <= 8) or WideChainDev (9 .. 16); the head of the constraint's record, its refusals and the dispatch
+// on CH are constraint_device.hpp's.
 //
 // The paths of a call are processed in chunks of at most OPTIK_HIP_PATH_SHORTCUT_CHUNK_BYTES of workspace, launched
 // one after the other on the stream; a path's blocks see only that path, so nothing depends on P or on the chunking.
-#include "collision_device.hpp"
-#include "constraint_measure.hpp"
+#include "constraint_device.hpp"
 #include "shortcut_constrained_measure.hpp"
 
 using namespace optik;
 using namespace optik::host;
 using namespace optik::hostparams;
 using namespace optik::colldev;
+using namespace optik::condev;
 
 static_assert(shortcut::MAX_POINTS == OPTIK_HIP_PATH_OPTIMIZE_MAX_WAYPOINTS && shortcut::MAX_POINTS == 64,
               "a shortcut path is a path path_optimize takes; one lane of a wave per vertex");
@@ -220,34 +221,11 @@ __global__ __launch_bounds__(RESAMPLE_BLOCK) void shortcut_resample_kernel(const
 
 // The constraint's side of a launch: it travels with the call, the chain handle keeps nothing of it.
 struct ConLaunch {
-    const ChainDev *chain;       // n <= 8
-    const WideChainDev *wchain;  // 9 .. 16 joint positions
-    EvalParams ep;               // only the ee_offset part is used
-    constraint::Box c;
-    double h, tol;               // the check along a motion
-    double ptol, damping, max_step;  // the projection
-    int piters;
+    ConstraintDev d;
+    ProjectArgs p;
     double *verts;               // [n][Pc * V] the chunk's final vertices (shortcut)
     int32_t *projected;          // [2][P] or null
 };
-
-template <class CH>
-__device__ __forceinline__ const CH *table_of(const ConLaunch &k);
-template <>
-__device__ __forceinline__ const ChainDev *table_of<ChainDev>(const ConLaunch &k) { return k.chain; }
-template <>
-__device__ __forceinline__ const WideChainDev *table_of<WideChainDev>(const ConLaunch &k) { return k.wchain; }
-
-// (ik_constraint.hip's stage_table)
-template <class CH>
-__device__ __forceinline__ void stage_table(CH &dst, const CH *src) {
-    constexpr int ND = (int)(sizeof(CH) / sizeof(double));
-    static_assert(sizeof(CH) % sizeof(double) == 0, "the chain table is a whole number of doubles");
-    const double *s = reinterpret_cast<const double *>(src);
-    double *d = reinterpret_cast<double *>(&dst);
-    for (int i = threadIdx.x; i < ND; i += blockDim.x) d[i] = s[i];
-    __syncthreads();
-}
 
 template <class CH>
 __global__ __launch_bounds__(GATHER_BLOCK) void shortcut_cgather_kernel(const ShortcutLaunch a, const ConLaunch k) {
@@ -255,7 +233,7 @@ __global__ __launch_bounds__(GATHER_BLOCK) void shortcut_cgather_kernel(const Sh
     __shared__ CH sch;
     const long long pc = blockIdx.x, p = a.p0 + pc;
     const int tid = threadIdx.x, n = a.n;
-    stage_table(sch, table_of<CH>(k));
+    stage_table(sch, table_of<CH>(k.d));
     build_vertices<false>(a, p, s);
     const int nv = s.prep.nv;
     // rule 2': lane u projects vertex u, in its own column of the LDS block
@@ -263,8 +241,7 @@ __global__ __launch_bounds__(GATHER_BLOCK) void shortcut_cgather_kernel(const Sh
     if (tid < nv && !shortcut::is_waypoint(s.off, shortcut::vertex_segment(s.prep.le, s.off, tid), tid)) {
         double x[constraint::MAXN];
         for (int i = 0; i < n; ++i) x[i] = s.v[i * MP + tid];
-        const constraint::Projected pr =
-            constraint::project(sch, k.ep, k.c, n, k.ptol, k.piters, k.damping, k.max_step, x);
+        const constraint::Projected pr = project(sch, k.d, k.p, n, x);
         tried = true;
         ended = pr.status == constraint::PROJECTED;
         for (int i = 0; i < n; ++i) s.v[i * MP + tid] = shortcut::vertex_after(pr.status, x[i]);
@@ -284,22 +261,9 @@ __global__ __launch_bounds__(GATHER_BLOCK) void shortcut_cgather_kernel(const Sh
 }
 
 template <class CH>
-__global__ __launch_bounds__(256) void constraint_motion_mask_kernel(const ConLaunch k, const double *qa,
-                                                                     const double *qb, long long B, uint8_t *flag) {
-    __shared__ CH sch;
-    stage_table(sch, table_of<CH>(k));
-    const int n = sch.n_pos;
-    for (long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x; b < B;
-         b += (long long)gridDim.x * blockDim.x) {
-        if (flag[b] == 0) continue;  // (rule 3': the verdict is the AND; the skip only saves the samples)
-        flag[b] = (uint8_t)constraint::motion(sch, k.ep, k.c, n, qa + b, B, qb + b, B, k.h, k.tol).ok;
-    }
-}
-
-template <class CH>
 __global__ __launch_bounds__(SC_WAVE) void shortcut_cresample_kernel(const ResampleLaunch a, const ConLaunch k) {
     __shared__ CH sch;
-    stage_table(sch, table_of<CH>(k));
+    stage_table(sch, table_of<CH>(k.d));
     const long long p = blockIdx.x;
     const int j = threadIdx.x, n = a.n;
     bool tried = false, ended = false;
@@ -310,8 +274,7 @@ __global__ __launch_bounds__(SC_WAVE) void shortcut_cresample_kernel(const Resam
         st = shortcut::resample_waypoint(n, a.path + p * n, a.P * n, len, a.Lin, a.Lout, j, x, 1);
         if (shortcut::projects(st, a.Lout, j)) {
             for (int i = 0; i < n; ++i) y[i] = x[i];
-            const constraint::Projected pr =
-                constraint::project(sch, k.ep, k.c, n, k.ptol, k.piters, k.damping, k.max_step, y);
+            const constraint::Projected pr = project(sch, k.d, k.p, n, y);
             tried = true;
             ended = pr.status == constraint::PROJECTED;
             if (ended)
@@ -331,18 +294,6 @@ __global__ __launch_bounds__(SC_WAVE) void shortcut_cresample_kernel(const Resam
     }
 }
 
-void fill_con(const optik_hip_chain *ch, const double *ee_offset7, const double *ref7, const double *lo6,
-              const double *hi6, ConLaunch &k) {
-    std::memset(&k, 0, sizeof k);
-    k.chain = ch->dev;
-    k.wchain = ch->wdev;
-    const double one[3] = {1, 1, 1};
-    make_eval_params(one, one, ee_offset7, k.ep);
-    std::memcpy(k.c.ref, ref7, sizeof k.c.ref);
-    std::memcpy(k.c.lo, lo6, sizeof k.c.lo);
-    std::memcpy(k.c.hi, hi6, sizeof k.c.hi);
-}
-
 // The refusals of the constraint entries, in ik_constraint.hip's order (B = 0 there): the constraint, tol and the
 // chain with with_tol; then ptol, piters, damping and max_step.
 int check_con(const optik_hip_chain *ch, const double *ref7, const double *lo6, const double *hi6, bool with_tol,
@@ -357,24 +308,86 @@ int check_con(const optik_hip_chain *ch, const double *ref7, const double *lo6, 
 
 bool points_ok(int v) { return v >= shortcut::MIN_POINTS && v <= shortcut::MAX_POINTS; }
 
-// per path under a constraint: what bytes_per_path counts and the stored vertices
-size_t bytes_per_path_constrained(int n, int V) {
-    return (size_t)shortcut::pair_count(V) * (sizeof(double) * 2 * (size_t)n + 1 + 24) + sizeof(double) * (size_t)n * V;
+// per path: the gathered segments, their free flags, and the motion check's own words; under a constraint the stored
+// vertices too
+size_t bytes_per_path(int n, int V, bool constrained) {
+    return (size_t)shortcut::pair_count(V) * (sizeof(double) * 2 * (size_t)n + 1 + 24)
+           + (constrained ? sizeof(double) * (size_t)n * V : 0);
 }
 
-long long chunk_paths_constrained(int n, int V) {
-    const long long c = (long long)((size_t)OPTIK_HIP_PATH_SHORTCUT_CHUNK_BYTES / bytes_per_path_constrained(n, V));
+long long chunk_paths(int n, int V, bool constrained) {
+    const long long c = (long long)((size_t)OPTIK_HIP_PATH_SHORTCUT_CHUNK_BYTES / bytes_per_path(n, V, constrained));
     return c < 1 ? 1 : c;
 }
 
-// per path: the gathered segments, their free flags, and the motion check's own words
-size_t bytes_per_path(int n, int V) {
-    return (size_t)shortcut::pair_count(V) * (sizeof(double) * 2 * (size_t)n + 1 + 24);
+// The host's side of a constrained call: the pointers the constraint entries take, and the device's record.
+struct ConCall {
+    const double *ref7, *lo6, *hi6;
+    double tol;
+    ConLaunch k;
+};
+
+// The chunk loop of both shortcut entries, their arguments checked and `a` filled but for the chunk and the workspace.
+// cc null: no constraint.
+int shortcut_chunks(optik_hip_chain *ch, const double *ee_offset7, ShortcutLaunch &a, double resolution, ConCall *cc,
+                    hipStream_t stream) {
+    const size_t n = (size_t)ch->n;
+    const long long P = a.P, pairs = shortcut::pair_count(a.V), V = cc ? a.V : 0;  // (V: the stored vertices per path)
+    const long long cap = chunk_paths(ch->n, a.V, cc != nullptr), chunk = P < cap ? P : cap;
+    {
+        std::lock_guard<std::mutex> lock(ch->mu);
+        BIND_DEVICE(ch);
+        // (every chunk is at most the first one's size: neither this block nor the motion check's grows in between;
+        // the doubles first: the segments twice, then the vertices)
+        HIP_TRY(ch->shortcut_ws.reserve((sizeof(double) * 2 * n + 1) * (size_t)(chunk * pairs)
+                                        + sizeof(double) * n * (size_t)(chunk * V)));
+        a.qa = reinterpret_cast<double *>(ch->shortcut_ws.get());
+    }
+    for (long long p0 = 0; p0 < P; p0 += chunk) {
+        const long long Pc = P - p0 < chunk ? P - p0 : chunk, B = Pc * pairs;
+        a.p0 = p0; a.Pc = Pc;
+        a.qb = a.qa + n * (size_t)B;
+        double *verts = a.qb + n * (size_t)B;
+        uint8_t *d_free = reinterpret_cast<uint8_t *>(verts + n * (size_t)(Pc * V));
+        a.free_flag = d_free;
+        {
+            BIND_DEVICE(ch);
+            if (cc) {
+                cc->k.verts = verts;
+                CONSTRAINT_LAUNCH(shortcut_cgather_kernel, ch, (unsigned)Pc, GATHER_BLOCK, stream, a, cc->k);
+            } else {
+                hipLaunchKernelGGL(shortcut_gather_kernel, dim3((unsigned)Pc), dim3(GATHER_BLOCK), 0, stream, a);
+                HIP_TRY(hipGetLastError());
+            }
+        }
+        if (int rc = optik_hip_collision_motion_batch(ch, ee_offset7, a.qa, a.qb, B, resolution, nullptr, d_free,
+                                                      nullptr, nullptr, stream))
+            return rc;
+        if (cc)
+            if (int rc = constraint_mask_launch(ch, ee_offset7, cc->ref7, cc->lo6, cc->hi6, a.qa, a.qb, B, resolution,
+                                                cc->tol, d_free, stream))
+                return rc;
+        BIND_DEVICE(ch);
+        if (cc)
+            hipLaunchKernelGGL(shortcut_route_stored_kernel, dim3((unsigned)Pc), dim3(SC_WAVE), 0, stream, a,
+                               (const double *)verts);
+        else hipLaunchKernelGGL(shortcut_route_kernel, dim3((unsigned)Pc), dim3(SC_WAVE), 0, stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
 }
 
-long long chunk_paths(int n, int V) {
-    const long long c = (long long)((size_t)OPTIK_HIP_PATH_SHORTCUT_CHUNK_BYTES / bytes_per_path(n, V));
-    return c < 1 ? 1 : c;
+// What both shortcut entries put into the record before the chunk loop.
+ShortcutLaunch make_launch(const optik_hip_chain *ch, const double *d_path, const int32_t *d_len, int32_t Lin, int64_t P,
+                           int32_t V, double hop_penalty, int32_t Lout, double *d_out, int32_t *d_len_out,
+                           double *d_cost, double *d_cost_in, int32_t *d_status) {
+    ShortcutLaunch a;
+    std::memset(&a, 0, sizeof a);
+    a.path = d_path; a.len = d_len; a.P = P;
+    a.n = ch->n; a.Lin = Lin; a.V = V; a.Lout = Lout;
+    a.hop = hop_penalty;
+    a.out = d_out; a.len_out = d_len_out; a.cost = d_cost; a.cost_in = d_cost_in; a.status = d_status;
+    return a;
 }
 
 }  // namespace
@@ -383,7 +396,7 @@ extern "C" {
 
 int64_t optik_hip_path_shortcut_chunk(const optik_hip_chain *ch, int32_t V) {
     if (!ch || !points_ok(V)) return fail(OPTIK_HIP_EINVAL, "bad argument");
-    return chunk_paths(ch->n, V);
+    return chunk_paths(ch->n, V, false);
 }
 
 int optik_hip_path_shortcut(optik_hip_chain *ch, const double *ee_offset7, const double *d_path, const int32_t *d_len,
@@ -402,41 +415,9 @@ int optik_hip_path_shortcut(optik_hip_chain *ch, const double *ee_offset7, const
         return rc;
     if (P == 0 || (!d_out && !d_len_out && !d_cost && !d_cost_in && !d_status)) return 0;
     if (!d_path) return fail(OPTIK_HIP_EINVAL, "bad argument");
-    const size_t n = (size_t)ch->n;
-    const long long pairs = shortcut::pair_count(V);
-    const long long chunk = P < chunk_paths(ch->n, V) ? P : chunk_paths(ch->n, V);
-    ShortcutLaunch a;
-    std::memset(&a, 0, sizeof a);
-    {
-        std::lock_guard<std::mutex> lock(ch->mu);
-        BIND_DEVICE(ch);
-        // (every chunk is at most the first one's size: neither this block nor the motion check's grows in between)
-        HIP_TRY(ch->shortcut_ws.reserve((sizeof(double) * 2 * n + 1) * (size_t)(chunk * pairs)));
-        a.qa = reinterpret_cast<double *>(ch->shortcut_ws.get());
-    }
-    a.path = d_path; a.len = d_len; a.P = P;
-    a.n = ch->n; a.Lin = Lin; a.V = V; a.Lout = Lout;
-    a.hop = hop_penalty;
-    a.out = d_out; a.len_out = d_len_out; a.cost = d_cost; a.cost_in = d_cost_in; a.status = d_status;
-    for (long long p0 = 0; p0 < P; p0 += chunk) {
-        const long long Pc = P - p0 < chunk ? P - p0 : chunk, B = Pc * pairs;
-        a.p0 = p0; a.Pc = Pc;
-        a.qb = a.qa + n * (size_t)B;
-        uint8_t *d_free = reinterpret_cast<uint8_t *>(a.qb + n * (size_t)B);
-        a.free_flag = d_free;
-        {
-            BIND_DEVICE(ch);
-            hipLaunchKernelGGL(shortcut_gather_kernel, dim3((unsigned)Pc), dim3(GATHER_BLOCK), 0, (hipStream_t)stream, a);
-            HIP_TRY(hipGetLastError());
-        }
-        if (int rc = optik_hip_collision_motion_batch(ch, ee_offset7, a.qa, a.qb, B, resolution, nullptr, d_free,
-                                                      nullptr, nullptr, stream))
-            return rc;
-        BIND_DEVICE(ch);
-        hipLaunchKernelGGL(shortcut_route_kernel, dim3((unsigned)Pc), dim3(SC_WAVE), 0, (hipStream_t)stream, a);
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
+    ShortcutLaunch a =
+        make_launch(ch, d_path, d_len, Lin, P, V, hop_penalty, Lout, d_out, d_len_out, d_cost, d_cost_in, d_status);
+    return shortcut_chunks(ch, ee_offset7, a, resolution, nullptr, (hipStream_t)stream);
 }
 
 int optik_hip_path_resample(const optik_hip_chain *ch, const double *d_path, const int32_t *d_len, int32_t Lin,
@@ -458,36 +439,9 @@ int optik_hip_path_resample(const optik_hip_chain *ch, const double *d_path, con
 
 // ---- under a pose constraint ------------------------------------------------------------------------------------
 
-#define CON_LAUNCH(KERNEL, CHAIN, GRID, BLOCK, STREAM, ...)                                                        \
-    do {                                                                                                           \
-        if ((CHAIN)->wide) hipLaunchKernelGGL(KERNEL<WideChainDev>, dim3(GRID), dim3(BLOCK), 0, (STREAM), __VA_ARGS__); \
-        else hipLaunchKernelGGL(KERNEL<ChainDev>, dim3(GRID), dim3(BLOCK), 0, (STREAM), __VA_ARGS__);              \
-        HIP_TRY(hipGetLastError());                                                                                \
-    } while (0)
-
 int64_t optik_hip_path_shortcut_constrained_chunk(const optik_hip_chain *ch, int32_t V) {
     if (!ch || !points_ok(V)) return fail(OPTIK_HIP_EINVAL, "bad argument");
-    return chunk_paths_constrained(ch->n, V);
-}
-
-int optik_hip_constraint_motion_mask(const optik_hip_chain *ch, const double *ee_offset7, const double *ref7,
-                                     const double *lo6, const double *hi6, const double *d_qa, const double *d_qb,
-                                     int64_t B, double resolution, double tol, uint8_t *d_flag, void *stream) {
-    // (B = 0: optik_hip_constraint_motion_batch's own refusals)
-    if (int rc = optik_hip_constraint_motion_batch(ch, nullptr, ref7, lo6, hi6, nullptr, nullptr, 0, resolution, tol,
-                                                   nullptr, nullptr, nullptr, nullptr, nullptr))
-        return rc;
-    if (B < 0) return fail(OPTIK_HIP_EINVAL, "bad argument");
-    if (B == 0) return 0;
-    if (!d_qa || !d_qb || !d_flag) return fail(OPTIK_HIP_EINVAL, "bad argument");
-    BIND_DEVICE(ch);
-    ConLaunch k;
-    fill_con(ch, ee_offset7, ref7, lo6, hi6, k);
-    k.h = resolution;
-    k.tol = tol;
-    const int grid = grid_for(ch, B, 256, 8);
-    CON_LAUNCH(constraint_motion_mask_kernel, ch, grid, 256, (hipStream_t)stream, k, d_qa, d_qb, (long long)B, d_flag);
-    return 0;
+    return chunk_paths(ch->n, V, true);
 }
 
 int optik_hip_path_shortcut_constrained(optik_hip_chain *ch, const double *ee_offset7, const double *d_path,
@@ -505,51 +459,13 @@ int optik_hip_path_shortcut_constrained(optik_hip_chain *ch, const double *ee_of
     if (int rc = check_con(ch, ref7, lo6, hi6, true, resolution, tol, ptol, piters, damping, max_step)) return rc;
     if (P == 0 || (!d_out && !d_len_out && !d_cost && !d_cost_in && !d_status && !d_projected)) return 0;
     if (!d_path) return fail(OPTIK_HIP_EINVAL, "bad argument");
-    const size_t n = (size_t)ch->n;
-    const long long pairs = shortcut::pair_count(V);
-    const long long chunk = P < chunk_paths_constrained(ch->n, V) ? P : chunk_paths_constrained(ch->n, V);
-    ShortcutLaunch a;
-    std::memset(&a, 0, sizeof a);
-    ConLaunch k;
-    fill_con(ch, ee_offset7, ref7, lo6, hi6, k);
-    k.h = resolution; k.tol = tol;
-    k.ptol = ptol; k.piters = piters; k.damping = damping; k.max_step = max_step;
-    k.projected = d_projected;
-    {
-        std::lock_guard<std::mutex> lock(ch->mu);
-        BIND_DEVICE(ch);
-        // (every chunk is at most the first one's size; the doubles first: the segments twice, then the vertices)
-        HIP_TRY(ch->shortcut_ws.reserve((sizeof(double) * 2 * n + 1) * (size_t)(chunk * pairs)
-                                        + sizeof(double) * n * (size_t)(chunk * V)));
-        a.qa = reinterpret_cast<double *>(ch->shortcut_ws.get());
-    }
-    a.path = d_path; a.len = d_len; a.P = P;
-    a.n = ch->n; a.Lin = Lin; a.V = V; a.Lout = Lout;
-    a.hop = hop_penalty;
-    a.out = d_out; a.len_out = d_len_out; a.cost = d_cost; a.cost_in = d_cost_in; a.status = d_status;
-    for (long long p0 = 0; p0 < P; p0 += chunk) {
-        const long long Pc = P - p0 < chunk ? P - p0 : chunk, B = Pc * pairs;
-        a.p0 = p0; a.Pc = Pc;
-        a.qb = a.qa + n * (size_t)B;
-        k.verts = a.qb + n * (size_t)B;
-        uint8_t *d_free = reinterpret_cast<uint8_t *>(k.verts + n * (size_t)(Pc * V));
-        a.free_flag = d_free;
-        {
-            BIND_DEVICE(ch);
-            CON_LAUNCH(shortcut_cgather_kernel, ch, (unsigned)Pc, GATHER_BLOCK, (hipStream_t)stream, a, k);
-        }
-        if (int rc = optik_hip_collision_motion_batch(ch, ee_offset7, a.qa, a.qb, B, resolution, nullptr, d_free,
-                                                      nullptr, nullptr, stream))
-            return rc;
-        BIND_DEVICE(ch);
-        const int grid = grid_for(ch, B, 256, 8);
-        CON_LAUNCH(constraint_motion_mask_kernel, ch, grid, 256, (hipStream_t)stream, k, (const double *)a.qa,
-                   (const double *)a.qb, B, d_free);
-        hipLaunchKernelGGL(shortcut_route_stored_kernel, dim3((unsigned)Pc), dim3(SC_WAVE), 0, (hipStream_t)stream, a,
-                           (const double *)k.verts);
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
+    ShortcutLaunch a =
+        make_launch(ch, d_path, d_len, Lin, P, V, hop_penalty, Lout, d_out, d_len_out, d_cost, d_cost_in, d_status);
+    ConCall cc{ref7, lo6, hi6, tol, {}};
+    fill_constraint(ch, ee_offset7, ref7, lo6, hi6, cc.k.d);
+    cc.k.p = ProjectArgs{ptol, damping, max_step, piters};
+    cc.k.projected = d_projected;
+    return shortcut_chunks(ch, ee_offset7, a, resolution, &cc, (hipStream_t)stream);
 }
 
 int optik_hip_path_resample_constrained(const optik_hip_chain *ch, const double *ee_offset7, const double *d_path,
@@ -566,11 +482,11 @@ int optik_hip_path_resample_constrained(const optik_hip_chain *ch, const double 
     if (!d_path || !d_out) return fail(OPTIK_HIP_EINVAL, "bad argument");
     BIND_DEVICE(ch);
     ResampleLaunch a{d_path, d_len, P, ch->n, Lin, Lout, d_out, d_status};
-    ConLaunch k;
-    fill_con(ch, ee_offset7, ref7, lo6, hi6, k);
-    k.ptol = ptol; k.piters = piters; k.damping = damping; k.max_step = max_step;
+    ConLaunch k{};
+    fill_constraint(ch, ee_offset7, ref7, lo6, hi6, k.d);
+    k.p = ProjectArgs{ptol, damping, max_step, piters};
     k.projected = d_projected;
-    CON_LAUNCH(shortcut_cresample_kernel, ch, (unsigned)P, SC_WAVE, (hipStream_t)stream, a, k);
+    CONSTRAINT_LAUNCH(shortcut_cresample_kernel, ch, (unsigned)P, SC_WAVE, (hipStream_t)stream, a, k);
     return 0;
 }
 

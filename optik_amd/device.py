@@ -27,6 +27,18 @@ def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def _dpn(a):
+    """_dp, or a null pointer for None (an end-effector offset that was not given)."""
+    return _dp(a) if a is not None else None
+
+
+def _box_ptrs(arrays):
+    """The three pointers a constraint entry takes (ref7, lo6, hi6), of a PoseConstraint's arrays
+    (constraint.constraint_arrays); each keeps its array alive."""
+    ref7, lo, hi = arrays
+    return _dp(ref7), _dp(lo), _dp(hi)
+
+
 class LazyRoadmap:
     """The state of a lazy roadmap (HipChain.roadmap_build_lazy), device tensors: nodes
     [n, N], nbr [k, N] int32, the unchecked weights w0 [k, N], the working weights w [k, N] (w0, +inf where blocked:
@@ -89,7 +101,7 @@ class HipChain:
         t7 = np.ascontiguousarray(target7, dtype=np.float64)
         ee = np.ascontiguousarray(ee_offset7, dtype=np.float64) if ee_offset7 is not None else None
         nat.check(nat.lib().optik_hip_eval_batch(self._h, C.byref(cfg), _dp(t7),
-                                                 _dp(ee) if ee is not None else None, _ptr(q), B,
+                                                 _dpn(ee), _ptr(q), B,
                                                  _ptr(f), _ptr(g), _stream_ptr()))
         return f, g
 
@@ -100,7 +112,7 @@ class HipChain:
         pose = torch.empty((7, B), dtype=torch.float64, device=q.device)
         jac = torch.empty((6 * self.n, B), dtype=torch.float64, device=q.device) if jacobian else None
         ee = np.ascontiguousarray(ee_offset7, dtype=np.float64) if ee_offset7 is not None else None
-        nat.check(nat.lib().optik_hip_fk_batch(self._h, _dp(ee) if ee is not None else None, _ptr(q),
+        nat.check(nat.lib().optik_hip_fk_batch(self._h, _dpn(ee), _ptr(q),
                                                B, _ptr(pose), _ptr(jac), _stream_ptr()))
         return (pose, jac) if jacobian else pose
 
@@ -118,7 +130,7 @@ class HipChain:
         status = torch.empty(B, dtype=torch.int32, device=q.device)
         ee = np.ascontiguousarray(ee_offset7, dtype=np.float64) if ee_offset7 is not None else None
         nat.check(nat.lib().optik_hip_diff_ik_batch(
-            self._h, _dp(ee) if ee is not None else None, _ptr(q), _ptr(V), B if V.dim() == 2 else 0,
+            self._h, _dpn(ee), _ptr(q), _ptr(V), B if V.dim() == 2 else 0,
             _ptr(v_max), B if v_max.dim() == 2 else 0, B, _ptr(alpha), _ptr(v), _ptr(status), _stream_ptr()))
         return alpha, v, status
 
@@ -136,7 +148,7 @@ class HipChain:
         status = torch.empty(B, dtype=torch.int32, device=q.device)
         ee = np.ascontiguousarray(ee_offset7, dtype=np.float64) if ee_offset7 is not None else None
         nat.check(nat.lib().optik_hip_diff_ik_avoid_batch(
-            self._h, _dp(ee) if ee is not None else None, _ptr(q), _ptr(V), B if V.dim() == 2 else 0,
+            self._h, _dpn(ee), _ptr(q), _ptr(V), B if V.dim() == 2 else 0,
             _ptr(v_max), B if v_max.dim() == 2 else 0, B, float(influence), float(safety), float(gain),
             _ptr(alpha), _ptr(v), _ptr(status), _stream_ptr()))
         return alpha, v, status
@@ -150,7 +162,7 @@ class HipChain:
         grad = torch.empty((F, self.n, B), dtype=torch.float64, device=q.device)
         wit = torch.empty((F, 3, B), dtype=torch.int32, device=q.device)
         ee = np.ascontiguousarray(ee_offset7, dtype=np.float64) if ee_offset7 is not None else None
-        nat.check(nat.lib().optik_hip_collision_witness_batch(self._h, _dp(ee) if ee is not None else None, _ptr(q), B,
+        nat.check(nat.lib().optik_hip_collision_witness_batch(self._h, _dpn(ee), _ptr(q), B,
                                                               _ptr(dist), _ptr(grad), _ptr(wit), _stream_ptr()))
         return dist, grad, wit
 
@@ -168,7 +180,7 @@ class HipChain:
         ee = np.ascontiguousarray(ee_offset7, dtype=np.float64) if ee_offset7 is not None else None
         if ee is not None and ee.shape != (7,):
             raise ValueError("ee_offset7 must be 7 numbers: t, then the quaternion i, j, k, w")
-        nat.check(nat.lib().optik_hip_manip_batch(self._h, _dp(ee) if ee is not None else None, _ptr(q), B,
+        nat.check(nat.lib().optik_hip_manip_batch(self._h, _dpn(ee), _ptr(q), B,
                                                   _ptr(w), _ptr(c), _stream_ptr()))
         return w, c
 
@@ -401,7 +413,7 @@ class HipChain:
         B = self._check_q(q)
         ee = self._ee7(ee_offset7)
         frames = torch.empty((B, self.n + 2, 7), dtype=torch.float64, device=q.device)
-        nat.check(nat.lib().optik_hip_link_frames_batch(self._h, _dp(ee) if ee is not None else None, _ptr(q), B,
+        nat.check(nat.lib().optik_hip_link_frames_batch(self._h, _dpn(ee), _ptr(q), B,
                                                         _ptr(frames), _stream_ptr()))
         return frames
 
@@ -412,7 +424,7 @@ class HipChain:
         ee = self._ee7(ee_offset7)
         clearance = torch.empty(B, dtype=torch.float64, device=q.device)
         free = torch.empty(B, dtype=torch.uint8, device=q.device)
-        nat.check(nat.lib().optik_hip_collision_batch(self._h, _dp(ee) if ee is not None else None, _ptr(q), B,
+        nat.check(nat.lib().optik_hip_collision_batch(self._h, _dpn(ee), _ptr(q), B,
                                                       _ptr(clearance), _ptr(free), _stream_ptr()))
         return clearance, free.bool()
 
@@ -434,7 +446,7 @@ class HipChain:
         first = torch.empty(B, dtype=torch.int32, device=qa.device)
         steps = torch.empty(B, dtype=torch.int32, device=qa.device)
         nat.check(nat.lib().optik_hip_collision_motion_batch(
-            self._h, _dp(ee) if ee is not None else None, _ptr(qa), _ptr(qb), B, h, _ptr(clr), _ptr(free),
+            self._h, _dpn(ee), _ptr(qa), _ptr(qb), B, h, _ptr(clr), _ptr(free),
             _ptr(first), _ptr(steps), _stream_ptr()))
         return clr, free.bool(), first, steps
 
@@ -457,7 +469,7 @@ class HipChain:
                    t_stop=torch.empty(B, dtype=torch.float64, device=qa.device),
                    clearance=torch.empty(B, dtype=torch.float64, device=qa.device))
         nat.check(nat.lib().optik_hip_collision_motion_certify_batch(
-            self._h, _dp(ee) if ee is not None else None, _ptr(qa), _ptr(qb), B, tol, G, max_steps,
+            self._h, _dpn(ee), _ptr(qa), _ptr(qb), B, tol, G, max_steps,
             _ptr(out["status"]), _ptr(out["steps"]), _ptr(out["t_stop"]), _ptr(out["clearance"]), _stream_ptr()))
         return out
 
@@ -488,7 +500,7 @@ class HipChain:
                    clearance=torch.empty(P, dtype=torch.float64, device=q.device),
                    status=torch.empty(P, dtype=torch.int32, device=q.device))
         nat.check(nat.lib().optik_hip_path_optimize(
-            self._h, _dp(ee) if ee is not None else None, _ptr(q), L, P, int(iters), float(step), float(w_smooth),
+            self._h, _dpn(ee), _ptr(q), L, P, int(iters), float(step), float(w_smooth),
             float(w_obs), float(influence), float(safety), _ptr(out), _ptr(res["cost_first"]), _ptr(res["cost_last"]),
             _ptr(res["clearance"]), _ptr(res["status"]), _stream_ptr()))
         return res
@@ -509,7 +521,7 @@ class HipChain:
             raise ValueError(f"q must be a contiguous float64 cuda tensor [L, P, n] with n = {self.n}")
         L, P = int(q.shape[0]), int(q.shape[1])
         nat.check_path_optimize_args(L, iters, step, w_smooth, w_obs, influence, safety)
-        ref7, lo, hi = checked_constraint_arrays(c)
+        box = _box_ptrs(checked_constraint_arrays(c))
         ptol, piters, damping, max_step = nat.check_project_args(ptol, piters, damping, max_step)
         if out is None:
             out = torch.empty_like(q)
@@ -524,8 +536,8 @@ class HipChain:
                    violation=torch.empty(P, dtype=torch.float64, device=q.device),
                    projected=torch.empty((2, P), dtype=torch.int32, device=q.device))
         nat.check(nat.lib().optik_hip_path_optimize_constrained(
-            self._h, _dp(ee) if ee is not None else None, _ptr(q), L, P, int(iters), float(step), float(w_smooth),
-            float(w_obs), float(influence), float(safety), _dp(ref7), _dp(lo), _dp(hi), ptol, piters, damping, max_step,
+            self._h, _dpn(ee), _ptr(q), L, P, int(iters), float(step), float(w_smooth),
+            float(w_obs), float(influence), float(safety), *box, ptol, piters, damping, max_step,
             _ptr(out), _ptr(res["cost_first"]), _ptr(res["cost_last"]), _ptr(res["clearance"]), _ptr(res["status"]),
             _ptr(res["violation"]), _ptr(res["projected"]), _stream_ptr()))
         return res
@@ -565,7 +577,7 @@ class HipChain:
             k = self._check_slots(idx, Q, "idx", torch.int32)
         ee = self._ee7(ee_offset7)
         w = torch.empty((k, Q), dtype=torch.float64, device=frm.device)
-        nat.check(nat.lib().optik_hip_roadmap_edges(self._h, _dp(ee) if ee is not None else None, _ptr(frm), Q,
+        nat.check(nat.lib().optik_hip_roadmap_edges(self._h, _dpn(ee), _ptr(frm), Q,
                                                     _ptr(nodes), N, _ptr(idx), k, h, 1 if reverse else 0, _ptr(w),
                                                     _stream_ptr()))
         return w
@@ -623,12 +635,11 @@ class HipChain:
         """The residual [6, B] and the violation [B] of every column of q [n, B] against the pose constraint c
         (optik_amd.PoseConstraint; csrc/constraint_measure.hpp).  Stream-ordered."""
         B = self._check_q(q)
-        ref7, lo, hi = constraint_arrays(c)
+        box = _box_ptrs(constraint_arrays(c))
         ee = self._ee7(ee_offset7)
         r = torch.empty((6, B), dtype=torch.float64, device=q.device)
         v = torch.empty(B, dtype=torch.float64, device=q.device)
-        nat.check(nat.lib().optik_hip_constraint_batch(self._h, _dp(ee) if ee is not None else None, _dp(ref7), _dp(lo),
-                                                       _dp(hi), _ptr(q), B, _ptr(r), _ptr(v), _stream_ptr()))
+        nat.check(nat.lib().optik_hip_constraint_batch(self._h, _dpn(ee), *box, _ptr(q), B, _ptr(r), _ptr(v), _stream_ptr()))
         return r, v
 
     def constraint_project_batch(self, q, c, tol=nat.CONSTRAINT_TOL, iters=nat.CONSTRAINT_ITERS,
@@ -639,14 +650,14 @@ class HipChain:
         CONSTRAINT_FAILED: a NaN or infinite joint, or a failed factorisation) and iterations [B] int32.  A column
         that satisfies c comes back unchanged after 0 iterations.  Stream-ordered."""
         B = self._check_q(q)
-        ref7, lo, hi = constraint_arrays(c)
+        box = _box_ptrs(constraint_arrays(c))
         tol, iters, damping, max_step = nat.check_project_args(tol, iters, damping, max_step)
         ee = self._ee7(ee_offset7)
         out = dict(x=torch.empty_like(q), violation=torch.empty(B, dtype=torch.float64, device=q.device),
                    status=torch.empty(B, dtype=torch.int32, device=q.device),
                    iterations=torch.empty(B, dtype=torch.int32, device=q.device))
         nat.check(nat.lib().optik_hip_constraint_project_batch(
-            self._h, _dp(ee) if ee is not None else None, _dp(ref7), _dp(lo), _dp(hi), _ptr(q), B, tol, iters, damping,
+            self._h, _dpn(ee), *box, _ptr(q), B, tol, iters, damping,
             max_step, _ptr(out["x"]), _ptr(out["violation"]), _ptr(out["status"]), _ptr(out["iterations"]),
             _stream_ptr()))
         return out
@@ -661,7 +672,7 @@ class HipChain:
         if self._check_q(qb) != B or qb.device != qa.device:
             raise ValueError(f"qa and qb must have the same shape and device, got {tuple(qa.shape)} and {tuple(qb.shape)}")
         h = nat.check_resolution(resolution)
-        ref7, lo, hi = constraint_arrays(c)
+        box = _box_ptrs(constraint_arrays(c))
         tol = nat.check_constraint_tol(tol)
         ee = self._ee7(ee_offset7)
         v = torch.empty(B, dtype=torch.float64, device=qa.device)
@@ -669,7 +680,7 @@ class HipChain:
         first = torch.empty(B, dtype=torch.int32, device=qa.device)
         steps = torch.empty(B, dtype=torch.int32, device=qa.device)
         nat.check(nat.lib().optik_hip_constraint_motion_batch(
-            self._h, _dp(ee) if ee is not None else None, _dp(ref7), _dp(lo), _dp(hi), _ptr(qa), _ptr(qb), B, h, tol,
+            self._h, _dpn(ee), *box, _ptr(qa), _ptr(qb), B, h, tol,
             _ptr(v), _ptr(ok), _ptr(first), _ptr(steps), _stream_ptr()))
         return v, ok.bool(), first, steps
 
@@ -848,7 +859,7 @@ class HipChain:
             raise ValueError(f"node_free must be a contiguous uint8 cuda tensor of {N} flags")
         ee = self._ee7(ee_offset7)
         nat.check(nat.lib().optik_hip_roadmap_lazy_reset(
-            self._h, _dp(ee) if ee is not None else None, _ptr(rm.nodes), N, _ptr(rm.nbr), k, 1 if lengths else 0,
+            self._h, _dpn(ee), _ptr(rm.nodes), N, _ptr(rm.nbr), k, 1 if lengths else 0,
             _ptr(rm.w0), _ptr(node_free), _ptr(rm.verdict), _ptr(rm.w), _stream_ptr()))
         return rm
 
@@ -896,7 +907,7 @@ class HipChain:
         ee = self._ee7(ee_offset7)
         return self._lazy_loop(rm, (starts, goals, sidx, sw, gidx, gw, direct), Lmax, rounds,
                                lambda k, N, q: nat.lib().optik_hip_roadmap_lazy_plan(
-                                   self._h, _dp(ee) if ee is not None else None, _ptr(rm.nodes), N, _ptr(rm.nbr),
+                                   self._h, _dpn(ee), _ptr(rm.nodes), N, _ptr(rm.nbr),
                                    _ptr(rm.w), _ptr(rm.verdict), k, h, *q))
 
     def roadmap_plan_lazy_from_flags(self, roadmap, edge_free, node_free, start, goal, sidx, sw, gidx, gw, direct,
@@ -936,7 +947,7 @@ class HipChain:
                    nodes=torch.empty((2, Q), dtype=torch.int32, device=dev))
         ee = self._ee7(ee_offset7)
         nat.check(nat.lib().optik_hip_rrt_plan(
-            self._h, _dp(ee) if ee is not None else None, _ptr(starts), _ptr(goals), Q, iters, step, h, first,
+            self._h, _dpn(ee), _ptr(starts), _ptr(goals), Q, iters, step, h, first,
             max_nodes, int(Lmax), poll, _ptr(res["path"]), _ptr(res["len"]), _ptr(res["cost"]), _ptr(res["status"]),
             _ptr(res["iters"]), _ptr(res["nodes"]), _stream_ptr()))
         return res
@@ -973,7 +984,7 @@ class HipChain:
                    which=torch.empty(Q, dtype=torch.int32, device=dev))
         ee = self._ee7(ee_offset7)
         nat.check(nat.lib().optik_hip_rrt_plan_goals(
-            self._h, _dp(ee) if ee is not None else None, _ptr(starts), _ptr(goals), _ptr(gcount), Q, G, iters, step, h,
+            self._h, _dpn(ee), _ptr(starts), _ptr(goals), _ptr(gcount), Q, G, iters, step, h,
             first, max_nodes, int(Lmax), poll, _ptr(res["path"]), _ptr(res["len"]), _ptr(res["cost"]),
             _ptr(res["status"]), _ptr(res["iters"]), _ptr(res["nodes"]), _ptr(res["which"]), _stream_ptr()))
         return res
@@ -1002,7 +1013,7 @@ class HipChain:
         iters, step, max_nodes, poll, first = nat.check_rrt_args(iters, step, max_nodes, Lmax, poll, first)
         G = nat.check_rrt_goals(int(goals.shape[0]), max_nodes)
         h = nat.check_resolution(resolution)
-        ref7, lo, hi = constraint_arrays(c)
+        box = _box_ptrs(constraint_arrays(c))
         tol = nat.check_constraint_tol(tol)
         ptol, piters, damping, max_step = nat.check_project_args(ptol, piters, damping, max_step)
         dev = starts.device
@@ -1016,7 +1027,7 @@ class HipChain:
                    projected=torch.empty((2, Q), dtype=torch.int32, device=dev))
         ee = self._ee7(ee_offset7)
         nat.check(nat.lib().optik_hip_rrt_plan_constrained(
-            self._h, _dp(ee) if ee is not None else None, _dp(ref7), _dp(lo), _dp(hi), tol, ptol, piters, damping,
+            self._h, _dpn(ee), *box, tol, ptol, piters, damping,
             max_step, _ptr(starts), _ptr(goals), _ptr(gcount), Q, G, iters, step, h, first, max_nodes, int(Lmax), poll,
             _ptr(res["path"]), _ptr(res["len"]), _ptr(res["cost"]), _ptr(res["status"]), _ptr(res["iters"]),
             _ptr(res["nodes"]), _ptr(res["which"]), _ptr(res["projected"]), _stream_ptr()))
@@ -1068,7 +1079,7 @@ class HipChain:
                    cost_in=torch.empty(P, dtype=torch.float64, device=dev),
                    status=torch.empty(P, dtype=torch.int32, device=dev))
         nat.check(nat.lib().optik_hip_path_shortcut(
-            self._h, _dp(ee) if ee is not None else None, _ptr(path), _ptr(lens), L, P, int(vertices), h, hop,
+            self._h, _dpn(ee), _ptr(path), _ptr(lens), L, P, int(vertices), h, hop,
             int(Lout), _ptr(res["path"]), _ptr(res["len"]), _ptr(res["cost"]), _ptr(res["cost_in"]),
             _ptr(res["status"]), _stream_ptr()))
         return res
@@ -1107,7 +1118,7 @@ class HipChain:
         L, P = self._check_paths(path, lens)
         Lout = L if max_waypoints is None else max_waypoints
         h, hop = nat.check_shortcut_args(L, vertices, Lout, resolution, hop_penalty)
-        ref7, lo, hi = constraint_arrays(c)
+        box = _box_ptrs(constraint_arrays(c))
         tol = nat.check_constraint_tol(tol)
         ptol, piters, damping, max_step = nat.check_project_args(ptol, piters, damping, max_step)
         ee = self._ee7(ee_offset7)
@@ -1119,8 +1130,8 @@ class HipChain:
                    status=torch.empty(P, dtype=torch.int32, device=dev),
                    projected=torch.empty((2, P), dtype=torch.int32, device=dev))
         nat.check(nat.lib().optik_hip_path_shortcut_constrained(
-            self._h, _dp(ee) if ee is not None else None, _ptr(path), _ptr(lens), L, P, int(vertices), h, hop,
-            int(Lout), _dp(ref7), _dp(lo), _dp(hi), tol, ptol, piters, damping, max_step, _ptr(res["path"]),
+            self._h, _dpn(ee), _ptr(path), _ptr(lens), L, P, int(vertices), h, hop,
+            int(Lout), *box, tol, ptol, piters, damping, max_step, _ptr(res["path"]),
             _ptr(res["len"]), _ptr(res["cost"]), _ptr(res["cost_in"]), _ptr(res["status"]), _ptr(res["projected"]),
             _stream_ptr()))
         return res
@@ -1136,15 +1147,14 @@ class HipChain:
         Stream-ordered."""
         L, P = self._check_paths(path, lens)
         nat.check_shortcut_args(L, max_waypoints=waypoints)
-        ref7, lo, hi = constraint_arrays(c)
+        box = _box_ptrs(constraint_arrays(c))
         ptol, piters, damping, max_step = nat.check_project_args(ptol, piters, damping, max_step)
         ee = self._ee7(ee_offset7)
         out = torch.empty((int(waypoints), P, self.n), dtype=torch.float64, device=path.device)
         status = torch.empty(P, dtype=torch.int32, device=path.device)
         projected = torch.empty((2, P), dtype=torch.int32, device=path.device)
         nat.check(nat.lib().optik_hip_path_resample_constrained(
-            self._h, _dp(ee) if ee is not None else None, _ptr(path), _ptr(lens), L, P, int(waypoints), _dp(ref7),
-            _dp(lo), _dp(hi), ptol, piters, damping, max_step, _ptr(out), _ptr(status), _ptr(projected),
+            self._h, _dpn(ee), _ptr(path), _ptr(lens), L, P, int(waypoints), *box, ptol, piters, damping, max_step, _ptr(out), _ptr(status), _ptr(projected),
             _stream_ptr()))
         return out, status, projected
 
@@ -1160,11 +1170,11 @@ class HipChain:
                 and flag.is_contiguous() and flag.device == qa.device):
             raise ValueError(f"flag must be a contiguous uint8 cuda tensor of {B} flags on qa's device")
         h = nat.check_resolution(resolution)
-        ref7, lo, hi = constraint_arrays(c)
+        box = _box_ptrs(constraint_arrays(c))
         tol = nat.check_constraint_tol(tol)
         ee = self._ee7(ee_offset7)
         nat.check(nat.lib().optik_hip_constraint_motion_mask(
-            self._h, _dp(ee) if ee is not None else None, _dp(ref7), _dp(lo), _dp(hi), _ptr(qa), _ptr(qb), B, h, tol,
+            self._h, _dpn(ee), *box, _ptr(qa), _ptr(qb), B, h, tol,
             _ptr(flag), _stream_ptr()))
         return flag
 
@@ -1261,7 +1271,7 @@ class HipChain:
         o.d_win_idx, o.d_win_key = _ptr(bufs["win_idx"]), _ptr(bufs["win_key"])
         ee = np.ascontiguousarray(ee_offset7, dtype=np.float64) if ee_offset7 is not None else None
         nat.check(nat.lib().optik_hip_ik_batch(
-            self._h, C.byref(cfg), _ptr(targets), _ptr(x0), T, _dp(ee) if ee is not None else None,
+            self._h, C.byref(cfg), _ptr(targets), _ptr(x0), T, _dpn(ee),
             int(restart_begin), int(restart_end), int(flags), float(deadline_s), C.byref(o),
             _stream_ptr()))
         return bufs
@@ -1294,7 +1304,7 @@ class HipChain:
         o.d_idx, o.d_key = _ptr(bufs.get("idx")), _ptr(bufs.get("key"))
         ee = np.ascontiguousarray(ee_offset7, dtype=np.float64) if ee_offset7 is not None else None
         nat.check(nat.lib().optik_hip_ik_solutions(
-            self._h, C.byref(cfg), _ptr(targets), _ptr(x0), T, _dp(ee) if ee is not None else None,
+            self._h, C.byref(cfg), _ptr(targets), _ptr(x0), T, _dpn(ee),
             int(restart_begin), int(restart_end), float(deadline_s), k, min_dist, C.byref(o), _stream_ptr()))
         return bufs
 
@@ -1347,7 +1357,7 @@ class HipChain:
         o.d_sol_idx, o.d_sol_key = _ptr(res["idx"]), _ptr(res["key"])
         ee = self._ee7(ee_offset7)
         nat.check(nat.lib().optik_hip_ik_region(
-            self._h, _dp(ee) if ee is not None else None, _ptr(regions), _ptr(x0), T, b, e, tol, iters, damping,
+            self._h, _dpn(ee), _ptr(regions), _ptr(x0), T, b, e, tol, iters, damping,
             max_step, mode, _dp(kp[0]) if kp else None, _dp(kp[1]) if kp else None, _dp(kp[2]) if kp else None,
             kp[3] if kp else 0.0, k, min_dist, C.byref(o), _stream_ptr()))
         return res
@@ -1434,7 +1444,7 @@ class HipChain:
         o.d_key, o.d_step, o.d_last = _ptr(bufs.get("key")), _ptr(bufs.get("step")), _ptr(bufs.get("last"))
         ee = np.ascontiguousarray(ee_offset7, dtype=np.float64) if ee_offset7 is not None else None
         nat.check(nat.lib().optik_hip_ik_path(
-            self._h, C.byref(cfg), _ptr(targets), _ptr(x0), P, L, _dp(ee) if ee is not None else None, b, e,
+            self._h, C.byref(cfg), _ptr(targets), _ptr(x0), P, L, _dpn(ee), b, e,
             int(flags), float(deadline_s), max_step, C.byref(o), _stream_ptr()))
         return bufs
 
@@ -1449,7 +1459,7 @@ class HipChain:
         win_idx = np.zeros(T, dtype=np.uint64)
         ee = np.ascontiguousarray(ee_offset7, dtype=np.float64) if ee_offset7 is not None else None
         nat.check(nat.lib().optik_hip_ik_host(
-            self._h, C.byref(cfg), _dp(targets), _dp(x0), T, _dp(ee) if ee is not None else None,
+            self._h, C.byref(cfg), _dp(targets), _dp(x0), T, _dpn(ee),
             int(restart_begin), int(restart_end), int(flags), float(deadline_s), _dp(win_x), _dp(win_f),
             win_idx.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(win_key)))
         return dict(win_x=win_x, win_f=win_f, win_idx=win_idx.astype(np.int64), win_key=win_key)
