@@ -316,10 +316,25 @@ int optik_robot_roadmap_plan_lazy(const optik_robot *robot, const double *starts
  * bit), and goal_out [Q]: the goal reached for status 0, -1 otherwise.  A found path ends in that goal; any other is
  * the start, then goal 0 repeated (the start repeated without goals).  Ties go to the direct motion to the lowest goal.
  * Queries run in chunks of 4 096.  rc 0, or -1: what optik_robot_roadmap_plan refuses, G out of range, and a lazy
- * roadmap -- goal sets are planned over eager roadmaps only. */
+ * roadmap -- this call plans over eager roadmaps only; optik_robot_roadmap_plan_goals_lazy plans goal sets over lazy
+ * ones. */
 int optik_robot_roadmap_plan_goals(const optik_robot *robot, const double *starts, const double *goals,
                                    const int32_t *counts, int32_t G, int64_t Q, int32_t Lmax, double *paths_out,
                                    int32_t *len_out, double *cost_out, int32_t *status_out, int32_t *goal_out);
+/* Goal sets on lazy roadmaps (extension; include/optik_hip.h: optik_hip_roadmap_lazy_plan_goals; DESIGN.md section
+ * 5.34): "the world just changed, now plan to this pose".  optik_robot_roadmap_plan_goals_lazy takes
+ * optik_robot_roadmap_plan_goals' arguments and outputs over the roadmap of optik_robot_roadmap_build_lazy, with
+ * `rounds`, rounds_used_out and checked_out as optik_robot_roadmap_plan_lazy has them: a world that changed since the
+ * last call resets the verdicts first, the chunks of 4 096 queries share the verdicts, and the two counters are
+ * added up over the chunks.  One more status, 4: the route found last still holds an unchecked edge -- len 2, the
+ * start, then goal 0 repeated, goal -1, the cost a lower bound.  A plan of status 0, 1 or 3 equals
+ * optik_robot_roadmap_plan_goals over an eager roadmap of the same N, k, resolution, first and world, bit for bit.
+ * rc 0, or -1: null argument, G, Lmax or rounds out of range, no roadmap, and an eager roadmap (the message names
+ * optik_robot_roadmap_plan_goals). */
+int optik_robot_roadmap_plan_goals_lazy(const optik_robot *robot, const double *starts, const double *goals,
+                                        const int32_t *counts, int32_t G, int64_t Q, int32_t Lmax, int32_t rounds,
+                                        double *paths_out, int32_t *len_out, double *cost_out, int32_t *status_out,
+                                        int32_t *goal_out, int32_t *rounds_used_out, int64_t *checked_out);
 /* The bidirectional tree planner (extension; include/optik_hip.h: optik_hip_rrt_plan): what to
  * run on the rows that optik_robot_roadmap_plan returns as status 1.  It reads no roadmap and keeps no state in the
  * robot: starts, goals [Q][n] row-major; two trees per query of at most max_nodes (2 .. 4096) nodes grow from the

@@ -350,6 +350,49 @@ int optik_hip_roadmap_query_goals(const optik_hip_chain *chain, const double *d_
                                   const double *d_direct, int32_t Lmax, double *d_path, int32_t *d_len, double *d_cost,
                                   int32_t *d_status, int32_t *d_which, int32_t *d_route, int32_t *d_hop, void *stream);
 
+/* Goal-set planning on lazy roadmaps (extension; the rules, the theorem and the freezing rule:
+ * csrc/roadmap_goals_lazy_measure.hpp): the loop of optik_hip_roadmap_lazy_plan with optik_hip_roadmap_query_goals as
+ * its pass.  The state d_w, d_verdict [k][N] is a lazy roadmap's and optik_hip_roadmap_lazy_reset resets it; the query
+ * arguments are optik_hip_roadmap_query_goals' (the start links, the G x kg goal links and the G direct weights
+ * checked by the caller); `rounds` as optik_hip_roadmap_lazy_plan.  C is the set of UNKNOWN hop slots over the FOUND
+ * routes of a pass; the call ends when C is empty or after `rounds` checks.  Outputs as
+ * optik_hip_roadmap_query_goals (any may be NULL) with status 4, unsettled: the last pass found a route that still
+ * holds an UNKNOWN slot -- len 2, the start, then goal 0 repeated, which -1, the cost that route's, a lower bound.
+ * For status 0, 1 and 3 the status, len, cost, path and which are those of optik_hip_roadmap_query_goals over the
+ * eagerly checked graph, bit for bit; for status 2 the cost is a lower bound.  gcount = 0 is status 1.
+ * skip_settled = 0 runs every pass on all Q queries, as the rules are written.  skip_settled != 0 runs every pass
+ * after the first on the live queries only -- those of status 2, and those of status 0 whose route holds an UNKNOWN
+ * slot --: their arguments are gathered into compact arrays, queried, and the results scattered back.  A query that
+ * is left out is frozen: every later pass would write what it holds, bit for bit (the proof is in the rules' header),
+ * so every output, *rounds_used and *checked are identical in the two forms.
+ * The loop runs on the host: it reads two int32 in one copy per round, the size of C and the live count -- one
+ * synchronise of `stream` per round, none once `rounds` checks are made.  The routes, the lists, the compact arrays
+ * (room for Q queries) and the claimed segments are the chain's lazy workspace, grown on demand: one call per chain
+ * handle at a time; calls that share d_w and d_verdict must not overlap.
+ * optik_hip_roadmap_lazy_plan_goals_from_flags (a test hook): d_edge_free [k][N] uint8 in place of the motion check,
+ * d_node_free [N] uint8 not NULL runs the reset from it first, as optik_hip_roadmap_lazy_plan_from_flags.
+ * Both refuse what optik_hip_roadmap_query_goals and optik_hip_roadmap_lazy_plan refuse (rounds outside 0 .. 4096, the
+ * resolution, prismatic chains, Q above 2^30), with the same codes, before any device work; Q = 0 is a no-op. */
+int optik_hip_roadmap_lazy_plan_goals(optik_hip_chain *chain, const double *ee_offset7, const double *d_nodes,
+                                      int32_t N, const int32_t *d_nbr, double *d_w, int32_t *d_verdict, int32_t k,
+                                      double resolution, const double *d_start, const double *d_goals,
+                                      const int32_t *d_gcount, int32_t G, int64_t Q, const int32_t *d_sidx,
+                                      const double *d_sw, int32_t ks, const int32_t *d_gidx, const double *d_gw,
+                                      int32_t kg, const double *d_direct, int32_t Lmax, int32_t rounds,
+                                      int32_t skip_settled, double *d_path, int32_t *d_len, double *d_cost,
+                                      int32_t *d_status, int32_t *d_which, int32_t *rounds_used, int64_t *checked,
+                                      void *stream);
+int optik_hip_roadmap_lazy_plan_goals_from_flags(optik_hip_chain *chain, const double *d_nodes, int32_t N,
+                                                 const int32_t *d_nbr, double *d_w0, double *d_w, int32_t *d_verdict,
+                                                 int32_t k, const uint8_t *d_edge_free, const uint8_t *d_node_free,
+                                                 const double *d_start, const double *d_goals,
+                                                 const int32_t *d_gcount, int32_t G, int64_t Q, const int32_t *d_sidx,
+                                                 const double *d_sw, int32_t ks, const int32_t *d_gidx,
+                                                 const double *d_gw, int32_t kg, const double *d_direct, int32_t Lmax,
+                                                 int32_t rounds, int32_t skip_settled, double *d_path, int32_t *d_len,
+                                                 double *d_cost, int32_t *d_status, int32_t *d_which,
+                                                 int32_t *rounds_used, int64_t *checked, void *stream);
+
 /* The bidirectional tree planner (extension; the rules and their operation order:
  * csrc/rrt_measure.hpp): RRT-Connect with one extension per tree and iteration, for the queries a roadmap returns as
  * status 1 -- a start or goal in a pocket none of its nodes sees.  It needs no roadmap: each query grows tree 0 from

@@ -205,6 +205,12 @@ def lib():
     L.optik_hip_roadmap_lazy_plan.argtypes = [vp, dp, vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_double] + query_args
     L.optik_hip_roadmap_lazy_plan_from_flags.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, C.c_int32, vp,
                                                          vp] + query_args
+    goals_query_args = [vp, vp, vp, C.c_int32, C.c_int64, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32,
+                        C.c_int32, vp, vp, vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64), vp]
+    L.optik_hip_roadmap_lazy_plan_goals.argtypes = [vp, dp, vp, C.c_int32, vp, vp, vp, C.c_int32,
+                                                    C.c_double] + goals_query_args
+    L.optik_hip_roadmap_lazy_plan_goals_from_flags.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, C.c_int32, vp,
+                                                               vp] + goals_query_args
     L.optik_hip_rrt_plan.argtypes = [vp, dp, vp, vp, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_uint64, C.c_int32,
                                      C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
     L.optik_hip_rrt_plan_goals.argtypes = [vp, dp, vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double,

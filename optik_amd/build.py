@@ -18,7 +18,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "liboptik_amd.so")
-SOURCES = ["ik_capi.hip", "ik_select.hip", "ik_solutions.hip", "ik_path.hip", "ik_manip.hip", "ik_collision.hip", "ik_motion.hip", "ik_constraint.hip", "ik_region.hip", "ik_advance.hip", "ik_avoid.hip", "ik_path_optimize.hip", "ik_roadmap.hip", "ik_roadmap_lazy.hip", "ik_roadmap_goals.hip", "ik_rrt.hip", "ik_shortcut.hip", "ik_time.hip", "ik_occupancy.hip", "ik_depth.hip", "ik_mesh.hip", "ik_spherefit.hip", "ik_batch_ops.hip", "ik_quad_kernel.hip", "ik_lane_kernel.hip", "ik_wide_kernel.hip",
+SOURCES = ["ik_capi.hip", "ik_select.hip", "ik_solutions.hip", "ik_path.hip", "ik_manip.hip", "ik_collision.hip", "ik_motion.hip", "ik_constraint.hip", "ik_region.hip", "ik_advance.hip", "ik_avoid.hip", "ik_path_optimize.hip", "ik_roadmap.hip", "ik_roadmap_lazy.hip", "ik_roadmap_goals.hip", "ik_roadmap_goals_lazy.hip", "ik_rrt.hip", "ik_shortcut.hip", "ik_time.hip", "ik_occupancy.hip", "ik_depth.hip", "ik_mesh.hip", "ik_spherefit.hip", "ik_batch_ops.hip", "ik_quad_kernel.hip", "ik_lane_kernel.hip", "ik_wide_kernel.hip",
            "robot_host.cpp", "robot_rows.cpp", "robot_constraint.cpp"]
 # translation units: (source, object, extra flags).  ik_quad_kernel.hip is compiled twice -- its
 # throughput form (two waves per SIMD) without the machine-LICM pass, which otherwise hoists constants and
@@ -39,6 +39,7 @@ UNITS = [("ik_capi.hip", "ik_capi.o", []),          # chains, options, the resta
          ("ik_roadmap.hip", "ik_roadmap.o", []),    # roadmap planning: nearest neighbours, checked edges, path queries
          ("ik_roadmap_lazy.hip", "ik_roadmap_lazy.o", []),  # lazy roadmaps: edges checked when a route uses them
          ("ik_roadmap_goals.hip", "ik_roadmap_goals.o", []),  # goal-set planning: routes to the nearest of several goals
+         ("ik_roadmap_goals_lazy.hip", "ik_roadmap_goals_lazy.o", []),  # goal sets on lazy roadmaps: only live queries re-run
          ("ik_rrt.hip", "ik_rrt.o", []),            # bidirectional tree planner: two trees per query, one goal or a goal set, under a pose constraint too
          ("ik_shortcut.hip", "ik_shortcut.o", []),  # path shortcutting over all-pairs visibility, resampling
          ("ik_time.hip", "ik_time.o", []),          # timing of joint paths under velocity / acceleration limits, sampling

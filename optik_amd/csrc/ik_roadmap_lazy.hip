@@ -16,24 +16,24 @@
 //   (optik_hip_collision_motion_batch, classify form, on the same stream: the motion check's own code)
 //   lazy_mark_kernel      one thread per claimed slot: from the free flag to the verdict and w
 //
+// The workspace, the reset and the check of a round's claimed slots (gather, motion check, mark) are functions of
+// roadmap_lazy_device.hpp: the goal-set loop of ik_roadmap_goals_lazy.hip calls them too.
 // The loop runs on the host and reads one int32 per round, the size of the round's list: one stream synchronise a
 // round, none in the last pass once `rounds` checks are made.
 #include <algorithm>
 
-#include "collision_device.hpp"
-#include "roadmap_lazy_measure.hpp"
+#include "roadmap_lazy_device.hpp"
 
 using namespace optik;
 using namespace optik::host;
 using namespace optik::colldev;
+using namespace optik::lazydev;
 
 static_assert(roadmap::MAX_ROUNDS == OPTIK_HIP_ROADMAP_LAZY_MAX_ROUNDS && roadmap::UNKNOWN == OPTIK_HIP_ROADMAP_UNKNOWN
                   && roadmap::FREE == OPTIK_HIP_ROADMAP_FREE && roadmap::BLOCKED == OPTIK_HIP_ROADMAP_BLOCKED,
               "optik_hip.h states the constants of roadmap_lazy_measure.hpp");
 
 namespace {
-
-constexpr int LAZY_BLOCK = 256;
 
 struct SlotLaunch {
     const double *nodes;  // [n][N]
@@ -145,11 +145,10 @@ __global__ __launch_bounds__(LAZY_BLOCK) void lazy_mark_kernel(const MarkLaunch 
     if (verdict == roadmap::BLOCKED) a.w[e] = roadmap::inf();
 }
 
-inline unsigned blocks(long long work) { return (unsigned)((work + LAZY_BLOCK - 1) / LAZY_BLOCK); }
-inline size_t align16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+}  // namespace
 
-// the chain's lazy workspace, at least `bytes` (grown on demand, as optik_hip_roadmap_edges grows its own)
-int reserve_ws(optik_hip_chain *ch, size_t bytes, unsigned char **out) {
+// (roadmap_lazy_device.hpp: shared with the goal-set loop of ik_roadmap_goals_lazy.hip)
+int optik::lazydev::reserve_ws(optik_hip_chain *ch, size_t bytes, unsigned char **out) {
     std::lock_guard<std::mutex> lock(ch->mu);
     BIND_DEVICE(ch);
     HIP_TRY(ch->roadmap_lazy_ws.reserve(bytes));
@@ -157,13 +156,7 @@ int reserve_ws(optik_hip_chain *ch, size_t bytes, unsigned char **out) {
     return 0;
 }
 
-struct GraphArgs {
-    const double *nodes;
-    int32_t N, k;
-    const int32_t *nbr;
-    double *w0, *w;
-    int32_t *verdict;
-};
+namespace {
 
 // what reset refuses: the graph as optik_hip_roadmap_query refuses it
 int check_lazy_graph(const optik_hip_chain *ch, int32_t N, int32_t k) {
@@ -172,8 +165,10 @@ int check_lazy_graph(const optik_hip_chain *ch, int32_t N, int32_t k) {
                                          nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
-int reset_launch(optik_hip_chain *ch, const double *ee_offset7, const GraphArgs &g, int lengths,
-                 const uint8_t *d_node_free, hipStream_t stream) {
+}  // namespace
+
+int optik::lazydev::reset_launch(optik_hip_chain *ch, const double *ee_offset7, const GraphArgs &g, int lengths,
+                                 const uint8_t *d_node_free, hipStream_t stream) {
     if (!g.nodes || !g.nbr || !g.w0 || !g.verdict || !g.w) return fail(OPTIK_HIP_EINVAL, "bad argument");
     if (!d_node_free) {
         unsigned char *ws = nullptr;
@@ -189,6 +184,37 @@ int reset_launch(optik_hip_chain *ch, const double *ee_offset7, const GraphArgs 
     HIP_TRY(hipGetLastError());
     return 0;
 }
+
+int optik::lazydev::check_claimed(optik_hip_chain *ch, const double *ee_offset7, const GraphArgs &g, double resolution,
+                                  const uint8_t *d_edge_free, const int32_t *d_list, int32_t count,
+                                  unsigned char *d_free, double *d_qa, hipStream_t stream) {
+    MarkLaunch m;
+    std::memset(&m, 0, sizeof m);
+    m.B = count;
+    m.N = g.N; m.k = g.k; m.n = ch->n;
+    m.list = d_list; m.nbr = g.nbr; m.nodes = g.nodes;
+    m.qa = d_qa;
+    m.qb = d_qa ? d_qa + (size_t)ch->n * (size_t)count : nullptr;
+    m.free_flag = d_edge_free ? d_edge_free : d_free;
+    m.by_slot = d_edge_free ? 1 : 0;
+    m.verdict = g.verdict; m.w = g.w;
+    if (!d_edge_free) {
+        {
+            BIND_DEVICE(ch);
+            hipLaunchKernelGGL(lazy_gather_kernel, dim3(blocks(count)), dim3(LAZY_BLOCK), 0, stream, m);
+            HIP_TRY(hipGetLastError());
+        }
+        if (int rc = optik_hip_collision_motion_batch(ch, ee_offset7, m.qa, m.qb, count, resolution, nullptr, d_free,
+                                                      nullptr, nullptr, stream))
+            return rc;
+    }
+    BIND_DEVICE(ch);
+    hipLaunchKernelGGL(lazy_mark_kernel, dim3(blocks(count)), dim3(LAZY_BLOCK), 0, stream, m);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+namespace {
 
 struct QueryArgs {
     const double *start, *goal;
@@ -230,14 +256,6 @@ int lazy_loop(optik_hip_chain *ch, const double *ee_offset7, const GraphArgs &g,
     s.count = d_count;
     s.unknown = ws + o_unknown;
     s.goal = q.goal; s.path = q.path; s.len = q.len; s.status = q.status;
-    MarkLaunch m;
-    std::memset(&m, 0, sizeof m);
-    m.N = g.N; m.k = g.k; m.n = ch->n;
-    m.list = s.list; m.nbr = g.nbr; m.nodes = g.nodes;
-    m.qa = reinterpret_cast<double *>(ws + o_qa);
-    m.free_flag = d_edge_free ? d_edge_free : ws + o_free;
-    m.by_slot = d_edge_free ? 1 : 0;
-    m.verdict = g.verdict; m.w = g.w;
     int32_t used = 0;
     int64_t total = 0;
     for (;;) {
@@ -260,21 +278,9 @@ int lazy_loop(optik_hip_chain *ch, const double *ee_offset7, const GraphArgs &g,
         }
         if (count <= 0) break;
         if ((size_t)count > cap) return fail(OPTIK_HIP_EINVAL, "roadmap_lazy_plan: the verdicts are not a lazy roadmap's");
-        m.B = count;
-        m.qb = m.qa + n * (size_t)count;
-        if (!d_edge_free) {
-            {
-                BIND_DEVICE(ch);
-                hipLaunchKernelGGL(lazy_gather_kernel, dim3(blocks(count)), dim3(LAZY_BLOCK), 0, stream, m);
-                HIP_TRY(hipGetLastError());
-            }
-            if (int rc = optik_hip_collision_motion_batch(ch, ee_offset7, m.qa, m.qb, count, resolution, nullptr,
-                                                          ws + o_free, nullptr, nullptr, stream))
-                return rc;
-        }
-        BIND_DEVICE(ch);
-        hipLaunchKernelGGL(lazy_mark_kernel, dim3(blocks(count)), dim3(LAZY_BLOCK), 0, stream, m);
-        HIP_TRY(hipGetLastError());
+        if (int rc = check_claimed(ch, ee_offset7, g, resolution, d_edge_free, s.list, count, ws + o_free,
+                                   reinterpret_cast<double *>(ws + o_qa), stream))
+            return rc;
         used += 1;
         total += count;
     }

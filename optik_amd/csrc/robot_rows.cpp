@@ -1281,6 +1281,120 @@ int optik_robot_roadmap_plan_lazy(const optik_robot *r, const double *starts, co
     return set_err(-1, "roadmap_plan_lazy: the world or the roadmap kept changing during the call");
 }
 
+// Q goal-set plans over the robot's lazy roadmap (include/optik.h):
+// optik_robot_roadmap_plan_goals' staging and links with optik_robot_roadmap_plan_lazy's state -- the epoch compared
+// and the verdicts reset under the robot's mutex, the chunks against the shared verdicts, the call started again if
+// the world changed under it -- and the loop of optik_hip_roadmap_lazy_plan_goals in place of the query.
+int optik_robot_roadmap_plan_goals_lazy(const optik_robot *r, const double *starts, const double *goals,
+                                        const int32_t *counts, int32_t G, int64_t Q, int32_t Lmax, int32_t rounds,
+                                        double *paths_out, int32_t *len_out, double *cost_out, int32_t *status_out,
+                                        int32_t *goal_out, int32_t *rounds_used_out, int64_t *checked_out) {
+    if (!r || !starts || !goals) return set_err(-1, "null argument");
+    if (Q < 0) return set_err(-1, "bad argument");
+    if (G < 1 || G > OPTIK_HIP_ROADMAP_MAX_GOALS)
+        return set_err(-1, "roadmap_plan_goals_lazy: G must be in 1 .. " + std::to_string(OPTIK_HIP_ROADMAP_MAX_GOALS)
+                               + " goals per query");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    if (rounds_used_out) *rounds_used_out = 0;
+    if (checked_out) *checked_out = 0;
+    const size_t n = (size_t)r->n, uG = (size_t)G;
+    const std::vector<int32_t> all((size_t)(Q < kPlanChunk ? Q : kPlanChunk), G);  // counts NULL: every goal exists
+    for (int attempt = 0; attempt < 8; ++attempt) {
+        int32_t N, k;
+        double h;
+        uint64_t epoch;
+        {
+            // (under the robot's mutex no setter is half-way: the epoch and the chain's world belong together)
+            std::lock_guard<std::mutex> world_lock(r->mu);
+            BatchGuard guard(c);
+            if (!guard.ok()) return set_err(-1, kSetDeviceMsg);
+            if (c->rm_N == 0)
+                return set_err(-1, "roadmap_plan_goals_lazy: no roadmap (call optik_robot_roadmap_build_lazy first)");
+            if (!c->rm_lazy)
+                return set_err(-1, "roadmap_plan_goals_lazy: the roadmap is an eager one (call "
+                                   "optik_robot_roadmap_plan_goals)");
+            N = c->rm_N; k = c->rm_k; h = c->rm_h;
+            // (Q = 0: the kernel layer's refusals of Lmax, G and rounds)
+            if (optik_hip_roadmap_lazy_plan_goals(c->chain, nullptr, nullptr, N, nullptr, nullptr, nullptr, k, h, nullptr,
+                                                  nullptr, nullptr, G, 0, nullptr, nullptr, k, nullptr, nullptr, k,
+                                                  nullptr, Lmax, rounds, 1, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                  nullptr, nullptr, nullptr))
+                return set_err(-1, optik_hip_last_error());
+            epoch = r->world_epoch.load();
+            if (c->rm_epoch != epoch) {
+                if (lazy_reset(c, n, false, nullptr)) return -1;
+                c->rm_epoch = epoch;
+            }
+        }
+        if (Q == 0) return 0;
+        const size_t w = (size_t)Lmax * n, uk = (size_t)k, cells = uk * (size_t)N;
+        bool changed = false, upload_failed = false;
+        int64_t used = 0, checked = 0, done = 0;  // (the chunks come in order: done = the rows before this one)
+        // (per query out and the chunk's scratch behind it: as optik_robot_roadmap_plan_goals)
+        const RowInput in[] = {{starts, n}, {goals, uG * n}};
+        const int rc = stage_rows(
+            c, Q, in, sizeof(double) * (w + 3 + uG + uk + uG * uk) + sizeof(int32_t) * (uk + uG * uk), kPlanChunk,
+            [&](optik_hip_chain *ch, const double *d_s, int64_t L, double *d_out) -> int {
+                if (c->rm_N != N || c->rm_k != k || !c->rm_lazy || c->rm_epoch != epoch
+                    || epoch != r->world_epoch.load()) {
+                    changed = true;
+                    return 1;
+                }
+                const size_t uL = (size_t)L;
+                const double *d_g = d_s + n * uL, *d_nodes = c->rm_graph.get();
+                double *d_w = c->rm_graph.get() + n * (size_t)N;
+                int32_t *d_verdict = c->rm_nbr.get() + cells;
+                double *d_cost = d_out + w * uL;
+                int32_t *d_len = reinterpret_cast<int32_t *>(d_cost + uL), *d_status = d_len + uL;
+                int32_t *d_which = reinterpret_cast<int32_t *>(d_cost + 2 * uL), *d_gcount = d_which + uL;
+                double *d_direct = d_cost + 3 * uL, *d_sw = d_direct + uG * uL, *d_gw = d_sw + uk * uL;
+                int32_t *d_sidx = reinterpret_cast<int32_t *>(d_gw + uG * uk * uL), *d_gidx = d_sidx + uk * uL;
+                if (hipMemcpyAsync(d_gcount, counts ? counts + done : all.data(), sizeof(int32_t) * uL,
+                                   hipMemcpyHostToDevice, nullptr) != hipSuccess) {
+                    upload_failed = true;
+                    return 1;
+                }
+                done += L;
+                if (optik_hip_roadmap_knn(ch, d_s, L, d_nodes, N, k, 0, d_sidx, nullptr, nullptr)
+                    || optik_hip_roadmap_edges(ch, nullptr, d_s, L, d_nodes, N, d_sidx, k, h, 0, d_sw, nullptr))
+                    return 1;
+                for (size_t g = 0; g < uG; ++g) {
+                    const double *d_goal = d_g + g * n * uL;
+                    int32_t *d_gi = d_gidx + g * uk * uL;
+                    if (optik_hip_roadmap_knn(ch, d_goal, L, d_nodes, N, k, 0, d_gi, nullptr, nullptr)
+                        || optik_hip_roadmap_edges(ch, nullptr, d_goal, L, d_nodes, N, d_gi, k, h, 1,
+                                                   d_gw + g * uk * uL, nullptr)
+                        || optik_hip_roadmap_edges(ch, nullptr, d_s, L, d_goal, (int32_t)L, nullptr, 1, h, 0,
+                                                   d_direct + g * uL, nullptr))
+                        return 1;
+                }
+                int32_t chunk_used = 0;
+                int64_t chunk_checked = 0;
+                if (optik_hip_roadmap_lazy_plan_goals(ch, nullptr, d_nodes, N, c->rm_nbr.get(), d_w, d_verdict, k, h, d_s,
+                                                      d_g, d_gcount, G, L, d_sidx, d_sw, k, d_gidx, d_gw, k, d_direct,
+                                                      Lmax, rounds, 1, d_out, d_len, d_cost, d_status, d_which,
+                                                      &chunk_used, &chunk_checked, nullptr))
+                    return 1;
+                used += chunk_used;
+                checked += chunk_checked;
+                return 0;
+            },
+            [&](size_t b0, size_t L, const double *h_out) {
+                const int32_t *h_which =
+                    scatter_plans(h_out, b0, L, (size_t)Lmax, n, paths_out, len_out, cost_out, status_out);
+                if (goal_out) std::memcpy(goal_out + b0, h_which, sizeof(int32_t) * L);
+            });
+        if (changed) continue;
+        if (upload_failed) return set_err(-1, "upload failed");
+        if (rc) return rc;
+        if (rounds_used_out) *rounds_used_out = (int32_t)(used > INT32_MAX ? INT32_MAX : used);
+        if (checked_out) *checked_out = checked;
+        return 0;
+    }
+    return set_err(-1, "roadmap_plan_goals_lazy: the world or the roadmap kept changing during the call");
+}
+
 namespace {
 
 // The staging of both tree-planner wrappers, their arguments checked: G goal rows per query -- staged as [G][n][L],

@@ -54,8 +54,9 @@ class HipChain:
     """A flat kinematic chain uploaded to the GPU (optik_hip_chain).
 
     Every batch operator is stream-ordered on the current stream and returns without waiting for the device, with
-    one exception: roadmap_plan_lazy (and its test hook roadmap_plan_lazy_from_flags) runs its loop on the host
-    and reads one int32 per round, so it synchronises the current stream once per round of checks it makes.
+    one exception: roadmap_plan_lazy and roadmap_plan_goals_lazy (and their test hooks, and the _poses_lazy and
+    _region_lazy forms) run their loop on the host and read one or two int32 per round, so they synchronise the
+    current stream once per round of checks they make.
     roadmap_plan keeps its promise of no host synchronisation."""
 
     def __init__(self, types, origins, axes, lb, ub, device="cuda:0"):
@@ -789,7 +790,8 @@ class HipChain:
                 and goals.shape[1] == self.n and goals.shape[2] == Q and goals.is_contiguous()):
             raise ValueError(f"goals must be a contiguous float64 cuda tensor [G, n, Q] = [G, {self.n}, {Q}]")
         G = nat.check_roadmap_goals(int(goals.shape[0]))
-        cols = goals.permute(1, 0, 2).reshape(self.n, G * Q)  # [n, G * Q]: goal g of query q is column g * Q + q
+        # [n, G * Q]: goal g of query q is column g * Q + q (for Q = 1 the reshape is a transposed view: a copy then)
+        cols = goals.permute(1, 0, 2).reshape(self.n, G * Q).contiguous()
         sidx, _ = self.roadmap_knn(starts, nodes, ks)
         gidx, _ = self.roadmap_knn(cols, nodes, ks)
         sw = self.roadmap_edges(starts, nodes, sidx, resolution, ee_offset7=ee_offset7)
@@ -922,6 +924,113 @@ class HipChain:
                                lambda k, N, q: nat.lib().optik_hip_roadmap_lazy_plan_from_flags(
                                    self._h, _ptr(rm.nodes), N, _ptr(rm.nbr), _ptr(rm.w0), _ptr(rm.w), _ptr(rm.verdict),
                                    k, _ptr(edge_free), _ptr(node_free), *q))
+
+    # -- goal sets on lazy roadmaps (include/optik_hip.h) ------------------------------------
+    def _goals_lazy_loop(self, rm, q, Lmax, rounds, skip_settled, call):
+        start, goals, gcount, sidx, sw, gidx, gw, direct = q
+        N, Q = self._check_q(rm.nodes), self._check_q(start)
+        if not (isinstance(goals, torch.Tensor) and goals.is_cuda and goals.dtype == torch.float64 and goals.dim() == 3
+                and goals.shape[1] == self.n and goals.shape[2] == Q and goals.is_contiguous()):
+            raise ValueError(f"goals must be a contiguous float64 cuda tensor [G, n, Q] = [G, {self.n}, {Q}]")
+        G = nat.check_roadmap_goals(int(goals.shape[0]))
+        nat.check_roadmap_args(N=N, max_waypoints=Lmax)
+        rounds = nat.check_lazy_rounds(rounds)
+        if not (isinstance(gcount, torch.Tensor) and gcount.is_cuda and gcount.dtype == torch.int32
+                and tuple(gcount.shape) == (Q,) and gcount.is_contiguous()):
+            raise ValueError(f"gcount must be a contiguous int32 cuda tensor [{Q}]")
+        k = self._check_slots(rm.nbr, N, "nbr", torch.int32)
+        ks = self._check_slots(sidx, Q, "sidx", torch.int32)
+        kg = self._check_goal_slots(gidx, G, Q, "gidx", torch.int32)
+        if self._check_slots(sw, Q, "sw", torch.float64) != ks or self._check_goal_slots(gw, G, Q, "gw",
+                                                                                       torch.float64) != kg:
+            raise ValueError("a link's indices and weights must have the same shape")
+        if not (isinstance(direct, torch.Tensor) and direct.is_cuda and direct.dtype == torch.float64
+                and tuple(direct.shape) == (G, Q) and direct.is_contiguous()):
+            raise ValueError(f"direct must be a contiguous float64 cuda tensor [{G}, {Q}]")
+        dev = rm.nodes.device
+        res = dict(path=torch.empty((int(Lmax), Q, self.n), dtype=torch.float64, device=dev),
+                   len=torch.empty(Q, dtype=torch.int32, device=dev),
+                   cost=torch.empty(Q, dtype=torch.float64, device=dev),
+                   status=torch.empty(Q, dtype=torch.int32, device=dev),
+                   which=torch.empty(Q, dtype=torch.int32, device=dev))
+        used, checked = C.c_int32(0), C.c_int64(0)
+        nat.check(call(k, N, (_ptr(start), _ptr(goals), _ptr(gcount), G, Q, _ptr(sidx), _ptr(sw), ks, _ptr(gidx),
+                              _ptr(gw), kg, _ptr(direct), int(Lmax), rounds, 1 if skip_settled else 0,
+                              _ptr(res["path"]), _ptr(res["len"]), _ptr(res["cost"]), _ptr(res["status"]),
+                              _ptr(res["which"]), C.byref(used), C.byref(checked), _stream_ptr())))
+        res["rounds"], res["checked"] = int(used.value), int(checked.value)
+        return res
+
+    def roadmap_plan_goals_lazy(self, roadmap, starts, goals, gcount, ks, Lmax, rounds=None, ee_offset7=None,
+                                _skip_settled=True):
+        """roadmap_plan_goals over a LazyRoadmap (optik_hip_roadmap_lazy_plan_goals): the start links, the G * ks goal
+        links and the G direct motions are checked as roadmap_plan_goals checks them, then passes of the goal-set
+        query alternate with checks of the unknown edges that the found routes use, at most `rounds` times (None:
+        nat.ROADMAP_LAZY_ROUNDS); the verdicts stay in the roadmap.  Every pass after the first runs only the queries
+        that can still change (_skip_settled=False runs all of them every time: the same outputs, for measurements).
+        Returns roadmap_query_goals' dict with status 4 (nat.ROADMAP_UNSETTLED) for a route that still holds an
+        unchecked edge (which -1, the start and then goal 0), and "rounds" and "checked" as Python ints.  Like
+        roadmap_plan_lazy this call synchronises the current stream once per round made."""
+        rm = roadmap
+        h = rm.resolution
+        Q = self._check_q(starts)
+        if not (isinstance(goals, torch.Tensor) and goals.is_cuda and goals.dtype == torch.float64 and goals.dim() == 3
+                and goals.shape[1] == self.n and goals.shape[2] == Q and goals.is_contiguous()):
+            raise ValueError(f"goals must be a contiguous float64 cuda tensor [G, n, Q] = [G, {self.n}, {Q}]")
+        G = nat.check_roadmap_goals(int(goals.shape[0]))
+        # [n, G * Q]: goal g of query q is column g * Q + q (for Q = 1 the reshape is a transposed view: a copy then)
+        cols = goals.permute(1, 0, 2).reshape(self.n, G * Q).contiguous()
+        sidx, _ = self.roadmap_knn(starts, rm.nodes, ks)
+        gidx, _ = self.roadmap_knn(cols, rm.nodes, ks)
+        sw = self.roadmap_edges(starts, rm.nodes, sidx, h, ee_offset7=ee_offset7)
+        gw = self.roadmap_edges(cols, rm.nodes, gidx, h, reverse=True, ee_offset7=ee_offset7)
+        direct = self.roadmap_edges(starts.repeat(1, G), cols, None, h, ee_offset7=ee_offset7)
+        ks = int(ks)
+        ee = self._ee7(ee_offset7)
+        return self._goals_lazy_loop(
+            rm, (starts, goals, gcount, sidx, sw, gidx.reshape(ks, G, Q).permute(1, 0, 2).contiguous(),
+                 gw.reshape(ks, G, Q).permute(1, 0, 2).contiguous(), direct.reshape(G, Q)), Lmax, rounds, _skip_settled,
+            lambda k, N, q: nat.lib().optik_hip_roadmap_lazy_plan_goals(
+                self._h, _dpn(ee), _ptr(rm.nodes), N, _ptr(rm.nbr), _ptr(rm.w), _ptr(rm.verdict), k, h, *q))
+
+    def roadmap_plan_goals_lazy_from_flags(self, roadmap, edge_free, node_free, start, goals, gcount, sidx, sw, gidx,
+                                           gw, direct, Lmax, rounds, skip_settled=True):
+        """The loop of roadmap_plan_goals_lazy with edge_free [k, N] uint8 in place of the motion check (a test hook:
+        optik_hip_roadmap_lazy_plan_goals_from_flags); node_free [N] uint8 not None resets the roadmap from it first.
+        The links and the direct weights are given, as for roadmap_query_goals."""
+        rm = roadmap
+        if self._check_slots(edge_free, rm.nodes.shape[1], "edge_free", torch.uint8) != rm.nbr.shape[0]:
+            raise ValueError("edge_free must have nbr's shape")
+        return self._goals_lazy_loop(rm, (start, goals, gcount, sidx, sw, gidx, gw, direct), Lmax, rounds, skip_settled,
+                                     lambda k, N, q: nat.lib().optik_hip_roadmap_lazy_plan_goals_from_flags(
+                                         self._h, _ptr(rm.nodes), N, _ptr(rm.nbr), _ptr(rm.w0), _ptr(rm.w),
+                                         _ptr(rm.verdict), k, _ptr(edge_free), _ptr(node_free), *q))
+
+    def roadmap_plan_poses_lazy(self, roadmap, cfg, targets, starts, restart_begin, restart_end, K, min_dist, ks, Lmax,
+                                rounds=None, ee_offset7=None):
+        """roadmap_plan_poses over a LazyRoadmap: ik_solutions with x0 = the starts in front of roadmap_plan_goals_lazy
+        on the same stream.  Returns roadmap_plan_goals_lazy's dict plus goals [K, n, Q] and count [Q] int32."""
+        K = nat.check_roadmap_goals(K)
+        self._check_q(starts)
+        sol = self.ik_solutions(cfg, targets, starts.t().contiguous(), restart_begin, restart_end, K, min_dist,
+                                ee_offset7=ee_offset7)
+        goals = sol["x"].permute(1, 2, 0).contiguous()
+        res = self.roadmap_plan_goals_lazy(roadmap, starts, goals, sol["count"], ks, Lmax, rounds=rounds,
+                                           ee_offset7=ee_offset7)
+        res["goals"], res["count"] = goals, sol["count"]
+        return res
+
+    def roadmap_plan_region_lazy(self, roadmap, regions, starts, restart_begin, restart_end, K, min_dist, ks, Lmax,
+                                 rounds=None, ee_offset7=None, region_args=None):
+        """roadmap_plan_region over a LazyRoadmap: ik_region with x0 = the starts (region_args: a dict of its own
+        arguments) in front of roadmap_plan_goals_lazy on the same stream.  Returns roadmap_plan_goals_lazy's dict
+        plus goals [K, n, Q] and count [Q] int32."""
+        goals, count = self._region_goals(regions, starts, restart_begin, restart_end, K, min_dist,
+                                          dict(region_args or {}, ee_offset7=ee_offset7))
+        res = self.roadmap_plan_goals_lazy(roadmap, starts, goals, count, ks, Lmax, rounds=rounds,
+                                           ee_offset7=ee_offset7)
+        res["goals"], res["count"] = goals, count
+        return res
 
     # -- the bidirectional tree planner (include/optik_hip.h; DESIGN.md section 5.26) -----------------------------
     def rrt_plan(self, starts, goals, iters, step, resolution, first=0, max_nodes=nat.RRT_NODES, Lmax=64,

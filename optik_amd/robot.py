@@ -87,6 +87,8 @@ def _bind(L):
     L.optik_robot_roadmap_build.restype = C.c_int64
     L.optik_robot_roadmap_plan.argtypes = [vp, dp, dp, C.c_int64, C.c_int32, dp, ip, dp, ip]
     L.optik_robot_roadmap_plan_goals.argtypes = [vp, dp, dp, ip, C.c_int32, C.c_int64, C.c_int32, dp, ip, dp, ip, ip]
+    L.optik_robot_roadmap_plan_goals_lazy.argtypes = [vp, dp, dp, ip, C.c_int32, C.c_int64, C.c_int32, C.c_int32, dp, ip,
+                                                      dp, ip, ip, ip, C.POINTER(C.c_int64)]
     L.optik_robot_roadmap_build_lazy.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_uint64]
     L.optik_robot_roadmap_build_lazy.restype = C.c_int64
     L.optik_robot_roadmap_plan_lazy.argtypes = [vp, dp, dp, C.c_int64, C.c_int32, C.c_int32, dp, ip, dp, ip, ip,
@@ -1100,7 +1102,8 @@ class Robot:
 
     # -- goal-set planning (extension; include/optik.h) --------------------------------------
     _LAZY_GOALS_MSG = ("goal sets are planned over eager roadmaps only: the roadmap is a lazy one "
-                       "(build_roadmap(lazy=False), or plan to single goals with plan_paths)")
+                       "(build_roadmap(lazy=False), or plan to single goals with plan_paths; over a lazy roadmap goal "
+                       "sets are planned by plan_to_goals_lazy, plan_to_poses_lazy and plan_to_region_lazy)")
 
     def plan_to_goals(self, starts, goals, counts=None, max_waypoints=nat.PATH_OPTIMIZE_MAX_WAYPOINTS):
         """plan_paths to the nearest of several goals per query, in one pass over the roadmap: starts [Q, n], goals
@@ -1152,6 +1155,68 @@ class Robot:
         x, _, _, count = self.ik_solutions_batch_arrays(config, targets, starts, k=k, min_dist=min_dist,
                                                         ee_offset=ee_offset)
         res = self.plan_to_goals(starts, x, counts=count, max_waypoints=max_waypoints)
+        res["goals"], res["count"] = x, count
+        return res
+
+    # -- goal sets on lazy roadmaps (extension; include/optik.h) -----------------------------
+    def _need_lazy_roadmap(self):
+        lazy = getattr(self, "_roadmap_lazy", None)
+        if lazy is None:
+            raise RuntimeError("no roadmap (call build_roadmap(lazy=True) first)")
+        if not lazy:
+            raise RuntimeError("the roadmap is an eager one: plan goal sets over it with plan_to_goals, plan_to_poses "
+                               "and plan_to_region (or build_roadmap(lazy=True))")
+
+    def plan_to_goals_lazy(self, starts, goals, counts=None, max_waypoints=nat.PATH_OPTIMIZE_MAX_WAYPOINTS, rounds=None):
+        """plan_to_goals over a lazy roadmap (build_roadmap(lazy=True)): "the world just changed, now plan to these
+        goals" without a rebuild.  starts [Q, n], goals [Q, G, n], counts [Q] as plan_to_goals; `rounds` (0 .. 4096;
+        None: nat.ROADMAP_LAZY_ROUNDS) bounds the rounds of checking the unknown edges of the current routes, as in
+        plan_paths.  The start links, the goal links and the direct motions are checked with the call; the graph's
+        edges only where a cheapest route uses them, and after the first pass only the queries that can still change
+        are planned again.  Returns plan_to_goals' dict plus "rounds" and "checked".  One more status, 4: unsettled --
+        the path is the start, then goal 0 repeated, goal -1, the cost a lower bound (as is the cost of status 2).
+        Plans of status 0, 1 and 3 are those of plan_to_goals on an eager roadmap of the same arguments in the same
+        world, bit for bit.  A world that changed since the last call resets the verdicts first.
+        RuntimeError without a roadmap and with an eager one (plan_to_goals plans over those); ValueError for the
+        shapes, G outside 1 .. 16, max_waypoints outside 2 .. 64 and rounds out of range."""
+        self._need_lazy_roadmap()
+        starts = self._check_xs(starts)
+        Q, n = starts.shape
+        goals = np.ascontiguousarray(goals, dtype=np.float64)
+        if goals.ndim != 3 or goals.shape[0] != Q or goals.shape[2] != n:
+            raise ValueError(f"goals must be [Q, G, n] = [{Q}, G, {n}], got {list(goals.shape)}")
+        G = nat.check_roadmap_goals(goals.shape[1])
+        if counts is not None:
+            counts = np.ascontiguousarray(counts, dtype=np.int32)
+            if counts.shape != (Q,):
+                raise ValueError(f"counts must be [Q] = [{Q}], got {list(counts.shape)}")
+        nat.check_roadmap_args(max_waypoints=max_waypoints)
+        rounds = nat.check_lazy_rounds(rounds)
+        L = int(max_waypoints)
+        paths, cost = np.zeros((Q, L, n)), np.zeros(Q)
+        ln, status, goal = (np.zeros(Q, dtype=np.int32) for _ in range(3))
+        ip = C.POINTER(C.c_int32)
+        used, checked = C.c_int32(0), C.c_int64(0)
+        if self._L.optik_robot_roadmap_plan_goals_lazy(self._h, _dp(starts), _dp(goals),
+                                                       counts.ctypes.data_as(ip) if counts is not None else None, G, Q,
+                                                       L, rounds, _dp(paths), ln.ctypes.data_as(ip), _dp(cost),
+                                                       status.ctypes.data_as(ip), goal.ctypes.data_as(ip),
+                                                       C.byref(used), C.byref(checked)):
+            raise RuntimeError(_err(self._L))
+        return dict(paths=paths, len=ln, cost=cost, status=status, goal=goal, rounds=int(used.value),
+                    checked=int(checked.value))
+
+    def plan_to_poses_lazy(self, config: SolverConfig, starts, targets, k=8, min_dist=0.1,
+                           max_waypoints=nat.PATH_OPTIMIZE_MAX_WAYPOINTS, rounds=None, ee_offset=None):
+        """plan_to_poses over a lazy roadmap: ik_solutions_batch_arrays with the starts as seeds, then
+        plan_to_goals_lazy to the nearest of the solutions.  Returns plan_to_goals_lazy's dict plus "goals" [Q, k, n]
+        (NaN past the count) and "count" [Q] int32; an unreachable pose has count 0, status 1 and goal -1."""
+        self._need_lazy_roadmap()
+        k = nat.check_roadmap_goals(k)
+        starts = self._check_xs(starts)
+        x, _, _, count = self.ik_solutions_batch_arrays(config, targets, starts, k=k, min_dist=min_dist,
+                                                        ee_offset=ee_offset)
+        res = self.plan_to_goals_lazy(starts, x, counts=count, max_waypoints=max_waypoints, rounds=rounds)
         res["goals"], res["count"] = x, count
         return res
 
@@ -1803,6 +1868,19 @@ class Robot:
         starts, x, count = self._region_goals(config, starts, regions, k, min_dist,
                                               dict(region_args or {}, ee_offset=ee_offset))
         res = self.plan_to_goals(starts, x, counts=count, max_waypoints=max_waypoints)
+        res["goals"], res["count"] = x, count
+        return res
+
+    def plan_to_region_lazy(self, config: SolverConfig, starts, regions, k=8, min_dist=0.1,
+                            max_waypoints=nat.PATH_OPTIMIZE_MAX_WAYPOINTS, rounds=None, ee_offset=None,
+                            region_args=None):
+        """plan_to_region over a lazy roadmap: ik_region_batch_arrays with the starts as x0s (region_args: a dict of its
+        own arguments), then plan_to_goals_lazy.  Returns plan_to_goals_lazy's dict plus "goals" [Q, k, n] and "count"
+        [Q]; a region nothing projected onto has count 0, status 1 and goal -1."""
+        self._need_lazy_roadmap()
+        starts, x, count = self._region_goals(config, starts, regions, k, min_dist,
+                                              dict(region_args or {}, ee_offset=ee_offset))
+        res = self.plan_to_goals_lazy(starts, x, counts=count, max_waypoints=max_waypoints, rounds=rounds)
         res["goals"], res["count"] = x, count
         return res
 
