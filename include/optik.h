@@ -450,6 +450,17 @@ int optik_robot_trajectory_sample(const optik_robot *robot, int64_t P, int32_t L
                                   const int32_t *lens, const double *times, const double *velocities,
                                   const int32_t *status, double dt, int32_t T, double *q_out, double *qd_out);
 const double *optik_robot_velocity_limits(const optik_robot *robot);
+/* optik_robot_path_time with limits on the tool as well (extension; include/optik_hip.h: optik_hip_path_time_tool;
+ * DESIGN.md section 5.35).  tool_limits4: the tool centre point's speed, its tangential and its normal acceleration and
+ * the end effector's angular speed, each > 0, +inf for "no limit"; the tool is the end effector with ee_offset16 (may
+ * be NULL).  Beside optik_robot_path_time's outputs: tool_speed_out [P][L], tool_accel_out [P][L][2] (tangential,
+ * normal), tool_wspeed_out [P][L] at the waypoints.  Any output may be NULL.  rc 0, or -1: null argument, what the
+ * kernel layer refuses (a tool limit that is NaN or <= 0 among it). */
+int optik_robot_path_time_tool(const optik_robot *robot, int64_t P, int32_t L, const double *paths,
+                               const int32_t *lens, const double *v_max, const double *a_max,
+                               const double *tool_limits4, const double *ee_offset16, double *times_out,
+                               double *vel_out, double *acc_out, double *duration_out, int32_t *status_out,
+                               double *tool_speed_out, double *tool_accel_out, double *tool_wspeed_out);
 /* The motion check (extension; include/optik_hip.h: optik_hip_collision_motion_batch and what precedes it).  B segments
  * xa, xb [B][n] row-major at `resolution` (finite, > 0) -> clearance_out [B], free_out [B], first_out [B], steps_out
  * [B]; any may be NULL (clearance_out NULL: the call only classifies).  On the robot's first device, 65 536 segments

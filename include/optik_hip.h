@@ -696,6 +696,26 @@ int optik_hip_trajectory_sample(const optik_hip_chain *chain, const double *d_pa
                                 int64_t P, const double *d_t, const double *d_qd, const int32_t *d_status, double dt,
                                 int32_t Tout, double *d_q, double *d_qd_out, void *stream);
 
+/* optik_hip_path_time with limits on the tool as well (extension; the arithmetic and its
+ * operation order: csrc/time_tool_measure.hpp).  tool_limits4, in HOST memory: the speed of the tool centre point
+ * (m/s), its tangential and its normal acceleration (m/s^2) and the end effector's angular speed (rad/s), each > 0 and
+ * +inf for "no limit".  The tool is the pose fk_batch returns, with ee_offset7 (host memory, may be NULL).  The path
+ * derivative of that pose, by the same differences over the waypoint index as the joints', gives one more row of each
+ * stage (the tangential acceleration) and three more bounds on the squared path speed (speed, normal acceleration,
+ * angular speed).  Guaranteed at the waypoints: tool speed <= v, |tangential| <= a_t, normal <= a_n, angular speed <= w,
+ * hence |tool acceleration| <= sqrt(a_t^2 + a_n^2).  Not bounded: the angular acceleration and anything between
+ * waypoints.  Everything optik_hip_path_time says of its arguments, outputs and statuses holds; three more outputs, any
+ * may be NULL: d_tool_speed [L][P], d_tool_accel [L][P][2] (tangential, normal) and d_tool_wspeed [L][P] at the
+ * waypoints, 0 wherever the velocities are.  With all four limits +inf the shared outputs are optik_hip_path_time's
+ * bit for bit.  One wave per path, the forward kinematics of waypoint i on lane i; no workspace; bit for bit
+ * time_tool_measure.hpp's serial reference.  Refusals: optik_hip_path_time's, and OPTIK_HIP_EINVAL for tool_limits4
+ * NULL or a tool limit that is NaN or <= 0. */
+int optik_hip_path_time_tool(const optik_hip_chain *chain, const double *d_path, const int32_t *d_len, int32_t L,
+                             int64_t P, const double *d_vmax, const double *d_amax, const double *tool_limits4,
+                             const double *ee_offset7, double *d_t, double *d_qd, double *d_qdd, double *d_x,
+                             double *d_duration, int32_t *d_status, double *d_tool_speed, double *d_tool_accel,
+                             double *d_tool_wspeed, void *stream);
+
 /* The measures of solution modes 3 and 4 for B configurations d_q [n][B] (any chain of 1 .. 16 revolute joint
  * positions): d_w [B] manipulability w = sqrt(det G), d_c [B] condition c = sigma_min / sigma_max, both of the body
  * Jacobian fk_batch returns (ee_offset7 may be NULL).  Either output may be NULL.  A G that is not numerically

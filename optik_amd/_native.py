@@ -236,6 +236,8 @@ def lib():
     L.optik_hip_path_time.argtypes = [vp, vp, vp, C.c_int32, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.optik_hip_trajectory_sample.argtypes = [vp, vp, vp, C.c_int32, C.c_int64, vp, vp, vp, C.c_double, C.c_int32, vp,
                                               vp, vp]
+    L.optik_hip_path_time_tool.argtypes = [vp, vp, vp, C.c_int32, C.c_int64, vp, vp, dp, dp, vp, vp, vp, vp, vp, vp,
+                                           vp, vp, vp, vp]
     L.optik_hip_path_shortcut_chunk.restype = C.c_int64
     L.optik_hip_ik_batch.argtypes = [vp, C.POINTER(SolverConfigC), vp, vp, C.c_int32, dp,
                                      C.c_uint64, C.c_uint64, C.c_uint32, C.c_double,
@@ -563,6 +565,29 @@ def check_time_args(n, L=3, a_max=1.0, v_max=math.inf, scale=1.0):
     if not np.all(np.isfinite(a) & (a > 0.0)):
         raise ValueError(f"a_max must be finite and > 0, got {a_max!r}")
     return v, a
+
+
+def check_time_tool_args(tool_v_max=math.inf, tool_a_tangential=math.inf, tool_a_normal=math.inf,
+                         tool_w_max=math.inf, scale=1.0):
+    """The tool limits of optik_hip_path_time_tool, checked on the host; returns them as a float64 array of 4 in the
+    order the entry takes them.  Each is a number > 0 (+inf: no limit).  `scale` in (0, 1] multiplies the velocity-like
+    ones (the speed, the angular speed) as it multiplies v_max and the acceleration-like ones (tangential, normal) as
+    it multiplies a_max."""
+    import numpy as np
+    scale = float(scale)
+    if not 0.0 < scale <= 1.0:
+        raise ValueError(f"scale must be in (0, 1], got {scale!r}")
+    out = np.empty(4, dtype=np.float64)
+    for i, (name, v) in enumerate((("tool_v_max", tool_v_max), ("tool_a_tangential", tool_a_tangential),
+                                   ("tool_a_normal", tool_a_normal), ("tool_w_max", tool_w_max))):
+        try:
+            v = float(v)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be a number, got {v!r}") from None
+        if not v > 0.0:
+            raise ValueError(f"{name} must be > 0 (inf: no limit), got {v!r}")
+        out[i] = v * scale
+    return out
 
 
 def check_sample_args(dt, T=1):

@@ -11,16 +11,33 @@
 //                              after four butterfly steps.  The square roots and the segment times are the owning
 //                              lanes', the time prefix is lane 0's, in the header's order.  Dynamic LDS: (3 n + 5) * 64
 //                              doubles (4 608 bytes at n = 1, 13 824 at n = 7, 27 136 at n = 16); no workspace.
+//   path_time_tool_kernel<CH>  path_time_kernel with the tool's limits (time_tool_measure.hpp; DESIGN.md section 5.35;
+//                              optik_hip_path_time_tool), a kernel of its own so that path_time_kernel stays what it
+//                              is.  CH is ChainDev (n <= 8) or WideChainDev (9 .. 16), the table staged in static LDS.
+//                              Lane i runs the forward kinematics of waypoint i from its own LDS column -- the rolled
+//                              joint loop without the joint frames, so the pose is seven doubles of registers -- and
+//                              stages the pose [7][64]; after a barrier it forms the tool's derivatives from its
+//                              neighbours' columns (conflict-free like the joints': lane t reads column t +- 1), the
+//                              tool member as row n of the members and the tool caps into the stage's cap.  The
+//                              backward pass splits (n + 2)^2 pairs -- 9 at n = 1, 324 at n = 16, six a lane.  The
+//                              forward pass has up to 17 members, which lane & 15 does not cover: it FOLDS OVER 32
+//                              LANES, lane l holding member l & 31, five butterfly steps, so that either half of the
+//                              wave ends with the minimum.  Dynamic LDS: (3 n + 14) * 64 doubles -- path_time_kernel's
+//                              (3 n + 5) rows, one more slope and one more offset row for the tool member, seven pose
+//                              rows -- 8 704 bytes at n = 1, 17 920 at n = 7, 31 744 at n = 16; plus the chain table,
+//                              840 or 1 736 bytes static; no workspace.
 //   trajectory_sample_kernel   one thread per (path, sample), the path running fastest so that a wave writes
 //                              neighbouring paths (beyond 2^28 samples a thread strides on); no LDS, no workspace.
 //
 // A path's block sees only that path, so nothing depends on P or on the launch shape.
-#include "collision_device.hpp"
+#include "constraint_device.hpp"
 #include "time_measure.hpp"
+#include "time_tool_measure.hpp"
 
 using namespace optik;
 using namespace optik::host;
 using namespace optik::colldev;
+using namespace optik::condev;
 
 static_assert(timing::MAX_POINTS == OPTIK_HIP_PATH_TIME_MAX_WAYPOINTS && timing::MAX_POINTS == 64,
               "one lane of a wave per waypoint");
@@ -174,6 +191,161 @@ __global__ __launch_bounds__(TM_WAVE) void path_time_kernel(const TimeLaunch a) 
     }
 }
 
+struct ToolLaunch {
+    TimeLaunch t;
+    ConstraintDev d;                // the chain's tables and the ee_offset (no box)
+    double lim[tooltime::LIMITS];   // v_tool, a_t, a_n, w_tool; +inf: absent
+    double *tool_speed;             // [L][P] or null
+    double *tool_accel;             // [L][P][2] or null
+    double *tool_wspeed;            // [L][P] or null
+};
+
+// rows of 64 doubles of dynamic LDS: the waypoints [n], the members' slopes and offsets [n + 1] each (the tool's is row
+// n), the five rows of path_time_kernel, the end effector's pose per waypoint [7]
+constexpr int tool_lds_rows(int n) { return 3 * n + 14; }
+
+template <class CH>
+__global__ __launch_bounds__(TM_WAVE) void path_time_tool_kernel(const ToolLaunch b) {
+    extern __shared__ double tm_lds[];
+    __shared__ CH sch;
+    const TimeLaunch &a = b.t;
+    const int n = a.n, L = a.L, lane = threadIdx.x, nm = n + 1;  // nm: the stored members of a stage
+    double *q = tm_lds;          // [n][64] joint j of waypoint t at q[j * 64 + t]
+    double *s = q + n * MP;      // [n + 1][64] the members' slopes, stage i at s[j * 64 + i]; row n: the tool's
+    double *k = s + nm * MP;     // [n + 1][64] and offsets
+    double *bet = k + nm * MP;   // [64] xcap, then beta
+    double *xs = bet + MP;       // [64]
+    double *rt = xs + MP;        // [64] sqrt x
+    double *seg = rt + MP;       // [64] segment times
+    double *ts = seg + MP;       // [64]
+    double *pe = ts + MP;        // [7][64] the end effector's pose, component r of waypoint t at pe[r * 64 + t]
+    copy_table(sch, table_of<CH>(b.d));  // (the barrier behind the waypoints' staging is the table's too)
+    const long long p = blockIdx.x;
+    const double *path = a.path + p * n;
+    const long long st = a.P * n;
+    const int m = __builtin_amdgcn_readfirstlane(a.len ? a.len[p] : L);
+    int status = timing::TIMED;
+    if (!timing::length_ok(m, L)) status = timing::BAD_LENGTH;
+    if (status == timing::TIMED) {
+        bool fin = true;
+        if (lane < m)
+            for (int j = 0; j < n; ++j) {
+                const double v = path[lane * st + j];
+                q[j * MP + lane] = v;
+                fin = fin && timing::is_finite(v);
+            }
+        if (!__syncthreads_and(fin)) status = timing::PATH_NAN;
+    }
+    double duration = timing::nan();
+    double x_mine = 0.0;
+    tooltime::Stage tool{0.0, 0.0, 0.0, 0.0};
+    if (status == timing::TIMED) {
+        // the tool at waypoint `lane`: its pose from the lane's own column, then its derivatives from the neighbours'
+        if (lane < m) tooltime::store_ee(pe, MP, 1, lane, tooltime::fk_ee(sch, b.d.ep, n, q + lane, MP));
+        __syncthreads();
+        if (lane < m) tool = tooltime::stage_terms(pe, MP, 1, m, lane);
+        // the stage of lane i: members and cap
+        if (lane < m - 1) {
+            double cap = timing::inf();
+            for (int j = 0; j < n; ++j) {
+                const double d = timing::deriv_d(q + j * MP, 1, m, lane), c = timing::deriv_c(q + j * MP, 1, m, lane);
+                const double aj = a.amax[j];
+                const timing::Member mb = timing::member(d, c, aj);
+                s[j * MP + lane] = mb.s;
+                k[j * MP + lane] = mb.k;
+                cap = timing::take_min(cap, timing::cap_term(d, c, a.vmax[j], aj));
+            }
+            const timing::Member mb = tooltime::tool_member(tool, b.lim);
+            s[n * MP + lane] = mb.s;
+            k[n * MP + lane] = mb.k;
+            bet[lane] = timing::take_min(cap, tooltime::tool_cap(tool, b.lim));
+        }
+        __syncthreads();
+        // backward
+        const int pairs = (nm + 1) * (nm + 1);
+        double bnext = 0.0, beta_mine = 0.0;  // beta_(m-1)
+        bool unbounded = false;
+        for (int i = m - 2; i >= 0; --i) {
+            double bb = bet[i];
+            for (int e = lane; e < pairs; e += TM_WAVE)
+                bb = timing::take_min(bb, timing::stage_pair(nm, s + i, k + i, MP, bnext, e));
+            bb = wave_min(bb, TM_WAVE / 2);
+            if (lane == i) beta_mine = bb;
+            if (!(bb < timing::inf())) unbounded = true;
+            bnext = bb;
+        }
+        __syncthreads();
+        if (lane < m) bet[lane] = beta_mine;
+        __syncthreads();
+        if (unbounded) status = timing::UNBOUNDED;
+    }
+    if (status == timing::TIMED) {
+        // forward: lane l holds member l & 31 (17 of them at n = 16), so either half of the wave ends with the minimum
+        const int j = lane & (TM_WAVE / 2 - 1);
+        double xi = 0.0;
+        for (int i = 0; i < m - 1; ++i) {
+            double h = timing::inf();
+            if (j < nm) h = timing::take_min(h, timing::hi_value(s[j * MP + i], k[j * MP + i], xi));
+            h = wave_min(h, TM_WAVE / 4);
+            h = timing::take_min(h, bet[i + 1]);
+            xi = timing::clamp_x(h);
+            if (lane == i + 1) x_mine = xi;
+        }
+        if (lane < m) {
+            xs[lane] = x_mine;
+            rt[lane] = timing::tm_sqrt(x_mine);
+        }
+        __syncthreads();
+        bool bad = false;
+        if (lane < m - 1) {
+            bad = timing::segment_bad(rt[lane], rt[lane + 1]);
+            seg[lane] = timing::segment_time(rt[lane], rt[lane + 1]);
+        }
+        const bool any_bad = __syncthreads_or(bad) != 0;
+        if (lane == 0) {
+            double acc = 0.0;
+            ts[0] = acc;
+            for (int i = 0; i < m - 1; ++i) {
+                acc = acc + seg[i];
+                ts[i + 1] = acc;
+            }
+        }
+        __syncthreads();
+        duration = ts[m - 1];
+        if (any_bad || !timing::is_finite(duration)) status = timing::STALLED;
+    }
+    const bool timed = status == timing::TIMED;
+    if (!timed) duration = timing::nan();
+    if (lane == 0) {
+        if (a.duration) a.duration[p] = duration;
+        if (a.status) a.status[p] = status;
+    }
+    if (lane >= L) return;
+    const bool own = (timed || status == timing::STALLED) && lane < m;  // (STALLED: the profile is still written)
+    const long long lp = (long long)lane * a.P + p;
+    if (a.t) a.t[lp] = timed && lane < m ? ts[lane] : duration;
+    if (a.x) a.x[lp] = own ? x_mine : 0.0;
+    const double r = own ? rt[lane] : 0.0, u = own && lane < m - 1 ? timing::accel_u(x_mine, xs[lane + 1]) : 0.0;
+    if (b.tool_speed) b.tool_speed[lp] = own ? tooltime::out_speed(tool, r) : 0.0;
+    if (b.tool_wspeed) b.tool_wspeed[lp] = own ? tooltime::out_wspeed(tool, r) : 0.0;
+    if (b.tool_accel) {
+        b.tool_accel[2 * lp] = own && lane < m - 1 ? tooltime::out_tangential(tool, u, x_mine) : 0.0;
+        b.tool_accel[2 * lp + 1] = own ? tooltime::out_normal(tool, x_mine) : 0.0;
+    }
+    if (!a.qd && !a.qdd) return;
+    const long long o = lp * n;
+    for (int j = 0; j < n; ++j) {
+        double v = 0.0, acc = 0.0;
+        if (own) {
+            const double d = timing::deriv_d(q + j * MP, 1, m, lane), c = timing::deriv_c(q + j * MP, 1, m, lane);
+            v = timing::out_qd(d, r);
+            if (lane < m - 1) acc = timing::out_qdd(d, u, c, x_mine);
+        }
+        if (a.qd) a.qd[o + j] = v;
+        if (a.qdd) a.qdd[o + j] = acc;
+    }
+}
+
 struct SampleLaunch {
     const double *path;     // [L][P][n]
     const int32_t *len;     // [P] or null: L
@@ -215,6 +387,42 @@ int optik_hip_path_time(const optik_hip_chain *ch, const double *d_path, const i
     TimeLaunch a{d_path, d_len, d_vmax, d_amax, P, ch->n, L, d_t, d_qd, d_qdd, d_x, d_duration, d_status};
     const size_t lds = sizeof(double) * (size_t)(3 * ch->n + 5) * MP;
     hipLaunchKernelGGL(path_time_kernel, dim3((unsigned)P), dim3(TM_WAVE), lds, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int optik_hip_path_time_tool(const optik_hip_chain *ch, const double *d_path, const int32_t *d_len, int32_t L,
+                             int64_t P, const double *d_vmax, const double *d_amax, const double *tool_limits4,
+                             const double *ee_offset7, double *d_t, double *d_qd, double *d_qdd, double *d_x,
+                             double *d_duration, int32_t *d_status, double *d_tool_speed, double *d_tool_accel,
+                             double *d_tool_wspeed, void *stream) {
+    if (!ch || P < 0 || !tool_limits4) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    if (!points_ok(L)) return fail(OPTIK_HIP_EINVAL, "path_time_tool: a path has 3 .. 64 waypoints");
+    if (P > MAX_PATHS) return fail(OPTIK_HIP_EINVAL, "path_time_tool: more than 2^30 paths in one launch");
+    for (int i = 0; i < tooltime::LIMITS; ++i)
+        if (!tooltime::limit_ok(tool_limits4[i]))
+            return fail(OPTIK_HIP_EINVAL, "path_time_tool: a tool limit must be > 0 (+inf: no limit), no NaN");
+    if (ch->prismatic) return fail(OPTIK_HIP_EUNSUPPORTED, prismatic_msg());
+    if (P == 0 || (!d_t && !d_qd && !d_qdd && !d_x && !d_duration && !d_status && !d_tool_speed && !d_tool_accel
+                   && !d_tool_wspeed))
+        return 0;
+    if (!d_path || !d_vmax || !d_amax) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    BIND_DEVICE(ch);
+    ToolLaunch a;
+    std::memset(&a, 0, sizeof a);
+    a.t = TimeLaunch{d_path, d_len, d_vmax, d_amax, P, ch->n, L, d_t, d_qd, d_qdd, d_x, d_duration, d_status};
+    fill_constraint(ch, ee_offset7, nullptr, nullptr, nullptr, a.d);
+    std::memcpy(a.lim, tool_limits4, sizeof a.lim);
+    a.tool_speed = d_tool_speed;
+    a.tool_accel = d_tool_accel;
+    a.tool_wspeed = d_tool_wspeed;
+    const size_t lds = sizeof(double) * (size_t)tool_lds_rows(ch->n) * MP;
+    if (ch->wide)
+        hipLaunchKernelGGL(path_time_tool_kernel<WideChainDev>, dim3((unsigned)P), dim3(TM_WAVE), lds,
+                           (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(path_time_tool_kernel<ChainDev>, dim3((unsigned)P), dim3(TM_WAVE), lds, (hipStream_t)stream,
+                           a);
     HIP_TRY(hipGetLastError());
     return 0;
 }

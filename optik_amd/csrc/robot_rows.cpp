@@ -892,6 +892,56 @@ int optik_robot_path_time(const optik_robot *r, int64_t P, int32_t L, const doub
         limits.data(), limits.size());
 }
 
+// P paths through optik_hip_path_time_tool, exactly as optik_robot_path_time goes; the tool's limits are host arguments.
+int optik_robot_path_time_tool(const optik_robot *r, int64_t P, int32_t L, const double *paths, const int32_t *lens,
+                               const double *v_max, const double *a_max, const double *tool_limits4,
+                               const double *ee16, double *times_out, double *vel_out, double *acc_out,
+                               double *duration_out, int32_t *status_out, double *tool_speed_out,
+                               double *tool_accel_out, double *tool_wspeed_out) {
+    if (!r || !paths || !v_max || !a_max || !tool_limits4) return set_err(-1, "null argument");
+    if (P < 0) return set_err(-1, "bad argument");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    // (P = 0: the kernel layer's refusals of the chain, the sizes and the tool limits)
+    if (optik_hip_path_time_tool(c->chain, nullptr, nullptr, L, 0, nullptr, nullptr, tool_limits4, nullptr, nullptr,
+                                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (P == 0 || (!times_out && !vel_out && !acc_out && !duration_out && !status_out && !tool_speed_out
+                   && !tool_accel_out && !tool_wspeed_out))
+        return 0;
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    const size_t n = (size_t)r->n, nl = (size_t)L, w = nl * n;
+    std::vector<double> limits(v_max, v_max + n);
+    limits.insert(limits.end(), a_max, a_max + n);
+    // per path out: times [L], velocities [L][n], accelerations [L][n], tool speed [L], tool acceleration [L][2], tool
+    // angular speed [L], the duration, then the status in one more double
+    return stage_paths(
+        c, paths, lens, P, nl, n, 5 * nl + 2 * w + 2,
+        [&](const double *d_in, const int32_t *d_len, int64_t Lc, double *d_out) {
+            const double *d_lim = d_in + paths_extra_offset(nl, n, (size_t)Lc);
+            double *d_t = d_out, *d_qd = d_t + nl * (size_t)Lc, *d_qdd = d_qd + w * (size_t)Lc,
+                   *d_ts = d_qdd + w * (size_t)Lc, *d_ta = d_ts + nl * (size_t)Lc, *d_tw = d_ta + 2 * nl * (size_t)Lc,
+                   *d_dur = d_tw + nl * (size_t)Lc;
+            return optik_hip_path_time_tool(c->chain, d_in, d_len, L, Lc, d_lim, d_lim + n, tool_limits4,
+                                            ee16 ? ee7 : nullptr, d_t, d_qd, d_qdd, nullptr, d_dur,
+                                            reinterpret_cast<int32_t *>(d_dur + Lc), d_ts, d_ta, d_tw, nullptr);
+        },
+        [&](size_t b0, size_t Lc, const double *h_out) {
+            const double *h_t = h_out, *h_qd = h_t + nl * Lc, *h_qdd = h_qd + w * Lc, *h_ts = h_qdd + w * Lc,
+                         *h_ta = h_ts + nl * Lc, *h_tw = h_ta + 2 * nl * Lc, *h_dur = h_tw + nl * Lc;
+            if (times_out) scatter_paths(times_out, h_t, b0, Lc, nl, 1);
+            if (vel_out) scatter_paths(vel_out, h_qd, b0, Lc, nl, n);
+            if (acc_out) scatter_paths(acc_out, h_qdd, b0, Lc, nl, n);
+            if (tool_speed_out) scatter_paths(tool_speed_out, h_ts, b0, Lc, nl, 1);
+            if (tool_accel_out) scatter_paths(tool_accel_out, h_ta, b0, Lc, nl, 2);
+            if (tool_wspeed_out) scatter_paths(tool_wspeed_out, h_tw, b0, Lc, nl, 1);
+            if (duration_out) std::memcpy(duration_out + b0, h_dur, sizeof(double) * Lc);
+            if (status_out) std::memcpy(status_out + b0, h_dur + Lc, sizeof(int32_t) * Lc);
+        },
+        limits.data(), limits.size());
+}
+
 // P timed paths through optik_hip_trajectory_sample.  A path's samples are 2 T n doubles -- 7 MB at T = 65 536, n = 7 --
 // so the chunk is sized by the bytes of its results (kSampleChunkDoubles), not by kPathChunk.
 int optik_robot_trajectory_sample(const optik_robot *r, int64_t P, int32_t L, const double *paths, const int32_t *lens,

@@ -7,6 +7,7 @@ PyTorch is used only as plumbing: HBM allocation, streams, and (in ``bench.py``)
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -1317,6 +1318,35 @@ class HipChain:
         nat.check(nat.lib().optik_hip_path_time(self._h, _ptr(path), _ptr(lens), L, P, _ptr(v_max), _ptr(a_max),
                                                 _ptr(res["t"]), _ptr(res["qd"]), _ptr(res["qdd"]), _ptr(res["x"]),
                                                 _ptr(res["duration"]), _ptr(res["status"]), _stream_ptr()))
+        return res
+
+    def path_time_tool(self, path, lens=None, v_max=None, a_max=None, tool_v_max=math.inf,
+                       tool_a_tangential=math.inf, tool_a_normal=math.inf, tool_w_max=math.inf, ee_offset7=None):
+        """path_time with limits on the tool as well (optik_hip_path_time_tool): the tool
+        centre point's speed tool_v_max (m/s), its tangential and normal acceleration (m/s^2) and the end effector's
+        angular speed tool_w_max (rad/s), host numbers > 0, inf for "no limit"; the tool is fk_batch's pose with
+        ee_offset7.  Returns path_time's dict plus tool_speed [L, P], tool_accel [L, P, 2] (tangential, normal) and
+        tool_wspeed [L, P] at the waypoints; it goes into trajectory_sample as it is.  With every tool limit inf the
+        shared entries are path_time's bit for bit.  Stream-ordered."""
+        L, P = self._check_paths(path, lens)
+        nat.check_time_args(self.n, L)
+        lim = nat.check_time_tool_args(tool_v_max, tool_a_tangential, tool_a_normal, tool_w_max)
+        ee = self._ee7(ee_offset7)
+        dev = path.device
+        v_max, a_max = self._limits(v_max, "v_max", dev), self._limits(a_max, "a_max", dev)
+        res = dict(t=torch.empty((L, P), dtype=torch.float64, device=dev),
+                   qd=torch.empty((L, P, self.n), dtype=torch.float64, device=dev),
+                   qdd=torch.empty((L, P, self.n), dtype=torch.float64, device=dev),
+                   x=torch.empty((L, P), dtype=torch.float64, device=dev),
+                   duration=torch.empty(P, dtype=torch.float64, device=dev),
+                   status=torch.empty(P, dtype=torch.int32, device=dev),
+                   tool_speed=torch.empty((L, P), dtype=torch.float64, device=dev),
+                   tool_accel=torch.empty((L, P, 2), dtype=torch.float64, device=dev),
+                   tool_wspeed=torch.empty((L, P), dtype=torch.float64, device=dev))
+        nat.check(nat.lib().optik_hip_path_time_tool(
+            self._h, _ptr(path), _ptr(lens), L, P, _ptr(v_max), _ptr(a_max), _dp(lim), _dpn(ee), _ptr(res["t"]),
+            _ptr(res["qd"]), _ptr(res["qdd"]), _ptr(res["x"]), _ptr(res["duration"]), _ptr(res["status"]),
+            _ptr(res["tool_speed"]), _ptr(res["tool_accel"]), _ptr(res["tool_wspeed"]), _stream_ptr()))
         return res
 
     def trajectory_sample(self, path, timing, dt, samples, lens=None):

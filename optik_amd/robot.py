@@ -115,6 +115,8 @@ def _bind(L):
     L.optik_robot_path_time.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, dp, dp, dp, dp, dp, dp, ip]
     L.optik_robot_trajectory_sample.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, dp, dp, ip, C.c_double, C.c_int32, dp,
                                                 dp]
+    L.optik_robot_path_time_tool.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, dp, dp, dp, dp, dp, dp, dp, dp, ip, dp,
+                                             dp, dp]
     L.optik_robot_velocity_limits.argtypes = [vp]
     L.optik_robot_velocity_limits.restype = C.POINTER(C.c_double)
     L.optik_robot_joint_jacobian_ex.argtypes = [vp, dp, dp, dp]
@@ -1432,6 +1434,40 @@ class Robot:
                                          status.ctypes.data_as(ip)):
             raise RuntimeError(_err(self._L))
         return dict(times=times, velocities=vel, accelerations=acc, duration=dur, status=status)
+
+    def time_paths_tool(self, paths, lens=None, a_max=None, v_max=None, tool_v_max=np.inf, tool_a_tangential=np.inf,
+                        tool_a_normal=np.inf, tool_w_max=np.inf, scale=1.0, ee_offset=None):
+        """time_paths with limits on the tool as well: `tool_v_max` the speed of the tool centre point (m/s; a
+        collaborative cell's reduced speed is 0.25), `tool_a_tangential` and `tool_a_normal` its acceleration along
+        and across its path (m/s^2), `tool_w_max` the end effector's angular speed (rad/s); each a number > 0, inf for
+        "no limit".  The tool is the end effector with `ee_offset` [4, 4].  `scale` multiplies the speed limits as it
+        multiplies v_max and the acceleration limits as it multiplies a_max.  Returns time_paths' dict plus
+        "tool_speed" [P, L], "tool_accel" [P, L, 2] (tangential, normal) and "tool_wspeed" [P, L] at the waypoints, to
+        check the limits with; the dict goes into sample_trajectories as it is.  Guaranteed at the waypoints: speed <=
+        tool_v_max, |tangential| <= tool_a_tangential, normal <= tool_a_normal (so |acceleration| <= their root sum of
+        squares), angular speed <= tool_w_max.  NOT bounded: the angular acceleration, and anything between waypoints
+        -- resample densely.  With every tool limit inf the result is time_paths'.
+        ValueError for what time_paths refuses and for a tool limit that is <= 0 or NaN."""
+        paths, lens = self._check_paths(paths, lens)
+        P, L, n = paths.shape
+        if a_max is None:
+            raise ValueError("a_max is required: a URDF carries no acceleration limits")
+        v, a = nat.check_time_args(n, L, a_max, self.velocity_limits() if v_max is None else v_max, scale)
+        lim = nat.check_time_tool_args(tool_v_max, tool_a_tangential, tool_a_normal, tool_w_max, scale)
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        times, dur = np.zeros((P, L)), np.zeros(P)
+        vel, acc = np.zeros((P, L, n)), np.zeros((P, L, n))
+        status = np.zeros(P, dtype=np.int32)
+        speed, taccel, wspeed = np.zeros((P, L)), np.zeros((P, L, 2)), np.zeros((P, L))
+        ip = C.POINTER(C.c_int32)
+        if self._L.optik_robot_path_time_tool(self._h, P, L, _dp(paths),
+                                              lens.ctypes.data_as(ip) if lens is not None else None, _dp(v), _dp(a),
+                                              _dp(lim), _dp(ee) if ee is not None else None, _dp(times), _dp(vel),
+                                              _dp(acc), _dp(dur), status.ctypes.data_as(ip), _dp(speed), _dp(taccel),
+                                              _dp(wspeed)):
+            raise RuntimeError(_err(self._L))
+        return dict(times=times, velocities=vel, accelerations=acc, duration=dur, status=status, tool_speed=speed,
+                    tool_accel=taccel, tool_wspeed=wspeed)
 
     def sample_trajectories(self, paths, timing, dt, lens=None, resolution=None, ee_offset=None):
         """Samples the trajectories time_paths timed (`timing`: its result for these `paths` and `lens`) every `dt`
