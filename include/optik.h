@@ -461,6 +461,16 @@ int optik_robot_path_time_tool(const optik_robot *robot, int64_t P, int32_t L, c
                                const double *tool_limits4, const double *ee_offset16, double *times_out,
                                double *vel_out, double *acc_out, double *duration_out, int32_t *status_out,
                                double *tool_speed_out, double *tool_accel_out, double *tool_wspeed_out);
+/* Spline retiming of timed paths (extension; include/optik_hip.h: optik_hip_path_time_spline):
+ * paths [P][L][n], lens (may be NULL), times [P][L] and status [P] (may be NULL: all 0) as optik_robot_path_time
+ * returned them; v_max, a_max, j_max [n], each > 0, +inf for "no limit".  Outputs, any may be NULL: times_out [P][L],
+ * vel_out and acc_out [P][L][n], duration_out [P], factor_out [P], ratios_out [P][3], status_out [P].  rc 0, or -1:
+ * null argument, what the kernel layer refuses. */
+int optik_robot_path_time_spline(const optik_robot *robot, int64_t P, int32_t L, const double *paths,
+                                 const int32_t *lens, const double *times, const int32_t *status,
+                                 const double *v_max, const double *a_max, const double *j_max, double *times_out,
+                                 double *vel_out, double *acc_out, double *duration_out, double *factor_out,
+                                 double *ratios_out, int32_t *status_out);
 /* The motion check (extension; include/optik_hip.h: optik_hip_collision_motion_batch and what precedes it).  B segments
  * xa, xb [B][n] row-major at `resolution` (finite, > 0) -> clearance_out [B], free_out [B], first_out [B], steps_out
  * [B]; any may be NULL (clearance_out NULL: the call only classifies).  On the robot's first device, 65 536 segments

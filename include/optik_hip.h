@@ -716,6 +716,31 @@ int optik_hip_path_time_tool(const optik_hip_chain *chain, const double *d_path,
                              double *d_duration, int32_t *d_status, double *d_tool_speed, double *d_tool_accel,
                              double *d_tool_wspeed, void *stream);
 
+/* Spline retiming: the stage between optik_hip_path_time / _path_time_tool and optik_hip_trajectory_sample (extension;
+ * DESIGN.md section 5.36; the arithmetic and its operation order: csrc/time_spline_measure.hpp).  d_path, d_len, L, P
+ * as optik_hip_path_time takes them; d_t_in [L][P] and d_status_in [P] (may be NULL: all 0) are its d_t and d_status.
+ * The result is the clamped (rest to rest) C2 cubic spline through the waypoints at the times k * d_t_in, k >= 1 the
+ * least factor at which |velocity| <= d_vmax, |acceleration| <= d_amax and |jerk| <= d_jmax [n] (device memory; each
+ * > 0, +inf for "no limit") hold along the whole curve, not only at the waypoints; k = 1 returns the input times bit
+ * for bit.  Outputs, any may be NULL: d_t [L][P] the new times, d_qd and d_qdd [L][P][n] the spline's velocity and
+ * acceleration at the waypoints, d_duration [P], d_factor [P] (k), d_ratios [P][3] (the final peak velocity,
+ * acceleration and jerk over their limits, the largest over the joints), d_status [P]: 0; 1 the input status was
+ * neither 0 nor 4, or the times do not increase strictly from 0, or k is not finite; 2 a length outside 3 .. min(L,
+ * 64); 3 a waypoint or a time that is not finite; 4 a final ratio still above 1 -- the products k * t round the knot
+ * times, which moves the jerk ratio by up to a few 1e-12 at 64 waypoints, in rare cases more than the headroom of
+ * 3e-12.  A result with status 4 carries valid times: passed in again as d_t_in and d_status_in it is retimed once
+ * more (by about 1 + 2e-12) and ends at 0.  For 1 .. 3 the times and the duration are NaN and everything else 0; the
+ * waypoints behind a path's own hold the duration and zeros.  A C2 cubic spline is the cubic
+ * Hermite curve of its own knot velocities: (d_t, d_qd, d_status) goes into optik_hip_trajectory_sample as it is (a
+ * path with status 4 is sampled as its start, like every status other than 0).  The jerk is bounded on the open
+ * interval: the motion starts and stops with a finite acceleration step.  One wave per path, striding when the grid is
+ * capped; no workspace; bit for bit time_spline_measure.hpp's serial reference.  Refusals: optik_hip_path_time's. */
+int optik_hip_path_time_spline(const optik_hip_chain *chain, const double *d_path, const int32_t *d_len, int32_t L,
+                               int64_t P, const double *d_t_in, const int32_t *d_status_in, const double *d_vmax,
+                               const double *d_amax, const double *d_jmax, double *d_t, double *d_qd, double *d_qdd,
+                               double *d_duration, double *d_factor, double *d_ratios, int32_t *d_status,
+                               void *stream);
+
 /* The measures of solution modes 3 and 4 for B configurations d_q [n][B] (any chain of 1 .. 16 revolute joint
  * positions): d_w [B] manipulability w = sqrt(det G), d_c [B] condition c = sigma_min / sigma_max, both of the body
  * Jacobian fk_batch returns (ee_offset7 may be NULL).  Either output may be NULL.  A G that is not numerically

@@ -238,6 +238,8 @@ def lib():
                                               vp, vp]
     L.optik_hip_path_time_tool.argtypes = [vp, vp, vp, C.c_int32, C.c_int64, vp, vp, dp, dp, vp, vp, vp, vp, vp, vp,
                                            vp, vp, vp, vp]
+    L.optik_hip_path_time_spline.argtypes = [vp, vp, vp, C.c_int32, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                             vp, vp, vp]
     L.optik_hip_path_shortcut_chunk.restype = C.c_int64
     L.optik_hip_ik_batch.argtypes = [vp, C.POINTER(SolverConfigC), vp, vp, C.c_int32, dp,
                                      C.c_uint64, C.c_uint64, C.c_uint32, C.c_double,
@@ -588,6 +590,32 @@ def check_time_tool_args(tool_v_max=math.inf, tool_a_tangential=math.inf, tool_a
             raise ValueError(f"{name} must be > 0 (inf: no limit), got {v!r}")
         out[i] = v * scale
     return out
+
+
+# optik_hip_path_time_spline's statuses (csrc/time_spline_measure.hpp)
+SPLINE_SMOOTH, SPLINE_BAD_TIMES, SPLINE_BAD_LENGTH, SPLINE_NOT_FINITE, SPLINE_OVER_LIMIT = 0, 1, 2, 3, 4
+
+
+def check_time_spline_args(n, L=3, j_max=math.inf, a_max=math.inf, v_max=math.inf):
+    """The argument rules of optik_hip_path_time_spline, checked on the host; returns (v_max [n], a_max [n], j_max [n])
+    as float64 arrays, each a scalar or n values.  Every limit must be > 0; +inf means "no limit" (for a_max too, unlike
+    optik_hip_path_time's, which needs one to bound the profile)."""
+    import numpy as np
+    if isinstance(L, bool) or int(L) != L or not PATH_TIME_MIN_WAYPOINTS <= int(L) <= PATH_TIME_MAX_WAYPOINTS:
+        raise ValueError(f"L must be an integer in {PATH_TIME_MIN_WAYPOINTS} .. {PATH_TIME_MAX_WAYPOINTS}, got {L!r}")
+    out = []
+    for name, v in (("v_max", v_max), ("a_max", a_max), ("j_max", j_max)):
+        try:
+            a = np.asarray(v, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be a number or [n] numbers, got {v!r}") from None
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != n):
+            raise ValueError(f"{name} must be a scalar or [n] with n = {n}, got shape {list(a.shape)}")
+        a = np.ascontiguousarray(np.broadcast_to(a, (n,)))
+        if not np.all(a > 0.0):
+            raise ValueError(f"{name} must be > 0 (inf: no limit), got {v!r}")
+        out.append(a.copy())
+    return tuple(out)
 
 
 def check_sample_args(dt, T=1):

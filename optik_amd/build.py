@@ -105,6 +105,8 @@ RESOURCE_LIMITS = [
     (r"^optik::ik_quad_kernel<7, (true|false), 2>$", {"scratch": 0, "vgpr": 256}),
     # the certified motion check keeps a whole FK in registers per lane (ik_advance.hip): no scratch for n <= 8
     (r"^advance_kernel<[1-8], (true|false)>$", {"scratch": 0}),
+    # spline retiming keeps its columns in LDS and walks them with run-time indices (ik_time.hip): no scratch
+    (r"^path_time_spline_kernel$", {"scratch": 0}),
 ]
 
 

@@ -28,10 +28,22 @@
 //                              840 or 1 736 bytes static; no workspace.
 //   trajectory_sample_kernel   one thread per (path, sample), the path running fastest so that a wave writes
 //                              neighbouring paths (beyond 2^28 samples a thread strides on); no LDS, no workspace.
+//   path_time_spline_kernel    spline retiming (time_spline_measure.hpp; DESIGN.md section 5.36;
+//                              optik_hip_path_time_spline): one wave per path, the wave striding over the paths when
+//                              the grid is smaller than P.  Waypoints q, and the two work columns e and d of the
+//                              Thomas recurrence, are [joint][64] in LDS with row j rotated by j columns (spl_at): in
+//                              the recurrences lane j < n walks row j serially, and without the rotation the n lanes
+//                              would read n addresses 512 bytes apart, one bank; with it they read n neighbouring
+//                              columns.  In the measure lane i < m - 1 walks column i of every row, neighbouring
+//                              addresses with or without the rotation.  The times and the inverse spacings are one
+//                              row each: (3 n + 2) * 64 doubles of dynamic LDS (2 560 bytes at n = 1, 11 776 at n = 7,
+//                              25 600 at n = 16); no workspace.  A butterfly takes the three maxima; every lane then
+//                              holds the same ratios and computes the same factor.
 //
 // A path's block sees only that path, so nothing depends on P or on the launch shape.
 #include "constraint_device.hpp"
 #include "time_measure.hpp"
+#include "time_spline_measure.hpp"
 #include "time_tool_measure.hpp"
 
 using namespace optik;
@@ -368,6 +380,172 @@ __global__ __launch_bounds__(SAMPLE_BLOCK) void trajectory_sample_kernel(const S
     }
 }
 
+struct SplineLaunch {
+    const double *path;         // [L][P][n]
+    const int32_t *len;         // [P] or null: L
+    const double *t_in;         // [L][P]
+    const int32_t *status_in;   // [P] or null: 0
+    const double *vmax, *amax, *jmax;  // [n]
+    long long P;
+    int n, L;
+    double *t;                  // [L][P] or null
+    double *qd, *qdd;           // [L][P][n] or null
+    double *duration, *factor;  // [P] or null
+    double *ratios;             // [P][3] or null
+    int32_t *status;            // [P] or null
+};
+
+constexpr int SPLINE_BLOCKS_PER_CU = 32;  // one wave each; the LDS admits 6 (n = 16) to 64 (n = 1) of them
+constexpr int spline_lds_rows(int n) { return 3 * n + 2; }
+
+// joint j of waypoint (or row, or segment) i in a [joint][64] block whose row j is rotated by j columns
+__device__ __forceinline__ int spl_at(int j, int i) { return j * MP + ((i + j) & (MP - 1)); }
+
+__device__ __forceinline__ double wave_max(double b) {
+#pragma unroll
+    for (int o = TM_WAVE / 2; o >= 1; o >>= 1) b = splinetime::take_max(b, __shfl_xor(b, o, TM_WAVE));
+    return b;
+}
+
+// Steps 1 to 3 of time_spline_measure.hpp on the times ts: the knot velocities into d, the wave's ratios returned.
+__device__ splinetime::Peaks spline_measure(const SplineLaunch &a, int m, int lane, const double *q, double *e,
+                                            double *d, const double *ts, double *g) {
+    const int n = a.n;
+    if (lane < m - 1) g[lane] = splinetime::inv_spacing(ts[lane], ts[lane + 1]);
+    __syncthreads();
+    if (lane < n) {
+        const int j = lane;
+        double ep = 0.0, dp = 0.0, gm = g[0], q1 = q[spl_at(j, 1)];
+        double dm = splinetime::chord(q[spl_at(j, 0)], q1, gm);
+        for (int i = 1; i < m - 1; ++i) {
+            const double gi = g[i], q2 = q[spl_at(j, i + 1)], di = splinetime::chord(q1, q2, gi);
+            const splinetime::Sweep s = splinetime::sweep_row(gm, gi, dm, di, ep, dp);
+            e[spl_at(j, i)] = s.e;
+            d[spl_at(j, i)] = s.d;
+            ep = s.e;
+            dp = s.d;
+            gm = gi;
+            dm = di;
+            q1 = q2;
+        }
+        double v = 0.0;
+        d[spl_at(j, m - 1)] = v;
+        for (int i = m - 2; i >= 1; --i) {
+            v = splinetime::back_row(e[spl_at(j, i)], d[spl_at(j, i)], v);
+            d[spl_at(j, i)] = v;
+        }
+        d[spl_at(j, 0)] = 0.0;
+    }
+    __syncthreads();
+    splinetime::Peaks pk = splinetime::no_peaks();
+    if (lane < m - 1) {
+        const double gi = g[lane];
+        for (int j = 0; j < n; ++j) {
+            const double v0 = d[spl_at(j, lane)];
+            const splinetime::Segment s = splinetime::segment(
+                splinetime::chord(q[spl_at(j, lane)], q[spl_at(j, lane + 1)], gi), v0, d[spl_at(j, lane + 1)], gi);
+            splinetime::fold_segment(pk, s, v0, a.vmax[j], a.amax[j], a.jmax[j]);
+        }
+    }
+    pk.v = wave_max(pk.v);
+    pk.a = wave_max(pk.a);
+    pk.j = wave_max(pk.j);
+    pk.ok = __syncthreads_and(pk.ok) != 0;
+    return pk;
+}
+
+__global__ __launch_bounds__(TM_WAVE) void path_time_spline_kernel(const SplineLaunch a) {
+    extern __shared__ double tm_lds[];
+    const int n = a.n, L = a.L, lane = threadIdx.x;
+    double *q = tm_lds;       // [n][64] rotated: joint j of waypoint t at q[spl_at(j, t)]
+    double *e = q + n * MP;   // [n][64] rotated: the recurrence's e of row i
+    double *d = e + n * MP;   // [n][64] rotated: its d, then the knot velocities
+    double *ts = d + n * MP;  // [64] the times
+    double *g = ts + MP;      // [64] the inverse spacings
+    const long long st = a.P * n;
+    for (long long p = blockIdx.x; p < a.P; p += gridDim.x) {
+        const double *path = a.path + p * n;
+        const int m = __builtin_amdgcn_readfirstlane(a.len ? a.len[p] : L);
+        const int sin = __builtin_amdgcn_readfirstlane(a.status_in ? a.status_in[p] : 0);
+        const bool timed_in = splinetime::input_timed(sin);  // (0, or a former result's 4: its times are valid)
+        int status = splinetime::SMOOTH;
+        if (!timing::length_ok(m, L)) status = splinetime::BAD_LENGTH;
+        if (status == splinetime::SMOOTH) {
+            bool fin = true;
+            if (lane < m) {
+                for (int j = 0; j < n; ++j) {
+                    const double v = path[lane * st + j];
+                    q[spl_at(j, lane)] = v;
+                    fin = fin && timing::is_finite(v);
+                }
+                if (timed_in) {
+                    const double tv = a.t_in[(long long)lane * a.P + p];
+                    ts[lane] = tv;
+                    fin = fin && timing::is_finite(tv);
+                }
+            }
+            if (!__syncthreads_and(fin)) status = splinetime::NOT_FINITE;
+        }
+        if (status == splinetime::SMOOTH && !timed_in) status = splinetime::BAD_TIMES;
+        if (status == splinetime::SMOOTH) {
+            const bool inc = lane < m - 1 ? splinetime::times_step_ok(lane, ts[lane], ts[lane + 1]) : true;
+            if (!__syncthreads_and(inc)) status = splinetime::BAD_TIMES;
+        }
+        double k = 0.0;
+        splinetime::Peaks pk = splinetime::no_peaks();
+        if (status == splinetime::SMOOTH) {
+            pk = spline_measure(a, m, lane, q, e, d, ts, g);
+            k = splinetime::factor(pk);
+            if (!timing::is_finite(k)) {
+                status = splinetime::BAD_TIMES;
+            } else if (k > 1.0) {  // (k == 1: t' = t, and the second measure would repeat the first bit for bit)
+                const double tv = lane < m ? k * ts[lane] : 0.0;
+                __syncthreads();
+                if (lane < m) ts[lane] = tv;
+                __syncthreads();
+                pk = spline_measure(a, m, lane, q, e, d, ts, g);
+                if (!pk.ok) status = splinetime::BAD_TIMES;
+            }
+            if (status == splinetime::SMOOTH && splinetime::over_limit(pk)) status = splinetime::OVER_LIMIT;
+        }
+        const bool good = status == splinetime::SMOOTH || status == splinetime::OVER_LIMIT;
+        const double duration = good ? ts[m - 1] : timing::nan();
+        if (lane == 0) {
+            if (a.duration) a.duration[p] = duration;
+            if (a.factor) a.factor[p] = good ? k : 0.0;
+            if (a.ratios) {
+                a.ratios[3 * p] = good ? pk.v : 0.0;
+                a.ratios[3 * p + 1] = good ? pk.a : 0.0;
+                a.ratios[3 * p + 2] = good ? pk.j : 0.0;
+            }
+            if (a.status) a.status[p] = status;
+        }
+        if (lane < L) {
+            const bool own = good && lane < m;
+            const long long lp = (long long)lane * a.P + p;
+            if (a.t) a.t[lp] = own ? ts[lane] : duration;
+            if (a.qd || a.qdd) {
+                // the segment whose end this knot is read at: its own, the last knot the one before it
+                const int i = lane < m - 1 ? lane : m - 2;
+                const double gi = own ? g[i] : 0.0;
+                for (int j = 0; j < n; ++j) {
+                    double v = 0.0, acc = 0.0;
+                    if (own) {
+                        v = d[spl_at(j, lane)];
+                        const splinetime::Segment s = splinetime::segment(
+                            splinetime::chord(q[spl_at(j, i)], q[spl_at(j, i + 1)], gi), d[spl_at(j, i)],
+                            d[spl_at(j, i + 1)], gi);
+                        acc = lane < m - 1 ? s.a0 : s.a1;
+                    }
+                    if (a.qd) a.qd[lp * n + j] = v;
+                    if (a.qdd) a.qdd[lp * n + j] = acc;
+                }
+            }
+        }
+        __syncthreads();  // (the next path of this wave reuses the LDS)
+    }
+}
+
 bool points_ok(int v) { return v >= timing::MIN_POINTS && v <= timing::MAX_POINTS; }
 
 }  // namespace
@@ -423,6 +601,27 @@ int optik_hip_path_time_tool(const optik_hip_chain *ch, const double *d_path, co
     else
         hipLaunchKernelGGL(path_time_tool_kernel<ChainDev>, dim3((unsigned)P), dim3(TM_WAVE), lds, (hipStream_t)stream,
                            a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int optik_hip_path_time_spline(const optik_hip_chain *ch, const double *d_path, const int32_t *d_len, int32_t L,
+                               int64_t P, const double *d_t_in, const int32_t *d_status_in, const double *d_vmax,
+                               const double *d_amax, const double *d_jmax, double *d_t, double *d_qd, double *d_qdd,
+                               double *d_duration, double *d_factor, double *d_ratios, int32_t *d_status,
+                               void *stream) {
+    if (!ch || P < 0) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    if (!points_ok(L)) return fail(OPTIK_HIP_EINVAL, "path_time_spline: a path has 3 .. 64 waypoints");
+    if (P > MAX_PATHS) return fail(OPTIK_HIP_EINVAL, "path_time_spline: more than 2^30 paths in one launch");
+    if (ch->prismatic) return fail(OPTIK_HIP_EUNSUPPORTED, prismatic_msg());
+    if (P == 0 || (!d_t && !d_qd && !d_qdd && !d_duration && !d_factor && !d_ratios && !d_status)) return 0;
+    if (!d_path || !d_t_in || !d_vmax || !d_amax || !d_jmax) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    BIND_DEVICE(ch);
+    SplineLaunch a{d_path, d_len, d_t_in, d_status_in, d_vmax, d_amax, d_jmax, P, ch->n, L,
+                   d_t,    d_qd,  d_qdd,  d_duration,  d_factor, d_ratios, d_status};
+    const size_t lds = sizeof(double) * (size_t)spline_lds_rows(ch->n) * MP;
+    const unsigned grid = (unsigned)grid_for(ch, P, 1, SPLINE_BLOCKS_PER_CU);
+    hipLaunchKernelGGL(path_time_spline_kernel, dim3(grid), dim3(TM_WAVE), lds, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -942,6 +942,79 @@ int optik_robot_path_time_tool(const optik_robot *r, int64_t P, int32_t L, const
         limits.data(), limits.size());
 }
 
+// P timed paths through optik_hip_path_time_spline.  The times travel waypoint-major like the paths; the three limit
+// vectors, the lengths and the input statuses behind them.
+int optik_robot_path_time_spline(const optik_robot *r, int64_t P, int32_t L, const double *paths, const int32_t *lens,
+                                 const double *times, const int32_t *status, const double *v_max, const double *a_max,
+                                 const double *j_max, double *times_out, double *vel_out, double *acc_out,
+                                 double *duration_out, double *factor_out, double *ratios_out, int32_t *status_out) {
+    if (!r || !paths || !times || !v_max || !a_max || !j_max) return set_err(-1, "null argument");
+    if (P < 0) return set_err(-1, "bad argument");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    // (P = 0: the kernel layer's refusals of the chain and the sizes)
+    if (optik_hip_path_time_spline(c->chain, nullptr, nullptr, L, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                   nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (P == 0 || (!times_out && !vel_out && !acc_out && !duration_out && !factor_out && !ratios_out && !status_out))
+        return 0;
+    BatchGuard guard(c);
+    if (!guard.ok()) return set_err(-1, kSetDeviceMsg);
+    const size_t n = (size_t)r->n, nl = (size_t)L, w = nl * n;
+    // per path in: the path, its times, its length and status (two int32: one double); out: times [L], velocities and
+    // accelerations [L][n], the duration, the factor, three ratios, then the status in one more double
+    const size_t per_in = w + nl + 1, per_out = nl + 2 * w + 6;
+    const int64_t chunk = P < kPathChunk ? P : kPathChunk;
+    if (!reserve_batch(c, (per_in + per_out) * (size_t)chunk + 3 * n)) return set_err(-1, kBatchAllocMsg);
+    for (int64_t b0 = 0; b0 < P; b0 += chunk) {
+        const size_t Lc = (size_t)(P - b0 < chunk ? P - b0 : chunk);
+        // in: paths [L][Lc][n] | times [L][Lc] | v_max, a_max, j_max [n] | lens [Lc], status [Lc] (int32)
+        const size_t in_doubles = per_in * Lc + 3 * n;
+        double *h_in = c->h_batch.get(), *h_out = h_in + in_doubles;
+        double *d_in = c->d_batch.get(), *d_out = d_in + in_doubles;
+        double *h_t = h_in + w * Lc, *h_lim = h_t + nl * Lc;
+        int32_t *h_len = reinterpret_cast<int32_t *>(h_lim + 3 * n);
+        parallel_ranges(Lc, [&](size_t k0, size_t k1) {
+            for (size_t k = k0; k < k1; ++k)
+                for (size_t t = 0; t < nl; ++t) {
+                    const size_t src = ((size_t)b0 + k) * nl + t;
+                    std::memcpy(h_in + (t * Lc + k) * n, paths + src * n, sizeof(double) * n);
+                    h_t[t * Lc + k] = times[src];
+                }
+        });
+        std::memcpy(h_lim, v_max, sizeof(double) * n);
+        std::memcpy(h_lim + n, a_max, sizeof(double) * n);
+        std::memcpy(h_lim + 2 * n, j_max, sizeof(double) * n);
+        for (size_t k = 0; k < Lc; ++k) {
+            h_len[k] = lens ? lens[(size_t)b0 + k] : L;
+            h_len[Lc + k] = status ? status[(size_t)b0 + k] : 0;
+        }
+        if (hipMemcpyAsync(d_in, h_in, sizeof(double) * in_doubles, hipMemcpyHostToDevice, nullptr) != hipSuccess)
+            return set_err(-1, "upload failed");
+        const double *d_tin = d_in + w * Lc, *d_lim = d_tin + nl * Lc;
+        const int32_t *d_len = reinterpret_cast<const int32_t *>(d_lim + 3 * n);
+        double *d_t = d_out, *d_qd = d_t + nl * Lc, *d_qdd = d_qd + w * Lc, *d_dur = d_qdd + w * Lc, *d_fac = d_dur + Lc,
+               *d_rat = d_fac + Lc;
+        if (optik_hip_path_time_spline(c->chain, d_in, d_len, L, (int64_t)Lc, d_tin, d_len + Lc, d_lim, d_lim + n,
+                                       d_lim + 2 * n, d_t, d_qd, d_qdd, d_dur, d_fac, d_rat,
+                                       reinterpret_cast<int32_t *>(d_rat + 3 * Lc), nullptr))
+            return set_err(-1, optik_hip_last_error());
+        if (hipMemcpyAsync(h_out, d_out, sizeof(double) * per_out * Lc, hipMemcpyDeviceToHost, nullptr) != hipSuccess
+            || hipStreamSynchronize(nullptr) != hipSuccess)
+            return set_err(-1, "download failed");
+        const double *o_t = h_out, *o_qd = o_t + nl * Lc, *o_qdd = o_qd + w * Lc, *o_dur = o_qdd + w * Lc,
+                     *o_fac = o_dur + Lc, *o_rat = o_fac + Lc;
+        if (times_out) scatter_paths(times_out, o_t, (size_t)b0, Lc, nl, 1);
+        if (vel_out) scatter_paths(vel_out, o_qd, (size_t)b0, Lc, nl, n);
+        if (acc_out) scatter_paths(acc_out, o_qdd, (size_t)b0, Lc, nl, n);
+        if (duration_out) std::memcpy(duration_out + b0, o_dur, sizeof(double) * Lc);
+        if (factor_out) std::memcpy(factor_out + b0, o_fac, sizeof(double) * Lc);
+        if (ratios_out) std::memcpy(ratios_out + 3 * b0, o_rat, sizeof(double) * 3 * Lc);
+        if (status_out) std::memcpy(status_out + b0, o_rat + 3 * Lc, sizeof(int32_t) * Lc);
+    }
+    return 0;
+}
+
 // P timed paths through optik_hip_trajectory_sample.  A path's samples are 2 T n doubles -- 7 MB at T = 65 536, n = 7 --
 // so the chunk is sized by the bytes of its results (kSampleChunkDoubles), not by kPathChunk.
 int optik_robot_trajectory_sample(const optik_robot *r, int64_t P, int32_t L, const double *paths, const int32_t *lens,

@@ -1349,6 +1349,41 @@ class HipChain:
             _ptr(res["tool_speed"]), _ptr(res["tool_accel"]), _ptr(res["tool_wspeed"]), _stream_ptr()))
         return res
 
+    def path_time_spline(self, path, timing, j_max, a_max, v_max, lens=None):
+        """Spline retiming of timed paths (optik_hip_path_time_spline): path and lens as
+        path_time took them, timing its result (or path_time_tool's; "t" and "status" are read); j_max, a_max, v_max
+        float64 cuda tensors [n] (> 0, inf allowed).  Returns a dict of device tensors: t [L, P], qd and qdd [L, P, n]
+        -- the clamped C2 cubic spline through the waypoints at the times factor * t, slowed uniformly until the three
+        limits hold along the whole curve --, duration [P], factor [P], ratios [P, 3] (peak velocity, acceleration,
+        jerk over their limits), status [P] int32 (nat.SPLINE_*).  It goes into trajectory_sample as it is; a path
+        with status 4 (nat.SPLINE_OVER_LIMIT: rare, rounding) is held at its start there like every status other than
+        0, and is cleared by passing the result in again as `timing`.  As in path_time the limits' VALUES are not
+        checked here -- they are device tensors --: a limit that is 0, negative or NaN gives status 1 or ratios without
+        meaning, not a refusal; Robot.smooth_timing checks them on the host.  Stream-ordered."""
+        L, P = self._check_paths(path, lens)
+        nat.check_time_spline_args(self.n, L)
+        dev = path.device
+        t_in, status_in = timing["t"], timing["status"]
+        if not (isinstance(t_in, torch.Tensor) and isinstance(status_in, torch.Tensor) and t_in.shape == (L, P)
+                and status_in.shape == (P,) and t_in.is_contiguous() and status_in.is_contiguous()
+                and t_in.dtype == torch.float64 and status_in.dtype == torch.int32
+                and t_in.device == status_in.device == dev):
+            raise ValueError("timing must be path_time's result for this path")
+        v_max, a_max, j_max = (self._limits(v_max, "v_max", dev), self._limits(a_max, "a_max", dev),
+                               self._limits(j_max, "j_max", dev))
+        res = dict(t=torch.empty((L, P), dtype=torch.float64, device=dev),
+                   qd=torch.empty((L, P, self.n), dtype=torch.float64, device=dev),
+                   qdd=torch.empty((L, P, self.n), dtype=torch.float64, device=dev),
+                   duration=torch.empty(P, dtype=torch.float64, device=dev),
+                   factor=torch.empty(P, dtype=torch.float64, device=dev),
+                   ratios=torch.empty((P, 3), dtype=torch.float64, device=dev),
+                   status=torch.empty(P, dtype=torch.int32, device=dev))
+        nat.check(nat.lib().optik_hip_path_time_spline(
+            self._h, _ptr(path), _ptr(lens), L, P, _ptr(t_in), _ptr(status_in), _ptr(v_max), _ptr(a_max), _ptr(j_max),
+            _ptr(res["t"]), _ptr(res["qd"]), _ptr(res["qdd"]), _ptr(res["duration"]), _ptr(res["factor"]),
+            _ptr(res["ratios"]), _ptr(res["status"]), _stream_ptr()))
+        return res
+
     def trajectory_sample(self, path, timing, dt, samples, lens=None):
         """`samples` samples of each timed path at k * dt by cubic Hermite interpolation over the waypoints' times,
         positions and velocities (optik_hip_trajectory_sample): path and lens as path_time took them, timing its

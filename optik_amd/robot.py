@@ -117,6 +117,8 @@ def _bind(L):
                                                 dp]
     L.optik_robot_path_time_tool.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, dp, dp, dp, dp, dp, dp, dp, dp, ip, dp,
                                              dp, dp]
+    L.optik_robot_path_time_spline.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, dp, ip, dp, dp, dp, dp, dp, dp, dp, dp,
+                                               dp, ip]
     L.optik_robot_velocity_limits.argtypes = [vp]
     L.optik_robot_velocity_limits.restype = C.POINTER(C.c_double)
     L.optik_robot_joint_jacobian_ex.argtypes = [vp, dp, dp, dp]
@@ -1468,6 +1470,45 @@ class Robot:
             raise RuntimeError(_err(self._L))
         return dict(times=times, velocities=vel, accelerations=acc, duration=dur, status=status, tool_speed=speed,
                     tool_accel=taccel, tool_wspeed=wspeed)
+
+    def smooth_timing(self, paths, timing, j_max, a_max, v_max=None, lens=None):
+        """Spline retiming, the stage between time_paths / time_paths_tool and sample_trajectories: `timing` is their
+        result for these `paths` [P, L, n] and `lens`.  The waypoints keep their places and get new times, velocities
+        and accelerations: those of the C2 cubic spline through them, rest to rest, with every time multiplied by the
+        least factor >= 1 at which |velocity| <= v_max, |acceleration| <= a_max and |jerk| <= j_max hold along the
+        WHOLE curve, between the waypoints too.  j_max (rad/s^3), a_max (rad/s^2) and v_max (rad/s; None: the URDF's,
+        velocity_limits()) are a scalar or [n], each > 0, inf for "no limit".  Returns time_paths' dict -- times [P, L],
+        velocities and accelerations [P, L, n], duration [P], status [P] int32 -- plus factor [P] and ratios [P, 3], the
+        final peak velocity, acceleration and jerk over their limits (all <= 1 for status 0).  status: 0; 1 the input
+        status was neither 0 nor 4, or its times do not increase strictly from 0; 2 a length outside 3 .. L; 3 a NaN or
+        an infinity; 4 a ratio still above 1: rounding of the new times, rare, seen at 1 + 3e-12 with the jerk binding
+        at 64 waypoints; unless 0 or 4 the times and the duration are NaN.  sample_trajectories treats every status
+        other than 0 as untimed and holds such a path at its start, a 4 included: pass a result that holds a 4 through
+        smooth_timing once more (`timing` = that result), which retimes those paths by about 1 + 2e-12 and leaves the
+        ones with status 0 at factor 1, bit for bit.  The
+        sampler's cubic Hermite curve over (times, waypoints, velocities) IS this spline, so the dict goes into
+        sample_trajectories as it is and (q, qd, qdd) are consistent.  Not covered: the
+        motion starts and stops with a finite acceleration step -- the jerk is bounded on the open interval --, the
+        slow-down is uniform, time_paths_tool's tool limits are only scaled down.
+        ValueError for a limit that is <= 0 or NaN, L outside 3 .. 64, a timing of another shape."""
+        paths, lens = self._check_paths(paths, lens)
+        P, L, n = paths.shape
+        v, a, j = nat.check_time_spline_args(n, L, j_max, a_max, self.velocity_limits() if v_max is None else v_max)
+        t_in = np.ascontiguousarray(timing["times"], dtype=np.float64)
+        s_in = np.ascontiguousarray(timing["status"], dtype=np.int32)
+        if t_in.shape != (P, L) or s_in.shape != (P,):
+            raise ValueError("timing must be time_paths' result for these paths")
+        times, dur, fac, ratios = np.zeros((P, L)), np.zeros(P), np.zeros(P), np.zeros((P, 3))
+        vel, acc = np.zeros((P, L, n)), np.zeros((P, L, n))
+        status = np.zeros(P, dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        if self._L.optik_robot_path_time_spline(self._h, P, L, _dp(paths),
+                                                lens.ctypes.data_as(ip) if lens is not None else None, _dp(t_in),
+                                                s_in.ctypes.data_as(ip), _dp(v), _dp(a), _dp(j), _dp(times), _dp(vel),
+                                                _dp(acc), _dp(dur), _dp(fac), _dp(ratios), status.ctypes.data_as(ip)):
+            raise RuntimeError(_err(self._L))
+        return dict(times=times, velocities=vel, accelerations=acc, duration=dur, status=status, factor=fac,
+                    ratios=ratios)
 
     def sample_trajectories(self, paths, timing, dt, lens=None, resolution=None, ee_offset=None):
         """Samples the trajectories time_paths timed (`timing`: its result for these `paths` and `lens`) every `dt`
