@@ -448,6 +448,27 @@ int optik_hip_rrt_plan(optik_hip_chain *chain, const double *ee_offset7, const d
                        int32_t *d_iters, int32_t *d_nodes, void *stream);
 int64_t optik_hip_rrt_chunk(const optik_hip_chain *chain, int32_t max_nodes);
 
+/* A test hook (a diagnostic, as optik_hip_select_from_keys): `nearest` and `steer` of the tree planner on a tree the
+ * caller wrote, with no planner around them -- the wave code that every iteration of optik_hip_rrt_plan, _plan_goals
+ * and _plan_constrained runs (the step kernel's own nearest search and rrt_measure.hpp's steer_joint, not copies).
+ * d_conf [n][max_nodes]: node j's joint i at i * max_nodes + j, the planner's layout of one tree; only the nodes
+ * j < count are read.  d_x [n][X]: X query points, one wave each.  n and the joint limits lo, hi are the chain's;
+ * neither a model nor a world is read.  Outputs, none may be NULL:
+ *   d_index [X] int32   the node first in the total order on (distance to x, index) -- a number before a NaN, the
+ *                       smaller distance, the smaller index; never -1, since count >= 1;
+ *   d_dist [X]          that node's L-infinity distance to x (NaN if every node's is);
+ *   d_cand [n][X]       the steer from that node towards x with `step`, clamped to lo, hi -- the candidate c of an
+ *                       iteration.  Where the planner's iteration ends without a candidate, d_dist 0 (x equals the
+ *                       node), NaN or infinite, every joint of the column is NaN.
+ * Stream-ordered, no workspace, no lock.  Refused with OPTIK_HIP_EINVAL before any device work: X < 0 (X = 0 is a
+ * no-op) or above 2^30, a step that is not finite and > 0, max_nodes outside 1 .. OPTIK_HIP_RRT_MAX_NODES (a tree of
+ * one node is a tree here), count outside 1 .. max_nodes, and, where X > 0, a NULL buffer (at X = 0 no buffer is
+ * looked at and all may be NULL); with OPTIK_HIP_EUNSUPPORTED, also when X = 0, chains of more than 16 joint
+ * positions. */
+int optik_hip_rrt_nearest_from_nodes(optik_hip_chain *chain, const double *d_conf, int32_t max_nodes, int32_t count,
+                                     const double *d_x, int64_t X, double step, int32_t *d_index, double *d_dist,
+                                     double *d_cand, void *stream);
+
 /* The tree planner with a goal set (extension; the rules and their operation order:
  * csrc/rrt_goals_measure.hpp): optik_hip_rrt_plan with G goal slots per query, 1 <= G <= OPTIK_HIP_RRT_MAX_GOALS, in
  * place of the one goal -- the IK solutions of a pose, for one.  d_goals [G][n][Q]; d_gcount [Q] int32: only the goals

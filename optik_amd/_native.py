@@ -221,6 +221,9 @@ def lib():
                                                  vp, vp, vp, vp, vp]
     L.optik_hip_rrt_chunk.argtypes = [vp, C.c_int32]
     L.optik_hip_rrt_chunk.restype = C.c_int64
+    # test hook: nearest and steer on the caller's own tree (include/optik_hip.h)
+    L.optik_hip_rrt_nearest_from_nodes.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, C.c_int64, C.c_double, vp, vp, vp,
+                                                   vp]
     L.optik_hip_path_shortcut.argtypes = [vp, dp, vp, vp, C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_double,
                                           C.c_int32, vp, vp, vp, vp, vp, vp]
     L.optik_hip_path_resample.argtypes = [vp, vp, vp, C.c_int32, C.c_int64, C.c_int32, vp, vp, vp]

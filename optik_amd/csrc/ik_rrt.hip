@@ -31,6 +31,8 @@
 //                       scratch by then), walks start -> junction -> root adding the cost forwards, and the wave
 //                       writes the path; the goal slot of the root that tree 1's branch ends in is `which`, and the
 //                       path is padded with that goal.
+//   rrt_nearest_kernel  (a test hook, optik_hip_rrt_nearest_from_nodes) one wave per query point: wave_nearest and
+//                       rrt::steer_joint, the two functions of rrt_step_body, on a tree the caller wrote.
 //
 // Under a pose constraint (rrt_constrained_measure.hpp; optik_hip_rrt_plan_constrained) the
 // same planner body runs with a constraint record (RrtConstraint), which swaps one kernel and adds two:
@@ -436,6 +438,43 @@ __global__ __launch_bounds__(RRT_WAVE) void rrt_cstep_kernel(const RrtLaunch a, 
     rrt_step_body<CH>(a, &k);
 }
 
+// optik_hip_rrt_nearest_from_nodes: rules 1 and 2 on a tree the caller wrote, one wave per query point -- the step
+// body's own wave_nearest and rrt::steer_joint, with the point staged in LDS as the step stages its sample.
+struct RrtProbe {
+    const double *conf;          // [n][M] the caller's
+    const double *x;             // [n][X] the caller's
+    const double *lo, *hi;       // [n] the joint limits (the chain's table)
+    long long X;
+    int n, M, count;
+    double eta;
+    int32_t *index;              // [X]
+    double *dist;                // [X]
+    double *cand;                // [n][X]
+};
+
+__global__ __launch_bounds__(RRT_WAVE) void rrt_nearest_kernel(const RrtProbe a) {
+    __shared__ double s_x[OPTIK_HIP_MAX_DOF];
+    const long long q = blockIdx.x;
+    const int lane = threadIdx.x, n = a.n, M = a.M;
+    const bool joint = lane < n;
+    if (joint) s_x[lane] = a.x[(long long)lane * a.X + q];
+    __syncthreads();
+    double d;
+    int p;
+    wave_nearest(a.conf, n, M, a.count, s_x, lane, d, p);
+    if (lane == 0) {
+        a.index[q] = p;
+        a.dist[q] = d;
+    }
+    if (joint) {
+        // (no candidate where the step gives up: NaN)
+        const bool made = rrt::steers(d) && p >= 0;
+        a.cand[(long long)lane * a.X + q] =
+            made ? rrt::steer_joint(a.conf[(size_t)lane * M + p], s_x[lane], d, a.eta, a.lo[lane], a.hi[lane])
+                 : roadmap::nan_value();
+    }
+}
+
 __global__ __launch_bounds__(RRT_WAVE) void rrt_walk_kernel(const RrtLaunch a) {
     __shared__ int s_way[roadmap::MAX_WAYPOINTS];  // waypoint t: node v of tree 0, or M + v of tree 1
     __shared__ int s_len, s_pad;                   // s_pad: the goal slot the path is padded with, -1 for the start
@@ -712,6 +751,32 @@ int64_t optik_hip_rrt_chunk(const optik_hip_chain *ch, int32_t max_nodes) {
     if (!ch || max_nodes < 1) return 0;
     const int64_t per = 2 * (int64_t)max_nodes * (8 * (int64_t)ch->n + 4);
     return std::max<int64_t>(1, OPTIK_HIP_RRT_CHUNK_BYTES / per);
+}
+
+int optik_hip_rrt_nearest_from_nodes(optik_hip_chain *ch, const double *d_conf, int32_t max_nodes, int32_t count,
+                                     const double *d_x, int64_t X, double step, int32_t *d_index, double *d_dist,
+                                     double *d_cand, void *stream_) {
+    if (!ch || X < 0) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    if (X > MAX_QUERIES) return fail(OPTIK_HIP_EINVAL, "rrt_nearest_from_nodes: more than 2^30 points in one launch");
+    if (!(step > 0.0) || !std::isfinite(step))
+        return fail(OPTIK_HIP_EINVAL, "rrt_nearest_from_nodes: step must be finite and > 0");
+    if (max_nodes < 1 || max_nodes > rrt::MAX_NODES)
+        return fail(OPTIK_HIP_EINVAL, "rrt_nearest_from_nodes: max_nodes must be in 1 .. " + std::to_string(rrt::MAX_NODES));
+    if (count < 1 || count > max_nodes)
+        return fail(OPTIK_HIP_EINVAL, "rrt_nearest_from_nodes: count must be in 1 .. max_nodes");
+    if (ch->n < 1 || ch->n > OPTIK_HIP_MAX_DOF)
+        return fail(OPTIK_HIP_EUNSUPPORTED, "rrt_nearest_from_nodes: chains of 1 .. 16 joint positions");
+    if (X == 0) return 0;
+    if (!d_conf || !d_x || !d_index || !d_dist || !d_cand) return fail(OPTIK_HIP_EINVAL, "bad argument");
+    RrtProbe a;
+    a.conf = d_conf; a.x = d_x; a.X = X; a.n = ch->n; a.M = max_nodes; a.count = count; a.eta = step;
+    a.lo = ch->wide ? ch->wdev->lb : ch->dev->lb;
+    a.hi = ch->wide ? ch->wdev->ub : ch->dev->ub;
+    a.index = d_index; a.dist = d_dist; a.cand = d_cand;
+    BIND_DEVICE(ch);
+    hipLaunchKernelGGL(rrt_nearest_kernel, dim3((unsigned)X), dim3(RRT_WAVE), 0, (hipStream_t)stream_, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 int optik_hip_rrt_plan(optik_hip_chain *ch, const double *ee_offset7, const double *d_start, const double *d_goal,

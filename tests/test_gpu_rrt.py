@@ -202,6 +202,63 @@ def test_caps(torch_dev, wall, wall_want):
     _install(wall, model=False)
 
 
+# ---- trees past one wave, trees that fill, the Lmax border -----------------------------------------------------------
+# The wall scene at step 0.3 ends with trees of 17 and 13 nodes (23 and 22 for the pair reversed) with the host motion
+# check: no lane of the nearest search ever holds a second node.  With a step of 0.1 the same pair needs 574 iterations
+# and ends with 262 and 232 nodes and 39 waypoints on the host; with max_nodes = 70 the same growth fills tree 0 first
+# and then tree 1, and no route is found.  (Chosen on the CPU with the host motion check; the preconditions below are
+# asserted on the reference fed with the device's verdicts.)
+LARGE = dict(iters=640, step=0.1, first=tu.WALL_FIRST, max_nodes=tu.MAX_NODES)
+FILL_NODES = 70
+
+
+def test_trees_larger_than_a_wave(torch_dev, ref, wall):
+    _install(wall)
+    s, g = wall["start"][None], wall["goal"][None]
+    want = _reference(ref, wall, s, g, Lmax=64, **LARGE)
+    print("large trees: status", want["status"], "len", want["len"], "iters", want["iters"], "nodes", want["nodes"].T)
+    assert want["nodes"].max() > 128
+    _assert_parity(_device(torch_dev, wall, s, g, Lmax=64, **LARGE), want, "large trees")
+    _install(wall, model=False)
+
+
+@pytest.mark.parametrize("iters, both", [(144, False), (256, True)])
+def test_a_tree_that_fills_while_the_other_grows(torch_dev, ref, wall, iters, both):
+    """max_nodes = 70 at step 0.1.  On the host tree 0 holds 69 nodes after 130 iterations and 70 after 140, tree 1 holds
+    65 after 140, 67 after 150 and 70 after 160.  After 144 one tree is full and the other is not: the full tree's own
+    iterations give up (cnt_a >= M), the other tree's go on, and its back-extensions into the full tree are refused
+    (extends_back, and the commit's cnt_b < M).  After 256 both are full and the query ends in status 1 at the budget."""
+    _install(wall)
+    s, g = wall["start"][None], wall["goal"][None]
+    args = dict(iters=iters, step=0.1, first=tu.WALL_FIRST, max_nodes=FILL_NODES, Lmax=64)
+    want = _reference(ref, wall, s, g, **args)
+    print("fill: status", want["status"], "iters", want["iters"], "nodes", want["nodes"].T)
+    assert want["status"][0] == tu.NO_ROUTE and want["iters"][0] == iters
+    nodes = sorted(want["nodes"][:, 0].tolist())
+    assert nodes[1] == FILL_NODES and (nodes[0] == FILL_NODES if both else 2 < nodes[0] < FILL_NODES)
+    _assert_parity(_device(torch_dev, wall, s, g, **args), want, f"fill after {iters}")
+    _install(wall, model=False)
+
+
+def test_lmax_border(torch_dev, ref, wall, wall_want):
+    """found_status is W <= Lmax: Lmax = W is found with no padding row, Lmax = W - 1 is status 2 with the cost kept."""
+    _install(wall)
+    s, g = wall["start"][None], wall["goal"][None]
+    W = int(wall_want["len"][0])
+    assert wall_want["status"][0] == tu.FOUND and W >= 4
+    for Lmax, status in ((W, tu.FOUND), (W - 1, tu.TOO_LONG)):
+        want = _reference(ref, wall, s, g, Lmax=Lmax, **WALL)
+        assert want["status"][0] == status and want["len"][0] == (W if status == tu.FOUND else 2)
+        assert_bit_equal(want["cost"], wall_want["cost"][:1], "the cost is the route's either way")
+        if status == tu.FOUND:
+            assert_bit_equal(want["path"][:, 0], wall_want["path"][:W, 0], "the waypoints and nothing behind them")
+        else:
+            assert np.array_equal(want["path"][:, 0],
+                                  np.concatenate([wall["start"][None], np.tile(wall["goal"], (W - 2, 1))]))
+        _assert_parity(_device(torch_dev, wall, s, g, Lmax=Lmax, **WALL), want, f"Lmax {Lmax}")
+    _install(wall, model=False)
+
+
 def test_without_a_model_every_finite_pair_is_direct(torch_dev, wall):
     _install(wall, model=False)
     rng = np.random.default_rng(28)
@@ -226,6 +283,45 @@ def test_other_chains(torch_dev, ref, name, start, goal, box):
     want = _reference(ref, sc, s, g, **args)
     assert want["status"][0] == tu.FOUND and want["len"][0] > 2
     _assert_parity(_device(torch_dev, sc, s, g, **args), want, name)
+    _install(sc, model=False)
+
+
+def test_one_joint(torch_dev, ref):
+    """n = 1 (panda1): only lane 0 steers and writes.  One sphere of 5 cm, 0.4 m off the joint's axis on the turning
+    link, and a box where that sphere passes at q = 0: the sweep from -0.9 to 0.9 is blocked, and with one joint there is
+    no way round, so the trees grow on their own sides until the budget ends (19 and 12 nodes with the host motion
+    check).  The same start with a goal on its own side is a direct motion."""
+    sc = _scene("panda1", [[0.4, 0.0, 0.333, 0, 0, 0, 1, 0.05, 0.05, 0.05]])
+    sc["frames"], sc["centers"], sc["radii"] = np.array([1], dtype=np.int32), np.array([[0.4, 0.0, 0.0]]), np.array([0.05])
+    _install(sc)
+    starts, goals = np.array([[-0.9], [-0.9]]), np.array([[0.9], [-2.0]])
+    assert not sc["robot"].collision_motion_batch_arrays(starts[:1], goals[:1], sc["h"])[1][0]
+    args = dict(iters=64, step=0.3, first=1, max_nodes=64, Lmax=64)
+    want = _reference(ref, sc, starts, goals, **args)
+    print("panda1: status", want["status"], "iters", want["iters"], "nodes", want["nodes"].T)
+    assert want["status"].tolist() == [tu.NO_ROUTE, tu.FOUND]
+    assert want["iters"].tolist() == [64, 0] and want["nodes"][:, 0].min() > 2 and want["len"][1] == 2
+    _assert_parity(_device(torch_dev, sc, starts, goals, **args), want, "panda1")
+    _install(sc, model=False)
+
+
+# The 16-joint arm (the general kernels at their widest), the sweep of test_other_chains: the box sits where the end
+# effector passes at q0 = 0, and is small enough that both ends are free (chosen on the CPU with the host motion check,
+# which joins the trees after 4 iterations with 4 waypoints).
+ARM16 = dict(start=[-0.9] + [0.3] * 15, goal=[0.9] + [0.3] * 15,
+             box=[-0.277, -0.501, 0.043, 0, 0, 0, 1, 0.02, 0.02, 0.1])
+
+
+def test_sixteen_joints(torch_dev, ref):
+    sc = _scene("arm16", [ARM16["box"]])
+    _install(sc)
+    s, g = (np.array(ARM16[k], dtype=np.float64)[None] for k in ("start", "goal"))
+    assert not sc["robot"].collision_motion_batch_arrays(s, g, sc["h"])[1][0]
+    args = dict(iters=128, step=0.3, first=1, max_nodes=64, Lmax=64)
+    want = _reference(ref, sc, s, g, **args)
+    print("arm16: status", want["status"], "len", want["len"], "iters", want["iters"], "nodes", want["nodes"].T)
+    assert want["status"][0] == tu.FOUND and want["len"][0] > 2
+    _assert_parity(_device(torch_dev, sc, s, g, **args), want, "arm16")
     _install(sc, model=False)
 
 

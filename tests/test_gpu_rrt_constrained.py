@@ -203,6 +203,30 @@ def test_goal_sets_with_counts(torch_dev, xref, wall, upright):
     _install(wall, model=False)
 
 
+@pytest.mark.parametrize("iters, max_nodes", [(448, 4096), (142, 70), (256, 70)])
+def test_large_trees_and_full_trees(torch_dev, xref, wall, upright, iters, max_nodes):
+    """The wall pair at step 0.1 (chosen with the host build: no junction within 640 iterations, 291 and 260 nodes by
+    then; with max_nodes = 70 tree 0 holds 68 nodes after 130 iterations and 70 after 140, tree 1 holds 66 after 140 and
+    70 after 150).  Trees past 128 nodes put every lane of the nearest search through several trips.  After 142
+    iterations one tree is full while the other still grows through the commit whose guard needs cnt_a < M, the motion
+    check's flag and the constraint's ok byte; after 256 both are full and every step leaves by cnt_a >= M before it
+    projects anything, which the counters show."""
+    _install(wall)
+    starts, goals, counts = wall["start"][None], wall["goal"][None, None, :], np.ones(1, dtype=np.int32)
+    args = dict(iters=iters, step=0.1, first=xu.FIRST, max_nodes=max_nodes, Lmax=64)
+    want = _reference(xref, wall, upright, starts, goals, counts, **args, **CON)
+    print("step 0.1: status", want["status"], "iters", want["iters"], "nodes", want["nodes"].T, "projected",
+          want["projected"].T)
+    if max_nodes == 70:
+        assert want["status"][0] == tu.NO_ROUTE and want["iters"][0] == iters
+        nodes = sorted(want["nodes"][:, 0].tolist())
+        assert nodes[1] == 70 and (nodes[0] == 70 if iters == 256 else 2 < nodes[0] < 70)
+    else:
+        assert want["nodes"].max() > 128
+    _assert_parity(_device(torch_dev, wall, upright, starts, goals, counts, **args, **CON), want, f"M {max_nodes}")
+    _install(wall, model=False)
+
+
 def test_a_query_does_not_depend_on_the_batch_or_on_poll(torch_dev, wall, upright, five_want):
     _install(wall)
     starts, goals, counts = _five(wall)
@@ -299,6 +323,25 @@ def test_other_chains(torch_dev, xref, name, start, goal, box, tilt, found, ee):
     assert want["status"][0] == tu.FOUND
     assert (want["len"][0], want["iters"][0], want["nodes"][:, 0].tolist(), want["projected"][:, 0].tolist()) == found
     _assert_parity(_device(torch_dev, sc, c, s, g, counts, ee7=ee7, **args, **con), want, name)
+    _install(sc, model=False)
+
+
+def test_sixteen_joints(torch_dev, xref):
+    """The WideChainDev table at its largest, staged in LDS by the constrained step: test_gpu_rrt.py's 16-joint scene
+    under upright(fk(start), 2.0), which the goal keeps (violation 0 on the host).  Whether the trees join is left open;
+    the iterations begin, so at least one candidate is projected."""
+    from test_gpu_rrt import ARM16
+    sc = _scene("arm16", [ARM16["box"]])
+    _install(sc)
+    s = np.array(ARM16["start"], dtype=np.float64)[None]
+    g = np.array(ARM16["goal"], dtype=np.float64)[None, None, :]
+    c = _upright(sc["robot"], s[0], 2.0)
+    args, con, counts = dict(iters=32, step=0.3, first=1, max_nodes=64, Lmax=64), dict(CON, tol=0.1), np.ones(1, dtype=np.int32)
+    want = _reference(xref, sc, c, s, g, counts, **args, **con)
+    print("arm16: status", want["status"], "len", want["len"], "iters", want["iters"], "nodes", want["nodes"].T,
+          "projected", want["projected"].T)
+    assert want["projected"][0, 0] >= 1
+    _assert_parity(_device(torch_dev, sc, c, s, g, counts, **args, **con), want, "arm16")
     _install(sc, model=False)
 
 

@@ -301,6 +301,48 @@ def test_caps(torch_dev, wall, sets_want):
     _install(wall, model=False)
 
 
+def test_trees_larger_than_a_wave(torch_dev, gref, wall):
+    """test_gpu_rrt.py's large-tree case with G = 3 -- a goal in the wall, the goal, the goal moved: on the host 574
+    iterations at step 0.1, 262 and 233 nodes, 39 waypoints, goal 1."""
+    _install(wall)
+    start, goal = wall["start"], wall["goal"]
+    inside = start.copy()
+    inside[0] = 0.0
+    goals = np.stack([inside, goal, goal + np.array([0.2, 0.1, 0, 0.2, 0, 0, 0])])[None]
+    counts, args = np.array([3], dtype=np.int32), dict(iters=640, step=0.1, first=tu.WALL_FIRST, max_nodes=4096, Lmax=64)
+    want = _reference(gref, wall, start[None], goals, counts, **args)
+    print("large trees: status", want["status"], "len", want["len"], "iters", want["iters"], "nodes", want["nodes"].T,
+          "which", want["which"], "roots", want["roots"])
+    assert want["roots"][0] == 2 and want["nodes"].max() > 128
+    _assert_parity(_device(torch_dev, wall, start[None], goals, counts, **args), want, "large trees")
+    _install(wall, model=False)
+
+
+def test_duplicate_goals(torch_dev, gref, wall, sets_want):
+    """G = 16 with the slots g, g, h, g, h, ...: tree 1 begins with roots that are copies of each other, so every
+    nearest search over it meets exact ties from its first node on, and the lower index has to win each: `which` is
+    the lowest slot among equal goals.  A copy never wins a search, so it never gets a child: but for the slots, the
+    answer is that of the set (g, h), query 2 of the goal sets above."""
+    _install(wall)
+    g, h = wall["goal"], wall["goal"] + np.array([0.2, 0.1, 0, 0.2, 0, 0, 0])
+    row = np.stack([g, g] + [h if k % 2 == 0 else g for k in range(14)])
+    goals, counts = np.tile(row, (3, 1, 1)), np.array([16, 3, 1], dtype=np.int32)
+    starts = np.tile(wall["start"], (3, 1))
+    want = _reference(gref, wall, starts, goals, counts, Lmax=64, **WALL)
+    print("duplicate goals: status", want["status"], "which", want["which"], "roots", want["roots"], "iters",
+          want["iters"], "nodes", want["nodes"].T)
+    assert want["roots"].tolist() == [16, 3, 1]
+    assert (want["status"] == tu.FOUND).all() and (want["len"] > 2).all()
+    for q in range(3):
+        w = want["which"][q]
+        assert w == min(k for k in range(counts[q]) if np.array_equal(row[k], row[w])), (q, w)
+    for q in (0, 1):
+        assert want["len"][q] == sets_want["len"][2] and want["iters"][q] == sets_want["iters"][2]
+        assert_bit_equal(want["cost"][q:q + 1], sets_want["cost"][2:3], "the cost of the set (g, h)")
+    _assert_parity(_device(torch_dev, wall, starts, goals, counts, Lmax=64, **WALL), want, "duplicate goals")
+    _install(wall, model=False)
+
+
 def _pose7(m44):
     """The Python front end's reading of a 4x4 target (include/optik.h: optik_pose_from_matrix, flags 0)."""
     from optik_amd import _native as nat

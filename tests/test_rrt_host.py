@@ -163,7 +163,8 @@ def lib():
 
 
 def test_rrt_symbols_are_exported(lib):
-    for name in ("optik_hip_rrt_plan", "optik_hip_rrt_chunk", "optik_robot_rrt_plan"):
+    for name in ("optik_hip_rrt_plan", "optik_hip_rrt_chunk", "optik_robot_rrt_plan",
+                 "optik_hip_rrt_nearest_from_nodes"):
         assert hasattr(lib, name), name
 
 
