@@ -430,6 +430,17 @@ int optik_robot_path_optimize_constrained(const optik_robot *robot, int64_t P, i
                                           const double *ee_offset16, double *paths_out, double *cost_first_out,
                                           double *cost_last_out, double *clearance_out, int32_t *status_out,
                                           double *violation_out, int32_t *projected_out);
+/* Collision repair (extension; include/optik_hip.h: optik_hip_collision_repair_batch).  B rows
+ * x [B][n] row-major, each pushed out of collision on its own along the gradient of its clearance until the clearance
+ * is >= safety, with ref7, lo6, hi6 (all NULL: no box) projected back onto that pose box at ptol after every step.
+ * x_out [B][n], clearance_out, violation_out, moved_out [B], status_out [B] (0 free, 1 iters spent, 2 stuck, 3 NaN),
+ * iterations_out [B]; any output may be NULL.  rc 0, or -1: null argument, what the kernel layer refuses. */
+int optik_robot_collision_repair_batch(const optik_robot *robot, int64_t B, const double *x, double influence,
+                                       double safety, double step, int32_t iters, double max_move, const double *ref7,
+                                       const double *lo6, const double *hi6, double ptol, int32_t piters,
+                                       double damping, double project_max_step, const double *ee_offset16,
+                                       double *x_out, double *clearance_out, double *violation_out, double *moved_out,
+                                       int32_t *status_out, int32_t *iterations_out);
 /* Timing planned paths and sampling the trajectory (extension; include/optik_hip.h: optik_hip_path_time and
  * optik_hip_trajectory_sample).  paths [P][L][n] row-major with lens [P] waypoints each (NULL: L
  * each), 3 <= L <= 64 -- optik_robot_path_resample's paths_out as it is.
@@ -527,6 +538,15 @@ int optik_robot_ik_region(const optik_robot *robot, int32_t T, const double *reg
                           const double *keep_ref7, const double *keep_lo6, const double *keep_hi6, double keep_tol,
                           int32_t K, double min_dist, const double *ee_offset16, int32_t *count_out, double *x_out,
                           double *violation_out, uint64_t *idx_out, double *key_out);
+/* optik_robot_ik_region with collision repair (include/optik_hip.h: optik_hip_ik_region_repair; DESIGN.md section
+ * 5.37).  repair5 = influence, safety, step, iters, max_move (NULL: optik_robot_ik_region itself); repaired_out [T] (may
+ * be NULL): the restarts of each region that took a repaired configuration. */
+int optik_robot_ik_region_repair(const optik_robot *robot, int32_t T, const double *regions19, const double *x0,
+                                 uint64_t restarts, double tol, int32_t iters, double damping, double max_step,
+                                 int32_t mode, const double *keep_ref7, const double *keep_lo6, const double *keep_hi6,
+                                 double keep_tol, int32_t K, double min_dist, const double *repair5,
+                                 const double *ee_offset16, int32_t *count_out, double *x_out, double *violation_out,
+                                 uint64_t *idx_out, double *key_out, int32_t *repaired_out);
 int optik_robot_fk_ex(const optik_robot *robot, const double *x, const double *ee_offset16,
                       double *pose16_out);
 int optik_robot_joint_jacobian_ex(const optik_robot *robot, const double *x,

@@ -678,6 +678,51 @@ int optik_hip_path_optimize_constrained(const optik_hip_chain *chain, const doub
                                         double *d_q_out, double *d_cost_first, double *d_cost_last, double *d_clearance,
                                         int32_t *d_status, double *d_violation, int32_t *d_projected, void *stream);
 
+/* Collision repair (extension; the rules and their operation order: csrc/repair_measure.hpp on
+ * top of csrc/collision_gradient.hpp and csrc/constraint_measure.hpp).  Every column of d_x [n][B] on its own is pushed
+ * out of collision: while its clearance (optik_hip_collision_batch's number: the margin is not in it) is below `safety`
+ * it steps by `step` down the gradient of optik_hip_path_optimize's hinge of its witness rows (influence, safety),
+ * clamped to the joint limits, and -- with a pose box ref7, lo6, hi6 of optik_hip_constraint_batch -- is projected back
+ * onto the box with optik_hip_constraint_project_batch's method at ptol (piters, damping, project_max_step); at most
+ * `iters` (0 .. OPTIK_HIP_REPAIR_MAX_ITERS) steps.  ref7, lo6 and hi6 all NULL: no box (ptol .. project_max_step are
+ * then ignored).  max_move (>= 0, +inf: no bound) bounds the L-infinity distance from the input.  A fixed step without
+ * a line search; step-then-project, not a step in the constraint's null space.
+ * d_status [B]:
+ *   OPTIK_HIP_REPAIR_FREE   the returned x has clearance >= safety.  With d_iterations > 0 it also lies within the
+ *                           joint limits and satisfies the box at ptol; with d_iterations == 0 the input was free
+ *                           already and is returned bit for bit, d_moved 0
+ *   OPTIK_HIP_REPAIR_LIMIT  `iters` steps were not enough
+ *   OPTIK_HIP_REPAIR_STUCK  the gradient vanished, a projection did not end OPTIK_HIP_CONSTRAINT_PROJECTED, or the step
+ *                           would have left max_move: x is the last accepted iterate
+ *   OPTIK_HIP_REPAIR_NAN    the clearance is NaN (a NaN or infinite joint)
+ * and, of the returned x whatever the status: d_x [n][B] (may be the input buffer), d_clearance [B], d_violation [B]
+ * (optik_hip_constraint_batch's; 0.0 without a box or with a box free on all six axes), d_moved [B] (max_i |x_i -
+ * input_i|), d_iterations [B] (accepted steps).  Any output pointer may be NULL.
+ * One configuration per lane, the whole loop in one launch; stream-ordered, no workspace, no allocation; the result of
+ * a column does not depend on B or on the launch shape.  Revolute chains of 1 .. 8 joints.
+ * Refusals, before any device work and also when B = 0: OPTIK_HIP_EUNSUPPORTED for chains of 9 .. 16 joint positions
+ * and prismatic chains; OPTIK_HIP_EINVAL for parameters outside influence > safety >= 0, step > 0 (all finite), iters
+ * in 0 .. 4096, max_move >= 0; what optik_hip_constraint_project_batch refuses of a box and its projection's
+ * arguments; a chain without a collision model. */
+#define OPTIK_HIP_REPAIR_MAX_ITERS 4096
+#define OPTIK_HIP_REPAIR_FREE 0
+#define OPTIK_HIP_REPAIR_LIMIT 1
+#define OPTIK_HIP_REPAIR_STUCK 2
+#define OPTIK_HIP_REPAIR_NAN 3
+typedef struct optik_hip_collision_repair_outputs {
+    double *d_x;             /* [n][B] */
+    double *d_clearance;     /* [B] */
+    double *d_violation;     /* [B] */
+    double *d_moved;         /* [B] */
+    int32_t *d_status;       /* [B] */
+    int32_t *d_iterations;   /* [B] */
+} optik_hip_collision_repair_outputs;
+int optik_hip_collision_repair_batch(const optik_hip_chain *chain, const double *ee_offset7, const double *d_x,
+                                     int64_t B, double influence, double safety, double step, int32_t iters,
+                                     double max_move, const double *ref7, const double *lo6, const double *hi6,
+                                     double ptol, int32_t piters, double damping, double project_max_step,
+                                     const optik_hip_collision_repair_outputs *out, void *stream);
+
 /* Timing of joint paths under velocity and acceleration limits, and the sampling of the timed trajectory (extension;
  * DESIGN.md section 5.20; the arithmetic and its operation order: csrc/time_measure.hpp).  Paths are d_path [L][P][n]
  * as above, path p having d_len[p] waypoints (d_len NULL: L each), 3 <= d_len[p] <= L <= 64.  Any revolute chain of
@@ -1246,6 +1291,31 @@ int optik_hip_ik_region(optik_hip_chain *chain, const double *ee_offset7, const 
                         double damping, double max_step, int32_t mode, const double *keep_ref7, const double *keep_lo6,
                         const double *keep_hi6, double keep_tol, int32_t K, double min_dist,
                         const optik_hip_ik_region_outputs *out, void *stream);
+
+/* optik_hip_ik_region with collision repair.  repair NULL: optik_hip_ik_region itself, bit for
+ * bit and with not one launch more.  Otherwise optik_hip_collision_repair_batch's loop (influence, safety, step, iters,
+ * max_move) runs on the same stream between the region kernel and the key passes, on every column whose key is finite,
+ * with the column's own region as the box and ptol = tol (piters = iters, damping, max_step: the projection's).  A
+ * column that ends OPTIK_HIP_REPAIR_FREE after at least one step takes the repaired x and violation; its key is
+ * recomputed by the region kernel's rule from the new x (OPTIK_MODE_SPEED keeps the index, every other mode
+ * ||x - x0[t]||_2 in the same summation order) and re-measured against the keep box.  Every other column is left bit for
+ * bit, and the collision filter then drops it as before.  The manipulability / condition pass, the filter and the
+ * selection follow unchanged.  d_repaired [T] (may be NULL): the columns of each region that took a repaired x.  The
+ * per-restart d_status and d_iterations stay the projection's.
+ * Refusals as optik_hip_ik_region, and, at T = 0 too: OPTIK_HIP_EUNSUPPORTED for chains of 9 .. 16 joint positions,
+ * OPTIK_HIP_EINVAL for what optik_hip_collision_repair_batch refuses of the five parameters and for a chain without a
+ * collision model. */
+typedef struct optik_hip_region_repair {
+    double influence, safety, step, max_move;
+    int32_t iters;
+    int32_t *d_repaired;      /* [T] or NULL */
+} optik_hip_region_repair;
+int optik_hip_ik_region_repair(optik_hip_chain *chain, const double *ee_offset7, const double *d_regions,
+                               const double *d_x0, int32_t T, uint64_t restart_begin, uint64_t restart_end, double tol,
+                               int32_t iters, double damping, double max_step, int32_t mode, const double *keep_ref7,
+                               const double *keep_lo6, const double *keep_hi6, double keep_tol, int32_t K,
+                               double min_dist, const optik_hip_region_repair *repair,
+                               const optik_hip_ik_region_outputs *out, void *stream);
 
 /* Test hooks: the selection stage of the three entry points above on the caller's own per-restart arrays, with no
  * solve in front -- what optik_hip_ik_batch, optik_hip_ik_solutions and one waypoint of optik_hip_ik_path launch behind

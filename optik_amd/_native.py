@@ -190,6 +190,9 @@ def lib():
                                                       C.c_double, C.c_double, C.c_double, C.c_double, dp, dp, dp,
                                                       C.c_double, C.c_int32, C.c_double, C.c_double, vp, vp, vp, vp, vp,
                                                       vp, vp, vp]
+    L.optik_hip_collision_repair_batch.argtypes = [vp, dp, vp, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int32,
+                                                   C.c_double, dp, dp, dp, C.c_double, C.c_int32, C.c_double,
+                                                   C.c_double, vp, vp]
     L.optik_hip_roadmap_knn.argtypes = [vp, vp, C.c_int64, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]
     L.optik_hip_roadmap_edges.argtypes = [vp, dp, vp, C.c_int64, vp, C.c_int32, vp, C.c_int32, C.c_double, C.c_int32,
                                           vp, vp]
@@ -255,6 +258,9 @@ def lib():
     L.optik_hip_ik_region.argtypes = [vp, dp, vp, vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_double, C.c_int32,
                                       C.c_double, C.c_double, C.c_int32, dp, dp, dp, C.c_double, C.c_int32, C.c_double,
                                       C.POINTER(IkRegionOutputs), vp]
+    L.optik_hip_ik_region_repair.argtypes = [vp, dp, vp, vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_double, C.c_int32,
+                                             C.c_double, C.c_double, C.c_int32, dp, dp, dp, C.c_double, C.c_int32,
+                                             C.c_double, vp, C.POINTER(IkRegionOutputs), vp]
     # test hooks: the selection stages on the caller's own keys (include/optik_hip.h)
     L.optik_hip_select_from_keys.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(IkOutputs), vp]
     L.optik_hip_solutions_from_keys.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32,
@@ -389,6 +395,48 @@ PATH_OPTIMIZE_MAX_WAYPOINTS = 64  # include/optik_hip.h: OPTIK_HIP_PATH_OPTIMIZE
 # The values with which the host reference (csrc/path_optimize.hpp under g++) clears the L = 16 scene of
 # tests/test_path_optimize_host.py: that and nothing more.
 PATH_OPTIMIZE_ITERS, PATH_OPTIMIZE_STEP, PATH_OPTIMIZE_W_SMOOTH, PATH_OPTIMIZE_W_OBS = 100, 0.05, 1.0, 1.0
+
+
+# include/optik_hip.h: OPTIK_HIP_REPAIR_MAX_ITERS and the statuses of optik_hip_collision_repair_batch
+REPAIR_MAX_ITERS = 4096
+REPAIR_FREE, REPAIR_LIMIT, REPAIR_STUCK, REPAIR_NAN = 0, 1, 2, 3
+# The values with which the host reference (csrc/repair_measure.hpp) clears the scene of examples/ik_repair.py: its
+# start state in 2 steps and 9 in 10 of the colliding configurations of its cell (177 steps at the 90th percentile);
+# a quarter of the budget frees fewer than half of them (tests/test_repair_host.py asserts both).  That and nothing more.
+REPAIR_STEP, REPAIR_ITERS = 0.05, 256
+
+
+class RepairOutputs(C.Structure):
+    """optik_hip_collision_repair_outputs (include/optik_hip.h)."""
+    _fields_ = [(k, C.c_void_p) for k in ("d_x", "d_clearance", "d_violation", "d_moved", "d_status", "d_iterations")]
+
+
+class RegionRepair(C.Structure):
+    """optik_hip_region_repair (include/optik_hip.h)."""
+    _fields_ = [("influence", C.c_double), ("safety", C.c_double), ("step", C.c_double), ("max_move", C.c_double),
+                ("iters", C.c_int32), ("d_repaired", C.c_void_p)]
+
+
+def region_repair_args(repair):
+    """ik_region's repair=dict(influence, safety, step=REPAIR_STEP, iters=REPAIR_ITERS, max_move=inf), checked:
+    (influence, safety, step, iters, max_move).  ValueError for another key, a missing one or a bad value."""
+    if not isinstance(repair, dict) or set(repair) - {"influence", "safety", "step", "iters", "max_move"} \
+            or not {"influence", "safety"} <= set(repair):
+        raise ValueError("repair must be a dict with influence and safety, and optionally step, iters and max_move")
+    return check_repair_args(repair["influence"], repair["safety"], repair.get("step", REPAIR_STEP),
+                             repair.get("iters", REPAIR_ITERS), repair.get("max_move", math.inf))
+
+
+def check_repair_args(influence, safety, step, iters, max_move):
+    """The argument rules of optik_hip_collision_repair_batch, checked on the host."""
+    if isinstance(iters, bool) or int(iters) != iters or not 0 <= int(iters) <= REPAIR_MAX_ITERS:
+        raise ValueError(f"iters must be an integer in 0 .. {REPAIR_MAX_ITERS}, got {iters!r}")
+    influence, safety, step, max_move = float(influence), float(safety), float(step), float(max_move)
+    if not (math.isfinite(influence) and math.isfinite(step) and influence > safety >= 0.0 and step > 0.0):
+        raise ValueError("collision_repair: needs influence > safety >= 0 and step > 0, all finite")
+    if not max_move >= 0.0:
+        raise ValueError(f"max_move must be >= 0 (inf: no bound), got {max_move!r}")
+    return influence, safety, step, int(iters), max_move
 
 
 def check_path_optimize_args(L, iters, step, w_smooth, w_obs, influence, safety):

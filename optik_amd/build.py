@@ -18,7 +18,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "liboptik_amd.so")
-SOURCES = ["ik_capi.hip", "ik_select.hip", "ik_solutions.hip", "ik_path.hip", "ik_manip.hip", "ik_collision.hip", "ik_motion.hip", "ik_constraint.hip", "ik_region.hip", "ik_advance.hip", "ik_avoid.hip", "ik_path_optimize.hip", "ik_roadmap.hip", "ik_roadmap_lazy.hip", "ik_roadmap_goals.hip", "ik_roadmap_goals_lazy.hip", "ik_rrt.hip", "ik_shortcut.hip", "ik_time.hip", "ik_occupancy.hip", "ik_depth.hip", "ik_mesh.hip", "ik_spherefit.hip", "ik_batch_ops.hip", "ik_quad_kernel.hip", "ik_lane_kernel.hip", "ik_wide_kernel.hip",
+SOURCES = ["ik_capi.hip", "ik_select.hip", "ik_solutions.hip", "ik_path.hip", "ik_manip.hip", "ik_collision.hip", "ik_motion.hip", "ik_constraint.hip", "ik_region.hip", "ik_advance.hip", "ik_avoid.hip", "ik_path_optimize.hip", "ik_repair.hip", "ik_roadmap.hip", "ik_roadmap_lazy.hip", "ik_roadmap_goals.hip", "ik_roadmap_goals_lazy.hip", "ik_rrt.hip", "ik_shortcut.hip", "ik_time.hip", "ik_occupancy.hip", "ik_depth.hip", "ik_mesh.hip", "ik_spherefit.hip", "ik_batch_ops.hip", "ik_quad_kernel.hip", "ik_lane_kernel.hip", "ik_wide_kernel.hip",
            "robot_host.cpp", "robot_rows.cpp", "robot_constraint.cpp"]
 # translation units: (source, object, extra flags).  ik_quad_kernel.hip is compiled twice -- its
 # throughput form (two waves per SIMD) without the machine-LICM pass, which otherwise hoists constants and
@@ -36,6 +36,7 @@ UNITS = [("ik_capi.hip", "ik_capi.o", []),          # chains, options, the resta
          ("ik_advance.hip", "ik_advance.o", []),    # certified motion check: conservative advancement, a wave per segment
          ("ik_avoid.hip", "ik_avoid.o", []),        # clearance witnesses and gradients, diff_ik with velocity dampers
          ("ik_path_optimize.hip", "ik_path_optimize.o", []),  # covariant gradient smoothing of joint paths
+         ("ik_repair.hip", "ik_repair.o", []),      # collision repair: configurations pushed free, a pose box kept
          ("ik_roadmap.hip", "ik_roadmap.o", []),    # roadmap planning: nearest neighbours, checked edges, path queries
          ("ik_roadmap_lazy.hip", "ik_roadmap_lazy.o", []),  # lazy roadmaps: edges checked when a route uses them
          ("ik_roadmap_goals.hip", "ik_roadmap_goals.o", []),  # goal-set planning: routes to the nearest of several goals

@@ -13,6 +13,7 @@
 // (ik_collision.hip) and the selection of ik_solutions.hip, in the order ik_capi.hip runs them behind its solver.
 #include "constraint_device.hpp"
 #include "region_measure.hpp"
+#include "repair_device.hpp"
 
 using namespace optik;
 using namespace optik::host;
@@ -62,15 +63,12 @@ __global__ __launch_bounds__(256) void ik_region_kernel(const RegionLaunch a) {
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-int optik_hip_ik_region(optik_hip_chain *ch, const double *ee_offset7, const double *d_regions, const double *d_x0,
-                        int32_t T, uint64_t restart_begin, uint64_t restart_end, double tol, int32_t iters,
-                        double damping, double max_step, int32_t mode, const double *keep_ref7, const double *keep_lo6,
-                        const double *keep_hi6, double keep_tol, int32_t K, double min_dist,
-                        const optik_hip_ik_region_outputs *out, void *stream_v) {
+// The one body of optik_hip_ik_region (rep null: not one launch more) and optik_hip_ik_region_repair.
+int region_body(optik_hip_chain *ch, const double *ee_offset7, const double *d_regions, const double *d_x0, int32_t T,
+                uint64_t restart_begin, uint64_t restart_end, double tol, int32_t iters, double damping, double max_step,
+                int32_t mode, const double *keep_ref7, const double *keep_lo6, const double *keep_hi6, double keep_tol,
+                int32_t K, double min_dist, const optik_hip_region_repair *rep, const optik_hip_ik_region_outputs *out,
+                void *stream_v) {
     if (!ch || !out || T < 0) return fail(OPTIK_HIP_EINVAL, "bad argument");
     if (restart_end <= restart_begin) return fail(OPTIK_HIP_EINVAL, "empty restart range");
     if (mode < OPTIK_MODE_QUALITY || mode > OPTIK_MODE_CONDITION)
@@ -97,6 +95,8 @@ int optik_hip_ik_region(optik_hip_chain *ch, const double *ee_offset7, const dou
             if (std::isnan(ch->scale[k]))
             return fail(OPTIK_HIP_EINVAL, "random restarts need finite joint limits (reference: random_range panics)");
     if (ch->prismatic) return fail(OPTIK_HIP_EUNSUPPORTED, colldev::prismatic_msg());
+    if (rep)
+        if (int rc = repairdev::check_region_repair(ch, rep)) return rc;
     if (T == 0) return 0;
     if (!d_regions || !d_x0) return fail(OPTIK_HIP_EINVAL, "bad argument");
 
@@ -142,6 +142,11 @@ int optik_hip_ik_region(optik_hip_chain *ch, const double *ee_offset7, const dou
     a.status = out->d_status; a.iterations = out->d_iterations;
     const int grid = grid_for(ch, (long long)cols, 256, 8);
     CONSTRAINT_LAUNCH(ik_region_kernel, ch, grid, 256, stream, a);
+    // the repair pass: between the region kernel and the key passes, on the same stream
+    if (rep)
+        if (int rc = repairdev::region_repair_launch(ch, ee_offset7, rep, d_regions, d_x0, T, R, cols, mode, a.p, a.d.c,
+                                                     a.keep_on, a.keep_tol, px, pv, pk, stream))
+            return rc;
     // the key passes, in ik_capi.hip's order: modes 3 and 4, then the collision filter
     if (manip)
         if (int rc = manip_key_launch(ch, mode, ee_offset7, px, pk, cols, stream)) return rc;
@@ -160,6 +165,29 @@ int optik_hip_ik_region(optik_hip_chain *ch, const double *ee_offset7, const dou
         HIP_TRY(solutions_launch(make_solutions_launch(ch, in, K, min_dist, &so, nullptr), T, stream));
     }
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int optik_hip_ik_region(optik_hip_chain *ch, const double *ee_offset7, const double *d_regions, const double *d_x0,
+                        int32_t T, uint64_t restart_begin, uint64_t restart_end, double tol, int32_t iters,
+                        double damping, double max_step, int32_t mode, const double *keep_ref7, const double *keep_lo6,
+                        const double *keep_hi6, double keep_tol, int32_t K, double min_dist,
+                        const optik_hip_ik_region_outputs *out, void *stream_v) {
+    return region_body(ch, ee_offset7, d_regions, d_x0, T, restart_begin, restart_end, tol, iters, damping, max_step,
+                       mode, keep_ref7, keep_lo6, keep_hi6, keep_tol, K, min_dist, nullptr, out, stream_v);
+}
+
+int optik_hip_ik_region_repair(optik_hip_chain *ch, const double *ee_offset7, const double *d_regions,
+                               const double *d_x0, int32_t T, uint64_t restart_begin, uint64_t restart_end, double tol,
+                               int32_t iters, double damping, double max_step, int32_t mode, const double *keep_ref7,
+                               const double *keep_lo6, const double *keep_hi6, double keep_tol, int32_t K,
+                               double min_dist, const optik_hip_region_repair *repair,
+                               const optik_hip_ik_region_outputs *out, void *stream_v) {
+    return region_body(ch, ee_offset7, d_regions, d_x0, T, restart_begin, restart_end, tol, iters, damping, max_step,
+                       mode, keep_ref7, keep_lo6, keep_hi6, keep_tol, K, min_dist, repair, out, stream_v);
 }
 
 }  // extern "C"

@@ -708,6 +708,55 @@ int optik_robot_path_optimize_constrained(const optik_robot *r, int64_t P, int32
         });
 }
 
+// B rows through optik_hip_collision_repair_batch.
+int optik_robot_collision_repair_batch(const optik_robot *r, int64_t B, const double *x, double influence,
+                                       double safety, double step, int32_t iters, double max_move, const double *ref7,
+                                       const double *lo6, const double *hi6, double ptol, int32_t piters,
+                                       double damping, double project_max_step, const double *ee16, double *x_out,
+                                       double *clearance_out, double *violation_out, double *moved_out,
+                                       int32_t *status_out, int32_t *iterations_out) {
+    if (!r) return set_err(-1, "null argument");
+    if (B < 0) return set_err(-1, "bad argument");
+    DeviceCtx *c = device_ctx(r);
+    if (!c) return -1;
+    // (B = 0: the kernel layer's refusals of the chain, the parameters, the box and the missing model)
+    if (optik_hip_collision_repair_batch(c->chain, nullptr, nullptr, 0, influence, safety, step, iters, max_move, ref7,
+                                         lo6, hi6, ptol, piters, damping, project_max_step, nullptr, nullptr))
+        return set_err(-1, optik_hip_last_error());
+    if (B == 0 || (!x_out && !clearance_out && !violation_out && !moved_out && !status_out && !iterations_out)) return 0;
+    if (!x) return set_err(-1, "null argument");
+    double ee7[7];
+    if (ee16) pose7_from_mat16(ee16, ee7);
+    const size_t n = (size_t)r->n;
+    // per row: x n doubles in; x n | clearance, violation, moved 3 doubles, then the status and iteration words in one
+    // more double out
+    const RowInput in[] = {{x, n}};
+    return stage_rows(
+        c, B, in, sizeof(double) * (n + 4), kRowChunk,
+        [&](optik_hip_chain *ch, const double *d_q, int64_t L, double *d_x) {
+            double *d_c = d_x + n * (size_t)L;
+            int32_t *d_st = reinterpret_cast<int32_t *>(d_c + 3 * (size_t)L);
+            const optik_hip_collision_repair_outputs o{d_x, d_c, d_c + L, d_c + 2 * (size_t)L, d_st, d_st + L};
+            return optik_hip_collision_repair_batch(ch, ee16 ? ee7 : nullptr, d_q, L, influence, safety, step, iters,
+                                                    max_move, ref7, lo6, hi6, ptol, piters, damping, project_max_step,
+                                                    &o, nullptr);
+        },
+        [&](size_t b0, size_t L, const double *h_x) {
+            const double *h_c = h_x + n * L;
+            const int32_t *h_st = reinterpret_cast<const int32_t *>(h_c + 3 * L);
+            if (x_out)
+                parallel_ranges(L, [&](size_t k0, size_t k1) {
+                    for (size_t k = k0; k < k1; ++k)
+                        for (size_t i = 0; i < n; ++i) x_out[(b0 + k) * n + i] = h_x[i * L + k];
+                });
+            if (clearance_out) std::memcpy(clearance_out + b0, h_c, sizeof(double) * L);
+            if (violation_out) std::memcpy(violation_out + b0, h_c + L, sizeof(double) * L);
+            if (moved_out) std::memcpy(moved_out + b0, h_c + 2 * L, sizeof(double) * L);
+            if (status_out) std::memcpy(status_out + b0, h_st, sizeof(int32_t) * L);
+            if (iterations_out) std::memcpy(iterations_out + b0, h_st + L, sizeof(int32_t) * L);
+        });
+}
+
 // P paths through optik_hip_path_shortcut, staged as optik_robot_path_optimize stages its paths.
 int optik_robot_path_shortcut(const optik_robot *r, int64_t P, int32_t L, const double *paths, const int32_t *lens,
                               int32_t vertices, double resolution, double hop_penalty, int32_t Lout,
@@ -1771,6 +1820,18 @@ int optik_robot_ik_region(const optik_robot *r, int32_t T, const double *regions
                           const double *keep_ref7, const double *keep_lo6, const double *keep_hi6, double keep_tol,
                           int32_t K, double min_dist, const double *ee16, int32_t *count_out, double *x_out,
                           double *violation_out, uint64_t *idx_out, double *key_out) {
+    return optik_robot_ik_region_repair(r, T, regions19, x0, restarts, tol, iters, damping, max_step, mode, keep_ref7,
+                                        keep_lo6, keep_hi6, keep_tol, K, min_dist, nullptr, ee16, count_out, x_out,
+                                        violation_out, idx_out, key_out, nullptr);
+}
+
+// The one body of both: repair5 = influence, safety, step, iters, max_move (null: optik_robot_ik_region).
+int optik_robot_ik_region_repair(const optik_robot *r, int32_t T, const double *regions19, const double *x0,
+                                 uint64_t restarts, double tol, int32_t iters, double damping, double max_step,
+                                 int32_t mode, const double *keep_ref7, const double *keep_lo6, const double *keep_hi6,
+                                 double keep_tol, int32_t K, double min_dist, const double *repair5, const double *ee16,
+                                 int32_t *count_out, double *x_out, double *violation_out, uint64_t *idx_out,
+                                 double *key_out, int32_t *repaired_out) {
     if (!r || T < 0 || (T > 0 && (!regions19 || !x0))) return set_err(-1, "null argument");
     if (restarts < 1 || restarts > ((uint64_t)1 << 22))
         return set_err(-1, "ik_region: restarts must be in 1 .. 2^22 (every restart index in [0, restarts) runs)");
@@ -1778,9 +1839,18 @@ int optik_robot_ik_region(const optik_robot *r, int32_t T, const double *regions
     if (!c) return -1;
     optik_hip_ik_region_outputs o;
     std::memset(&o, 0, sizeof o);
+    optik_hip_region_repair rep;
+    std::memset(&rep, 0, sizeof rep);
+    if (repair5) {
+        if (!(repair5[3] >= 0.0 && repair5[3] <= 4096.0 && repair5[3] == (double)(int32_t)repair5[3]))
+            return set_err(-1, "ik_region: repair iters must be an integer in 0 .. 4096");
+        rep.influence = repair5[0]; rep.safety = repair5[1]; rep.step = repair5[2];
+        rep.iters = (int32_t)repair5[3]; rep.max_move = repair5[4];
+    }
+    const optik_hip_region_repair *prep = repair5 ? &rep : nullptr;
     // (T = 0: the kernel layer's refusals, before anything is staged)
-    if (optik_hip_ik_region(c->chain, nullptr, nullptr, nullptr, 0, 0, restarts, tol, iters, damping, max_step, mode,
-                            keep_ref7, keep_lo6, keep_hi6, keep_tol, K, min_dist, &o, nullptr))
+    if (optik_hip_ik_region_repair(c->chain, nullptr, nullptr, nullptr, 0, 0, restarts, tol, iters, damping, max_step,
+                                   mode, keep_ref7, keep_lo6, keep_hi6, keep_tol, K, min_dist, prep, &o, nullptr))
         return set_err(-1, optik_hip_last_error());
     for (int64_t t = 0; t < T; ++t)
         if (int rc = check_region_row(t, regions19 + (size_t)t * OPTIK_HIP_REGION_DOUBLES)) return rc;
@@ -1789,11 +1859,12 @@ int optik_robot_ik_region(const optik_robot *r, int32_t T, const double *regions
     if (ee16) pose7_from_mat16(ee16, ee7);
     const size_t n = (size_t)r->n, W = OPTIK_HIP_REGION_DOUBLES;
     // chunks of whole regions, about 4 M (region, restart) items a launch at most (as optik_robot_ik_solutions).  The
-    // robot's batch block: in = regions [C][19] | x0 [C][n]; out = x [C][K][n] | violation, key, idx [C][K] | count [C]
+    // robot's batch block: in = regions [C][19] | x0 [C][n]; out = x [C][K][n] | violation, key, idx [C][K] | count [C] |
+    // repaired [C]
     const size_t chunk = (size_t)std::min<uint64_t>((uint64_t)T, std::max<uint64_t>(1, ((uint64_t)4 << 20) / restarts));
     BatchGuard guard(c);
     if (!guard.ok()) return set_err(-1, kSetDeviceMsg);
-    if (!reserve_batch(c, (W + n) * chunk + (size_t)K * chunk * (n + 3) + chunk)) return set_err(-1, kBatchAllocMsg);
+    if (!reserve_batch(c, (W + n) * chunk + (size_t)K * chunk * (n + 3) + 2 * chunk)) return set_err(-1, kBatchAllocMsg);
     for (size_t t0 = 0; t0 < (size_t)T; t0 += chunk) {
         const size_t L = std::min(chunk, (size_t)T - t0), KL = (size_t)K * L, n_in = (W + n) * L;
         double *h_in = c->h_batch.get(), *h_out = h_in + n_in;
@@ -1805,11 +1876,13 @@ int optik_robot_ik_region(const optik_robot *r, int32_t T, const double *regions
         if (hipMemcpyAsync(d_in, h_in, sizeof(double) * n_in, hipMemcpyHostToDevice, nullptr) != hipSuccess)
             return set_err(-1, "upload failed");
         o.d_count = d_count; o.d_sol_x = d_x; o.d_sol_violation = d_v; o.d_sol_idx = d_idx; o.d_sol_key = d_key;
-        if (optik_hip_ik_region(c->chain, ee16 ? ee7 : nullptr, d_in, d_in + W * L, (int32_t)L, 0, restarts, tol, iters,
-                                damping, max_step, mode, keep_ref7, keep_lo6, keep_hi6, keep_tol, K, min_dist, &o,
-                                nullptr))
+        rep.d_repaired = d_count + L;
+        if (optik_hip_ik_region_repair(c->chain, ee16 ? ee7 : nullptr, d_in, d_in + W * L, (int32_t)L, 0, restarts, tol,
+                                       iters, damping, max_step, mode, keep_ref7, keep_lo6, keep_hi6, keep_tol, K,
+                                       min_dist, prep, &o, nullptr))
             return set_err(-1, optik_hip_last_error());
-        if (hipMemcpyAsync(h_out, d_x, sizeof(double) * (KL * (n + 3) + L), hipMemcpyDeviceToHost, nullptr) != hipSuccess
+        if (hipMemcpyAsync(h_out, d_x, sizeof(double) * (KL * (n + 3) + (prep ? 2 * L : L)), hipMemcpyDeviceToHost, nullptr)
+                != hipSuccess
             || hipStreamSynchronize(nullptr) != hipSuccess)
             return set_err(-1, "download failed");
         const double *hx = h_out, *hv = hx + KL * n, *hk = hv + KL;
@@ -1820,6 +1893,10 @@ int optik_robot_ik_region(const optik_robot *r, int32_t T, const double *regions
         if (key_out) std::memcpy(key_out + t0 * (size_t)K, hk, sizeof(double) * KL);
         if (idx_out) std::memcpy(idx_out + t0 * (size_t)K, hi, sizeof(uint64_t) * KL);
         if (count_out) std::memcpy(count_out + t0, hc, sizeof(int32_t) * L);
+        if (repaired_out) {
+            if (prep) std::memcpy(repaired_out + t0, hc + L, sizeof(int32_t) * L);
+            else std::memset(repaired_out + t0, 0, sizeof(int32_t) * L);
+        }
     }
     return 0;
 }

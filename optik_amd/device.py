@@ -544,6 +544,52 @@ class HipChain:
             _ptr(res["violation"]), _ptr(res["projected"]), _stream_ptr()))
         return res
 
+    # -- collision repair (include/optik_hip.h) -------------------------------------------
+    def collision_repair_batch(self, q, influence, safety, step=nat.REPAIR_STEP, iters=nat.REPAIR_ITERS, c=None,
+                               max_move=math.inf, ptol=nat.CONSTRAINT_TOL, piters=nat.CONSTRAINT_ITERS,
+                               damping=nat.CONSTRAINT_DAMPING, max_step=nat.CONSTRAINT_MAX_STEP, ee_offset7=None,
+                               out=None):
+        """Every column of q [n, B] pushed out of collision on its own (optik_hip_collision_repair_batch;
+        csrc/repair_measure.hpp): steps of `step` down the gradient of path_optimize's hinge (influence, safety) of
+        the column's witness rows, clamped to the joint limits, until its clearance is >= safety or `iters` steps are
+        spent; with the pose constraint c every step is projected back onto c (constraint_project_batch's method at
+        ptol, piters, damping, max_step).  max_move bounds the L-infinity distance from the input.  `out`: the
+        tensor that receives the configurations (q itself: in place; default: a new one).  Returns a dict of device
+        tensors: x [n, B], clearance [B], violation [B] (0 without c), moved [B], status [B] int32 (nat.REPAIR_FREE,
+        REPAIR_LIMIT, REPAIR_STUCK, REPAIR_NAN) and iterations [B] int32.  A column that was free already comes back
+        bit for bit with 0 iterations.  Stream-ordered."""
+        B = self._check_q(q)
+        influence, safety, step, iters, max_move = nat.check_repair_args(influence, safety, step, iters, max_move)
+        box = (None, None, None)
+        if c is not None:
+            box = _box_ptrs(checked_constraint_arrays(c))
+            ptol, piters, damping, max_step = nat.check_project_args(ptol, piters, damping, max_step)
+        if out is None:
+            out = torch.empty_like(q)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous()
+                  and out.shape == q.shape and out.device == q.device):
+            raise ValueError("out must be a contiguous float64 cuda tensor of q's shape and device")
+        ee = self._ee7(ee_offset7)
+        res = dict(x=out, clearance=torch.empty(B, dtype=torch.float64, device=q.device),
+                   violation=torch.empty(B, dtype=torch.float64, device=q.device),
+                   moved=torch.empty(B, dtype=torch.float64, device=q.device),
+                   status=torch.empty(B, dtype=torch.int32, device=q.device),
+                   iterations=torch.empty(B, dtype=torch.int32, device=q.device))
+        return self.collision_repair_into(q, influence, safety, step, iters, max_move, box, ptol, piters, damping,
+                                          max_step, ee, res)
+
+    def collision_repair_into(self, q, influence, safety, step, iters, max_move, box, ptol, piters, damping, max_step,
+                              ee, res):
+        """collision_repair_batch's call into the caller's tensors (`res`: the dict it returns, an entry None: that
+        output is not wanted); the arguments as the C entry takes them, box = three pointers or Nones."""
+        o = nat.RepairOutputs(*(res[k].data_ptr() if res.get(k) is not None else None
+                                for k in ("x", "clearance", "violation", "moved", "status", "iterations")))
+        nat.check(nat.lib().optik_hip_collision_repair_batch(
+            self._h, _dpn(ee), _ptr(q), int(q.shape[1]), float(influence), float(safety), float(step), int(iters),
+            float(max_move), *box, float(ptol), int(piters), float(damping), float(max_step), C.byref(o),
+            _stream_ptr()))
+        return res
+
     # -- roadmap planning (include/optik_hip.h; DESIGN.md section 5.18) -------------------------------------------
     def _check_slots(self, t, Q, name, dtype):
         if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.dim() == 2 and t.shape[1] == Q
@@ -1485,7 +1531,7 @@ class HipChain:
     # -- IK into pose regions (include/optik_hip.h) ----------------------------------------
     def ik_region(self, regions, x0, restart_begin, restart_end, k, min_dist, tol=nat.CONSTRAINT_TOL,
                   iters=nat.CONSTRAINT_ITERS, damping=nat.CONSTRAINT_DAMPING, max_step=nat.CONSTRAINT_MAX_STEP,
-                  mode="quality", keep=None, ee_offset7=None, per_restart=False):
+                  mode="quality", keep=None, ee_offset7=None, per_restart=False, repair=None):
         """Up to k distinct configurations per pose region (optik_hip_ik_region; csrc/region_measure.hpp): regions
         [T, 19] (per row ref7, lo, hi -- optik_amd.constraint.region_rows makes it; device data, not validated here:
         a NaN in a row's reference gives it count 0) and x0 [T, n], float64 cuda tensors.  Restart i of [restart_begin,
@@ -1496,8 +1542,16 @@ class HipChain:
         tol), and kept if their largest joint difference to every row kept before is > min_dist.  Stream-ordered;
         returns a dict of device tensors: count [T] int32, x [T, k, n] (NaN past count), violation [T, k] (NaN), idx
         [T, k] int64 (-1), key [T, k] (+inf); with per_restart also restart_x [n, T * R], restart_violation,
-        restart_key [T * R], restart_status, restart_iterations [T * R] int32 (column t * R + i - restart_begin)."""
+        restart_key [T * R], restart_status, restart_iterations [T * R] int32 (column t * R + i - restart_begin).
+        repair = dict(influence, safety, step, iters, max_move) (optik_hip_ik_region_repair):
+        between the projection and the key passes every projected restart that is in collision is pushed free by
+        collision_repair_batch's loop under its own region at tol; one that ends free takes the repaired x, violation
+        and key, every other one is left as it was and is dropped by the collision filter as before.  The dict then
+        also has "repaired" [T] int32, the restarts of each region that took a repaired x.  repair=None is the call
+        without the argument, bit for bit and with not one launch more: the dict then has no "repaired" (a tensor of
+        zeros would be a fill on the stream)."""
         k, min_dist = nat.check_solutions_args(k, min_dist)
+        rp = nat.region_repair_args(repair) if repair is not None else None
         tol, iters, damping, max_step = nat.check_project_args(tol, iters, damping, max_step)
         mode = nat.solution_mode_code(mode) if isinstance(mode, str) else int(mode)
         kp = keep_arrays(keep)
@@ -1530,10 +1584,15 @@ class HipChain:
         o.d_count, o.d_sol_x, o.d_sol_violation = _ptr(res["count"]), _ptr(res["x"]), _ptr(res["violation"])
         o.d_sol_idx, o.d_sol_key = _ptr(res["idx"]), _ptr(res["key"])
         ee = self._ee7(ee_offset7)
-        nat.check(nat.lib().optik_hip_ik_region(
-            self._h, _dpn(ee), _ptr(regions), _ptr(x0), T, b, e, tol, iters, damping,
-            max_step, mode, _dp(kp[0]) if kp else None, _dp(kp[1]) if kp else None, _dp(kp[2]) if kp else None,
-            kp[3] if kp else 0.0, k, min_dist, C.byref(o), _stream_ptr()))
+        head = (self._h, _dpn(ee), _ptr(regions), _ptr(x0), T, b, e, tol, iters, damping, max_step, mode,
+                _dp(kp[0]) if kp else None, _dp(kp[1]) if kp else None, _dp(kp[2]) if kp else None,
+                kp[3] if kp else 0.0, k, min_dist)
+        if rp is None:
+            nat.check(nat.lib().optik_hip_ik_region(*head, C.byref(o), _stream_ptr()))
+            return res
+        res["repaired"] = torch.empty(T, dtype=torch.int32, device=dev)
+        rs = nat.RegionRepair(rp[0], rp[1], rp[2], rp[4], rp[3], res["repaired"].data_ptr())
+        nat.check(nat.lib().optik_hip_ik_region_repair(*head, C.byref(rs), C.byref(o), _stream_ptr()))
         return res
 
     def _region_goals(self, regions, starts, restart_begin, restart_end, K, min_dist, region_args):

@@ -70,6 +70,9 @@ def _bind(L):
     L.optik_robot_ik_region.argtypes = [vp, C.c_int32, dp, dp, C.c_uint64, C.c_double, C.c_int32, C.c_double, C.c_double,
                                         C.c_int32, dp, dp, dp, C.c_double, C.c_int32, C.c_double, dp, ip, dp, dp,
                                         C.POINTER(C.c_uint64), dp]
+    L.optik_robot_ik_region_repair.argtypes = [vp, C.c_int32, dp, dp, C.c_uint64, C.c_double, C.c_int32, C.c_double,
+                                               C.c_double, C.c_int32, dp, dp, dp, C.c_double, C.c_int32, C.c_double, dp,
+                                               dp, ip, dp, dp, C.POINTER(C.c_uint64), dp, ip]
     L.optik_robot_constraint_motion_batch.argtypes = [vp, C.c_int64, dp, dp, C.c_double, dp, dp, dp, C.c_double, dp,
                                                       dp, C.POINTER(C.c_uint8), ip, ip]
     L.optik_robot_collision_motion_certify_batch.argtypes = [vp, C.c_int64, dp, dp, C.c_double, C.c_double, C.c_int32,
@@ -112,6 +115,9 @@ def _bind(L):
     L.optik_robot_path_optimize_constrained.argtypes = [vp, C.c_int64, C.c_int32, dp, C.c_int32, C.c_double, C.c_double,
                                                         C.c_double, C.c_double, C.c_double, dp, dp, dp, C.c_double,
                                                         C.c_int32, C.c_double, C.c_double, dp, dp, dp, dp, dp, ip, dp, ip]
+    L.optik_robot_collision_repair_batch.argtypes = [vp, C.c_int64, dp, C.c_double, C.c_double, C.c_double, C.c_int32,
+                                                     C.c_double, dp, dp, dp, C.c_double, C.c_int32, C.c_double,
+                                                     C.c_double, dp, dp, dp, dp, dp, ip, ip]
     L.optik_robot_path_time.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, dp, dp, dp, dp, dp, dp, ip]
     L.optik_robot_trajectory_sample.argtypes = [vp, C.c_int64, C.c_int32, dp, ip, dp, dp, ip, C.c_double, C.c_int32, dp,
                                                 dp]
@@ -1882,7 +1888,7 @@ class Robot:
     def ik_region_batch_arrays(self, config: SolverConfig, regions, x0s, k=8, min_dist=0.1,
                                restarts=nat.REGION_RESTARTS, tol=nat.CONSTRAINT_TOL, iters=nat.CONSTRAINT_ITERS,
                                damping=nat.CONSTRAINT_DAMPING, max_step=nat.CONSTRAINT_MAX_STEP, keep=None,
-                               ee_offset=None):
+                               ee_offset=None, repair=None):
         """Up to k distinct configurations per pose REGION: ik_solutions_batch_arrays whose target is a box on the
         pose error (optik_amd.PoseConstraint -- position_only, axis_free, around, upright or any box) instead of an
         exact pose.  regions: one PoseConstraint, broadcast over the rows of x0s [T, n], or a sequence of T.  Every
@@ -1898,7 +1904,13 @@ class Robot:
         is collision-free under a model, and is more than min_dist from the rows before it.  Gauss-Newton from a seed
         is not the SLSQP solver of ik(): it may miss what ik() finds on a pinned region, and nothing is promised
         about how the rows cover the region's solution manifold.  ValueError for a bad region (naming the row), k,
-        min_dist, restarts, keep or projection argument."""
+        min_dist, restarts, keep or projection argument.
+        repair = dict(influence, safety, step=.., iters=.., max_move=inf) (repair_configurations' parameters; DESIGN.md
+        section 5.37): with a collision model, a restart that projected but is in collision is not thrown away at once:
+        it is first pushed free under its own region at tol, and takes part in the ranking with its repaired x if that
+        ends free (re-measured against keep).  The dict then also has repaired [T] int32, the restarts of each region
+        that took a repaired x (zeros without repair).  repair=None is the call without the argument, bit for bit.
+        Chains of 1 .. 8 joints with a model."""
         from .constraint import keep_arrays, region_rows
         x0s = self._check_xs(x0s)
         T, n = x0s.shape
@@ -1912,14 +1924,22 @@ class Robot:
         count = np.zeros(T, dtype=np.int32)
         x, v, key = np.full((T, k, n), np.nan), np.full((T, k), np.nan), np.full((T, k), np.inf)
         idx = np.full((T, k), U64_MAX, dtype=np.uint64)
-        if self._L.optik_robot_ik_region(
-                self._h, T, _dp(reg), _dp(x0s), restarts, tol, iters, damping, max_step, mode,
+        repaired = np.zeros(T, dtype=np.int32)
+        head = (self._h, T, _dp(reg), _dp(x0s), restarts, tol, iters, damping, max_step, mode,
                 _dp(kp[0]) if kp else None, _dp(kp[1]) if kp else None, _dp(kp[2]) if kp else None,
-                kp[3] if kp else 0.0, k, min_dist, _dp(ee) if ee is not None else None,
-                count.ctypes.data_as(C.POINTER(C.c_int32)), _dp(x), _dp(v), idx.ctypes.data_as(C.POINTER(C.c_uint64)),
-                _dp(key)):
+                kp[3] if kp else 0.0, k, min_dist)
+        tail = (_dp(ee) if ee is not None else None, count.ctypes.data_as(C.POINTER(C.c_int32)), _dp(x), _dp(v),
+                idx.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(key))
+        if repair is None:
+            rc = self._L.optik_robot_ik_region(*head, *tail)
+        else:
+            rp = nat.region_repair_args(repair)
+            r5 = np.array([rp[0], rp[1], rp[2], rp[3], rp[4]], dtype=np.float64)
+            rc = self._L.optik_robot_ik_region_repair(*head, _dp(r5), *tail,
+                                                      repaired.ctypes.data_as(C.POINTER(C.c_int32)))
+        if rc:
             raise RuntimeError(_err(self._L))
-        return dict(count=count, x=x, violation=v, idx=idx, key=key)
+        return dict(count=count, x=x, violation=v, idx=idx, key=key, repaired=repaired)
 
     def ik_region(self, config: SolverConfig, region, x0, **kwargs):
         """The single-region form of ik_region_batch_arrays (its keyword arguments): a list of up to k
@@ -2126,6 +2146,51 @@ class Robot:
             if tol is not None:
                 res["keeps"] = self.check_paths_constraint(out, None, c, tol, resolution, ee_offset)["ok"]
         return res
+
+    # -- collision repair (extension; include/optik.h) --------------------------------------
+    def repair_configurations(self, xs, influence, safety, step=nat.REPAIR_STEP, iters=nat.REPAIR_ITERS,
+                              region=None, max_move=np.inf, tol=nat.CONSTRAINT_TOL,
+                              iters_project=nat.CONSTRAINT_ITERS, damping=nat.CONSTRAINT_DAMPING,
+                              max_step=nat.CONSTRAINT_MAX_STEP, ee_offset=None):
+        """Pushes configurations out of collision: the start state that sensor noise put a few millimetres inside a
+        table, the IK solution that ends a few centimetres inside an obstacle.  Every row of xs [B, n] on its own
+        steps by `step` down the gradient of optimize_paths' hinge (influence, safety) of its clearance witnesses,
+        clamped to the joint limits, until its clearance -- collision_clearance_batch_arrays' number -- is >= safety,
+        at most `iters` steps.  With `region` (a PoseConstraint) every step is projected back onto that pose box
+        (constraint_project_batch_arrays' method at tol, at most iters_project iterations, damping, max_step), so a
+        redundant arm slides out through its null space while the tool stays inside the box.  max_move bounds the
+        L-infinity distance of the result from the input.  A fixed step without a line search; the defaults of step
+        and iters are the values that clear the scenes of examples/ik_repair.py, and nothing more.
+        Returns a dict: x [B, n], clearance [B], violation [B] (of the region; 0 without one), moved [B], status [B]
+        int32 -- 0 free (with iterations > 0 also within the joint limits and inside the region at tol; with
+        iterations == 0 the row was free already and is returned bit for bit), 1 iters spent, 2 stuck (no gradient,
+        a projection that failed, or max_move reached: x is the last accepted iterate), 3 a NaN -- and iterations [B]
+        int32.  Revolute chains of 1 .. 8 joints with a collision model.
+        ValueError for what the kernel layer refuses of the parameters and the region."""
+        n = self.num_positions()
+        xs = np.ascontiguousarray(xs, dtype=np.float64)
+        if xs.ndim != 2 or xs.shape[1] != n:
+            raise ValueError(f"xs must be [B, n] with n = {n}, got {list(xs.shape)}")
+        B = xs.shape[0]
+        influence, safety, step, iters, max_move = nat.check_repair_args(influence, safety, step, iters, max_move)
+        box = (None, None, None)
+        keep = None
+        if region is not None:
+            keep = checked_constraint_arrays(region)
+            box = tuple(_dp(a) for a in keep)
+            tol, iters_project, damping, max_step = nat.check_project_args(tol, iters_project, damping, max_step)
+        piters = int(iters_project)
+        ee = _pose16(ee_offset) if ee_offset is not None else None
+        x, clr, viol, moved = np.zeros((B, n)), np.zeros(B), np.zeros(B), np.zeros(B)
+        status, iterations = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        if self._L.optik_robot_collision_repair_batch(
+                self._h, B, _dp(xs), influence, safety, step, iters, max_move, *box, float(tol), piters, float(damping),
+                float(max_step),
+                _dp(ee) if ee is not None else None, _dp(x), _dp(clr), _dp(viol), _dp(moved),
+                status.ctypes.data_as(ip), iterations.ctypes.data_as(ip)):
+            raise RuntimeError(_err(self._L))
+        return dict(x=x, clearance=clr, violation=viol, moved=moved, status=status, iterations=iterations)
 
     def set_motion_resolution(self, h):
         """The resolution of ik_path*'s motion check (0, the default: off).  While it is > 0 and a collision model is
